@@ -7,7 +7,11 @@ Jacobi pressure projection, three advections, fractal frame emit) + the fused CN
 (256^2 grid, batch 64, Jacobi-100).  Grids are independent: ranks own disjoint grids, no data-path collective
 ("scaling": "weak", batch 64 per GPU).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run measures the headline and nothing else: set-up, warm-up, K timed steps, the outputs of the last timed step if
+--dump-outputs is given, the JSON line.  --full adds every other leg (configs[1], the other encoder arithmetic, the encoder on
+dense frames, the HBM copy, inference ms, the dataset, configs[4], the CPU baseline, the train step, the replayed counters).
 
 N>1 runs one process per GPU over RCCL.  Either the caller starts the ranks (python -m torch.distributed.run
 --nproc-per-node N bench.py --gpus N ...: RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* come from the environment) or plain
@@ -35,6 +39,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0                       # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 MFMA_PEAK_TFLOPS = {"f32": 157.3, "bf16x3": 2500.0, "bf16": 2500.0, "i8x3": 5000.0}   # dense peaks (MI355X_MICROARCH.md)
+PREROLL_MAX = 200                           # headline steps run in place of the secondary legs without --full (main: "Leg order")
 
 
 def encoder_weights(seed=0):
@@ -557,6 +562,22 @@ def second_config(dev, rank, K, W):
                                  "peak": MFMA_PEAK_TFLOPS["f32"], "unit": "TFLOP/s", "frac": tf / MFMA_PEAK_TFLOPS["f32"]}}
 
 
+DUMP_BUDGET_BYTES = 60_000_000                # data bytes; the .npy headers stay well inside 64 MB
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write each array as path/<name>.npy in float32.  Over `budget` bytes in all, every array keeps its share of the budget as a
+    fixed sample (sorted flat indices drawn with seed 0), so that two builds given the same arguments write comparable files."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > budget:
+            keep = int(a.size * budget // total)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -578,7 +599,7 @@ def parse_args(argv=None):
     ap.add_argument("--no-config1", action="store_true", help="skip the secondary configs[1] block (128^2 x 32, Jacobi-20, fp32 encoder)")
     ap.add_argument("--train-step", dest="train_step", action="store_true", default=True,
                     help="time train.py's optimisation step (BASELINE configs[3]'s per-GPU shape: --batch frames of --grid^2, full model; "
-                         "under DistributedDataParallel when N > 1: the RCCL gradient all-reduce).  On by default at every N, so that the "
+                         "under DistributedDataParallel when N > 1: the RCCL gradient all-reduce).  On by default under --full at every N, so that the "
                          "1 -> N curve of the DDP step has its N = 1 point (adds about 20 s)")
     ap.add_argument("--no-train-step", dest="train_step", action="store_false", help="skip the train-step leg (profiling runs)")
     ap.add_argument("--force-dist", dest="force_dist", action="store_true", default=True,
@@ -587,6 +608,11 @@ def parse_args(argv=None):
     ap.add_argument("--no-force-dist", dest="force_dist", action="store_false", help="N = 1: the bare model, no process group")
     ap.add_argument("--train-step-limit", type=float, default=240.0,
                     help="seconds after which a stuck train-step leg is abandoned: rank 0 prints the headline line without it")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg beside the headline (the --no-* switches above cut them); without it the run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0: the emitted frame and the encoder's "
+                         "features) as DIR/<name>.npy, float32, at most 64 MB in all (a fixed, seeded sample beyond that)")
     ap.add_argument("--master-port", type=int, default=0, help="self-launch only: rendezvous port (0 = pick a free one)")
     ap.add_argument("--dry-run", action="store_true", help="self-launch only: print the child command as JSON and exit")
     return ap.parse_args(argv)
@@ -634,10 +660,12 @@ def main(argv=None):
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.dry_run):
         raise SystemExit(self_launch(args, argv))
 
+    full = args.full
     # the train-step leg's MIOpen convolutions (the reconstruction head): a find-db of the bench's own, so that entries another run left in
     # the account's (a deterministic run's restricted solvers: smokephysai_amd/utils/miopen_db.py) cannot slow the measured step
-    from smokephysai_amd.utils.miopen_db import use_private_find_db
-    use_private_find_db("smokephys_bench")
+    if full:
+        from smokephysai_amd.utils.miopen_db import use_private_find_db
+        use_private_find_db("smokephys_bench")
 
     # stdout carries ONE JSON line and nothing else: native libraries write there too (RCCL prints a five-line version banner when a
     # process group is created), so fd 1 is pointed at stderr for the life of the process and the line goes to a duplicate of the real stdout
@@ -701,10 +729,11 @@ def main(argv=None):
         if dist is not None:
             dist.barrier()
 
-    def timed(dtype):
-        """W warm-up steps, then exactly K timed steps between barrier + synchronize; max over ranks."""
+    def timed(dtype, preroll=0):
+        """`preroll` + W warm-up steps, then exactly K timed steps between barrier + synchronize; max over ranks.  Also returns what the
+        last timed step computed."""
         step = make_step(dtype)
-        for _ in range(W):
+        for _ in range(preroll + W):
             step()
         events = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(K)]
         barrier(); torch.cuda.synchronize()
@@ -720,27 +749,38 @@ def main(argv=None):
         assert torch.isfinite(frame).all() and (feats is None or torch.isfinite(feats).all())
         ms_sim = float(np.mean([e[0].elapsed_time(e[1]) for e in events]))      # HIP events on the launch stream
         ms_enc = float(np.mean([e[1].elapsed_time(e[2]) for e in events]))
-        return elapsed, ms_sim, ms_enc
+        return elapsed, ms_sim, ms_enc, feats
 
     # Leg order: the secondary legs (configs[1], the other encoder arithmetic) run BEFORE the headline on every rank, at every N: a fresh
     # process's first ~20 launches run 10-25 % slower while the clocks ramp (profiles/README.md), and a 20-step timed region is short
     # enough to see it.  Each leg does its own W warm-up steps and times exactly K steps; the order is printed as "leg_order".
+    # Without --full the two legs do not run; the headline step itself runs in their place, W + K steps for each (at most PREROLL_MAX in
+    # all), so that the headline is timed after as many device steps as under --full.  The count depends on the arguments alone.
+    want_config1 = not args.no_config1 and not args.no_encode
+    want_alt = not args.no_encode and not args.no_alt and args.encoder_dtype in ("i8x3", "bf16x3")
+    preroll = 0 if full else min(PREROLL_MAX, (W + K) * (int(want_config1) + int(want_alt)))
     leg_order = []
     config1 = None
-    if not args.no_config1 and not args.no_encode:
+    if full and want_config1:
         config1 = second_config(dev, rank, K, W)
         leg_order.append("config1")
     alt = None
-    if not args.no_encode and not args.no_alt and args.encoder_dtype in ("i8x3", "bf16x3"):
+    if full and want_alt:
         other = "bf16x3" if args.encoder_dtype == "i8x3" else "i8x3"
-        a_el, a_sim, a_enc = timed(other)
+        a_el, a_sim, a_enc, _ = timed(other)
         alt = {"encoder_dtype": other, "value": world * B * K / a_el, "unit": "frames/s", "ms_per_step": a_el / K * 1e3,
                "ms_encode_per_step": a_enc, "counted_TFLOPs": B * 153728.0 * N * N / (a_enc * 1e-3) / 1e12}
         leg_order.append("alt")
-    elapsed, ms_sim, ms_enc = timed(args.encoder_dtype)
+    elapsed, ms_sim, ms_enc, feats = timed(args.encoder_dtype, preroll)
     leg_order.append("headline")
+    if args.dump_outputs and rank == 0:
+        outputs = {"frame": frame.cpu().numpy()}                         # [B, N, N]: the frame the stepper emitted
+        if feats is not None:                                            # [B, 1024, 128] tokens, or [B, 128, 32, 32] for f32
+            outputs["features"] = feats.float().cpu().numpy()
+        dump_outputs(args.dump_outputs, outputs)
+    del feats
     ms_enc_dense = None
-    if not args.no_encode and rank == 0:
+    if full and not args.no_encode and rank == 0:
         # the same encoder launch on DENSE frames (U(0, 1.8), the fixtures' dense-frame distribution): the simulated frames above are
         # > 99 % background and matrix-core power (hence clock) depends on the operand data
         dense = torch.rand(B, N, N, device=dev, generator=torch.Generator(device=dev).manual_seed(7)) * 1.8
@@ -755,7 +795,7 @@ def main(argv=None):
         torch.cuda.synchronize()
         ms_enc_dense = e0.elapsed_time(e1) / K
     config4_sharded = None
-    if world > 1 and 8 % world == 0 and not args.no_config4 and not args.no_encode:
+    if full and world > 1 and 8 % world == 0 and not args.no_config4 and not args.no_encode:
         config4_sharded = config4_leg(dev, rank=rank, world=world, dist=dist, backend=backend)      # every rank: 8 / N volumes each
         leg_order.append("config4")
 
@@ -814,8 +854,9 @@ def main(argv=None):
             out["roofline"] = roof_stencil
         if alt is not None:
             out["alt"] = alt
-        attach_counters(out, args.encoder_dtype)
-        if world == 1:
+        if full:
+            attach_counters(out, args.encoder_dtype)
+        if full and world == 1:
             out["hbm_copy_measured_GBs"] = hbm_copy_gbs(dev)
         # secondary legs: a failure in one is reported in its block (and in the exit code); the headline line is still printed
         def secondary(name, fn):
@@ -825,28 +866,29 @@ def main(argv=None):
             except Exception as e:        # noqa: BLE001
                 out[name] = {"error": f"{type(e).__name__}: {e}"[:400]}
                 return 4
-        if world == 1 and not args.no_encode and not args.no_inference:
+        if full and world == 1 and not args.no_encode and not args.no_inference:
             secondary_rc |= secondary("inference_ms_per_frame", lambda: inference_ms(dev, N, frame, args.encoder_dtype))
         if config1 is not None:
             out["config1"] = config1
-        if world == 1 and not args.no_dataset:
+        if full and world == 1 and not args.no_dataset:
             secondary_rc |= secondary("dataset", lambda: dataset_leg(dev))
-        if world == 1 and not args.no_config4:
+        if full and world == 1 and not args.no_config4:
             secondary_rc |= secondary("config4", lambda: config4_leg(dev))
         elif config4_sharded is not None:
             out["config4"] = config4_sharded
             secondary_rc |= 4 if "error" in config4_sharded else 0
-        if world == 1 and args.cpu_frames > 0:
+        if full and world == 1 and args.cpu_frames > 0:
             secondary_rc |= secondary("cpu_baseline", lambda: cpu_baseline(N, J, weights, args.cpu_frames))
         # what the device had run when the headline's timed region began: the W warm-up steps of the headline leg itself plus the full
-        # secondary legs in front of it (a fresh process's first launches run slower while the clocks ramp; README "leg order")
+        # secondary legs in front of it, or the headline steps run in their place (a fresh process's first launches run slower while the
+        # clocks ramp; README "leg order")
         out["effective_warmup_steps"] = {"headline_leg": W, "config1_leg_before": (W + K) if config1 is not None else 0,
-                                         "alt_leg_before": (W + K) if alt is not None else 0,
-                                         "total_steps_before_timed_region": W + ((W + K) if config1 is not None else 0) + ((W + K) if alt is not None else 0)}
-        out["leg_order"] = leg_order + [k for k in ("inference_ms_per_frame", "dataset", "config4", "cpu_baseline") if k in out and k not in leg_order] + (["train_step"] if args.train_step else [])
+                                         "alt_leg_before": (W + K) if alt is not None else 0, "headline_preroll": preroll,
+                                         "total_steps_before_timed_region": W + preroll + ((W + K) if config1 is not None else 0) + ((W + K) if alt is not None else 0)}
+        out["leg_order"] = leg_order + [k for k in ("inference_ms_per_frame", "dataset", "config4", "cpu_baseline") if k in out and k not in leg_order] + (["train_step"] if full and args.train_step else [])
 
     exit_code = secondary_rc if rank == 0 else 0
-    if args.train_step:
+    if full and args.train_step:
         # A collective that never completes on one rank would hang every rank: a watchdog on each rank abandons the leg at the same
         # deadline.  Rank 0 still prints the headline line it holds (with the partial train_step block), and then EVERY rank exits
         # non-zero: each has touched the GPU, and an abandoned leg must not look like a clean run to torchrun or the driver.  One lock

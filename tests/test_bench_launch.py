@@ -65,7 +65,7 @@ def test_world_size_mismatch_is_refused():
 def test_self_launched_two_ranks_gloo_rehearsal():
     """`python bench.py --gpus 2` with no torchrun environment, on ONE card (gloo, both ranks on cuda:0): the parent spawns the
     ranks, rank 0 prints one JSON line with n_gpus 2 and the DDP train-step block (2 ranks exchanged gradients)."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--grid", "128", "--batch", "4",
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--grid", "128", "--batch", "4",
                         "--jacobi", "20", "--train-step-limit", "240"], capture_output=True, text=True, env=_clean_env(SMK_BENCH_BACKEND="gloo"),
                        timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
