@@ -1010,7 +1010,9 @@ int64_t smk_linear_ln_max_rows(smk_linear *lin) {
     if (guard.rc) return 0;
     // (round 3: one tile per workgroup, i.e. 2 CUs / column tiles x 32 rows.)  The statistics now follow the chunk stream across the tiles a
     // workgroup walks, so the only bound is the 32-bit offset range of the activation buffer
-    return ((1LL << 30) / lin->l.K) - 256;
+    // the largest rows with (rows + 256) * K < 2^30 (smk_linear_forward_ln_split's check, strict); none for K > 2^22
+    const int64_t r = ((1LL << 30) - 1) / lin->l.K - 256;
+    return r > 0 ? r : 0;
 }
 
 int smk_linear_forward_ln(smk_linear *lin, const float *x, int64_t rows, int64_t ldx, float *y, int64_t ldy, const float *wsum, double eps,

@@ -33,7 +33,17 @@ constexpr int LN_PITCH = 144;      // bytes per staged row per plane: 64 bf16 + 
 #endif
 constexpr int LN_RING = 4;         // B fragments in flight: 3 k-steps ahead; 4 k-steps per chunk keep the ring indices static
 template <int MB> constexpr int ln_plane_bytes() { return MB * 32 * LN_PITCH; }
-template <int MB, int NW> constexpr int ln_lds_bytes() { return 2 * 2 * ln_plane_bytes<MB>() + 2048; }   // + bias tile (+ fused-LayerNorm column sums, row statistics); MB = 4: 75,264 B -> 2 workgroups per CU
+// LDS of one k_linear_x3 wave group, in bytes from its base: two chunk buffers of (hi | lo) planes, the bias tile (TN = 32 NW floats), then
+// (LNF) the column sums of W' (TN floats) and (mean - pivot, rstd) per tile row (TM = 32 MB rows).  The kernel's pointers and launch_mb's
+// request both come from here.  MB = 4: 74,240 B (NW = 4) .. 76,800 B (NW = 8, LNF) -> 2 workgroups per CU fit the 160 KiB either way.
+template <int MB, int NW, bool LNF> struct x3_lds {
+    static constexpr int bias = 2 * 2 * ln_plane_bytes<MB>();
+    static constexpr int wsum = bias + 4 * NW * 32;
+    static constexpr int stat = wsum + (LNF ? 4 * NW * 32 : 0);
+    static constexpr int bytes = stat + (LNF ? 8 * MB * 32 : 0);
+};
+// the dynamic LDS launch_mb requests: KS wave groups, then the merge area of groups 1 .. KS-1 (MB accumulators of 16 floats per thread)
+template <int MB, int NW, int KS, bool LNF> constexpr int x3_lds_request() { return KS * x3_lds<MB, NW, LNF>::bytes + (KS - 1) * NW * 64 * MB * 16 * 4; }
 
 // transposed: `w` is [K][N] row-major (the handle then computes x W for a layer whose weight is W [K][N]: its input-gradient GEMM).
 // ld: source row pitch in floats; k_valid: k >= k_valid reads as zero (the weight-gradient form pads the token rows to whole segments).
@@ -167,7 +177,8 @@ __global__ __launch_bounds__(NW * 64 * KS, KS > 2 ? 1 : 2) void k_linear_x3(cons
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
     constexpr int TM = MB * 32, PLANE = ln_plane_bytes<MB>();
     const int grp = KS == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)threadIdx.x / (NW * 64));
-    unsigned char *smem = smem_all + grp * ln_lds_bytes<MB, NW>();
+    using lay = x3_lds<MB, NW, LNF>;
+    unsigned char *smem = smem_all + grp * lay::bytes;
     const int tid = KS == 1 ? (int)threadIdx.x : (int)threadIdx.x % (NW * 64), lane = tid & 63, r = lane & 31, hi = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int K = a.l.K, N = a.l.N, M = a.c.M;
@@ -319,9 +330,14 @@ __global__ __launch_bounds__(NW * 64 * KS, KS > 2 ? 1 : 2) void k_linear_x3(cons
     int buf = 0;
     load_a(0, 0, ahA, alA);
     const bool nw_ok = tn * TN + wave * 32 < N;
-    float *bias_s = reinterpret_cast<float *>(smem + 4 * PLANE);       // this workgroup's 128 bias values
+    // the last wave group's bias tile and (LNF) its tile rows' statistics end inside the bytes the launch requests (a test cannot see an
+    // overrun: the allocation granule hides it)
+    static_assert(lay::bias == 4 * PLANE && lay::bias + 4 * TN <= lay::wsum, "LDS layout: chunk buffers, then the bias tile");
+    static_assert((KS - 1) * lay::bytes + (LNF ? lay::stat + 2 * TM * 4 : lay::wsum) <= x3_lds_request<MB, NW, KS, LNF>(),
+                  "LDS layout: stat_s[2 * TM] past the requested bytes");
+    float *bias_s = reinterpret_cast<float *>(smem + lay::bias);        // this workgroup's TN bias values
     if (tid < TN) bias_s[tid] = (a.l.bias && tn * TN + tid < N) ? a.l.bias[tn * TN + tid] : 0.f;   // visible after the first barrier below             // N % 32 == 0: a wave's 32 columns are all inside or all outside
-    float *wsum_s = bias_s + TN, *stat_s = wsum_s + TN;                  // LNF: column sums of W', then (mean, rstd) per tile row
+    float *wsum_s = reinterpret_cast<float *>(smem + lay::wsum), *stat_s = reinterpret_cast<float *>(smem + lay::stat);   // LNF: column sums of W', then (mean, rstd) per tile row
     if (LNF && tid < TN) wsum_s[tid] = tn * TN + tid < N ? a.c.ln_wsum[tn * TN + tid] : 0.f;
 
 #ifdef SMK_LN_STAMPS
@@ -435,7 +451,7 @@ __global__ __launch_bounds__(NW * 64 * KS, KS > 2 ? 1 : 2) void k_linear_x3(cons
         LN_STAMP(t_k1);
 #endif
         if (KS > 1) {   // merge the wave groups' partial sums: groups 1.. park theirs in LDS, group 0 adds them in group order
-            float *xch = reinterpret_cast<float *>(smem_all + KS * ln_lds_bytes<MB, NW>());
+            float *xch = reinterpret_cast<float *>(smem_all + KS * lay::bytes);
             if (grp > 0) {
                 float *dstp = xch + ((size_t)(grp - 1) * (NW * 64) + tid) * (MB * 16);
 #pragma unroll
@@ -599,7 +615,7 @@ __global__ __launch_bounds__(NW * 64 * KS, KS > 2 ? 1 : 2) void k_linear_x3(cons
 
 template <int MB, int NW, bool AS, int KS = 1, int RING = LN_RING, bool LNF = false>
 static hipError_t launch_mb(const LinearArgs &a, hipStream_t st) {
-    constexpr int lds = KS * ln_lds_bytes<MB, NW>() + (KS - 1) * NW * 64 * MB * 16 * 4;
+    constexpr int lds = x3_lds_request<MB, NW, KS, LNF>();
     once_per_device((const void *)k_linear_x3<MB, NW, AS, KS, RING, LNF>, [&] {
         (void)hipFuncSetAttribute((const void *)k_linear_x3<MB, NW, AS, KS, RING, LNF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     });
@@ -653,6 +669,14 @@ static hipError_t launch_mb(const LinearArgs &a, hipStream_t st) {
 //   compile-time indices; needs an even number of 64-k chunks).
 // LNF: LayerNorm fused in front, as in k_linear_x3 (pivot-shifted rows, statistics gathered while the rows are staged and carried across the
 // tiles of the chunk stream, rstd ((x - p) W'^T - (mean - p) wsum) + b' in the epilogue); plain layers only (CONV = 0).
+// LDS of k_linear_b16, in bytes: two chunk buffers of (hi | lo) [128][64] bf16 planes, the bias tile (256 floats: room for NW = 8), then (LNF) the
+// column sums of W' (256 floats) and (mean - pivot, rstd) of the 128 tile rows.  The kernel's pointers and launch_b16's request both come from here.
+template <bool LNF> struct b16_lds {
+    static constexpr int bias = 4 * 128 * 128;
+    static constexpr int wsum = bias + 4 * 256;
+    static constexpr int stat = wsum + 4 * 256;
+    static constexpr int bytes = LNF ? stat + 8 * 128 : wsum;
+};
 template <int NW, int CONV = 0, int R = 2, bool LNF = false>
 __global__ __launch_bounds__(NW * 64, 2) void k_linear_b16(const LinearArgs a) {
     static_assert(!LNF || CONV == 0, "fused LayerNorm: plain layers");
@@ -789,9 +813,12 @@ __global__ __launch_bounds__(NW * 64, 2) void k_linear_b16(const LinearArgs a) {
         stage_load(ld_tm, ld_c, j);
     }
     advance();
-    float *bias_s = reinterpret_cast<float *>(smem + 4 * PLANE);
+    using lay = b16_lds<LNF>;
+    static_assert(lay::bias == 4 * PLANE && lay::bias + 4 * TN <= lay::wsum, "LDS layout: chunk buffers, then the bias tile");
+    static_assert(!LNF || lay::stat + 2 * TM * 4 <= lay::bytes, "LDS layout: stat_s[2 * TM] past the requested bytes");
+    float *bias_s = reinterpret_cast<float *>(smem + lay::bias);
     if (tid < TN) bias_s[tid] = (a.l.bias && tn * TN + tid < N) ? a.l.bias[tn * TN + tid] : 0.f;
-    float *wsum_s = bias_s + 256, *stat_s = wsum_s + 256;    // LNF: column sums of W', then (mean - pivot, rstd) per tile row
+    float *wsum_s = reinterpret_cast<float *>(smem + lay::wsum), *stat_s = reinterpret_cast<float *>(smem + lay::stat);   // LNF: column sums of W', then (mean - pivot, rstd) per tile row
     if (LNF && tid < TN) wsum_s[tid] = tn * TN + tid < N ? a.c.ln_wsum[tn * TN + tid] : 0.f;
     __syncthreads();
 
@@ -1012,7 +1039,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_linear_b16(const LinearArgs a) {
 
 template <int NW, int CONV = 0, int R = 2, bool LNF = false>
 static hipError_t launch_b16(const LinearArgs &a, hipStream_t st) {
-    constexpr int lds = 4 * 128 * 128 + 1024 + (LNF ? 2048 : 0);          // + bias tile (+ LNF: wsum tile, row statistics)
+    constexpr int lds = b16_lds<LNF>::bytes;                               // + bias tile (+ LNF: wsum tile, row statistics)
     once_per_device((const void *)k_linear_b16<NW, CONV, R, LNF>, [&] {
         (void)hipFuncSetAttribute((const void *)k_linear_b16<NW, CONV, R, LNF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     });

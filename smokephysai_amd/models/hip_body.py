@@ -132,14 +132,14 @@ class HipBody:
         # Measured neutral on MI355X (the K loop is not bound by the split arithmetic: DESIGN.md 3.3), so it is off by default.
         sp = self.split_activations and D % 8 == 0 and layer.ffn[0].out_features % 8 == 0
         # each LayerNorm runs inside the layer that follows it (HipLinearLN: statistics gathered while the kernel stages the raw rows) -- 12
-        # launches and their round trips less per forward, at every batch size.  The gate is the HANDLE's own limit (max_rows)
+        # launches and their round trips less per forward, at every batch size.  The gate is the HANDLE's own limit at x's row pitch (accepts)
         fuse_ln = (self.fuse_layernorm and not sp and all(ln.elementwise_affine and ln.bias is not None for ln in (layer.norm1, layer.norm2)))
         add15 = self._addend_buffer(name, B, D, x.device)
         if not addend_ready:
             att.chaos_addend_hip(B, x.device, noise, out=add15)
         qkv_ln = self.linear_ln(name + "chaos_attention.qkv", (att.q_proj, att.k_proj, att.v_proj), layer.norm1) if fuse_ln else None
         kvs = False
-        if qkv_ln is not None and B * L <= qkv_ln.max_rows:
+        if qkv_ln is not None and qkv_ln.accepts(x):
             kvs = self.kv_presplit and hip_attention_supported(L, d) and D % 32 == 0
             qkv = qkv_ln.forward_ln(x, periodic_add=add15, rows_per_group=L, split_from=D if kvs else None)
         else:
@@ -156,7 +156,7 @@ class HipBody:
             o = to_split(o) if sp else o
         self.linear(name + "chaos_attention.out_proj", att.out_proj)(o, residual=x, out=x, x_split=sp)     # x += attn
         ffn_ln = self.linear_ln(name + "ffn.0", (layer.ffn[0],), layer.norm2) if fuse_ln else None
-        if ffn_ln is not None and B * L <= ffn_ln.max_rows:
+        if ffn_ln is not None and ffn_ln.accepts(x):
             f = ffn_ln.forward_ln(x, activation="gelu")
         else:
             h = self.layernorm(x, layer.norm2, out_split=sp)

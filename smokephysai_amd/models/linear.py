@@ -130,7 +130,7 @@ class HipLinear:
         act = {None: _lib.SMK_ACT_NONE, "none": _lib.SMK_ACT_NONE, "gelu": _lib.SMK_ACT_GELU, "relu": _lib.SMK_ACT_RELU}[activation]
         # one launch addresses x with 32-bit offsets: larger inputs go in row chunks (whole groups when a periodic addend is set)
         unit = rpg if pa_ptr else 128
-        max_rows = max(unit, ((MAX_X_ELEMS // max(ldx, 1) - 256) // unit) * unit)
+        max_rows = max(unit, (((MAX_X_ELEMS - 1) // max(ldx, 1) - 256) // unit) * unit)
         x_row_bytes = (2 * self.in_features * 2) if x_split else ldx * 4
         y_row_bytes = (2 * self.out_features * 2) if out_split else ldy * 4
         r0 = 0
@@ -148,7 +148,8 @@ class HipLinear:
 class HipLinearLN(HipLinear):
     """LayerNorm + Linear as ONE launch (smk_linear_forward_ln): the handle holds the folded parameters W' = W diag(gamma),
     b' = b + W beta; the kernel normalises inside (row statistics gathered while it stages the raw rows, the mean / rstd correction in
-    its epilogue).  `max_rows`: the largest row count the handle serves (the library's own answer, smk_linear_ln_max_rows)."""
+    its epilogue).  `max_rows`: the largest row count the handle serves for dense rows (the library's own answer, smk_linear_ln_max_rows);
+    rows_limit(ldx) / accepts(x): the same bound at a row pitch ldx > in_features."""
 
     def __init__(self, weight: torch.Tensor, bias: Optional[torch.Tensor], ln_weight: torch.Tensor, ln_bias: torch.Tensor, eps: float,
                  device=None):
@@ -161,6 +162,21 @@ class HipLinearLN(HipLinear):
         self.wsum = wf.sum(dim=1).float().to(self._dev).contiguous()
         self.max_rows = int(self._L.smk_linear_ln_max_rows(self._handle))
 
+    def rows_limit(self, ldx: int) -> int:
+        """The largest row count forward_ln serves at row pitch ldx (floats): (rows + 256) * ldx < 2^30, and never above max_rows."""
+        return min(self.max_rows, max(0, (MAX_X_ELEMS - 1) // ldx - 256))
+
+    def _rows2d(self, x: torch.Tensor) -> torch.Tensor:
+        x2 = x.reshape(-1, self.in_features)
+        if x2.stride(1) != 1 or x2.stride(0) % 4 != 0 or x2.data_ptr() % 16 != 0:
+            x2 = x2.contiguous()
+        return x2
+
+    def accepts(self, x: torch.Tensor) -> bool:
+        """Whether forward_ln serves x as it is laid out (its row count against the bound at its own row pitch)."""
+        x2 = self._rows2d(x)
+        return x2.shape[0] <= self.rows_limit(x2.stride(0))
+
     def forward_ln(self, x: torch.Tensor, activation: Optional[str] = None, periodic_add: Optional[torch.Tensor] = None,
                    rows_per_group: int = 0, out: Optional[torch.Tensor] = None, split_from: Optional[int] = None) -> torch.Tensor:
         """x [..., in_features] RAW (not normalised) -> act(LayerNorm(x) W^T + b + periodic_add).
@@ -168,12 +184,11 @@ class HipLinearLN(HipLinear):
         {hi[0..3], lo[0..3]} (bf16) instead of 4 floats -- for hip_attention(kv_split=True); unsplit4_inplace() decodes them."""
         if x.device != self._dev or x.dtype != torch.float32 or x.shape[-1] != self.in_features:
             raise ValueError(f"HipLinearLN: x must be float32 [..., {self.in_features}] on {self._dev}")
-        x2 = x.reshape(-1, self.in_features)
-        if x2.stride(1) != 1 or x2.stride(0) % 4 != 0 or x2.data_ptr() % 16 != 0:
-            x2 = x2.contiguous()
+        x2 = self._rows2d(x)
         rows = x2.shape[0]
-        if rows > self.max_rows:
-            raise ValueError(f"HipLinearLN: {rows} rows > max_rows {self.max_rows} (use the LayerNorm kernel + HipLinear)")
+        if rows > self.rows_limit(x2.stride(0)):
+            raise ValueError(f"HipLinearLN: {rows} rows > {self.rows_limit(x2.stride(0))} at row pitch {x2.stride(0)} (max_rows {self.max_rows}; "
+                             "use the LayerNorm kernel + HipLinear)")
         y = out if out is not None else torch.empty(*x.shape[:-1], self.out_features, device=self._dev, dtype=torch.float32)
         y2 = y.view(-1, self.out_features)
         pa_ptr, period, rpg = 0, 1, 1
