@@ -219,6 +219,17 @@ int smk_chaos_stats(const float *frames, int64_t frame_stride, int32_t n, int32_
 int smk_frame_diff_norms(const float *frames, int64_t frame_stride, int32_t n, int32_t H, int32_t W, float *norms,
                          void *stream);
 
+/* RobustnessEvaluator.compute_ssim's SSIM map and F.mse_loss's squared error (robustness_metrics.py:76-103) for n fp32 planes [H][W]
+ * (dense rows; plane strides pred_stride / target_stride floats), summed per plane in fp64 in a fixed order (bit-reproducible):
+ * ssim_sum [n], sqerr_sum [n].  avg_pool2d(window, stride 1, padding window/2, count_include_pad) with zeros outside the plane;
+ * sigma^2 = E[x^2] - mu^2 and sigma_xy = E[xy] - mu_x mu_y in fp32 as the reference computes them; c1, c2 are the stabilisers
+ * (0.01^2, 0.03^2 there).  Odd window 1..31, any H, W >= 1, n <= 65535.  workspace: device memory of at least
+ * smk_image_quality_workspace(n, H, W) bytes, passed with its size. */
+int64_t smk_image_quality_workspace(int32_t n, int32_t H, int32_t W);
+int smk_image_quality(const float *pred, int64_t pred_stride, const float *target, int64_t target_stride, int32_t n, int32_t H,
+                      int32_t W, int32_t window, double c1, double c2, void *workspace, int64_t workspace_bytes, double *ssim_sum,
+                      double *sqerr_sum, void *stream);
+
 /* ------------------------------------------------------------------ CNN encoder */
 /* SMK_F32: fp32 MFMA; SMK_BF16X3: split-bf16 MFMA (fp32-class accuracy); SMK_BF16: single-pass bf16;
  * SMK_I8X3: 16-bit fixed point as two int8 limbs on int8 MFMA (per-tile activation scale, exact i32 accumulation). */

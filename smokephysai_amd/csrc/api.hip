@@ -14,6 +14,7 @@
 #include "encoder.h"
 #include "linear.h"
 #include "norm.h"
+#include "quality.h"
 #include "stencil.h"
 #include "stencil3d.h"
 #include "transformer.h"
@@ -783,6 +784,26 @@ int smk_frame_diff_norms(const float *frames, int64_t frame_stride, int32_t n, i
                          void *stream) {
     SMK_REQUIRE(frames && norms && n >= 2 && H >= 1 && W >= 1 && frame_stride >= (int64_t)H * W, "bad arguments");
     return check_launch(launch_diff_norms(frames, frame_stride, n - 1, H * W, norms, (hipStream_t)stream), "diff_norms");
+}
+
+// ------------------------------------------------------------------ image quality (SSIM map + squared error)
+int64_t smk_image_quality_workspace(int32_t n, int32_t H, int32_t W) {
+    if (n < 1 || H < 1 || W < 1) return 0;
+    return (int64_t)n * quality_tiles(H, W) * 2 * (int64_t)sizeof(double);
+}
+
+int smk_image_quality(const float *pred, int64_t pred_stride, const float *target, int64_t target_stride, int32_t n, int32_t H,
+                      int32_t W, int32_t window, double c1, double c2, void *workspace, int64_t workspace_bytes, double *ssim_sum,
+                      double *sqerr_sum, void *stream) {
+    SMK_REQUIRE(pred && target && workspace && ssim_sum && sqerr_sum, "null pointer");
+    SMK_REQUIRE(n >= 1 && n <= 65535 && H >= 1 && W >= 1, "1 <= n <= 65535, H, W >= 1");
+    SMK_REQUIRE(pred_stride >= (int64_t)H * W && target_stride >= (int64_t)H * W, "plane strides >= H*W");
+    SMK_REQUIRE(window >= 1 && window <= QUALITY_MAX_WINDOW && window % 2 == 1, "window: odd, 1..31");
+    SMK_REQUIRE(quality_tiles(H, W) <= INT32_MAX, "plane too large");
+    SMK_REQUIRE(workspace_bytes >= smk_image_quality_workspace(n, H, W), "workspace smaller than smk_image_quality_workspace(n, H, W)");
+    return check_launch(launch_image_quality(pred, pred_stride, target, target_stride, n, H, W, window, (float)c1, (float)c2, workspace,
+                                             ssim_sum, sqerr_sum, (hipStream_t)stream),
+                        "image_quality");
 }
 
 // ------------------------------------------------------------------ encoder

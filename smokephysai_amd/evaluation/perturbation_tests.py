@@ -1,0 +1,156 @@
+"""Perturbation tests -- drop-in for src/evaluation/perturbation_tests.py (PerturbationTester).
+
+Same methods, arguments, defaults and result keys; the work underneath is batched:
+  physics_perturbation_test: every scenario is drawn first (the same np.random calls in the same order as the reference's loop;
+      simulation draws nothing), then all scenarios run as the grids of ONE batched SmokeSimulator (bit-identical frames to the
+      serial loop) and the num_tests x 20 frames go through the model in chunks of `batch_size`.  The caller's simulator is left
+      as the reference's loop leaves it: last scenario's final state, history holding the frames the loop would have appended.
+  gaussian_noise_test: every noise tensor is drawn first -- randn_like(test_data) * level, in level order -- then the baseline
+      and all noisy copies run as one chunked forward.  The reference interleaves its draws with its forwards (the model's chaos
+      term draws from the same torch generator), so a seeded run matches the reference's numbers in distribution, not exactly.
+  adversarial_test: the reference's PGD loop, with the gradient taken by torch.autograd.grad with respect to the perturbation
+      only, the parameters' requires_grad switched off for the attack (and restored): no weight-gradient GEMMs run and no .grad
+      is left on the model's parameters (the reference's loss.backward() accumulates them there).
+"""
+import warnings
+from typing import Dict, List
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from ..physics import SmokeSimulator
+
+
+def draw_scenarios(num_tests: int, h: int, w: int) -> List[List[tuple]]:
+    """The smoke sources of physics_perturbation_test's scenarios, drawn from the global np.random exactly as the reference's loop
+    draws them (perturbation_tests.py:113-118): per test randint(1, 4) sources, each x = randint(20, w-20),
+    y = randint(20, h-20), intensity = uniform(0.5, 2.0).  Returns one list of (x, y, intensity) per test."""
+    scenarios = []
+    for _ in range(num_tests):
+        sources = []
+        for _ in range(np.random.randint(1, 4)):
+            x = np.random.randint(20, w - 20)
+            y = np.random.randint(20, h - 20)
+            intensity = np.random.uniform(0.5, 2.0)
+            sources.append((x, y, intensity))
+        scenarios.append(sources)
+    return scenarios
+
+
+def _chunked_forward(model: nn.Module, frames: torch.Tensor, batch_size: int, keys) -> Dict[str, torch.Tensor]:
+    """model(frames[i:i+batch_size]) over frames [N, 1, H, W] (no_grad); the outputs named in `keys`, concatenated."""
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+    outs = {k: [] for k in keys}
+    with torch.no_grad():
+        for s in range(0, frames.shape[0], batch_size):
+            pred = model(frames[s:s + batch_size])
+            for k in keys:
+                outs[k].append(pred[k])
+    return {k: torch.cat(v) for k, v in outs.items()}
+
+
+class PerturbationTester:
+    """Perturbation tester (perturbation_tests.py:8-146)."""
+
+    def __init__(self, device: str = 'cuda'):
+        self.device = device
+
+    def gaussian_noise_test(self, model: nn.Module, test_data: torch.Tensor,
+                            noise_levels: List[float] = [0.01, 0.05, 0.1, 0.2], *, batch_size: int = 64) -> Dict:
+        """{'gaussian_<level>': {'feature_stability', 'reconstruction_mse'}} (perturbation_tests.py:14-52).  All noise is drawn
+        before any forward, randn_like(test_data) * level in level order; see the module docstring."""
+        model.eval()
+        noisy = [torch.clamp(test_data + torch.randn_like(test_data) * level, 0, 1) for level in noise_levels]
+        B = test_data.shape[0]
+        out = _chunked_forward(model, torch.cat([test_data] + noisy), batch_size, ('latent_features', 'reconstructed'))
+        base_feat, base_rec = out['latent_features'][:B], out['reconstructed'][:B]
+        results = {}
+        for i, level in enumerate(noise_levels):
+            feat = out['latent_features'][(i + 1) * B:(i + 2) * B]
+            rec = out['reconstructed'][(i + 1) * B:(i + 2) * B]
+            results[f'gaussian_{level}'] = {
+                'feature_stability': F.cosine_similarity(base_feat, feat, dim=1).mean().item(),
+                'reconstruction_mse': F.mse_loss(rec, base_rec).item(),
+            }
+        return results
+
+    def adversarial_test(self, model: nn.Module, test_data: torch.Tensor, epsilon: float = 0.1, num_steps: int = 10) -> Dict:
+        """PGD on the reconstruction error (perturbation_tests.py:54-98): {'adversarial_feature_stability',
+        'adversarial_perturbation_norm'}.  The gradient is taken with respect to the perturbation only (module docstring)."""
+        model.eval()
+        delta = torch.zeros_like(test_data, requires_grad=True)
+        params = [p for p in model.parameters() if p.requires_grad]
+        warned = model.__dict__.get("_warned_grad")
+        try:
+            for p in params:                 # no weight-gradient work at all, and nothing accumulates in the parameters' .grad
+                p.requires_grad_(False)
+            with warnings.catch_warnings():
+                # the differentiable eval route is what this attack needs: SmokePhysNet's one-time hint about it does not apply here
+                warnings.filterwarnings("ignore", message="SmokePhysNet: eval forward with autograd")
+                for _ in range(num_steps):
+                    with torch.enable_grad():
+                        output = model(torch.clamp(test_data + delta, 0, 1))
+                        loss = -F.mse_loss(output['reconstructed'], test_data)      # maximise the reconstruction error
+                        (grad,) = torch.autograd.grad(loss, delta)
+                    with torch.no_grad():
+                        delta += epsilon / num_steps * torch.sign(grad)
+                        delta.clamp_(-epsilon, epsilon)
+        finally:
+            for p in params:
+                p.requires_grad_(True)
+            if warned is None:
+                model.__dict__.pop("_warned_grad", None)        # a later, unintended autograd forward still gets its hint
+        with torch.no_grad():
+            baseline = model(test_data)
+            adversarial_output = model(torch.clamp(test_data + delta, 0, 1))
+            feature_stability = F.cosine_similarity(baseline['latent_features'], adversarial_output['latent_features'],
+                                                    dim=1).mean().item()
+        return {'adversarial_feature_stability': feature_stability,
+                'adversarial_perturbation_norm': torch.norm(delta.detach()).item()}
+
+    def physics_perturbation_test(self, model: nn.Module, simulator, num_tests: int = 50, *, batch_size: int = 64) -> Dict:
+        """{'physics_prediction_stability', 'num_tests'} (perturbation_tests.py:100-146): 1 / (1 + mean over scenarios of the
+        unbiased variance over 20 frames of physics_features, averaged over the 3 outputs).  `simulator` is an un-batched
+        SmokeSimulator; its grid size, dt, viscosity and Jacobi sweeps define the scenarios."""
+        if simulator.batch_size is not None:
+            raise ValueError("physics_perturbation_test: pass an un-batched SmokeSimulator (batch_size=None); "
+                             "the scenarios are batched internally")
+        if num_tests < 1:
+            raise ValueError(f"physics_perturbation_test: num_tests must be >= 1, got {num_tests}")
+        ns = simulator.ns_solver
+        scenarios = draw_scenarios(num_tests, ns.h, ns.w)
+        _, features = self.perturbation_rollout(model, simulator, scenarios, batch_size=batch_size)
+        variances = features.var(dim=1).mean(dim=1).tolist()         # per scenario: torch.var over the 20 frames, mean of 3
+        return {'physics_prediction_stability': 1.0 / (1.0 + np.mean(variances)), 'num_tests': num_tests}
+
+    def perturbation_rollout(self, model: nn.Module, simulator, scenarios, *, batch_size: int = 64):
+        """The simulation and model half of physics_perturbation_test for given scenarios (lists of (x, y, intensity), as
+        draw_scenarios returns): returns frames [num_tests, 20, H, W] (the fractal-perturbed densities simulate_step would emit)
+        and physics_features [num_tests, 20, 3].  Leaves `simulator` as the reference's loop would: u, v, p, density equal
+        to the last scenario's final state, history extended by the frames in scenario order (trimmed to max_history)."""
+        if simulator.batch_size is not None:
+            raise ValueError("perturbation_rollout: pass an un-batched SmokeSimulator (batch_size=None)")
+        model.eval()
+        ns = simulator.ns_solver
+        T, steps = len(scenarios), 20
+        sim = SmokeSimulator(ns.grid_size, dt=ns.dt, viscosity=ns.viscosity, device=ns.device, batch_size=T,
+                             jacobi_iters=ns.jacobi_iters)
+        for g, sources in enumerate(scenarios):
+            for x, y, intensity in sources:                          # one source at a time, in draw order, as the reference adds them
+                sim.add_incense_source([(x, y)], [intensity], grid=g)
+        frames = sim.simulate_sequence(steps, add_fractal=True)      # [T, 20, H, W]
+        H, W = frames.shape[2:]
+        features = _chunked_forward(model, frames.view(T * steps, 1, H, W), batch_size, ('physics_features',))['physics_features']
+        # the caller's simulator: the state and history the serial loop would have left
+        last = sim.ns_solver
+        ns.u, ns.v, ns.p, ns.density = last.u[-1], last.v[-1], last.p[-1], last.density[-1]
+        ns.boundary.zero_()                                          # (setup_grid's other effect)
+        keep = min(simulator.max_history, T * steps)
+        simulator.history.extend(f.clone() for f in frames.view(T * steps, H, W)[T * steps - keep:])
+        del simulator.history[:max(0, len(simulator.history) - simulator.max_history)]
+        ns.check()
+        sim.ns_solver.close()
+        return frames, features.view(T, steps, -1)
