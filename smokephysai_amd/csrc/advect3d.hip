@@ -613,19 +613,12 @@ hipError_t launch3_diffuse_div_march(const Geom3 &g, State3 in, State3 out, floa
     return hipGetLastError();
 }
 
-template <int R, int NW, int MINW, int BU, bool GRAD>
-static hipError_t launch3_advect_march_t(const Geom3 &g, State3 in, const float *p, State3 out, float *frames, int64_t fsb, hipStream_t st) {
-    const long long nb = (long long)cdiv(g.W, 64) * cdiv(g.H, R * NW) * g.B;
-    if (nb > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((k3_advect_march<R, NW, MINW, BU, GRAD>), dim3((unsigned)nb), dim3(NW * 64), 0, st, g, in, p, out, frames, fsb);
-    return hipGetLastError();
-}
-
 hipError_t launch3_advect_march(const Geom3 &g, State3 in, const float *p, State3 out, float *frames, int64_t fsb, hipStream_t st) {
-    static const int shape = [] { const char *e = getenv("SMK_ADVECT3_ROWS"); return e ? atoi(e) : 4; }();      // rows per wave (diagnostic: 2, 3; default 4)
-    if (shape == 4) return p ? launch3_advect_march_t<4, 4, 2, 3, true>(g, in, p, out, frames, fsb, st) : launch3_advect_march_t<4, 4, 2, 3, false>(g, in, nullptr, out, frames, fsb, st);
-    if (shape == 2) return p ? launch3_advect_march_t<2, 4, 4, 2, true>(g, in, p, out, frames, fsb, st) : launch3_advect_march_t<2, 4, 4, 2, false>(g, in, nullptr, out, frames, fsb, st);
-    return p ? launch3_advect_march_t<3, 4, 3, 2, true>(g, in, p, out, frames, fsb, st) : launch3_advect_march_t<3, 4, 3, 2, false>(g, in, nullptr, out, frames, fsb, st);
+    constexpr int R = 4, NW = 4;                                  // 4 rows per wave (measured against 2 and 3)
+    const long long nb = (long long)cdiv(g.W, 64) * cdiv(g.H, R * NW) * g.B;
+    if (!p || nb > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k3_advect_march<R, NW, 2, 3, true>), dim3((unsigned)nb), dim3(NW * 64), 0, st, g, in, p, out, frames, fsb);
+    return hipGetLastError();
 }
 
 }  // namespace smk

@@ -169,7 +169,7 @@ int sim_entry(smk_sim *sim) {
     return project_sync_take_timeout(sim->psync) ? report_timeout() : SMK_OK;
 }
 
-int run_stage(smk_sim *sim, int stage, float *frames, int64_t fsb, const float *fractal, float fint, hipStream_t st) {
+int run_stage(smk_sim *sim, int stage, hipStream_t st) {
     const Geom &g = sim->g;
     StateView &s = sim->s, &t = sim->t;
     switch (stage) {
@@ -184,8 +184,8 @@ int run_stage(smk_sim *sim, int stage, float *frames, int64_t fsb, const float *
         case SMK_STAGE_ADVECT_V:       // v <- adv(v2; u, v2)
             return check_launch(launch_advect(g, 1, t.v, s.v, s.u, t.v, nullptr, 0, nullptr, 0.f, nullptr, nullptr, st),
                                 "advect_v");
-        case SMK_STAGE_ADVECT_D:       // density <- adv(d2; u, v) * 0.995 (+ frame emit)
-            return check_launch(launch_advect(g, 2, t.d, s.d, s.u, s.v, frames, fsb, fractal, fint, nullptr, nullptr, st),
+        case SMK_STAGE_ADVECT_D:       // density <- adv(d2; u, v) * 0.995
+            return check_launch(launch_advect(g, 2, t.d, s.d, s.u, s.v, nullptr, 0, nullptr, 0.f, nullptr, nullptr, st),
                                 "advect_d");
     }
     set_error("unknown stage");
@@ -339,21 +339,12 @@ int smk_sim_step(smk_sim *sim, int32_t n_steps, float *frames, int64_t fsb, int6
     const float *fr = (add_fractal && frames) ? sim->fractal : nullptr;
     for (int t = 0; t < n_steps; ++t) {
         float *ft = frames ? frames + (size_t)t * fst : nullptr;
-        static const bool staged = getenv("SMK_ADVECT_STAGED") != nullptr;      // diagnostic: the three advections as three launches
-        if (staged) {
-            for (int stage = SMK_STAGE_BUOY_DIFFUSE; stage <= SMK_STAGE_ADVECT_D; ++stage) {
-                rc = run_stage(sim, stage, stage == SMK_STAGE_ADVECT_D ? ft : nullptr, fsb, fr, (float)fractal_intensity, st);
-                if (rc) return rc;
-            }
-        } else {
-            // buoyancy + diffusion + projection: one persistent launch where the plan allows (stencil.hip: launch_buoy_project)
-            rc = project_status(launch_buoy_project(sim->g, sim->s, sim->t, sim->s.p, sim->div, sim->jacobi_iters, st, &sim->psync));
-            if (rc) return rc;
-        }
-        if (!staged) {      // u <- adv(u2; u2, v2), v <- adv(v2; u, v2), density <- adv(d2; u, v) * 0.995 (+ frame) in one launch
-            rc = check_launch(launch_advect_fused(sim->g, sim->t, sim->s, ft, fsb, fr, (float)fractal_intensity, st), "advect_fused");
-            if (rc) return rc;
-        }
+        // buoyancy + diffusion + projection: one persistent launch where the plan allows (stencil.hip: launch_buoy_project)
+        rc = project_status(launch_buoy_project(sim->g, sim->s, sim->t, sim->s.p, sim->div, sim->jacobi_iters, st, &sim->psync));
+        if (rc) return rc;
+        // u <- adv(u2; u2, v2), v <- adv(v2; u, v2), density <- adv(d2; u, v) * 0.995 (+ frame) in one launch
+        rc = check_launch(launch_advect_fused(sim->g, sim->t, sim->s, ft, fsb, fr, (float)fractal_intensity, st), "advect_fused");
+        if (rc) return rc;
     }
     return SMK_OK;
 }
@@ -375,25 +366,25 @@ int smk_sim_run_stage(smk_sim *sim, int32_t stage, void *stream) {
     };
     switch (stage) {
         case SMK_STAGE_BUOY_DIFFUSE:
-            rc = run_stage(sim, stage, nullptr, 0, nullptr, 0.f, st);
+            rc = run_stage(sim, stage, st);
             if (rc) return rc;
             SMK_HIP_TRY(cp(s.u, t.u, B * g.su)); SMK_HIP_TRY(cp(s.v, t.v, B * g.sv)); SMK_HIP_TRY(cp(s.d, t.d, B * g.sc));
             return SMK_OK;
         case SMK_STAGE_PROJECT:
             SMK_HIP_TRY(cp(t.u, s.u, B * g.su)); SMK_HIP_TRY(cp(t.v, s.v, B * g.sv));
-            rc = run_stage(sim, stage, nullptr, 0, nullptr, 0.f, st);
+            rc = run_stage(sim, stage, st);
             if (rc) return rc;
             SMK_HIP_TRY(cp(s.u, t.u, B * g.su)); SMK_HIP_TRY(cp(s.v, t.v, B * g.sv));
             return SMK_OK;
         case SMK_STAGE_ADVECT_U:      // reads (u, v) -> writes u
             SMK_HIP_TRY(cp(t.u, s.u, B * g.su)); SMK_HIP_TRY(cp(t.v, s.v, B * g.sv));
-            return run_stage(sim, stage, nullptr, 0, nullptr, 0.f, st);
+            return run_stage(sim, stage, st);
         case SMK_STAGE_ADVECT_V:      // reads v (field), u (already advected), v -> writes v
             SMK_HIP_TRY(cp(t.v, s.v, B * g.sv));
-            return run_stage(sim, stage, nullptr, 0, nullptr, 0.f, st);
+            return run_stage(sim, stage, st);
         case SMK_STAGE_ADVECT_D:
             SMK_HIP_TRY(cp(t.d, s.d, B * g.sc));
-            return run_stage(sim, stage, nullptr, 0, nullptr, 0.f, st);
+            return run_stage(sim, stage, st);
     }
     set_error("unknown stage");
     return SMK_ERR_INVALID;
@@ -437,7 +428,7 @@ int smk_sim_describe(smk_sim *sim, char *buf, int64_t capacity) {
     DeviceGuard guard(sim->device);
     if (guard.rc) return guard.rc;
     const std::string d = "{\"projection\": " + describe_projection(sim->g, sim->jacobi_iters, &sim->psync) +
-                          ", \"advection\": \"k_advect_fused (u, v, density + frame in one LDS-tiled launch)\", \"launches_per_step\": null}";
+                          ", \"advection\": \"k_advect_rows<8,4,3> (u, v, density + frame in one launch)\", \"launches_per_step\": null}";
     if ((int64_t)d.size() + 1 > capacity) {
         set_error("smk_sim_describe: buffer too small");
         return SMK_ERR_INVALID;
@@ -558,7 +549,7 @@ int smk_sim3d_add_sources(smk_sim3d *sim, const smk_source3d *src, int32_t n, vo
 namespace {
 // one stage on the ping-pong pair: s = caller's tensors, t = scratch.  A step runs
 //   (u, v, w, d) --buoy+diffuse--> t --project (p in place via p2)--> t --advect u--> s.u --advect v--> s.v --advect w--> s.w --advect d--> s.d
-int run_stage3d(smk_sim3d *sim, int stage, float *frames, int64_t fsb, hipStream_t st, bool keep_gradient = false) {
+int run_stage3d(smk_sim3d *sim, int stage, hipStream_t st) {
     const Geom3 &g = sim->g;
     State3 &s = sim->s, &t = sim->t;
     switch (stage) {
@@ -568,7 +559,7 @@ int run_stage3d(smk_sim3d *sim, int stage, float *frames, int64_t fsb, hipStream
             int rc = check_launch(launch3_divergence(g, t, sim->div, st), "divergence3d");
             if (rc) return rc;
             rc = check_launch(launch3_jacobi(g, s.p, t.p, sim->p3, sim->div, sim->jacobi_iters, st), "jacobi3d");
-            if (rc || keep_gradient) return rc;          // keep_gradient: the advection launch subtracts dt grad p while it stages its inputs
+            if (rc) return rc;
             return check_launch(launch3_grad_subtract(g, t, s.p, st), "grad_subtract3d");
         }
         case SMK_STAGE3D_ADVECT_U:
@@ -578,7 +569,7 @@ int run_stage3d(smk_sim3d *sim, int stage, float *frames, int64_t fsb, hipStream
         case SMK_STAGE3D_ADVECT_W:
             return check_launch(launch3_advect(g, 2, t.w, s.w, s.u, s.v, t.w, nullptr, 0, st), "advect_w3d");
         case SMK_STAGE3D_ADVECT_D:
-            return check_launch(launch3_advect(g, 3, t.d, s.d, s.u, s.v, s.w, frames, fsb, st), "advect_d3d");
+            return check_launch(launch3_advect(g, 3, t.d, s.d, s.u, s.v, s.w, nullptr, 0, st), "advect_d3d");
     }
     set_error("unknown 3-D stage");
     return SMK_ERR_INVALID;
@@ -590,43 +581,17 @@ int smk_sim3d_step(smk_sim3d *sim, int32_t n_steps, float *frames, int64_t fsb, 
     hipStream_t st = (hipStream_t)stream;
     DeviceGuard guard(sim->device);
     if (guard.rc) return guard.rc;
-    // diagnostics (read once): SMK_ADVECT3_STAGED the four advections as four launches; SMK_ADVECT3_TILE the 8 x 8 x 32 tile launch of
-    // round 3; SMK_ADVECT3_GRAD=0 the z-marching launch behind a separate gradient-subtraction launch.  Default: the z-marching launch
-    // with the gradient subtraction applied while it stages its inputs.
-    static const bool staged = getenv("SMK_ADVECT3_STAGED") != nullptr;
-    static const bool tiled = getenv("SMK_ADVECT3_TILE") != nullptr;
-    static const bool fold_grad = !staged && !tiled && !(getenv("SMK_ADVECT3_GRAD") && atoi(getenv("SMK_ADVECT3_GRAD")) == 0);
-    // SMK_DIFFUSE3_FUSED=0: buoyancy + diffusion and the divergence as two launches (the per-stage forms) instead of the z-marching one
-    static const bool fused_dd = !(getenv("SMK_DIFFUSE3_FUSED") && atoi(getenv("SMK_DIFFUSE3_FUSED")) == 0);
+    // buoyancy + diffusion + divergence (one z-marching launch), the Jacobi sweeps, then the four advections as one z-marching launch that
+    // applies the projection's gradient subtraction while it stages its inputs
     const Geom3 &g = sim->g;
     for (int t = 0; t < n_steps; ++t) {
         float *ft = frames ? frames + (size_t)t * fst : nullptr;
-        int rc;
-        if (fused_dd) {
-            rc = check_launch(launch3_diffuse_div_march(g, sim->s, sim->t, sim->div, st), "diffuse_div_march3d");
-            if (rc) return rc;
-            rc = check_launch(launch3_jacobi(g, sim->s.p, sim->t.p, sim->p3, sim->div, sim->jacobi_iters, st), "jacobi3d");
-            if (rc) return rc;
-            if (!fold_grad) {
-                rc = check_launch(launch3_grad_subtract(g, sim->t, sim->s.p, st), "grad_subtract3d");
-                if (rc) return rc;
-            }
-        } else {
-            for (int stage = SMK_STAGE3D_BUOY_DIFFUSE; stage <= SMK_STAGE3D_PROJECT; ++stage) {
-                rc = run_stage3d(sim, stage, nullptr, fsb, st, fold_grad);
-                if (rc) return rc;
-            }
-        }
-        if (staged) {
-            for (int stage = SMK_STAGE3D_ADVECT_U; stage <= SMK_STAGE3D_ADVECT_D; ++stage) {
-                rc = run_stage3d(sim, stage, stage == SMK_STAGE3D_ADVECT_D ? ft : nullptr, fsb, st);
-                if (rc) return rc;
-            }
-        } else {
-            rc = tiled ? check_launch(launch3_advect_fused(g, sim->t, sim->s, ft, fsb, st), "advect_fused3d")
-                       : check_launch(launch3_advect_march(g, sim->t, fold_grad ? sim->s.p : nullptr, sim->s, ft, fsb, st), "advect_march3d");
-            if (rc) return rc;
-        }
+        int rc = check_launch(launch3_diffuse_div_march(g, sim->s, sim->t, sim->div, st), "diffuse_div_march3d");
+        if (rc) return rc;
+        rc = check_launch(launch3_jacobi(g, sim->s.p, sim->t.p, sim->p3, sim->div, sim->jacobi_iters, st), "jacobi3d");
+        if (rc) return rc;
+        rc = check_launch(launch3_advect_march(g, sim->t, sim->s.p, sim->s, ft, fsb, st), "advect_march3d");
+        if (rc) return rc;
     }
     return SMK_OK;
 }
@@ -644,29 +609,29 @@ int smk_sim3d_run_stage(smk_sim3d *sim, int32_t stage, void *stream) {
     int rc;
     switch (stage) {
         case SMK_STAGE3D_BUOY_DIFFUSE:
-            rc = run_stage3d(sim, stage, nullptr, 0, st);
+            rc = run_stage3d(sim, stage, st);
             if (rc) return rc;
             SMK_HIP_TRY(cp(s.u, t.u, B * g.su)); SMK_HIP_TRY(cp(s.v, t.v, B * g.sv)); SMK_HIP_TRY(cp(s.w, t.w, B * g.sw));
             SMK_HIP_TRY(cp(s.d, t.d, B * g.sc));
             return SMK_OK;
         case SMK_STAGE3D_PROJECT:
             SMK_HIP_TRY(cp(t.u, s.u, B * g.su)); SMK_HIP_TRY(cp(t.v, s.v, B * g.sv)); SMK_HIP_TRY(cp(t.w, s.w, B * g.sw));
-            rc = run_stage3d(sim, stage, nullptr, 0, st);
+            rc = run_stage3d(sim, stage, st);
             if (rc) return rc;
             SMK_HIP_TRY(cp(s.u, t.u, B * g.su)); SMK_HIP_TRY(cp(s.v, t.v, B * g.sv)); SMK_HIP_TRY(cp(s.w, t.w, B * g.sw));
             return SMK_OK;
         case SMK_STAGE3D_ADVECT_U:      // reads (u, v, w) -> writes u
             SMK_HIP_TRY(cp(t.u, s.u, B * g.su)); SMK_HIP_TRY(cp(t.v, s.v, B * g.sv)); SMK_HIP_TRY(cp(t.w, s.w, B * g.sw));
-            return run_stage3d(sim, stage, nullptr, 0, st);
+            return run_stage3d(sim, stage, st);
         case SMK_STAGE3D_ADVECT_V:      // reads v (field), u (already advected), v, w -> writes v
             SMK_HIP_TRY(cp(t.v, s.v, B * g.sv)); SMK_HIP_TRY(cp(t.w, s.w, B * g.sw));
-            return run_stage3d(sim, stage, nullptr, 0, st);
+            return run_stage3d(sim, stage, st);
         case SMK_STAGE3D_ADVECT_W:
             SMK_HIP_TRY(cp(t.w, s.w, B * g.sw));
-            return run_stage3d(sim, stage, nullptr, 0, st);
+            return run_stage3d(sim, stage, st);
         case SMK_STAGE3D_ADVECT_D:
             SMK_HIP_TRY(cp(t.d, s.d, B * g.sc));
-            return run_stage3d(sim, stage, nullptr, 0, st);
+            return run_stage3d(sim, stage, st);
     }
     set_error("unknown 3-D stage");
     return SMK_ERR_INVALID;

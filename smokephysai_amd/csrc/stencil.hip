@@ -101,11 +101,6 @@ hipError_t launch_diffuse(const float *in, float *out, int B, int R, int C, int 
     return hipGetLastError();
 }
 
-static bool knobs_scalar_diffuse() {                         // SMK_DIFFUSE_SCALAR=1: the one-cell-per-thread form (diagnostic)
-    static const bool v = [] { const char *e = getenv("SMK_DIFFUSE_SCALAR"); return e && e[0] == '1'; }();
-    return v;
-}
-
 // buoyancy (navier_stokes.py:154-155) fused into the three diffusions (:158-160).
 // v_b(i,j) = j < W ? v + dt*(density*0.1) : v    -- the buoyancy-updated v that diffusion_step(v) sees.
 __device__ __forceinline__ float vbuoy(const float *v, const float *d, const Geom &g, int i, int j) {
@@ -215,7 +210,7 @@ __global__ __launch_bounds__(256) void k_buoy_diffuse4(Geom g, StateView in, Sta
 }
 
 hipError_t launch_buoy_diffuse(const Geom &g, StateView in, StateView out, hipStream_t st) {
-    if (g.W % 4 == 0 && g.pc % 4 == 0 && g.pv % 4 == 0 && !knobs_scalar_diffuse()) {
+    if (g.W % 4 == 0 && g.pc % 4 == 0 && g.pv % 4 == 0) {
         dim3 grid(cdiv(g.W / 4, TX), cdiv(g.H + 1, TY), g.B), block(TX, TY);
         hipLaunchKernelGGL(k_buoy_diffuse4, grid, block, 0, st, g, in, out);
         return hipGetLastError();
@@ -738,26 +733,15 @@ __global__ __launch_bounds__(JB_NW * 64) void k_jacobi_band(Geom g, const float 
     }
 }
 
-// Diagnostic switches of the projection, read ONCE per process (never on the per-step path):
-//   SMK_JACOBI_GENERIC=1   one launch per sweep (k_jacobi_sweep)        SMK_PROJECT_UNFUSED=1  divergence / gradient as own launches
-//   SMK_JACOBI_RPW, SMK_JACOBI_BANDS   pin the band plan of k_jacobi_band   SMK_STENCIL_DEBUG=1    print the chosen plan
+// Switches of the projection, read ONCE per process (never on the per-step path):
 //   SMK_JACOBI_PERSIST=0   one launch per chunk of sweeps instead of the single persistent launch
 //   SMK_JACOBI_FAULT=1     (test only) one band never publishes its hand-off: exercises the bounded wait and the error report
-//   SMK_PROJECT_FOLD=0     buoyancy + diffusion as their own launch in front of the persistent projection
 struct StencilKnobs {
-    bool generic, unfused, debug, persist, fault, fold;
-    int rpw, bands;
+    bool persist, fault;
     StencilKnobs() {
         auto flag = [](const char *n, bool dflt) { const char *v = getenv(n); return v ? v[0] == '1' : dflt; };
-        auto num = [](const char *n) { const char *v = getenv(n); return v ? atoi(v) : 0; };
-        generic = flag("SMK_JACOBI_GENERIC", false);
-        unfused = flag("SMK_PROJECT_UNFUSED", false);
-        debug = flag("SMK_STENCIL_DEBUG", false);
         persist = flag("SMK_JACOBI_PERSIST", true);
         fault = flag("SMK_JACOBI_FAULT", false);
-        fold = flag("SMK_PROJECT_FOLD", true);
-        rpw = num("SMK_JACOBI_RPW");
-        bands = num("SMK_JACOBI_BANDS");
     }
 };
 static const StencilKnobs &knobs() {
@@ -770,20 +754,16 @@ struct JacobiPlan { int vec, rpw, br, nb, halo; };
 // persist: cost the plan for the single-launch form (a hand-off between chunks instead of a relaunch)
 static bool plan_jacobi(const Geom &g, JacobiPlan &pl, int iters = 100, bool persist = false) {
     if (g.W % 64 != 0 || g.W / 64 > 8 || (g.W / 64 & (g.W / 64 - 1)) || g.pc % 4 != 0) return false;
-    if (knobs().generic) return false;
     pl.vec = g.W / 64;
     // candidates: rows/wave; pick the plan with the least estimated time ~ launches*(t0 + iters*waves_of_work)
     const int rpws[] = {2, 3, 4, 6, 8};
     double best = 1e30;
     bool ok = false;
-    const int env_rpw = knobs().rpw, env_nb = knobs().bands;
     for (int rpw : rpws) {
-        if (env_rpw && env_rpw != rpw) continue;
         if (pl.vec * rpw > 32) continue;                      // register budget (p + div)
         const int TR = JB_NW * rpw;
         if (TR > g.H) continue;
         for (int nb = 1; nb <= g.H / 8; ++nb) {
-            if (env_nb && env_nb != nb) continue;
             // nb bands of TR rows cover H owned rows with a halo on every inner side: 2 (TR - h) + (nb - 2)(TR - 2h) >= H
             int halo = nb == 1 ? 1 << 20 : (nb * TR - g.H) / (2 * nb - 2);
             if (nb == 1 && TR != g.H) continue;
@@ -925,7 +905,7 @@ void project_sync_destroy(ProjectSync &ps) {
 }
 
 static bool use_persist(const Geom &g, const ProjectSync *ps, int iters, JacobiPlan &pl, int &chunks) {
-    if (!ps || !ps->flags || ps->disabled || !knobs().persist || knobs().unfused || iters < 2) return false;
+    if (!ps || !ps->flags || ps->disabled || !knobs().persist || iters < 2) return false;
     if (!plan_jacobi(g, pl, iters, true) || pl.halo < 3) return false;
     if (pl.nb > device_num_cu()) return false;
     return persist_chunks(g, pl, iters, chunks);
@@ -982,9 +962,6 @@ hipError_t launch_project(const Geom &g, float *u, float *v, float *p, float *p2
     if (!capturing && use_persist(g, ps, iters, pl, chunks)) {
         int per = device_num_cu() / pl.nb;                    // grids whose bands are all co-resident (one 1024-thread workgroup per CU)
         if (per >= 8) per &= ~7;
-        if (knobs().debug)
-            fprintf(stderr, "[smk] project %dx%dx%d J=%d: persistent, vec=%d rpw=%d nb=%d halo=%d, %d chunks, %d grids per launch\n", g.B, g.H, g.W,
-                    iters, pl.vec, pl.rpw, pl.nb, pl.halo, chunks, per);
         JacobiSync sy{};
         sy.flags = ps->flags; sy.status = const_cast<unsigned *>(ps->status); sy.x0 = div; sy.x1 = p2;
         sy.base = ps->seq; sy.chunks = chunks; sy.nb = pl.nb; sy.abort_slot = ps->flags_len - 1; sy.fault = knobs().fault ? 1 : 0;
@@ -992,7 +969,7 @@ hipError_t launch_project(const Geom &g, float *u, float *v, float *p, float *p2
         ps->seq += (unsigned)chunks;
         const std::unique_lock<std::mutex> launch_order = order_persistent_launch(st);
         // the buoyancy + diffusion stage as this launch's prologue (16-byte row accesses: pitches in multiples of 4; up to 4 cells per lane)
-        const bool fold = fold_in && fold_d_out && knobs().fold && pl.vec <= 4 && g.pv % 4 == 0 && g.pc % 4 == 0;
+        const bool fold = fold_in && fold_d_out && pl.vec <= 4 && g.pv % 4 == 0 && g.pc % 4 == 0;
         if (fold) {
             sy.u_in = fold_in->u; sy.v_in = fold_in->v; sy.d_in = fold_in->d; sy.d_out = fold_d_out;
             if (folded) *folded = true;
@@ -1005,7 +982,7 @@ hipError_t launch_project(const Geom &g, float *u, float *v, float *p, float *p2
         }
         return hipGetLastError();
     }
-    if (iters < 2 || !plan_jacobi(g, pl, iters) || pl.halo < 3 || knobs().unfused) {
+    if (iters < 2 || !plan_jacobi(g, pl, iters) || pl.halo < 3) {
         hipError_t e = launch_divergence(g, u, v, div, g.pc, g.sc, st);
         if (e != hipSuccess) return e;
         e = launch_jacobi(g, p, p2, div, iters, st);
@@ -1014,9 +991,6 @@ hipError_t launch_project(const Geom &g, float *u, float *v, float *p, float *p2
     }
     const int cap = pl.halo - 1;                              // the fused gradient needs the row above the owned range exact
     const int L = 2 * ((iters + 2 * cap - 1) / (2 * cap));
-    if (knobs().debug)
-        fprintf(stderr, "[smk] project %dx%dx%d J=%d: band plan vec=%d rpw=%d nb=%d halo=%d -> %d launches\n", g.B, g.H, g.W, iters, pl.vec,
-                pl.rpw, pl.nb, pl.halo, L);
     float *cur = p, *nxt = p2;
     int done = 0;
     for (int c = 0; c < L; ++c) {
@@ -1039,7 +1013,7 @@ hipError_t launch_buoy_project(const Geom &g, StateView in, StateView out, float
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     const bool capturing = hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
     const bool pending_error = ps && ps->status && *ps->status != 0u;
-    if (!capturing && !pending_error && use_persist(g, ps, iters, pl, chunks) && knobs().fold && pl.vec <= 4 && g.pv % 4 == 0 && g.pc % 4 == 0) {
+    if (!capturing && !pending_error && use_persist(g, ps, iters, pl, chunks) && pl.vec <= 4 && g.pv % 4 == 0 && g.pc % 4 == 0) {
         const hipError_t e = launch_project(g, out.u, out.v, p, out.p, div, iters, st, ps, &in, out.d, &folded);
         if (e != hipSuccess || folded) return e;
         return hipErrorUnknown;                               // (unreachable: the conditions above are launch_project's own)
@@ -1056,7 +1030,7 @@ std::string describe_projection(const Geom &g, int iters, const ProjectSync *ps)
     char buf[1280];
     int chunks = 0;
     const bool persist = use_persist(g, ps, iters, pl, chunks);
-    if (!persist && (iters < 2 || !plan_jacobi(g, pl, iters) || pl.halo < 3 || knobs().unfused)) {
+    if (!persist && (iters < 2 || !plan_jacobi(g, pl, iters) || pl.halo < 3)) {
         snprintf(buf, sizeof buf, "{\"kernel\": \"k_jacobi_sweep\", \"launches\": %d, \"sweeps\": %d, \"bound\": \"hbm (one pass over p and div per sweep)\"}",
                  iters + 2, iters);
         return buf;
@@ -1182,7 +1156,6 @@ hipError_t launch_advect(const Geom &g, int kind, const float *field, float *out
     return hipGetLastError();
 }
 
-
 // ---- the three advections of a step as ONE launch (navier_stokes.py:166-171) --------------------------------------------------------
 // u <- adv(u2; u2, v2), v <- adv(v2; u, v2), density <- adv(d2; u, v) * 0.995 are sequentially dependent, but only through the
 // velocity SAMPLING, which happens at the integer cell coordinates (advection_step builds Y, X with meshgrid, :79-81), where
@@ -1191,147 +1164,7 @@ hipError_t launch_advect(const Geom &g, int kind, const float *field, float *out
 //   v at (y + 0.5, X = j): x0 = j with weight (x1 - j) in {1, 0}, y-weights 0.5 / 0.5  ->  vi = 0.5*V[i][j] + 0.5*V[i+1][j]   (i <= H-2, j <= W-1)
 //   and 0 otherwise (both clamped indices coincide: the zero-at-the-upper-edge quirk).  The dropped terms are products with an exact
 //   zero weight: for finite fields they are +-0 and change at most the sign of a zero, which X - dt*ui cannot see (X >= 0).
-// The displacement-dependent gathers read u2, v2, d2 -- inputs of the launch.  So a workgroup that owns a TH x TW tile of cells stages
-// u2, v2, d2 (tile + 1 halo, + 2 on the high side for u2 / v2) in LDS, computes the advected u on the tile extended by one row and
-// column and the advected v on the tile extended by one row (redundantly with its neighbours: ~5 % more points), keeps both in LDS
-// for the next field's sampling, and writes its own cells of u, v, density and the emitted frame.  A back-trace that leaves the
-// staged window (|dt * velocity| >= 1 cell: never in the reference's regime, |velocity| ~ 0.1) gathers from global memory instead
-// -- one wave-level branch per cell, same values either way.  Per point the gather arithmetic is bilinear()'s (one rounding per
-// reference op).  HBM traffic: u2, v2, d2, fractal in; u, v, density, frame out -- 8 floats per cell instead of the 12 of three
-// launches; vector instructions per cell and field: ~60 instead of ~150 (k_advect evaluates all three bilinears in the general form).
-constexpr int AF_TH = 32, AF_TW = 64, AF_THREADS = 256;
 
-// the final gather of advection_step: bilinear_interpolate(field[R][C], py, px) with py, px already clamped into [0, R-1] x [0, C-1]
-// (:91-92), so floor == truncation and the lower index clamps of :120-123 are no-ops.  `f` = window in LDS (top-left cell (oi, oj),
-// nr x nc, pitch lp) or, when the four taps do not all lie inside it, the field in global memory (pitch gp).
-// (the fallback is a real call: inlined, the compiler merges the two arms into ONE flat_load through a selected generic pointer, and
-// flat loads of LDS addresses run at a fraction of ds_read's rate -- the first version of this kernel took 75 us instead of 3 x 19)
-__device__ __attribute__((noinline)) void gather_far(const float *glob, int gp, int y0, int y1, int x0, int x1, float (&f)[4]) {
-    f[0] = glob[(size_t)y0 * gp + x0]; f[1] = glob[(size_t)y0 * gp + x1];
-    f[2] = glob[(size_t)y1 * gp + x0]; f[3] = glob[(size_t)y1 * gp + x1];
-}
-
-__device__ __forceinline__ float gather_cell(const float *lds, int oi, int oj, int nr, int nc, int lp, const float *glob, int gp, int R,
-                                             int C, float py, float px) {
-    const int x0 = (int)px, y0 = (int)py;
-    int x1 = x0 + 1, y1 = y0 + 1;
-    x1 = x1 > C - 1 ? C - 1 : x1;
-    y1 = y1 > R - 1 ? R - 1 : y1;
-    const float fx0 = (float)x0, fx1 = (float)x1, fy0 = (float)y0, fy1 = (float)y1;
-    const float wa = (fx1 - px) * (fy1 - py);
-    const float wb = (px - fx0) * (fy1 - py);
-    const float wc = (fx1 - px) * (py - fy0);
-    const float wd = (px - fx0) * (py - fy0);
-    float f[4];
-    const int r0 = y0 - oi, r1 = y1 - oi, c0 = x0 - oj, c1 = x1 - oj;
-    if (__builtin_expect(r0 >= 0 && r1 < nr && c0 >= 0 && c1 < nc, 1)) {
-        f[0] = lds[r0 * lp + c0]; f[1] = lds[r0 * lp + c1]; f[2] = lds[r1 * lp + c0]; f[3] = lds[r1 * lp + c1];
-    } else {
-        gather_far(glob, gp, y0, y1, x0, x1, f);
-    }
-    float r = wa * f[0] + wb * f[1];
-    r = r + wc * f[2];
-    r = r + wd * f[3];
-    return r;
-}
-
-__global__ __launch_bounds__(AF_THREADS) void k_advect_fused(Geom g, StateView in, StateView out, float *frames, int64_t fsb,
-                                                            const float *fractal, float fint) {
-    constexpr int TH = AF_TH, TW = AF_TW;
-    constexpr int UR = TH + 3, UC = TW + 3;      // u2 / v2 / d2 windows: rows i0-1 .. i0+TH+1, columns j0-1 .. j0+TW+1
-    constexpr int NR = TH + 1, NC = TW + 1;      // advected u and v: rows i0 .. i0+TH, columns j0 .. j0+TW
-    __shared__ float us[UR * UC], vs[UR * UC], ds[UR * UC], un[NR * NC], vn[NR * NC];
-    const int b = blockIdx.z, i0 = blockIdx.y * TH, j0 = blockIdx.x * TW, tid = threadIdx.x;
-    const int i1 = i0 + TH < g.H ? i0 + TH : g.H, j1 = j0 + TW < g.W ? j0 + TW : g.W;
-    const int H = g.H, W = g.W;
-    const float *u2 = in.u + b * g.su, *v2 = in.v + b * g.sv, *d2 = in.d + b * g.sc;
-    // stage the inputs: all loads of a thread are issued before the first LDS write (addresses clamped into the field instead of
-    // branches: a load under a branch waits for its data before the next one is issued -- 30 serial HBM latencies per thread)
-    constexpr int NST = (UR * UC + AF_THREADS - 1) / AF_THREADS;
-    float ru[NST], rv[NST], rd[NST];
-#pragma unroll
-    for (int it = 0; it < NST; ++it) {
-        int idx = tid + it * AF_THREADS;
-        idx = idx < UR * UC ? idx : UR * UC - 1;
-        const int r = idx / UC, c = idx - r * UC, gi = i0 - 1 + r, gj = j0 - 1 + c;
-        const int ci = clampi(gi, 0, H - 1), cj = clampi(gj, 0, W - 1);
-        ru[it] = u2[(size_t)clampi(gi, 0, H) * g.pc + cj];
-        rv[it] = v2[(size_t)ci * g.pv + clampi(gj, 0, W)];
-        rd[it] = d2[(size_t)ci * g.pc + cj];
-    }
-#pragma unroll
-    for (int it = 0; it < NST; ++it) {
-        const int idx = tid + it * AF_THREADS;
-        if (idx < UR * UC) { us[idx] = ru[it]; vs[idx] = rv[it]; ds[idx] = rd[it]; }
-    }
-    __syncthreads();
-    // window-local index of cell (i, j) of the staged inputs
-    auto wi = [&](int i, int j) { return (i - i0 + 1) * UC + (j - j0 + 1); };
-    // 1. u <- adv(u2; u2, v2) on rows i0 .. i0+TH, columns j0 .. j0+TW (field shape [H+1][W])
-    float *uo = out.u + b * g.su;
-    // thread (ty, tx) walks rows ty, ty + 4, ... of column tx (no index division); the extra column TW is a pass of its own
-    const int tx = tid & 63, ty = tid >> 6;
-    auto adv_u = [&](int r, int c) {
-        const int i = i0 + r, j = j0 + c, idx = r * NC + c;
-        if (i > H || j >= W) return;
-        float ui = 0.f, vi = 0.f;
-        if (i <= H - 1 && j <= W - 2) ui = 0.5f * us[wi(i, j)] + 0.5f * us[wi(i, j + 1)];
-        if (i <= H - 2) vi = 0.5f * vs[wi(i, j)] + 0.5f * vs[wi(i + 1, j)];
-        const float px = clampf((float)j - g.dt * ui, 0.f, (float)(W - 1));
-        const float py = clampf((float)i - g.dt * vi, 0.f, (float)H);
-        const float val = gather_cell(us, i0 - 1, j0 - 1, UR, UC, UC, u2, g.pc, H + 1, W, py, px);
-        un[idx] = val;
-        if ((i < i1 || (i == H && i1 == H)) && j < j1) uo[(size_t)i * g.pc + j] = val;
-    };
-#pragma unroll 3
-    for (int r = ty; r < NR; r += 4) adv_u(r, tx);
-    if (tid < NR) adv_u(tid, TW);
-    __syncthreads();
-    // 2. v <- adv(v2; u, v2) on rows i0 .. i0+TH, columns j0 .. j0+TW (field shape [H][W+1]); u = the advected u in LDS
-    float *vo = out.v + b * g.sv;
-    auto adv_v = [&](int r, int c) {
-        const int i = i0 + r, j = j0 + c, idx = r * NC + c;
-        if (i >= H || j > W) return;
-        float ui = 0.f, vi = 0.f;
-        if (j <= W - 2) ui = 0.5f * un[idx] + 0.5f * un[idx + 1];
-        if (i <= H - 2 && j <= W - 1) vi = 0.5f * vs[wi(i, j)] + 0.5f * vs[wi(i + 1, j)];
-        const float px = clampf((float)j - g.dt * ui, 0.f, (float)W);
-        const float py = clampf((float)i - g.dt * vi, 0.f, (float)(H - 1));
-        const float val = gather_cell(vs, i0 - 1, j0 - 1, UR, UC, UC, v2, g.pv, H, W + 1, py, px);
-        vn[idx] = val;
-        if (i < i1 && (j < j1 || j == W)) vo[(size_t)i * g.pv + j] = val;
-    };
-#pragma unroll 3
-    for (int r = ty; r < NR; r += 4) adv_v(r, tx);
-    if (tid < NR && j0 + TW == W) adv_v(tid, TW);             // column j0+TW is needed only as the field's last column
-    __syncthreads();
-    // 3. density <- adv(d2; u, v) * 0.995 (+ frame emit) on the tile; u, v = the advected fields in LDS
-#pragma unroll 4
-    for (int r = ty; r < TH; r += 4) {
-        const int c = tx, i = i0 + r, j = j0 + c;
-        if (i >= i1 || j >= j1) continue;
-        const int n = r * NC + c;
-        float ui = 0.f, vi = 0.f;
-        if (j <= W - 2) ui = 0.5f * un[n] + 0.5f * un[n + 1];
-        if (i <= H - 2) vi = 0.5f * vn[n] + 0.5f * vn[n + NC];
-        const float px = clampf((float)j - g.dt * ui, 0.f, (float)(W - 1));
-        const float py = clampf((float)i - g.dt * vi, 0.f, (float)(H - 1));
-        float val = gather_cell(ds, i0 - 1, j0 - 1, UR, UC, UC, d2, g.pc, H, W, py, px);
-        val = val * 0.995f;                                           // :171
-        if (frames) {
-            float fr = val;
-            if (fractal) {                                            // fractal_generator.py:62 (F is [W][H], square)
-                float t = fint * fractal[(size_t)i * W + j];
-                t = t * val;
-                fr = val + t;
-            }
-            frames[(size_t)b * fsb + (size_t)i * W + j] = fr;
-        }
-        out.d[b * g.sc + (size_t)i * g.pc + j] = val;
-    }
-}
-
-// ---- the same launch with wave-autonomous rows (round 4; the organisation of csrc/advect3d.hip's k3_advect_march, one plane) ------------
 // One advected value in the general form, every tap from GLOBAL memory: what a wave falls back to when a back-trace of its units leaves the
 // 2 x 2 LDS neighbourhood (never in the reference's regime).  A real call, so the hot code carries neither its registers nor its loads.
 // Field [Rf][Cf] (pitch `pitch`); (y, x) = the cell; ui, vi = the velocity samples already formed by the caller.
@@ -1354,14 +1187,15 @@ __device__ __attribute__((noinline)) float far_value2(const float *f, int pitch,
 }
 
 
+// Wave-autonomous rows (round 4, in place of round 2's LDS-tiled launch; the organisation of csrc/advect3d.hip's k3_advect_march, one plane).
 // Workgroup = NW waves = a (NW R) x 64 tile; u2, v2, d2 windows (tile + 1 low, + 2 high; every out-of-grid element holds the CLAMPED in-grid
 // value, which is exactly what bilinear()'s clamped indices read) staged once into LDS, ONE barrier.  A wave then owns R consecutive rows:
 // thread = column, the advected u and v of its rows (+ the next row) live in REGISTERS -- x + 1 comes from the next lane by DPP, lane 63's
-// from the extra-column unit by v_readlane -- so nothing separates the three fields (k_advect_fused: two more barriers and two LDS round
-// trips).  With |dt * velocity| < 1 cell a back-trace lands on floor(p) in {i-1, i}: four taps at immediate offsets from ONE LDS address;
+// from the extra-column unit by v_readlane -- so nothing separates the three fields (round 2's LDS-tiled form: two more barriers and two LDS
+// round trips).  With |dt * velocity| < 1 cell a back-trace lands on floor(p) in {i-1, i}: four taps at immediate offsets from ONE LDS address;
 // the test is one wave-level vote per batch of units, the fall-back the general form per lane (far_value2).  EDGE = false is the same
 // arithmetic with the tests that cannot fail inside the grid removed (existence, the sampling rules' extents, the clamps: an unclamped
-// back-trace that would have needed its clamp fails the neighbourhood test).  Bit-identical to k_advect_fused.
+// back-trace that would have needed its clamp fails the neighbourhood test).  Bit-identical to the staged k_advect launches.
 template <int R, int NW, int BU>
 __global__ __launch_bounds__(NW * 64) void k_advect_rows(Geom g, StateView in, StateView out, float *frames, int64_t fsb,
                                                          const float *__restrict__ fractal, float fint) {
@@ -1582,18 +1416,11 @@ __global__ __launch_bounds__(NW * 64) void k_advect_rows(Geom g, StateView in, S
 
 hipError_t launch_advect_fused(const Geom &g, StateView in, StateView out, float *frames, int64_t fsb, const float *fractal, float fint,
                                hipStream_t st) {
-    static int rows_env = -1;            // SMK_ADVECT_ROWS=0: round 2's k_advect_fused (A/B runs)
-    if (rows_env < 0) { const char *sv = getenv("SMK_ADVECT_ROWS"); rows_env = sv ? atoi(sv) : 1; }
-    if (rows_env) {
-        // R x NW = 8 x 4 rows per workgroup (measured at configs[2] against 4 x 4, 4 x 8, 8 x 8, 16 x 2 rows and batches of 5 units: equal within
-        // noise except 16 x 2, +7 %)
-        constexpr int R = 8, NW = 4;
-        const long long n = (long long)cdiv(g.W, 64) * cdiv(g.H, R * NW) * g.B;
-        hipLaunchKernelGGL((k_advect_rows<R, NW, 3>), dim3((unsigned)n), dim3(NW * 64), 0, st, g, in, out, frames, fsb, fractal, fint);
-        return hipGetLastError();
-    }
-    dim3 grid(cdiv(g.W, AF_TW), cdiv(g.H, AF_TH), g.B), block(AF_THREADS);
-    hipLaunchKernelGGL(k_advect_fused, grid, block, 0, st, g, in, out, frames, fsb, fractal, fint);
+    // R x NW = 8 x 4 rows per workgroup (measured at configs[2] against 4 x 4, 4 x 8, 8 x 8, 16 x 2 rows and batches of 5 units: equal within
+    // noise except 16 x 2, +7 %)
+    constexpr int R = 8, NW = 4;
+    const long long n = (long long)cdiv(g.W, 64) * cdiv(g.H, R * NW) * g.B;
+    hipLaunchKernelGGL((k_advect_rows<R, NW, 3>), dim3((unsigned)n), dim3(NW * 64), 0, st, g, in, out, frames, fsb, fractal, fint);
     return hipGetLastError();
 }
 

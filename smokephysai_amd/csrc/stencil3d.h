@@ -30,11 +30,9 @@ hipError_t launch3_grad_subtract(const Geom3 &g, State3 s, const float *p, hipSt
 // which 0..3 = u, v, w, density (x 0.995, + optional frame [B][D][H][W] dense at frame_stride_b floats per grid)
 hipError_t launch3_advect(const Geom3 &g, int which, const float *field, float *out, const float *u, const float *v, const float *w,
                           float *frames, int64_t frame_stride_b, hipStream_t st);
-
-// the four advections of one step as one launch: in = (u2, v2, w2, -, d2), out = (u, v, w, -, density); bit-identical to the four launches
-hipError_t launch3_advect_fused(const Geom3 &g, State3 in, State3 out, float *frames, int64_t frame_stride_b, hipStream_t st);
-// the same as a z-marching launch (inputs staged once into LDS rings).  p != nullptr: `in` holds the velocities BEFORE the projection's
-// gradient subtraction and the launch applies it on the fly (launch3_grad_subtract is then not run); bit-identical either way
+// the four advections of one step as one z-marching launch (inputs staged once into LDS rings): in = (u2, v2, w2, -, d2), out = (u, v, w, -,
+// density).  `in` holds the velocities BEFORE the projection's gradient subtraction and the launch applies it with the pressure p (not null)
+// on the fly, so launch3_grad_subtract is not run; bit-identical to the grad_subtract launch followed by the four advection launches
 hipError_t launch3_advect_march(const Geom3 &g, State3 in, const float *p, State3 out, float *frames, int64_t frame_stride_b, hipStream_t st);
 
 

@@ -200,8 +200,7 @@ __global__ __launch_bounds__(TXB * TYB) void k3_buoy_diffuse_march(Geom3 g, Stat
 }
 
 hipError_t launch3_buoy_diffuse(const Geom3 &g, State3 in, State3 out, hipStream_t st) {
-    static const bool cellwise = getenv("SMK_DIFFUSE3_CELLWISE") != nullptr;      // diagnostic: the one-cell-per-thread form
-    if (!cellwise && g.B <= 65535) {
+    if (g.B <= 65535) {
         constexpr int TXB = 64, TYB = 4;
         hipLaunchKernelGGL((k3_buoy_diffuse_march<TXB, TYB>), dim3((unsigned)(cdiv(g.W, TXB) * cdiv(g.H + 1, TYB) * g.B)), dim3(TXB, TYB), 0, st, g, in, out);
         return hipGetLastError();
@@ -475,10 +474,8 @@ __global__ __launch_bounds__(512, 2) void k3_jacobi_v4(Geom3 g, const float *__r
 template <int T>
 static void launch3_jacobi_v4(const Geom3 &g, const float *cur, float *nxt, const float *div, hipStream_t st) {
     const unsigned nb = (unsigned)(cdiv(g.W, 56) * cdiv(g.H, 24) * g.B);
-    static const int pd = [] { const char *e = getenv("SMK_JACOBI3_PD"); return e ? atoi(e) : 2; }();     // planes requested ahead (measured per configs[4] step: 1 -> 6.00 ms, 2 -> 5.98, 3 -> 6.70; the one-cell-per-thread kernel 6.50)
-    if (pd == 1) hipLaunchKernelGGL((k3_jacobi_v4<T, 1>), dim3(nb), dim3(512), 0, st, g, cur, nxt, div);
-    else if (pd == 2) hipLaunchKernelGGL((k3_jacobi_v4<T, 2>), dim3(nb), dim3(512), 0, st, g, cur, nxt, div);
-    else hipLaunchKernelGGL((k3_jacobi_v4<T, 3>), dim3(nb), dim3(512), 0, st, g, cur, nxt, div);
+    // 2 planes requested ahead (measured per configs[4] step: 1 -> 6.00 ms, 2 -> 5.98, 3 -> 6.70; the one-cell-per-thread kernel 6.50)
+    hipLaunchKernelGGL((k3_jacobi_v4<T, 2>), dim3(nb), dim3(512), 0, st, g, cur, nxt, div);
 }
 
 template <int T, int TXB, int TYB, int CY>
@@ -488,26 +485,23 @@ static void launch3_jacobi_xt(const Geom3 &g, const float *cur, float *nxt, cons
 }
 
 hipError_t launch3_jacobi(const Geom3 &g, float *p, float *p2, float *p3, const float *div, int iters, hipStream_t st) {
-    const bool vec = g.W % 4 == 0 && g.pc % 4 == 0 && getenv("SMK_JACOBI3_SCALAR") == nullptr;
+    const bool vec = g.W % 4 == 0 && g.pc % 4 == 0;
     dim3 block(TX3, TY3), grid(cdiv(vec ? g.W / 4 : g.W, TX3), cdiv(g.H, TY3), g.B * g.D);
-    // temporally blocked launches first (SMK_JACOBI3_T = 1, 2, 4 caps the sweeps per launch; default 4), single sweeps for the rest
-    static const int tmax = [] { const char *e = getenv("SMK_JACOBI3_T"); return e ? atoi(e) : 4; }();
-    // four cells per thread (k3_jacobi_v4) where rows are whole quads; SMK_JACOBI3_QUAD=0 keeps the one-cell-per-thread blocked kernel
-    static const int quad_env = [] { const char *e = getenv("SMK_JACOBI3_QUAD"); return e ? atoi(e) : 1; }();      // 0 never, 1 always, 2 for the 2-sweep launches only
-    const bool quad_ok = vec && (((uintptr_t)p | (uintptr_t)p2 | (uintptr_t)p3 | (uintptr_t)div) & 15) == 0 && g.sc % 4 == 0;
-    const bool quad = quad_ok && quad_env == 1, quad2 = quad_ok && quad_env >= 1;
+    // temporally blocked launches of at most 4 sweeps first, single sweeps for the rest; four cells per thread (k3_jacobi_v4) where rows
+    // are whole aligned quads, otherwise the one-cell-per-thread blocked kernel (k3_jacobi_xt)
+    const bool quad = vec && (((uintptr_t)p | (uintptr_t)p2 | (uintptr_t)p3 | (uintptr_t)div) & 15) == 0 && g.sc % 4 == 0;
     // the launch plan: sweeps per launch.  The result must end in p without a copy.  Two buffers ping-pong, so an even launch count does;
     // an odd count of three or more goes p -> p2 -> p3 -> p2 -> ... -> p through the third buffer (J = 20: five 4-sweep launches); without a
     // third buffer one 4-sweep launch is traded for two 2-sweep ones (round 3's plan: 4 x 4 + 2 x 2)
     int plan[64], n = 0, left = iters;
     const bool blocked = g.B <= 65535;
-    int n4 = (blocked && tmax >= 4) ? left / 4 : 0;
+    int n4 = blocked ? left / 4 : 0;
     if (n4 > 60) n4 = 60;
-    const bool third = p3 != nullptr && getenv("SMK_JACOBI3_THIRD") == nullptr;
+    const bool third = p3 != nullptr;
     if (!third && left % 4 == 0 && (n4 & 1) && n4 * 4 == left) --n4;
     for (int k = 0; k < n4; ++k) plan[n++] = 4;
     left -= 4 * n4;
-    if (blocked && tmax >= 2)
+    if (blocked)
         for (; left >= 2 && n < 62; left -= 2) plan[n++] = 2;
     float *cur = p;
     auto target = [&](int i, int total) -> float * {            // where launch i of `total` writes
@@ -522,7 +516,7 @@ hipError_t launch3_jacobi(const Geom3 &g, float *p, float *p2, float *p3, const 
             if (quad) launch3_jacobi_v4<4>(g, cur, nxt, div, st);
             else launch3_jacobi_xt<4, 64, 16, 2>(g, cur, nxt, div, st);
         } else {
-            if (quad2) launch3_jacobi_v4<2>(g, cur, nxt, div, st);
+            if (quad) launch3_jacobi_v4<2>(g, cur, nxt, div, st);
             else launch3_jacobi_xt<2, 64, 16, 1>(g, cur, nxt, div, st);
         }
         cur = nxt;
@@ -645,107 +639,6 @@ hipError_t launch3_advect(const Geom3 &g, int which, const float *field, float *
         case 3: hipLaunchKernelGGL(k3_advect<3>, grid, block, 0, st, g, field, out, u, v, w, frames, fsb); break;
         default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------- the four advections of a step as ONE launch
-// u <- adv(u2; u2, v2, w2), v <- adv(v2; u, v2, w2), w <- adv(w2; u, v, w2), density <- adv(d2; u, v, w) * 0.995 depend on each other only
-// through the velocity SAMPLING, which happens at integer cell indices where it collapses to 0.5 c[lo] + 0.5 c[hi] (vel3_at).  A
-// workgroup owns a TZ x TY x TX tile of cells; it forms the advected u, v, w on the tile + 1 in z / y / x (what the later fields' samples
-// reach: about 30 % redundant points at 8 x 8 x 32) into LDS, with a workgroup barrier between the fields, then the density and the frame.
-// The displacement-dependent eight-tap gathers read u2, v2, w2, d2 -- inputs of the launch -- straight from global memory (L1 / L2: the
-// taps of neighbouring cells coincide).  HBM traffic: four fields in (tile + halo), four fields + the frame out, instead of seventeen
-// field passes; bit-identical to the four-launch form (same expressions per cell).  The extra row of u (y = H), column of v (x = W) and
-// plane of w (z = D) belong to the last tile along that axis.
-template <int TZ, int TY, int TX>
-__global__ __launch_bounds__(512) void k3_advect_fused(Geom3 g, State3 in, State3 out, float *__restrict__ frames, int64_t fsb) {
-    constexpr int EZ = TZ + 1, EY = TY + 1, EX = TX + 1, NE = EZ * EY * EX;
-    __shared__ float Us[NE], Vs[NE], Ws[NE];
-    const int D = g.D, H = g.H, W = g.W;
-    const int ntx = (W + TX - 1) / TX, nty = (H + TY - 1) / TY, ntz = (D + TZ - 1) / TZ;
-    int bid = blockIdx.x;
-    const int tix = bid % ntx; bid /= ntx;
-    const int tiy = bid % nty; bid /= nty;
-    const int tiz = bid % ntz;
-    const int b = bid / ntz;
-    const int x0 = tix * TX, y0 = tiy * TY, z0 = tiz * TZ;
-    const bool lastx = tix == ntx - 1, lasty = tiy == nty - 1, lastz = tiz == ntz - 1;
-    const float *u2 = in.u + b * g.su, *v2 = in.v + b * g.sv, *w2 = in.w + b * g.sw, *d2 = in.d + b * g.sc;
-    // velocity sample from an LDS tile holding the ADVECTED component: the rule of vel3_at in global indices, the values from the tile
-    auto lds_vel = [&](const float *tile, int Dc, int Hc, int Wc, int step, int z, int y, int x) -> float {
-        if (z > Dc - 2 || y > Hc - 2 || x > Wc - 2) return 0.f;
-        const int o = ((z - z0) * EY + (y - y0)) * EX + (x - x0);
-        return 0.5f * tile[o] + 0.5f * tile[o + step];
-    };
-    // one advected value: field f (extents Df, Hf, Wf, pitch) at (z, y, x) with the three velocity samples given
-    auto advect_at = [&](const float *f, int Df, int Hf, int Wf, int pitch, int z, int y, int x, float ui, float vi, float wi) -> float {
-        const float tx = g.dt * ui, ty = g.dt * vi, tz = g.dt * wi;
-        const float px = clampf3((float)x - tx, 0.f, (float)(Wf - 1));
-        const float py = clampf3((float)y - ty, 0.f, (float)(Hf - 1));
-        const float pz = clampf3((float)z - tz, 0.f, (float)(Df - 1));
-        return interp3(f, Df, Hf, Wf, pitch, pz, py, px);
-    };
-    // ---- u on the tile + 1 (extents D, H+1, W)
-    for (int e = threadIdx.x; e < NE; e += 512) {
-        const int ex = e % EX, ey = (e / EX) % EY, ez = e / (EX * EY);
-        const int x = x0 + ex, y = y0 + ey, z = z0 + ez;
-        float r = 0.f;
-        if (z < D && y <= H && x < W) {
-            const float ui = vel3_at<2>(u2, D, H + 1, W, g.pc, z, y, x), vi = vel3_at<1>(v2, D, H, W + 1, g.pv, z, y, x);
-            const float wi = vel3_at<0>(w2, D + 1, H, W, g.pc, z, y, x);
-            r = advect_at(u2, D, H + 1, W, g.pc, z, y, x, ui, vi, wi);
-            if (ez < TZ && ex < TX && (ey < TY || lasty)) out.u[b * g.su + (z * (H + 1) + y) * g.pc + x] = r;
-        }
-        Us[e] = r;
-    }
-    __syncthreads();
-    // ---- v on the tile + 1 in z, y (and the extra column x = W in the last x tile): extents D, H, W+1
-    for (int e = threadIdx.x; e < NE; e += 512) {
-        const int ex = e % EX, ey = (e / EX) % EY, ez = e / (EX * EY);
-        const int x = x0 + ex, y = y0 + ey, z = z0 + ez;
-        float r = 0.f;
-        if (z < D && y < H && x <= W && (ex < TX || lastx)) {
-            const float ui = lds_vel(Us, D, H + 1, W, 1, z, y, x), vi = vel3_at<1>(v2, D, H, W + 1, g.pv, z, y, x);
-            const float wi = vel3_at<0>(w2, D + 1, H, W, g.pc, z, y, x);
-            r = advect_at(v2, D, H, W + 1, g.pv, z, y, x, ui, vi, wi);
-            if (ez < TZ && ey < TY) out.v[b * g.sv + (z * H + y) * g.pv + x] = r;
-        }
-        Vs[e] = r;
-    }
-    __syncthreads();
-    // ---- w on the tile + 1 in z (the extra plane z = D in the last z tile): extents D+1, H, W
-    for (int e = threadIdx.x; e < NE; e += 512) {
-        const int ex = e % EX, ey = (e / EX) % EY, ez = e / (EX * EY);
-        const int x = x0 + ex, y = y0 + ey, z = z0 + ez;
-        float r = 0.f;
-        if (ex < TX && ey < TY && z <= D && y < H && x < W) {
-            const float ui = lds_vel(Us, D, H + 1, W, 1, z, y, x), vi = lds_vel(Vs, D, H, W + 1, EX, z, y, x);
-            const float wi = vel3_at<0>(w2, D + 1, H, W, g.pc, z, y, x);
-            r = advect_at(w2, D + 1, H, W, g.pc, z, y, x, ui, vi, wi);
-            if (ez < TZ || lastz) out.w[b * g.sw + (z * H + y) * g.pc + x] = r;
-        }
-        Ws[e] = r;
-    }
-    __syncthreads();
-    // ---- density on the tile (+ 0.995 decay, frame)
-    for (int e = threadIdx.x; e < TZ * TY * TX; e += 512) {
-        const int ex = e % TX, ey = (e / TX) % TY, ez = e / (TX * TY);
-        const int x = x0 + ex, y = y0 + ey, z = z0 + ez;
-        if (z >= D || y >= H || x >= W) continue;
-        const float ui = lds_vel(Us, D, H + 1, W, 1, z, y, x), vi = lds_vel(Vs, D, H, W + 1, EX, z, y, x);
-        const float wi = lds_vel(Ws, D + 1, H, W, EX * EY, z, y, x);
-        float r = advect_at(d2, D, H, W, g.pc, z, y, x, ui, vi, wi);
-        r = r * 0.995f;                                       // navier_stokes.py:171
-        if (frames) frames[(size_t)b * fsb + (z * H + y) * W + x] = r;
-        out.d[b * g.sc + (z * H + y) * g.pc + x] = r;
-    }
-}
-
-hipError_t launch3_advect_fused(const Geom3 &g, State3 in, State3 out, float *frames, int64_t fsb, hipStream_t st) {
-    constexpr int TZ = 8, TY = 8, TX = 32;
-    const long long nb = (long long)cdiv(g.W, TX) * cdiv(g.H, TY) * cdiv(g.D, TZ) * g.B;
-    if (nb > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((k3_advect_fused<TZ, TY, TX>), dim3((unsigned)nb), dim3(512), 0, st, g, in, out, frames, fsb);
     return hipGetLastError();
 }
 

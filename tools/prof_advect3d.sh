@@ -1,5 +1,5 @@
 #!/bin/bash
-# SQ counters of the 3-D advection launch inside the configs[4] step (tools/sim3d_only.py); env (SMK_ADVECT3_*) passes through.
+# SQ counters of the 3-D advection launch inside the configs[4] step (tools/sim3d_only.py).
 # usage: tools/prof_advect3d.sh <tag>
 set -u
 TAG=${1:-adv3}
