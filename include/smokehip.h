@@ -554,6 +554,33 @@ int smk_decoder_destroy(smk_decoder *dec);
 int smk_decoder_forward(smk_decoder *dec, const float *tokens, int32_t B, int32_t S, float *tmp1, float *tmp2,
                         float *recon, void *stream);
 
+/* The same head in TRAINING mode, under autograd: its three convolutions alone (the BatchNorms run on smk_bn_relu_pool_* with pool 1, on
+ * batch statistics).  Plain fp32 FMAs; every reduction is per-workgroup partial sums in the caller's workspace added in a fixed order (no
+ * atomics: repeated calls are bit-identical).  Device pointers, enqueued on `stream`.
+ * ConvTranspose2d(CIN, COUT, 4, stride 2, padding 1), weight [CIN][COUT][4][4], bias [COUT] or NULL; x [B][CIN][H][W], or token-major
+ * [B][H*W][CIN] when `tok` != 0 (output_decoder's result, no transpose); z / dz [B][COUT][2H][2W].  Shapes: COUT 16 or 32, CIN a multiple
+ * of 16 (COUT 32) or 32 (COUT 16) up to 4096, H and W multiples of 16, 1 <= B <= 65535 (else SMK_ERR_UNSUPPORTED).
+ *   forward: z = conv(x) + bias, raw (no activation);
+ *   dgrad:   dx = the data gradient from dz, written in the layout `tok` names (dX[c][i][j] = sum over o, ky, kx of
+ *            dz[o][2i-1+ky][2j-1+kx] W[c][o][ky][kx]);
+ *   wgrad:   dw [CIN][COUT][4][4] and db [COUT] (unless NULL) from dz and the saved x; `workspace`: smk_convt4s2_train_wgrad_workspace()
+ *            bytes (0 for an unsupported shape). */
+int smk_convt4s2_train_forward(const float *x, const float *weight, const float *bias, int32_t B, int32_t CIN, int32_t COUT, int32_t H,
+                               int32_t W, int32_t tok, float *z, void *stream);
+int smk_convt4s2_train_dgrad(const float *dz, const float *weight, int32_t B, int32_t CIN, int32_t COUT, int32_t H, int32_t W, int32_t tok,
+                             float *dx, void *stream);
+int64_t smk_convt4s2_train_wgrad_workspace(int32_t B, int32_t CIN, int32_t COUT, int32_t H, int32_t W);
+int smk_convt4s2_train_wgrad(const float *dz, const float *x, int32_t B, int32_t CIN, int32_t COUT, int32_t H, int32_t W, int32_t tok,
+                             float *dw, float *db, void *workspace, void *stream);
+/* Conv2d(16, 1, 3, padding 1) + Sigmoid: x [B][16][H][W] -> y [B][H][W]; H % 8 == 0, W % 32 == 0, 1 <= B <= 65535.  weight [16][3][3],
+ * bias [1] or NULL.  The backward takes dy, the forward's y and x: g = dy y (1 - y), then dx [B][16][H][W], and dw [16][3][3] / db [1]
+ * unless both are NULL; `workspace`: smk_conv3_sigmoid_train_workspace() bytes (g and the partial sums). */
+int smk_conv3_sigmoid_train_forward(const float *x, const float *weight, const float *bias, int32_t B, int32_t H, int32_t W, float *y,
+                                    void *stream);
+int64_t smk_conv3_sigmoid_train_workspace(int32_t B, int32_t H, int32_t W);
+int smk_conv3_sigmoid_train_backward(const float *dy, const float *y, const float *x, const float *weight, int32_t B, int32_t H, int32_t W,
+                                     float *dx, float *dw, float *db, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

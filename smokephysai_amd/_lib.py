@@ -124,6 +124,11 @@ _SIGNATURES = {
     "smk_conv2_train_forward": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
     "smk_conv2_train_dgrad": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
     "smk_conv2_train_wgrad": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "smk_convt4s2_train_forward": [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p, C.c_void_p],
+    "smk_convt4s2_train_dgrad": [C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p, C.c_void_p],
+    "smk_convt4s2_train_wgrad": [C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p] * 4,
+    "smk_conv3_sigmoid_train_forward": [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p],
+    "smk_conv3_sigmoid_train_backward": [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p] * 5,
     "smk_bn_relu_pool_forward": [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p, C.c_double, C.c_int32] + [C.c_void_p] * 6,
     "smk_bn_relu_pool_backward": [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 5,
     "smk_bn_relu_pool_phase": [C.c_int32, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p, C.c_double] + [C.c_void_p] * 3 +
@@ -143,7 +148,8 @@ _SIGNATURES = {
     "smk_linear_forward": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                            C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p],
 }
-EXPORTS = ["smk_abi_version", "smk_last_error", "smk_linear_wgrad_workspace", "smk_bn_train_workspace", "smk_layernorm_bwd_workspace", "smk_conv2_train_workspace", "smk_conv2_train_wgrad_workspace", "smk_conv1_train_wgrad_workspace", "smk_attention_workspace_bytes", "smk_linear_ln_max_rows", "smk_image_quality_workspace"] + list(_SIGNATURES)
+EXPORTS = ["smk_abi_version", "smk_last_error", "smk_linear_wgrad_workspace", "smk_bn_train_workspace", "smk_layernorm_bwd_workspace", "smk_conv2_train_workspace", "smk_conv2_train_wgrad_workspace", "smk_conv1_train_wgrad_workspace", "smk_attention_workspace_bytes", "smk_linear_ln_max_rows", "smk_image_quality_workspace", "smk_convt4s2_train_wgrad_workspace",
+           "smk_conv3_sigmoid_train_workspace"] + list(_SIGNATURES)
 
 _lib = None
 
@@ -193,6 +199,10 @@ def load():
         L.smk_linear_ln_max_rows.restype = C.c_int64
         L.smk_image_quality_workspace.argtypes = [C.c_int32] * 3
         L.smk_image_quality_workspace.restype = C.c_int64
+        L.smk_convt4s2_train_wgrad_workspace.argtypes = [C.c_int32] * 5
+        L.smk_convt4s2_train_wgrad_workspace.restype = C.c_int64
+        L.smk_conv3_sigmoid_train_workspace.argtypes = [C.c_int32] * 3
+        L.smk_conv3_sigmoid_train_workspace.restype = C.c_int64
         for name, args in _SIGNATURES.items():
             fn = getattr(L, name)
             fn.argtypes = args

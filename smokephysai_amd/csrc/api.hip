@@ -10,6 +10,7 @@
 #include "chaos.h"
 #include "conv3d.h"
 #include "decoder.h"
+#include "decoder_train.h"
 #include "elementwise.h"
 #include "encoder.h"
 #include "linear.h"
@@ -1337,6 +1338,71 @@ int smk_conv2_train_wgrad(const float *dz, const float *a1, int32_t B, int32_t H
         return SMK_ERR_UNSUPPORTED;
     }
     return check_launch(launch_conv2_train_wgrad(dz, a1, B, H, W, dw, db, workspace, (hipStream_t)stream), "conv2_train_wgrad");
+}
+
+// ------------------------------------------------------------------ reconstruction head, training (csrc/decoder_train.hip)
+static int convt_train_check(int32_t B, int32_t CIN, int32_t COUT, int32_t H, int32_t W, const char *what) {
+    if (!convt_train_shape_ok(B, CIN, COUT, H, W)) {
+        set_error(std::string(what) + ": COUT 16 or 32, CIN a multiple of 16 (COUT 32) or 32 (COUT 16) up to 4096, H and W multiples of 16, "
+                  "1 <= B <= 65535");
+        return SMK_ERR_UNSUPPORTED;
+    }
+    return SMK_OK;
+}
+
+int smk_convt4s2_train_forward(const float *x, const float *weight, const float *bias, int32_t B, int32_t CIN, int32_t COUT, int32_t H,
+                               int32_t W, int32_t tok, float *z, void *stream) {
+    SMK_REQUIRE(x && weight && z, "null x/weight/z");
+    SMK_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)z & 7) == 0, "alignment");
+    if (int rc = convt_train_check(B, CIN, COUT, H, W, "convt4s2_train_forward")) return rc;
+    return check_launch(launch_convt_train_forward(x, weight, bias, B, CIN, COUT, H, W, tok != 0, z, (hipStream_t)stream), "convt4s2_train_forward");
+}
+
+int smk_convt4s2_train_dgrad(const float *dz, const float *weight, int32_t B, int32_t CIN, int32_t COUT, int32_t H, int32_t W, int32_t tok,
+                             float *dx, void *stream) {
+    SMK_REQUIRE(dz && weight && dx, "null dz/weight/dx");
+    SMK_REQUIRE(((uintptr_t)dx & 15) == 0, "alignment");
+    if (int rc = convt_train_check(B, CIN, COUT, H, W, "convt4s2_train_dgrad")) return rc;
+    return check_launch(launch_convt_train_dgrad(dz, weight, B, CIN, COUT, H, W, tok != 0, dx, (hipStream_t)stream), "convt4s2_train_dgrad");
+}
+
+int64_t smk_convt4s2_train_wgrad_workspace(int32_t B, int32_t CIN, int32_t COUT, int32_t H, int32_t W) {
+    return (int64_t)convt_train_wgrad_workspace_bytes(B, CIN, COUT, H, W);
+}
+
+int smk_convt4s2_train_wgrad(const float *dz, const float *x, int32_t B, int32_t CIN, int32_t COUT, int32_t H, int32_t W, int32_t tok,
+                             float *dw, float *db, void *workspace, void *stream) {
+    SMK_REQUIRE(dz && x && dw && workspace, "null dz/x/dw/workspace");
+    SMK_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)workspace & 15) == 0, "alignment");
+    if (int rc = convt_train_check(B, CIN, COUT, H, W, "convt4s2_train_wgrad")) return rc;
+    return check_launch(launch_convt_train_wgrad(dz, x, B, CIN, COUT, H, W, tok != 0, dw, db, workspace, (hipStream_t)stream),
+                        "convt4s2_train_wgrad");
+}
+
+static int conv3_train_check(int32_t B, int32_t H, int32_t W, const char *what) {
+    if (!conv3_train_shape_ok(B, H, W)) {
+        set_error(std::string(what) + ": H a multiple of 8, W a multiple of 32, 1 <= B <= 65535");
+        return SMK_ERR_UNSUPPORTED;
+    }
+    return SMK_OK;
+}
+
+int smk_conv3_sigmoid_train_forward(const float *x, const float *weight, const float *bias, int32_t B, int32_t H, int32_t W, float *y,
+                                    void *stream) {
+    SMK_REQUIRE(x && weight && y, "null x/weight/y");
+    if (int rc = conv3_train_check(B, H, W, "conv3_sigmoid_train_forward")) return rc;
+    return check_launch(launch_conv3_sigmoid_train_forward(x, weight, bias, B, H, W, y, (hipStream_t)stream), "conv3_sigmoid_train_forward");
+}
+
+int64_t smk_conv3_sigmoid_train_workspace(int32_t B, int32_t H, int32_t W) { return (int64_t)conv3_sigmoid_train_workspace_bytes(B, H, W); }
+
+int smk_conv3_sigmoid_train_backward(const float *dy, const float *y, const float *x, const float *weight, int32_t B, int32_t H, int32_t W,
+                                     float *dx, float *dw, float *db, void *workspace, void *stream) {
+    SMK_REQUIRE(dy && y && x && weight && dx && workspace, "null dy/y/x/weight/dx/workspace");
+    SMK_REQUIRE(((uintptr_t)workspace & 15) == 0, "alignment");
+    if (int rc = conv3_train_check(B, H, W, "conv3_sigmoid_train_backward")) return rc;
+    return check_launch(launch_conv3_sigmoid_train_backward(dy, y, x, weight, B, H, W, dx, dw, db, workspace, (hipStream_t)stream),
+                        "conv3_sigmoid_train_backward");
 }
 
 int64_t smk_bn_train_workspace(int32_t B, int32_t C, int32_t H, int32_t W, int32_t pool) {

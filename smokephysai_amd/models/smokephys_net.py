@@ -9,7 +9,8 @@ attention on its split-bf16 flash kernel (csrc/transformer.hip, chaos term folde
 reconstruction head (csrc/decoder.hip, BatchNorms folded) on their own kernels; only the 3-element physics head and the
 token mean are PyTorch-ROCm ops.
 Training (train mode): the encoder runs as autograd-tracked PyTorch ops with batch-statistics BatchNorm, exactly the
-reference's op sequence (smokephys_net.py:87-91).
+reference's op sequence (smokephys_net.py:87-91).  With head_train="hip" the reconstruction head trains on libsmokehip too
+(models/decoder_train.py): its three convolutions and two BatchNorms, forward and backward, with no MIOpen call.
 """
 import os
 import warnings
@@ -22,6 +23,7 @@ import torch.nn.functional as F
 from .attention import hip_layernorm_supported, hip_layernorm_train
 from .chaos_attention import ChaosAttention
 from .decoder import HipDecoder, decoder_weight_dict, hip_decoder_supported
+from .decoder_train import hip_head_train, hip_head_train_supported
 from .encoder import HipEncoder, encoder_weight_dict
 from .hip_body import HipBody
 from .ffn import hip_dropout_add, hip_ffn_elementwise_supported, hip_gelu_dropout
@@ -80,7 +82,7 @@ def _mlp(din: int, dhid: int, dout: int, linear=nn.Linear) -> nn.Sequential:
 class SmokePhysNet(nn.Module):
     def __init__(self, input_dim: int = 128, hidden_dim: int = 512, num_layers: int = 6, num_heads: int = 8,
                  output_channels: int = 64, chaos_strength: float = 0.1, encoder_dtype: str = "bf16x3",
-                 linear_dtype: str = "bf16x3"):
+                 linear_dtype: str = "bf16x3", head_train: str = "torch"):
         super().__init__()
         self.input_dim = input_dim
         self.hidden_dim = hidden_dim
@@ -89,6 +91,7 @@ class SmokePhysNet(nn.Module):
         if linear_dtype not in ("bf16x3", "f32"):
             raise ValueError("linear_dtype: 'bf16x3' (libsmokehip split-bf16 MFMA kernel) or 'f32' (PyTorch-ROCm GEMMs)")
         self.linear_dtype = linear_dtype
+        self.head_train = head_train
         # Construction order and Sequential indices follow the reference exactly: that fixes both the state_dict keys
         # (input_encoder.{0,1,3,4}, reconstruction_head.{0,1,3,4,6}, ...) and the RNG stream of the default initialisation.
         self.input_encoder = nn.Sequential(*_conv_block(1, 64, 7), *_conv_block(64, 128, 3),
@@ -110,6 +113,18 @@ class SmokePhysNet(nn.Module):
         for m in self.modules():
             if isinstance(m, (TrainableHipLinear, ChaosAttention, ChaosTransformerLayer)):
                 m.hip_train = linear_dtype == "bf16x3"
+
+    # training route of reconstruction_head: "torch" (default) the PyTorch modules (MIOpen convolutions and BatchNorms); "hip" the
+    # libsmokehip kernels of models/decoder_train.py wherever hip_head_train_supported holds (deterministic, no MIOpen)
+    @property
+    def head_train(self) -> str:
+        return self.__dict__.get("_head_train", "torch")
+
+    @head_train.setter
+    def head_train(self, value: str) -> None:
+        if value not in ("torch", "hip"):
+            raise ValueError(f"head_train: 'torch' (PyTorch modules) or 'hip' (libsmokehip kernels), not {value!r}")
+        self.__dict__["_head_train"] = value
 
     # copy.deepcopy / pickling of the module: the libsmokehip handles are per-instance device mirrors, rebuilt on first use
     def __getstate__(self):
@@ -332,7 +347,9 @@ class SmokePhysNet(nn.Module):
             for li, layer in enumerate(self.chaos_layers):
                 features = layer(features, noise=None if chaos_noise is None else chaos_noise[li])
             output_features = self.output_decoder(features)
-        if (not self.training and not torch.is_grad_enabled() and self.linear_dtype == "bf16x3" and output_features.is_cuda
+        if self.training and self.head_train == "hip" and hip_head_train_supported(self.reconstruction_head, output_features):
+            reconstructed = hip_head_train(self.reconstruction_head, output_features)      # tokens read in place, no transpose
+        elif (not self.training and not torch.is_grad_enabled() and self.linear_dtype == "bf16x3" and output_features.is_cuda
                 and output_features.dtype == torch.float32 and output_features.shape[2] == 64
                 and hip_decoder_supported(self.reconstruction_head, pool_size)):
             reconstructed = self.hip_decoder()(output_features)           # 3 fused launches, BN folded

@@ -138,6 +138,16 @@ def validate_epoch(model: nn.Module, val_loader: DataLoader, physics_regularizer
     return dict(zip(("total_loss", "recon_loss", "physics_loss", "chaos_loss"), avg))
 
 
+def build_model(config: dict):
+    """SmokePhysNet from the config's `model` section and the optional `mi355x` keys (encoder_dtype, recon_head), on the CPU."""
+    from smokephysai_amd.models.smokephys_net import SmokePhysNet
+    hw = config.get("mi355x", {}) or {}
+    return SmokePhysNet(input_dim=config["model"]["input_dim"], hidden_dim=config["model"]["hidden_dim"],
+                        num_layers=config["model"]["num_layers"], num_heads=config["model"]["num_heads"],
+                        chaos_strength=config["model"]["chaos_strength"],
+                        encoder_dtype=hw.get("encoder_dtype", "bf16x3"), head_train=str(hw.get("recon_head", "torch")))
+
+
 def main():
     parser = argparse.ArgumentParser(description="SmokePhysAI Training")
     parser.add_argument("--config", type=str, default="config/config.yaml", help="Path to config file")
@@ -148,7 +158,8 @@ def main():
     if hw.get("deterministic", False):
         # run-to-run reproducible steps: MIOpen's default backward-weights solvers for the reconstruction head's three convolutions
         # accumulate with atomics (the only non-reproducible op of the step: tools/rccl_diag.py); this restricts MIOpen to its
-        # deterministic solvers.  Every libsmokehip kernel is deterministic either way.
+        # deterministic solvers.  Every libsmokehip kernel is deterministic either way: with mi355x.recon_head = hip the head runs on
+        # libsmokehip (models/decoder_train.py) and the step is reproducible without this flag.
         torch.backends.cudnn.deterministic = True
         torch.backends.cudnn.benchmark = False
         # ... and keeps what MIOpen finds under that restriction out of the account's ordinary find-db (utils/miopen_db.py: a later
@@ -164,11 +175,7 @@ def main():
         cache_dir=config["data"]["cache_dir"], sim_batch=hw.get("sim_batch", 64),
         jacobi_iters=hw.get("jacobi_iters", 20), rank=rank, world=world)
 
-    from smokephysai_amd.models.smokephys_net import SmokePhysNet
-    model = SmokePhysNet(input_dim=config["model"]["input_dim"], hidden_dim=config["model"]["hidden_dim"],
-                         num_layers=config["model"]["num_layers"], num_heads=config["model"]["num_heads"],
-                         chaos_strength=config["model"]["chaos_strength"],
-                         encoder_dtype=hw.get("encoder_dtype", "bf16x3")).to(device)
+    model = build_model(config).to(device)
     physics_regularizer = PhysicsRegularizer(conservation_weight=config["physics"]["conservation_weight"],
                                              continuity_weight=config["physics"]["continuity_weight"],
                                              energy_weight=config["physics"]["energy_weight"])
