@@ -805,22 +805,36 @@ hipError_t launch_attention_bwd_x3(const AttnBwdArgs &a, hipStream_t st) {
 // nn.LayerNorm over the last dimension (smokephys_net.py:149-150,161,165; eps 1e-5, biased variance): one wave per token row,
 // the row held in registers (D <= 2048: up to 8 float4 per lane), mean and centred second moment by wave reductions, one
 // read and one write of the row -- an HBM-bound stream.
+// The row is shifted by a pivot, its first element, before anything is summed: a plain fp32 sum of x loses the digits of a row whose
+// mean dwarfs its spread (-300 + 0.01 randn: up to 8e-4 of y), the sum of x - pivot does not.  `mean` below is mean - pivot and v holds
+// x - pivot, so x - mean is formed as (x - pivot) - (mean - pivot).  k_layernorm_bwd repeats this arithmetic exactly (ln_pivot).
+template <int NV>
+__device__ __forceinline__ float ln_pivot(float4 (&v)[NV], int lane, int D) {
+    const float p = __shfl(v[0].x, 0);                       // x[row][0] (D >= 4: lane 0's first float4 is always loaded)
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+        if ((i * 64 + lane) * 4 < D) {
+            v[i] = make_float4(v[i].x - p, v[i].y - p, v[i].z - p, v[i].w - p);
+            sum += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+        }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    return sum;
+}
+
 template <int NV>   // float4 per lane
 __global__ __launch_bounds__(256) void k_layernorm(const LayerNormArgs a) {
     const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= a.rows) return;
     const float *xp = a.x + (long long)row * a.ldx;
     float4 v[NV];
-    float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         const int c = (i * 64 + lane) * 4;
         v[i] = c < a.D ? *reinterpret_cast<const float4 *>(xp + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-        sum += (v[i].x + v[i].y) + (v[i].z + v[i].w);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-    const float mean = sum / (float)a.D;
+    const float mean = ln_pivot(v, lane, a.D) / (float)a.D;
     float sq = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -878,18 +892,14 @@ __global__ __launch_bounds__(256) void k_layernorm_bwd(const LayerNormBwdArgs a)
     for (int row = blockIdx.x * 4 + wave; row < a.rows; row += gridDim.x * 4) {
         const float *xp = a.x + (long long)row * a.ldx, *gp = a.dy + (long long)row * a.lddy;
         float4 v[NV], g[NV];
-        float sum = 0.f;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int c = (i * 64 + lane) * 4;
             const bool ok = c < a.D;
             v[i] = ok ? *reinterpret_cast<const float4 *>(xp + c) : make_float4(0.f, 0.f, 0.f, 0.f);
             g[i] = ok ? *reinterpret_cast<const float4 *>(gp + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-            sum += (v[i].x + v[i].y) + (v[i].z + v[i].w);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-        const float mean = sum * invD;
+        const float mean = ln_pivot(v, lane, a.D) / (float)a.D;   // mean - pivot, v = x - pivot: the forward's statistics, bit for bit
         float sq = 0.f;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
@@ -901,7 +911,7 @@ __global__ __launch_bounds__(256) void k_layernorm_bwd(const LayerNormBwdArgs a)
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
-        const float rstd = 1.0f / sqrtf(sq * invD + a.eps);
+        const float rstd = 1.0f / sqrtf(sq / (float)a.D + a.eps);
         float s1 = 0.f, s2 = 0.f;                              // sum(g w), sum(g w xhat)
 #pragma unroll
         for (int i = 0; i < NV; ++i) {

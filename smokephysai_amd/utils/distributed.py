@@ -175,6 +175,19 @@ def wrap_ddp(model: torch.nn.Module, device, sync_bn: bool = False, grad_exchang
     return ddp
 
 
+def clip_grad_norm_(parameters, max_norm: float) -> torch.Tensor:
+    """torch.nn.utils.clip_grad_norm_ (2-norm) whose total norm does not depend on where the gradients live.  torch's foreach norm sums
+    a tensor whose storage is 16-byte aligned in another order than one that is not, and DDP's bucket views (gradient_as_bucket_view)
+    start wherever the previous gradient ended: a one-rank DDP step could clip by a norm one ulp away from the unwrapped step's.
+    Unaligned gradients are measured on an aligned copy; aligned ones (every gradient of an unwrapped model) as they are, so the
+    result is bit for bit torch's wherever torch's is layout-independent.  The scaling is elementwise, the same on any layout."""
+    params = [p for p in parameters if p.grad is not None]
+    grads = [p.grad if p.grad.data_ptr() % 16 == 0 else p.grad.clone() for p in params]
+    total = torch.nn.utils.get_total_norm(grads, 2.0)
+    torch.nn.utils.clip_grads_with_norm_(params, max_norm, total)
+    return total
+
+
 def ddp_bucket_report(ddp) -> dict:
     """What the gradient exchange of one step looks like: the reducer's bucket sizes (bytes, in all-reduce launch order)
     and the collective backend.  Empty for an unwrapped (single-process) model."""

@@ -10,7 +10,7 @@ import torch.nn.functional as F
 
 from smokephysai_amd.models import PhysicsRegularizer, SmokePhysNet
 from smokephysai_amd.utils.data_loader import draw_source_configs
-from smokephysai_amd.utils.distributed import shard_range
+from smokephysai_amd.utils.distributed import clip_grad_norm_, shard_range
 
 
 def test_shard_range_partitions():
@@ -21,6 +21,32 @@ def test_shard_range_partitions():
             assert all(blocks[i][1] == blocks[i + 1][0] for i in range(world - 1))
             sizes = [b - a for a, b in blocks]
             assert max(sizes) - min(sizes) <= 1
+
+
+def test_clip_grad_norm_equals_torch_and_ignores_where_gradients_live():
+    """train.py's clip: torch.nn.utils.clip_grad_norm_ bit for bit on separately allocated gradients, and the same bits when the gradients
+    are views into one flat buffer at offsets that are not 16-byte aligned (DDP's bucket views)."""
+    g = torch.Generator().manual_seed(0)
+    sizes = (5, 1000, 37, 4096, 3)
+    grads = [torch.randn(n, generator=g) * 3 for n in sizes]
+
+    def params(gs):
+        ps = [torch.nn.Parameter(torch.zeros(n)) for n in sizes]
+        for p, gr in zip(ps, gs):
+            p.grad = gr
+        return ps
+    a, b = params([x.clone() for x in grads]), params([x.clone() for x in grads])
+    na, nb = clip_grad_norm_(a, 1.0), torch.nn.utils.clip_grad_norm_(b, 1.0)
+    assert torch.equal(na, nb) and all(torch.equal(p.grad, q.grad) for p, q in zip(a, b))
+    flat = torch.zeros(sum(sizes) + 1)
+    views, o = [], 1
+    for x in grads:
+        views.append(flat[o:o + x.numel()])
+        views[-1].copy_(x)
+        o += x.numel()
+    c = params(views)
+    assert any(v.data_ptr() % 16 for v in views)
+    assert torch.equal(clip_grad_norm_(c, 1.0), na) and all(torch.equal(p.grad, q.grad) for p, q in zip(c, a))
 
 
 @pytest.mark.parametrize("N,nsamp", [(64, 2), (128, 1)])

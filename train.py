@@ -23,8 +23,8 @@ from tqdm import tqdm
 
 from smokephysai_amd.models.physics_regularizer import PhysicsRegularizer
 from smokephysai_amd.utils.data_loader import create_data_loaders
-from smokephysai_amd.utils.distributed import (all_reduce_weighted_mean, ddp_bucket_report, init_distributed, max_over_ranks,
-                                               wrap_ddp)
+from smokephysai_amd.utils.distributed import (all_reduce_weighted_mean, clip_grad_norm_, ddp_bucket_report, init_distributed,
+                                               max_over_ranks, wrap_ddp)
 
 
 class _NullWriter:
@@ -105,7 +105,7 @@ def train_epoch(model: nn.Module, train_loader: DataLoader, optimizer: optim.Opt
         optimizer.zero_grad()
         total, recon, phys, chaos = batch_losses(model, physics_regularizer, batch, device)
         total.backward()                      # DDP: bucketed RCCL all-reduce (mean over ranks) overlaps this backward
-        torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm=1.0)
+        clip_grad_norm_(model.parameters(), max_norm=1.0)     # (= torch's; layout-independent under DDP's bucket views)
         optimizer.step()
         vals = [total.item(), recon.item(), phys.item(), chaos.item()]
         n = int(batch["input"].shape[0])
