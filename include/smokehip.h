@@ -218,6 +218,19 @@ int smk_chaos_stats(const float *frames, int64_t frame_stride, int32_t n, int32_
 /* ||frame[i+1] - frame[i]||_2 for i < n-1 (smoke_simulator.py:73-79) -> norms [n-1] fp32 (fp64 accumulation). */
 int smk_frame_diff_norms(const float *frames, int64_t frame_stride, int32_t n, int32_t H, int32_t W, float *norms,
                          void *stream);
+/* SmokeSimulator.get_chaos_features' scalar formulas (smoke_simulator.py:67-87, 116-122, 136-140) on the results of the two calls
+ * above over one stream of S frames: norms [S-1] (may be NULL when S == 1), box_counts [S][5], hist [S][256] (16-byte aligned).
+ * Row k < F names the stream frame pos[k] and the history length hist_len[k] the reference's simulator would hold at that frame
+ * (int32 device arrays, never read on the host).  features [F][3] fp64 = (lyapunov, fractal dimension, entropy):
+ *   lyapunov = 0 when hist_len < 20, else max(0, mean of the 18 differences of log(norms[pos-19 .. pos-1] + 1e-8));
+ *   fractal dimension = |least-squares slope| of log(count + 1) over log(2, 4, 8, 16, 32);
+ *   entropy = -sum p log2(p + 1e-8), p = count / total (NaN for an empty histogram, as 0/0 in the reference).
+ * All arithmetic in fp64, fixed summation order (bit-reproducible).  A row with pos outside [0, S) gets three NaNs, a row with
+ * hist_len >= 20 and pos < 19 a NaN lyapunov; nothing outside the arrays is read.  n_groups > 0 (must divide F): also
+ * means [n_groups][3] = the mean of each F / n_groups consecutive rows, added in ascending row order (the per-sample label of
+ * data_loader.py:71-88); n_groups == 0: means is not touched and may be NULL.  One launch. */
+int smk_chaos_features(const float *norms, const int32_t *box_counts, const int32_t *hist, int32_t S, const int32_t *pos,
+                       const int32_t *hist_len, int32_t F, int32_t n_groups, double *features, double *means, void *stream);
 
 /* RobustnessEvaluator.compute_ssim's SSIM map and F.mse_loss's squared error (robustness_metrics.py:76-103) for n fp32 planes [H][W]
  * (dense rows; plane strides pred_stride / target_stride floats), summed per plane in fp64 in a fixed order (bit-reproducible):

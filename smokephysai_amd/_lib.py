@@ -88,6 +88,8 @@ _SIGNATURES = {
     "smk_chaos_stats": [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                         C.c_void_p],
     "smk_frame_diff_norms": [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p],
+    "smk_chaos_features": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                           C.c_void_p, C.c_void_p],
     "smk_image_quality": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                           C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
     "smk_encoder_create": [C.POINTER(SmkEncoderWeights), C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)],

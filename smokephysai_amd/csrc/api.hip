@@ -752,6 +752,16 @@ int smk_frame_diff_norms(const float *frames, int64_t frame_stride, int32_t n, i
     return check_launch(launch_diff_norms(frames, frame_stride, n - 1, H * W, norms, (hipStream_t)stream), "diff_norms");
 }
 
+int smk_chaos_features(const float *norms, const int32_t *box_counts, const int32_t *hist, int32_t S, const int32_t *pos,
+                       const int32_t *hist_len, int32_t F, int32_t n_groups, double *features, double *means, void *stream) {
+    SMK_REQUIRE(box_counts && hist && pos && hist_len && features, "null pointer");
+    SMK_REQUIRE(S >= 1 && F >= 1 && (norms || S == 1), "S >= 1, F >= 1, norms unless S == 1");
+    SMK_REQUIRE(((uintptr_t)hist & 15) == 0 && ((uintptr_t)features & 7) == 0 && ((uintptr_t)means & 7) == 0, "16-byte aligned hist, 8-byte aligned outputs");
+    SMK_REQUIRE(n_groups >= 0 && (n_groups == 0 || (means && F % n_groups == 0)), "n_groups > 0 needs means and must divide F");
+    return check_launch(launch_chaos_features(norms, box_counts, hist, S, pos, hist_len, F, n_groups, features, means,
+                                              (hipStream_t)stream), "chaos_features");
+}
+
 // ------------------------------------------------------------------ image quality (SSIM map + squared error)
 int64_t smk_image_quality_workspace(int32_t n, int32_t H, int32_t W) {
     if (n < 1 || H < 1 || W < 1) return 0;

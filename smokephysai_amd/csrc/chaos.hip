@@ -5,6 +5,8 @@
 //   histogram       : torch.histogram(bins=256, range=(0,1)) counts (:134-135): values outside [0,1] dropped, 1.0 -> last bin
 //   difference norms: ||frame[i+1] - frame[i]||_2 (:73-79), fp64 accumulation
 // One 1024-thread workgroup per frame; wavefront shuffles + LDS for the reductions.
+//   label scalars   : the formulas on those results (:67-87 Lyapunov, :116-122 slope, :136-140 entropy) in fp64, one wave per
+//                     feature row, and the per-sample means of data_loader.py:71-88 (k_chaos_features)
 #include "chaos.h"
 
 namespace smk {
@@ -98,6 +100,97 @@ __global__ __launch_bounds__(1024) void k_diff_norms(const float *__restrict__ f
     if (threadIdx.x == 0) norms[blockIdx.x] = (float)sqrt(t);
 }
 
+// ---- label scalars from the reduction results (no host round trip) ------------------------------------------------------
+// One wave per feature row.  A block owns `rows_per_block` consecutive rows (its waves stride over them); with group means that
+// is one group, and after a barrier threads 0..2 add the group's rows in ascending order.  No float atomics anywhere: every sum
+// has one fixed order, so a call repeats bit for bit.
+__device__ __forceinline__ void chaos_feature_row(const float *__restrict__ norms, const int32_t *__restrict__ box_counts,
+                                                  const int32_t *__restrict__ hist, int S, int pos, int hist_len, int lane,
+                                                  double *__restrict__ out) {
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    if (pos < 0 || pos >= S) {                      // wave-uniform: the row names no frame of the stream
+        if (lane < 3) out[lane] = nan;
+        return;
+    }
+    // entropy: p = count / total, -sum p log2(p + 1e-8); four consecutive bins per lane, then the shuffle tree
+    const int4 c = *reinterpret_cast<const int4 *>(hist + (size_t)pos * 256 + 4 * lane);
+    long long tot = (long long)c.x + c.y + c.z + c.w;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off);      // integers: exact, the same in every lane
+    const double total = (double)tot;                                        // 0 -> 0/0 = NaN, as the host formula
+    const double p0 = (double)c.x / total, p1 = (double)c.y / total, p2 = (double)c.z / total, p3 = (double)c.w / total;
+    double e = p0 * log2(p0 + 1e-8);
+    e += p1 * log2(p1 + 1e-8);
+    e += p2 * log2(p2 + 1e-8);
+    e += p3 * log2(p3 + 1e-8);
+    e = -wave_sum(e);                                                        // valid in lane 0
+
+    // fractal dimension: |slope| of the least-squares line through (log s, log(count_s + 1)), s = 2..32, centred closed form
+    double x = 0.0, y = 0.0;
+    if (lane < 5) {
+        x = log((double)(2 << lane));
+        y = log((double)box_counts[(size_t)pos * 5 + lane] + 1.0);
+    }
+    double xs[5], ys[5], xm = 0.0, ym = 0.0;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        xs[i] = __shfl(x, i);
+        ys[i] = __shfl(y, i);
+        xm += xs[i];
+        ym += ys[i];
+    }
+    xm /= 5.0;
+    ym /= 5.0;
+    double sxy = 0.0, sxx = 0.0;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        sxy += (xs[i] - xm) * (ys[i] - ym);
+        sxx += (xs[i] - xm) * (xs[i] - xm);
+    }
+    const double slope = fabs(sxy / sxx);
+
+    // Lyapunov: 0 below 20 frames of history, else max(0, mean of the 18 log-ratios of the last 19 distances), summed in
+    // ascending order and NOT telescoped (the host formula rounds every difference)
+    double lyap = 0.0;
+    if (hist_len >= 20) {                           // wave-uniform
+        if (pos < 19) {
+            lyap = nan;                             // the caller's error: the window would start before the stream
+        } else {
+            double l = 0.0;
+            if (lane < 19) l = log((double)norms[pos - 19 + lane] + 1e-8);   // norms[pos-19 .. pos-1], pos - 1 <= S - 2
+            const double d = __shfl_down(l, 1) - l;                          // lanes 0..17
+            double s = 0.0;
+#pragma unroll
+            for (int i = 0; i < 18; ++i) s += __shfl(d, i);
+            s /= 18.0;
+            lyap = s > 0.0 ? s : 0.0;
+        }
+    }
+    if (lane == 0) {
+        out[0] = lyap;
+        out[1] = slope;
+        out[2] = e;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_chaos_features(const float *__restrict__ norms, const int32_t *__restrict__ box_counts,
+                                                        const int32_t *__restrict__ hist, int S, const int32_t *__restrict__ pos,
+                                                        const int32_t *__restrict__ hist_len, int F, int rows_per_block,
+                                                        double *features, double *__restrict__ means) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r0 = blockIdx.x * rows_per_block;
+    const int r1 = r0 + rows_per_block < F ? r0 + rows_per_block : F;
+    for (int k = r0 + wave; k < r1; k += 4)
+        chaos_feature_row(norms, box_counts, hist, S, pos[k], hist_len[k], lane, features + (size_t)k * 3);
+    if (means == nullptr) return;                   // kernel argument: uniform over the grid
+    __syncthreads();                                // the block's own global writes are visible to it past the barrier
+    if (threadIdx.x < 3) {
+        double s = 0.0;
+        for (int k = r0; k < r1; ++k) s += features[(size_t)k * 3 + threadIdx.x];
+        means[(size_t)blockIdx.x * 3 + threadIdx.x] = s / (double)(r1 - r0);
+    }
+}
+
 hipError_t launch_chaos_stats(const float *frames, int64_t stride, int n, int H, int W, float *means, int32_t *box_counts,
                               int32_t *hist, hipStream_t st) {
     const size_t lds = (size_t)(H / 2) * (W / 2);
@@ -107,6 +200,15 @@ hipError_t launch_chaos_stats(const float *frames, int64_t stride, int n, int H,
 
 hipError_t launch_diff_norms(const float *frames, int64_t stride, int n_pairs, int n_cells, float *norms, hipStream_t st) {
     hipLaunchKernelGGL(k_diff_norms, dim3(n_pairs), dim3(1024), 0, st, frames, stride, n_cells, norms);
+    return hipGetLastError();
+}
+
+hipError_t launch_chaos_features(const float *norms, const int32_t *box_counts, const int32_t *hist, int S, const int32_t *pos,
+                                 const int32_t *hist_len, int F, int n_groups, double *features, double *means, hipStream_t st) {
+    const int rows = n_groups > 0 ? F / n_groups : 4;                       // one group per block, else one row per wave
+    const int blocks = n_groups > 0 ? n_groups : (F + 3) / 4;
+    hipLaunchKernelGGL(k_chaos_features, dim3(blocks), dim3(256), 0, st, norms, box_counts, hist, S, pos, hist_len, F, rows, features,
+                       n_groups > 0 ? means : nullptr);
     return hipGetLastError();
 }
 

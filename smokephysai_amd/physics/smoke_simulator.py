@@ -3,7 +3,8 @@
 simulate_step = one fused stencil step of the batched solver; the fractal perturbation is applied to the emitted
 frame only (the solver keeps the unperturbed density, smoke_simulator.py:36-39) inside the density-advect kernel.
 The chaos statistics (smoke_simulator.py:47-140) use the HIP reductions of csrc/chaos.hip (mean, box counts, histogram,
-frame-difference norms); only the scalar formulas on their results run on the host, as in the reference.
+frame-difference norms); the scalar formulas on their results run on the host, as in the reference, or -- for callers that want
+the labels as tensors -- on the device (chaos_features_device, get_chaos_features(as_tensor=True)).
 """
 from typing import Optional
 
@@ -27,6 +28,7 @@ class SmokeSimulator(nn.Module):
         self.batch_size = batch_size
         self.history = []          # smoke_simulator.py:22-24
         self.max_history = 100
+        self._feature_rows = {}    # (grids, frames per grid, history length) -> (pos, hist_len) device tensors of get_chaos_features(as_tensor=True)
 
     def add_incense_source(self, positions: list, intensities: list, grid: Optional[int] = None):
         """smoke_simulator.py:26-29 (radius 8).  Batched: `grid` selects the grid, None = every grid."""
@@ -55,11 +57,17 @@ class SmokeSimulator(nn.Module):
         return out
 
     # ---- chaos statistics (smoke_simulator.py:47-140) -------------------------------------------------------
-    def get_chaos_features(self):
-        """Un-batched: the reference's dict (or {} with fewer than 10 frames).  Batched: a list with one dict per grid."""
+    def get_chaos_features(self, as_tensor: bool = False):
+        """Un-batched: the reference's dict (or {} with fewer than 10 frames).  Batched: a list with one dict per grid.
+        as_tensor=True: (lyapunov, fractal dimension, entropy) as an fp64 device tensor instead, [B,3] batched / [3] un-batched,
+        None with fewer than 10 frames; the formulas run on the device and nothing is copied to the host."""
         if len(self.history) < 10:
+            if as_tensor:
+                return None
             return {} if self.batch_size is None else [{} for _ in range(self.ns_solver._B)]
-        self.ns_solver.check()     # the statistics go to the host: the frames behind them must be real
+        self.ns_solver.check()     # the statistics leave the simulator: the frames behind them must be real
+        if as_tensor:
+            return self._chaos_features_tensor()
         if self.batch_size is None:
             return {"lyapunov_exponent": self.compute_lyapunov_exponent(),
                     "fractal_dimension": self.compute_fractal_dimension(),
@@ -75,6 +83,23 @@ class SmokeSimulator(nn.Module):
             lyap = [lyapunov_from_norms(d[20 * b:20 * b + 19]) for b in range(cur.shape[0])]
         return [{"lyapunov_exponent": lyap[b], "fractal_dimension": fractal_dimension_from_counts(box[b]),
                  "entropy": entropy_from_hist(hist[b])} for b in range(cur.shape[0])]
+
+    def _chaos_features_tensor(self) -> torch.Tensor:
+        B = self.ns_solver._B
+        n = 20 if len(self.history) >= 20 else 1                        # frames per grid the formulas look at
+        hist_len = min(len(self.history), 20)                            # the formulas only ask "below 20?"
+        states = torch.stack(self.history[-n:], dim=-3)                  # [B,n,H,W] ([n,H,W] un-batched): one flat stream, grid after grid
+        stream = states.view(-1, *states.shape[-2:])
+        key = (B, n, hist_len)
+        if key not in self._feature_rows:
+            pos = torch.arange(n - 1, B * n, n, dtype=torch.int32, device=stream.device)     # each grid's newest frame
+            self._feature_rows[key] = (pos, torch.full_like(pos, hist_len))
+        # smk_chaos_features indexes all three results by one stream position, so both reductions run over the whole stream: the pair
+        # (last frame of grid b, first of b+1) and the statistics of the 19 older frames per grid are computed and never read (microseconds)
+        norms = frame_diff_norms(stream) if B * n > 1 else None
+        _, box, hist = chaos_stats(stream)
+        feats = chaos_features_device(norms, box, hist, *self._feature_rows[key])
+        return feats if self.batch_size is not None else feats[0]
 
     def _single_grid(self, what):
         if self.batch_size is not None:
@@ -126,6 +151,33 @@ def frame_diff_norms(frames: torch.Tensor) -> torch.Tensor:
     out = torch.empty(n - 1, device=dev)
     _lib.check(_lib.load().smk_frame_diff_norms(f.data_ptr(), f.stride(0), n, h, w, out.data_ptr(), _lib.stream_ptr(dev)))
     return out
+
+
+def chaos_features_device(norms: Optional[torch.Tensor], box: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor,
+                          hist_len: torch.Tensor, groups: Optional[int] = None):
+    """The label scalars of smoke_simulator.py:47-140 on the device, from frame_diff_norms' [S-1] and chaos_stats' [S,5] / [S,256]
+    over one stream of S frames.  Row k reads frame pos[k] of the stream with the history length hist_len[k] the reference's
+    simulator would hold there (int32 device tensors [F]).  Returns features [F,3] fp64 = (lyapunov, fractal dimension, entropy);
+    with groups=g (g divides F) also means [g,3], the mean over each F/g consecutive rows.  One launch, no copy to the host."""
+    dev = _lib.require_cuda(box.device, "chaos_features_device")
+    S, F = box.shape[0], pos.shape[0]
+    if tuple(box.shape) != (S, 5) or tuple(hist.shape) != (S, 256) or box.dtype != torch.int32 or hist.dtype != torch.int32:
+        raise ValueError("box must be int32 [S,5] and hist int32 [S,256] (chaos_stats' outputs)")
+    if norms is not None and (tuple(norms.shape) != (S - 1,) or norms.dtype != torch.float32):
+        raise ValueError(f"norms must be fp32 [S-1] = [{S - 1}] (frame_diff_norms' output)")
+    if pos.dtype != torch.int32 or hist_len.dtype != torch.int32 or tuple(hist_len.shape) != (F,) or pos.dim() != 1:
+        raise ValueError("pos and hist_len must be int32 [F]")
+    if groups is not None and (groups < 1 or F % groups):
+        raise ValueError(f"groups={groups} must divide the {F} feature rows")
+    args = [t.contiguous() if t is not None else None for t in (norms, box, hist, pos, hist_len)]
+    if any(t is not None and t.device != dev for t in args):
+        raise ValueError("all inputs must live on the same ROCm device")
+    feats = torch.empty(F, 3, dtype=torch.float64, device=dev)
+    means = torch.empty(groups, 3, dtype=torch.float64, device=dev) if groups is not None else None
+    ptr = [t.data_ptr() if t is not None else None for t in args]
+    _lib.check(_lib.load().smk_chaos_features(ptr[0], ptr[1], ptr[2], S, ptr[3], ptr[4], F, groups or 0, feats.data_ptr(),
+                                              means.data_ptr() if means is not None else None, _lib.stream_ptr(dev)))
+    return feats if groups is None else (feats, means)
 
 
 def lyapunov_from_norms(distances) -> float:

@@ -16,8 +16,8 @@ import torch
 from torch.utils.data import DataLoader, Dataset
 
 from .. import _lib
-from ..physics.smoke_simulator import (SmokeSimulator, chaos_stats, entropy_from_hist, fractal_dimension_from_counts,
-                                       frame_diff_norms, lyapunov_from_norms)
+from ..physics.smoke_simulator import (SmokeSimulator, chaos_features_device, chaos_stats, entropy_from_hist,
+                                       fractal_dimension_from_counts, frame_diff_norms, lyapunov_from_norms)
 from .distributed import shard_range
 
 
@@ -95,14 +95,57 @@ def chunk_chaos_labels(buf: torch.Tensor, n_samples: int, T: int, valid_head: in
     return out
 
 
+def chaos_label_rows(n_samples: int, T: int, valid_head: int, start: int = 10) -> Tuple[np.ndarray, np.ndarray]:
+    """The feature rows of a chunk buffer (layout: chunk_chaos_labels) as smk_chaos_features wants them: for sample i and frame
+    t = start..T-1, in that order, the buffer index of the frame and the length of the history the reference's simulator holds
+    once it has appended that frame -- labels_from_stats' `e + 1` with off = min(HIST_TAIL, valid_head + i * T); only "below 10"
+    and "below 20" are ever asked of it, so the cap at HIST_TAIL earlier frames changes nothing.  int32 [n_samples * (T - start)]."""
+    i = np.repeat(np.arange(n_samples), max(T - start, 0))
+    t = np.tile(np.arange(start, T), n_samples)
+    off = np.minimum(HIST_TAIL, valid_head + i * T)
+    return (HIST_TAIL + i * T + t).astype(np.int32), (off + t + 1).astype(np.int32)
+
+
+_LABEL_ROWS = {}     # (n_samples, T, valid_head, start, device) -> chaos_label_rows on that device: built once per shape
+
+
+def chunk_chaos_labels_device(buf: torch.Tensor, n_samples: int, T: int, valid_head: int, start: int = 10) -> torch.Tensor:
+    """chunk_chaos_labels without the host: the same buffer, the same two reductions (the statistics over the whole buffer, so
+    that one frame index serves all three results), then one smk_chaos_features launch for the scalars of every frame
+    t = start..T-1 and their per-sample means.  Returns [n_samples, 3] fp64 on the device (lyapunov, fractal dimension, entropy).
+    start >= 9 only: below that labels_from_stats skips frames whose history is shorter than 10, which is not emulated."""
+    if start < 9:
+        raise ValueError(f"start={start}: frames with fewer than 10 frames of history are skipped by the host route; use start >= 9")
+    if tuple(buf.shape[:1]) != (HIST_TAIL + n_samples * T,) or not 0 <= valid_head <= HIST_TAIL:
+        raise ValueError(f"buf must hold HIST_TAIL + n_samples * T = {HIST_TAIL + n_samples * T} frames, valid_head in 0..{HIST_TAIL}")
+    dev = _lib.require_cuda(buf.device, "chunk_chaos_labels_device")
+    if T <= start:                                                            # no frame contributes: labels_from_stats' defaults
+        return torch.tensor([[0.0, 1.0, 0.0]], dtype=torch.float64, device=dev).repeat(n_samples, 1)
+    key = (n_samples, T, valid_head, start, dev)
+    if key not in _LABEL_ROWS:
+        _LABEL_ROWS[key] = tuple(torch.from_numpy(a).to(dev) for a in chaos_label_rows(n_samples, T, valid_head, start))
+    norms = frame_diff_norms(buf)
+    _, box, hist = chaos_stats(buf)              # the HIST_TAIL head frames too (never read by a row): one index for all results
+    return chaos_features_device(norms, box, hist, *_LABEL_ROWS[key], groups=n_samples)[1]
+
+
+_LABEL_KEYS = ("lyapunov_exponent", "fractal_dimension", "entropy")
+
+
 class SyntheticSmokeDataset(Dataset):
     """Same constructor/items as the reference (data_loader.py:13-123).  Extra keyword-only knobs:
     sim_batch (grids per launch), jacobi_iters, storage_device (where sequences are kept; default = device),
-    rank/world (generate and hold only this rank's contiguous block of the global sample list)."""
+    rank/world (generate and hold only this rank's contiguous block of the global sample list),
+    labels ("host": the label formulas run in numpy on copied-back reduction results, as the reference computes them;
+    "device": they run in one HIP launch per chunk and come to the host once, after the last chunk -- same frames, same
+    sources, labels equal to ~1e-6 (entropy is fp32 on the host route); items and caches have the same schema either way)."""
 
     def __init__(self, num_samples: int = 1000, grid_size: Tuple[int, int] = (128, 128), sequence_length: int = 20,
                  device: str = "cuda", cache_path: Optional[str] = None, *, sim_batch: int = 64, jacobi_iters: int = 20,
-                 storage_device: Optional[str] = None, rank: int = 0, world: int = 1):
+                 storage_device: Optional[str] = None, rank: int = 0, world: int = 1, labels: str = "host"):
+        if labels not in ("host", "device"):
+            raise ValueError(f"labels={labels!r}: 'host' or 'device'")
+        self.labels = labels
         self.num_samples = num_samples
         self.grid_size = tuple(grid_size)
         self.sequence_length = sequence_length
@@ -125,6 +168,8 @@ class SyntheticSmokeDataset(Dataset):
                 print(f"Saved synthetic data to {self.cache_path}")
 
     def _generate_synthetic_data(self) -> List[Dict]:
+        if self.labels == "device":
+            return self._generate_device_labels()
         dev = _lib.require_cuda(self.device, "SyntheticSmokeDataset")
         cfgs = draw_source_configs(self.num_samples, self.grid_size)       # every rank draws the full list
         lo, hi = shard_range(self.num_samples, self.rank, self.world)
@@ -155,6 +200,48 @@ class SyntheticSmokeDataset(Dataset):
             tail = buf[HIST_TAIL - valid_head:][-HIST_TAIL:].clone()        # (buf[HIST_TAIL - valid_head:] = every real frame in the buffer)
             valid_head = tail.shape[0]
             del sim
+        return data
+
+    def _generate_device_labels(self) -> List[Dict]:
+        """The generator above with the labels left on the device (chunk_chaos_labels_device): no copy to the host and no host
+        formula per chunk, one [samples, 3] copy at the end.  Same draws, chunks, buffers and stepper calls, so the frames are
+        the host mode's bit for bit.  Also dropped, because they change no result: the simulator is built once per chunk size
+        and zeroed between chunks (setup_grid) instead of created per chunk, and with storage_device == device a sample is a
+        view of its chunk buffer instead of a copy."""
+        dev = _lib.require_cuda(self.device, "SyntheticSmokeDataset")
+        cfgs = draw_source_configs(self.num_samples, self.grid_size)
+        lo, hi = shard_range(self.num_samples, self.rank, self.world)
+        first = max(lo - 1, 0)
+        T = self.sequence_length
+        H, W = self.grid_size
+        in_place = torch.device(self.storage_device) == dev or str(self.storage_device) == str(self.device)
+        data, chunk_labels, sims = [], [], {}
+        tail, valid_head = None, 0
+        for c0 in range(first, hi, self.sim_batch):
+            c1 = min(c0 + self.sim_batch, hi)
+            n = c1 - c0
+            if n in sims:
+                sim = sims[n]
+                sim.ns_solver.setup_grid()
+            else:
+                sim = sims[n] = SmokeSimulator(self.grid_size, device=dev, batch_size=n, jacobi_iters=self.jacobi_iters)
+            sim.ns_solver.add_smoke_sources([(i - c0, x, y, 8, inten) for i in range(c0, c1)
+                                             for (x, y), inten in zip(cfgs[i]["positions"], cfgs[i]["intensities"])])
+            buf = torch.empty(HIST_TAIL + n * T, H, W, device=dev)
+            if tail is not None:
+                buf[HIST_TAIL - tail.shape[0]:HIST_TAIL] = tail
+            seqs = buf[HIST_TAIL:].view(n, T, H, W)
+            sim.simulate_sequence(T, add_fractal=True, out=seqs)
+            chunk_labels.append(chunk_chaos_labels_device(buf, n, T, valid_head)[max(lo - c0, 0):])
+            for i in range(max(c0, lo), c1):
+                seq = seqs[i - c0]
+                data.append({"sequence": seq if in_place else seq.to(self.storage_device).clone(), "chaos_features": None,
+                             "source_config": cfgs[i]})
+            tail = buf[HIST_TAIL - valid_head:][-HIST_TAIL:].clone()
+            valid_head = tail.shape[0]
+        if data:
+            for d, row in zip(data, torch.cat(chunk_labels).cpu().tolist()):     # the one device-to-host copy of the labels
+                d["chaos_features"] = dict(zip(_LABEL_KEYS, row))
         return data
 
     def __len__(self) -> int:

@@ -148,6 +148,15 @@ def build_model(config: dict):
                         encoder_dtype=hw.get("encoder_dtype", "bf16x3"), head_train=str(hw.get("recon_head", "torch")))
 
 
+def data_loader_kwargs(config: dict, rank: int = 0, world: int = 1) -> dict:
+    """create_data_loaders' keyword arguments (all but `device`) from the config's `training` / `data` sections and the optional
+    `mi355x` keys (sim_batch, jacobi_iters, dataset_labels); a missing key or a missing section means the reference-equivalent default."""
+    hw = config.get("mi355x", {}) or {}
+    return dict(batch_size=config["training"]["batch_size"], num_train=config["data"]["num_train"], num_val=config["data"]["num_val"],
+                grid_size=tuple(config["data"]["grid_size"]), cache_dir=config["data"]["cache_dir"], sim_batch=hw.get("sim_batch", 64),
+                jacobi_iters=hw.get("jacobi_iters", 20), labels=str(hw.get("dataset_labels", "host")), rank=rank, world=world)
+
+
 def main():
     parser = argparse.ArgumentParser(description="SmokePhysAI Training")
     parser.add_argument("--config", type=str, default="config/config.yaml", help="Path to config file")
@@ -169,11 +178,7 @@ def main():
     rank, world, local_rank = init_distributed()
     exp_dir, writer, device = setup_experiment(config, rank, local_rank)
 
-    train_loader, val_loader = create_data_loaders(
-        batch_size=config["training"]["batch_size"], num_train=config["data"]["num_train"],
-        num_val=config["data"]["num_val"], grid_size=tuple(config["data"]["grid_size"]), device=device,
-        cache_dir=config["data"]["cache_dir"], sim_batch=hw.get("sim_batch", 64),
-        jacobi_iters=hw.get("jacobi_iters", 20), rank=rank, world=world)
+    train_loader, val_loader = create_data_loaders(device=device, **data_loader_kwargs(config, rank, world))
 
     model = build_model(config).to(device)
     physics_regularizer = PhysicsRegularizer(conservation_weight=config["physics"]["conservation_weight"],
