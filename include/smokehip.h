@@ -263,7 +263,15 @@ int smk_encoder_destroy(smk_encoder *enc);
 /* SmokePhysNet.input_encoder + both adaptive pools (smokephys_net.py:87-91):
  * frames [B][H][W] fp32 (row pitch W, frame stride frame_stride floats) -> features [B][128][32][32] fp32.
  * Requires H == W, H % 32 == 0, and input_dim a multiple/divisor of H (then the two pools compose to an
- * (H/32)^2 block mean); anything else returns SMK_ERR_UNSUPPORTED. */
+ * (H/32)^2 block mean); anything else returns SMK_ERR_UNSUPPORTED.
+ * Tile skip (SMK_BF16X3, SMK_BF16, SMK_I8X3; both smk_encoder_forward and smk_encoder_forward_tokens): when a call has more 8 x 16
+ * tiles than the device runs workgroups, a scan pass first finds the tiles whose 16 x 24 input window is all-zero words, fills
+ * their features from the handle's zero-response table (the same kernel's output for an all-zero frame: bit-identical to computing
+ * them) and hands the main kernel a compact list of the others.  Dense input keeps the cost of the scan (about 1 %); SMK_ENC_SKIP=0
+ * (read once per process) runs every tile.  Table and workspace live in the handle, are built on the first eligible call outside
+ * stream capture, and are reused by every later call: CALLS ON ONE HANDLE MUST BE STREAM-ORDERED (one stream, or ordered by events);
+ * two forwards of one handle running concurrently on different streams would share the tile list.  Nothing in the forward copies
+ * to the host or synchronises, and every launch can be captured into a graph. */
 int smk_encoder_forward(smk_encoder *enc, const float *frames, int64_t frame_stride, int32_t B, int32_t H,
                         int32_t W, int32_t input_dim, float *features, int32_t dtype, void *stream);
 
@@ -271,6 +279,10 @@ int smk_encoder_forward(smk_encoder *enc, const float *frames, int64_t frame_str
  * `encoded.flatten(2).transpose(1, 2)` (smokephys_net.py:95) hands to feature_proj; coalesced stores. bf16 dtypes only. */
 int smk_encoder_forward_tokens(smk_encoder *enc, const float *frames, int64_t frame_stride, int32_t B, int32_t H,
                                int32_t W, int32_t input_dim, float *tokens, int32_t dtype, void *stream);
+
+/* Tile counts of the handle's LAST forward, for tests and profiles: synchronises `stream`, then tiles_total = B * (H/8) * (W/16) and
+ * tiles_run = the tiles the main kernel computed (== tiles_total after a call that ran without the tile skip). */
+int smk_encoder_skip_stats(smk_encoder *enc, int64_t *tiles_total, int64_t *tiles_run, void *stream);
 
 /* conv1+BN+ReLU activations only (smokephys_net.py:25-27), [B][64][H][W] fp32 -- parity hook. */
 int smk_encoder_conv1(smk_encoder *enc, const float *frames, int64_t frame_stride, int32_t B, int32_t H,

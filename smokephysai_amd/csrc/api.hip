@@ -121,6 +121,7 @@ struct smk_encoder {
     float *blob = nullptr;
     unsigned short *blob16 = nullptr;
     int device = 0;
+    EncoderSkip skip;     // tile-skip tables and workspace (lazy; a new handle starts without them)
 };
 
 namespace {
@@ -830,6 +831,7 @@ int smk_encoder_destroy(smk_encoder *enc) {
     DeviceGuard guard(enc->device);              // frees run on the handle's device; the caller's device is restored
     if (enc->blob) (void)hipFree(enc->blob);
     if (enc->blob16) (void)hipFree(enc->blob16);
+    enc->skip.release();
     delete enc;
     return SMK_OK;
 }
@@ -860,9 +862,9 @@ int smk_encoder_forward(smk_encoder *enc, const float *frames, int64_t frame_str
         return check_launch(launch_encoder_f32(frames, frame_stride, B, H, W, enc->e, features, (hipStream_t)stream), "encoder_f32");
     if (dtype == SMK_BF16X3 || dtype == SMK_BF16)
         return check_launch(launch_encoder_bf16(frames, frame_stride, B, H, W, enc->e, features, dtype == SMK_BF16X3, false,
-                                                (hipStream_t)stream), "encoder_bf16");
+                                                (hipStream_t)stream, &enc->skip), "encoder_bf16");
     if (dtype == SMK_I8X3)
-        return check_launch(launch_encoder_i8(frames, frame_stride, B, H, W, enc->e, features, false, (hipStream_t)stream),
+        return check_launch(launch_encoder_i8(frames, frame_stride, B, H, W, enc->e, features, false, (hipStream_t)stream, &enc->skip),
                             "encoder_i8");
     set_error("unknown encoder dtype");
     return SMK_ERR_INVALID;
@@ -878,14 +880,21 @@ int smk_encoder_forward_tokens(smk_encoder *enc, const float *frames, int64_t fr
     rc = guard.rc;
     if (rc) return rc;
     if (dtype == SMK_I8X3)
-        return check_launch(launch_encoder_i8(frames, frame_stride, B, H, W, enc->e, tokens, true, (hipStream_t)stream),
+        return check_launch(launch_encoder_i8(frames, frame_stride, B, H, W, enc->e, tokens, true, (hipStream_t)stream, &enc->skip),
                             "encoder_i8_tokens");
     if (dtype != SMK_BF16X3 && dtype != SMK_BF16) {
         set_error("token-major output is built for the MFMA kernels SMK_BF16X3, SMK_BF16, SMK_I8X3");
         return SMK_ERR_UNSUPPORTED;
     }
     return check_launch(launch_encoder_bf16(frames, frame_stride, B, H, W, enc->e, tokens, dtype == SMK_BF16X3, true,
-                                            (hipStream_t)stream), "encoder_bf16_tokens");
+                                            (hipStream_t)stream, &enc->skip), "encoder_bf16_tokens");
+}
+
+int smk_encoder_skip_stats(smk_encoder *enc, int64_t *tiles_total, int64_t *tiles_run, void *stream) {
+    SMK_REQUIRE(enc && tiles_total && tiles_run, "null enc/tiles_total/tiles_run");
+    DeviceGuard guard(enc->device);
+    if (guard.rc) return guard.rc;
+    return check_launch(encoder_skip_stats(enc->skip, tiles_total, tiles_run, (hipStream_t)stream), "encoder_skip_stats");
 }
 
 int smk_encoder_conv1(smk_encoder *enc, const float *frames, int64_t frame_stride, int32_t B, int32_t H, int32_t W,

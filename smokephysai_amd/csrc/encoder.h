@@ -1,4 +1,7 @@
 #pragma once
+#include <mutex>
+#include <vector>
+
 #include "common.h"
 
 namespace smk {
@@ -18,6 +21,19 @@ struct EncoderDev {
     unsigned short *w2s;   // [18 k-steps = tap*2 + c/32][2 hi/lo][128 o][32 c]  (16x16x32 B fragments: 16 o x 64 B = 1 KiB)
 };
 
+// Per-handle state of the tile-skip path (encoder.hip, "tile skip"): lazily built, guarded by mu, released with the handle.
+struct EncoderSkip {
+    std::mutex mu;
+    float *table[3][3][2] = {};       // zero-response tables [form: bf16x3 | bf16 | i8x3][H: 64 | 128 | 256][layout: NCHW | tokens]
+    int *ws = nullptr;                // workspace: list length, band masks, tile list for ws_tiles tiles
+    size_t ws_tiles = 0;
+    std::vector<void *> retired;      // outgrown workspaces (captured graphs may still name them)
+    int64_t last_total = 0;           // tiles of the last forward ...
+    const int *last_count = nullptr;  // ... and where the device keeps how many of them ran (null: direct path, all ran)
+    void release();                   // frees the device memory (the handle's device is current)
+};
+hipError_t encoder_skip_stats(EncoderSkip &sk, int64_t *tiles_total, int64_t *tiles_run, hipStream_t st);
+
 hipError_t launch_fold_weights(const smk_encoder_weights &w, const EncoderDev &e, hipStream_t st);
 hipError_t launch_conv1_only(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e, float *act,
                              hipStream_t st);
@@ -26,15 +42,16 @@ hipError_t launch_encoder_f32(const float *frames, int64_t fstride, int B, int H
 
 // x3 = true: split-bf16 (hi*hi + hi*lo + lo*hi, ~fp32 accuracy); false: single-pass bf16.
 // tokens = true: features written token-major [B][32*32][128] (coalesced; the layout feature_proj consumes).
+// skip (all three persistent MFMA forms below): the handle's tile-skip state, or null to run every tile.
 hipError_t launch_encoder_bf16(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e,
-                               float *features, bool x3, bool tokens, hipStream_t st);
+                               float *features, bool x3, bool tokens, hipStream_t st, EncoderSkip *skip = nullptr);
 // split-bf16 on the 16x16x32 MFMA shape (same arithmetic and tiles; higher sustained clock under the power limit)
 hipError_t launch_encoder_b16(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e,
-                              float *features, bool tokens, hipStream_t st);
+                              float *features, bool tokens, hipStream_t st, EncoderSkip *skip = nullptr);
 
 // int8 two-limb fixed point (activations scaled per tile, weights per output channel), exact i32 accumulation.
 hipError_t launch_encoder_i8(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e,
-                             float *features, bool tokens, hipStream_t st);
+                             float *features, bool tokens, hipStream_t st, EncoderSkip *skip = nullptr);
 
 // Training: z2 = conv2(a1) + bias alone (Conv2d(64, 128, 3, padding = 1); NCHW fp32 in and out; H % 8 == 0, W % 16 == 0); `workspace` holds
 // the split weights (conv2_train_workspace_bytes), rebuilt from `weight` [128][64][3][3] in the same call.

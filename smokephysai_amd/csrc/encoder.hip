@@ -352,13 +352,25 @@ constexpr int B3_W1_BYTES = 64 * B3_W1_PITCH;            // 9216 per part
 constexpr int B3_ST_BYTES = 2 * 64 * 4;                  // BN1 scale | shift
 template <bool X3> constexpr int b3_lds_total() { return b3_lds_bytes<X3>() + (X3 ? 2 : 1) * B3_W1_BYTES + B3_ST_BYTES; }   // 73,136 (x3)
 
-// Persistent: each workgroup walks tiles t = blockIdx.x, +gridDim.x, ... .  Per-workgroup costs (conv1 weights -> LDS,
-// BN2 scale/shift, B-ring fill) are paid once; the next tile's x halo is prefetched into registers under the K loop and
+// Work list of the persistent kernels.  Direct path (list == nullptr): entry k is tile k, all ntiles tiles run.  Skip path: the
+// compact list and its length come from k_encoder_tile_scan / k_encoder_tile_scan_pack, launched before on the same stream (a
+// kernel boundary orders them); tiles not on the list were already written by the scan.  k is wave-uniform, so both are scalar
+// loads; a list of all ntiles tiles (dense input) is not read at all.
+__device__ __forceinline__ int tiles_to_run(const int *__restrict__ list, const int *__restrict__ count, int ntiles) {
+    return list ? __builtin_amdgcn_readfirstlane(*count) : ntiles;
+}
+__device__ __forceinline__ int tile_at(const int *__restrict__ list, int k) {
+    return list ? __builtin_amdgcn_readfirstlane(list[k]) : k;
+}
+
+// Persistent: each workgroup walks work-list entries k = blockIdx.x, +gridDim.x, ... (t = tile_at(list, k)).  Per-workgroup
+// costs (conv1 weights -> LDS, BN2 scale/shift, B-ring fill) are paid once; the next tile's x halo is prefetched into registers under the K loop and
 // the B-fragment ring simply keeps running across tiles (the weights do not depend on the tile).
 template <bool X3, int PS, bool TOKENS>
 __global__ __launch_bounds__(256, 2) void k_encoder_bf16(const float *__restrict__ frames, int64_t fstride, int H, int W,
                                                       EncoderDev e, float *__restrict__ features, int lg_tiles_x,
-                                                      int lg_tiles_per_frame, int ntiles, int stagger) {
+                                                      int lg_tiles_per_frame, int ntiles, int stagger,
+                                                      const int *__restrict__ list, const int *__restrict__ count) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *xs = reinterpret_cast<float *>(smem);
     unsigned char *a1h = smem + B3_XS_BYTES, *a1l = a1h + B3_A1_BYTES;
@@ -410,19 +422,22 @@ __global__ __launch_bounds__(256, 2) void k_encoder_bf16(const float *__restrict
         const bool ok = row < B3_XH - 1 && col < B3_XW - 1 && ii >= 0 && ii < H && jj >= 0 && jj < W;
         return ok ? frames[(size_t)bb * fstride + (size_t)ii * W + jj] : 0.f;
     };
-    int t = blockIdx.x;
+    int k = blockIdx.x;
+    const int nrun = tiles_to_run(list, count, ntiles);
+    if (nrun == ntiles) list = nullptr;                       // a complete list is ascending, i.e. the identity: no list loads
+    int t = k < nrun ? tile_at(list, k) : 0;
     // Workgroups that share a CU run the same program with the same period; started together they stay in lockstep
     // (both in the VALU-heavy conv1 phase, then both in the MFMA loop).  Delay every other dispatch round by about
     // half a tile so that one workgroup's conv1 overlaps the other's K loop (speed only, never correctness).
     if (stagger > 0 && ((blockIdx.x / 256) & 1))
         for (int i = 0; i < stagger; ++i) __builtin_amdgcn_s_sleep(127);
-    if (t < ntiles) {
+    if (k < nrun) {
         xs[tid] = x_fetch(t, tid);
         if (tid + 256 < B3_XH * B3_XW) xs[tid + 256] = x_fetch(t, tid + 256);
     }
     __syncthreads();
 
-    for (; t < ntiles; t += gridDim.x) {
+    for (; k < nrun; k += gridDim.x) {
         const int b = t >> lg_tiles_per_frame, rem = t & ((1 << lg_tiles_per_frame) - 1);
         const int r0 = (rem >> lg_tiles_x) * B3_TH, c0 = (rem & ((1 << lg_tiles_x) - 1)) * B3_TW;
 
@@ -513,9 +528,10 @@ __global__ __launch_bounds__(256, 2) void k_encoder_bf16(const float *__restrict
         __builtin_amdgcn_s_setprio(1);
 
         // next tile's x halo -> registers (lands under the K loop)
-        const int tn = t + gridDim.x;
+        const int kn = k + gridDim.x;
+        const int tn = kn < nrun ? tile_at(list, kn) : 0;
         float xr0 = 0.f, xr1 = 0.f;
-        if (tn < ntiles) {
+        if (kn < nrun) {
             xr0 = x_fetch(tn, tid);
             xr1 = x_fetch(tn, tid + 256);
         }
@@ -629,6 +645,7 @@ __global__ __launch_bounds__(256, 2) void k_encoder_bf16(const float *__restrict
         xs[tid] = xr0;
         if (tid + 256 < B3_XH * B3_XW) xs[tid + 256] = xr1;
         __syncthreads();
+        t = tn;
     }
 }
 
@@ -657,7 +674,8 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 template <int PS, bool TOKENS>
 __global__ __launch_bounds__(256, 2) void k_encoder_b16(const float *__restrict__ frames, int64_t fstride, int H, int W,
                                                      EncoderDev e, float *__restrict__ features, int lg_tiles_x,
-                                                     int lg_tiles_per_frame, int ntiles, int stagger) {
+                                                     int lg_tiles_per_frame, int ntiles, int stagger,
+                                                     const int *__restrict__ list, const int *__restrict__ count) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // x tile kept already split: one word per pixel, hi bf16 in the low half, lo bf16 in the high half (split once by the staging
     // thread; every wave's fragment builder then needs one v_perm_b32 per element pair instead of two 3-instruction splits)
@@ -717,23 +735,26 @@ __global__ __launch_bounds__(256, 2) void k_encoder_b16(const float *__restrict_
         split_bf16(v, vh, vl);
         return (unsigned int)__builtin_bit_cast(unsigned short, vh) | ((unsigned int)__builtin_bit_cast(unsigned short, vl) << 16);
     };
-    int t = blockIdx.x;
+    int k = blockIdx.x;
+    const int nrun = tiles_to_run(list, count, ntiles);
+    if (nrun == ntiles) list = nullptr;                       // a complete list is ascending, i.e. the identity: no list loads
+    int t = k < nrun ? tile_at(list, k) : 0;
     if (stagger > 0 && ((blockIdx.x / 256) & 1))
         for (int i = 0; i < stagger; ++i) __builtin_amdgcn_s_sleep(127);
-    if (t < ntiles) {
+    if (k < nrun) {
         xs[tid] = pack_split(x_fetch(t, tid));
         if (tid + 256 < B3_XH * B3_XW) xs[tid + 256] = pack_split(x_fetch(t, tid + 256));
     }
     __syncthreads();
 
-    for (; t < ntiles; t += gridDim.x) {
+    for (; k < nrun; k += gridDim.x) {
         const int b = t >> lg_tiles_per_frame, rem = t & ((1 << lg_tiles_per_frame) - 1);
         const int r0 = (rem >> lg_tiles_x) * B3_TH, c0 = (rem & ((1 << lg_tiles_x) - 1)) * B3_TW;
 
         __builtin_amdgcn_s_setprio(S16_PRIO_CONV1);
 #ifdef SMK_ENC_ABLATE      // timing ablations (tools/enc_ablate.sh; never a product build): 1 conv1 only on a workgroup's first tile,
                            // 2 no BN/ReLU/pool epilogue, 4 no workgroup barriers, 8 no conv2 MFMAs -- results are wrong by construction
-        const bool abl_conv1 = !((SMK_ENC_ABLATE & 1) && t != (int)blockIdx.x);
+        const bool abl_conv1 = !((SMK_ENC_ABLATE & 1) && k != (int)blockIdx.x);
 #else
         constexpr bool abl_conv1 = true;
 #endif
@@ -824,9 +845,10 @@ __global__ __launch_bounds__(256, 2) void k_encoder_b16(const float *__restrict_
 #endif
         __builtin_amdgcn_s_setprio(S16_PRIO_KLOOP);
 
-        const int tn = t + gridDim.x;
+        const int kn = k + gridDim.x;
+        const int tn = kn < nrun ? tile_at(list, kn) : 0;
         float xr0 = 0.f, xr1 = 0.f;
-        if (tn < ntiles) {
+        if (kn < nrun) {
             xr0 = x_fetch(tn, tid);
             xr1 = x_fetch(tn, tid + 256);
         }
@@ -974,6 +996,7 @@ __global__ __launch_bounds__(256, 2) void k_encoder_b16(const float *__restrict_
 #if !defined(SMK_ENC_ABLATE) || !(SMK_ENC_ABLATE & 4)
         __syncthreads();
 #endif
+        t = tn;
     }
 }
 
@@ -1777,14 +1800,18 @@ hipError_t launch_conv2_train_forward(const float *a1, const float *weight, cons
 }
 
 // Diagnostic switches, read once per process: SMK_ENC_STAGGER (s_sleep units of the second workgroup wave, default 1),
-// SMK_ENC_WGS_PER_CU (override the occupancy query), SMK_ENC_SHAPE=32 (split-bf16 on the 32x32x16 kernel instead of 16x16x32).
+// SMK_ENC_WGS_PER_CU (override the occupancy query), SMK_ENC_SHAPE=32 (split-bf16 on the 32x32x16 kernel instead of 16x16x32),
+// SMK_ENC_SKIP=0 (every tile runs: no tile scan, see below).
 struct EncoderKnobs {
     int stagger, wgs_per_cu, shape;
+    bool skip;
     EncoderKnobs() {
         const char *sv = getenv("SMK_ENC_STAGGER"), *ov = getenv("SMK_ENC_WGS_PER_CU"), *sh = getenv("SMK_ENC_SHAPE");
+        const char *sk = getenv("SMK_ENC_SKIP");
         stagger = sv ? atoi(sv) : 1;
         wgs_per_cu = ov && atoi(ov) > 0 ? atoi(ov) : 0;
         shape = sh && atoi(sh) == 32 ? 32 : 16;
+        skip = !(sk && atoi(sk) == 0);
     }
 };
 static const EncoderKnobs &enc_knobs() {
@@ -1792,15 +1819,227 @@ static const EncoderKnobs &enc_knobs() {
     return k;
 }
 
+// ---------------------------------------------------------------- tile skip: input windows that are all zero
+// A tile's result depends on its 16 x 24 input window (tile + 4 pixels each way, outside the image = zero) and on its position in the
+// frame, nothing else.  A tile whose window is all zero therefore equals the same tile of an all-zero frame, bit for bit, and the
+// simulator's frames are mostly background.  Before the persistent kernel (k_encoder_b16, k_encoder_bf16, k_encoder_i8):
+//   k_encoder_tile_scan       one workgroup per band of SCAN_ROWS tile rows of a frame.  Reads the band's 32 + 8 image rows once
+//          (16-byte loads when the frames allow), keeps one flag per 4 x 4 pixel block in LDS (window edges fall on multiples of 4),
+//          ORs 4 x 6 flags per tile.  EMPTY means every 32-bit word of the window inside the image is 0x00000000: bits are compared,
+//          so -0.0, denormals, NaN and Inf all keep a tile on the normal path.  Empty tiles get their pooled cells copied from the
+//          handle's zero-response table (the same kernel form's output for one all-zero frame, in the layout of the call); the
+//          band's non-empty tiles go out as one 64-bit mask.
+//   k_encoder_tile_scan_pack  one wave per band: its offset = the popcounts of all earlier masks (each workgroup sums them itself), its
+//          lanes write the band's tiles in order -> ascending list of the tiles to run and its length in device memory.  Every word the main kernel reads is rewritten by these two launches each call, so nothing needs a
+//          reset, nothing is read back by the host, the list is the same on every run, and all three launches are capturable.
+// No workgroup waits for another one; kernel boundaries order scan, pack and main kernel.
+constexpr int SCAN_ROWS = 4;                                  // tile rows per band: <= 64 tiles at W = 256 (one mask word)
+constexpr int SCAN_BR = 2 * SCAN_ROWS + 2;                    // 4-row flag blocks per band (the band's rows + 4 each way)
+constexpr int SCAN_FW = 256 / 4 + 2;                          // flag columns: the widest frame's 4-pixel blocks + one pad each side
+constexpr int ENC_FRAME_FEATS = 128 * 1024;                   // features per frame, either layout
+
+template <int PS, bool TOKENS, bool VEC>
+__global__ __launch_bounds__(256) void k_encoder_tile_scan(const float *__restrict__ frames, int64_t fstride, int H, int W, int lg_tiles_x,
+                                                           int bands_per_frame, const float *__restrict__ table,
+                                                           float *__restrict__ features, unsigned long long *__restrict__ masks) {
+    __shared__ unsigned int flag[SCAN_BR][SCAN_FW];
+    __shared__ unsigned long long s_mask;
+    const int tid = threadIdx.x;
+    const int band = blockIdx.x, b = band / bands_per_frame, bi = band - b * bands_per_frame;
+    const int tiles_x = 1 << lg_tiles_x, band_tiles = SCAN_ROWS * tiles_x;
+    for (int i = tid; i < SCAN_BR * SCAN_FW; i += 256) (&flag[0][0])[i] = 0;
+    __syncthreads();
+    const int W4 = W >> 2, row0 = bi * (SCAN_ROWS * B3_TH) - 4;
+    const unsigned int *src = reinterpret_cast<const unsigned int *>(frames) + (size_t)b * fstride;
+    for (int i = tid; i < SCAN_BR * 4 * W4; i += 256) {
+        const int rr = i / W4, c4 = i - rr * W4, row = row0 + rr;
+        if (row < 0 || row >= H) continue;
+        const unsigned int *p = src + (size_t)row * W + 4 * c4;
+        unsigned int any;
+        if (VEC) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(p);
+            any = v.x | v.y | v.z | v.w;
+        } else {
+            any = p[0] | p[1] | p[2] | p[3];
+        }
+        if (any) flag[rr >> 2][c4 + 1] = 1;                   // racing writers all store the same value
+    }
+    __syncthreads();
+    if (tid < 64) {                                           // wave 0: one lane per tile of the band
+        unsigned int any = 0;
+        if (tid < band_tiles) {
+            const int tyl = tid >> lg_tiles_x, tx = tid & (tiles_x - 1);
+#pragma unroll
+            for (int br = 0; br < 4; ++br)
+#pragma unroll
+                for (int bc = 0; bc < 6; ++bc) any |= flag[2 * tyl + br][4 * tx + bc];
+        }
+        const unsigned long long m = __ballot(any != 0);
+        if (tid == 0) {
+            s_mask = m;
+            masks[band] = m;
+        }
+    }
+    __syncthreads();
+    const unsigned long long m = s_mask;
+    // empty tiles: pooled cells from the zero-response table (same offsets within the frame)
+    constexpr int CR = B3_TH / PS, CC = B3_TW / PS;           // cells per tile: rows x columns
+    float *out = features + (size_t)b * ENC_FRAME_FEATS;
+    const int ty0 = bi * SCAN_ROWS;
+    if (TOKENS) {
+        constexpr int ROWV = CC * 32, UPT = CR * ROWV;        // float4 per cell row (CC cells x 128 channels, contiguous) / per tile
+        for (int i = tid; i < band_tiles * UPT; i += 256) {
+            const int tl = i / UPT, u = i - tl * UPT;
+            if ((m >> tl) & 1) continue;
+            const int ty = ty0 + (tl >> lg_tiles_x), tx = tl & (tiles_x - 1);
+            const int a = u / ROWV, q = u - a * ROWV;
+            const size_t off = (size_t)((ty * CR + a) * 32 + tx * CC) * 128 + q * 4;
+            *reinterpret_cast<float4 *>(out + off) = *reinterpret_cast<const float4 *>(table + off);
+        }
+    } else {
+        constexpr int VW = CC < 4 ? CC : 4, VPR = CC / VW, UPT = 128 * CR * VPR;   // a channel's cells of one row: CC contiguous floats
+        for (int i = tid; i < band_tiles * UPT; i += 256) {
+            const int tl = i / UPT, u = i - tl * UPT;
+            if ((m >> tl) & 1) continue;
+            const int ty = ty0 + (tl >> lg_tiles_x), tx = tl & (tiles_x - 1);
+            const int v = u % VPR, a = (u / VPR) % CR, o = u / (VPR * CR);
+            const size_t off = (size_t)o * 1024 + (ty * CR + a) * 32 + tx * CC + v * VW;
+            if (VW == 2) *reinterpret_cast<float2 *>(out + off) = *reinterpret_cast<const float2 *>(table + off);
+            else *reinterpret_cast<float4 *>(out + off) = *reinterpret_cast<const float4 *>(table + off);
+        }
+    }
+}
+
+constexpr int PACK_BANDS = 4;                                 // bands per pack workgroup: one wave each, one lane per tile
+__global__ __launch_bounds__(64 * PACK_BANDS) void k_encoder_tile_scan_pack(const unsigned long long *__restrict__ masks, int nbands,
+                                                                            int lg_band_tiles, int *__restrict__ list,
+                                                                            int *__restrict__ count) {
+    __shared__ int part[PACK_BANDS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int first = blockIdx.x * PACK_BANDS, band = first + wave;
+    // tiles on the list before this workgroup's bands: every workgroup sums the earlier masks itself (<= 8 bytes per band, from L2)
+    int c = 0;
+    for (int j = tid; j < first; j += 64 * PACK_BANDS) c += __popcll(masks[j]);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
+    if (lane == 0) part[wave] = c;
+    __syncthreads();
+    int before = 0;
+#pragma unroll
+    for (int w = 0; w < PACK_BANDS; ++w) before += part[w];
+    if (band >= nbands) return;
+    for (int w = 0; w < wave; ++w) before += __popcll(masks[first + w]);      // first + w < band < nbands
+    const unsigned long long m = masks[band];
+    if ((m >> lane) & 1) list[before + __popcll(m & ((1ull << lane) - 1))] = (band << lg_band_tiles) + lane;
+    if (band == nbands - 1 && lane == 0) *count = before + __popcll(m);
+}
+
+void EncoderSkip::release() {
+    for (auto &f : table)
+        for (auto &h : f)
+            for (float *&t : h) {
+                if (t) (void)hipFree(t);
+                t = nullptr;
+            }
+    if (ws) (void)hipFree(ws);
+    for (void *p : retired) (void)hipFree(p);
+    retired.clear();
+    ws = nullptr;
+    ws_tiles = 0;
+    last_count = nullptr;
+}
+
+hipError_t encoder_skip_stats(EncoderSkip &sk, int64_t *tiles_total, int64_t *tiles_run, hipStream_t st) {
+    std::lock_guard<std::mutex> lk(sk.mu);
+    hipError_t err = hipStreamSynchronize(st);
+    if (err != hipSuccess) return err;
+    int n = 0;
+    if (sk.last_count && (err = hipMemcpy(&n, sk.last_count, sizeof(int), hipMemcpyDeviceToHost)) != hipSuccess) return err;
+    *tiles_total = sk.last_total;
+    *tiles_run = sk.last_count ? n : sk.last_total;
+    return hipSuccess;
+}
+
+struct SkipPlan {
+    const int *list = nullptr, *count = nullptr;              // both null: direct path
+};
+
+// Decides between the direct and the skip path of one forward call and, for the skip path, launches scan + pack.  FORM: 0 split-bf16,
+// 1 single-pass bf16, 2 int8 limbs (one zero-response table each, per frame size and layout).  zero_launch(zero_frame, table) runs
+// the call's own kernel form on the direct path over one all-zero frame.  Direct when the call has no more tiles than workgroups (one
+// round either way: the scan could only cost), when SMK_ENC_SKIP=0, when `features` is not 16-byte aligned, and while the stream is
+// capturing unless table and workspace already exist (nothing is allocated inside a capture).  Outgrown workspaces are kept until the
+// handle is destroyed: a captured graph may still name them.
+template <int FORM, bool TOKENS, class ZeroLaunch>
+static hipError_t skip_prepare(EncoderSkip *sk, const float *frames, int64_t fstride, int B, int H, int W, float *features, int lg_tx,
+                               int ntiles, int nwg, hipStream_t st, ZeroLaunch zero_launch, SkipPlan &plan) {
+    if (!sk) return hipSuccess;
+    std::lock_guard<std::mutex> lk(sk->mu);
+    sk->last_total = ntiles;
+    sk->last_count = nullptr;
+    if (!enc_knobs().skip || ntiles <= nwg || (reinterpret_cast<uintptr_t>(features) & 15)) return hipSuccess;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) {
+        (void)hipGetLastError();
+        return hipSuccess;
+    }
+    const bool capturing = cs != hipStreamCaptureStatusNone;
+    hipError_t err;
+    float *&tab = sk->table[FORM][H == 64 ? 0 : H == 128 ? 1 : 2][TOKENS ? 1 : 0];
+    if (!tab) {
+        if (capturing) return hipSuccess;
+        float *p = nullptr;                                   // [table 1024 x 128][zero frame H x W]
+        if ((err = hipMalloc((void **)&p, ((size_t)ENC_FRAME_FEATS + (size_t)H * W) * sizeof(float))) != hipSuccess) return err;
+        err = hipMemsetAsync(p + ENC_FRAME_FEATS, 0, (size_t)H * W * sizeof(float), st);
+        if (err == hipSuccess) err = zero_launch(p + ENC_FRAME_FEATS, p);
+        if (err != hipSuccess) {
+            (void)hipFree(p);
+            return err;
+        }
+        tab = p;
+    }
+    if (sk->ws_tiles < (size_t)ntiles) {
+        if (capturing) return hipSuccess;
+        int *p = nullptr;                                     // [count + pad: 4][band masks: 2 per 16 tiles][list: 1 per tile]
+        if ((err = hipMalloc((void **)&p, (4 + (size_t)ntiles / 8 + (size_t)ntiles) * sizeof(int))) != hipSuccess) return err;
+        if (sk->ws) sk->retired.push_back(sk->ws);
+        sk->ws = p;
+        sk->ws_tiles = ntiles;
+    }
+    int *count = sk->ws, *list = sk->ws + 4 + sk->ws_tiles / 8;
+    unsigned long long *masks = reinterpret_cast<unsigned long long *>(sk->ws + 4);
+    const int bands_per_frame = H / B3_TH / SCAN_ROWS, nbands = B * bands_per_frame;
+    const bool vec = (reinterpret_cast<uintptr_t>(frames) & 15) == 0 && (fstride & 3) == 0;
+    dim3 grid(nbands), block(256);
+#define SMK_SCAN_LAUNCH(PS_, VEC_)                                                                                                  \
+    hipLaunchKernelGGL((k_encoder_tile_scan<PS_, TOKENS, VEC_>), grid, block, 0, st, frames, fstride, H, W, lg_tx, bands_per_frame, \
+                       (const float *)tab, features, masks)
+    switch (H / 32) {
+        case 2: if (vec) SMK_SCAN_LAUNCH(2, true); else SMK_SCAN_LAUNCH(2, false); break;
+        case 4: if (vec) SMK_SCAN_LAUNCH(4, true); else SMK_SCAN_LAUNCH(4, false); break;
+        case 8: if (vec) SMK_SCAN_LAUNCH(8, true); else SMK_SCAN_LAUNCH(8, false); break;
+        default: return hipErrorInvalidValue;
+    }
+#undef SMK_SCAN_LAUNCH
+    if ((err = hipGetLastError()) != hipSuccess) return err;
+    hipLaunchKernelGGL(k_encoder_tile_scan_pack, dim3((nbands + PACK_BANDS - 1) / PACK_BANDS), dim3(64 * PACK_BANDS), 0, st,
+                       (const unsigned long long *)masks, nbands, lg_tx + 2, list, count);
+    if ((err = hipGetLastError()) != hipSuccess) return err;
+    plan.list = list;
+    plan.count = count;
+    sk->last_count = count;
+    return hipSuccess;
+}
+
 template <bool TOKENS>
 static hipError_t launch_b16_t(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e, float *features,
-                               hipStream_t st) {
+                               hipStream_t st, EncoderSkip *skip) {
     const int PS = H / 32;
     const int tiles_x = W / B3_TW, tiles_per_frame = tiles_x * (H / B3_TH), ntiles = B * tiles_per_frame;
     int lg_tx = 0, lg_tpf = 0;
     while ((1 << lg_tx) < tiles_x) ++lg_tx;
     while ((1 << lg_tpf) < tiles_per_frame) ++lg_tpf;
-    if ((1 << lg_tx) != tiles_x || (1 << lg_tpf) != tiles_per_frame) return hipErrorInvalidValue;
+    if ((1 << lg_tx) != tiles_x || (1 << lg_tpf) != tiles_per_frame || (PS != 2 && PS != 4 && PS != 8)) return hipErrorInvalidValue;
     const int stagger = enc_knobs().stagger;
     const int num_cu = device_num_cu();
     const int wgs_per_cu = device_cached_int((const void *)k_encoder_b16<8, TOKENS>, [] {
@@ -1811,33 +2050,42 @@ static hipError_t launch_b16_t(const float *frames, int64_t fstride, int B, int 
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k_encoder_b16<8, TOKENS>, 256, S16_LDS) != hipSuccess || n < 1) n = 2;
         return enc_knobs().wgs_per_cu ? enc_knobs().wgs_per_cu : n;
     });
-    int nwg = num_cu * wgs_per_cu;
-    if (nwg > ntiles) nwg = ntiles;
-    dim3 grid(nwg), block(256);
-    switch (PS) {
-        case 2: hipLaunchKernelGGL((k_encoder_b16<2, TOKENS>), grid, block, S16_LDS, st, frames, fstride, H, W, e, features, lg_tx, lg_tpf, ntiles, stagger); break;
-        case 4: hipLaunchKernelGGL((k_encoder_b16<4, TOKENS>), grid, block, S16_LDS, st, frames, fstride, H, W, e, features, lg_tx, lg_tpf, ntiles, stagger); break;
-        case 8: hipLaunchKernelGGL((k_encoder_b16<8, TOKENS>), grid, block, S16_LDS, st, frames, fstride, H, W, e, features, lg_tx, lg_tpf, ntiles, stagger); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    // the fixed persistent grid, capped by the tile count of the call (never by the device-side list length)
+    auto run = [&](const float *fr, int64_t fs, int nt, float *out, const int *list, const int *count) -> hipError_t {
+        int nwg = num_cu * wgs_per_cu;
+        if (nwg > nt) nwg = nt;
+        dim3 grid(nwg), block(256);
+        switch (PS) {
+            case 2: hipLaunchKernelGGL((k_encoder_b16<2, TOKENS>), grid, block, S16_LDS, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, list, count); break;
+            case 4: hipLaunchKernelGGL((k_encoder_b16<4, TOKENS>), grid, block, S16_LDS, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, list, count); break;
+            default: hipLaunchKernelGGL((k_encoder_b16<8, TOKENS>), grid, block, S16_LDS, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, list, count); break;
+        }
+        return hipGetLastError();
+    };
+    SkipPlan plan;
+    hipError_t err = skip_prepare<0, TOKENS>(
+        skip, frames, fstride, B, H, W, features, lg_tx, ntiles, num_cu * wgs_per_cu, st,
+        [&](const float *zero_frame, float *table) { return run(zero_frame, (int64_t)H * W, tiles_per_frame, table, nullptr, nullptr); },
+        plan);
+    if (err != hipSuccess) return err;
+    return run(frames, fstride, ntiles, features, plan.list, plan.count);
 }
 
 hipError_t launch_encoder_b16(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e, float *features,
-                              bool tokens, hipStream_t st) {
-    return tokens ? launch_b16_t<true>(frames, fstride, B, H, W, e, features, st)
-                  : launch_b16_t<false>(frames, fstride, B, H, W, e, features, st);
+                              bool tokens, hipStream_t st, EncoderSkip *skip) {
+    return tokens ? launch_b16_t<true>(frames, fstride, B, H, W, e, features, st, skip)
+                  : launch_b16_t<false>(frames, fstride, B, H, W, e, features, st, skip);
 }
 
 template <bool X3, bool TOKENS>
 static hipError_t launch_bf16_t(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e,
-                                float *features, hipStream_t st) {
+                                float *features, hipStream_t st, EncoderSkip *skip) {
     const int PS = H / 32;
     const int tiles_x = W / B3_TW, tiles_per_frame = tiles_x * (H / B3_TH), ntiles = tiles_per_frame * B;
     int lg_tx = 0, lg_tpf = 0;
     while ((1 << lg_tx) < tiles_x) ++lg_tx;
     while ((1 << lg_tpf) < tiles_per_frame) ++lg_tpf;
-    if ((1 << lg_tx) != tiles_x || (1 << lg_tpf) != tiles_per_frame) return hipErrorInvalidValue;   // H = W in {64,128,256}
+    if ((1 << lg_tx) != tiles_x || (1 << lg_tpf) != tiles_per_frame || (PS != 2 && PS != 4 && PS != 8)) return hipErrorInvalidValue;   // H = W in {64,128,256}
     const int stagger = enc_knobs().stagger;
     constexpr size_t lds_bytes = b3_lds_total<X3>();
     const int num_cu = device_num_cu();
@@ -1850,28 +2098,37 @@ static hipError_t launch_bf16_t(const float *frames, int64_t fstride, int B, int
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k_encoder_bf16<X3, 8, TOKENS>, 256, lb) != hipSuccess || n < 1) n = 2;
         return enc_knobs().wgs_per_cu ? enc_knobs().wgs_per_cu : n;
     });
-    int nwg = num_cu * wgs_per_cu;
-    if (nwg > ntiles) nwg = ntiles;
-    dim3 grid(nwg), block(256);
-    switch (PS) {
-        case 2: hipLaunchKernelGGL((k_encoder_bf16<X3, 2, TOKENS>), grid, block, lds_bytes, st, frames, fstride, H, W, e, features, lg_tx, lg_tpf, ntiles, stagger); break;
-        case 4: hipLaunchKernelGGL((k_encoder_bf16<X3, 4, TOKENS>), grid, block, lds_bytes, st, frames, fstride, H, W, e, features, lg_tx, lg_tpf, ntiles, stagger); break;
-        case 8: hipLaunchKernelGGL((k_encoder_bf16<X3, 8, TOKENS>), grid, block, lds_bytes, st, frames, fstride, H, W, e, features, lg_tx, lg_tpf, ntiles, stagger); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    // the fixed persistent grid, capped by the tile count of the call (never by the device-side list length)
+    auto run = [&](const float *fr, int64_t fs, int nt, float *out, const int *list, const int *count) -> hipError_t {
+        int nwg = num_cu * wgs_per_cu;
+        if (nwg > nt) nwg = nt;
+        dim3 grid(nwg), block(256);
+        switch (PS) {
+            case 2: hipLaunchKernelGGL((k_encoder_bf16<X3, 2, TOKENS>), grid, block, lds_bytes, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, list, count); break;
+            case 4: hipLaunchKernelGGL((k_encoder_bf16<X3, 4, TOKENS>), grid, block, lds_bytes, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, list, count); break;
+            default: hipLaunchKernelGGL((k_encoder_bf16<X3, 8, TOKENS>), grid, block, lds_bytes, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, list, count); break;
+        }
+        return hipGetLastError();
+    };
+    SkipPlan plan;
+    hipError_t err = skip_prepare<X3 ? 0 : 1, TOKENS>(
+        skip, frames, fstride, B, H, W, features, lg_tx, ntiles, num_cu * wgs_per_cu, st,
+        [&](const float *zero_frame, float *table) { return run(zero_frame, (int64_t)H * W, tiles_per_frame, table, nullptr, nullptr); },
+        plan);
+    if (err != hipSuccess) return err;
+    return run(frames, fstride, ntiles, features, plan.list, plan.count);
 }
 
 hipError_t launch_encoder_bf16(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e,
-                               float *features, bool x3, bool tokens, hipStream_t st) {
+                               float *features, bool x3, bool tokens, hipStream_t st, EncoderSkip *skip) {
     // split-bf16 runs on the 16x16x32 shape (k_encoder_b16: -7 % time, interleaved A/B); SMK_ENC_SHAPE=32 selects the
     // 32x32x16 kernel (k_encoder_bf16<true>) for comparison
     const int shape = enc_knobs().shape;
-    if (x3 && shape == 16) return launch_encoder_b16(frames, fstride, B, H, W, e, features, tokens, st);
-    if (x3) return tokens ? launch_bf16_t<true, true>(frames, fstride, B, H, W, e, features, st)
-                          : launch_bf16_t<true, false>(frames, fstride, B, H, W, e, features, st);
-    return tokens ? launch_bf16_t<false, true>(frames, fstride, B, H, W, e, features, st)
-                  : launch_bf16_t<false, false>(frames, fstride, B, H, W, e, features, st);
+    if (x3 && shape == 16) return launch_encoder_b16(frames, fstride, B, H, W, e, features, tokens, st, skip);
+    if (x3) return tokens ? launch_bf16_t<true, true>(frames, fstride, B, H, W, e, features, st, skip)
+                          : launch_bf16_t<true, false>(frames, fstride, B, H, W, e, features, st, skip);
+    return tokens ? launch_bf16_t<false, true>(frames, fstride, B, H, W, e, features, st, skip)
+                  : launch_bf16_t<false, false>(frames, fstride, B, H, W, e, features, st, skip);
 }
 
 // ---------------------------------------------------------------- fused encoder, int8 fixed-point MFMA ("i8x3")
@@ -1896,7 +2153,8 @@ constexpr int I8_LDS_BYTES = B3_XS_BYTES + 2 * I8_A1_BYTES + 2 * B3_W1_BYTES + B
 template <int PS, bool TOKENS>
 __global__ __launch_bounds__(256, 2) void k_encoder_i8(const float *__restrict__ frames, int64_t fstride, int H, int W,
                                                     EncoderDev e, float *__restrict__ features, int lg_tiles_x,
-                                                    int lg_tiles_per_frame, int ntiles) {
+                                                    int lg_tiles_per_frame, int ntiles,
+                                                    const int *__restrict__ list, const int *__restrict__ count) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *xs = reinterpret_cast<float *>(smem);
     unsigned char *a1h = smem + B3_XS_BYTES, *a1l = a1h + I8_A1_BYTES;
@@ -1944,15 +2202,18 @@ __global__ __launch_bounds__(256, 2) void k_encoder_i8(const float *__restrict__
         const bool ok = row < B3_XH - 1 && col < B3_XW - 1 && ii >= 0 && ii < H && jj >= 0 && jj < W;
         return ok ? frames[(size_t)bb * fstride + (size_t)ii * W + jj] : 0.f;
     };
-    int t = blockIdx.x;
-    if (t < ntiles) {
+    int k = blockIdx.x;
+    const int nrun = tiles_to_run(list, count, ntiles);
+    if (nrun == ntiles) list = nullptr;                       // a complete list is ascending, i.e. the identity: no list loads
+    int t = k < nrun ? tile_at(list, k) : 0;
+    if (k < nrun) {
         xs[tid] = x_fetch(t, tid);
         if (tid + 256 < B3_XH * B3_XW) xs[tid + 256] = x_fetch(t, tid + 256);
     }
     __syncthreads();
 
     // [stamp:begin]
-    for (; t < ntiles; t += gridDim.x) {
+    for (; k < nrun; k += gridDim.x) {
         // [stamp:T0]
         const int b = t >> lg_tiles_per_frame, rem = t & ((1 << lg_tiles_per_frame) - 1);
         const int r0 = (rem >> lg_tiles_x) * B3_TH, c0 = (rem & ((1 << lg_tiles_x) - 1)) * B3_TW;
@@ -2076,9 +2337,10 @@ __global__ __launch_bounds__(256, 2) void k_encoder_i8(const float *__restrict__
         __builtin_amdgcn_s_setprio(1);                        // K loop at raised priority (see k_encoder_bf16)
         // [stamp:T4]
 
-        const int tn = t + gridDim.x;
+        const int kn = k + gridDim.x;
+        const int tn = kn < nrun ? tile_at(list, kn) : 0;
         float xr0 = 0.f, xr1 = 0.f;
-        if (tn < ntiles) {
+        if (kn < nrun) {
             xr0 = x_fetch(tn, tid);
             xr1 = x_fetch(tn, tid + 256);
         }
@@ -2208,19 +2470,20 @@ __global__ __launch_bounds__(256, 2) void k_encoder_i8(const float *__restrict__
         __syncthreads();
         // [stamp:T7]
         // [stamp:accumulate]
+        t = tn;
     }
     // [stamp:end]
 }
 
 template <bool TOKENS>
 static hipError_t launch_i8_t(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e, float *features,
-                              hipStream_t st) {
+                              hipStream_t st, EncoderSkip *skip) {
     const int PS = H / 32;
     const int tiles_x = W / B3_TW, tiles_per_frame = tiles_x * (H / B3_TH), ntiles = tiles_per_frame * B;
     int lg_tx = 0, lg_tpf = 0;
     while ((1 << lg_tx) < tiles_x) ++lg_tx;
     while ((1 << lg_tpf) < tiles_per_frame) ++lg_tpf;
-    if ((1 << lg_tx) != tiles_x || (1 << lg_tpf) != tiles_per_frame) return hipErrorInvalidValue;
+    if ((1 << lg_tx) != tiles_x || (1 << lg_tpf) != tiles_per_frame || (PS != 2 && PS != 4 && PS != 8)) return hipErrorInvalidValue;
     constexpr size_t lds_bytes = I8_LDS_BYTES;
     const int num_cu = device_num_cu();
     const int wgs_per_cu = device_cached_int((const void *)k_encoder_i8<8, TOKENS>, [] {
@@ -2228,22 +2491,31 @@ static hipError_t launch_i8_t(const float *frames, int64_t fstride, int B, int H
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k_encoder_i8<8, TOKENS>, 256, I8_LDS_BYTES) != hipSuccess || n < 1) n = 2;
         return enc_knobs().wgs_per_cu ? enc_knobs().wgs_per_cu : n;
     });
-    int nwg = num_cu * wgs_per_cu;
-    if (nwg > ntiles) nwg = ntiles;
-    dim3 grid(nwg), block(256);
-    switch (PS) {
-        case 2: hipLaunchKernelGGL((k_encoder_i8<2, TOKENS>), grid, block, lds_bytes, st, frames, fstride, H, W, e, features, lg_tx, lg_tpf, ntiles); break;
-        case 4: hipLaunchKernelGGL((k_encoder_i8<4, TOKENS>), grid, block, lds_bytes, st, frames, fstride, H, W, e, features, lg_tx, lg_tpf, ntiles); break;
-        case 8: hipLaunchKernelGGL((k_encoder_i8<8, TOKENS>), grid, block, lds_bytes, st, frames, fstride, H, W, e, features, lg_tx, lg_tpf, ntiles); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    // the fixed persistent grid, capped by the tile count of the call (never by the device-side list length)
+    auto run = [&](const float *fr, int64_t fs, int nt, float *out, const int *list, const int *count) -> hipError_t {
+        int nwg = num_cu * wgs_per_cu;
+        if (nwg > nt) nwg = nt;
+        dim3 grid(nwg), block(256);
+        switch (PS) {
+            case 2: hipLaunchKernelGGL((k_encoder_i8<2, TOKENS>), grid, block, lds_bytes, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, list, count); break;
+            case 4: hipLaunchKernelGGL((k_encoder_i8<4, TOKENS>), grid, block, lds_bytes, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, list, count); break;
+            default: hipLaunchKernelGGL((k_encoder_i8<8, TOKENS>), grid, block, lds_bytes, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, list, count); break;
+        }
+        return hipGetLastError();
+    };
+    SkipPlan plan;
+    hipError_t err = skip_prepare<2, TOKENS>(
+        skip, frames, fstride, B, H, W, features, lg_tx, ntiles, num_cu * wgs_per_cu, st,
+        [&](const float *zero_frame, float *table) { return run(zero_frame, (int64_t)H * W, tiles_per_frame, table, nullptr, nullptr); },
+        plan);
+    if (err != hipSuccess) return err;
+    return run(frames, fstride, ntiles, features, plan.list, plan.count);
 }
 
 hipError_t launch_encoder_i8(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e, float *features,
-                             bool tokens, hipStream_t st) {
-    return tokens ? launch_i8_t<true>(frames, fstride, B, H, W, e, features, st)
-                  : launch_i8_t<false>(frames, fstride, B, H, W, e, features, st);
+                             bool tokens, hipStream_t st, EncoderSkip *skip) {
+    return tokens ? launch_i8_t<true>(frames, fstride, B, H, W, e, features, st, skip)
+                  : launch_i8_t<false>(frames, fstride, B, H, W, e, features, st, skip);
 }
 
 }  // namespace smk

@@ -74,6 +74,13 @@ class HipEncoder:
                                                       out.data_ptr(), _lib.DTYPES[dtype], _lib.stream_ptr(self._dev)))
         return out
 
+    def skip_stats(self):
+        """(tiles_total, tiles_run) of this handle's last forward (smk_encoder_skip_stats; synchronises the current stream):
+        tiles_run < tiles_total when the tile scan found all-zero input windows, equal when every tile ran."""
+        total, run = C.c_int64(), C.c_int64()
+        _lib.check(self._L.smk_encoder_skip_stats(self._handle, C.byref(total), C.byref(run), _lib.stream_ptr(self._dev)))
+        return total.value, run.value
+
     def conv1_activations(self, x: torch.Tensor) -> torch.Tensor:
         x = self._frames(x)
         B, H, W = x.shape
