@@ -381,6 +381,13 @@ __device__ __forceinline__ void stv_sc1(__amdgpu_buffer_rsrc_t rs, unsigned byte
     }
 }
 
+// Which order a sweep of k_jacobi_band takes (see `sweep` there), and how its interior rows split around the barrier.
+// The persistent 4 x 8 instantiations sit at the 128-VGPR cap of a 1024-thread workgroup and would spill more in the pipelined order.
+constexpr bool jb_pipelined(int vec, int rpw, bool persist) { return !(persist && vec == 4 && rpw == 8); }
+// Interior rows computed ahead of the barrier (they cover the publish); the others follow the reads.  Measured at 6 and 8 rows per wave
+// (profiles/r07): one row ahead is the fastest split at 4 cells per lane; with none the stores are exposed, with all of them the reads.
+constexpr int jb_rows_before_barrier(int rpw) { return rpw > 2 ? 1 : 0; }
+
 template <int VEC, int RPW, int MODE, bool PERSIST = false, bool FOLD = false>
 __global__ __launch_bounds__(JB_NW * 64) void k_jacobi_band(Geom g, const float *__restrict__ p_in,
                                                             float *__restrict__ p_out, float *__restrict__ div,
@@ -549,60 +556,98 @@ __global__ __launch_bounds__(JB_NW * 64) void k_jacobi_band(Geom g, const float 
     }
     // ring rows (grid row 0 / H-1) exist only in the first wave of the first band and the last wave of the last band
     const int ring_k = __builtin_amdgcn_readfirstlane(row0 == 0 ? 0 : (row0 + RPW == g.H ? RPW - 1 : -1));   // wave-uniform
-    // one sweep src -> dst (register ping-pong: no row copies); par selects the LDS edge buffer
-    auto sweep = [&](const float (&src)[RPW][VEC], float (&dst)[RPW][VEC], int par) {
+    static_assert(RPW >= 2, "the sweep keeps a wave's first and last row apart");
+    // one row of a sweep src -> dst; up / dn: the rows above and below (registers, or the neighbour wave's edge row)
+    auto row = [&](const float (&src)[RPW][VEC], float (&dst)[RPW][VEC], int k, const float (&up)[VEC], const float (&dn)[VEC]) {
+        const float lin = wave_shr1(src[k][VEC - 1]), rin = wave_shl1(src[k][0]);
 #pragma unroll
         for (int c = 0; c < VEC; ++c) {
-            edge[par][wave][0][j0 + c] = src[0][c];
-            edge[par][wave][1][j0 + c] = src[RPW - 1][c];
+            const float l = c > 0 ? src[k][c - 1] : lin;
+            const float r = c < VEC - 1 ? src[k][c + 1] : rin;
+            float sm = up[c] + dn[c];
+            sm = sm + l;
+            sm = sm + r;
+            sm = sm - dv[k][c];
+            dst[k][c] = 0.25f * sm;
         }
-        __builtin_amdgcn_sched_barrier(0);                    // publish first: the neighbours' edge rows wait on these stores
-        // one row of the sweep; up / dn: the rows above and below (registers, or the neighbour wave's edge row)
-        auto row = [&](int k, const float (&up)[VEC], const float (&dn)[VEC]) {
-            const float lin = wave_shr1(src[k][VEC - 1]), rin = wave_shl1(src[k][0]);
+        dst[k][0] = first_col ? 0.f : dst[k][0];              // column ring: only the two edge cells need a select
+        dst[k][VEC - 1] = last_col ? 0.f : dst[k][VEC - 1];
+    };
+    // a wave's first and last row go to edge buffer `par`; the neighbour waves' facing rows come back from it (after a barrier)
+    auto publish = [&](const float (&r)[RPW][VEC], int par) {
 #pragma unroll
-            for (int c = 0; c < VEC; ++c) {
-                const float l = c > 0 ? src[k][c - 1] : lin;
-                const float r = c < VEC - 1 ? src[k][c + 1] : rin;
-                float sm = up[c] + dn[c];
-                sm = sm + l;
-                sm = sm + r;
-                sm = sm - dv[k][c];
-                dst[k][c] = 0.25f * sm;
-            }
-            dst[k][0] = first_col ? 0.f : dst[k][0];          // column ring: only the two edge cells need a select
-            dst[k][VEC - 1] = last_col ? 0.f : dst[k][VEC - 1];
-        };
-        // The sweep is bound by publish -> barrier -> read -> compute, not by VALU throughput: the rows that need nothing from
-        // the neighbour waves (1 .. RPW-2) are computed BEFORE the barrier, under the wait; only the two edge rows follow it.
-#pragma unroll
-        for (int k = 1; k < RPW - 1; ++k) row(k, src[k - 1], src[k + 1]);
-        __builtin_amdgcn_sched_barrier(0);                    // (hipcc otherwise sinks these rows below the barrier)
-        __syncthreads();
+        for (int c = 0; c < VEC; ++c) {
+            edge[par][wave][0][j0 + c] = r[0][c];
+            edge[par][wave][1][j0 + c] = r[RPW - 1][c];
+        }
+    };
+    float above[VEC], below[VEC];
+    auto fetch = [&](int par) {
         const float *eu = &edge[par][wave > 0 ? wave - 1 : 0][1][j0];            // top wave: value unused (ring or halo row)
         const float *ed = &edge[par][wave < JB_NW - 1 ? wave + 1 : JB_NW - 1][0][j0];
-        float above[VEC], below[VEC];
 #pragma unroll
         for (int c = 0; c < VEC; ++c) {
             above[c] = eu[c];
             below[c] = ed[c];
         }
-        if (RPW == 1) {
-            row(0, above, below);
-        } else {
-            row(0, above, src[1]);
-            row(RPW - 1, src[RPW - 2], below);
-        }
-        // row ring (grid row 0 / H-1: 2 waves of a grid): wave-uniform selects -- as scalar branches they cost more in register
-        // copies at the control-flow merges (16 v_mov per sweep) than the 2 * VEC v_cndmask they save
+    };
+    // the two rows that need `above` / `below`, with the row ring (grid row 0 / H-1: 2 waves of a grid) as wave-uniform selects -- as
+    // scalar branches they cost more in register copies at the control-flow merges (16 v_mov per sweep) than the 2 * VEC v_cndmask
+    // they save
+    auto edge_rows = [&](const float (&src)[RPW][VEC], float (&dst)[RPW][VEC]) {
+        row(src, dst, 0, above, src[1]);
+        row(src, dst, RPW - 1, src[RPW - 2], below);
 #pragma unroll
         for (int c = 0; c < VEC; ++c) {
             dst[0][c] = ring_k == 0 ? 0.f : dst[0][c];
             dst[RPW - 1][c] = ring_k == RPW - 1 ? 0.f : dst[RPW - 1][c];
         }
     };
+    // One sweep src -> dst (register ping-pong: no row copies); par selects the LDS edge buffer.  The order is software-pipelined over two
+    // sweeps (PIPE): `above` / `below` of src are already in registers when a sweep starts (run() primes them); the wave first computes the
+    // two rows that need them and publishes those rows of dst -- the NEXT sweep's edge rows -- into the other buffer, covers the stores with
+    // NA interior rows, passes the barrier, issues the reads of the next sweep's `above` / `below`, and covers those with the remaining
+    // interior rows: no wave waits on an LDS trip with nothing to issue.  What a sweep then costs is the vector issue of its rows, which the
+    // four waves of a SIMD take in turns, the youngest last, the others waiting for it at the barrier (stamps: DESIGN 3.1, profiles/r07).
+    // Buffer s & 1 is rewritten in sweep s + 2, after barrier s + 1, which every wave passes only after it has consumed (in sweep
+    // s + 1's first two rows) what it read from buffer s.  RPW 2 / 3 have 0 / 1 interior rows: the same chain as the plain order.
+    // Plain order (PIPE false): publish src's edge rows, interior rows, barrier, read, the two edge rows.
+    constexpr bool PIPE = jb_pipelined(VEC, RPW, PERSIST);
+    constexpr int NA = jb_rows_before_barrier(RPW);           // interior rows ahead of the barrier (cover the stores); the rest follow the reads
+    auto sweep = [&](const float (&src)[RPW][VEC], float (&dst)[RPW][VEC], int par) {
+        if constexpr (PIPE) {
+            edge_rows(src, dst);
+            publish(dst, par);
+            __builtin_amdgcn_sched_barrier(0);                // first: the neighbours' next sweep waits on these stores
+#pragma unroll
+            for (int k = 1; k < 1 + NA; ++k) row(src, dst, k, src[k - 1], src[k + 1]);
+            __builtin_amdgcn_sched_barrier(0);                // (hipcc otherwise sinks these rows below the barrier)
+            __syncthreads();
+            fetch(par);
+            __builtin_amdgcn_sched_barrier(0);                // reads in flight before the rows that cover them
+#pragma unroll
+            for (int k = 1 + NA; k < RPW - 1; ++k) row(src, dst, k, src[k - 1], src[k + 1]);
+            __builtin_amdgcn_sched_barrier(0);                // (the wait for the reads belongs to the next sweep's first rows)
+        } else {
+            publish(src, par);
+            __builtin_amdgcn_sched_barrier(0);                // publish first: the neighbours' edge rows wait on these stores
+#pragma unroll
+            for (int k = 1; k < RPW - 1; ++k) row(src, dst, k, src[k - 1], src[k + 1]);
+            __builtin_amdgcn_sched_barrier(0);                // (hipcc otherwise sinks these rows below the barrier)
+            __syncthreads();
+            fetch(par);
+            edge_rows(src, dst);
+        }
+    };
     float pw[RPW][VEC];
     auto run = [&](int n) {                                   // n sweeps, result in pv
+        if constexpr (PIPE) {
+            // prime the pipeline: pv's own edge rows (after a hand-off: with the halo rows just reloaded) through buffer 1, which the
+            // first sweep leaves alone.  Every caller has a workgroup barrier between a run's last reads and this store.
+            publish(pv, 1);
+            __syncthreads();
+            fetch(1);
+        }
         int it = 0;
         for (; it + 2 <= n; it += 2) {
             sweep(pv, pw, 0);
@@ -779,12 +824,19 @@ static bool plan_jacobi(const Geom &g, JacobiPlan &pl, int iters = 100, bool per
             }
             const int br = halo;                              // handed to the kernel (it derives the owned ranges from it)
             const double wgs = (double)nb * g.B, rounds = ceil(wgs / 256.0);
-            // measured on MI355X (256^2 x 64, profiles/r01): ~6 us fixed per launch, ~1.33 us per sweep at 96 rows per
-            // workgroup (barrier + LDS round trip bound, roughly linear in the rows a CU owns)
-            const double cost_per_sweep = rounds * TR * (1.33 / 96.0), launch = 6.0;
-            // a relaunch reloads the band's p and div (~6 us with the boundary); a hand-off inside the persistent launch moves 2 * halo rows
-            // per band through sc1 stores / flag / sc1 loads (~3.5 us)
-            const double cost = persist ? launch + (ceil((double)iters / halo) - 1) * 3.5 + iters * cost_per_sweep
+            // measured on MI355X with the pipelined sweep (profiles/r07/planner_fit.json: 256 rows x 64 grids at 6 rows per wave, J = 20 / 40 /
+            // 60 / 100, and the nearest plans of 128^2 x 32 / x 64 at J = 20): a sweep of a 96-row workgroup takes 0.32 / 0.51 / 0.83 us at 1 / 2 /
+            // 4 cells per lane, roughly linear in the rows a CU owns; prologue, loads and the gradient cost a row about 13 sweeps' worth; a
+            // hand-off inside the persistent launch (2 * halo rows per band through sc1 stores / flag / sc1 loads) 2.8 us; a launch ~6 us, and
+            // a relaunch reloads the band's p and div (~6 us with the boundary)
+            const double cost_per_sweep = rounds * TR * ((0.15 + 0.17 * pl.vec) / 96.0), launch = 6.0, handoff = 2.8, fixed_sweeps = 13.0;
+            int chunks = 1;                                   // as persist_chunks() will cut the sweeps
+            if (persist && nb > 1) {
+                chunks = (iters + halo - 1) / halo;
+                if (chunks < 2) chunks = 2;
+                while (chunks < iters && ((iters + chunks - 1) / chunks > halo || iters / chunks > halo - 1)) ++chunks;
+            }
+            const double cost = persist ? launch + (chunks - 1) * handoff + (iters + fixed_sweeps) * cost_per_sweep
                                         : 2 * ceil(0.5 * iters / halo) * launch + iters * cost_per_sweep;
             if (cost < best) { best = cost; pl.rpw = rpw; pl.br = br; pl.nb = nb; pl.halo = halo; ok = true; }
         }
@@ -1027,7 +1079,7 @@ hipError_t launch_buoy_project(const Geom &g, StateView in, StateView out, float
 // Jacobi sweeps never touch HBM, so what limits them is sweeps x rows per workgroup x vector-issue time, not bytes).
 std::string describe_projection(const Geom &g, int iters, const ProjectSync *ps) {
     JacobiPlan pl;
-    char buf[1280];
+    char buf[1792];
     int chunks = 0;
     const bool persist = use_persist(g, ps, iters, pl, chunks);
     if (!persist && (iters < 2 || !plan_jacobi(g, pl, iters) || pl.halo < 3)) {
@@ -1041,16 +1093,22 @@ std::string describe_projection(const Geom &g, int iters, const ProjectSync *ps)
     const int parts = persist ? chunks : L;                   // runs of sweeps between two refreshes of the halo rows
     const double wgs = (double)pl.nb * g.B, rounds = ceil(wgs / device_num_cu());
     // measured (tools/probes/valu_probe, 4 waves per SIMD): a sweep row of 64 VEC-cell lanes = ~18 vector instructions of which 2 are DPP
-    // wave shifts, ~2.6 cycles per instruction and SIMD -> TR rows on 4 SIMDs; plus the publish -> s_barrier -> read round trip per sweep
+    // wave shifts, ~2.6 cycles per instruction and SIMD -> TR rows on 4 SIMDs.  The edge-row exchange (publish -> s_barrier -> read) is
+    // software-pipelined under those rows; what the in-kernel stamps show beyond the estimate is the four waves of a SIMD taking turns at its
+    // vector issue, the youngest last, with the others waiting for it at the sweep's barrier (profiles/r07)
     const double valu_us_per_sweep = rounds * (TR / 4.0) * 18.0 * 2.6 / 2100.0;
     snprintf(buf, sizeof buf,
              "{\"kernel\": \"k_jacobi_band<%d,%d>\", \"persistent\": %s, \"bands_per_grid\": %d, \"rows_per_workgroup\": %d, \"halo_rows\": %d, "
              "\"workgroups\": %d, \"launches\": %d, \"halo_handoffs\": %d, \"sweeps\": %d, \"sweeps_per_chunk\": %d, \"redundant_row_factor\": %.3f, "
              "\"vector_issue_us_per_sweep_estimate\": %.3f, \"vector_issue_us_total_estimate\": %.1f, "
-             "\"bound\": \"on-chip: sweeps x (vector issue of rows_per_workgroup rows + one LDS publish/barrier/read round trip); p and div are "
+             "\"bound\": \"on-chip: sweeps x vector issue of rows_per_workgroup rows, one barrier per sweep (%s); p and div are "
              "register-resident %s\"}",
              pl.vec, pl.rpw, persist ? "true" : "false", pl.nb, TR, pl.halo, (int)wgs, L, persist ? chunks - 1 : 0, iters, (iters + parts - 1) / parts,
              (double)pl.nb * TR / g.H, valu_us_per_sweep, valu_us_per_sweep * iters,
+             jb_pipelined(pl.vec, pl.rpw, persist)
+                 ? "the LDS edge-row exchange is pipelined over two sweeps: a wave's two edge rows and their publish come first, the interior rows "
+                   "cover the stores and the read of the next sweep's neighbour rows"
+                 : "plain order at the register cap: publish, interior rows, barrier, read of the neighbour rows, the two edge rows",
              persist ? "for the whole projection; bands hand halo rows to their neighbours through HBM between chunks" : "within a launch");
     return buf;
 }
