@@ -265,12 +265,13 @@ int smk_encoder_destroy(smk_encoder *enc);
  * Requires H == W, H % 32 == 0, and input_dim a multiple/divisor of H (then the two pools compose to an
  * (H/32)^2 block mean); anything else returns SMK_ERR_UNSUPPORTED.
  * Tile skip (SMK_BF16X3, SMK_BF16, SMK_I8X3; both smk_encoder_forward and smk_encoder_forward_tokens): when a call has more 8 x 16
- * tiles than the device runs workgroups, a scan pass first finds the tiles whose 16 x 24 input window is all-zero words, fills
- * their features from the handle's zero-response table (the same kernel's output for an all-zero frame: bit-identical to computing
- * them) and hands the main kernel a compact list of the others.  Dense input keeps the cost of the scan (about 1 %); SMK_ENC_SKIP=0
+ * tiles than the device runs workgroups, a scan launch first finds the tiles whose 16 x 24 input window is all-zero words and leaves
+ * one bit per tile; the main kernel's workgroups derive their tiles from those bits themselves and copy the features of the empty
+ * tiles from the handle's zero-response table (the same kernel's output for an all-zero frame: bit-identical to computing them).
+ * Two launches per call; dense input keeps the cost of the scan (about 0.5 %); SMK_ENC_SKIP=0
  * (read once per process) runs every tile.  Table and workspace live in the handle, are built on the first eligible call outside
  * stream capture, and are reused by every later call: CALLS ON ONE HANDLE MUST BE STREAM-ORDERED (one stream, or ordered by events);
- * two forwards of one handle running concurrently on different streams would share the tile list.  Nothing in the forward copies
+ * two forwards of one handle running concurrently on different streams would share the tile bits.  Nothing in the forward copies
  * to the host or synchronises, and every launch can be captured into a graph. */
 int smk_encoder_forward(smk_encoder *enc, const float *frames, int64_t frame_stride, int32_t B, int32_t H,
                         int32_t W, int32_t input_dim, float *features, int32_t dtype, void *stream);

@@ -25,8 +25,8 @@ struct EncoderDev {
 struct EncoderSkip {
     std::mutex mu;
     float *table[3][3][2] = {};       // zero-response tables [form: bf16x3 | bf16 | i8x3][H: 64 | 128 | 256][layout: NCHW | tokens]
-    int *ws = nullptr;                // workspace: list length, band masks, tile list for ws_tiles tiles
-    size_t ws_tiles = 0;
+    int *ws = nullptr;                // workspace: tiles run (written by the main kernel), band masks for ws_bands bands
+    size_t ws_bands = 0;
     std::vector<void *> retired;      // outgrown workspaces (captured graphs may still name them)
     int64_t last_total = 0;           // tiles of the last forward ...
     const int *last_count = nullptr;  // ... and where the device keeps how many of them ran (null: direct path, all ran)

@@ -352,25 +352,166 @@ constexpr int B3_W1_BYTES = 64 * B3_W1_PITCH;            // 9216 per part
 constexpr int B3_ST_BYTES = 2 * 64 * 4;                  // BN1 scale | shift
 template <bool X3> constexpr int b3_lds_total() { return b3_lds_bytes<X3>() + (X3 ? 2 : 1) * B3_W1_BYTES + B3_ST_BYTES; }   // 73,136 (x3)
 
-// Work list of the persistent kernels.  Direct path (list == nullptr): entry k is tile k, all ntiles tiles run.  Skip path: the
-// compact list and its length come from k_encoder_tile_scan / k_encoder_tile_scan_pack, launched before on the same stream (a
-// kernel boundary orders them); tiles not on the list were already written by the scan.  k is wave-uniform, so both are scalar
-// loads; a list of all ntiles tiles (dense input) is not read at all.
-__device__ __forceinline__ int tiles_to_run(const int *__restrict__ list, const int *__restrict__ count, int ntiles) {
-    return list ? __builtin_amdgcn_readfirstlane(*count) : ntiles;
-}
-__device__ __forceinline__ int tile_at(const int *__restrict__ list, int k) {
-    return list ? __builtin_amdgcn_readfirstlane(list[k]) : k;
+// Work list of the persistent kernels.  Direct path (sa.masks == nullptr): entry k is tile k, all ntiles tiles run.  Skip path:
+// entry k is the k-th non-empty tile in ascending order, found by every workgroup itself from the band masks that
+// k_encoder_tile_scan wrote before on the same stream (a kernel boundary orders them; bit i of mask j = tile j * band_tiles + i).
+//   tiles_to_run  once per workgroup: thread c sums the popcounts of chunk c of the masks (SKIP_CHUNKS chunks of
+//                 ceil(nbands / SKIP_CHUNKS) bands each, so the array is fixed and the band count is not), an exclusive scan over
+//                 the chunks stays in LDS for the whole kernel, the total is the number of tiles to run.
+//   skip_lookup   rank k -> tile: binary search for the chunk that holds rank k, walk its masks, select the n-th set bit.
+//   skip_slate    the first SKIP_SLATE lanes look up the workgroup's next SKIP_SLATE rounds (k = blockIdx.x + round * gridDim.x) at
+//                 once: one lookup's latency per SKIP_SLATE tiles, paid in the prologue beside the weight loads; inside the tile loop
+//                 tile_at is one LDS word.  A launch of more rounds refills the slate every SKIP_SLATE rounds.
+// All masks full (dense input): the list is the identity, nothing is looked up.
+struct SkipArgs {
+    const unsigned long long *masks = nullptr;              // null: direct path
+    int *count = nullptr;                                     // workgroup 0 stores the number of tiles run (smk_encoder_skip_stats)
+    const float *table = nullptr;                             // the call's zero-response table: what an empty tile's cells hold
+    int nbands = 0, lg_band_tiles = 0, bands_per_frame = 0;
+};
+constexpr int SCAN_ROWS = 4;                                  // tile rows per band: <= 64 tiles at W = 256 (one mask word)
+constexpr int ENC_FRAME_FEATS = 128 * 1024;                   // features per frame, either layout
+constexpr int SKIP_CHUNKS = 256, SKIP_SLATE = 16;
+struct SkipLds {
+    int cpre[SKIP_CHUNKS + 1];                                // tiles to run before chunk c; [SKIP_CHUNKS] = all of them
+    int wsum[4];
+    int slate[SKIP_SLATE];                                    // tile of round (r0 + i), r0 a multiple of SKIP_SLATE
+};
+
+__device__ __forceinline__ int skip_lookup(const SkipLds &s, const SkipArgs &sa, int k) {
+    int c = 0;                                                // the largest c with cpre[c] <= k: chunk c holds rank k (k < total)
+#pragma unroll
+    for (int step = SKIP_CHUNKS / 2; step >= 1; step >>= 1)
+        if (s.cpre[c + step] <= k) c += step;
+    int n = k - s.cpre[c];
+    int j = c * ((sa.nbands + SKIP_CHUNKS - 1) / SKIP_CHUNKS);
+    unsigned long long m = sa.masks[j];
+    for (int pc = __popcll(m); n >= pc; pc = __popcll(m)) {   // ends inside the chunk: it holds rank k
+        n -= pc;
+        m = sa.masks[++j];
+    }
+    int pos = 0;                                              // the n-th set bit of m (n < popcount)
+#pragma unroll
+    for (int w = 32; w >= 1; w >>= 1) {
+        const int cnt = __popcll((m >> pos) & ((1ull << w) - 1));
+        if (n >= cnt) {
+            n -= cnt;
+            pos += w;
+        }
+    }
+    return (j << sa.lg_band_tiles) + pos;
 }
 
-// Persistent: each workgroup walks work-list entries k = blockIdx.x, +gridDim.x, ... (t = tile_at(list, k)).  Per-workgroup
+// rounds r0 .. r0 + SKIP_SLATE - 1 of this workgroup -> s.slate (the caller's barrier publishes it)
+__device__ __forceinline__ void skip_slate(SkipLds &s, const SkipArgs &sa, int r0, int nrun) {
+    const int i = threadIdx.x;
+    if (i < SKIP_SLATE) {
+        const long long k = (long long)blockIdx.x + (long long)(r0 + i) * gridDim.x;
+        if (k < nrun) s.slate[i] = skip_lookup(s, sa, (int)k);
+    }
+}
+
+// Number of work-list entries (workgroup-uniform; all 256 threads call it, it holds barriers); leaves the chunk sums and, unless
+// the list is the identity, the slate of rounds 0 .. SKIP_SLATE - 1 in LDS.
+__device__ __forceinline__ int tiles_to_run(SkipLds &s, const SkipArgs &sa, int ntiles) {
+    if (!sa.masks) return ntiles;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int cs = (sa.nbands + SKIP_CHUNKS - 1) / SKIP_CHUNKS;
+    int c = 0;
+    for (int j = tid * cs, je = min(j + cs, sa.nbands); j < je; ++j) c += __popcll(sa.masks[j]);
+    int inc = c;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int v = __shfl_up(inc, d);
+        if (lane >= d) inc += v;
+    }
+    if (lane == 63) s.wsum[wave] = inc;
+    __syncthreads();
+    int base = 0;
+    for (int w = 0; w < wave; ++w) base += s.wsum[w];
+    s.cpre[tid] = base + inc - c;
+    if (tid == SKIP_CHUNKS - 1) s.cpre[SKIP_CHUNKS] = base + inc;
+    __syncthreads();
+    const int nrun = __builtin_amdgcn_readfirstlane(s.cpre[SKIP_CHUNKS]);
+    if (blockIdx.x == 0 && tid == 0) *sa.count = nrun;
+    if (nrun != ntiles) {
+        skip_slate(s, sa, 0, nrun);
+        __syncthreads();
+    }
+    return nrun;
+}
+// Entry k = blockIdx.x + round * gridDim.x of the list (k < nrun).  Workgroup-uniform; at a multiple of SKIP_SLATE > 0 it refills
+// the slate behind a barrier, so every thread of the workgroup calls it at the same place.
+__device__ __forceinline__ int tile_at(SkipLds &s, const SkipArgs &sa, bool listed, int round, int k, int nrun) {
+    if (!listed) return k;
+    if (round > 0 && (round & (SKIP_SLATE - 1)) == 0) {
+        skip_slate(s, sa, round, nrun);                       // the slate's last reader is one barrier back at least
+        __syncthreads();
+    }
+    return __builtin_amdgcn_readfirstlane(s.slate[round & (SKIP_SLATE - 1)]);
+}
+
+// The empty tiles' pooled cells, copied from the zero-response table (same offsets within the frame).  Partitioned by band straight
+// from the masks: workgroup g takes bands g, g + gridDim.x, ...  Empty and non-empty tiles are disjoint words of the features, so the
+// copy needs no ordering against the tile loop; it runs outside it (four loads in flight per thread, nothing live across a tile).
+// The stores are non-temporal: 31 MB per headline launch that nothing in the launch reads again, beside a K loop whose weight
+// fragments come from L2.
+template <int PS, bool TOKENS>
+__device__ __forceinline__ void skip_fill(const SkipArgs &sa, int lg_tiles_x, float *__restrict__ features) {
+    constexpr int CR = B3_TH / PS, CC = B3_TW / PS;           // cells per tile: rows x columns
+    // token-major: a cell row of a tile is CC cells x 128 channels, contiguous (float4).  NCHW: a channel's CC cells of one row.
+    constexpr int VW = TOKENS ? 4 : (CC < 4 ? CC : 4), VPR = TOKENS ? 1 : CC / VW, ROWV = CC * 32;
+    constexpr int UPT = TOKENS ? CR * ROWV : 128 * CR * VPR;  // vectors per tile
+    constexpr int UNR = 4;
+    typedef float vec_t __attribute__((ext_vector_type(VW)));
+    const int tid = threadIdx.x, tiles_x = 1 << lg_tiles_x, band_tiles = 1 << sa.lg_band_tiles, total = band_tiles * UPT;
+    const unsigned long long full = band_tiles == 64 ? ~0ull : (1ull << band_tiles) - 1;
+    for (int band = blockIdx.x; band < sa.nbands; band += gridDim.x) {
+        const unsigned long long mv = sa.masks[band];
+        const unsigned long long m = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned int)(mv >> 32)) << 32) |
+                                     (unsigned int)__builtin_amdgcn_readfirstlane((unsigned int)mv);
+        if (m == full) continue;
+        const int b = band / sa.bands_per_frame, ty0 = (band - b * sa.bands_per_frame) * SCAN_ROWS;
+        float *out = features + (size_t)b * ENC_FRAME_FEATS;
+        for (int i0 = tid; i0 < total; i0 += 256 * UNR) {
+            vec_t v[UNR];
+            int off[UNR];
+#pragma unroll
+            for (int j = 0; j < UNR; ++j) {
+                const int i = i0 + 256 * j, tl = i / UPT, u = i - tl * UPT;
+                off[j] = -1;
+                if (i >= total || ((m >> tl) & 1)) continue;
+                const int ty = ty0 + (tl >> lg_tiles_x), tx = tl & (tiles_x - 1);
+                if (TOKENS) {
+                    const int a = u / ROWV, q = u - a * ROWV;
+                    off[j] = ((ty * CR + a) * 32 + tx * CC) * 128 + q * 4;
+                } else {
+                    const int vv = u % VPR, a = (u / VPR) % CR, o = u / (VPR * CR);
+                    off[j] = o * 1024 + (ty * CR + a) * 32 + tx * CC + vv * VW;
+                }
+                v[j] = *reinterpret_cast<const vec_t *>(sa.table + off[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < UNR; ++j)
+                if (off[j] >= 0) __builtin_nontemporal_store(v[j], reinterpret_cast<vec_t *>(out + off[j]));
+        }
+    }
+}
+// When a workgroup copies.  The second dispatch round (the workgroups that share a CU with one of the first round) copies before
+// its first tile, in place of the start delay that takes it out of phase with its partner (see the stagger below); the first round
+// copies after its last tile, while the partner, started later, is still in its K loop.  Either way the copy of one workgroup runs
+// beside the matrix work of the other.  Measured against "all after", "all before" and "only workgroups with a round to spare":
+// DESIGN.md 3.2.
+__device__ __forceinline__ bool skip_fill_first() { return (blockIdx.x / 256) & 1; }
+
+// Persistent: each workgroup walks work-list entries k = blockIdx.x, +gridDim.x, ... (t = tile_at(..., k)).  Per-workgroup
 // costs (conv1 weights -> LDS, BN2 scale/shift, B-ring fill) are paid once; the next tile's x halo is prefetched into registers under the K loop and
 // the B-fragment ring simply keeps running across tiles (the weights do not depend on the tile).
 template <bool X3, int PS, bool TOKENS>
 __global__ __launch_bounds__(256, 2) void k_encoder_bf16(const float *__restrict__ frames, int64_t fstride, int H, int W,
                                                       EncoderDev e, float *__restrict__ features, int lg_tiles_x,
                                                       int lg_tiles_per_frame, int ntiles, int stagger,
-                                                      const int *__restrict__ list, const int *__restrict__ count) {
+                                                      SkipArgs sa) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *xs = reinterpret_cast<float *>(smem);
     unsigned char *a1h = smem + B3_XS_BYTES, *a1l = a1h + B3_A1_BYTES;
@@ -423,13 +564,17 @@ __global__ __launch_bounds__(256, 2) void k_encoder_bf16(const float *__restrict
         return ok ? frames[(size_t)bb * fstride + (size_t)ii * W + jj] : 0.f;
     };
     int k = blockIdx.x;
-    const int nrun = tiles_to_run(list, count, ntiles);
-    if (nrun == ntiles) list = nullptr;                       // a complete list is ascending, i.e. the identity: no list loads
-    int t = k < nrun ? tile_at(list, k) : 0;
+    __shared__ SkipLds skl;
+    const int nrun = tiles_to_run(skl, sa, ntiles);
+    const bool listed = nrun != ntiles;                       // a complete list is ascending, i.e. the identity: no lookups
+    int round = 0;
+    int t = k < nrun ? tile_at(skl, sa, listed, 0, k, nrun) : 0;
     // Workgroups that share a CU run the same program with the same period; started together they stay in lockstep
     // (both in the VALU-heavy conv1 phase, then both in the MFMA loop).  Delay every other dispatch round by about
     // half a tile so that one workgroup's conv1 overlaps the other's K loop (speed only, never correctness).
-    if (stagger > 0 && ((blockIdx.x / 256) & 1))
+    // On the skip path that round copies its share of the empty tiles' cells instead (skip_fill_first): the same shift, not idle.
+    if (listed && skip_fill_first()) skip_fill<PS, TOKENS>(sa, lg_tiles_x, features);
+    else if (stagger > 0 && ((blockIdx.x / 256) & 1))
         for (int i = 0; i < stagger; ++i) __builtin_amdgcn_s_sleep(127);
     if (k < nrun) {
         xs[tid] = x_fetch(t, tid);
@@ -529,7 +674,8 @@ __global__ __launch_bounds__(256, 2) void k_encoder_bf16(const float *__restrict
 
         // next tile's x halo -> registers (lands under the K loop)
         const int kn = k + gridDim.x;
-        const int tn = kn < nrun ? tile_at(list, kn) : 0;
+        ++round;
+        const int tn = kn < nrun ? tile_at(skl, sa, listed, round, kn, nrun) : 0;
         float xr0 = 0.f, xr1 = 0.f;
         if (kn < nrun) {
             xr0 = x_fetch(tn, tid);
@@ -647,6 +793,10 @@ __global__ __launch_bounds__(256, 2) void k_encoder_bf16(const float *__restrict
         __syncthreads();
         t = tn;
     }
+    if (listed && !skip_fill_first()) {
+        __builtin_amdgcn_s_setprio(0);
+        skip_fill<PS, TOKENS>(sa, lg_tiles_x, features);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -675,7 +825,7 @@ template <int PS, bool TOKENS>
 __global__ __launch_bounds__(256, 2) void k_encoder_b16(const float *__restrict__ frames, int64_t fstride, int H, int W,
                                                      EncoderDev e, float *__restrict__ features, int lg_tiles_x,
                                                      int lg_tiles_per_frame, int ntiles, int stagger,
-                                                     const int *__restrict__ list, const int *__restrict__ count) {
+                                                     SkipArgs sa) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // x tile kept already split: one word per pixel, hi bf16 in the low half, lo bf16 in the high half (split once by the staging
     // thread; every wave's fragment builder then needs one v_perm_b32 per element pair instead of two 3-instruction splits)
@@ -736,10 +886,13 @@ __global__ __launch_bounds__(256, 2) void k_encoder_b16(const float *__restrict_
         return (unsigned int)__builtin_bit_cast(unsigned short, vh) | ((unsigned int)__builtin_bit_cast(unsigned short, vl) << 16);
     };
     int k = blockIdx.x;
-    const int nrun = tiles_to_run(list, count, ntiles);
-    if (nrun == ntiles) list = nullptr;                       // a complete list is ascending, i.e. the identity: no list loads
-    int t = k < nrun ? tile_at(list, k) : 0;
-    if (stagger > 0 && ((blockIdx.x / 256) & 1))
+    __shared__ SkipLds skl;
+    const int nrun = tiles_to_run(skl, sa, ntiles);
+    const bool listed = nrun != ntiles;                       // a complete list is ascending, i.e. the identity: no lookups
+    int round = 0;
+    int t = k < nrun ? tile_at(skl, sa, listed, 0, k, nrun) : 0;
+    if (listed && skip_fill_first()) skip_fill<PS, TOKENS>(sa, lg_tiles_x, features);
+    else if (stagger > 0 && ((blockIdx.x / 256) & 1))
         for (int i = 0; i < stagger; ++i) __builtin_amdgcn_s_sleep(127);
     if (k < nrun) {
         xs[tid] = pack_split(x_fetch(t, tid));
@@ -846,7 +999,8 @@ __global__ __launch_bounds__(256, 2) void k_encoder_b16(const float *__restrict_
         __builtin_amdgcn_s_setprio(S16_PRIO_KLOOP);
 
         const int kn = k + gridDim.x;
-        const int tn = kn < nrun ? tile_at(list, kn) : 0;
+        ++round;
+        const int tn = kn < nrun ? tile_at(skl, sa, listed, round, kn, nrun) : 0;
         float xr0 = 0.f, xr1 = 0.f;
         if (kn < nrun) {
             xr0 = x_fetch(tn, tid);
@@ -997,6 +1151,10 @@ __global__ __launch_bounds__(256, 2) void k_encoder_b16(const float *__restrict_
         __syncthreads();
 #endif
         t = tn;
+    }
+    if (listed && !skip_fill_first()) {
+        __builtin_amdgcn_s_setprio(0);
+        skip_fill<PS, TOKENS>(sa, lg_tiles_x, features);
     }
 }
 
@@ -1822,28 +1980,26 @@ static const EncoderKnobs &enc_knobs() {
 // ---------------------------------------------------------------- tile skip: input windows that are all zero
 // A tile's result depends on its 16 x 24 input window (tile + 4 pixels each way, outside the image = zero) and on its position in the
 // frame, nothing else.  A tile whose window is all zero therefore equals the same tile of an all-zero frame, bit for bit, and the
-// simulator's frames are mostly background.  Before the persistent kernel (k_encoder_b16, k_encoder_bf16, k_encoder_i8):
+// simulator's frames are mostly background.  Two launches per call:
 //   k_encoder_tile_scan       one workgroup per band of SCAN_ROWS tile rows of a frame.  Reads the band's 32 + 8 image rows once
 //          (16-byte loads when the frames allow), keeps one flag per 4 x 4 pixel block in LDS (window edges fall on multiples of 4),
 //          ORs 4 x 6 flags per tile.  EMPTY means every 32-bit word of the window inside the image is 0x00000000: bits are compared,
-//          so -0.0, denormals, NaN and Inf all keep a tile on the normal path.  Empty tiles get their pooled cells copied from the
-//          handle's zero-response table (the same kernel form's output for one all-zero frame, in the layout of the call); the
-//          band's non-empty tiles go out as one 64-bit mask.
-//   k_encoder_tile_scan_pack  one wave per band: its offset = the popcounts of all earlier masks (each workgroup sums them itself), its
-//          lanes write the band's tiles in order -> ascending list of the tiles to run and its length in device memory.  Every word the main kernel reads is rewritten by these two launches each call, so nothing needs a
-//          reset, nothing is read back by the host, the list is the same on every run, and all three launches are capturable.
-// No workgroup waits for another one; kernel boundaries order scan, pack and main kernel.
-constexpr int SCAN_ROWS = 4;                                  // tile rows per band: <= 64 tiles at W = 256 (one mask word)
+//          so -0.0, denormals, NaN and Inf all keep a tile on the normal path.  The band's non-empty tiles go out as one 64-bit
+//          mask; that is all it writes.
+//   the main kernel (k_encoder_b16, k_encoder_bf16, k_encoder_i8) reads the masks: tiles_to_run / tile_at turn them into "my k-th
+//          tile" inside every workgroup (no list in memory, no pack launch), skip_fill copies the empty tiles' pooled cells from the
+//          handle's zero-response table (the same kernel form's output for one all-zero frame, in the layout of the call) outside the
+//          tile loop, and workgroup 0 stores the number of tiles run for smk_encoder_skip_stats.
+// Every word the main kernel reads is rewritten by the scan of the same call, so nothing needs a reset, nothing is read back by the
+// host, the walk is the same on every run, and both launches are capturable.  No workgroup waits for another one; the kernel
+// boundary orders scan and main kernel.
 constexpr int SCAN_BR = 2 * SCAN_ROWS + 2;                    // 4-row flag blocks per band (the band's rows + 4 each way)
 constexpr int SCAN_FW = 256 / 4 + 2;                          // flag columns: the widest frame's 4-pixel blocks + one pad each side
-constexpr int ENC_FRAME_FEATS = 128 * 1024;                   // features per frame, either layout
 
-template <int PS, bool TOKENS, bool VEC>
+template <bool VEC>
 __global__ __launch_bounds__(256) void k_encoder_tile_scan(const float *__restrict__ frames, int64_t fstride, int H, int W, int lg_tiles_x,
-                                                           int bands_per_frame, const float *__restrict__ table,
-                                                           float *__restrict__ features, unsigned long long *__restrict__ masks) {
+                                                           int bands_per_frame, unsigned long long *__restrict__ masks) {
     __shared__ unsigned int flag[SCAN_BR][SCAN_FW];
-    __shared__ unsigned long long s_mask;
     const int tid = threadIdx.x;
     const int band = blockIdx.x, b = band / bands_per_frame, bi = band - b * bands_per_frame;
     const int tiles_x = 1 << lg_tiles_x, band_tiles = SCAN_ROWS * tiles_x;
@@ -1875,63 +2031,8 @@ __global__ __launch_bounds__(256) void k_encoder_tile_scan(const float *__restri
                 for (int bc = 0; bc < 6; ++bc) any |= flag[2 * tyl + br][4 * tx + bc];
         }
         const unsigned long long m = __ballot(any != 0);
-        if (tid == 0) {
-            s_mask = m;
-            masks[band] = m;
-        }
+        if (tid == 0) masks[band] = m;
     }
-    __syncthreads();
-    const unsigned long long m = s_mask;
-    // empty tiles: pooled cells from the zero-response table (same offsets within the frame)
-    constexpr int CR = B3_TH / PS, CC = B3_TW / PS;           // cells per tile: rows x columns
-    float *out = features + (size_t)b * ENC_FRAME_FEATS;
-    const int ty0 = bi * SCAN_ROWS;
-    if (TOKENS) {
-        constexpr int ROWV = CC * 32, UPT = CR * ROWV;        // float4 per cell row (CC cells x 128 channels, contiguous) / per tile
-        for (int i = tid; i < band_tiles * UPT; i += 256) {
-            const int tl = i / UPT, u = i - tl * UPT;
-            if ((m >> tl) & 1) continue;
-            const int ty = ty0 + (tl >> lg_tiles_x), tx = tl & (tiles_x - 1);
-            const int a = u / ROWV, q = u - a * ROWV;
-            const size_t off = (size_t)((ty * CR + a) * 32 + tx * CC) * 128 + q * 4;
-            *reinterpret_cast<float4 *>(out + off) = *reinterpret_cast<const float4 *>(table + off);
-        }
-    } else {
-        constexpr int VW = CC < 4 ? CC : 4, VPR = CC / VW, UPT = 128 * CR * VPR;   // a channel's cells of one row: CC contiguous floats
-        for (int i = tid; i < band_tiles * UPT; i += 256) {
-            const int tl = i / UPT, u = i - tl * UPT;
-            if ((m >> tl) & 1) continue;
-            const int ty = ty0 + (tl >> lg_tiles_x), tx = tl & (tiles_x - 1);
-            const int v = u % VPR, a = (u / VPR) % CR, o = u / (VPR * CR);
-            const size_t off = (size_t)o * 1024 + (ty * CR + a) * 32 + tx * CC + v * VW;
-            if (VW == 2) *reinterpret_cast<float2 *>(out + off) = *reinterpret_cast<const float2 *>(table + off);
-            else *reinterpret_cast<float4 *>(out + off) = *reinterpret_cast<const float4 *>(table + off);
-        }
-    }
-}
-
-constexpr int PACK_BANDS = 4;                                 // bands per pack workgroup: one wave each, one lane per tile
-__global__ __launch_bounds__(64 * PACK_BANDS) void k_encoder_tile_scan_pack(const unsigned long long *__restrict__ masks, int nbands,
-                                                                            int lg_band_tiles, int *__restrict__ list,
-                                                                            int *__restrict__ count) {
-    __shared__ int part[PACK_BANDS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int first = blockIdx.x * PACK_BANDS, band = first + wave;
-    // tiles on the list before this workgroup's bands: every workgroup sums the earlier masks itself (<= 8 bytes per band, from L2)
-    int c = 0;
-    for (int j = tid; j < first; j += 64 * PACK_BANDS) c += __popcll(masks[j]);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
-    if (lane == 0) part[wave] = c;
-    __syncthreads();
-    int before = 0;
-#pragma unroll
-    for (int w = 0; w < PACK_BANDS; ++w) before += part[w];
-    if (band >= nbands) return;
-    for (int w = 0; w < wave; ++w) before += __popcll(masks[first + w]);      // first + w < band < nbands
-    const unsigned long long m = masks[band];
-    if ((m >> lane) & 1) list[before + __popcll(m & ((1ull << lane) - 1))] = (band << lg_band_tiles) + lane;
-    if (band == nbands - 1 && lane == 0) *count = before + __popcll(m);
 }
 
 void EncoderSkip::release() {
@@ -1945,7 +2046,7 @@ void EncoderSkip::release() {
     for (void *p : retired) (void)hipFree(p);
     retired.clear();
     ws = nullptr;
-    ws_tiles = 0;
+    ws_bands = 0;
     last_count = nullptr;
 }
 
@@ -1960,11 +2061,7 @@ hipError_t encoder_skip_stats(EncoderSkip &sk, int64_t *tiles_total, int64_t *ti
     return hipSuccess;
 }
 
-struct SkipPlan {
-    const int *list = nullptr, *count = nullptr;              // both null: direct path
-};
-
-// Decides between the direct and the skip path of one forward call and, for the skip path, launches scan + pack.  FORM: 0 split-bf16,
+// Decides between the direct and the skip path of one forward call and, for the skip path, launches the scan.  FORM: 0 split-bf16,
 // 1 single-pass bf16, 2 int8 limbs (one zero-response table each, per frame size and layout).  zero_launch(zero_frame, table) runs
 // the call's own kernel form on the direct path over one all-zero frame.  Direct when the call has no more tiles than workgroups (one
 // round either way: the scan could only cost), when SMK_ENC_SKIP=0, when `features` is not 16-byte aligned, and while the stream is
@@ -1972,7 +2069,7 @@ struct SkipPlan {
 // handle is destroyed: a captured graph may still name them.
 template <int FORM, bool TOKENS, class ZeroLaunch>
 static hipError_t skip_prepare(EncoderSkip *sk, const float *frames, int64_t fstride, int B, int H, int W, float *features, int lg_tx,
-                               int ntiles, int nwg, hipStream_t st, ZeroLaunch zero_launch, SkipPlan &plan) {
+                               int ntiles, int nwg, hipStream_t st, ZeroLaunch zero_launch, SkipArgs &plan) {
     if (!sk) return hipSuccess;
     std::lock_guard<std::mutex> lk(sk->mu);
     sk->last_total = ntiles;
@@ -1998,35 +2095,29 @@ static hipError_t skip_prepare(EncoderSkip *sk, const float *frames, int64_t fst
         }
         tab = p;
     }
-    if (sk->ws_tiles < (size_t)ntiles) {
+    const int bands_per_frame = H / B3_TH / SCAN_ROWS, nbands = B * bands_per_frame;
+    if (sk->ws_bands < (size_t)nbands) {
         if (capturing) return hipSuccess;
-        int *p = nullptr;                                     // [count + pad: 4][band masks: 2 per 16 tiles][list: 1 per tile]
-        if ((err = hipMalloc((void **)&p, (4 + (size_t)ntiles / 8 + (size_t)ntiles) * sizeof(int))) != hipSuccess) return err;
+        int *p = nullptr;                                     // [tiles run + pad: 4][band masks: 2 per band]
+        if ((err = hipMalloc((void **)&p, (4 + 2 * (size_t)nbands) * sizeof(int))) != hipSuccess) return err;
         if (sk->ws) sk->retired.push_back(sk->ws);
         sk->ws = p;
-        sk->ws_tiles = ntiles;
+        sk->ws_bands = nbands;
     }
-    int *count = sk->ws, *list = sk->ws + 4 + sk->ws_tiles / 8;
+    int *count = sk->ws;
     unsigned long long *masks = reinterpret_cast<unsigned long long *>(sk->ws + 4);
-    const int bands_per_frame = H / B3_TH / SCAN_ROWS, nbands = B * bands_per_frame;
     const bool vec = (reinterpret_cast<uintptr_t>(frames) & 15) == 0 && (fstride & 3) == 0;
     dim3 grid(nbands), block(256);
-#define SMK_SCAN_LAUNCH(PS_, VEC_)                                                                                                  \
-    hipLaunchKernelGGL((k_encoder_tile_scan<PS_, TOKENS, VEC_>), grid, block, 0, st, frames, fstride, H, W, lg_tx, bands_per_frame, \
-                       (const float *)tab, features, masks)
-    switch (H / 32) {
-        case 2: if (vec) SMK_SCAN_LAUNCH(2, true); else SMK_SCAN_LAUNCH(2, false); break;
-        case 4: if (vec) SMK_SCAN_LAUNCH(4, true); else SMK_SCAN_LAUNCH(4, false); break;
-        case 8: if (vec) SMK_SCAN_LAUNCH(8, true); else SMK_SCAN_LAUNCH(8, false); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef SMK_SCAN_LAUNCH
+    if (H != 64 && H != 128 && H != 256) return hipErrorInvalidValue;
+    if (vec) hipLaunchKernelGGL(k_encoder_tile_scan<true>, grid, block, 0, st, frames, fstride, H, W, lg_tx, bands_per_frame, masks);
+    else hipLaunchKernelGGL(k_encoder_tile_scan<false>, grid, block, 0, st, frames, fstride, H, W, lg_tx, bands_per_frame, masks);
     if ((err = hipGetLastError()) != hipSuccess) return err;
-    hipLaunchKernelGGL(k_encoder_tile_scan_pack, dim3((nbands + PACK_BANDS - 1) / PACK_BANDS), dim3(64 * PACK_BANDS), 0, st,
-                       (const unsigned long long *)masks, nbands, lg_tx + 2, list, count);
-    if ((err = hipGetLastError()) != hipSuccess) return err;
-    plan.list = list;
+    plan.masks = masks;
     plan.count = count;
+    plan.nbands = nbands;
+    plan.lg_band_tiles = lg_tx + 2;                           // SCAN_ROWS = 4 tile rows
+    plan.table = tab;
+    plan.bands_per_frame = bands_per_frame;
     sk->last_count = count;
     return hipSuccess;
 }
@@ -2051,24 +2142,24 @@ static hipError_t launch_b16_t(const float *frames, int64_t fstride, int B, int 
         return enc_knobs().wgs_per_cu ? enc_knobs().wgs_per_cu : n;
     });
     // the fixed persistent grid, capped by the tile count of the call (never by the device-side list length)
-    auto run = [&](const float *fr, int64_t fs, int nt, float *out, const int *list, const int *count) -> hipError_t {
+    auto run = [&](const float *fr, int64_t fs, int nt, float *out, const SkipArgs &sa) -> hipError_t {
         int nwg = num_cu * wgs_per_cu;
         if (nwg > nt) nwg = nt;
         dim3 grid(nwg), block(256);
         switch (PS) {
-            case 2: hipLaunchKernelGGL((k_encoder_b16<2, TOKENS>), grid, block, S16_LDS, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, list, count); break;
-            case 4: hipLaunchKernelGGL((k_encoder_b16<4, TOKENS>), grid, block, S16_LDS, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, list, count); break;
-            default: hipLaunchKernelGGL((k_encoder_b16<8, TOKENS>), grid, block, S16_LDS, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, list, count); break;
+            case 2: hipLaunchKernelGGL((k_encoder_b16<2, TOKENS>), grid, block, S16_LDS, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, sa); break;
+            case 4: hipLaunchKernelGGL((k_encoder_b16<4, TOKENS>), grid, block, S16_LDS, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, sa); break;
+            default: hipLaunchKernelGGL((k_encoder_b16<8, TOKENS>), grid, block, S16_LDS, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, sa); break;
         }
         return hipGetLastError();
     };
-    SkipPlan plan;
+    SkipArgs plan;
     hipError_t err = skip_prepare<0, TOKENS>(
         skip, frames, fstride, B, H, W, features, lg_tx, ntiles, num_cu * wgs_per_cu, st,
-        [&](const float *zero_frame, float *table) { return run(zero_frame, (int64_t)H * W, tiles_per_frame, table, nullptr, nullptr); },
+        [&](const float *zero_frame, float *table) { return run(zero_frame, (int64_t)H * W, tiles_per_frame, table, SkipArgs()); },
         plan);
     if (err != hipSuccess) return err;
-    return run(frames, fstride, ntiles, features, plan.list, plan.count);
+    return run(frames, fstride, ntiles, features, plan);
 }
 
 hipError_t launch_encoder_b16(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e, float *features,
@@ -2099,24 +2190,24 @@ static hipError_t launch_bf16_t(const float *frames, int64_t fstride, int B, int
         return enc_knobs().wgs_per_cu ? enc_knobs().wgs_per_cu : n;
     });
     // the fixed persistent grid, capped by the tile count of the call (never by the device-side list length)
-    auto run = [&](const float *fr, int64_t fs, int nt, float *out, const int *list, const int *count) -> hipError_t {
+    auto run = [&](const float *fr, int64_t fs, int nt, float *out, const SkipArgs &sa) -> hipError_t {
         int nwg = num_cu * wgs_per_cu;
         if (nwg > nt) nwg = nt;
         dim3 grid(nwg), block(256);
         switch (PS) {
-            case 2: hipLaunchKernelGGL((k_encoder_bf16<X3, 2, TOKENS>), grid, block, lds_bytes, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, list, count); break;
-            case 4: hipLaunchKernelGGL((k_encoder_bf16<X3, 4, TOKENS>), grid, block, lds_bytes, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, list, count); break;
-            default: hipLaunchKernelGGL((k_encoder_bf16<X3, 8, TOKENS>), grid, block, lds_bytes, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, list, count); break;
+            case 2: hipLaunchKernelGGL((k_encoder_bf16<X3, 2, TOKENS>), grid, block, lds_bytes, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, sa); break;
+            case 4: hipLaunchKernelGGL((k_encoder_bf16<X3, 4, TOKENS>), grid, block, lds_bytes, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, sa); break;
+            default: hipLaunchKernelGGL((k_encoder_bf16<X3, 8, TOKENS>), grid, block, lds_bytes, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, sa); break;
         }
         return hipGetLastError();
     };
-    SkipPlan plan;
+    SkipArgs plan;
     hipError_t err = skip_prepare<X3 ? 0 : 1, TOKENS>(
         skip, frames, fstride, B, H, W, features, lg_tx, ntiles, num_cu * wgs_per_cu, st,
-        [&](const float *zero_frame, float *table) { return run(zero_frame, (int64_t)H * W, tiles_per_frame, table, nullptr, nullptr); },
+        [&](const float *zero_frame, float *table) { return run(zero_frame, (int64_t)H * W, tiles_per_frame, table, SkipArgs()); },
         plan);
     if (err != hipSuccess) return err;
-    return run(frames, fstride, ntiles, features, plan.list, plan.count);
+    return run(frames, fstride, ntiles, features, plan);
 }
 
 hipError_t launch_encoder_bf16(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e,
@@ -2154,7 +2245,7 @@ template <int PS, bool TOKENS>
 __global__ __launch_bounds__(256, 2) void k_encoder_i8(const float *__restrict__ frames, int64_t fstride, int H, int W,
                                                     EncoderDev e, float *__restrict__ features, int lg_tiles_x,
                                                     int lg_tiles_per_frame, int ntiles,
-                                                    const int *__restrict__ list, const int *__restrict__ count) {
+                                                    SkipArgs sa) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *xs = reinterpret_cast<float *>(smem);
     unsigned char *a1h = smem + B3_XS_BYTES, *a1l = a1h + I8_A1_BYTES;
@@ -2203,9 +2294,12 @@ __global__ __launch_bounds__(256, 2) void k_encoder_i8(const float *__restrict__
         return ok ? frames[(size_t)bb * fstride + (size_t)ii * W + jj] : 0.f;
     };
     int k = blockIdx.x;
-    const int nrun = tiles_to_run(list, count, ntiles);
-    if (nrun == ntiles) list = nullptr;                       // a complete list is ascending, i.e. the identity: no list loads
-    int t = k < nrun ? tile_at(list, k) : 0;
+    __shared__ SkipLds skl;
+    const int nrun = tiles_to_run(skl, sa, ntiles);
+    const bool listed = nrun != ntiles;                       // a complete list is ascending, i.e. the identity: no lookups
+    int round = 0;
+    int t = k < nrun ? tile_at(skl, sa, listed, 0, k, nrun) : 0;
+    if (listed && skip_fill_first()) skip_fill<PS, TOKENS>(sa, lg_tiles_x, features);
     if (k < nrun) {
         xs[tid] = x_fetch(t, tid);
         if (tid + 256 < B3_XH * B3_XW) xs[tid + 256] = x_fetch(t, tid + 256);
@@ -2338,7 +2432,8 @@ __global__ __launch_bounds__(256, 2) void k_encoder_i8(const float *__restrict__
         // [stamp:T4]
 
         const int kn = k + gridDim.x;
-        const int tn = kn < nrun ? tile_at(list, kn) : 0;
+        ++round;
+        const int tn = kn < nrun ? tile_at(skl, sa, listed, round, kn, nrun) : 0;
         float xr0 = 0.f, xr1 = 0.f;
         if (kn < nrun) {
             xr0 = x_fetch(tn, tid);
@@ -2473,6 +2568,10 @@ __global__ __launch_bounds__(256, 2) void k_encoder_i8(const float *__restrict__
         t = tn;
     }
     // [stamp:end]
+    if (listed && !skip_fill_first()) {
+        __builtin_amdgcn_s_setprio(0);
+        skip_fill<PS, TOKENS>(sa, lg_tiles_x, features);
+    }
 }
 
 template <bool TOKENS>
@@ -2492,24 +2591,24 @@ static hipError_t launch_i8_t(const float *frames, int64_t fstride, int B, int H
         return enc_knobs().wgs_per_cu ? enc_knobs().wgs_per_cu : n;
     });
     // the fixed persistent grid, capped by the tile count of the call (never by the device-side list length)
-    auto run = [&](const float *fr, int64_t fs, int nt, float *out, const int *list, const int *count) -> hipError_t {
+    auto run = [&](const float *fr, int64_t fs, int nt, float *out, const SkipArgs &sa) -> hipError_t {
         int nwg = num_cu * wgs_per_cu;
         if (nwg > nt) nwg = nt;
         dim3 grid(nwg), block(256);
         switch (PS) {
-            case 2: hipLaunchKernelGGL((k_encoder_i8<2, TOKENS>), grid, block, lds_bytes, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, list, count); break;
-            case 4: hipLaunchKernelGGL((k_encoder_i8<4, TOKENS>), grid, block, lds_bytes, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, list, count); break;
-            default: hipLaunchKernelGGL((k_encoder_i8<8, TOKENS>), grid, block, lds_bytes, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, list, count); break;
+            case 2: hipLaunchKernelGGL((k_encoder_i8<2, TOKENS>), grid, block, lds_bytes, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, sa); break;
+            case 4: hipLaunchKernelGGL((k_encoder_i8<4, TOKENS>), grid, block, lds_bytes, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, sa); break;
+            default: hipLaunchKernelGGL((k_encoder_i8<8, TOKENS>), grid, block, lds_bytes, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, sa); break;
         }
         return hipGetLastError();
     };
-    SkipPlan plan;
+    SkipArgs plan;
     hipError_t err = skip_prepare<2, TOKENS>(
         skip, frames, fstride, B, H, W, features, lg_tx, ntiles, num_cu * wgs_per_cu, st,
-        [&](const float *zero_frame, float *table) { return run(zero_frame, (int64_t)H * W, tiles_per_frame, table, nullptr, nullptr); },
+        [&](const float *zero_frame, float *table) { return run(zero_frame, (int64_t)H * W, tiles_per_frame, table, SkipArgs()); },
         plan);
     if (err != hipSuccess) return err;
-    return run(frames, fstride, ntiles, features, plan.list, plan.count);
+    return run(frames, fstride, ntiles, features, plan);
 }
 
 hipError_t launch_encoder_i8(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e, float *features,
