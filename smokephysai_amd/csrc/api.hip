@@ -13,6 +13,7 @@
 #include "decoder_train.h"
 #include "elementwise.h"
 #include "encoder.h"
+#include "encoder_train.h"
 #include "linear.h"
 #include "norm.h"
 #include "quality.h"

@@ -18,9 +18,15 @@
 //                   product-major MFMA emission, pinned read / ring-load placement (-22 % time vs k_encoder_bf16<X3>).
 //   k_encoder_i8    same structure as k_encoder_bf16; conv2 on v_mfma_i32_32x32x32_i8 with 16-bit fixed-point operands as two
 //                   int8 limbs.
+// The three persistent kernels (bf16, b16, i8) share one scaffold, written once ahead of them: conv1 staging, the work-list walk
+// (TileWalk), the x halo fetch (TileSrc), conv1's MFMA units and the pooled store of the 32x32 layout; one launcher template
+// (launch_persistent) launches all three.  Also here: weight folding (k_fold_weights, k_quant_w2), the conv1 parity hook and the
+// tile skip (k_encoder_tile_scan, skip_prepare).  The convolutions under autograd are in encoder_train.hip.
 #include "encoder.h"
 
 #include <stdlib.h>
+
+#include "encoder_tile.h"
 
 namespace smk {
 
@@ -315,11 +321,8 @@ hipError_t launch_encoder_f32(const float *frames, int64_t fstride, int B, int H
 //        A fragments = 16-byte reads of a1s (pixel pitch 144 B = 9*16); B fragments straight from L2 as coalesced
 //        1 KiB loads into a 3-deep register ring (layout [k-step][hi|lo][o][16 c]); no barrier inside the K loop.
 // epilogue: BN2 + ReLU + block-mean pool in registers (+ one wave shuffle for PS = 8); NCHW or token-major stores.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
-constexpr int B3_TH = 8, B3_TW = 16;                     // output tile
-constexpr int B3_AW = B3_TW + 2, B3_APIX = (B3_TH + 2) * B3_AW;   // a1 halo tile: 10 x 18 = 180 pixels
 constexpr int B3_XH = B3_TH + 9, B3_XW = B3_TW + 9;      // x tile 16 x 24 (+1 zero row, +1 pad column) = 17 x 25
 constexpr int B3_XS_BYTES = ((B3_XH * B3_XW * 4 + 15) / 16) * 16;   // 1712
 constexpr int B3_A1_PITCH = 144;                         // bytes per halo pixel: 64 ch * 2 B + 16 pad (9 x 16 B: odd)
@@ -327,11 +330,6 @@ constexpr int B3_A1_ROW = B3_AW * B3_A1_PITCH + 32;      // 2624 B per halo row:
                                                          // an M block of rows (m, m+4) x 16 cols reads conflict-free
 constexpr int B3_A1_BYTES = (B3_TH + 2) * B3_A1_ROW;     // 26240
 template <bool X3> constexpr int b3_lds_bytes() { return B3_XS_BYTES + (X3 ? 2 : 1) * B3_A1_BYTES; }   // 54,192 (x3): 3 per CU
-
-__device__ __forceinline__ void split_bf16(float v, __bf16 &hi, __bf16 &lo) {
-    hi = (__bf16)v;
-    lo = (__bf16)(v - (float)hi);
-}
 
 template <bool X3>
 __device__ __forceinline__ void mma3(f32x16 &acc, const bf16x8 &ah, const bf16x8 &al, const bf16x8 &bh, const bf16x8 &bl) {
@@ -504,6 +502,222 @@ __device__ __forceinline__ void skip_fill(const SkipArgs &sa, int lg_tiles_x, fl
 // DESIGN.md 3.2.
 __device__ __forceinline__ bool skip_fill_first() { return (blockIdx.x / 256) & 1; }
 
+// ---------------------------------------------------------------- what the three persistent kernels share
+// k_encoder_bf16, k_encoder_b16 and k_encoder_i8 are one design: stage the conv1 weights, walk the work list of 8 x 16 tiles,
+// conv1 on MFMA into an LDS image, prefetch the next tile's input under the conv2 K loop, pool, store.  The parts below exist
+// once; a kernel keeps its conv2 K loop, its a1 image and what it does with conv1's results.
+
+// BN1 scale | shift and the conv1 weights [part][ch][64 k] -> LDS with a 144-byte row pitch (16-byte chunks: 8 per row); once
+// per workgroup.  PARTS = 2: hi and lo.
+template <int PARTS>
+__device__ __forceinline__ void conv1_stage(const EncoderDev &e, unsigned char *w1s, float *st1) {
+    const int tid = threadIdx.x;
+    if (tid < 128) st1[tid] = tid < 64 ? e.s1[tid] : e.t1[tid - 64];
+    const uint4 *src = reinterpret_cast<const uint4 *>(e.w1p);
+    for (int c = tid; c < PARTS * 64 * 8; c += 256) {
+        const int row = c >> 3, u = c & 7;                     // row = part*64 + ch
+        *reinterpret_cast<uint4 *>(w1s + row * B3_W1_PITCH + u * 16) = src[c];
+    }
+}
+
+// The frames of a call and their grid of tiles (tile counts are 2^n).
+struct TileSrc {
+    const float *frames;
+    int64_t fstride;
+    int H, W, lg_tiles_x, lg_tiles_per_frame;
+    // tile id -> frame, first row, first column
+    __device__ __forceinline__ void decode(int t, int &b, int &r0, int &c0) const {
+        b = t >> lg_tiles_per_frame;
+        const int rem = t & ((1 << lg_tiles_per_frame) - 1);
+        r0 = (rem >> lg_tiles_x) * B3_TH;
+        c0 = (rem & ((1 << lg_tiles_x) - 1)) * B3_TW;
+    }
+    // x halo element k of tile t (2 per thread): value or 0 outside the image / in the pad row and column
+    __device__ __forceinline__ float fetch(int t, int k) const {
+        if (k >= B3_XH * B3_XW) return 0.f;
+        int bb, rr0, cc0;
+        decode(t, bb, rr0, cc0);
+        const int row = k / B3_XW, col = k - row * B3_XW;
+        const int ii = rr0 - 4 + row, jj = cc0 - 4 + col;
+        const bool ok = row < B3_XH - 1 && col < B3_XW - 1 && ii >= 0 && ii < H && jj >= 0 && jj < W;
+        return ok ? frames[(size_t)bb * fstride + (size_t)ii * W + jj] : 0.f;
+    }
+};
+
+// A thread's two x halo elements -> the LDS tile; word(v) is what a kernel keeps per element (the float, or b16's split pair).
+template <class T, class Word>
+__device__ __forceinline__ void halo_to_lds(T *xs, float v0, float v1, Word word) {
+    const int tid = threadIdx.x;
+    xs[tid] = word(v0);
+    if (tid + 256 < B3_XH * B3_XW) xs[tid + 256] = word(v1);
+}
+
+// The walk of a workgroup over the work list: entries k = blockIdx.x, + gridDim.x, ...; t is the tile of entry k.
+//   begin   list length, first tile, the fill or the start delay, first halo -> LDS, barrier
+//   next    rank and tile of the following round, its halo into registers (lands under the K loop); after the a1 barrier
+//   the kernel's loop tail puts those registers into LDS (halo_to_lds), holds its barrier and sets t = tn
+//   end     the trailing fill
+// tiles_to_run and tile_at hold barriers: every thread of the workgroup calls begin and next, at the same place.
+struct TileWalk {
+    int k, nrun, round, t, tn;
+    bool listed;
+
+    template <int PS, bool TOKENS, class T, class Word>
+    __device__ __forceinline__ void begin(SkipLds &skl, const SkipArgs &sa, const TileSrc &src, int ntiles, int stagger,
+                                          float *__restrict__ features, T *xs, Word word) {
+        k = blockIdx.x;
+        nrun = tiles_to_run(skl, sa, ntiles);
+        listed = nrun != ntiles;                              // a complete list is ascending, i.e. the identity: no lookups
+        round = 0;
+        t = k < nrun ? tile_at(skl, sa, listed, 0, k, nrun) : 0;
+        // Workgroups that share a CU run the same program with the same period; started together they stay in lockstep
+        // (both in the VALU-heavy conv1 phase, then both in the MFMA loop).  Delay every other dispatch round by about
+        // half a tile so that one workgroup's conv1 overlaps the other's K loop (speed only, never correctness).
+        // On the skip path that round copies its share of the empty tiles' cells instead (skip_fill_first): the same shift, not idle.
+        if (listed && skip_fill_first()) skip_fill<PS, TOKENS>(sa, src.lg_tiles_x, features);
+        else if (stagger > 0 && ((blockIdx.x / 256) & 1))
+            for (int i = 0; i < stagger; ++i) __builtin_amdgcn_s_sleep(127);
+        const int tid = threadIdx.x;
+        if (k < nrun) halo_to_lds(xs, src.fetch(t, tid), src.fetch(t, tid + 256), word);
+        __syncthreads();
+    }
+    __device__ __forceinline__ void next(SkipLds &skl, const SkipArgs &sa, const TileSrc &src, float &xr0, float &xr1) {
+        const int kn = k + gridDim.x;
+        ++round;
+        tn = kn < nrun ? tile_at(skl, sa, listed, round, kn, nrun) : 0;
+        xr0 = 0.f;
+        xr1 = 0.f;
+        if (kn < nrun) {
+            const int tid = threadIdx.x;
+            xr0 = src.fetch(tn, tid);
+            xr1 = src.fetch(tn, tid + 256);
+        }
+    }
+    template <int PS, bool TOKENS>
+    __device__ __forceinline__ void end(const SkipArgs &sa, const TileSrc &src, float *__restrict__ features) const {
+        if (listed && !skip_fill_first()) {
+            __builtin_amdgcn_s_setprio(0);
+            skip_fill<PS, TOKENS>(sa, src.lg_tiles_x, features);
+        }
+    }
+};
+
+// conv1's B fragments for pixel block pb of the a1 halo tile (32 halo pixels, lane r = one pixel), from the fp32 x tile: a lane's
+// 8 k-values are 8 consecutive pixels of one row, split into hi and lo.  aoff = the pixel's byte offset in an a1 image of the
+// given row and pixel pitch; valid = the pixel exists (pixel block 5 is partial); inimg = it lies inside the image.
+template <int A1_ROW, int A1_PITCH>
+__device__ __forceinline__ void x_frags(const float *xs, int pb, int r0, int c0, int H, int W, bf16x8 (&xh)[4], bf16x8 (&xl)[4],
+                                        int &aoff, bool &valid, bool &inimg) {
+    const int r = threadIdx.x & 31, hi = (threadIdx.x >> 5) & 1;
+    const int pix = pb * 32 + r;
+    valid = pix < B3_APIX;
+    const int pc = valid ? pix : B3_APIX - 1;
+    const int ar = pc / B3_AW, ac = pc - ar * B3_AW;
+    const int ii = r0 - 1 + ar, jj = c0 - 1 + ac;
+    inimg = valid && ii >= 0 && ii < H && jj >= 0 && jj < W;
+    aoff = ar * A1_ROW + ac * A1_PITCH;
+    const float *xp = xs + (ar + hi) * B3_XW + ac;                          // row ar + 2s + hi, cols ac .. ac+7
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            __bf16 vh, vl;
+            split_bf16(xp[s * 2 * B3_XW + j], vh, vl);
+            xh[s][j] = vh; xl[s][j] = vl;
+        }
+}
+
+// conv1 on MFMA: 6 blocks of 32 halo pixels x 2 blocks of 32 channels.  Wave w takes pixel block w for BOTH channel blocks (x
+// fragments built once, two independent accumulator chains: conv1_both) and one half of a shared block (pixel block 4 + w/2,
+// channel block w&1: conv1_one): 3 (block, channel-block) units per wave.
+template <bool X3>
+__device__ __forceinline__ void conv1_both(const unsigned char *w1s, const bf16x8 (&xh)[4], const bf16x8 (&xl)[4], f32x16 &acc0,
+                                           f32x16 &acc1) {
+    const int r = threadIdx.x & 31, hi = (threadIdx.x >> 5) & 1;
+#pragma unroll
+    for (int g = 0; g < 16; ++g) { acc0[g] = 0.f; acc1[g] = 0.f; }
+    const unsigned char *wrow = w1s + r * B3_W1_PITCH + 8 * hi * 2;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const bf16x8 a0h = *reinterpret_cast<const bf16x8 *>(wrow + s * 32);
+        const bf16x8 a1hh = *reinterpret_cast<const bf16x8 *>(wrow + 32 * B3_W1_PITCH + s * 32);
+        const bf16x8 a0l = X3 ? *reinterpret_cast<const bf16x8 *>(wrow + B3_W1_BYTES + s * 32) : a0h;
+        const bf16x8 a1l_ = X3 ? *reinterpret_cast<const bf16x8 *>(wrow + B3_W1_BYTES + 32 * B3_W1_PITCH + s * 32) : a1hh;
+        mma3<X3>(acc0, a0h, a0l, xh[s], xl[s]);
+        mma3<X3>(acc1, a1hh, a1l_, xh[s], xl[s]);
+    }
+}
+template <bool X3>
+__device__ __forceinline__ void conv1_one(const unsigned char *w1s, int cb, const bf16x8 (&xh)[4], const bf16x8 (&xl)[4],
+                                          f32x16 &acc) {
+    const int r = threadIdx.x & 31, hi = (threadIdx.x >> 5) & 1;
+#pragma unroll
+    for (int g = 0; g < 16; ++g) acc[g] = 0.f;
+    const unsigned char *wrow = w1s + (cb * 32 + r) * B3_W1_PITCH + 8 * hi * 2;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const bf16x8 ah = *reinterpret_cast<const bf16x8 *>(wrow + s * 32);
+        const bf16x8 al = X3 ? *reinterpret_cast<const bf16x8 *>(wrow + B3_W1_BYTES + s * 32) : ah;
+        mma3<X3>(acc, ah, al, xh[s], xl[s]);
+    }
+}
+
+// Block-mean pool + store for the 32x32 accumulator layout (k_encoder_bf16, k_encoder_i8); val(mi, g) is the finished activation
+// of register g of M block mi: pixel p = (g&3) + 8(g>>2) + 4hi of the block -> tile row mi + 4(p>>4), col p & 15,
+// i.e. q = g>>2 = 2qr + qc: row mi + 4qr, cols 8qc + 4hi + (g&3).  o = the lane's output channel.
+template <int PS, bool TOKENS, class Val>
+__device__ __forceinline__ void pool_store_32(float *__restrict__ features, int b, int o, int r0, int c0, Val val) {
+    const int hi = (threadIdx.x >> 5) & 1;
+    auto out_index = [&](int pi, int pj) -> size_t {
+        return TOKENS ? ((size_t)b * 1024 + pi * 32 + pj) * 128 + o : ((size_t)b * 128 + o) * 1024 + pi * 32 + pj;
+    };
+    if (PS == 2) {          // cell rows (mi, mi+1) for even mi, cell cols = column pairs
+#pragma unroll
+        for (int mp = 0; mp < 2; ++mp)
+#pragma unroll
+            for (int qr = 0; qr < 2; ++qr)
+#pragma unroll
+                for (int qc = 0; qc < 2; ++qc)
+#pragma unroll
+                    for (int cg = 0; cg < 2; ++cg) {
+                        float sum = 0.f;
+#pragma unroll
+                        for (int mi = 2 * mp; mi < 2 * mp + 2; ++mi)
+#pragma unroll
+                            for (int i = 2 * cg; i < 2 * cg + 2; ++i) sum += val(mi, 4 * (2 * qr + qc) + i);
+                        features[out_index((r0 + 2 * mp + 4 * qr) / 2, (c0 + 8 * qc + 4 * hi + 2 * cg) / 2)] = sum * 0.25f;
+                    }
+    } else if (PS == 4) {   // cell row = qr (rows 4qr .. 4qr+3 = all mi), cell col = 2qc + hi
+#pragma unroll
+        for (int qr = 0; qr < 2; ++qr)
+#pragma unroll
+            for (int qc = 0; qc < 2; ++qc) {
+                float sum = 0.f;
+#pragma unroll
+                for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) sum += val(mi, 4 * (2 * qr + qc) + i);
+                features[out_index((r0 + 4 * qr) / 4, (c0 + 8 * qc + 4 * hi) / 4)] = sum * (1.0f / 16);
+            }
+    } else {   // PS == 8: two cells (qc); each is split over the two lane halves (hi)
+        float cell[2];
+#pragma unroll
+        for (int qc = 0; qc < 2; ++qc) {
+            float sum = 0.f;
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+                for (int qr = 0; qr < 2; ++qr)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) sum += val(mi, 4 * (2 * qr + qc) + i);
+            cell[qc] = sum;
+        }
+        const float other0 = __shfl_xor(cell[0], 32), other1 = __shfl_xor(cell[1], 32);
+        const float total = hi == 0 ? cell[0] + other0 : cell[1] + other1;   // a+b == b+a: both halves agree bitwise
+        features[out_index(r0 / 8, c0 / 8 + hi)] = total * (1.0f / 64);
+    }
+}
+
 // Persistent: each workgroup walks work-list entries k = blockIdx.x, +gridDim.x, ... (t = tile_at(..., k)).  Per-workgroup
 // costs (conv1 weights -> LDS, BN2 scale/shift, B-ring fill) are paid once; the next tile's x halo is prefetched into registers under the K loop and
 // the B-fragment ring simply keeps running across tiles (the weights do not depend on the tile).
@@ -520,16 +734,7 @@ __global__ __launch_bounds__(256, 2) void k_encoder_bf16(const float *__restrict
     const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, hi = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    // ---- once per workgroup
-    if (tid < 128) st1[tid] = tid < 64 ? e.s1[tid] : e.t1[tid - 64];
-    {   // conv1 weights [part][ch][64 k] -> LDS with a 144-byte row pitch (16-byte chunks: 8 per row)
-        constexpr int NCH = (X3 ? 2 : 1) * 64 * 8;
-        const uint4 *src = reinterpret_cast<const uint4 *>(e.w1p);
-        for (int c = tid; c < NCH; c += 256) {
-            const int row = c >> 3, u = c & 7;                 // row = part*64 + ch
-            *reinterpret_cast<uint4 *>(w1s + row * B3_W1_PITCH + u * 16) = src[c];
-        }
-    }
+    conv1_stage<X3 ? 2 : 1>(e, w1s, st1);                     // once per workgroup
     const int o = wave * 32 + r;
     const float s2 = e.s2[o], t2 = e.t2[o];
     // w2q: [k-step 36][hi|lo][o 128][16 c] bf16 = 4 KiB per (k-step, part); this lane reads 16 bytes at a constant
@@ -553,61 +758,17 @@ __global__ __launch_bounds__(256, 2) void k_encoder_bf16(const float *__restrict
     }
     const int lane_off = (r >> 4) * 4 * B3_A1_ROW + (r & 15) * B3_A1_PITCH + 8 * hi * 2;
 
-    // x halo element k of a tile (2 per thread): value or 0 outside the image / in the pad row and column
-    auto x_fetch = [&](int t, int k) -> float {
-        if (k >= B3_XH * B3_XW) return 0.f;
-        const int bb = t >> lg_tiles_per_frame, rem = t & ((1 << lg_tiles_per_frame) - 1);     // tile counts are 2^n
-        const int rr0 = (rem >> lg_tiles_x) * B3_TH, cc0 = (rem & ((1 << lg_tiles_x) - 1)) * B3_TW;
-        const int row = k / B3_XW, col = k - row * B3_XW;
-        const int ii = rr0 - 4 + row, jj = cc0 - 4 + col;
-        const bool ok = row < B3_XH - 1 && col < B3_XW - 1 && ii >= 0 && ii < H && jj >= 0 && jj < W;
-        return ok ? frames[(size_t)bb * fstride + (size_t)ii * W + jj] : 0.f;
-    };
-    int k = blockIdx.x;
+    const TileSrc src{frames, fstride, H, W, lg_tiles_x, lg_tiles_per_frame};
     __shared__ SkipLds skl;
-    const int nrun = tiles_to_run(skl, sa, ntiles);
-    const bool listed = nrun != ntiles;                       // a complete list is ascending, i.e. the identity: no lookups
-    int round = 0;
-    int t = k < nrun ? tile_at(skl, sa, listed, 0, k, nrun) : 0;
-    // Workgroups that share a CU run the same program with the same period; started together they stay in lockstep
-    // (both in the VALU-heavy conv1 phase, then both in the MFMA loop).  Delay every other dispatch round by about
-    // half a tile so that one workgroup's conv1 overlaps the other's K loop (speed only, never correctness).
-    // On the skip path that round copies its share of the empty tiles' cells instead (skip_fill_first): the same shift, not idle.
-    if (listed && skip_fill_first()) skip_fill<PS, TOKENS>(sa, lg_tiles_x, features);
-    else if (stagger > 0 && ((blockIdx.x / 256) & 1))
-        for (int i = 0; i < stagger; ++i) __builtin_amdgcn_s_sleep(127);
-    if (k < nrun) {
-        xs[tid] = x_fetch(t, tid);
-        if (tid + 256 < B3_XH * B3_XW) xs[tid + 256] = x_fetch(t, tid + 256);
-    }
-    __syncthreads();
+    TileWalk wk;
+    wk.begin<PS, TOKENS>(skl, sa, src, ntiles, stagger, features, xs, [](float v) { return v; });
 
-    for (; k < nrun; k += gridDim.x) {
-        const int b = t >> lg_tiles_per_frame, rem = t & ((1 << lg_tiles_per_frame) - 1);
-        const int r0 = (rem >> lg_tiles_x) * B3_TH, c0 = (rem & ((1 << lg_tiles_x) - 1)) * B3_TW;
+    for (; wk.k < wk.nrun; wk.k += gridDim.x) {
+        int b, r0, c0;
+        src.decode(wk.t, b, r0, c0);
 
         __builtin_amdgcn_s_setprio(0);
-        // ---- conv1 on MFMA: 6 blocks of 32 halo pixels x 2 blocks of 32 channels.  Wave w takes pixel block w for BOTH
-        //      channel blocks (x fragments built once, two independent accumulator chains) and one half of a shared
-        //      block (pixel block 4 + w/2, channel block w&1): 3 (block, channel-block) units per wave.
-        auto x_frags = [&](int pb, bf16x8 (&xh)[4], bf16x8 (&xl)[4], int &aoff, bool &valid, bool &inimg) {
-            const int pix = pb * 32 + r;
-            valid = pix < B3_APIX;
-            const int pc = valid ? pix : B3_APIX - 1;
-            const int ar = pc / B3_AW, ac = pc - ar * B3_AW;
-            const int ii = r0 - 1 + ar, jj = c0 - 1 + ac;
-            inimg = valid && ii >= 0 && ii < H && jj >= 0 && jj < W;
-            aoff = ar * B3_A1_ROW + ac * B3_A1_PITCH;
-            const float *xp = xs + (ar + hi) * B3_XW + ac;                          // row ar + 2s + hi, cols ac .. ac+7
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    __bf16 vh, vl;
-                    split_bf16(xp[s * 2 * B3_XW + j], vh, vl);
-                    xh[s][j] = vh; xl[s][j] = vl;
-                }
-        };
+        // ---- conv1 on MFMA (x_frags, conv1_both, conv1_one): results split and stored into the a1 image
         auto conv1_store = [&](const f32x16 &acc, int cb, int aoff, bool valid, bool inimg) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -632,20 +793,9 @@ __global__ __launch_bounds__(256, 2) void k_encoder_bf16(const float *__restrict
         {
             bf16x8 xh[4], xl[4];
             int aoff; bool valid, inimg;
-            x_frags(wave, xh, xl, aoff, valid, inimg);
+            x_frags<B3_A1_ROW, B3_A1_PITCH>(xs, wave, r0, c0, H, W, xh, xl, aoff, valid, inimg);
             f32x16 acc0, acc1;
-#pragma unroll
-            for (int g = 0; g < 16; ++g) { acc0[g] = 0.f; acc1[g] = 0.f; }
-            const unsigned char *wrow = w1s + r * B3_W1_PITCH + 8 * hi * 2;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const bf16x8 a0h = *reinterpret_cast<const bf16x8 *>(wrow + s * 32);
-                const bf16x8 a1hh = *reinterpret_cast<const bf16x8 *>(wrow + 32 * B3_W1_PITCH + s * 32);
-                const bf16x8 a0l = X3 ? *reinterpret_cast<const bf16x8 *>(wrow + B3_W1_BYTES + s * 32) : a0h;
-                const bf16x8 a1l_ = X3 ? *reinterpret_cast<const bf16x8 *>(wrow + B3_W1_BYTES + 32 * B3_W1_PITCH + s * 32) : a1hh;
-                mma3<X3>(acc0, a0h, a0l, xh[s], xl[s]);
-                mma3<X3>(acc1, a1hh, a1l_, xh[s], xl[s]);
-            }
+            conv1_both<X3>(w1s, xh, xl, acc0, acc1);
             conv1_store(acc0, 0, aoff, valid, inimg);
             conv1_store(acc1, 1, aoff, valid, inimg);
         }
@@ -653,17 +803,9 @@ __global__ __launch_bounds__(256, 2) void k_encoder_bf16(const float *__restrict
             bf16x8 xh[4], xl[4];
             int aoff; bool valid, inimg;
             const int cb = wave & 1;
-            x_frags(4 + (wave >> 1), xh, xl, aoff, valid, inimg);
+            x_frags<B3_A1_ROW, B3_A1_PITCH>(xs, 4 + (wave >> 1), r0, c0, H, W, xh, xl, aoff, valid, inimg);
             f32x16 acc;
-#pragma unroll
-            for (int g = 0; g < 16; ++g) acc[g] = 0.f;
-            const unsigned char *wrow = w1s + (cb * 32 + r) * B3_W1_PITCH + 8 * hi * 2;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const bf16x8 ah = *reinterpret_cast<const bf16x8 *>(wrow + s * 32);
-                const bf16x8 al = X3 ? *reinterpret_cast<const bf16x8 *>(wrow + B3_W1_BYTES + s * 32) : ah;
-                mma3<X3>(acc, ah, al, xh[s], xl[s]);
-            }
+            conv1_one<X3>(w1s, cb, xh, xl, acc);
             conv1_store(acc, cb, aoff, valid, inimg);
         }
         __syncthreads();                                      // a1s complete; xs is free again
@@ -672,15 +814,8 @@ __global__ __launch_bounds__(256, 2) void k_encoder_bf16(const float *__restrict
         // raising it before the barrier or to priority 3 gives -4 %.
         __builtin_amdgcn_s_setprio(1);
 
-        // next tile's x halo -> registers (lands under the K loop)
-        const int kn = k + gridDim.x;
-        ++round;
-        const int tn = kn < nrun ? tile_at(skl, sa, listed, round, kn, nrun) : 0;
-        float xr0 = 0.f, xr1 = 0.f;
-        if (kn < nrun) {
-            xr0 = x_fetch(tn, tid);
-            xr1 = x_fetch(tn, tid + 256);
-        }
+        float xr0, xr1;                                       // next tile's x halo -> registers (lands under the K loop)
+        wk.next(skl, sa, src, xr0, xr1);
 
         // ---- conv2: wave = channel block; 4 M blocks (rows mi and mi+4, 16 cols each)
         f32x16 acc[4];
@@ -735,68 +870,16 @@ __global__ __launch_bounds__(256, 2) void k_encoder_bf16(const float *__restrict
             }
         }
 
-        // ---- epilogue.  acc[mi][g]: pixel p = (g&3) + 8(g>>2) + 4hi of M block mi -> tile row mi + 4(p>>4), col p & 15
-        //      i.e. q = g>>2 = 2qr + qc: row mi + 4qr, cols 8qc + 4hi + (g&3)
-        auto out_index = [&](int pi, int pj) -> size_t {
-            return TOKENS ? ((size_t)b * 1024 + pi * 32 + pj) * 128 + o : ((size_t)b * 128 + o) * 1024 + pi * 32 + pj;
-        };
-        if (PS == 2) {          // cell rows (mi, mi+1) for even mi, cell cols = column pairs
-#pragma unroll
-            for (int mp = 0; mp < 2; ++mp)
-#pragma unroll
-                for (int qr = 0; qr < 2; ++qr)
-#pragma unroll
-                    for (int qc = 0; qc < 2; ++qc)
-#pragma unroll
-                        for (int cg = 0; cg < 2; ++cg) {
-                            float sum = 0.f;
-#pragma unroll
-                            for (int mi = 2 * mp; mi < 2 * mp + 2; ++mi)
-#pragma unroll
-                                for (int i = 2 * cg; i < 2 * cg + 2; ++i) sum += bn_relu(acc[mi][4 * (2 * qr + qc) + i], s2, t2);
-                            features[out_index((r0 + 2 * mp + 4 * qr) / 2, (c0 + 8 * qc + 4 * hi + 2 * cg) / 2)] = sum * 0.25f;
-                        }
-        } else if (PS == 4) {   // cell row = qr (rows 4qr .. 4qr+3 = all mi), cell col = 2qc + hi
-#pragma unroll
-            for (int qr = 0; qr < 2; ++qr)
-#pragma unroll
-                for (int qc = 0; qc < 2; ++qc) {
-                    float sum = 0.f;
-#pragma unroll
-                    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) sum += bn_relu(acc[mi][4 * (2 * qr + qc) + i], s2, t2);
-                    features[out_index((r0 + 4 * qr) / 4, (c0 + 8 * qc + 4 * hi) / 4)] = sum * (1.0f / 16);
-                }
-        } else {   // PS == 8: two cells (qc); each is split over the two lane halves (hi)
-            float cell[2];
-#pragma unroll
-            for (int qc = 0; qc < 2; ++qc) {
-                float sum = 0.f;
-#pragma unroll
-                for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                    for (int qr = 0; qr < 2; ++qr)
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) sum += bn_relu(acc[mi][4 * (2 * qr + qc) + i], s2, t2);
-                cell[qc] = sum;
-            }
-            const float other0 = __shfl_xor(cell[0], 32), other1 = __shfl_xor(cell[1], 32);
-            const float total = hi == 0 ? cell[0] + other0 : cell[1] + other1;   // a+b == b+a: both halves agree bitwise
-            features[out_index(r0 / 8, c0 / 8 + hi)] = total * (1.0f / 64);
-        }
+        // ---- epilogue: BN2 + ReLU + block-mean pool
+        pool_store_32<PS, TOKENS>(features, b, o, r0, c0, [&](int mi, int g) { return bn_relu(acc[mi][g], s2, t2); });
 
         // next tile's x halo -> LDS (xs has been free since the barrier above); one barrier then covers both
         // "every wave is done reading a1" and "xs is visible"
-        xs[tid] = xr0;
-        if (tid + 256 < B3_XH * B3_XW) xs[tid + 256] = xr1;
+        halo_to_lds(xs, xr0, xr1, [](float v) { return v; });
         __syncthreads();
-        t = tn;
+        wk.t = wk.tn;
     }
-    if (listed && !skip_fill_first()) {
-        __builtin_amdgcn_s_setprio(0);
-        skip_fill<PS, TOKENS>(sa, lg_tiles_x, features);
-    }
+    wk.end<PS, TOKENS>(sa, src, features);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -813,13 +896,7 @@ __global__ __launch_bounds__(256, 2) void k_encoder_bf16(const float *__restrict
 //   loop:  unit = half a k-step (M tiles 4hm..4hm+3: 24 MFMAs = 384 cycles, the same unit as k_encoder_bf16's k-step), so the
 //          skeleton -- A fragments of the next unit read under this unit's MFMAs, B ring from L2 -- and the register budget
 //          (64 acc + 64 A + 48 B) carry over.
-#ifndef S16_PRIO_CONV1
-#define S16_PRIO_CONV1 0
-#define S16_PRIO_KLOOP 1
-#endif
-constexpr int S16_A1_BYTES = B3_APIX * 128;                               // 23,040 per plane
 constexpr int S16_LDS = B3_XS_BYTES + 2 * S16_A1_BYTES + 2 * B3_W1_BYTES + B3_ST_BYTES;   // 66,736 -> 2 workgroups per CU
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 template <int PS, bool TOKENS>
 __global__ __launch_bounds__(256, 2) void k_encoder_b16(const float *__restrict__ frames, int64_t fstride, int H, int W,
@@ -836,14 +913,7 @@ __global__ __launch_bounds__(256, 2) void k_encoder_b16(const float *__restrict_
     const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, hi = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    if (tid < 128) st1[tid] = tid < 64 ? e.s1[tid] : e.t1[tid - 64];
-    {
-        const uint4 *src = reinterpret_cast<const uint4 *>(e.w1p);
-        for (int c = tid; c < 2 * 64 * 8; c += 256) {
-            const int row = c >> 3, u = c & 7;
-            *reinterpret_cast<uint4 *>(w1s + row * B3_W1_PITCH + u * 16) = src[c];
-        }
-    }
+    conv1_stage<2>(e, w1s, st1);
     // conv2 operand lanes: pixel / channel px = lane & 15, channel group kg = lane >> 4
     const int px = lane & 15, kg = lane >> 4;
     const int o0 = wave * 32 + px;                                            // N tile 0; tile 1 = + 16
@@ -871,43 +941,24 @@ __global__ __launch_bounds__(256, 2) void k_encoder_b16(const float *__restrict_
     // A addressing: pixel p = (mt + ki) * 18 + px + kj; unit = g ^ (p & 7), g = 4 half + kg.  p & 7 = (px + kj + 2 (mt + ki)) & 7
     // because 18 = 2 (mod 8): tq[kj] is the lane part, the row part is added per read.
 
-    auto x_fetch = [&](int t, int k) -> float {
-        if (k >= B3_XH * B3_XW) return 0.f;
-        const int bb = t >> lg_tiles_per_frame, rem = t & ((1 << lg_tiles_per_frame) - 1);
-        const int rr0 = (rem >> lg_tiles_x) * B3_TH, cc0 = (rem & ((1 << lg_tiles_x) - 1)) * B3_TW;
-        const int row = k / B3_XW, col = k - row * B3_XW;
-        const int ii = rr0 - 4 + row, jj = cc0 - 4 + col;
-        const bool ok = row < B3_XH - 1 && col < B3_XW - 1 && ii >= 0 && ii < H && jj >= 0 && jj < W;
-        return ok ? frames[(size_t)bb * fstride + (size_t)ii * W + jj] : 0.f;
-    };
     auto pack_split = [](float v) -> unsigned int {
         __bf16 vh, vl;
         split_bf16(v, vh, vl);
         return (unsigned int)__builtin_bit_cast(unsigned short, vh) | ((unsigned int)__builtin_bit_cast(unsigned short, vl) << 16);
     };
-    int k = blockIdx.x;
+    const TileSrc src{frames, fstride, H, W, lg_tiles_x, lg_tiles_per_frame};
     __shared__ SkipLds skl;
-    const int nrun = tiles_to_run(skl, sa, ntiles);
-    const bool listed = nrun != ntiles;                       // a complete list is ascending, i.e. the identity: no lookups
-    int round = 0;
-    int t = k < nrun ? tile_at(skl, sa, listed, 0, k, nrun) : 0;
-    if (listed && skip_fill_first()) skip_fill<PS, TOKENS>(sa, lg_tiles_x, features);
-    else if (stagger > 0 && ((blockIdx.x / 256) & 1))
-        for (int i = 0; i < stagger; ++i) __builtin_amdgcn_s_sleep(127);
-    if (k < nrun) {
-        xs[tid] = pack_split(x_fetch(t, tid));
-        if (tid + 256 < B3_XH * B3_XW) xs[tid + 256] = pack_split(x_fetch(t, tid + 256));
-    }
-    __syncthreads();
+    TileWalk wk;
+    wk.begin<PS, TOKENS>(skl, sa, src, ntiles, stagger, features, xs, pack_split);
 
-    for (; k < nrun; k += gridDim.x) {
-        const int b = t >> lg_tiles_per_frame, rem = t & ((1 << lg_tiles_per_frame) - 1);
-        const int r0 = (rem >> lg_tiles_x) * B3_TH, c0 = (rem & ((1 << lg_tiles_x) - 1)) * B3_TW;
+    for (; wk.k < wk.nrun; wk.k += gridDim.x) {
+        int b, r0, c0;
+        src.decode(wk.t, b, r0, c0);
 
         __builtin_amdgcn_s_setprio(S16_PRIO_CONV1);
 #ifdef SMK_ENC_ABLATE      // timing ablations (tools/enc_ablate.sh; never a product build): 1 conv1 only on a workgroup's first tile,
                            // 2 no BN/ReLU/pool epilogue, 4 no workgroup barriers, 8 no conv2 MFMAs -- results are wrong by construction
-        const bool abl_conv1 = !((SMK_ENC_ABLATE & 1) && k != (int)blockIdx.x);
+        const bool abl_conv1 = !((SMK_ENC_ABLATE & 1) && wk.k != (int)blockIdx.x);
 #else
         constexpr bool abl_conv1 = true;
 #endif
@@ -961,18 +1012,7 @@ __global__ __launch_bounds__(256, 2) void k_encoder_b16(const float *__restrict_
             int pix; bool valid, inimg;
             x_frags(wave, xh, xl, pix, valid, inimg);
             f32x16 acc0, acc1;
-#pragma unroll
-            for (int g = 0; g < 16; ++g) { acc0[g] = 0.f; acc1[g] = 0.f; }
-            const unsigned char *wrow = w1s + r * B3_W1_PITCH + 8 * hi * 2;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const bf16x8 a0h = *reinterpret_cast<const bf16x8 *>(wrow + s * 32);
-                const bf16x8 a1hh = *reinterpret_cast<const bf16x8 *>(wrow + 32 * B3_W1_PITCH + s * 32);
-                const bf16x8 a0l = *reinterpret_cast<const bf16x8 *>(wrow + B3_W1_BYTES + s * 32);
-                const bf16x8 a1l_ = *reinterpret_cast<const bf16x8 *>(wrow + B3_W1_BYTES + 32 * B3_W1_PITCH + s * 32);
-                mma3<true>(acc0, a0h, a0l, xh[s], xl[s]);
-                mma3<true>(acc1, a1hh, a1l_, xh[s], xl[s]);
-            }
+            conv1_both<true>(w1s, xh, xl, acc0, acc1);
             conv1_store(acc0, 0, pix, valid, inimg);
             conv1_store(acc1, 1, pix, valid, inimg);
         }
@@ -982,15 +1022,7 @@ __global__ __launch_bounds__(256, 2) void k_encoder_b16(const float *__restrict_
             const int cb = wave & 1;
             x_frags(4 + (wave >> 1), xh, xl, pix, valid, inimg);
             f32x16 acc;
-#pragma unroll
-            for (int g = 0; g < 16; ++g) acc[g] = 0.f;
-            const unsigned char *wrow = w1s + (cb * 32 + r) * B3_W1_PITCH + 8 * hi * 2;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const bf16x8 ah = *reinterpret_cast<const bf16x8 *>(wrow + s * 32);
-                const bf16x8 al = *reinterpret_cast<const bf16x8 *>(wrow + B3_W1_BYTES + s * 32);
-                mma3<true>(acc, ah, al, xh[s], xl[s]);
-            }
+            conv1_one<true>(w1s, cb, xh, xl, acc);
             conv1_store(acc, cb, pix, valid, inimg);
         }
 #if !defined(SMK_ENC_ABLATE) || !(SMK_ENC_ABLATE & 4)
@@ -998,14 +1030,8 @@ __global__ __launch_bounds__(256, 2) void k_encoder_b16(const float *__restrict_
 #endif
         __builtin_amdgcn_s_setprio(S16_PRIO_KLOOP);
 
-        const int kn = k + gridDim.x;
-        ++round;
-        const int tn = kn < nrun ? tile_at(skl, sa, listed, round, kn, nrun) : 0;
-        float xr0 = 0.f, xr1 = 0.f;
-        if (kn < nrun) {
-            xr0 = x_fetch(tn, tid);
-            xr1 = x_fetch(tn, tid + 256);
-        }
+        float xr0, xr1;                                       // next tile's x halo -> registers (lands under the K loop)
+        wk.next(skl, sa, src, xr0, xr1);
 
         // ---- conv2: acc[mt][nt][reg] = D(pixel row mt, column 4 kg + reg; channel 16 nt + px of the wave's 32)
         f32x4v acc[8][2];
@@ -1145,816 +1171,13 @@ __global__ __launch_bounds__(256, 2) void k_encoder_b16(const float *__restrict_
             }
         }
 
-        xs[tid] = pack_split(xr0);
-        if (tid + 256 < B3_XH * B3_XW) xs[tid + 256] = pack_split(xr1);
+        halo_to_lds(xs, xr0, xr1, pack_split);
 #if !defined(SMK_ENC_ABLATE) || !(SMK_ENC_ABLATE & 4)
         __syncthreads();
 #endif
-        t = tn;
+        wk.t = wk.tn;
     }
-    if (listed && !skip_fill_first()) {
-        __builtin_amdgcn_s_setprio(0);
-        skip_fill<PS, TOKENS>(sa, lg_tiles_x, features);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// The encoder's FIRST convolution for training (smokephys_net.py:25, Conv2d(1, 64, 7, padding=3) under autograd), in plain fp32 on the
-// vector ALUs -- 26 GFLOP per batch of 64 x 256^2, nothing for the matrix cores to win, and its output feeds train-mode BatchNorm +
-// ReLU, so it has to be as exact as an fp32 convolution (see k_conv2_fwd_b16).  Having both convolutions here also takes MIOpen's
-// find pass (20-50 s on a fresh machine for these two layers) out of the first training step.
-// k_conv1_train_fwd: z1[b][c][i][j] = bias[c] + sum over the 49 taps (ki-major, one fma chain) of x[b][i+ki-3][j+kj-3] * w[c][ki][kj].
-//   A workgroup = 4 rows x 256 columns; a thread = 4 consecutive pixels of one row, their 7 x 10 window of x in registers; the 64
-//   channels in turn, each channel's 49 weights as 13 broadcast ds_read_b128 for 196 fmas; z1 stored as float4.
-constexpr int C1_WP = 52;                                     // weights per channel in LDS (49 + 3 pad: 13 float4)
-__global__ __launch_bounds__(256) void k_conv1_train_fwd(const float *__restrict__ x, int H, int W, const float *__restrict__ w,
-                                                        const float *__restrict__ bias, float *__restrict__ z1) {
-    __shared__ __attribute__((aligned(16))) float ws[64 * C1_WP];
-    __shared__ float xs[10][264];                             // rows i0-3 .. i0+6, columns j0-3 .. j0+258 (+ pad)
-    const int tid = threadIdx.x, b = blockIdx.z, i0 = blockIdx.y * 4, j0 = blockIdx.x * 256;
-    for (int k = tid; k < 64 * C1_WP; k += 256) {
-        const int c = k / C1_WP, t = k - c * C1_WP;
-        ws[k] = t < 49 ? w[c * 49 + t] : 0.f;
-    }
-    const float *xb = x + (size_t)b * H * W;
-    // (addresses clamped into the image, values zeroed afterwards: a load under a condition is waited for before the next one is issued)
-    for (int k = tid; k < 10 * 262; k += 256) {
-        const int r = k / 262, cc = k - r * 262, ii = i0 - 3 + r, jj = j0 - 3 + cc;
-        const int ci = ii < 0 ? 0 : (ii > H - 1 ? H - 1 : ii), cj = jj < 0 ? 0 : (jj > W - 1 ? W - 1 : jj);
-        const float v = xb[(size_t)ci * W + cj];
-        xs[r][cc] = (ii == ci && jj == cj) ? v : 0.f;
-    }
-    __syncthreads();
-    const int jq = tid & 63, row = tid >> 6;
-    float win[7][10];
-#pragma unroll
-    for (int r = 0; r < 7; ++r)
-#pragma unroll
-        for (int cc = 0; cc < 10; ++cc) win[r][cc] = xs[row + r][4 * jq + cc];
-    const int i = i0 + row, j = j0 + 4 * jq;
-    if (i >= H || j >= W) return;                             // (W % 4 == 0: a quad is inside or outside as a whole)
-    float *dst = z1 + ((size_t)b * 64 * H + i) * W + j;
-#pragma unroll 1
-    for (int c = 0; c < 64; ++c) {
-        float wv[C1_WP];
-#pragma unroll
-        for (int q = 0; q < C1_WP / 4; ++q) {
-            const float4 t4 = *reinterpret_cast<const float4 *>(&ws[c * C1_WP + 4 * q]);
-            wv[4 * q] = t4.x; wv[4 * q + 1] = t4.y; wv[4 * q + 2] = t4.z; wv[4 * q + 3] = t4.w;
-        }
-        float acc[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ki = 0; ki < 7; ++ki)
-#pragma unroll
-            for (int kj = 0; kj < 7; ++kj)
-#pragma unroll
-                for (int p = 0; p < 4; ++p) acc[p] = fmaf(win[ki][kj + p], wv[ki * 7 + kj], acc[p]);
-        const float bb = bias ? bias[c] : 0.f;
-        *reinterpret_cast<float4 *>(dst + (size_t)c * H * W) = make_float4(acc[0] + bb, acc[1] + bb, acc[2] + bb, acc[3] + bb);
-    }
-}
-
-// k_conv1_train_wgrad: dW[c][ki][kj] = sum over b, i, j of dz[b][c][i][j] * x[b][i+ki-3][j+kj-3] (and db[c] = sum of dz): an outer-product
-// accumulation over 4.2 M pixels.  A persistent workgroup walks tiles of 4 rows x 64 columns; dz of the tile sits in LDS as float4 per
-// (4-channel group, pixel), x as a 10 x 70 halo; a thread owns 4 channels x one kernel row (28 accumulators + 4 for db) for half of the
-// tile's rows: per pixel one ds_read_b128 of dz, one new x value into a 7-wide sliding window, 28 fmas.  Partials per workgroup, added in
-// workgroup order by k_conv1_wgrad_finish (deterministic).
-constexpr int C1G_PX = 4 * 64;                                // pixels per tile
-constexpr int C1G_ZP = C1G_PX * 4 + 4;                        // floats per channel group in LDS (+ 4: the 16 groups start on different banks)
-__global__ __launch_bounds__(256) void k_conv1_train_wgrad(const float *__restrict__ dz, const float *__restrict__ x, int H, int W, int tiles_x,
-                                                          int tiles_per_frame, int ntiles, float *__restrict__ part) {
-    extern __shared__ __attribute__((aligned(16))) float smemf[];
-    float *zs = smemf;                                        // [16 groups][C1G_ZP]
-    float *xs = smemf + 16 * C1G_ZP;                          // [10][72]
-    const int tid = threadIdx.x;
-    const int st = tid / 112, rem = tid - st * 112, cg = rem / 7, ky = rem - cg * 7;      // tid >= 224: staging only
-    float acc[4][7], dbs[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int k = 0; k < 7; ++k) acc[c][k] = 0.f;
-    const size_t plane = (size_t)H * W;
-    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const int b = t / tiles_per_frame, rm = t - b * tiles_per_frame;
-        const int i0 = (rm / tiles_x) * 4, j0 = (rm % tiles_x) * 64;
-        // stage dz: (group g, pixel p) -> float4 of channels 4g .. 4g+3; 16 x 256 items, 16 per thread, lanes along the pixels
-#pragma unroll 4
-        for (int k = 0; k < 16; ++k) {
-            const int it = tid + 256 * k, g = it >> 8, p = it & 255, r = p >> 6, cc = p & 63;
-            const float *src = dz + ((size_t)b * 64 + 4 * g) * plane + (size_t)(i0 + r) * W + j0 + cc;
-            *reinterpret_cast<float4 *>(&zs[g * C1G_ZP + 4 * p]) = make_float4(src[0], src[plane], src[2 * plane], src[3 * plane]);
-        }
-        const float *xb = x + (size_t)b * plane;
-        for (int k = tid; k < 10 * 70; k += 256) {
-            const int r = k / 70, cc = k - r * 70, ii = i0 - 3 + r, jj = j0 - 3 + cc;
-            const int ci = ii < 0 ? 0 : (ii > H - 1 ? H - 1 : ii), cj = jj < 0 ? 0 : (jj > W - 1 ? W - 1 : jj);
-            const float v = xb[(size_t)ci * W + cj];            // (clamped address, value zeroed: no load under a condition)
-            xs[r * 72 + cc] = (ii == ci && jj == cj) ? v : 0.f;
-        }
-        __syncthreads();
-        if (tid < 224) {
-#pragma unroll 1
-            for (int r = 2 * st; r < 2 * st + 2; ++r) {
-                const float *xr = xs + (r + ky) * 72;         // x row i0 + r + ky - 3
-                float xv[7];
-#pragma unroll
-                for (int k = 0; k < 6; ++k) xv[k + 1] = xr[k];
-#pragma unroll 4
-                for (int cc = 0; cc < 64; ++cc) {
-#pragma unroll
-                    for (int k = 0; k < 6; ++k) xv[k] = xv[k + 1];
-                    xv[6] = xr[cc + 6];
-                    const float4 d = *reinterpret_cast<const float4 *>(&zs[cg * C1G_ZP + 4 * (r * 64 + cc)]);
-                    const float dv[4] = {d.x, d.y, d.z, d.w};
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-#pragma unroll
-                        for (int k = 0; k < 7; ++k) acc[c][k] = fmaf(dv[c], xv[k], acc[c][k]);
-                        if (ky == 0) dbs[c] += dv[c];
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    }
-    // the two row-halves of the workgroup: half 1 hands its sums to half 0 through LDS, half 0 stores the workgroup's partial
-    float *ex = smemf;                                        // [112][32]
-    if (st == 1 && tid < 224) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-#pragma unroll
-            for (int k = 0; k < 7; ++k) ex[rem * 32 + c * 7 + k] = acc[c][k];
-            ex[rem * 32 + 28 + c] = dbs[c];
-        }
-    }
-    __syncthreads();
-    if (st == 0) {
-        float *dst = part + (size_t)blockIdx.x * (64 * 49 + 64);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-#pragma unroll
-            for (int k = 0; k < 7; ++k) dst[(4 * cg + c) * 49 + ky * 7 + k] = acc[c][k] + ex[rem * 32 + c * 7 + k];
-            if (ky == 0) dst[64 * 49 + 4 * cg + c] = dbs[c] + ex[rem * 32 + 28 + c];
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_conv1_wgrad_finish(const float *__restrict__ part, int nparts, float *__restrict__ dw, float *__restrict__ db) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= 64 * 49 + 64) return;
-    float s = 0.f;
-    for (int k = 0; k < nparts; ++k) s += part[(size_t)k * (64 * 49 + 64) + i];
-    if (i < 64 * 49) dw[i] = s;
-    else if (db) db[i - 64 * 49] = s;
-}
-
-constexpr int C1G_LDS = (16 * C1G_ZP + 10 * 72) * 4;          // 68,672 B
-int conv1_wgrad_parts() { return device_num_cu() * 2; }
-size_t conv1_wgrad_workspace_bytes() { return (size_t)conv1_wgrad_parts() * (64 * 49 + 64) * sizeof(float); }
-
-hipError_t launch_conv1_train_forward(const float *x, const float *weight, const float *bias, int B, int H, int W, float *z1, hipStream_t st) {
-    if (W % 4 != 0 || B < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_conv1_train_fwd, dim3(cdiv(W, 256), cdiv(H, 4), B), dim3(256), 0, st, x, H, W, weight, bias, z1);
-    return hipGetLastError();
-}
-
-hipError_t launch_conv1_train_wgrad(const float *dz, const float *x, int B, int H, int W, float *dw, float *db, void *workspace, hipStream_t st) {
-    if (H % 4 != 0 || W % 64 != 0 || B < 1) return hipErrorInvalidValue;
-    const int tiles_x = W / 64, tiles_per_frame = tiles_x * (H / 4), ntiles = B * tiles_per_frame;
-    int nparts = conv1_wgrad_parts();
-    once_per_device((const void *)k_conv1_train_wgrad, [&] {
-        (void)hipFuncSetAttribute((const void *)k_conv1_train_wgrad, hipFuncAttributeMaxDynamicSharedMemorySize, C1G_LDS);
-    });
-    const int grid = nparts < ntiles ? nparts : ntiles;
-    float *part = static_cast<float *>(workspace);
-    hipLaunchKernelGGL(k_conv1_train_wgrad, dim3(grid), dim3(256), C1G_LDS, st, dz, x, H, W, tiles_x, tiles_per_frame, ntiles, part);
-    hipLaunchKernelGGL(k_conv1_wgrad_finish, dim3(cdiv(64 * 49 + 64, 256)), dim3(256), 0, st, part, grid, dw, db);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// k_conv2_fwd_b16: the encoder's second convolution alone, for TRAINING (smokephys_net.py:28, Conv2d(64, 128, 3, padding=1) under
-// autograd): z2 = conv(a1, w) + bias with a1 the activated first block [B, 64, H, W] and z2 [B, 128, H, W], both NCHW fp32 in HBM
-// (train-mode BatchNorm needs the whole z2 before it can normalise, so nothing fuses across it).  The tile (8 x 16 pixels, 180-pixel
-// halo image in LDS as swizzled bf16 planes) and the tap-loop skeleton are k_encoder_b16's; the prologue stages the halo tile from
-// HBM (a thread owns one pixel and one group of 8 channels: 8 loads whose lanes run along a row, one split, one 16-byte store per
-// plane) instead of computing it, and the epilogue stores the raw accumulators (+ bias) as 16-byte row pieces.
-// ARITHMETIC: three bf16 terms per operand (v = h + m + l, 24 bits) and the six products h*h, h*m, m*h, m*m, h*l, l*h -- not the eval
-// encoder's two terms / three products: this output feeds train-mode BatchNorm + ReLU, whose masks turn a 5e-6 forward error into a
-// 1e-2 error of conv2.weight.grad (in fp64, noise of relative size 5e-7 / 5e-6 on z2 moves that gradient by 4e-3 / 1.7e-2), so the
-// training forward has to be as exact as an fp32 convolution.  Per MFMA it moves LESS operand data than the three-product loop (12 A
-// fragments and 6 B fragments per 96 MFMAs against 8 and 4 per 48).
-constexpr int C2F_LDS = 3 * S16_A1_BYTES;                     // 69,120 -> 2 workgroups per CU
-__device__ __forceinline__ void split3_bf16(float v, __bf16 &h, __bf16 &m, __bf16 &l) {
-    h = (__bf16)v;
-    const float r1 = v - (float)h;
-    m = (__bf16)r1;
-    l = (__bf16)(r1 - (float)m);
-}
-
-__global__ __launch_bounds__(256, 2) void k_conv2_fwd_b16(const float *__restrict__ a1, int H, int W, const unsigned short *__restrict__ w2s,
-                                                       const float *__restrict__ bias, float *__restrict__ z2, int tiles_x,
-                                                       int tiles_per_frame, int ntiles) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char *a1p[3] = {smem, smem + S16_A1_BYTES, smem + 2 * S16_A1_BYTES};
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int px = lane & 15, kg = lane >> 4;
-    const int o0 = wave * 32 + px;                                            // N tile 0; tile 1 = + 16
-    const float b2a = bias ? bias[o0] : 0.f, b2b = bias ? bias[o0 + 16] : 0.f;
-    const int lane_b = o0 * 64 + kg * 16;
-    const __amdgpu_buffer_rsrc_t wrsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(w2s), 0, 18 * 3 * 8192, 0x00020000);
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    auto load_b = [&](int ks, int part, int nt) -> uint4 {
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane_b, (ks * 3 + part) * 8192 + nt * 1024, 0);
-        return make_uint4(v.x, v.y, v.z, v.w);
-    };
-    uint4 bq[2][2][3];                                        // [slot][nt][h | m | l]
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-        for (int part = 0; part < 3; ++part) bq[0][nt][part] = load_b(0, part, nt);
-    const size_t plane = (size_t)H * W;
-    constexpr int ITEMS = (B3_TH + 2) * 8 * B3_AW;            // 10 rows x 8 channel groups x 18 pixels = 1,440 (pixel fastest)
-    constexpr int NIT = (ITEMS + 255) / 256;                  // 6 per thread
-
-    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const int b = t / tiles_per_frame, rem = t - b * tiles_per_frame;
-        const int r0 = (rem / tiles_x) * B3_TH, c0 = (rem % tiles_x) * B3_TW;
-        __builtin_amdgcn_s_setprio(S16_PRIO_CONV1);
-        // ---- stage the halo tile: all of a thread's loads first (addresses clamped into the image, values zeroed afterwards), then split + store
-        {
-            const float *ab = a1 + (size_t)b * 64 * plane;
-            float v[NIT][8];
-#pragma unroll
-            for (int j = 0; j < NIT; ++j) {
-                int idx = tid + 256 * j;
-                idx = idx < ITEMS ? idx : ITEMS - 1;
-                const int row = idx / (8 * B3_AW), rm = idx - row * (8 * B3_AW), g = rm / B3_AW, pc = rm - g * B3_AW;
-                const int ii = r0 - 1 + row, jj = c0 - 1 + pc;
-                const int ci = ii < 0 ? 0 : (ii > H - 1 ? H - 1 : ii), cj = jj < 0 ? 0 : (jj > W - 1 ? W - 1 : jj);
-                const float *src = ab + (size_t)(8 * g) * plane + (size_t)ci * W + cj;
-#pragma unroll
-                for (int c = 0; c < 8; ++c) v[j][c] = src[(size_t)c * plane];
-            }
-#pragma unroll
-            for (int j = 0; j < NIT; ++j) {
-                const int idx = tid + 256 * j;
-                if (idx < ITEMS) {
-                    const int row = idx / (8 * B3_AW), rm = idx - row * (8 * B3_AW), g = rm / B3_AW, pc = rm - g * B3_AW;
-                    const int ii = r0 - 1 + row, jj = c0 - 1 + pc;
-                    const bool in = ii >= 0 && ii < H && jj >= 0 && jj < W;
-                    const int p = row * B3_AW + pc;
-                    bf16x8 vh, vm, vl;
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) {
-                        __bf16 hh, mm, ll;
-                        split3_bf16(in ? v[j][c] : 0.f, hh, mm, ll);
-                        vh[c] = hh; vm[c] = mm; vl[c] = ll;
-                    }
-                    const int off = p * 128 + ((g ^ (p & 7)) * 16);
-                    *reinterpret_cast<bf16x8 *>(a1p[0] + off) = vh;
-                    *reinterpret_cast<bf16x8 *>(a1p[1] + off) = vm;
-                    *reinterpret_cast<bf16x8 *>(a1p[2] + off) = vl;
-                }
-            }
-        }
-        __syncthreads();                                      // a1 complete
-        __builtin_amdgcn_s_setprio(S16_PRIO_KLOOP);
-
-        // ---- conv2: acc[mt][nt][reg] = D(pixel row mt, column 4 kg + reg; channel 16 nt + px of the wave's 32); units as in k_encoder_b16
-        f32x4v acc[8][2];
-#pragma unroll
-        for (int mt = 0; mt < 8; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) acc[mt][nt][g] = 0.f;
-        const int c16[2] = {kg << 4, (4 + kg) << 4};
-        auto tap_consts8 = [&](int ki, int kj, int (&om8)[8]) {
-#pragma unroll
-            for (int m = 0; m < 8; ++m) om8[m] = ((px + kj) << 7) ^ (((px + kj + 2 * (m + ki)) & 7) << 4);
-        };
-        auto load_a = [&](int ki, int half, int mq, const int (&om8)[8], bf16x8 (&af)[3][2]) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int m = 2 * mq + j;
-                const int off = (om8[m] ^ c16[half]) + (ki + m) * (B3_AW * 128);
-#pragma unroll
-                for (int part = 0; part < 3; ++part) af[part][j] = *reinterpret_cast<const bf16x8 *>(a1p[part] + off);
-            }
-        };
-        // unit u = half * 4 + mq of a tap: pixel rows 2mq, 2mq+1 of k-step (tap, half): 24 MFMAs on 6 A fragments and the k-step's 6 B fragments
-        bf16x8 afA[3][2], afB[3][2];
-        int om8[8];
-        tap_consts8(0, 0, om8);
-        load_a(0, 0, 0, om8, afA);
-        int ki = 0, kj = 0;
-#pragma unroll 1
-        for (int tap = 0; tap < 9; ++tap) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int half = u >> 2, mq = u & 3, slot = half;
-                if (mq == 0) {                                 // refill the other slot with k-step ks + 1: six fragments, at the k-step's start
-                    int kn = tap * 2 + half + 1;
-                    kn = kn >= 18 ? kn - 18 : kn;
-                    kn = __builtin_amdgcn_readfirstlane(kn);
-#pragma unroll
-                    for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                        for (int part = 0; part < 3; ++part) bq[slot ^ 1][nt][part] = load_b(kn, part, nt);
-                }
-                if (u < 7) {
-                    if (u & 1) load_a(ki, (u + 1) >> 2, (u + 1) & 3, om8, afA);
-                    else load_a(ki, (u + 1) >> 2, (u + 1) & 3, om8, afB);
-                } else if (tap < 8) {                          // u = 7 is odd: the next tap's first unit goes to set A
-                    kj = kj == 2 ? 0 : kj + 1;
-                    ki = kj == 0 ? ki + 1 : ki;
-                    tap_consts8(ki, kj, om8);
-                    load_a(ki, 0, 0, om8, afA);
-                }
-                // six products, smallest first, product-major (consecutive MFMAs go to different accumulators: dependency distance 4)
-#pragma unroll
-                for (int pr = 0; pr < 6; ++pr)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-#pragma unroll
-                        for (int nt = 0; nt < 2; ++nt) {
-                            constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};       // l*h, h*l, m*m, m*h, h*m, h*h
-                            const bf16x8 av = (u & 1) ? afB[PA[pr]][j] : afA[PA[pr]][j];
-                            const bf16x8 bv = __builtin_bit_cast(bf16x8, bq[slot][nt][PB[pr]]);
-                            f32x4v &c = acc[2 * mq + j][nt];
-                            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, c, 0, 0, 0);
-                        }
-                // 24 MFMAs: the next unit's 6 fragment reads one per four MFMAs, a k-step's six weight loads behind the first MFMAs of its first unit
-#pragma unroll
-                for (int i = 0; i < 24; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    if (i % 4 == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    else if (mq == 0 && i < 9) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-
-        // ---- epilogue: z2 = acc + bias.  Lane: channel o0 (nt 0) / o0 + 16 (nt 1), pixels (row mt, cols 4kg .. 4kg+3): 16-byte stores
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            const float bb = nt ? b2b : b2a;
-            float *dst = z2 + ((size_t)b * 128 + o0 + 16 * nt) * plane + (size_t)r0 * W + c0 + 4 * kg;
-#pragma unroll
-            for (int mt = 0; mt < 8; ++mt) {
-                const f32x4v c = acc[mt][nt];
-                *reinterpret_cast<float4 *>(dst + (size_t)mt * W) = make_float4(c[0] + bb, c[1] + bb, c[2] + bb, c[3] + bb);
-            }
-        }
-        __syncthreads();                                      // every wave is done reading a1
-    }
-}
-
-// k_conv2_dgrad_b16: the data gradient of the same convolution, dX[b][c] = sum over o, taps of dZ[b][o][y + ky' - 1][x + kx' - 1] * W[o][c][2 - ky'][2 - kx']
-// -- a 3x3 convolution from 128 channels to 64 with the flipped kernel.  Same tile, halo image and swizzle; the 128 input channels
-// go through the 64-channel LDS image as two passes (stage half, 18 k-steps, stage the other half, 18 more) into the same accumulators.
-// With only 64 outputs the waves split the tile's rows as well as the channels: wave = (4 M-tiles, 2 N-tiles), so every unit of 24
-// MFMAs is a k-step of its own (8 A-fragment reads as in the forward, 4 weight-fragment loads: twice the forward's weight stream).
-// w2d: [pass 2][k-step 18 = tap' * 2 + o_local / 32][hi|lo][c 64][32 o]: 4 KiB per (k-step, part).
-__global__ __launch_bounds__(256, 2) void k_conv2_dgrad_b16(const float *__restrict__ dz, int H, int W, const unsigned short *__restrict__ w2d,
-                                                         float *__restrict__ dx, int tiles_x, int tiles_per_frame, int ntiles) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char *a1h = smem, *a1l = a1h + S16_A1_BYTES;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int px = lane & 15, kg = lane >> 4;
-    const int mh = wave & 1, nh = wave >> 1;
-    const int c0o = nh * 32 + px;                                             // output channel of N tile 0; tile 1 = + 16
-    const int lane_b = c0o * 64 + kg * 16;
-    const __amdgpu_buffer_rsrc_t wrsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(w2d), 0, 2 * 18 * 2 * 4096, 0x00020000);
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    auto load_b = [&](int ks36, int part, int nt) -> uint4 {                  // ks36 = pass * 18 + k-step
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane_b, (ks36 * 2 + part) * 4096 + nt * 1024, 0);
-        return make_uint4(v.x, v.y, v.z, v.w);
-    };
-    uint4 bq[2][2][2];
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-        bq[0][nt][0] = load_b(0, 0, nt);
-        bq[0][nt][1] = load_b(0, 1, nt);
-    }
-    const size_t plane = (size_t)H * W;
-    constexpr int ITEMS = (B3_TH + 2) * 8 * B3_AW, NIT = (ITEMS + 255) / 256;
-    const unsigned char *a1h_w = a1h + mh * 4 * (B3_AW * 128), *a1l_w = a1l + mh * 4 * (B3_AW * 128);
-    const int c16[2] = {kg << 4, (4 + kg) << 4};
-
-    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const int b = t / tiles_per_frame, rem = t - b * tiles_per_frame;
-        const int r0 = (rem / tiles_x) * B3_TH, c0 = (rem % tiles_x) * B3_TW;
-        f32x4v acc[4][2];
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) acc[m][nt][g] = 0.f;
-#pragma unroll 1
-        for (int pass = 0; pass < 2; ++pass) {
-            __builtin_amdgcn_s_setprio(S16_PRIO_CONV1);
-            {   // stage the halo tile of dZ's channels 64 pass .. 64 pass + 63 (as k_conv2_fwd_b16 stages a1)
-                const float *ab = dz + ((size_t)b * 128 + 64 * pass) * plane;
-                float v[NIT][8];
-#pragma unroll
-                for (int j = 0; j < NIT; ++j) {
-                    int idx = tid + 256 * j;
-                    idx = idx < ITEMS ? idx : ITEMS - 1;
-                    const int row = idx / (8 * B3_AW), rm = idx - row * (8 * B3_AW), g = rm / B3_AW, pc = rm - g * B3_AW;
-                    const int ii = r0 - 1 + row, jj = c0 - 1 + pc;
-                    const int ci = ii < 0 ? 0 : (ii > H - 1 ? H - 1 : ii), cj = jj < 0 ? 0 : (jj > W - 1 ? W - 1 : jj);
-                    const float *src = ab + (size_t)(8 * g) * plane + (size_t)ci * W + cj;
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) v[j][c] = src[(size_t)c * plane];
-                }
-#pragma unroll
-                for (int j = 0; j < NIT; ++j) {
-                    const int idx = tid + 256 * j;
-                    if (idx < ITEMS) {
-                        const int row = idx / (8 * B3_AW), rm = idx - row * (8 * B3_AW), g = rm / B3_AW, pc = rm - g * B3_AW;
-                        const int ii = r0 - 1 + row, jj = c0 - 1 + pc;
-                        const bool in = ii >= 0 && ii < H && jj >= 0 && jj < W;
-                        const int p = row * B3_AW + pc;
-                        bf16x8 vh, vl;
-#pragma unroll
-                        for (int c = 0; c < 8; ++c) {
-                            __bf16 hh, ll;
-                            split_bf16(in ? v[j][c] : 0.f, hh, ll);
-                            vh[c] = hh; vl[c] = ll;
-                        }
-                        const int off = p * 128 + ((g ^ (p & 7)) * 16);
-                        *reinterpret_cast<bf16x8 *>(a1h + off) = vh;
-                        *reinterpret_cast<bf16x8 *>(a1l + off) = vl;
-                    }
-                }
-            }
-            __syncthreads();                                  // the image is complete
-            __builtin_amdgcn_s_setprio(S16_PRIO_KLOOP);
-            auto tap_consts = [&](int ki, int kj, int (&om)[4]) {
-#pragma unroll
-                for (int m = 0; m < 4; ++m) om[m] = ((px + kj) << 7) ^ (((px + kj + 2 * (m + ki)) & 7) << 4);
-            };
-            auto load_a = [&](int ki, int half, const int (&om)[4], bf16x8 (&ah)[4], bf16x8 (&al)[4]) {
-                const unsigned char *ph = a1h_w + ki * (B3_AW * 128), *pl = a1l_w + ki * (B3_AW * 128);
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    const int off = om[m] ^ c16[half];
-                    ah[m] = *reinterpret_cast<const bf16x8 *>(ph + off + m * (B3_AW * 128));
-                    al[m] = *reinterpret_cast<const bf16x8 *>(pl + off + m * (B3_AW * 128));
-                }
-            };
-            bf16x8 ahA[4], alA[4], ahB[4], alB[4];
-            int om[4];
-            tap_consts(0, 0, om);
-            load_a(0, 0, om, ahA, alA);
-            int ki = 0, kj = 0;
-#pragma unroll 1
-            for (int tap = 0; tap < 9; ++tap) {
-#pragma unroll
-                for (int half = 0; half < 2; ++half) {
-                    const int slot = half;
-                    {   // refill the other slot with the next k-step (the ring runs through both passes and on into the next tile)
-                        int kn = pass * 18 + tap * 2 + half + 1;
-                        kn = kn >= 36 ? kn - 36 : kn;
-                        kn = __builtin_amdgcn_readfirstlane(kn);
-#pragma unroll
-                        for (int nt = 0; nt < 2; ++nt) {
-                            bq[slot ^ 1][nt][0] = load_b(kn, 0, nt);
-                            bq[slot ^ 1][nt][1] = load_b(kn, 1, nt);
-                        }
-                    }
-                    if (half == 0) {
-                        load_a(ki, 1, om, ahB, alB);
-                    } else if (tap < 8) {
-                        kj = kj == 2 ? 0 : kj + 1;
-                        ki = kj == 0 ? ki + 1 : ki;
-                        tap_consts(ki, kj, om);
-                        load_a(ki, 0, om, ahA, alA);
-                    }
-#pragma unroll
-                    for (int pr = 0; pr < 3; ++pr)
-#pragma unroll
-                        for (int m = 0; m < 4; ++m)
-#pragma unroll
-                            for (int nt = 0; nt < 2; ++nt) {
-                                const bf16x8 bh = __builtin_bit_cast(bf16x8, bq[slot][nt][0]);
-                                const bf16x8 bl = __builtin_bit_cast(bf16x8, bq[slot][nt][1]);
-                                f32x4v &c = acc[m][nt];
-                                const bf16x8 ah = half ? ahB[m] : ahA[m], al = half ? alB[m] : alA[m];
-                                if (pr == 0) c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, c, 0, 0, 0);
-                                else if (pr == 1) c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, c, 0, 0, 0);
-                                else c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, c, 0, 0, 0);
-                            }
-#pragma unroll
-                    for (int i = 0; i < 24; ++i) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        if (i % 3 == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                        else if (i == 1 || i == 2 || i == 4 || i == 5) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            __syncthreads();                                  // every wave is done reading the image
-        }
-        // ---- epilogue: dX rows 4 mh + m, columns 4kg .. 4kg+3 of channel c0o (+ 16): 16-byte stores
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            float *dst = dx + ((size_t)b * 64 + c0o + 16 * nt) * plane + (size_t)(r0 + 4 * mh) * W + c0 + 4 * kg;
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const f32x4v c = acc[m][nt];
-                *reinterpret_cast<float4 *>(dst + (size_t)m * W) = make_float4(c[0], c[1], c[2], c[3]);
-            }
-        }
-    }
-}
-
-// w [128 o][64 c][3][3] -> w2d [pass = o / 64][k-step = tap' * 2 + (o % 64) / 32][hi|lo][c 64][32 o], tap' = the flipped tap (2 - ky, 2 - kx)
-__global__ void k_split_conv2_weights_dgrad(const float *__restrict__ w, unsigned short *__restrict__ w2d_) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= 9 * 64 * 128) return;
-    const int o = t % 128, c = (t / 128) % 64, tap = t / (64 * 128);
-    const float v = w[((size_t)o * 64 + c) * 9 + tap];
-    const int ky = tap / 3, kx = tap - 3 * ky, tapf = (2 - ky) * 3 + (2 - kx);
-    __bf16 *w2d = reinterpret_cast<__bf16 *>(w2d_);
-    const __bf16 hi = (__bf16)v;
-    const int pass = o >> 6, ol = o & 63, ks = tapf * 2 + (ol >> 5), o32 = ol & 31;
-    const size_t base = ((size_t)(pass * 18 + ks) * 2) * 64 * 32;
-    w2d[base + (size_t)c * 32 + o32] = hi;
-    w2d[base + (size_t)64 * 32 + (size_t)c * 32 + o32] = (__bf16)(v - (float)hi);
-}
-
-hipError_t launch_conv2_train_dgrad(const float *dz, const float *weight, int B, int H, int W, float *dx, void *workspace, hipStream_t st) {
-    if (H % B3_TH != 0 || W % B3_TW != 0 || B < 1) return hipErrorInvalidValue;
-    unsigned short *w2d = static_cast<unsigned short *>(workspace);
-    hipLaunchKernelGGL(k_split_conv2_weights_dgrad, dim3(cdiv(9 * 64 * 128, 256)), dim3(256), 0, st, weight, w2d);
-    const int tiles_x = W / B3_TW, tiles_per_frame = tiles_x * (H / B3_TH), ntiles = B * tiles_per_frame;
-    constexpr int lds = 2 * S16_A1_BYTES;
-    const int wgs_per_cu = device_cached_int((const void *)k_conv2_dgrad_b16, [] {
-        (void)hipFuncSetAttribute((const void *)k_conv2_dgrad_b16, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k_conv2_dgrad_b16, 256, lds) != hipSuccess || n < 1) n = 2;
-        return n;
-    });
-    int nwg = device_num_cu() * wgs_per_cu;
-    if (nwg > ntiles) nwg = ntiles;
-    hipLaunchKernelGGL(k_conv2_dgrad_b16, dim3(nwg), dim3(256), lds, st, dz, H, W, w2d, dx, tiles_x, tiles_per_frame, ntiles);
-    return hipGetLastError();
-}
-
-// k_conv2_wgrad_b16: the weight gradient of the same convolution, dW[o][c][ky][kx] = sum over b, y, x of dZ[b][o][y][x] * a1[b][c][y+ky-1][x+kx-1]:
-// per 8 x 16 tile a GEMM D[o][(tap, c)] += A[o][pixel] * B[(tap, c)][pixel] with the PIXELS as the MFMA k dimension -- both operands are
-// pixel-contiguous in NCHW already, so staging is a copy + split (16 bytes of bf16 per 8 pixels of a row).
-//   workgroup: 32 output channels (2 M-tiles) x all 576 (tap, c) columns (36 N-tiles) for its stream of tiles; wave w: channels 16w .. 16w+15
-//              of a1 and all 9 taps (9 N-tiles): 72 accumulator registers, kept for the whole launch.
-//   k-step:    32 pixels = tile rows 2s, 2s+1; a lane's k-group kg = 8 consecutive x of one row (row 2s + (kg >> 1), x0 = 8 (kg & 1)).
-//   LDS:       dZ tile [hi|lo][32 o][128 px] (row pitch 272 B), a1 tile [hi|lo][64 c][10 rows][16 px] (c pitch 336 B: 16 lanes of one
-//              k-group read conflict-free) + the two halo columns [hi|lo][64 c][10 rows][2].
-//   taps:      ky moves the row (an address), kx = 1 reads the aligned 16-byte chunk, kx = 0 / 2 need the chunk shifted by one bf16: the
-//              neighbouring element comes from the other chunk of the row or from the halo column (one ds_read_u16 at a per-lane address)
-//              and four v_alignbit_b32 build the fragment.
-//   output:    every workgroup adds its tiles into registers and stores ONE partial [32 o][9 taps][64 c]; k_conv2_wgrad_finish adds the
-//              partials of a channel group in stream order (deterministic) and writes dW [128][64][3][3] (and db from the staged dZ).
-constexpr int WG_OG = 32;                                     // output channels per workgroup
-constexpr int WG_ZP = 272;                                    // dZ row pitch (bytes): 128 px * 2 B + 16
-constexpr int WG_AC = 336;                                    // a1 channel pitch (bytes): 10 rows * 32 B + 16
-constexpr int WG_Z_BYTES = WG_OG * WG_ZP;                     // 8,704 per plane
-constexpr int WG_A_BYTES = 64 * WG_AC;                        // 21,504 per plane
-constexpr int WG_H_BYTES = 64 * 10 * 2 * 2;                   // 2,560 per plane: [c][row][left|right] bf16
-constexpr int WG_LDS = 2 * (WG_Z_BYTES + WG_A_BYTES + WG_H_BYTES);   // 65,536
-
-__global__ __launch_bounds__(256, 2) void k_conv2_wgrad_b16(const float *__restrict__ dz, const float *__restrict__ a1, int H, int W, int tiles_x,
-                                                         int tiles_per_frame, int ntiles, int nstreams, float *__restrict__ part,
-                                                         float *__restrict__ dbpart) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char *zh = smem, *zl = zh + WG_Z_BYTES, *ah = zl + WG_Z_BYTES, *al = ah + WG_A_BYTES, *hh = al + WG_A_BYTES, *hl = hh + WG_H_BYTES;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n15 = lane & 15, kg = lane >> 4;
-    // blocks i and i + 8 share an XCD: the four channel groups of one tile stream sit on one XCD (a1 is fetched into that L2 once)
-    const int xcd = blockIdx.x & 7, og = (blockIdx.x >> 3) & 3, stream = (blockIdx.x >> 5) * 8 + xcd;
-    const size_t plane = (size_t)H * W;
-    f32x4v acc[2][9];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int t9 = 0; t9 < 9; ++t9)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) acc[m][t9][g] = 0.f;
-    float dbsum = 0.f;                                        // this thread's share of db: channel og*32 + tid / 8, pixels 16 (tid % 8) ..
-
-    for (int t = stream; t < ntiles; t += nstreams) {
-        const int b = t / tiles_per_frame, rem = t - b * tiles_per_frame;
-        const int r0 = (rem / tiles_x) * B3_TH, c0 = (rem % tiles_x) * B3_TW;
-        // ---- stage dZ: 32 o x 8 rows x 16 px; thread: o = tid / 8, row = tid % 8 (16 px = 4 x float4)
-        {
-            const int o = tid >> 3, row = tid & 7;
-            const float *src = dz + ((size_t)b * 128 + og * WG_OG + o) * plane + (size_t)(r0 + row) * W + c0;
-            float4 v[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const float4 *>(src + 4 * q);
-#pragma unroll
-            for (int hlf = 0; hlf < 2; ++hlf) {
-                const float f[8] = {v[2 * hlf].x, v[2 * hlf].y, v[2 * hlf].z, v[2 * hlf].w, v[2 * hlf + 1].x, v[2 * hlf + 1].y, v[2 * hlf + 1].z, v[2 * hlf + 1].w};
-                bf16x8 vh, vl;
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    __bf16 a_, b_;
-                    split_bf16(f[c], a_, b_);
-                    vh[c] = a_; vl[c] = b_;
-                    dbsum += f[c];
-                }
-                const int off = o * WG_ZP + (row * 16 + 8 * hlf) * 2;
-                *reinterpret_cast<bf16x8 *>(zh + off) = vh;
-                *reinterpret_cast<bf16x8 *>(zl + off) = vl;
-            }
-        }
-        // ---- stage a1: 64 c x 10 rows x 16 px (+ 2 halo columns); items (c, row): 640 -> 3 per thread (the last partly)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int it = tid + 256 * j;
-            if (it < 640) {
-                const int c = it / 10, row = it - c * 10;
-                const int ii = r0 - 1 + row;
-                const bool rin = ii >= 0 && ii < H;
-                const float *src = a1 + ((size_t)b * 64 + c) * plane + (size_t)(rin ? ii : 0) * W + c0;
-                float4 v[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const float4 *>(src + 4 * q);
-                const float lft = (rin && c0 > 0) ? src[-1] : 0.f, rgt = (rin && c0 + 16 < W) ? src[16] : 0.f;
-#pragma unroll
-                for (int hlf = 0; hlf < 2; ++hlf) {
-                    const float f[8] = {v[2 * hlf].x, v[2 * hlf].y, v[2 * hlf].z, v[2 * hlf].w, v[2 * hlf + 1].x, v[2 * hlf + 1].y, v[2 * hlf + 1].z, v[2 * hlf + 1].w};
-                    bf16x8 vh, vl;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        __bf16 a_, b_;
-                        split_bf16(rin ? f[e] : 0.f, a_, b_);
-                        vh[e] = a_; vl[e] = b_;
-                    }
-                    const int off = c * WG_AC + row * 32 + 16 * hlf;
-                    *reinterpret_cast<bf16x8 *>(ah + off) = vh;
-                    *reinterpret_cast<bf16x8 *>(al + off) = vl;
-                }
-                __bf16 lh_, ll_, rh_, rl_;
-                split_bf16(lft, lh_, ll_);
-                split_bf16(rgt, rh_, rl_);
-                __bf16 *ph = reinterpret_cast<__bf16 *>(hh) + (c * 10 + row) * 2, *pl = reinterpret_cast<__bf16 *>(hl) + (c * 10 + row) * 2;
-                ph[0] = lh_; ph[1] = rh_;
-                pl[0] = ll_; pl[1] = rl_;
-            }
-        }
-        __syncthreads();
-        // ---- 4 k-steps of 32 pixels: A = dZ (2 M-tiles), B = a1 of the wave's 16 channels at the 9 taps
-        const int cw = wave * 16 + n15;                       // the lane's a1 channel (B row)
-        const int x0 = 8 * (kg & 1);
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) {
-            const int prow = 2 * s4 + (kg >> 1);              // the lane's tile row in this k-step
-            bf16x8 azh[2], azl[2];
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                const int off = (m * 16 + n15) * WG_ZP + (prow * 16 + x0) * 2;
-                azh[m] = *reinterpret_cast<const bf16x8 *>(zh + off);
-                azl[m] = *reinterpret_cast<const bf16x8 *>(zl + off);
-            }
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky) {
-                const int arow = prow + ky;                   // row of the 10-row halo tile (tile row + ky - 1, + 1 for the halo)
-                const int rbase = cw * WG_AC + arow * 32;
-                typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-                const u32x4 ch = *reinterpret_cast<const u32x4 *>(ah + rbase + 2 * x0), cl = *reinterpret_cast<const u32x4 *>(al + rbase + 2 * x0);
-                // the element left of the chunk (x0 - 1) and right of it (x0 + 8): the row's other chunk, or the halo column
-                const int lo_off = x0 ? rbase + 14 : -1, ro_off = x0 ? -1 : rbase + 16;
-                const int hidx = ((cw * 10 + arow) * 2) * 2;
-                const unsigned int leh = lo_off >= 0 ? *reinterpret_cast<const unsigned short *>(ah + lo_off) : *reinterpret_cast<const unsigned short *>(hh + hidx);
-                const unsigned int lel = lo_off >= 0 ? *reinterpret_cast<const unsigned short *>(al + lo_off) : *reinterpret_cast<const unsigned short *>(hl + hidx);
-                const unsigned int reh = ro_off >= 0 ? *reinterpret_cast<const unsigned short *>(ah + ro_off) : *reinterpret_cast<const unsigned short *>(hh + hidx + 2);
-                const unsigned int rel = ro_off >= 0 ? *reinterpret_cast<const unsigned short *>(al + ro_off) : *reinterpret_cast<const unsigned short *>(hl + hidx + 2);
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    u32x4 fh, fl;
-                    if (kx == 1) {
-                        fh = ch; fl = cl;
-                    } else if (kx == 0) {                     // elements x0-1 .. x0+6
-                        fh[0] = leh | (ch[0] << 16); fl[0] = lel | (cl[0] << 16);
-#pragma unroll
-                        for (int i = 1; i < 4; ++i) {
-                            fh[i] = __builtin_amdgcn_alignbit(ch[i], ch[i - 1], 16);
-                            fl[i] = __builtin_amdgcn_alignbit(cl[i], cl[i - 1], 16);
-                        }
-                    } else {                                  // elements x0+1 .. x0+8
-#pragma unroll
-                        for (int i = 0; i < 3; ++i) {
-                            fh[i] = __builtin_amdgcn_alignbit(ch[i + 1], ch[i], 16);
-                            fl[i] = __builtin_amdgcn_alignbit(cl[i + 1], cl[i], 16);
-                        }
-                        fh[3] = (ch[3] >> 16) | (reh << 16); fl[3] = (cl[3] >> 16) | (rel << 16);
-                    }
-                    const bf16x8 bh = __builtin_bit_cast(bf16x8, fh), bl = __builtin_bit_cast(bf16x8, fl);
-                    const int t9 = ky * 3 + kx;
-#pragma unroll
-                    for (int m = 0; m < 2; ++m) {
-                        f32x4v &c = acc[m][t9];
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(azl[m], bh, c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(azh[m], bl, c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(azh[m], bh, c, 0, 0, 0);
-                    }
-                }
-            }
-        }
-        __syncthreads();                                      // every wave is done reading the tiles
-    }
-    // ---- this workgroup's partial: part[stream][og][o_local 32][tap 9][c 64]; D layout: lane (n15 = column = c, kg) holds rows 4kg .. 4kg+3 (= o)
-    float *dst = part + ((size_t)stream * 4 + og) * (WG_OG * 9 * 64);
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int t9 = 0; t9 < 9; ++t9)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) dst[((size_t)(m * 16 + 4 * kg + g) * 9 + t9) * 64 + wave * 16 + n15] = acc[m][t9][g];
-    // db partial: 8 threads per channel (tid % 8 = the tile row they staged), added in lane order
-    float sdb = dbsum;
-    sdb += __shfl_xor(sdb, 1); sdb += __shfl_xor(sdb, 2); sdb += __shfl_xor(sdb, 4);
-    if ((tid & 7) == 0) dbpart[((size_t)stream * 4 + og) * WG_OG + (tid >> 3)] = sdb;
-}
-
-// dW[o][c][tap] = sum over streams (in stream order) of part[stream][o / 32][o % 32][tap][c]; db[o] likewise
-__global__ __launch_bounds__(256) void k_conv2_wgrad_finish(const float *__restrict__ part, const float *__restrict__ dbpart, int nstreams,
-                                                          float *__restrict__ dw, float *__restrict__ db) {
-    const int i = blockIdx.x * 256 + threadIdx.x;             // over [o 128][tap 9][c 64]
-    if (i < 128 * 9 * 64) {
-        const int c = i & 63, t9 = (i >> 6) % 9, o = i / (9 * 64);
-        const float *src = part + ((size_t)(o >> 5) * (WG_OG * 9 * 64)) + ((size_t)(o & 31) * 9 + t9) * 64 + c;
-        float s = 0.f;
-        for (int st = 0; st < nstreams; ++st) s += src[(size_t)st * 4 * (WG_OG * 9 * 64)];
-        dw[((size_t)o * 64 + c) * 9 + t9] = s;
-    }
-    if (db && i < 128) {
-        float s = 0.f;
-        for (int st = 0; st < nstreams; ++st) s += dbpart[((size_t)st * 4 + (i >> 5)) * WG_OG + (i & 31)];
-        db[i] = s;
-    }
-}
-
-size_t conv2_wgrad_workspace_bytes(int nstreams) { return ((size_t)nstreams * 4 * (WG_OG * 9 * 64) + (size_t)nstreams * 4 * WG_OG) * sizeof(float); }
-int conv2_wgrad_streams() { return (device_num_cu() * 2 / 32) * 8; }     // two workgroups per CU, four channel groups per stream, 8 XCD slots
-
-hipError_t launch_conv2_train_wgrad(const float *dz, const float *a1, int B, int H, int W, float *dw, float *db, void *workspace, hipStream_t st) {
-    if (H % B3_TH != 0 || W % B3_TW != 0 || B < 1) return hipErrorInvalidValue;
-    const int tiles_x = W / B3_TW, tiles_per_frame = tiles_x * (H / B3_TH), ntiles = B * tiles_per_frame;
-    const int nstreams = conv2_wgrad_streams();
-    if (nstreams < 8) return hipErrorInvalidValue;
-    float *part = static_cast<float *>(workspace), *dbpart = part + (size_t)nstreams * 4 * (WG_OG * 9 * 64);
-    once_per_device((const void *)k_conv2_wgrad_b16, [&] {
-        (void)hipFuncSetAttribute((const void *)k_conv2_wgrad_b16, hipFuncAttributeMaxDynamicSharedMemorySize, WG_LDS);
-    });
-    hipLaunchKernelGGL(k_conv2_wgrad_b16, dim3(nstreams * 4), dim3(256), WG_LDS, st, dz, a1, H, W, tiles_x, tiles_per_frame, ntiles, nstreams, part, dbpart);
-    hipLaunchKernelGGL(k_conv2_wgrad_finish, dim3(cdiv(128 * 9 * 64, 256)), dim3(256), 0, st, part, dbpart, nstreams, dw, db);
-    return hipGetLastError();
-}
-
-// w [128 o][64 c][3][3] -> w2s [k-step = tap*2 + c/32][h|m|l][o][32 c] (the B fragments of the training forward's tap loop: three bf16 terms)
-__global__ void k_split_conv2_weights(const float *__restrict__ w, unsigned short *__restrict__ w2s_) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= 9 * 64 * 128) return;
-    const int c = t % 64, o = (t / 64) % 128, tap = t / (64 * 128);
-    const float v = w[((size_t)o * 64 + c) * 9 + tap];
-    __bf16 *w2s = reinterpret_cast<__bf16 *>(w2s_);
-    __bf16 h, m, l;
-    split3_bf16(v, h, m, l);
-    const int ks2 = tap * 2 + (c >> 5), c32 = c & 31;
-    w2s[((size_t)(ks2 * 3 + 0) * 128 + o) * 32 + c32] = h;
-    w2s[((size_t)(ks2 * 3 + 1) * 128 + o) * 32 + c32] = m;
-    w2s[((size_t)(ks2 * 3 + 2) * 128 + o) * 32 + c32] = l;
-}
-
-size_t conv2_train_workspace_bytes() { return (size_t)18 * 3 * 128 * 32 * sizeof(unsigned short); }     // (the data gradient uses 2/3 of it)
-
-hipError_t launch_conv2_train_forward(const float *a1, const float *weight, const float *bias, int B, int H, int W, float *z2, void *workspace,
-                                      hipStream_t st) {
-    if (H % B3_TH != 0 || W % B3_TW != 0 || B < 1) return hipErrorInvalidValue;
-    unsigned short *w2s = static_cast<unsigned short *>(workspace);
-    hipLaunchKernelGGL(k_split_conv2_weights, dim3(cdiv(9 * 64 * 128, 256)), dim3(256), 0, st, weight, w2s);
-    const int tiles_x = W / B3_TW, tiles_per_frame = tiles_x * (H / B3_TH), ntiles = B * tiles_per_frame;
-    constexpr int lds = C2F_LDS;
-    const int wgs_per_cu = device_cached_int((const void *)k_conv2_fwd_b16, [] {
-        (void)hipFuncSetAttribute((const void *)k_conv2_fwd_b16, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k_conv2_fwd_b16, 256, lds) != hipSuccess || n < 1) n = 2;
-        return n;
-    });
-    int nwg = device_num_cu() * wgs_per_cu;
-    if (nwg > ntiles) nwg = ntiles;
-    hipLaunchKernelGGL(k_conv2_fwd_b16, dim3(nwg), dim3(256), lds, st, a1, H, W, w2s, bias, z2, tiles_x, tiles_per_frame, ntiles);
-    return hipGetLastError();
+    wk.end<PS, TOKENS>(sa, src, features);
 }
 
 // Diagnostic switches, read once per process: SMK_ENC_STAGGER (s_sleep units of the second workgroup wave, default 1),
@@ -2122,106 +1345,6 @@ static hipError_t skip_prepare(EncoderSkip *sk, const float *frames, int64_t fst
     return hipSuccess;
 }
 
-template <bool TOKENS>
-static hipError_t launch_b16_t(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e, float *features,
-                               hipStream_t st, EncoderSkip *skip) {
-    const int PS = H / 32;
-    const int tiles_x = W / B3_TW, tiles_per_frame = tiles_x * (H / B3_TH), ntiles = B * tiles_per_frame;
-    int lg_tx = 0, lg_tpf = 0;
-    while ((1 << lg_tx) < tiles_x) ++lg_tx;
-    while ((1 << lg_tpf) < tiles_per_frame) ++lg_tpf;
-    if ((1 << lg_tx) != tiles_x || (1 << lg_tpf) != tiles_per_frame || (PS != 2 && PS != 4 && PS != 8)) return hipErrorInvalidValue;
-    const int stagger = enc_knobs().stagger;
-    const int num_cu = device_num_cu();
-    const int wgs_per_cu = device_cached_int((const void *)k_encoder_b16<8, TOKENS>, [] {
-        (void)hipFuncSetAttribute((const void *)k_encoder_b16<8, TOKENS>, hipFuncAttributeMaxDynamicSharedMemorySize, S16_LDS);
-        (void)hipFuncSetAttribute((const void *)k_encoder_b16<4, TOKENS>, hipFuncAttributeMaxDynamicSharedMemorySize, S16_LDS);
-        (void)hipFuncSetAttribute((const void *)k_encoder_b16<2, TOKENS>, hipFuncAttributeMaxDynamicSharedMemorySize, S16_LDS);
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k_encoder_b16<8, TOKENS>, 256, S16_LDS) != hipSuccess || n < 1) n = 2;
-        return enc_knobs().wgs_per_cu ? enc_knobs().wgs_per_cu : n;
-    });
-    // the fixed persistent grid, capped by the tile count of the call (never by the device-side list length)
-    auto run = [&](const float *fr, int64_t fs, int nt, float *out, const SkipArgs &sa) -> hipError_t {
-        int nwg = num_cu * wgs_per_cu;
-        if (nwg > nt) nwg = nt;
-        dim3 grid(nwg), block(256);
-        switch (PS) {
-            case 2: hipLaunchKernelGGL((k_encoder_b16<2, TOKENS>), grid, block, S16_LDS, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, sa); break;
-            case 4: hipLaunchKernelGGL((k_encoder_b16<4, TOKENS>), grid, block, S16_LDS, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, sa); break;
-            default: hipLaunchKernelGGL((k_encoder_b16<8, TOKENS>), grid, block, S16_LDS, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, sa); break;
-        }
-        return hipGetLastError();
-    };
-    SkipArgs plan;
-    hipError_t err = skip_prepare<0, TOKENS>(
-        skip, frames, fstride, B, H, W, features, lg_tx, ntiles, num_cu * wgs_per_cu, st,
-        [&](const float *zero_frame, float *table) { return run(zero_frame, (int64_t)H * W, tiles_per_frame, table, SkipArgs()); },
-        plan);
-    if (err != hipSuccess) return err;
-    return run(frames, fstride, ntiles, features, plan);
-}
-
-hipError_t launch_encoder_b16(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e, float *features,
-                              bool tokens, hipStream_t st, EncoderSkip *skip) {
-    return tokens ? launch_b16_t<true>(frames, fstride, B, H, W, e, features, st, skip)
-                  : launch_b16_t<false>(frames, fstride, B, H, W, e, features, st, skip);
-}
-
-template <bool X3, bool TOKENS>
-static hipError_t launch_bf16_t(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e,
-                                float *features, hipStream_t st, EncoderSkip *skip) {
-    const int PS = H / 32;
-    const int tiles_x = W / B3_TW, tiles_per_frame = tiles_x * (H / B3_TH), ntiles = tiles_per_frame * B;
-    int lg_tx = 0, lg_tpf = 0;
-    while ((1 << lg_tx) < tiles_x) ++lg_tx;
-    while ((1 << lg_tpf) < tiles_per_frame) ++lg_tpf;
-    if ((1 << lg_tx) != tiles_x || (1 << lg_tpf) != tiles_per_frame || (PS != 2 && PS != 4 && PS != 8)) return hipErrorInvalidValue;   // H = W in {64,128,256}
-    const int stagger = enc_knobs().stagger;
-    constexpr size_t lds_bytes = b3_lds_total<X3>();
-    const int num_cu = device_num_cu();
-    const int wgs_per_cu = device_cached_int((const void *)k_encoder_bf16<X3, 8, TOKENS>, [] {
-        constexpr size_t lb = b3_lds_total<X3>();
-        (void)hipFuncSetAttribute((const void *)k_encoder_bf16<X3, 8, TOKENS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-        (void)hipFuncSetAttribute((const void *)k_encoder_bf16<X3, 4, TOKENS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-        (void)hipFuncSetAttribute((const void *)k_encoder_bf16<X3, 2, TOKENS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k_encoder_bf16<X3, 8, TOKENS>, 256, lb) != hipSuccess || n < 1) n = 2;
-        return enc_knobs().wgs_per_cu ? enc_knobs().wgs_per_cu : n;
-    });
-    // the fixed persistent grid, capped by the tile count of the call (never by the device-side list length)
-    auto run = [&](const float *fr, int64_t fs, int nt, float *out, const SkipArgs &sa) -> hipError_t {
-        int nwg = num_cu * wgs_per_cu;
-        if (nwg > nt) nwg = nt;
-        dim3 grid(nwg), block(256);
-        switch (PS) {
-            case 2: hipLaunchKernelGGL((k_encoder_bf16<X3, 2, TOKENS>), grid, block, lds_bytes, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, sa); break;
-            case 4: hipLaunchKernelGGL((k_encoder_bf16<X3, 4, TOKENS>), grid, block, lds_bytes, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, sa); break;
-            default: hipLaunchKernelGGL((k_encoder_bf16<X3, 8, TOKENS>), grid, block, lds_bytes, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, sa); break;
-        }
-        return hipGetLastError();
-    };
-    SkipArgs plan;
-    hipError_t err = skip_prepare<X3 ? 0 : 1, TOKENS>(
-        skip, frames, fstride, B, H, W, features, lg_tx, ntiles, num_cu * wgs_per_cu, st,
-        [&](const float *zero_frame, float *table) { return run(zero_frame, (int64_t)H * W, tiles_per_frame, table, SkipArgs()); },
-        plan);
-    if (err != hipSuccess) return err;
-    return run(frames, fstride, ntiles, features, plan);
-}
-
-hipError_t launch_encoder_bf16(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e,
-                               float *features, bool x3, bool tokens, hipStream_t st, EncoderSkip *skip) {
-    // split-bf16 runs on the 16x16x32 shape (k_encoder_b16: -7 % time, interleaved A/B); SMK_ENC_SHAPE=32 selects the
-    // 32x32x16 kernel (k_encoder_bf16<true>) for comparison
-    const int shape = enc_knobs().shape;
-    if (x3 && shape == 16) return launch_encoder_b16(frames, fstride, B, H, W, e, features, tokens, st, skip);
-    if (x3) return tokens ? launch_bf16_t<true, true>(frames, fstride, B, H, W, e, features, st, skip)
-                          : launch_bf16_t<true, false>(frames, fstride, B, H, W, e, features, st, skip);
-    return tokens ? launch_bf16_t<false, true>(frames, fstride, B, H, W, e, features, st, skip)
-                  : launch_bf16_t<false, false>(frames, fstride, B, H, W, e, features, st, skip);
-}
-
 // ---------------------------------------------------------------- fused encoder, int8 fixed-point MFMA ("i8x3")
 // conv1 as in the split-bf16 kernel; its fp32 outputs stay in registers until the tile's maximum is known, then every
 // a1 value (>= 0 after the ReLU) is quantised to UNSIGNED 16-bit fixed point with the TILE's scale,
@@ -2255,14 +1378,7 @@ __global__ __launch_bounds__(256, 2) void k_encoder_i8(const float *__restrict__
     const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, hi = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    if (tid < 128) st1[tid] = tid < 64 ? e.s1[tid] : e.t1[tid - 64];
-    {
-        const uint4 *src = reinterpret_cast<const uint4 *>(e.w1p);
-        for (int c = tid; c < 2 * 64 * 8; c += 256) {
-            const int row = c >> 3, u = c & 7;
-            *reinterpret_cast<uint4 *>(w1s + row * B3_W1_PITCH + u * 16) = src[c];
-        }
-    }
+    conv1_stage<2>(e, w1s, st1);
     const int o = wave * 32 + r;
     const float t2 = e.t2[o];
     const float scale_o = e.sw2[o] * e.s2[o];               // weight scale x BN2 scale (tile scale multiplies in later)
@@ -2284,33 +1400,16 @@ __global__ __launch_bounds__(256, 2) void k_encoder_i8(const float *__restrict__
     }
     const int lane_off = (r >> 4) * 4 * I8_A1_ROW + (r & 15) * I8_A1_PITCH + 16 * hi;
 
-    auto x_fetch = [&](int t, int k) -> float {
-        if (k >= B3_XH * B3_XW) return 0.f;
-        const int bb = t >> lg_tiles_per_frame, rem = t & ((1 << lg_tiles_per_frame) - 1);
-        const int rr0 = (rem >> lg_tiles_x) * B3_TH, cc0 = (rem & ((1 << lg_tiles_x) - 1)) * B3_TW;
-        const int row = k / B3_XW, col = k - row * B3_XW;
-        const int ii = rr0 - 4 + row, jj = cc0 - 4 + col;
-        const bool ok = row < B3_XH - 1 && col < B3_XW - 1 && ii >= 0 && ii < H && jj >= 0 && jj < W;
-        return ok ? frames[(size_t)bb * fstride + (size_t)ii * W + jj] : 0.f;
-    };
-    int k = blockIdx.x;
+    const TileSrc src{frames, fstride, H, W, lg_tiles_x, lg_tiles_per_frame};
     __shared__ SkipLds skl;
-    const int nrun = tiles_to_run(skl, sa, ntiles);
-    const bool listed = nrun != ntiles;                       // a complete list is ascending, i.e. the identity: no lookups
-    int round = 0;
-    int t = k < nrun ? tile_at(skl, sa, listed, 0, k, nrun) : 0;
-    if (listed && skip_fill_first()) skip_fill<PS, TOKENS>(sa, lg_tiles_x, features);
-    if (k < nrun) {
-        xs[tid] = x_fetch(t, tid);
-        if (tid + 256 < B3_XH * B3_XW) xs[tid + 256] = x_fetch(t, tid + 256);
-    }
-    __syncthreads();
+    TileWalk wk;
+    wk.begin<PS, TOKENS>(skl, sa, src, ntiles, 0, features, xs, [](float v) { return v; });   // this kernel does not stagger
 
     // [stamp:begin]
-    for (; k < nrun; k += gridDim.x) {
+    for (; wk.k < wk.nrun; wk.k += gridDim.x) {
         // [stamp:T0]
-        const int b = t >> lg_tiles_per_frame, rem = t & ((1 << lg_tiles_per_frame) - 1);
-        const int r0 = (rem >> lg_tiles_x) * B3_TH, c0 = (rem & ((1 << lg_tiles_x) - 1)) * B3_TW;
+        int b, r0, c0;
+        src.decode(wk.t, b, r0, c0);
 
         __builtin_amdgcn_s_setprio(0);
         // ---- conv1 (split-bf16 MFMA): 3 (pixel block, channel block) units per wave, fp32 results kept in registers
@@ -2318,24 +1417,6 @@ __global__ __launch_bounds__(256, 2) void k_encoder_i8(const float *__restrict__
         int aoffs[2];
         bool valids[2];
         float vmax = 0.f;
-        auto x_frags = [&](int pb, bf16x8 (&xh)[4], bf16x8 (&xl)[4], int &aoff, bool &valid, bool &inimg) {
-            const int pix = pb * 32 + r;
-            valid = pix < B3_APIX;
-            const int pc = valid ? pix : B3_APIX - 1;
-            const int ar = pc / B3_AW, ac = pc - ar * B3_AW;
-            const int ii = r0 - 1 + ar, jj = c0 - 1 + ac;
-            inimg = valid && ii >= 0 && ii < H && jj >= 0 && jj < W;
-            aoff = ar * I8_A1_ROW + ac * I8_A1_PITCH;
-            const float *xp = xs + (ar + hi) * B3_XW + ac;
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    __bf16 vh, vl;
-                    split_bf16(xp[s * 2 * B3_XW + j], vh, vl);
-                    xh[s][j] = vh; xl[s][j] = vl;
-                }
-        };
         bool inimgs[2];
         auto bn1 = [&](const f32x16 &acc, int cb, bool inimg, float (&y)[16]) {
             float umax = 0.f;
@@ -2357,21 +1438,10 @@ __global__ __launch_bounds__(256, 2) void k_encoder_i8(const float *__restrict__
         {
             bf16x8 xh[4], xl[4];
             bool inimg;
-            x_frags(wave, xh, xl, aoffs[0], valids[0], inimg);
+            x_frags<I8_A1_ROW, I8_A1_PITCH>(xs, wave, r0, c0, H, W, xh, xl, aoffs[0], valids[0], inimg);
             inimgs[0] = inimg;
             f32x16 acc0, acc1;
-#pragma unroll
-            for (int g = 0; g < 16; ++g) { acc0[g] = 0.f; acc1[g] = 0.f; }
-            const unsigned char *wrow = w1s + r * B3_W1_PITCH + 8 * hi * 2;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const bf16x8 a0h = *reinterpret_cast<const bf16x8 *>(wrow + s * 32);
-                const bf16x8 a1hh = *reinterpret_cast<const bf16x8 *>(wrow + 32 * B3_W1_PITCH + s * 32);
-                const bf16x8 a0l = *reinterpret_cast<const bf16x8 *>(wrow + B3_W1_BYTES + s * 32);
-                const bf16x8 a1l_ = *reinterpret_cast<const bf16x8 *>(wrow + B3_W1_BYTES + 32 * B3_W1_PITCH + s * 32);
-                mma3<true>(acc0, a0h, a0l, xh[s], xl[s]);
-                mma3<true>(acc1, a1hh, a1l_, xh[s], xl[s]);
-            }
+            conv1_both<true>(w1s, xh, xl, acc0, acc1);
             bn1(acc0, 0, inimg, yv[0]);
             bn1(acc1, 1, inimg, yv[1]);
         }
@@ -2379,18 +1449,10 @@ __global__ __launch_bounds__(256, 2) void k_encoder_i8(const float *__restrict__
         {
             bf16x8 xh[4], xl[4];
             bool inimg;
-            x_frags(4 + (wave >> 1), xh, xl, aoffs[1], valids[1], inimg);
+            x_frags<I8_A1_ROW, I8_A1_PITCH>(xs, 4 + (wave >> 1), r0, c0, H, W, xh, xl, aoffs[1], valids[1], inimg);
             inimgs[1] = inimg;
             f32x16 acc;
-#pragma unroll
-            for (int g = 0; g < 16; ++g) acc[g] = 0.f;
-            const unsigned char *wrow = w1s + (cbs * 32 + r) * B3_W1_PITCH + 8 * hi * 2;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const bf16x8 ah = *reinterpret_cast<const bf16x8 *>(wrow + s * 32);
-                const bf16x8 al = *reinterpret_cast<const bf16x8 *>(wrow + B3_W1_BYTES + s * 32);
-                mma3<true>(acc, ah, al, xh[s], xl[s]);
-            }
+            conv1_one<true>(w1s, cbs, xh, xl, acc);
             bn1(acc, cbs, inimg, yv[2]);
         }
         // [stamp:T1]
@@ -2431,14 +1493,8 @@ __global__ __launch_bounds__(256, 2) void k_encoder_i8(const float *__restrict__
         __builtin_amdgcn_s_setprio(1);                        // K loop at raised priority (see k_encoder_bf16)
         // [stamp:T4]
 
-        const int kn = k + gridDim.x;
-        ++round;
-        const int tn = kn < nrun ? tile_at(skl, sa, listed, round, kn, nrun) : 0;
-        float xr0 = 0.f, xr1 = 0.f;
-        if (kn < nrun) {
-            xr0 = x_fetch(tn, tid);
-            xr1 = x_fetch(tn, tid + 256);
-        }
+        float xr0, xr1;                                       // next tile's x halo -> registers (lands under the K loop)
+        wk.next(skl, sa, src, xr0, xr1);
 
         // ---- conv2 on int8 MFMA: 18 k-steps (tap, channel half) x 4 M blocks x 3 limb products
         i32x16 hh[4], mid[4];
@@ -2510,84 +1566,56 @@ __global__ __launch_bounds__(256, 2) void k_encoder_i8(const float *__restrict__
             const float y = fmaf(v, sc, t2);
             return y > 0.f ? y : 0.f;
         };
-        auto out_index = [&](int pi, int pj) -> size_t {
-            return TOKENS ? ((size_t)b * 1024 + pi * 32 + pj) * 128 + o : ((size_t)b * 128 + o) * 1024 + pi * 32 + pj;
-        };
-        if (PS == 2) {
-#pragma unroll
-            for (int mp = 0; mp < 2; ++mp)
-#pragma unroll
-                for (int qr = 0; qr < 2; ++qr)
-#pragma unroll
-                    for (int qc = 0; qc < 2; ++qc)
-#pragma unroll
-                        for (int cg = 0; cg < 2; ++cg) {
-                            float sum = 0.f;
-#pragma unroll
-                            for (int mi = 2 * mp; mi < 2 * mp + 2; ++mi)
-#pragma unroll
-                                for (int i = 2 * cg; i < 2 * cg + 2; ++i) sum += val(mi, 4 * (2 * qr + qc) + i);
-                            features[out_index((r0 + 2 * mp + 4 * qr) / 2, (c0 + 8 * qc + 4 * hi + 2 * cg) / 2)] = sum * 0.25f;
-                        }
-        } else if (PS == 4) {
-#pragma unroll
-            for (int qr = 0; qr < 2; ++qr)
-#pragma unroll
-                for (int qc = 0; qc < 2; ++qc) {
-                    float sum = 0.f;
-#pragma unroll
-                    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) sum += val(mi, 4 * (2 * qr + qc) + i);
-                    features[out_index((r0 + 4 * qr) / 4, (c0 + 8 * qc + 4 * hi) / 4)] = sum * (1.0f / 16);
-                }
-        } else {
-            float cell[2];
-#pragma unroll
-            for (int qc = 0; qc < 2; ++qc) {
-                float sum = 0.f;
-#pragma unroll
-                for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                    for (int qr = 0; qr < 2; ++qr)
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) sum += val(mi, 4 * (2 * qr + qc) + i);
-                cell[qc] = sum;
-            }
-            const float other0 = __shfl_xor(cell[0], 32), other1 = __shfl_xor(cell[1], 32);
-            const float total = hi == 0 ? cell[0] + other0 : cell[1] + other1;
-            features[out_index(r0 / 8, c0 / 8 + hi)] = total * (1.0f / 64);
-        }
+        pool_store_32<PS, TOKENS>(features, b, o, r0, c0, val);
 
-        xs[tid] = xr0;
-        if (tid + 256 < B3_XH * B3_XW) xs[tid + 256] = xr1;
+        halo_to_lds(xs, xr0, xr1, [](float v) { return v; });
         // [stamp:T6]
         __syncthreads();
         // [stamp:T7]
         // [stamp:accumulate]
-        t = tn;
+        wk.t = wk.tn;
     }
     // [stamp:end]
-    if (listed && !skip_fill_first()) {
-        __builtin_amdgcn_s_setprio(0);
-        skip_fill<PS, TOKENS>(sa, lg_tiles_x, features);
-    }
+    wk.end<PS, TOKENS>(sa, src, features);
 }
 
-template <bool TOKENS>
-static hipError_t launch_i8_t(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e, float *features,
-                              hipStream_t st, EncoderSkip *skip) {
+// ---------------------------------------------------------------- launching the persistent kernels
+// A kernel family for the launcher: its instantiation for <PS, TOKENS>, its dynamic LDS, its skip_prepare FORM (the zero-response
+// table it fills) and whether it takes the stagger argument.
+struct FormB16 {
+    static constexpr int FORM = 0, LDS = S16_LDS;
+    static constexpr bool STAGGERS = true;
+    template <int PS, bool TOKENS> static constexpr auto kernel = &k_encoder_b16<PS, TOKENS>;
+};
+template <bool X3>
+struct FormBf16 {
+    static constexpr int FORM = X3 ? 0 : 1, LDS = b3_lds_total<X3>();
+    static constexpr bool STAGGERS = true;
+    template <int PS, bool TOKENS> static constexpr auto kernel = &k_encoder_bf16<X3, PS, TOKENS>;
+};
+struct FormI8 {
+    static constexpr int FORM = 2, LDS = I8_LDS_BYTES;
+    static constexpr bool STAGGERS = false;
+    template <int PS, bool TOKENS> static constexpr auto kernel = &k_encoder_i8<PS, TOKENS>;
+};
+
+template <class F, bool TOKENS>
+static hipError_t launch_persistent(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e, float *features,
+                                    hipStream_t st, EncoderSkip *skip) {
     const int PS = H / 32;
-    const int tiles_x = W / B3_TW, tiles_per_frame = tiles_x * (H / B3_TH), ntiles = tiles_per_frame * B;
+    const int tiles_x = W / B3_TW, tiles_per_frame = tiles_x * (H / B3_TH), ntiles = B * tiles_per_frame;
     int lg_tx = 0, lg_tpf = 0;
     while ((1 << lg_tx) < tiles_x) ++lg_tx;
     while ((1 << lg_tpf) < tiles_per_frame) ++lg_tpf;
-    if ((1 << lg_tx) != tiles_x || (1 << lg_tpf) != tiles_per_frame || (PS != 2 && PS != 4 && PS != 8)) return hipErrorInvalidValue;
-    constexpr size_t lds_bytes = I8_LDS_BYTES;
+    if ((1 << lg_tx) != tiles_x || (1 << lg_tpf) != tiles_per_frame || (PS != 2 && PS != 4 && PS != 8)) return hipErrorInvalidValue;   // H = W in {64,128,256}
+    const int stagger = enc_knobs().stagger;
     const int num_cu = device_num_cu();
-    const int wgs_per_cu = device_cached_int((const void *)k_encoder_i8<8, TOKENS>, [] {
+    const int wgs_per_cu = device_cached_int((const void *)F::template kernel<8, TOKENS>, [] {
+        (void)hipFuncSetAttribute((const void *)F::template kernel<8, TOKENS>, hipFuncAttributeMaxDynamicSharedMemorySize, F::LDS);
+        (void)hipFuncSetAttribute((const void *)F::template kernel<4, TOKENS>, hipFuncAttributeMaxDynamicSharedMemorySize, F::LDS);
+        (void)hipFuncSetAttribute((const void *)F::template kernel<2, TOKENS>, hipFuncAttributeMaxDynamicSharedMemorySize, F::LDS);
         int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k_encoder_i8<8, TOKENS>, 256, I8_LDS_BYTES) != hipSuccess || n < 1) n = 2;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)F::template kernel<8, TOKENS>, 256, F::LDS) != hipSuccess || n < 1) n = 2;
         return enc_knobs().wgs_per_cu ? enc_knobs().wgs_per_cu : n;
     });
     // the fixed persistent grid, capped by the tile count of the call (never by the device-side list length)
@@ -2595,15 +1623,19 @@ static hipError_t launch_i8_t(const float *frames, int64_t fstride, int B, int H
         int nwg = num_cu * wgs_per_cu;
         if (nwg > nt) nwg = nt;
         dim3 grid(nwg), block(256);
+        auto go = [&](auto kern) {
+            if constexpr (F::STAGGERS) hipLaunchKernelGGL(kern, grid, block, F::LDS, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, stagger, sa);
+            else hipLaunchKernelGGL(kern, grid, block, F::LDS, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, sa);
+        };
         switch (PS) {
-            case 2: hipLaunchKernelGGL((k_encoder_i8<2, TOKENS>), grid, block, lds_bytes, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, sa); break;
-            case 4: hipLaunchKernelGGL((k_encoder_i8<4, TOKENS>), grid, block, lds_bytes, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, sa); break;
-            default: hipLaunchKernelGGL((k_encoder_i8<8, TOKENS>), grid, block, lds_bytes, st, fr, fs, H, W, e, out, lg_tx, lg_tpf, nt, sa); break;
+            case 2: go(F::template kernel<2, TOKENS>); break;
+            case 4: go(F::template kernel<4, TOKENS>); break;
+            default: go(F::template kernel<8, TOKENS>); break;
         }
         return hipGetLastError();
     };
     SkipArgs plan;
-    hipError_t err = skip_prepare<2, TOKENS>(
+    hipError_t err = skip_prepare<F::FORM, TOKENS>(
         skip, frames, fstride, B, H, W, features, lg_tx, ntiles, num_cu * wgs_per_cu, st,
         [&](const float *zero_frame, float *table) { return run(zero_frame, (int64_t)H * W, tiles_per_frame, table, SkipArgs()); },
         plan);
@@ -2611,10 +1643,28 @@ static hipError_t launch_i8_t(const float *frames, int64_t fstride, int B, int H
     return run(frames, fstride, ntiles, features, plan);
 }
 
+hipError_t launch_encoder_b16(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e, float *features,
+                              bool tokens, hipStream_t st, EncoderSkip *skip) {
+    return tokens ? launch_persistent<FormB16, true>(frames, fstride, B, H, W, e, features, st, skip)
+                  : launch_persistent<FormB16, false>(frames, fstride, B, H, W, e, features, st, skip);
+}
+
+hipError_t launch_encoder_bf16(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e,
+                               float *features, bool x3, bool tokens, hipStream_t st, EncoderSkip *skip) {
+    // split-bf16 runs on the 16x16x32 shape (k_encoder_b16: -7 % time, interleaved A/B); SMK_ENC_SHAPE=32 selects the
+    // 32x32x16 kernel (k_encoder_bf16<true>) for comparison
+    const int shape = enc_knobs().shape;
+    if (x3 && shape == 16) return launch_encoder_b16(frames, fstride, B, H, W, e, features, tokens, st, skip);
+    if (x3) return tokens ? launch_persistent<FormBf16<true>, true>(frames, fstride, B, H, W, e, features, st, skip)
+                          : launch_persistent<FormBf16<true>, false>(frames, fstride, B, H, W, e, features, st, skip);
+    return tokens ? launch_persistent<FormBf16<false>, true>(frames, fstride, B, H, W, e, features, st, skip)
+                  : launch_persistent<FormBf16<false>, false>(frames, fstride, B, H, W, e, features, st, skip);
+}
+
 hipError_t launch_encoder_i8(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e, float *features,
                              bool tokens, hipStream_t st, EncoderSkip *skip) {
-    return tokens ? launch_i8_t<true>(frames, fstride, B, H, W, e, features, st, skip)
-                  : launch_i8_t<false>(frames, fstride, B, H, W, e, features, st, skip);
+    return tokens ? launch_persistent<FormI8, true>(frames, fstride, B, H, W, e, features, st, skip)
+                  : launch_persistent<FormI8, false>(frames, fstride, B, H, W, e, features, st, skip);
 }
 
 }  // namespace smk

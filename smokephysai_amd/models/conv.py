@@ -1,5 +1,5 @@
 """Host side of libsmokehip's training convolution (smk_conv2_train_forward): SmokePhysNet.input_encoder's second convolution
-(smokephys_net.py:28, Conv2d(64, 128, 3, padding=1)) under autograd.  The data gradient (csrc/encoder.hip: k_conv2_dgrad_b16) and the weight / bias gradients (k_conv2_wgrad_b16) run on
+(smokephys_net.py:28, Conv2d(64, 128, 3, padding=1)) under autograd.  The data gradient (csrc/encoder_train.hip: k_conv2_dgrad_b16) and the weight / bias gradients (k_conv2_wgrad_b16) run on
 split-bf16 MFMA kernels, and so does the forward (k_conv2_fwd_b16, three bf16 terms per operand: see hip_conv2_train)."""
 import torch
 from torch import nn
