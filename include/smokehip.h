@@ -163,6 +163,14 @@ int smk_sim3d_add_sources(smk_sim3d *sim, const smk_source3d *sources, int32_t n
  * written to frames + t*frame_stride_t + b*frame_stride_b as [D][H][W] contiguous fp32 (frames may be NULL). */
 int smk_sim3d_step(smk_sim3d *sim, int32_t n_steps, float *frames, int64_t frame_stride_b, int64_t frame_stride_t, void *stream);
 
+/* smk_sim3d_step with SmokeSimulator.simulate_step's frame emit (smoke_simulator.py:31-45 -> SPEC_3D.md section 9): add_fractal != 0 writes
+ * frame + (fractal_intensity * F) * frame to `frames`, F the [W][H] shape-only constant that apply_fractal_perturbation
+ * (fractal_generator.py:53-62) builds from field.shape[-2:] and broadcasts over the planes, with the roundings of smk_apply_fractal; the
+ * solver state keeps the unperturbed density (smoke_simulator.py:36-39).  Needs H == W (SMK_ERR_UNSUPPORTED otherwise, as the reference
+ * raises).  add_fractal == 0 or frames == NULL: exactly smk_sim3d_step. */
+int smk_sim3d_step_emit(smk_sim3d *sim, int32_t n_steps, float *frames, int64_t frame_stride_b, int64_t frame_stride_t,
+                        int32_t add_fractal, double fractal_intensity, void *stream);
+
 /* Single stages of the 3-D step on the handle's state (per-stage parity tests); state is back in the caller's tensors afterwards. */
 typedef enum smk_stage3d {
     SMK_STAGE3D_BUOY_DIFFUSE = 0, /* SPEC_3D.md 6.1-6.2 */
@@ -231,6 +239,18 @@ int smk_frame_diff_norms(const float *frames, int64_t frame_stride, int32_t n, i
  * data_loader.py:71-88); n_groups == 0: means is not touched and may be NULL.  One launch. */
 int smk_chaos_features(const float *norms, const int32_t *box_counts, const int32_t *hist, int32_t S, const int32_t *pos,
                        const int32_t *hist_len, int32_t F, int32_t n_groups, double *features, double *means, void *stream);
+
+/* The reductions of smk_chaos_stats and smk_frame_diff_norms (smoke_simulator.py:47-140) for n volumes [D][H][W] (dense, `vol_stride`
+ * floats apart, 64-bit), SPEC_3D.md section 9: means [n] (fp64 sum over all voxels, rounded once), box_counts [n][5] (cubes of edge
+ * 2,4,8,16,32 of vol > mean on the (D/s) x (H/s) x (W/s) grid, upper remainders ignored as `h // scale` does at :100-101; a scale with no
+ * whole box counts 0), hist [n][256] (torch.histogram(bins=256, range=(0,1)) counts, :134-135) and, unless NULL, norms [n-1] =
+ * ||vol[i+1] - vol[i]||_2 (:73-79; fp64 accumulation).  D == 1 is the 2-axis instance (s x s boxes on [H][W]: smk_chaos_stats' rule
+ * without its size limit); a 3-D grid has D >= 2.  Any H, W >= 2; D*H*W <= 2^31 - 2^16.  Many workgroups per volume, two launches; all
+ * outputs are bit-reproducible (integer adds, and every fp64 sum in one fixed order).  workspace: device memory of at least
+ * smk_volume_stats_workspace(n, D, H, W) bytes, 8-byte aligned, passed with its size; nothing is allocated. */
+int64_t smk_volume_stats_workspace(int32_t n, int32_t D, int32_t H, int32_t W);
+int smk_volume_stats(const float *vols, int64_t vol_stride, int32_t n, int32_t D, int32_t H, int32_t W, float *means,
+                     int32_t *box_counts, int32_t *hist, float *norms, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* RobustnessEvaluator.compute_ssim's SSIM map and F.mse_loss's squared error (robustness_metrics.py:76-103) for n fp32 planes [H][W]
  * (dense rows; plane strides pred_stride / target_stride floats), summed per plane in fp64 in a fixed order (bit-reproducible):

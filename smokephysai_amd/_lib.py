@@ -62,6 +62,7 @@ _SIGNATURES = {
     "smk_sim3d_reset": [C.c_void_p, C.c_char_p, C.c_void_p],
     "smk_sim3d_add_sources": [C.c_void_p, C.POINTER(SmkSource3d), C.c_int32, C.c_void_p],
     "smk_sim3d_step": [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p],
+    "smk_sim3d_step_emit": [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_void_p],
     "smk_sim3d_run_stage": [C.c_void_p, C.c_int32, C.c_void_p],
     "smk_conv3d_im2col": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p],
     "smk_conv3d_cl_forward": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p],
@@ -88,6 +89,8 @@ _SIGNATURES = {
     "smk_chaos_stats": [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                         C.c_void_p],
     "smk_frame_diff_norms": [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p],
+    "smk_volume_stats": [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                         C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
     "smk_chaos_features": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                            C.c_void_p, C.c_void_p],
     "smk_image_quality": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
@@ -152,6 +155,7 @@ _SIGNATURES = {
                            C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p],
 }
 EXPORTS = ["smk_abi_version", "smk_last_error", "smk_linear_wgrad_workspace", "smk_bn_train_workspace", "smk_layernorm_bwd_workspace", "smk_conv2_train_workspace", "smk_conv2_train_wgrad_workspace", "smk_conv1_train_wgrad_workspace", "smk_attention_workspace_bytes", "smk_linear_ln_max_rows", "smk_image_quality_workspace", "smk_convt4s2_train_wgrad_workspace",
+           "smk_volume_stats_workspace",
            "smk_conv3_sigmoid_train_workspace"] + list(_SIGNATURES)
 
 _lib = None
@@ -202,6 +206,8 @@ def load():
         L.smk_linear_ln_max_rows.restype = C.c_int64
         L.smk_image_quality_workspace.argtypes = [C.c_int32] * 3
         L.smk_image_quality_workspace.restype = C.c_int64
+        L.smk_volume_stats_workspace.argtypes = [C.c_int32] * 4
+        L.smk_volume_stats_workspace.restype = C.c_int64
         L.smk_convt4s2_train_wgrad_workspace.argtypes = [C.c_int32] * 5
         L.smk_convt4s2_train_wgrad_workspace.restype = C.c_int64
         L.smk_conv3_sigmoid_train_workspace.argtypes = [C.c_int32] * 3

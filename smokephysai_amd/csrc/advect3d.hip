@@ -80,9 +80,13 @@ __device__ __attribute__((noinline)) float far_value3(const float *f, const floa
 // "every back-trace of these units lands in its 2 x 2 x 2 LDS neighbourhood" (always, in the reference's regime); the fall-back runs the
 // general form per lane.  EDGE = false is the same arithmetic with the tests that cannot fail inside the grid removed (existence of the
 // cell, vel3_at's extent rules, the x / y clamps: an unclamped back-trace that would have needed its clamp fails the neighbourhood test).
-template <int R, int NW, int MINW, int BU, bool GRAD>
+// FRAC: the emitted frame (never the state) gets the fractal perturbation, frame = v + (fint * F[y][x]) * v with the three roundings of
+// k_apply_fractal (fractal_generator.py:62; F is the [W][H] shape-only constant of a square (H, W), the same for every plane:
+// SPEC_3D.md section 9).  FRAC = false never touches `fractal` / `fint`: it is the kernel as it was before the flag existed.
+template <int R, int NW, int MINW, int BU, bool GRAD, bool FRAC>
 __global__ __launch_bounds__(NW * 64, MINW) void k3_advect_march(Geom3 g, State3 in, const float *__restrict__ pf, State3 out,
-                                                          float *__restrict__ frames, int64_t fsb) {
+                                                          float *__restrict__ frames, int64_t fsb,
+                                                          const float *__restrict__ fractal, float fint) {
     constexpr int TY = R * NW, TX = 64, NT = NW * 64;
     constexpr int WR = TY + 3, WC = TX + 3, WP = 68, WPL = WR * WP;       // input windows: rows y0-1 .. y0+TY+1, columns x0-1 .. x0+TX+1
     constexpr int NST = (WR * WC + NT - 1) / NT;
@@ -419,7 +423,15 @@ __global__ __launch_bounds__(NW * 64, MINW) void k3_advect_march(Geom3 g, State3
                     const float v = val[j] * 0.995f;                        // navier_stokes.py:171
                     if (ex[j]) {
                         const int y = yb + r;
-                        if (fr) stb(fr + (size_t)(z * H + y) * W, v);
+                        if constexpr (FRAC) {
+                            if (fr) {
+                                float t = fint * fractal[(unsigned)(y * W + x)];
+                                t = t * v;
+                                stb(fr + (size_t)(z * H + y) * W, v + t);
+                            }
+                        } else {
+                            if (fr) stb(fr + (size_t)(z * H + y) * W, v);
+                        }
                         stb(dn + (size_t)(z * H + y) * pc, v);
                     }
                 }
@@ -613,11 +625,17 @@ hipError_t launch3_diffuse_div_march(const Geom3 &g, State3 in, State3 out, floa
     return hipGetLastError();
 }
 
-hipError_t launch3_advect_march(const Geom3 &g, State3 in, const float *p, State3 out, float *frames, int64_t fsb, hipStream_t st) {
+hipError_t launch3_advect_march(const Geom3 &g, State3 in, const float *p, State3 out, float *frames, int64_t fsb, const float *fractal,
+                                float fint, hipStream_t st) {
     constexpr int R = 4, NW = 4;                                  // 4 rows per wave (measured against 2 and 3)
     const long long nb = (long long)cdiv(g.W, 64) * cdiv(g.H, R * NW) * g.B;
     if (!p || nb > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((k3_advect_march<R, NW, 2, 3, true>), dim3((unsigned)nb), dim3(NW * 64), 0, st, g, in, p, out, frames, fsb);
+    if (fractal && frames)
+        hipLaunchKernelGGL((k3_advect_march<R, NW, 2, 3, true, true>), dim3((unsigned)nb), dim3(NW * 64), 0, st, g, in, p, out, frames, fsb,
+                           fractal, fint);
+    else
+        hipLaunchKernelGGL((k3_advect_march<R, NW, 2, 3, true, false>), dim3((unsigned)nb), dim3(NW * 64), 0, st, g, in, p, out, frames, fsb,
+                           (const float *)nullptr, 0.f);
     return hipGetLastError();
 }
 

@@ -440,6 +440,27 @@ int smk_sim_describe(smk_sim *sim, char *buf, int64_t capacity) {
     return SMK_OK;
 }
 
+// fractal constant cache for the stateless smk_apply_fractal and the 3-D stepper's emit: one per (device, N)
+static std::mutex g_fr_mu;
+static std::map<std::pair<int, int>, float *> g_fr_cache;
+
+static int cached_fractal_field(int N, hipStream_t st, float **out) {
+    int dev = 0;
+    SMK_HIP_TRY(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(g_fr_mu);
+    auto it = g_fr_cache.find({dev, N});
+    if (it == g_fr_cache.end()) {
+        float *blob = nullptr;
+        size_t n = (size_t)N * N;
+        SMK_HIP_TRY(hipMalloc((void **)&blob, 3 * n * sizeof(float)));
+        int rc = check_launch(launch_fractal_constants(N, blob, blob + n, blob + 2 * n, st), "fractal");
+        if (rc) return rc;
+        it = g_fr_cache.emplace(std::make_pair(dev, N), blob + 2 * n).first;
+    }
+    *out = it->second;
+    return SMK_OK;
+}
+
 // ------------------------------------------------------------------ 3-D stepper (SPEC_3D.md)
 int smk_sim3d_create(const smk_sim3d_desc *d, smk_sim3d **out) {
     SMK_REQUIRE(d && out, "null desc/out");
@@ -579,11 +600,8 @@ int run_stage3d(smk_sim3d *sim, int stage, hipStream_t st) {
 }
 }  // namespace
 
-int smk_sim3d_step(smk_sim3d *sim, int32_t n_steps, float *frames, int64_t fsb, int64_t fst, void *stream) {
-    SMK_REQUIRE(sim && n_steps >= 0, "null sim / negative n_steps");
-    hipStream_t st = (hipStream_t)stream;
-    DeviceGuard guard(sim->device);
-    if (guard.rc) return guard.rc;
+static int sim3d_step(smk_sim3d *sim, int32_t n_steps, float *frames, int64_t fsb, int64_t fst, const float *fractal, float fint,
+                      hipStream_t st) {
     // buoyancy + diffusion + divergence (one z-marching launch), the Jacobi sweeps, then the four advections as one z-marching launch that
     // applies the projection's gradient subtraction while it stages its inputs
     const Geom3 &g = sim->g;
@@ -593,10 +611,35 @@ int smk_sim3d_step(smk_sim3d *sim, int32_t n_steps, float *frames, int64_t fsb, 
         if (rc) return rc;
         rc = check_launch(launch3_jacobi(g, sim->s.p, sim->t.p, sim->p3, sim->div, sim->jacobi_iters, st), "jacobi3d");
         if (rc) return rc;
-        rc = check_launch(launch3_advect_march(g, sim->t, sim->s.p, sim->s, ft, fsb, st), "advect_march3d");
+        rc = check_launch(launch3_advect_march(g, sim->t, sim->s.p, sim->s, ft, fsb, fractal, fint, st), "advect_march3d");
         if (rc) return rc;
     }
     return SMK_OK;
+}
+
+int smk_sim3d_step(smk_sim3d *sim, int32_t n_steps, float *frames, int64_t fsb, int64_t fst, void *stream) {
+    SMK_REQUIRE(sim && n_steps >= 0, "null sim / negative n_steps");
+    DeviceGuard guard(sim->device);
+    if (guard.rc) return guard.rc;
+    return sim3d_step(sim, n_steps, frames, fsb, fst, nullptr, 0.f, (hipStream_t)stream);
+}
+
+int smk_sim3d_step_emit(smk_sim3d *sim, int32_t n_steps, float *frames, int64_t fsb, int64_t fst, int32_t add_fractal,
+                        double fractal_intensity, void *stream) {
+    SMK_REQUIRE(sim && n_steps >= 0, "null sim / negative n_steps");
+    const bool frac = add_fractal && frames;
+    if (frac && sim->g.H != sim->g.W) {
+        // fractal_generator.py:44,49 builds its field from field.shape[-2:]: the [w,h] mask indexes an [h,w] buffer
+        set_error("fractal perturbation needs a grid that is square in (H, W) (reference raises an IndexError for H != W)");
+        return SMK_ERR_UNSUPPORTED;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    DeviceGuard guard(sim->device);
+    if (guard.rc) return guard.rc;
+    float *F = nullptr;
+    if (frac)
+        if (int rc = cached_fractal_field(sim->g.H, st, &F)) return rc;
+    return sim3d_step(sim, n_steps, frames, fsb, fst, F, (float)fractal_intensity, st);
 }
 
 int smk_sim3d_run_stage(smk_sim3d *sim, int32_t stage, void *stream) {
@@ -666,30 +709,10 @@ int smk_diffuse(const float *in, float *out, int32_t B, int32_t R, int32_t C, in
     return check_launch(launch_diffuse(in, out, B, R, C, pitch, (float)(dt * viscosity), (hipStream_t)stream), "diffuse");
 }
 
-// fractal constant cache for the stateless smk_apply_fractal: one per (device, N)
-static std::mutex g_fr_mu;
-static std::map<std::pair<int, int>, float *> g_fr_cache;
-
 int smk_apply_fractal(const float *in, float *out, int32_t n_fields, int32_t N, double intensity, void *stream) {
     SMK_REQUIRE(in && out && n_fields >= 1 && N >= 2, "null in/out or bad sizes");
-    int dev = 0;
-    SMK_HIP_TRY(hipGetDevice(&dev));
     float *F = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(g_fr_mu);
-        auto it = g_fr_cache.find({dev, N});
-        if (it == g_fr_cache.end()) {
-            float *blob = nullptr;
-            size_t n = (size_t)N * N;
-            SMK_HIP_TRY(hipMalloc((void **)&blob, 3 * n * sizeof(float)));
-            int rc = check_launch(launch_fractal_constants(N, blob, blob + n, blob + 2 * n, (hipStream_t)stream), "fractal");
-            if (rc) return rc;
-            F = blob + 2 * n;
-            g_fr_cache[{dev, N}] = F;
-        } else {
-            F = it->second;
-        }
-    }
+    if (int rc = cached_fractal_field(N, (hipStream_t)stream, &F)) return rc;
     return check_launch(launch_apply_fractal(in, out, F, n_fields, N, (float)intensity, (hipStream_t)stream), "apply_fractal");
 }
 
@@ -762,6 +785,25 @@ int smk_chaos_features(const float *norms, const int32_t *box_counts, const int3
     SMK_REQUIRE(n_groups >= 0 && (n_groups == 0 || (means && F % n_groups == 0)), "n_groups > 0 needs means and must divide F");
     return check_launch(launch_chaos_features(norms, box_counts, hist, S, pos, hist_len, F, n_groups, features, means,
                                               (hipStream_t)stream), "chaos_features");
+}
+
+static const int64_t VOLUME_STATS_MAX_CELLS = (1LL << 31) - (1LL << 16);
+
+int64_t smk_volume_stats_workspace(int32_t n, int32_t D, int32_t H, int32_t W) {
+    if (n < 1 || D < 1 || H < 2 || W < 2 || (int64_t)D * H * W > VOLUME_STATS_MAX_CELLS) return 0;
+    return volume_stats_workspace(n, (int64_t)D * H * W);
+}
+
+int smk_volume_stats(const float *vols, int64_t vol_stride, int32_t n, int32_t D, int32_t H, int32_t W, float *means,
+                     int32_t *box_counts, int32_t *hist, float *norms, void *workspace, int64_t workspace_bytes, void *stream) {
+    SMK_REQUIRE(vols && means && box_counts && hist && workspace, "null pointer");
+    SMK_REQUIRE(n >= 1 && D >= 1 && H >= 2 && W >= 2, "n, D >= 1; H, W >= 2");
+    SMK_REQUIRE((int64_t)D * H * W <= VOLUME_STATS_MAX_CELLS, "one volume must stay below 2^31 - 2^16 cells (32-bit offsets inside a volume)");
+    SMK_REQUIRE(vol_stride >= (int64_t)D * H * W, "vol_stride >= D*H*W");
+    SMK_REQUIRE(((uintptr_t)vols & 3) == 0 && ((uintptr_t)workspace & 7) == 0, "4-byte aligned vols, 8-byte aligned workspace");
+    SMK_REQUIRE(workspace_bytes >= smk_volume_stats_workspace(n, D, H, W), "workspace smaller than smk_volume_stats_workspace(n, D, H, W)");
+    return check_launch(launch_volume_stats(vols, vol_stride, n, D, H, W, means, box_counts, hist, norms, workspace, (hipStream_t)stream),
+                        "volume_stats");
 }
 
 // ------------------------------------------------------------------ image quality (SSIM map + squared error)

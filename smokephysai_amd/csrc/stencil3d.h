@@ -33,7 +33,9 @@ hipError_t launch3_advect(const Geom3 &g, int which, const float *field, float *
 // the four advections of one step as one z-marching launch (inputs staged once into LDS rings): in = (u2, v2, w2, -, d2), out = (u, v, w, -,
 // density).  `in` holds the velocities BEFORE the projection's gradient subtraction and the launch applies it with the pressure p (not null)
 // on the fly, so launch3_grad_subtract is not run; bit-identical to the grad_subtract launch followed by the four advection launches
-hipError_t launch3_advect_march(const Geom3 &g, State3 in, const float *p, State3 out, float *frames, int64_t frame_stride_b, hipStream_t st);
+// fractal != NULL (with frames): the emitted frames carry frame + (fint * F) * frame, F the [H][W] constant of a square (H, W); the state does not
+hipError_t launch3_advect_march(const Geom3 &g, State3 in, const float *p, State3 out, float *frames, int64_t frame_stride_b,
+                                const float *fractal, float fint, hipStream_t st);
 
 
 // ---- device helpers shared by the 3-D kernel files

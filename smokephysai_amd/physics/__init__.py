@@ -1,6 +1,7 @@
 from .navier_stokes import NavierStokesSimulator
 from .navier_stokes3d import NavierStokesSimulator3D
 from .smoke_simulator import SmokeSimulator
+from .smoke_simulator3d import SmokeSimulator3D
 from .fractal_generator import FractalGenerator
 
-__all__ = ["NavierStokesSimulator", "NavierStokesSimulator3D", "SmokeSimulator", "FractalGenerator"]
+__all__ = ["NavierStokesSimulator", "NavierStokesSimulator3D", "SmokeSimulator", "SmokeSimulator3D", "FractalGenerator"]

@@ -110,8 +110,9 @@ class NavierStokesSimulator3D(nn.Module):
         self.step_into(out)
         return out if self.batch_size is not None else out[0]
 
-    def step_into(self, frames: Optional[torch.Tensor], n_steps: int = 1):
-        """n_steps time steps; frame t of grid b goes to frames[b, t] (frames: [B, n_steps, D, H, W] or [B, D, H, W]; None = no frames)."""
+    def step_into(self, frames: Optional[torch.Tensor], n_steps: int = 1, add_fractal: bool = False, fractal_intensity: float = 0.05):
+        """n_steps time steps; frame t of grid b goes to frames[b, t] (frames: [B, n_steps, D, H, W] or [B, D, H, W]; None = no frames).
+        add_fractal: the emitted frames (never the state) get the per-plane fractal perturbation of SPEC_3D.md section 9; needs H == W."""
         D, H, W = self.grid_size
         ptr, sb, st_ = None, 0, 0
         if frames is not None:
@@ -123,7 +124,10 @@ class NavierStokesSimulator3D(nn.Module):
             if tuple(fr.shape) != (self._B, n_steps, D, H, W) or not fr[0, 0].is_contiguous():
                 raise ValueError(f"frames must be [B={self._B}, n_steps={n_steps}, {D}, {H}, {W}] with dense grids")
             ptr, sb, st_ = fr.data_ptr(), fr.stride(0), fr.stride(1)
-        _lib.check(self._L.smk_sim3d_step(self._handle, n_steps, ptr, sb, st_, self._st()))
+        if add_fractal:
+            _lib.check(self._L.smk_sim3d_step_emit(self._handle, n_steps, ptr, sb, st_, 1, float(fractal_intensity), self._st()))
+        else:
+            _lib.check(self._L.smk_sim3d_step(self._handle, n_steps, ptr, sb, st_, self._st()))
 
     def forward(self):
         return self.step()

@@ -127,11 +127,14 @@ class SmokeSimulator(nn.Module):
 # ---- chaos statistics: HIP reductions (csrc/chaos.hip) + the reference's tiny host-side formulas ---------------
 def chaos_stats(frames: torch.Tensor):
     """means [n] fp32, box counts [n,5] int32 (scales 2..32 of frame > mean), histogram [n,256] int32 of n frames
-    [n,H,W] on the device (smoke_simulator.py:89-140's reductions, one launch)."""
+    [n,H,W] on the device (smoke_simulator.py:89-140's reductions, one launch).  Frames above 512 x 512 and volumes [n,D,H,W]
+    (cubic boxes, SPEC_3D.md section 9) go to the multi-workgroup kernel (volume_stats)."""
     dev = _lib.require_cuda(frames.device, "chaos_stats")
     f = frames.to(torch.float32)
     if f.dim() == 2:
         f = f[None]
+    if f.dim() == 4 or (f.dim() == 3 and (f.shape[1] // 2) * (f.shape[2] // 2) > 65536):
+        return volume_stats(f)[:3]
     if f.stride(2) != 1 or f.stride(1) != f.shape[2]:
         f = f.contiguous()
     n, h, w = f.shape
@@ -144,13 +147,51 @@ def chaos_stats(frames: torch.Tensor):
 
 
 def frame_diff_norms(frames: torch.Tensor) -> torch.Tensor:
-    """||frames[i+1] - frames[i]||_2 for consecutive frames [n,H,W] -> [n-1] fp32 (smoke_simulator.py:73-79)."""
+    """||frames[i+1] - frames[i]||_2 for consecutive frames [n,H,W] -> [n-1] fp32 (smoke_simulator.py:73-79); volumes [n,D,H,W] too."""
     dev = _lib.require_cuda(frames.device, "frame_diff_norms")
+    if frames.dim() == 4:
+        return volume_stats(frames, norms=True)[3]
     f = frames.to(torch.float32).contiguous()
     n, h, w = f.shape
     out = torch.empty(n - 1, device=dev)
     _lib.check(_lib.load().smk_frame_diff_norms(f.data_ptr(), f.stride(0), n, h, w, out.data_ptr(), _lib.stream_ptr(dev)))
     return out
+
+
+def volume_stats_workspace(n: int, shape, device) -> torch.Tensor:
+    """The scratch buffer smk_volume_stats wants for n volumes of `shape` = (D, H, W) or (H, W); reusable across calls on one stream."""
+    d, h, w = (1, *shape) if len(shape) == 2 else shape
+    nbytes = _lib.load().smk_volume_stats_workspace(n, d, h, w)
+    if nbytes <= 0:
+        raise ValueError(f"volume_stats: n={n}, shape={tuple(shape)} is not supported (n >= 1, H, W >= 2, below 2^31 - 2^16 cells)")
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def volume_stats(vols: torch.Tensor, norms: bool = False, workspace: Optional[torch.Tensor] = None):
+    """chaos_stats and (norms=True) frame_diff_norms of n volumes [n,D,H,W] in one pass of the multi-workgroup kernel
+    (csrc/chaos_nd.hip; SPEC_3D.md section 9): means [n] fp32, box counts [n,5] int32 (cubes of edge 2..32), histogram [n,256] int32,
+    and norms [n-1] fp32 or None.  [n,H,W] is the 2-axis instance (squares; no size limit).  Each volume must be dense; the stride
+    between volumes is free.  Bit-reproducible."""
+    dev = _lib.require_cuda(vols.device, "volume_stats")
+    f = vols.to(torch.float32)
+    if f.dim() not in (3, 4):
+        raise ValueError("volume_stats: [n,D,H,W] volumes or [n,H,W] frames")
+    if not f[0].is_contiguous() or (f.shape[0] > 1 and f.stride(0) < f[0].numel()):
+        f = f.contiguous()
+    n, shape = f.shape[0], tuple(f.shape[1:])
+    d, h, w = (1, *shape) if len(shape) == 2 else shape
+    if len(shape) == 3 and d < 2:
+        raise ValueError("volume_stats: a 3-D grid has D >= 2 (pass [n,H,W] for frames)")
+    if workspace is None:
+        workspace = volume_stats_workspace(n, shape, dev)
+    means = torch.empty(n, device=dev)
+    box = torch.empty(n, 5, dtype=torch.int32, device=dev)
+    hist = torch.empty(n, 256, dtype=torch.int32, device=dev)
+    out = torch.empty(n - 1, device=dev) if norms and n > 1 else None
+    _lib.check(_lib.load().smk_volume_stats(f.data_ptr(), f.stride(0) if n > 1 else f[0].numel(), n, d, h, w, means.data_ptr(),
+                                            box.data_ptr(), hist.data_ptr(), out.data_ptr() if out is not None else None,
+                                            workspace.data_ptr(), workspace.numel() * workspace.element_size(), _lib.stream_ptr(dev)))
+    return means, box, hist, out
 
 
 def chaos_features_device(norms: Optional[torch.Tensor], box: torch.Tensor, hist: torch.Tensor, pos: torch.Tensor,

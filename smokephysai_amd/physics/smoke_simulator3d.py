@@ -1,0 +1,130 @@
+"""Smoke simulation system for 3-D grids on MI355X (BASELINE configs[4]) -- SmokeSimulator's surface (src/physics/smoke_simulator.py:8-139)
+for grids `(D, H, W)`; semantics: SPEC_3D.md section 9, the rule-by-rule generalisation of the 2-D code.
+
+simulate_step = one step of the batched 3-D solver; the fractal perturbation goes onto the emitted volume only, every plane with the [W][H]
+shape-only field (the solver keeps the unperturbed density, smoke_simulator.py:36-39), inside the advection kernel.  The chaos features are
+DEFINED on the list of emitted volumes exactly as in 2-D (smoke_simulator.py:47-140), but that list is never kept -- 100 volumes of
+configs[4] are 53 GB.  What the formulas read of it is kept on the device instead: the newest volume's box counts and histogram, the last 19
+distances between consecutive volumes per grid, and the history length (capped at 100).  Every simulate_step makes one smk_volume_stats call
+over {previous volume, current volume} of every grid (csrc/chaos_nd.hip).
+"""
+from typing import Optional
+
+import torch
+import torch.nn as nn
+
+from .navier_stokes3d import NavierStokesSimulator3D
+from .smoke_simulator import (chaos_features_device, entropy_from_hist, fractal_dimension_from_counts, lyapunov_from_norms, volume_stats,
+                              volume_stats_workspace)
+
+WINDOW = 20          # smoke_simulator.py:69-79: the Lyapunov estimate reads the last 20 states = 19 distances
+
+
+class SmokeSimulator3D(nn.Module):
+    def __init__(self, grid_size: tuple = (64, 128, 128), dt: float = 0.01, viscosity: float = 0.001,
+                 device: str = "cuda", batch_size: Optional[int] = None, jacobi_iters: int = 20):
+        super().__init__()
+        self.ns_solver = NavierStokesSimulator3D(grid_size, dt, viscosity, device, batch_size=batch_size, jacobi_iters=jacobi_iters)
+        self.device = device
+        self.batch_size = batch_size
+        self.max_history = 100
+        self.history_len = 0       # len(self.history) of the reference (smoke_simulator.py:22-24,41-43), capped at max_history
+        ns = self.ns_solver
+        B, dev = ns._B, ns._dev
+        # the previous and the current emitted volume of every grid, side by side: [B][2] is one stream of 2B volumes for smk_volume_stats,
+        # whose norm 2b is the distance between the two volumes of grid b whichever of them is the newer (the norm is symmetric)
+        self._pair = torch.zeros(B, 2, *ns.grid_size, device=dev)
+        self._slot = 1             # the slot of the newest volume; simulate_step writes the other one
+        self._ws = volume_stats_workspace(2 * B, ns.grid_size, dev)
+        # what smk_chaos_features reads, laid out as a stream of WINDOW "frames" per grid of which only the newest has statistics:
+        # norms[20 b .. 20 b + 18] = the last 19 distances of grid b, oldest first; box / hist row 20 b + 19 = the newest volume's
+        self._norms = torch.zeros(B * WINDOW - 1, device=dev)
+        self._ring = self._norms.as_strided((B, WINDOW - 1), (WINDOW, 1))
+        self._box = torch.zeros(B * WINDOW, 5, dtype=torch.int32, device=dev)
+        self._hist = torch.zeros(B * WINDOW, 256, dtype=torch.int32, device=dev)
+        self._pos = torch.arange(WINDOW - 1, B * WINDOW, WINDOW, dtype=torch.int32, device=dev)
+        self._pos64 = self._pos.long()
+        self._hist_len = {}        # min(history length, 20) -> int32 [B] device tensor (the formulas only ask "below 20?")
+
+    def add_incense_source(self, positions: list, intensities: list, grid: Optional[int] = None):
+        """smoke_simulator.py:26-29 (radius 8) with positions (x, y, z).  Batched: `grid` selects the grid, None = every grid."""
+        ns = self.ns_solver
+        grids = range(ns._B) if grid is None else [grid]
+        ns.add_smoke_sources([(g, x, y, z, 8, inten) for g in grids for (x, y, z), inten in zip(positions, intensities)])
+
+    def simulate_step(self, add_fractal: bool = True, copy: bool = True) -> torch.Tensor:
+        """smoke_simulator.py:31-45.  Returns the emitted volume(s), [B,D,H,W] batched / [D,H,W] un-batched.  copy=False returns the
+        simulator's own buffer instead of a copy of it: valid until the next-but-one simulate_step overwrites it."""
+        ns = self.ns_solver
+        B = ns._B
+        slot = 1 - self._slot
+        cur = self._pair[:, slot]
+        ns.step_into(cur, 1, add_fractal=add_fractal, fractal_intensity=0.05)
+        if self.history_len == 0:                                        # no previous volume yet: statistics only
+            _, box, hist, _ = volume_stats(cur, workspace=self._ws)
+        else:
+            _, box, hist, norms = volume_stats(self._pair.view(2 * B, *ns.grid_size), norms=True, workspace=self._ws)
+            box, hist = box[slot::2], hist[slot::2]
+            self._ring[:, :-1] = self._ring[:, 1:].clone()
+            self._ring[:, -1] = norms[0::2]
+        self._box.index_copy_(0, self._pos64, box)
+        self._hist.index_copy_(0, self._pos64, hist)
+        self._slot = slot
+        self.history_len = min(self.history_len + 1, self.max_history)
+        out = cur.clone() if copy else cur
+        return out if self.batch_size is not None else out[0]
+
+    def simulate_sequence(self, n_steps: int, add_fractal: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """n_steps volumes per grid straight into one [B, n_steps, D, H, W] tensor (no history bookkeeping)."""
+        ns = self.ns_solver
+        if out is None:
+            out = torch.empty(ns._B, n_steps, *ns.grid_size, device=ns._dev)
+        ns.step_into(out, n_steps, add_fractal=add_fractal, fractal_intensity=0.05)
+        return out
+
+    # ---- chaos statistics (smoke_simulator.py:47-140 on the list of emitted volumes) ------------------------------------
+    def get_chaos_features(self, as_tensor: bool = False):
+        """Un-batched: the reference's dict (or {} with fewer than 10 volumes).  Batched: a list with one dict per grid.
+        as_tensor=True: (lyapunov, fractal dimension, entropy) as an fp64 device tensor instead, [B,3] batched / [3] un-batched,
+        None with fewer than 10 volumes; the formulas run on the device and nothing is copied to the host."""
+        B = self.ns_solver._B
+        if self.history_len < 10:
+            if as_tensor:
+                return None
+            return {} if self.batch_size is None else [{} for _ in range(B)]
+        if as_tensor:
+            hl = min(self.history_len, WINDOW)
+            if hl not in self._hist_len:
+                self._hist_len[hl] = torch.full_like(self._pos, hl)
+            feats = chaos_features_device(self._norms if B * WINDOW > 1 else None, self._box, self._hist, self._pos, self._hist_len[hl])
+            return feats if self.batch_size is not None else feats[0]
+        box, hist = self._box[self._pos64].cpu().numpy(), self._hist[self._pos64].cpu().numpy()
+        lyap = [0.0] * B
+        if self.history_len >= WINDOW:
+            d = self._ring.cpu().numpy()
+            lyap = [lyapunov_from_norms(d[b]) for b in range(B)]
+        feats = [{"lyapunov_exponent": lyap[b], "fractal_dimension": fractal_dimension_from_counts(box[b]),
+                  "entropy": entropy_from_hist(hist[b])} for b in range(B)]
+        return feats if self.batch_size is not None else feats[0]
+
+    def _single_grid(self, what):
+        if self.batch_size is not None:
+            raise ValueError(f"{what}: batched simulator -- use get_chaos_features(), which returns one dict per grid")
+
+    def compute_lyapunov_exponent(self) -> float:
+        self._single_grid("compute_lyapunov_exponent")
+        if self.history_len < WINDOW:
+            return 0.0
+        return lyapunov_from_norms(self._ring[0].cpu().numpy())
+
+    def compute_fractal_dimension(self) -> float:
+        self._single_grid("compute_fractal_dimension")
+        if self.history_len == 0:
+            return 0.0
+        return fractal_dimension_from_counts(self._box[WINDOW - 1].cpu().numpy())
+
+    def compute_entropy(self) -> float:
+        self._single_grid("compute_entropy")
+        if self.history_len == 0:
+            return 0.0
+        return entropy_from_hist(self._hist[WINDOW - 1].cpu().numpy())

@@ -17,7 +17,8 @@ from torch.utils.data import DataLoader, Dataset
 
 from .. import _lib
 from ..physics.smoke_simulator import (SmokeSimulator, chaos_features_device, chaos_stats, entropy_from_hist,
-                                       fractal_dimension_from_counts, frame_diff_norms, lyapunov_from_norms)
+                                       fractal_dimension_from_counts, frame_diff_norms, lyapunov_from_norms, volume_stats)
+from ..physics.smoke_simulator3d import SmokeSimulator3D
 from .distributed import shard_range
 
 
@@ -255,6 +256,126 @@ class SyntheticSmokeDataset(Dataset):
                 "chaos_features": torch.tensor([sample["chaos_features"]["lyapunov_exponent"],
                                                 sample["chaos_features"]["fractal_dimension"],
                                                 sample["chaos_features"]["entropy"]], dtype=torch.float32),
+                "sequence": sample["sequence"]}
+
+
+# ---- 3-D volumes (BASELINE configs[4]; SPEC_3D.md section 9) ---------------------------------------------------------------------------
+def draw_source_configs3d(num_samples: int, grid_size: Tuple[int, int, int]) -> List[Dict]:
+    """data_loader.py:49-58 with a depth index: per sample k=randint(1,4), then k x (x, y, z, intensity) in that order from the global
+    np.random; z keeps the 20-cell margin where the depth allows it, m = min(20, D // 4)."""
+    D, H, W = grid_size
+    m = min(20, D // 4)
+    cfgs = []
+    for _ in range(num_samples):
+        k = np.random.randint(1, 4)
+        pos, inten = [], []
+        for _ in range(k):
+            x = np.random.randint(20, W - 20)
+            y = np.random.randint(20, H - 20)
+            z = np.random.randint(m, D - m)
+            intensity = np.random.uniform(0.5, 2.0)
+            pos.append((x, y, z))
+            inten.append(intensity)
+        cfgs.append({"positions": pos, "intensities": inten})
+    return cfgs
+
+
+def chunk_chaos_labels_device3d(buf: torch.Tensor, n_samples: int, T: int, valid_head: int, start: int = 10) -> torch.Tensor:
+    """chunk_chaos_labels_device for a chunk buffer of volumes [HIST_TAIL + n_samples * T, D, H, W]: one smk_volume_stats call over the
+    whole buffer (statistics and distances), then the same smk_chaos_features launch on the same rows.  [n_samples, 3] fp64, on the device."""
+    if start < 9:
+        raise ValueError(f"start={start}: frames with fewer than 10 frames of history are skipped by the host route; use start >= 9")
+    if buf.dim() != 4 or buf.shape[0] != HIST_TAIL + n_samples * T or not 0 <= valid_head <= HIST_TAIL:
+        raise ValueError(f"buf must hold HIST_TAIL + n_samples * T = {HIST_TAIL + n_samples * T} volumes, valid_head in 0..{HIST_TAIL}")
+    dev = _lib.require_cuda(buf.device, "chunk_chaos_labels_device3d")
+    if T <= start:
+        return torch.tensor([[0.0, 1.0, 0.0]], dtype=torch.float64, device=dev).repeat(n_samples, 1)
+    key = (n_samples, T, valid_head, start, dev)
+    if key not in _LABEL_ROWS:
+        _LABEL_ROWS[key] = tuple(torch.from_numpy(a).to(dev) for a in chaos_label_rows(n_samples, T, valid_head, start))
+    _, box, hist, norms = volume_stats(buf, norms=True)
+    return chaos_features_device(norms, box, hist, *_LABEL_ROWS[key], groups=n_samples)[1]
+
+
+class SyntheticSmokeDataset3D(Dataset):
+    """SyntheticSmokeDataset for volumes: the same item schema (input / target [1,D,H,W], chaos_features [3], sequence [T,D,H,W]) and the
+    same sim_batch, jacobi_iters, storage_device and rank/world knobs.  Sources: draw_source_configs3d.  The labels are computed on
+    the device only (chunk_chaos_labels_device3d) and come to the host once; the never-cleared-history quirk across samples is kept
+    (data_loader.py:46 resets only the solver)."""
+
+    def __init__(self, num_samples: int = 100, grid_size: Tuple[int, int, int] = (64, 128, 128), sequence_length: int = 20,
+                 device: str = "cuda", cache_path: Optional[str] = None, *, sim_batch: int = 8, jacobi_iters: int = 20,
+                 storage_device: Optional[str] = None, rank: int = 0, world: int = 1):
+        self.num_samples = num_samples
+        self.grid_size = tuple(grid_size)
+        if len(self.grid_size) != 3:
+            raise ValueError("grid_size must be (D, H, W)")
+        self.sequence_length = sequence_length
+        self.device = device
+        self.cache_path = cache_path
+        self.sim_batch = sim_batch
+        self.jacobi_iters = jacobi_iters
+        self.storage_device = storage_device if storage_device is not None else device
+        self.rank, self.world = rank, world
+        if self.cache_path and os.path.exists(self.cache_path):
+            with open(self.cache_path, "rb") as f:
+                self.data = pickle.load(f)
+            print(f"Loaded synthetic data from {self.cache_path}")
+        else:
+            self.data = self._generate_synthetic_data()
+            if self.cache_path:
+                os.makedirs(os.path.dirname(self.cache_path) or ".", exist_ok=True)
+                with open(self.cache_path, "wb") as f:
+                    pickle.dump([dict(d, sequence=d["sequence"].cpu()) for d in self.data], f)
+                print(f"Saved synthetic data to {self.cache_path}")
+
+    def _generate_synthetic_data(self) -> List[Dict]:
+        dev = _lib.require_cuda(self.device, "SyntheticSmokeDataset3D")
+        cfgs = draw_source_configs3d(self.num_samples, self.grid_size)      # every rank draws the full list
+        lo, hi = shard_range(self.num_samples, self.rank, self.world)
+        first = max(lo - 1, 0)                                              # one extra sample: its volumes seed the history
+        T = self.sequence_length
+        in_place = torch.device(self.storage_device) == dev or str(self.storage_device) == str(self.device)
+        data, chunk_labels, sims = [], [], {}
+        tail, valid_head = None, 0
+        for c0 in range(first, hi, self.sim_batch):
+            c1 = min(c0 + self.sim_batch, hi)
+            n = c1 - c0
+            if n in sims:
+                sim = sims[n]
+                sim.ns_solver.setup_grid()
+            else:
+                sim = sims[n] = SmokeSimulator3D(self.grid_size, device=dev, batch_size=n, jacobi_iters=self.jacobi_iters)
+            sim.ns_solver.add_smoke_sources([(i - c0, x, y, z, 8, inten) for i in range(c0, c1)
+                                             for (x, y, z), inten in zip(cfgs[i]["positions"], cfgs[i]["intensities"])])
+            # one buffer per chunk: [history tail | sample 0's T volumes | sample 1's ...]; the stepper writes the volumes in place
+            buf = torch.empty(HIST_TAIL + n * T, *self.grid_size, device=dev)
+            buf[:HIST_TAIL].zero_()                                         # slots no row reads, but the reductions run over them
+            if tail is not None:
+                buf[HIST_TAIL - tail.shape[0]:HIST_TAIL] = tail
+            seqs = buf[HIST_TAIL:].view(n, T, *self.grid_size)
+            sim.simulate_sequence(T, add_fractal=True, out=seqs)
+            chunk_labels.append(chunk_chaos_labels_device3d(buf, n, T, valid_head)[max(lo - c0, 0):])
+            for i in range(max(c0, lo), c1):
+                seq = seqs[i - c0]
+                data.append({"sequence": seq if in_place else seq.to(self.storage_device).clone(), "chaos_features": None,
+                             "source_config": cfgs[i]})
+            tail = buf[HIST_TAIL - valid_head:][-HIST_TAIL:].clone()
+            valid_head = tail.shape[0]
+        if data:
+            for d, row in zip(data, torch.cat(chunk_labels).cpu().tolist()):     # the one device-to-host copy of the labels
+                d["chaos_features"] = dict(zip(_LABEL_KEYS, row))
+        return data
+
+    def __len__(self) -> int:
+        return len(self.data)
+
+    def __getitem__(self, idx: int) -> Dict:
+        sample = self.data[idx]
+        frame_idx = np.random.randint(5, self.sequence_length - 5)         # data_loader.py:108
+        return {"input": sample["sequence"][frame_idx].unsqueeze(0),
+                "target": sample["sequence"][frame_idx + 1].unsqueeze(0),
+                "chaos_features": torch.tensor([sample["chaos_features"][k] for k in _LABEL_KEYS], dtype=torch.float32),
                 "sequence": sample["sequence"]}
 
 
