@@ -25,13 +25,7 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int LN_PITCH = 144;      // bytes per staged row per plane: 64 bf16 + 16 pad (9 x 16 B, odd: 16 rows hit 16 bank groups)
-#ifndef SMK_LINEAR_SCHED
-#define SMK_LINEAR_SCHED 1
-#endif
-#ifndef SMK_LN_RINGFIRST
-#define SMK_LN_RINGFIRST 1
-#endif
-constexpr int LN_RING = 4;         // B fragments in flight: 3 k-steps ahead; 4 k-steps per chunk keep the ring indices static
+constexpr int LN_RING = 4;        // B fragments in flight: 3 k-steps ahead; 4 k-steps per chunk keep the ring indices static
 template <int MB> constexpr int ln_plane_bytes() { return MB * 32 * LN_PITCH; }
 // LDS of one k_linear_x3 wave group, in bytes from its base: two chunk buffers of (hi | lo) planes, the bias tile (TN = 32 NW floats), then
 // (LNF) the column sums of W' (TN floats) and (mean - pivot, rstd) per tile row (TM = 32 MB rows).  The kernel's pointers and launch_mb's
@@ -121,42 +115,153 @@ __device__ __forceinline__ float gelu_erf(float v) {
     return 0.5f * v * (1.0f + copysignf(erf_abs, v));
 }
 
-#ifdef SMK_LN_STAMPS      /* diagnostic build only (tools/README.md): s_memtime phase stamps into a debug buffer */
-#define LN_STAMP(v) unsigned long long v; __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory"); __builtin_amdgcn_sched_barrier(0)
-#define LN_RSTAMP(v) unsigned long long v; __builtin_amdgcn_sched_barrier(0); asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory"); __builtin_amdgcn_sched_barrier(0)
-#endif
-// timing ablations (SMK_LINEAR_DBG) exist only in diagnostic builds; the product library ignores the variable
-#ifdef SMK_LN_DIAG
-#define LN_DBG(a, bit) ((a).dbg & (bit))
-#else
-#define LN_DBG(a, bit) 0
-#endif
-// 4 fp32 values as the 16 bytes {hi[0..3], lo[0..3]} (bf16 pairs: hi = RNE(v), lo = RNE(v - hi)): LinearCall::split_from
-__device__ __forceinline__ float4 split4_inplace(const float (&v)[4]) {
-    typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-    bf16x4_t vh, vl;
+// ---- the pieces k_linear_x3 and k_linear_b16 share outside their K loops
+
+// Workgroups are dealt to the 8 XCDs round-robin (id % 8).  This renumbers them so that one XCD holds a contiguous id range:
+// the tiles_n workgroups that share a row block (the same A rows) then run on ONE XCD at the same time and A is fetched
+// from HBM once (L2 hits for the others) instead of once per XCD.  (gridDim.x % (8 * tiles_n) == 0 or swz == 0: linear_grid.)
+__device__ __forceinline__ int xcd_contiguous_id(int swz) {
+    return swz ? (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+}
+
+// 4 fp32 values as bf16 pairs: hi = RNE(v), lo = RNE(v - hi)
+struct HiLo4 { bf16x4 hi, lo; };
+__device__ __forceinline__ HiLo4 split_hi_lo(const float (&v)[4]) {
+    HiLo4 s;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const __bf16 h = (__bf16)v[i];
-        vh[i] = h;
-        vl[i] = (__bf16)(v[i] - (float)h);
+        s.hi[i] = h;
+        s.lo[i] = (__bf16)(v[i] - (float)h);
     }
-    const float2 h2 = __builtin_bit_cast(float2, vh), l2 = __builtin_bit_cast(float2, vl);
+    return s;
+}
+// ... as the 16 bytes {hi[0..3], lo[0..3]}: LinearCall::split_from
+__device__ __forceinline__ float4 split4_inplace(const float (&v)[4]) {
+    const HiLo4 s = split_hi_lo(v);
+    const float2 h2 = __builtin_bit_cast(float2, s.hi), l2 = __builtin_bit_cast(float2, s.lo);
     return make_float4(h2.x, h2.y, l2.x, l2.y);
 }
+// 4 consecutive fp32 columns of y starting at column `col`: columns >= split_from (wave-uniform: split_from % 32 == 0) in the in-place split form
+__device__ __forceinline__ void store4_split_from(float *p, const float (&v)[4], int col, int split_from) {
+    const bool sp = split_from >= 0 && col >= split_from;
+    *reinterpret_cast<float4 *>(p) = sp ? split4_inplace(v) : make_float4(v[0], v[1], v[2], v[3]);
+}
+
+// The epilogue's global operand for output row `row`, columns ncol + QS q .. + 3 (q < NQ): the periodic addend (LinearCall::padd) or else the
+// residual; zeros for a row past M.  row0: the tile's first row -- a tile lies inside one group (plan_linear: rows_per_group % tile rows == 0).
+template <int NQ, int QS>
+__device__ __forceinline__ void fetch_extra(const LinearCall &c, int N, int row0, int row, int ncol, float4 (&e)[NQ]) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) e[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (row >= c.M) return;
+    if (c.padd) {
+        const int grp = row0 / c.rows_per_group;
+        const int xx = row - grp * c.rows_per_group;                          // (row in group) mod period, no integer division
+        int ph = xx - (int)((float)xx * (1.0f / (float)c.period)) * c.period;
+        ph = ph < 0 ? ph + c.period : (ph >= c.period ? ph - c.period : ph);
+        const float *pp = c.padd + ((size_t)grp * c.period + ph) * N + ncol;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) e[q] = *reinterpret_cast<const float4 *>(pp + QS * q);
+    } else {
+        const float *rp = c.res + (long long)row * c.ldr + ncol;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) e[q] = *reinterpret_cast<const float4 *>(rp + QS * q);
+    }
+}
+__device__ __forceinline__ void activate(int act, float (&v)[4]) {       // act is wave-uniform
+    if (act == 1) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = gelu_erf(v[i]);
+    } else if (act == 2) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = v[i] > 0.f ? v[i] : 0.f;
+    }
+}
+// y = res + act(v)  or  y = act(v + addend), eq = what fetch_extra brought (the operand order of each sum is part of the result's bits)
+__device__ __forceinline__ void activate_extra(const LinearCall &c, float (&v)[4], const float4 &eq) {
+    if (c.padd) { v[0] += eq.x; v[1] += eq.y; v[2] += eq.z; v[3] += eq.w; }
+    activate(c.act, v);
+    if (!c.padd) { v[0] = eq.x + v[0]; v[1] = eq.y + v[1]; v[2] = eq.z + v[2]; v[3] = eq.w + v[3]; }
+}
+
+// Fused LayerNorm, closing one staging row: s1 / s2 = this thread's share of the row's sum (x - pivot) / sum (x - pivot)^2; the 16 threads
+// sc = 0 .. 15 of a staging row hold its 64 k of every chunk between them.  stat = the row's (mean - pivot, rstd) in LDS.
+__device__ __forceinline__ void ln_close_row(float s1, float s2, int sc, int K, float eps, float *stat) {
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) { s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
+    if (sc == 0) {
+        const float dm = s1 / (float)K;                       // mean - pivot
+        float var = s2 / (float)K - dm * dm;
+        var = var > 0.f ? var : 0.f;
+        stat[0] = dm;
+        stat[1] = 1.0f / sqrtf(var + eps);
+    }
+}
+// ... and finishing 4 columns of that row: v = rstd ((x - p) W'^T - (mean - p) wsum) + b'; acc = (x - p) W'^T, wsum / b = the columns' sums of W' / b'
+__device__ __forceinline__ void ln_finish(float (&v)[4], const float4 &acc, const float *stat, const float *wsum, const float4 &b) {
+    const float dm = stat[0], rstd = stat[1];
+    const float4 wq4 = *reinterpret_cast<const float4 *>(wsum);
+    v[0] = rstd * (acc.x - dm * wq4.x) + b.x;
+    v[1] = rstd * (acc.y - dm * wq4.y) + b.y;
+    v[2] = rstd * (acc.z - dm * wq4.z) + b.z;
+    v[3] = rstd * (acc.w - dm * wq4.w) + b.w;
+}
+
+// Diagnostic build only (-DSMK_LN_STAMPS, tools/README.md): s_memtime phase stamps into a debug buffer.  Everything the stamps need sits in
+// LN_STAMPS(...), which the product build expands to nothing.
+#ifdef SMK_LN_STAMPS
+#define LN_STAMPS(...) __VA_ARGS__
+#define LN_STAMP(v) unsigned long long v; __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory"); __builtin_amdgcn_sched_barrier(0)
+#define LN_RSTAMP(v) unsigned long long v; __builtin_amdgcn_sched_barrier(0); asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory"); __builtin_amdgcn_sched_barrier(0)
+#else
+#define LN_STAMPS(...)
+#endif
 
 struct LinearArgs {
     LinearDev l;
     LinearCall c;
     int tiles_m, tiles_n;
-    int swz, stagger, stagger_unit, num_cu;
+    int swz, num_cu;
     // implicit-GEMM Conv3d (k_linear_b16<NW, true>): x is a channels-last slab [cDl][cH][cW][64], output rows are the voxels of planes
     // cz_off .. of that slab in memory order; chunk c of the K range is tap c of the 3 x 3 x 3 window (zero outside the slab)
     int cDl, cH, cW, cz_off;
-    unsigned long long *stamps;
-    int dbg;              // timing ablations, honoured only by -DSMK_LN_DIAG builds (results are wrong when non-zero): 1 A loads re-read tile 0,
-                          // 2 B ring re-reads k-step 0, 4 no epilogue, 8 epilogue stores as whole 128-byte row pieces
+    unsigned long long *stamps;       // SMK_LN_STAMPS builds
 };
+
+// The environment switches of this file, read once per process.  All are for A/B runs and tests (tools/README.md); unset = the product's choice.
+struct LinearKnobs {
+    int nw, mb, ks;       // SMK_LINEAR_NW / MB / KS: force the tile's waves (4 | 8), row blocks (1 | 2 | 4), split-K wave groups (1 | 2 | 4); 0: the plan's
+    int shape;            // SMK_LINEAR_SHAPE=32 keeps the 32x32x16 kernel (k_linear_x3) where k_linear_b16 would run
+    bool swz;             // SMK_LINEAR_SWZ=0: no XCD-contiguous workgroup ids
+    bool wgrad_tr;        // SMK_LINEAR_WGRAD_TR=0: the weight gradient through the transposed copy of dY
+};
+static const LinearKnobs &knobs() {
+    static const LinearKnobs k = [] {
+        auto num = [](const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; };
+        LinearKnobs r;
+        r.nw = num("SMK_LINEAR_NW", 0); r.mb = num("SMK_LINEAR_MB", 0); r.ks = num("SMK_LINEAR_KS", 0);
+        r.shape = num("SMK_LINEAR_SHAPE", 16);
+        r.swz = num("SMK_LINEAR_SWZ", 1) != 0;
+        const char *w = getenv("SMK_LINEAR_WGRAD_TR");
+        r.wgrad_tr = !(w && w[0] == '0');
+        return r;
+    }();
+    return k;
+}
+
+// Grid of a persistent launch of either kernel: wg_per_cu workgroups per CU at the most (8 waves per CU either way), a multiple of tiles_n so that
+// every workgroup keeps one column tile, the same walk per K-segment over its own [M][N] slab; sets a.swz (see xcd_contiguous_id).
+static unsigned linear_grid(LinearArgs &a, int wg_per_cu) {
+    const int nwg_max = wg_per_cu * a.num_cu / a.c.nseg;
+    const long long tiles = (long long)a.tiles_m * a.tiles_n;
+    long long nwg = tiles < nwg_max ? tiles : nwg_max;
+    nwg -= nwg % a.tiles_n;
+    if (nwg < a.tiles_n) nwg = a.tiles_n;
+    nwg *= a.c.nseg;
+    a.swz = knobs().swz && nwg % (8 * a.tiles_n) == 0;
+    return (unsigned)nwg;
+}
 
 // AS: the activations arrive already split (SMK_FMT_SPLIT_BF16: per row, per 8 k: 8 hi | 8 lo bf16 -- the same 4 bytes per
 // element as fp32, written by the producing kernel's epilogue): staging is then a 16-byte copy, no arithmetic in the K loop.
@@ -173,7 +278,6 @@ template <int MB, int NW, bool AS, int KS = 1, int RING = LN_RING, bool LNF = fa
 __global__ __launch_bounds__(NW * 64 * KS, KS > 2 ? 1 : 2) void k_linear_x3(const LinearArgs a) {
     static_assert(!LNF || (!AS && KS == 1), "fused LayerNorm: fp32 activations, one wave group");
     constexpr int TN = NW * 32, RP = AS ? NW * 8 : NW * 4;   // tile columns; rows staged per pass (fp32: 16 float4 per row chunk; split: 8 x 32 B)
-    constexpr bool sched = SMK_LINEAR_SCHED;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
     constexpr int TM = MB * 32, PLANE = ln_plane_bytes<MB>();
     const int grp = KS == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)threadIdx.x / (NW * 64));
@@ -184,10 +288,7 @@ __global__ __launch_bounds__(NW * 64 * KS, KS > 2 ? 1 : 2) void k_linear_x3(cons
     const int K = a.l.K, N = a.l.N, M = a.c.M;
     const int nchunks = (K >> 6) / KS, nks = nchunks * 4;      // this wave group's share of the K range
     const int c_off = grp * nchunks, k_off = c_off * 4;
-    // Workgroups are dealt to the 8 XCDs round-robin (id % 8).  vid renumbers them so that one XCD holds a contiguous id range:
-    // the tiles_n workgroups that share a row block (the same A rows) then run on ONE XCD at the same time and A is fetched
-    // from HBM once (L2 hits for the others) instead of once per XCD.  (gridDim.x % (8 * tiles_n) == 0 or swz == 0.)
-    const int vid0 = a.swz ? (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+    const int vid0 = xcd_contiguous_id(a.swz);
     // K-segmented launches (LinearCall::nseg > 1): a contiguous id range per segment; the segment only offsets the three base pointers
     const int wg_per_seg = (int)gridDim.x / a.c.nseg;
     const int seg = a.c.nseg > 1 ? vid0 / wg_per_seg : 0;
@@ -195,15 +296,6 @@ __global__ __launch_bounds__(NW * 64 * KS, KS > 2 ? 1 : 2) void k_linear_x3(cons
     const int tn = vid % a.tiles_n;                          // fixed for the life of the workgroup (wg_per_seg % tiles_n == 0)
     const int tm_step = wg_per_seg / a.tiles_n;
     int tm = vid / a.tiles_n;
-    // Two workgroups share a CU and run the same program with the same period: delay every other dispatch round by about
-    // half a tile so that one's epilogue / staging stalls overlap the other's MFMA stretch (speed only).
-    // Tiles of equal length keep all workgroups of the chip in lock-step: every epilogue is then one chip-wide write burst
-    // that drains at HBM write bandwidth while the matrix pipes idle.  Starting the workgroups in `stagger` phase groups
-    // spreads the bursts (a one-time cost of up to (stagger-1)/stagger of a tile for the last group).
-    if (a.stagger > 1) {
-        const int ph = (blockIdx.x >> 3) % a.stagger;          // same XCD, consecutive CUs -> different phases
-        for (int i = 0; i < ph * a.stagger_unit; ++i) __builtin_amdgcn_s_sleep(127);
-    }
     float *const y_seg = a.c.y + (size_t)seg * M * a.c.ldy;   // segment s writes its own dense [M][N] slab
     const int n = tn * TN + wave * 32 + r;                  // this lane's output column
     const bool n_ok = n < N;
@@ -214,7 +306,7 @@ __global__ __launch_bounds__(NW * 64 * KS, KS > 2 ? 1 : 2) void k_linear_x3(cons
         __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(a.l.wq) + (size_t)seg * K * N * 2, 0, K * N * 4, 0x00020000);
     const int frag_bytes = N * 32;                           // one (k-step, part) plane
     auto load_b = [&](int kn, int part) -> uint4 {
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane_b, ((LN_DBG(a, 2) ? 0 : kn + k_off) * 2 + part) * frag_bytes, 0);
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane_b, ((kn + k_off) * 2 + part) * frag_bytes, 0);
         return make_uint4(v[0], v[1], v[2], v[3]);
     };
     uint4 bqh[RING], bql[RING];
@@ -249,7 +341,7 @@ __global__ __launch_bounds__(NW * 64 * KS, KS > 2 ? 1 : 2) void k_linear_x3(cons
     const int ldxb = (int)a.c.ldx * 4;                       // row bytes (split rows are dense: ldx = K)
     const int lane_x = sr * ldxb + sc * (AS ? 32 : 16);
     auto stage_load = [&](int tmx, int cx, int j) {
-        const unsigned row_u = (unsigned)(LN_DBG(a, 1) ? 0 : tmx) * TM + RP * j;          // wave-uniform part (SALU); tmx <= tiles_m
+        const unsigned row_u = (unsigned)tmx * TM + RP * j;          // wave-uniform part (SALU); tmx <= tiles_m
         const unsigned off = row_u * (unsigned)ldxb + (unsigned)(cx + c_off) * 256u;      // < 2^32: api.hip bounds (rows + 256) * ldx
         if (AS) {
             sth[AS ? j : 0] = __builtin_amdgcn_raw_buffer_load_b128(xrsrc, (int)(off + (unsigned)lane_x), 0, 0);
@@ -270,7 +362,6 @@ __global__ __launch_bounds__(NW * 64 * KS, KS > 2 ? 1 : 2) void k_linear_x3(cons
             *reinterpret_cast<u32x4 *>(ph + PLANE) = stl[AS ? j : 0];
             return;
         }
-        unsigned char *ph = smem + buf * 2 * PLANE + (sr + RP * j) * LN_PITCH + sc * 8;
         float v[4] = {stage[AS ? 0 : j].x, stage[AS ? 0 : j].y, stage[AS ? 0 : j].z, stage[AS ? 0 : j].w};
         if constexpr (LNF) {
             const float pv = ln_piv[j];                                      // loaded with this very piece
@@ -282,20 +373,10 @@ __global__ __launch_bounds__(NW * 64 * KS, KS > 2 ? 1 : 2) void k_linear_x3(cons
             ln_ns[j] = first_of_next ? s1 : ln_ns[j];
             ln_nq[j] = first_of_next ? s2 : ln_nq[j];
         }
-        bf16x4 vh, vl;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#ifdef SMK_LN_NOCONV      /* timing-only build: no split arithmetic (wrong results) */
-            vh[i] = __builtin_bit_cast(__bf16, (unsigned short)(__builtin_bit_cast(unsigned, v[i]) >> 16));
-            vl[i] = vh[i];
-#else
-            const __bf16 h = (__bf16)v[i];
-            vh[i] = h;
-            vl[i] = (__bf16)(v[i] - (float)h);
-#endif
-        }
-        *reinterpret_cast<bf16x4 *>(ph) = vh;
-        *reinterpret_cast<bf16x4 *>(ph + PLANE) = vl;
+        const HiLo4 s = split_hi_lo(v);
+        unsigned char *ph = smem + buf * 2 * PLANE + (sr + RP * j) * LN_PITCH + sc * 8;
+        *reinterpret_cast<bf16x4 *>(ph) = s.hi;
+        *reinterpret_cast<bf16x4 *>(ph + PLANE) = s.lo;
     };
     // the chunk stream: (tile row, chunk) pairs in the order this workgroup consumes them; rows past M read as zeros
     int ld_tm = tm, ld_c = 0;
@@ -340,15 +421,9 @@ __global__ __launch_bounds__(NW * 64 * KS, KS > 2 ? 1 : 2) void k_linear_x3(cons
     float *wsum_s = reinterpret_cast<float *>(smem + lay::wsum), *stat_s = reinterpret_cast<float *>(smem + lay::stat);   // LNF: column sums of W', then (mean, rstd) per tile row
     if (LNF && tid < TN) wsum_s[tid] = tn * TN + tid < N ? a.c.ln_wsum[tn * TN + tid] : 0.f;
 
-#ifdef SMK_LN_STAMPS
-    unsigned long long sum_k = 0, sum_e = 0, ntl = 0, sum_u[5] = {0, 0, 0, 0, 0}, t_prev = 0;
-    LN_STAMP(t_begin);
-    LN_RSTAMP(r_begin);
-#endif
+    LN_STAMPS(unsigned long long sum_k = 0, sum_e = 0, ntl = 0, sum_u[5] = {0, 0, 0, 0, 0}, t_prev = 0; LN_STAMP(t_begin); LN_RSTAMP(r_begin);)
     for (; tm < a.tiles_m; tm += tm_step) {
-#ifdef SMK_LN_STAMPS
-        LN_STAMP(t_k0);
-#endif
+        LN_STAMPS(LN_STAMP(t_k0);)
         f32x16 acc[MB];
 #pragma unroll
         for (int mi = 0; mi < MB; ++mi)
@@ -360,12 +435,7 @@ __global__ __launch_bounds__(NW * 64 * KS, KS > 2 ? 1 : 2) void k_linear_x3(cons
             auto kstep = [&](auto U) {
                 constexpr int pu = decltype(U)::value, u = pu & 3;        // pu: k-step within the unrolled group of RING / 4 chunks
                 const int c = c0 + (pu >> 2);
-#ifdef SMK_LN_STAMPS
-                LN_STAMP(t_u);
-                if (u > 0) sum_u[u - 1] += t_u - t_prev;
-                else if (c > 0) sum_u[3] += t_u - t_prev;
-                t_prev = t_u;
-#endif
+                LN_STAMPS(LN_STAMP(t_u); if (u > 0) sum_u[u - 1] += t_u - t_prev; else if (c > 0) sum_u[3] += t_u - t_prev; t_prev = t_u;)
                 {   // refill the ring slot consumed one k-step ago (k index wraps: the next tile uses the same weights)
                     int kn = c * 4 + u + RING - 1;
                     kn = kn >= nks ? kn - nks : kn;
@@ -384,13 +454,11 @@ __global__ __launch_bounds__(NW * 64 * KS, KS > 2 ? 1 : 2) void k_linear_x3(cons
                     stage_load(ld_tm, ld_c, j);
                 }
                 if (u == 2) advance();
-#ifdef SMK_LN_STAMPS
-                if (u == 3) { LN_STAMP(t_b0); __syncthreads(); LN_STAMP(t_b1); sum_u[4] += t_b1 - t_b0; }
-#else
-#ifndef SMK_LN_NOBAR
-                if (u == 3) __syncthreads();     // other buffer complete and visible; every read of this buffer has returned
-#endif
-#endif
+                if (u == 3) {                    // other buffer complete and visible; every read of this buffer has returned
+                    LN_STAMPS(LN_STAMP(t_b0);)
+                    __syncthreads();
+                    LN_STAMPS(LN_STAMP(t_b1); sum_u[4] += t_b1 - t_b0;)
+                }
                 if (u & 1) load_a(u == 3 ? buf ^ 1 : buf, (u + 1) & 3, ahA, alA);
                 else load_a(buf, u + 1, ahB, alB);
                 const bf16x8 bh = __builtin_bit_cast(bf16x8, bqh[pu % RING]);
@@ -405,7 +473,7 @@ __global__ __launch_bounds__(NW * 64 * KS, KS > 2 ? 1 : 2) void k_linear_x3(cons
                 // Schedule of one k-step: next k-step's fragment reads, the ring refill and (k-steps 0,1) the staging work are
                 // issued INSIDE the gaps of this k-step's MFMAs (left alone, hipcc sinks every ds_read to just before its
                 // consumer and waits on it there).
-                if (sched) {
+                {
                     // per SIMD an MFMA gap hides about five other vector-issue slots (MI355X_MICROARCH.md, constants table), shared
                     // by the two resident waves: the split arithmetic is spread at ~12 VALU per piece over the k-step's gaps
                     constexpr int NMF = 3 * MB, NDS = 2 * MB, NPC = pend - pbeg;
@@ -413,20 +481,13 @@ __global__ __launch_bounds__(NW * 64 * KS, KS > 2 ? 1 : 2) void k_linear_x3(cons
 #pragma unroll
                     for (int i = 0; i < NMF; ++i) {
                         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                          // 1 MFMA
-#if SMK_LN_RINGFIRST
                         if (i < 2) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);               // ring refill first (L2 latency)
                         if (i < NDS) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);             // 1 DS read (next k-step's fragment)
-#else
-                        if (i < NDS) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);             // 1 DS read (next k-step's fragment)
-#endif
                         if (VPER) __builtin_amdgcn_sched_group_barrier(0x002, VPER, 0);             // split arithmetic
                         if (i >= NMF - NPC) {
                             __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);                      // a finished piece: 2 DS writes
                             __builtin_amdgcn_sched_group_barrier(0x020, (AS || LNF) ? 2 : 1, 0);    //   + its re-issued load(s) (LNF: + the pivot)
                         }
-#if !SMK_LN_RINGFIRST
-                        if (i >= NMF - 2) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);        // ring refill
-#endif
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -447,9 +508,7 @@ __global__ __launch_bounds__(NW * 64 * KS, KS > 2 ? 1 : 2) void k_linear_x3(cons
             }
         }
 
-#ifdef SMK_LN_STAMPS
-        LN_STAMP(t_k1);
-#endif
+        LN_STAMPS(LN_STAMP(t_k1);)
         if (KS > 1) {   // merge the wave groups' partial sums: groups 1.. park theirs in LDS, group 0 adds them in group order
             float *xch = reinterpret_cast<float *>(smem_all + KS * lay::bytes);
             if (grp > 0) {
@@ -481,136 +540,75 @@ __global__ __launch_bounds__(NW * 64 * KS, KS > 2 ? 1 : 2) void k_linear_x3(cons
         if constexpr (LNF) {   // row statistics: the 16 threads sc = 0 .. 15 of a staging row hold its 64 k of every chunk between them
 #pragma unroll
             for (int j = 0; j < NPC_ALL; ++j) {
-                float s1 = ln_s[j], s2 = ln_q[j];
-#pragma unroll
-                for (int o = 1; o < 16; o <<= 1) { s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
-                if (sc == 0) {
-                    const float dm = s1 / (float)K;                       // mean - pivot
-                    float var = s2 / (float)K - dm * dm;
-                    var = var > 0.f ? var : 0.f;
-                    stat_s[2 * (sr + RP * j)] = dm;
-                    stat_s[2 * (sr + RP * j) + 1] = 1.0f / sqrtf(var + a.c.ln_eps);
-                }
+                ln_close_row(ln_s[j], ln_q[j], sc, K, a.c.ln_eps, stat_s + 2 * (sr + RP * j));
                 ln_s[j] = ln_ns[j]; ln_q[j] = ln_nq[j];                   // the next tile's first chunk is already in
             }
             __syncthreads();
         }
         // ---- epilogue.  The weights are the MFMA's row operand, so acc[mi][4q + i] = output row mi*32 + r (this lane's token),
         //      column 8q + 4hi + i of the wave's 32: four consecutive columns per lane -> 16-byte loads and stores.
-        if (grp == 0 && nw_ok && !LN_DBG(a, 4)) {
+        if (grp == 0 && nw_ok) {
             const int row0 = tm * TM, ncol = tn * TN + wave * 32 + 4 * hi;
             const float *bias_w = bias_s + wave * 32 + 4 * hi;
             // Global loads (residual, periodic addend) of row block mi+1 are issued BEFORE the stores of block mi: vmcnt retires in
             // order, so a load issued after a store could only be consumed once that store had been acknowledged by memory.
-            float4 ex[2][4];                                 // per column group: residual (+ addend) of the block being finished
+            float4 ex[2][4];                                 // per column group: residual or addend of the block being finished
             const bool any_ex = a.c.res || a.c.padd;
-            auto fetch_extra = [&](int mi, float4 (&e)[4]) {
-                const int row = row0 + mi * 32 + r;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) e[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (row >= M) return;
-                if (a.c.padd) {                              // a tile lies inside one group (launcher: rows_per_group % TM == 0)
-                    const int grp = row0 / a.c.rows_per_group;
-                    const int xx = row - grp * a.c.rows_per_group;                      // (row in group) mod period, no integer division
-                    int ph = xx - (int)((float)xx * (1.0f / (float)a.c.period)) * a.c.period;
-                    ph = ph < 0 ? ph + a.c.period : (ph >= a.c.period ? ph - a.c.period : ph);
-                    const float *pp = a.c.padd + ((size_t)grp * a.c.period + ph) * N + ncol;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) e[q] = *reinterpret_cast<const float4 *>(pp + 8 * q);
-                } else {
-                    const float *rp = a.c.res + (long long)row * a.c.ldr + ncol;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) e[q] = *reinterpret_cast<const float4 *>(rp + 8 * q);
-                }
+            // bias (or the fused LayerNorm's finish) for row mi*32 + r, columns 8q + 4hi .. + 3 of the wave's 32
+            auto start4 = [&](float (&v)[4], int mi, int q) {
+                const float4 bq = *reinterpret_cast<const float4 *>(bias_w + 8 * q);
+                v[0] = acc[mi][4 * q] + bq.x; v[1] = acc[mi][4 * q + 1] + bq.y; v[2] = acc[mi][4 * q + 2] + bq.z; v[3] = acc[mi][4 * q + 3] + bq.w;
+                if constexpr (LNF)
+                    ln_finish(v, make_float4(acc[mi][4 * q], acc[mi][4 * q + 1], acc[mi][4 * q + 2], acc[mi][4 * q + 3]), stat_s + 2 * (mi * 32 + r),
+                              wsum_s + wave * 32 + 4 * hi + 8 * q, bq);
             };
-            // activation + store of 4 consecutive columns of one row (fp32 or split-bf16)
-            auto finish = [&](float (&v)[4], int row, int q) {
-                if (a.c.act == 1) {                       // wave-uniform
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) v[i] = gelu_erf(v[i]);
-                } else if (a.c.act == 2) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) v[i] = v[i] > 0.f ? v[i] : 0.f;
-                }
-            };
+            // store of 4 consecutive columns of one row (fp32 or split-bf16)
             auto store4 = [&](const float (&v)[4], int row, int q) {
                 if (row >= M) return;
                 if (a.c.y_split) {   // SMK_FMT_SPLIT_BF16: group (ncol + 8q) / 8 of the row, this lane's half (4 hi | 4 lo)
-                    bf16x4 vh, vl;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const __bf16 h = (__bf16)v[i];
-                        vh[i] = h;
-                        vl[i] = (__bf16)(v[i] - (float)h);
-                    }
+                    const HiLo4 s = split_hi_lo(v);
                     __bf16 *ys = reinterpret_cast<__bf16 *>(a.c.y) + (size_t)row * (2 * N) + ((ncol >> 3) + q) * 16 + 4 * hi;
-                    *reinterpret_cast<bf16x4 *>(ys) = vh;
-                    *reinterpret_cast<bf16x4 *>(ys + 8) = vl;
-                } else if (LN_DBG(a, 8)) {   // timing ablation: the same bytes as 8 rows x 128 contiguous bytes per store instruction (values misplaced)
-                    const int L = r + 32 * hi, rr = row - r + 8 * q + (L >> 3);
-                    if (rr < M) *reinterpret_cast<float4 *>(y_seg + (long long)rr * a.c.ldy + (ncol - 4 * hi) + (L & 7) * 4) = make_float4(v[0], v[1], v[2], v[3]);
+                    *reinterpret_cast<bf16x4 *>(ys) = s.hi;
+                    *reinterpret_cast<bf16x4 *>(ys + 8) = s.lo;
                 } else {
-                    const bool sp = a.c.split_from >= 0 && ncol + 8 * q >= a.c.split_from;        // wave-uniform (split_from % 32 == 0)
-                    *reinterpret_cast<float4 *>(y_seg + (long long)row * a.c.ldy + ncol + 8 * q) = sp ? split4_inplace(v) : make_float4(v[0], v[1], v[2], v[3]);
+                    store4_split_from(y_seg + (long long)row * a.c.ldy + ncol + 8 * q, v, ncol + 8 * q, a.c.split_from);
                 }
-            };
-            // fused LayerNorm: v = rstd ((x - p) W'^T - (mean - p) wsum) + b' for row mi*32 + r, columns 8q + 4hi .. + 3 of the wave's 32
-            auto ln_finish = [&](float (&v)[4], int mi, int q, const float4 &bq) {
-                const float mean = stat_s[2 * (mi * 32 + r)], rstd = stat_s[2 * (mi * 32 + r) + 1];      // ("mean" = mean - pivot)
-                const float4 wq4 = *reinterpret_cast<const float4 *>(wsum_s + wave * 32 + 4 * hi + 8 * q);
-                v[0] = rstd * (acc[mi][4 * q] - mean * wq4.x) + bq.x;
-                v[1] = rstd * (acc[mi][4 * q + 1] - mean * wq4.y) + bq.y;
-                v[2] = rstd * (acc[mi][4 * q + 2] - mean * wq4.z) + bq.z;
-                v[3] = rstd * (acc[mi][4 * q + 3] - mean * wq4.w) + bq.w;
             };
             if (!any_ex) {
                 // plain path: no global loads at all, so nothing ever waits on vmcnt -- which on CDNA4 also counts the stores
                 // (a wait here would drain every store to memory before the next one is issued)
 #pragma unroll
-                for (int mi = 0; mi < MB; ++mi) {
-                    const int row = row0 + mi * 32 + r;
+                for (int mi = 0; mi < MB; ++mi)
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        const float4 bq = *reinterpret_cast<const float4 *>(bias_w + 8 * q);
-                        float v[4] = {acc[mi][4 * q] + bq.x, acc[mi][4 * q + 1] + bq.y, acc[mi][4 * q + 2] + bq.z, acc[mi][4 * q + 3] + bq.w};
-                        if constexpr (LNF) ln_finish(v, mi, q, bq);
-                        finish(v, row, q);
-                        store4(v, row, q);
+                        float v[4];
+                        start4(v, mi, q);
+                        activate(a.c.act, v);
+                        store4(v, row0 + mi * 32 + r, q);
                     }
-                }
             } else {
-                fetch_extra(0, ex[0]);
+                fetch_extra<4, 8>(a.c, N, row0, row0 + r, ncol, ex[0]);
 #pragma unroll
                 for (int mi = 0; mi < MB; ++mi) {
-                    if (mi + 1 < MB) fetch_extra(mi + 1, ex[(mi + 1) & 1]);
-                    const int row = row0 + mi * 32 + r;
+                    if (mi + 1 < MB) fetch_extra<4, 8>(a.c, N, row0, row0 + (mi + 1) * 32 + r, ncol, ex[(mi + 1) & 1]);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        const float4 bq = *reinterpret_cast<const float4 *>(bias_w + 8 * q);
-                        const float4 eq = ex[mi & 1][q];
-                        float v[4] = {acc[mi][4 * q] + bq.x, acc[mi][4 * q + 1] + bq.y, acc[mi][4 * q + 2] + bq.z, acc[mi][4 * q + 3] + bq.w};
-                        if constexpr (LNF) ln_finish(v, mi, q, bq);
-                        if (a.c.padd) { v[0] += eq.x; v[1] += eq.y; v[2] += eq.z; v[3] += eq.w; }
-                        finish(v, row, q);
-                        if (!a.c.padd) { v[0] = eq.x + v[0]; v[1] = eq.y + v[1]; v[2] = eq.z + v[2]; v[3] = eq.w + v[3]; }
-                        store4(v, row, q);
+                        float v[4];
+                        start4(v, mi, q);
+                        activate_extra(a.c, v, ex[mi & 1][q]);
+                        store4(v, row0 + mi * 32 + r, q);
                     }
                 }
             }
         }
-#ifdef SMK_LN_STAMPS
-        LN_STAMP(t_e);
-        sum_k += t_k1 - t_k0; sum_e += t_e - t_k1; ++ntl;
-#endif
+        LN_STAMPS(LN_STAMP(t_e); sum_k += t_k1 - t_k0; sum_e += t_e - t_k1; ++ntl;)
     }
-#ifdef SMK_LN_STAMPS
-    LN_STAMP(t_end);
-    LN_RSTAMP(r_end);
-    if (a.stamps && lane == 0) {
-        unsigned long long *rec = a.stamps + (((size_t)blockIdx.x * NW + wave) & 4095) * 8;
-        rec[0] = sum_k; rec[1] = sum_e; rec[2] = t_end - t_begin; rec[3] = r_end - r_begin; rec[4] = ntl; rec[5] = sum_u[0] | (sum_u[1] << 32); rec[6] = sum_u[2] | (sum_u[3] << 32); rec[7] = sum_u[4];
-    }
-#endif
+    LN_STAMPS(LN_STAMP(t_end); LN_RSTAMP(r_end);
+              if (a.stamps && lane == 0) {
+                  unsigned long long *rec = a.stamps + (((size_t)blockIdx.x * NW + wave) & 4095) * 8;
+                  rec[0] = sum_k; rec[1] = sum_e; rec[2] = t_end - t_begin; rec[3] = r_end - r_begin; rec[4] = ntl;
+                  rec[5] = sum_u[0] | (sum_u[1] << 32); rec[6] = sum_u[2] | (sum_u[3] << 32); rec[7] = sum_u[4];
+              })
 }
 
 template <int MB, int NW, bool AS, int KS = 1, int RING = LN_RING, bool LNF = false>
@@ -619,23 +617,9 @@ static hipError_t launch_mb(const LinearArgs &a, hipStream_t st) {
     once_per_device((const void *)k_linear_x3<MB, NW, AS, KS, RING, LNF>, [&] {
         (void)hipFuncSetAttribute((const void *)k_linear_x3<MB, NW, AS, KS, RING, LNF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     });
-    const int nseg = a.c.nseg;
-    const int nwg_max = (NW == 8 || KS > 1 ? 1 : 2) * a.num_cu / nseg;     // 8 waves per CU either way (split-K: one workgroup per CU)
-    const long long tiles = (long long)a.tiles_m * a.tiles_n;
-    long long nwg = tiles < nwg_max ? tiles : nwg_max;
-    nwg -= nwg % a.tiles_n;                               // every workgroup keeps one column tile
-    if (nwg < a.tiles_n) nwg = a.tiles_n;
-    nwg *= nseg;                                          // per segment: the same walk over its own [M][N] slab
     LinearArgs b = a;
-    static int swz_env = -1, stg_env = -1;
-    if (swz_env < 0) { const char *s = getenv("SMK_LINEAR_SWZ"); swz_env = s ? atoi(s) : 1; }
-    if (stg_env < 0) { const char *s = getenv("SMK_LINEAR_STAGGER"); stg_env = s ? atoi(s) : 0; }
-    b.swz = swz_env && nwg % (8 * a.tiles_n) == 0;
-    b.stagger = stg_env;
-    // one tile ~ (K/64) chunks x ~4.2 K cycles + ~9 K epilogue; s_sleep(127) ~ 8 K cycles
-    b.stagger_unit = stg_env > 1 ? (int)(((a.l.K / 64) * 4200 + 9000) / 8128 / stg_env) : 0;
-    if (b.stagger_unit < 1) b.stagger = 0;
-    hipLaunchKernelGGL((k_linear_x3<MB, NW, AS, KS, RING, LNF>), dim3((unsigned)nwg), dim3(NW * 64 * KS), lds, st, b);
+    const unsigned nwg = linear_grid(b, NW == 8 || KS > 1 ? 1 : 2);       // (split-K: one workgroup per CU)
+    hipLaunchKernelGGL((k_linear_x3<MB, NW, AS, KS, RING, LNF>), dim3(nwg), dim3(NW * 64 * KS), lds, st, b);
     return hipGetLastError();
 }
 
@@ -687,7 +671,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_linear_b16(const LinearArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int K = a.l.K, N = a.l.N, M = a.c.M;
     const int nchunks = K >> 6, nks = nchunks * 2;           // 32-k steps
-    const int vid = a.swz ? (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;    // XCD-contiguous ids (see k_linear_x3)
+    const int vid = xcd_contiguous_id(a.swz);
     const int tn = vid % a.tiles_n, tm_step = (int)gridDim.x / a.tiles_n;
     int tm = vid / a.tiles_n;
     const int ncol0 = tn * TN + wave * 32;
@@ -776,7 +760,6 @@ __global__ __launch_bounds__(NW * 64, 2) void k_linear_b16(const LinearArgs a) {
     // row sr + RP j: RP is a multiple of 8, so (row & 7) = sr & 7 for every piece
     const int st_off = sr * 128 + ((((sc >> 1) ^ (sr & 7))) << 4) + (sc & 1) * 8;
     auto stage_store = [&](int buf, int j) {
-        unsigned char *ph = smem + buf * 2 * PLANE + st_off + RP * j * 128;
         float v[4] = {stage[j].x, stage[j].y, stage[j].z, stage[j].w};
         if constexpr (LNF) {
             const float pv = ln_piv[j];
@@ -785,15 +768,10 @@ __global__ __launch_bounds__(NW * 64, 2) void k_linear_b16(const LinearArgs a) {
             ln_s[j] += (v[0] + v[1]) + (v[2] + v[3]);
             ln_q[j] += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
         }
-        bf16x4 vh, vl;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const __bf16 h = (__bf16)v[i];
-            vh[i] = h;
-            vl[i] = (__bf16)(v[i] - (float)h);
-        }
-        *reinterpret_cast<bf16x4 *>(ph) = vh;
-        *reinterpret_cast<bf16x4 *>(ph + PLANE) = vl;
+        const HiLo4 s = split_hi_lo(v);
+        unsigned char *ph = smem + buf * 2 * PLANE + st_off + RP * j * 128;
+        *reinterpret_cast<bf16x4 *>(ph) = s.hi;
+        *reinterpret_cast<bf16x4 *>(ph + PLANE) = s.lo;
     };
     int ld_tm = tm, ld_c = 0;
     auto advance = [&]() {
@@ -836,11 +814,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_linear_b16(const LinearArgs a) {
     int buf = 0;
     load_a(0, 0, ahA, alA);
 
-#ifdef SMK_LN_STAMPS
-    unsigned long long sum_k = 0, sum_e = 0, ntl = 0;
-    LN_STAMP(t_begin);
-    LN_RSTAMP(r_begin);
-#endif
+    LN_STAMPS(unsigned long long sum_k = 0, sum_e = 0, ntl = 0; LN_STAMP(t_begin); LN_RSTAMP(r_begin);)
     // LNF: at the start of a tile's LAST chunk every piece of the tile has gone through stage_store: close its statistics (the 16 threads
     // sc = 0 .. 15 of a staging row hold its 64 k of every chunk between them) and hand the registers to the next tile, whose first
     // chunk is staged during this last chunk.  stat_s is read by this tile's epilogue; the previous tile's epilogue lies behind at
@@ -850,24 +824,13 @@ __global__ __launch_bounds__(NW * 64, 2) void k_linear_b16(const LinearArgs a) {
             if (cc != nchunks - 1) return;
 #pragma unroll
             for (int j = 0; j < NP; ++j) {
-                float s1 = ln_s[j], s2 = ln_q[j];
-#pragma unroll
-                for (int o = 1; o < 16; o <<= 1) { s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
-                if (sc == 0) {
-                    const float dm = s1 / (float)K;                       // mean - pivot
-                    float var = s2 / (float)K - dm * dm;
-                    var = var > 0.f ? var : 0.f;
-                    stat_s[2 * (sr + RP * j)] = dm;
-                    stat_s[2 * (sr + RP * j) + 1] = 1.0f / sqrtf(var + a.c.ln_eps);
-                }
+                ln_close_row(ln_s[j], ln_q[j], sc, K, a.c.ln_eps, stat_s + 2 * (sr + RP * j));
                 ln_s[j] = 0.f; ln_q[j] = 0.f;
             }
         }
     };
     for (; tm < a.tiles_m; tm += tm_step) {
-#ifdef SMK_LN_STAMPS
-        LN_STAMP(t_k0);
-#endif
+        LN_STAMPS(LN_STAMP(t_k0);)
         f32x4 acc[2][8];
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb)
@@ -952,9 +915,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_linear_b16(const LinearArgs a) {
             }
         }
 
-#ifdef SMK_LN_STAMPS
-        LN_STAMP(t_k1);
-#endif
+        LN_STAMPS(LN_STAMP(t_k1);)
         // ---- epilogue: acc[nb][t][i] = token row t*16 + l16, output column ncol0 + nb*16 + 4g + i
         if (nw_ok) {
             const int row0 = tm * TM, ncol = ncol0 + 4 * g;
@@ -962,79 +923,32 @@ __global__ __launch_bounds__(NW * 64, 2) void k_linear_b16(const LinearArgs a) {
             const float4 b0 = *reinterpret_cast<const float4 *>(bias_w), b1 = *reinterpret_cast<const float4 *>(bias_w + 16);
             const bool any_ex = a.c.res || a.c.padd;
             float4 ex[2][2];
-            auto fetch_extra = [&](int t, float4 (&e)[2]) {
-                const int row = row0 + t * 16 + l16;
-                e[0] = e[1] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (row >= M) return;
-                if (a.c.padd) {                              // a tile lies inside one group (launcher: rows_per_group % 128 == 0)
-                    const int grp = row0 / a.c.rows_per_group;
-                    const int xx = row - grp * a.c.rows_per_group;
-                    int ph = xx - (int)((float)xx * (1.0f / (float)a.c.period)) * a.c.period;
-                    ph = ph < 0 ? ph + a.c.period : (ph >= a.c.period ? ph - a.c.period : ph);
-                    const float *pp = a.c.padd + ((size_t)grp * a.c.period + ph) * N + ncol;
-                    e[0] = *reinterpret_cast<const float4 *>(pp);
-                    e[1] = *reinterpret_cast<const float4 *>(pp + 16);
-                } else {
-                    const float *rp = a.c.res + (long long)row * a.c.ldr + ncol;
-                    e[0] = *reinterpret_cast<const float4 *>(rp);
-                    e[1] = *reinterpret_cast<const float4 *>(rp + 16);
-                }
-            };
-            auto finish = [&](float (&v)[4]) {
-                if (a.c.act == 1) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) v[i] = gelu_erf(v[i]);
-                } else if (a.c.act == 2) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) v[i] = v[i] > 0.f ? v[i] : 0.f;
-                }
-            };
-            if (any_ex) fetch_extra(0, ex[0]);
+            if (any_ex) fetch_extra<2, 16>(a.c, N, row0, row0 + l16, ncol, ex[0]);
 #pragma unroll
             for (int t = 0; t < 8; ++t) {
                 // loads of block t+1 before the stores of block t: vmcnt retires stores in order with loads
-                if (any_ex && t + 1 < 8) fetch_extra(t + 1, ex[(t + 1) & 1]);
+                if (any_ex && t + 1 < 8) fetch_extra<2, 16>(a.c, N, row0, row0 + (t + 1) * 16 + l16, ncol, ex[(t + 1) & 1]);
                 const int row = row0 + t * 16 + l16;
 #pragma unroll
                 for (int nb = 0; nb < 2; ++nb) {
                     const float4 bb = nb ? b1 : b0;
                     float v[4] = {acc[nb][t][0] + bb.x, acc[nb][t][1] + bb.y, acc[nb][t][2] + bb.z, acc[nb][t][3] + bb.w};
-                    if constexpr (LNF) {   // rstd ((x - p) W'^T - (mean - p) wsum) + b' for row t*16 + l16, columns nb*16 + 4g .. + 3 of the wave's 32
-                        const float dm = stat_s[2 * (t * 16 + l16)], rstd = stat_s[2 * (t * 16 + l16) + 1];
-                        const float4 wq4 = *reinterpret_cast<const float4 *>(wsum_s + wave * 32 + 4 * g + 16 * nb);
-                        v[0] = rstd * (acc[nb][t][0] - dm * wq4.x) + bb.x;
-                        v[1] = rstd * (acc[nb][t][1] - dm * wq4.y) + bb.y;
-                        v[2] = rstd * (acc[nb][t][2] - dm * wq4.z) + bb.z;
-                        v[3] = rstd * (acc[nb][t][3] - dm * wq4.w) + bb.w;
-                    }
-                    if (any_ex) {
-                        const float4 eq = ex[t & 1][nb];
-                        if (a.c.padd) { v[0] += eq.x; v[1] += eq.y; v[2] += eq.z; v[3] += eq.w; }
-                        finish(v);
-                        if (!a.c.padd) { v[0] = eq.x + v[0]; v[1] = eq.y + v[1]; v[2] = eq.z + v[2]; v[3] = eq.w + v[3]; }
-                    } else {
-                        finish(v);
-                    }
-                    if (row < M) {
-                        const bool sp = a.c.split_from >= 0 && ncol + 16 * nb >= a.c.split_from;  // wave-uniform (split_from % 32 == 0)
-                        *reinterpret_cast<float4 *>(a.c.y + (long long)row * a.c.ldy + ncol + 16 * nb) = sp ? split4_inplace(v) : make_float4(v[0], v[1], v[2], v[3]);
-                    }
+                    if constexpr (LNF)     // row t*16 + l16, columns nb*16 + 4g .. + 3 of the wave's 32
+                        ln_finish(v, make_float4(acc[nb][t][0], acc[nb][t][1], acc[nb][t][2], acc[nb][t][3]), stat_s + 2 * (t * 16 + l16),
+                                  wsum_s + wave * 32 + 4 * g + 16 * nb, bb);
+                    if (any_ex) activate_extra(a.c, v, ex[t & 1][nb]);
+                    else activate(a.c.act, v);
+                    if (row < M) store4_split_from(a.c.y + (long long)row * a.c.ldy + ncol + 16 * nb, v, ncol + 16 * nb, a.c.split_from);
                 }
             }
         }
-#ifdef SMK_LN_STAMPS
-        LN_STAMP(t_e);
-        sum_k += t_k1 - t_k0; sum_e += t_e - t_k1; ++ntl;
-#endif
+        LN_STAMPS(LN_STAMP(t_e); sum_k += t_k1 - t_k0; sum_e += t_e - t_k1; ++ntl;)
     }
-#ifdef SMK_LN_STAMPS
-    LN_STAMP(t_end);
-    LN_RSTAMP(r_end);
-    if (a.stamps && lane == 0) {
-        unsigned long long *rec = a.stamps + (((size_t)blockIdx.x * NW + wave) & 4095) * 8;
-        rec[0] = sum_k; rec[1] = sum_e; rec[2] = t_end - t_begin; rec[3] = r_end - r_begin; rec[4] = ntl; rec[5] = 0; rec[6] = 0; rec[7] = 0;
-    }
-#endif
+    LN_STAMPS(LN_STAMP(t_end); LN_RSTAMP(r_end);
+              if (a.stamps && lane == 0) {
+                  unsigned long long *rec = a.stamps + (((size_t)blockIdx.x * NW + wave) & 4095) * 8;
+                  rec[0] = sum_k; rec[1] = sum_e; rec[2] = t_end - t_begin; rec[3] = r_end - r_begin; rec[4] = ntl; rec[5] = 0; rec[6] = 0; rec[7] = 0;
+              })
 }
 
 template <int NW, int CONV = 0, int R = 2, bool LNF = false>
@@ -1043,184 +957,170 @@ static hipError_t launch_b16(const LinearArgs &a, hipStream_t st) {
     once_per_device((const void *)k_linear_b16<NW, CONV, R, LNF>, [&] {
         (void)hipFuncSetAttribute((const void *)k_linear_b16<NW, CONV, R, LNF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     });
-    const int nwg_max = (NW == 8 ? 1 : 2) * a.num_cu;        // 8 waves per CU either way
-    const long long tiles = (long long)a.tiles_m * a.tiles_n;
-    long long nwg = tiles < nwg_max ? tiles : nwg_max;
-    nwg -= nwg % a.tiles_n;                                  // every workgroup keeps one column tile
-    if (nwg < a.tiles_n) nwg = a.tiles_n;
     LinearArgs b = a;
-    static int swz_env = -1;
-    if (swz_env < 0) { const char *s = getenv("SMK_LINEAR_SWZ"); swz_env = s ? atoi(s) : 1; }
-    b.swz = swz_env && nwg % (8 * a.tiles_n) == 0;
-    hipLaunchKernelGGL((k_linear_b16<NW, CONV, R, LNF>), dim3((unsigned)nwg), dim3(NW * 64), lds, st, b);
+    const unsigned nwg = linear_grid(b, NW == 8 ? 1 : 2);
+    hipLaunchKernelGGL((k_linear_b16<NW, CONV, R, LNF>), dim3(nwg), dim3(NW * 64), lds, st, b);
     return hipGetLastError();
 }
 
-// 3 x 3 x 3 Conv3d of a channels-last 64-channel slab as an implicit GEMM on the layer kernel (K = 27 x 64; weights in the layer layout,
-// column tap * 64 + c): rows = the voxels of planes z_off .. z_off + nz - 1 of the slab [Dl][H][W][64]; y [nz H W][N] + bias, activation
+// The implicit-GEMM convolutions' arguments: rows = the voxels of planes z_off .. z_off + nz - 1 of the slab; y [nz H W][N] + bias, activation
+static LinearArgs conv3d_args(const LinearDev &l, const float *slab, int Dl, int H, int W, int z_off, int nz, float *y, long long ldy, int act, int nw) {
+    LinearArgs a{};
+    a.l = l;
+    a.c.x = slab; a.c.ldx = 64; a.c.y = y; a.c.ldy = ldy; a.c.rows_per_group = 1; a.c.period = 1;
+    a.c.M = nz * H * W; a.c.act = act;
+    a.cDl = Dl; a.cH = H; a.cW = W; a.cz_off = z_off;
+    a.num_cu = device_num_cu();
+    a.tiles_n = cdiv(l.N, nw * 32);
+    a.tiles_m = cdiv(a.c.M, 128);
+    return a;
+}
+
+// 3 x 3 x 3 Conv3d of a channels-last 64-channel slab [Dl][H][W][64] as an implicit GEMM on the layer kernel (K = 27 x 64; weights in the layer
+// layout, column tap * 64 + c)
 hipError_t launch_conv3d_cl_b16(const LinearDev &l, const float *slab, int Dl, int H, int W, int z_off, int nz, float *y, long long ldy, int act,
                                 hipStream_t st) {
     if (l.K != 27 * 64 || H > 1023 || W > 1023 || Dl > 1022 || (long long)Dl * H * W * 256 >= (1LL << 32) - 256) return hipErrorInvalidValue;
-    LinearArgs a{};
-    a.l = l;
-    a.c.x = slab; a.c.ldx = 64; a.c.y = y; a.c.ldy = ldy; a.c.res = nullptr; a.c.ldr = 0; a.c.padd = nullptr; a.c.rows_per_group = 1; a.c.period = 1;
-    a.c.M = nz * H * W; a.c.act = act; a.c.x_split = 0; a.c.y_split = 0; a.c.nseg = 1;
-    a.cDl = Dl; a.cH = H; a.cW = W; a.cz_off = z_off;
-    a.num_cu = device_num_cu();
-    a.stamps = nullptr; a.dbg = 0; a.swz = 0; a.stagger = 0; a.stagger_unit = 0;
-    const int nw = (l.N >= 256 && (long long)cdiv(a.c.M, 128) * cdiv(l.N, 256) >= a.num_cu) ? 8 : 4;
-    a.tiles_n = cdiv(l.N, nw * 32);
-    a.tiles_m = cdiv(a.c.M, 128);
+    const int nw = (l.N >= 256 && (long long)cdiv(nz * H * W, 128) * cdiv(l.N, 256) >= device_num_cu()) ? 8 : 4;
+    const LinearArgs a = conv3d_args(l, slab, Dl, H, W, z_off, nz, y, ldy, act, nw);
     return nw == 8 ? launch_b16<8, 1>(a, st) : launch_b16<4, 1>(a, st);
 }
 
 // 7 x 7 x 7 Conv3d of a scalar slab [Dl][H][W] -> N channels as an implicit GEMM (k_linear_b16<4, 2>): weights = a layer handle with
-// K = 448, column (kz * 7 + ky) * 8 + kx (slot kx = 7 and rows >= 49 zero); rows = the voxels of planes z_off .. z_off + nz - 1
+// K = 448, column (kz * 7 + ky) * 8 + kx (slot kx = 7 and rows >= 49 zero)
 hipError_t launch_conv3d_s7_b16(const LinearDev &l, const float *slab, int Dl, int H, int W, int z_off, int nz, float *y, long long ldy, int act,
                                 hipStream_t st) {
     if (l.K != 448 || H > 1023 || W > 1023 || Dl > 1022 || (long long)Dl * H * W * 4 >= (1LL << 32) - 256) return hipErrorInvalidValue;
-    LinearArgs a{};
-    a.l = l;
-    a.c.x = slab; a.c.ldx = 64; a.c.y = y; a.c.ldy = ldy; a.c.res = nullptr; a.c.ldr = 0; a.c.padd = nullptr; a.c.rows_per_group = 1; a.c.period = 1;
-    a.c.M = nz * H * W; a.c.act = act; a.c.x_split = 0; a.c.y_split = 0; a.c.nseg = 1;
-    a.cDl = Dl; a.cH = H; a.cW = W; a.cz_off = z_off;
-    a.num_cu = device_num_cu();
-    a.stamps = nullptr; a.dbg = 0; a.swz = 0; a.stagger = 0; a.stagger_unit = 0;
-    a.tiles_n = cdiv(l.N, 128);
-    a.tiles_m = cdiv(a.c.M, 128);
-    return launch_b16<4, 2>(a, st);
+    return launch_b16<4, 2>(conv3d_args(l, slab, Dl, H, W, z_off, nz, y, ldy, act, 4), st);
 }
 
+// ---- which kernel a layer call runs, and on what tile: decided in plan_linear, launched by launch_plan
+struct LinearPlan {
+    bool b16;             // k_linear_b16 (16x16x32 MFMAs, 128-row tiles, fp32 in and out) or k_linear_x3 (32x32x16)
+    int mb, nw;           // tile = 32 mb rows x 32 nw columns
+    bool as;              // x3: the activations arrive split (LinearCall::x_split)
+    int ks;               // x3: wave groups that share a tile's K range
+    int ring;             // weight ring: x3 in 16-k steps (4 | 16), b16 in 32-k steps (2 | 4)
+    bool lnf;             // LayerNorm fused in front (LinearCall::ln_wsum)
+    int tiles_m, tiles_n;
+};
+
+// false: no kernel serves the call.  No side effects; k only overrides (A/B runs, tests).
+static bool plan_linear(const LinearDev &l, const LinearCall &c, int num_cu, const LinearKnobs &k, LinearPlan &p) {
+    p = LinearPlan{};
+    p.lnf = c.ln_wsum != nullptr;
+    p.as = c.x_split != 0;
+    if (p.lnf && (c.x_split || c.y_split || c.nseg != 1 || c.res)) return false;       // fused LayerNorm: fp32 rows in and out, no residual
+    if (c.padd && c.rows_per_group % 32 != 0) return false;                             // a tile lies inside one group of the periodic addend
+    // 8-wave workgroups (128 x 256 tile) halve the per-MFMA staging work (split arithmetic, LDS writes) and the re-reads of A; 4-wave ones
+    // (x 128) serve narrow layers and small problems (more workgroups).  8 waves from one round of 128 x 256 tiles on; the fused-LayerNorm
+    // layers from three quarters of a round on: the q | k | v layer at batch 4 is 192 such tiles -- ONE round on 75 % of the CUs, 34 us -- against
+    // three rounds of 64 x 128 tiles on k_linear_x3, 40 us (measured: 1.160 -> 1.111 ms per batch-4 forward)
+    const long long tiles8 = (long long)cdiv(c.M, 128) * cdiv(l.N, 256) * c.nseg;
+    int nw = (l.N >= 256 && (p.lnf ? 4 * tiles8 >= 3LL * num_cu : tiles8 >= num_cu)) ? 8 : 4;
+    if (k.nw == 4 || k.nw == 8) nw = k.nw;
+    // Row blocks per tile: the largest that still gives every CU its share of workgroups (small M: finer tiles) -- ONE workgroup per CU (measured
+    // round 4: batch 4 0.284 -> 0.276 ms per frame, batch 2 0.382 -> 0.375, larger batches unchanged: 64-row tiles at one workgroup per CU beat
+    // 32-row tiles at two), two for the fused-LayerNorm layers.  The 8-wave form is built for full 128-row tiles only.
+    const long long want = (p.lnf ? 2LL : 1LL) * num_cu;
+    int mb = 4;
+    while (nw != 8 && mb > 1 && (long long)cdiv(c.M, 32 * mb) * cdiv(l.N, nw * 32) * c.nseg < want) mb >>= 1;
+    if (k.mb == 1 || k.mb == 2 || k.mb == 4) mb = k.mb;
+    if (nw == 8 && mb != 4) {              // (only a forced MB: the plain layer keeps its 8 waves, the fused-LayerNorm one the forced rows)
+        if (p.lnf) nw = 4;
+        else mb = 4;
+    }
+    if (c.padd) {
+        if (nw == 8 && c.rows_per_group % 128 != 0) nw = 4;
+        while (mb > 1 && c.rows_per_group % (32 * mb) != 0) mb >>= 1;
+    }
+    p.nw = nw; p.mb = mb; p.ks = 1;
+    p.tiles_n = cdiv(l.N, nw * 32);
+    p.tiles_m = cdiv(c.M, 32 * mb);
+    const long long tiles = (long long)p.tiles_m * p.tiles_n * c.nseg;
+    const int nch = l.K / 64;
+    // Full 128-row tiles of fp32 activations: the 16x16x32-shape kernel, its weight ring 4 deep when the 64-k chunks pair up (the fused-LayerNorm
+    // form exists 2 deep only, and only for paired chunks).  (With a periodic addend mb == 4 means whole groups of 128 rows: the loop above.)
+    const bool paired = nch % 2 == 0 && l.K >= 128;
+    if (k.shape != 32 && mb == 4 && !c.x_split && !c.y_split && c.nseg == 1 && (paired || !p.lnf)) {
+        p.b16 = true;
+        p.ring = (paired && !p.lnf) ? 4 : 2;
+        return true;
+    }
+    p.ring = LN_RING;
+    const bool splits = !p.as && !p.lnf;       // the split-K forms: plain layers on fp32 activations
+    // 64-row tiles that leave every CU's second workgroup slot empty (batch 4: 256 tiles): two wave groups per workgroup split the K
+    // range instead (8 waves per CU either way; the serial K loop, which is what such a launch waits for, is half as long)
+    // (measured at M = 4,096: 2048 -> 512 33.3 -> 30.8 us; 512 -> 512 12.6 -> 13.5 us, where the merge outweighs four chunks less: K >= 2,048 only)
+    if (mb == 2 && splits && tiles <= num_cu && nch % 2 == 0 && l.K >= 2048) p.ks = 2;
+    if (mb == 1 && splits) {
+        // few 32 x 128 tiles (batch 1: 128 for the 2048 -> 512 layer): split K over 4 wave groups per workgroup
+        // (measured at M = 1024: 2048 -> 512 (128 tiles, 32 chunks) 24.4 -> 19.3 us with 4 groups; neutral at 8 chunks; with
+        // 512 tiles already on the chip a split only adds the merge (+15 %))
+        if (tiles <= num_cu / 2 && nch % 4 == 0 && nch >= 16) p.ks = 4;
+        if (k.ks == 1 || ((k.ks == 2 || k.ks == 4) && nch % k.ks == 0 && nch / k.ks >= 1)) p.ks = k.ks;
+    }
+    // One 32-row tile per workgroup (a single frame's layers, fp32 activations): the deep weight ring (see k_linear_x3) when K allows it
+    // (not with several wave groups: 1,024 threads leave 128 registers per wave, and the 16-slot ring then spills)
+    if (mb == 1 && !p.as && p.ks == 1 && nch % 4 == 0 && tiles <= 2 * num_cu) p.ring = 16;
+    return true;
+}
+
+constexpr int x3_key(int mb, int nw, bool as, int ks, int ring, bool lnf) { return ((((mb * 16 + nw) * 2 + as) * 8 + ks) * 32 + ring) * 2 + lnf; }
+
+// the plan's instantiation; hipErrorInvalidValue for a combination that has none
+static hipError_t launch_plan(const LinearPlan &p, LinearArgs &a, hipStream_t st) {
+    a.tiles_m = p.tiles_m;
+    a.tiles_n = p.tiles_n;
+    if (p.b16) {
+        if (p.lnf) return p.ring != 2 ? hipErrorInvalidValue : p.nw == 8 ? launch_b16<8, 0, 2, true>(a, st) : launch_b16<4, 0, 2, true>(a, st);
+        if (p.ring == 4) return p.nw == 8 ? launch_b16<8, 0, 4>(a, st) : launch_b16<4, 0, 4>(a, st);
+        return p.nw == 8 ? launch_b16<8>(a, st) : launch_b16<4>(a, st);
+    }
+#define SMK_X3(MB, NW, AS, KS, RING, LNF) case x3_key(MB, NW, AS, KS, RING, LNF): return launch_mb<MB, NW, AS, KS, RING, LNF>(a, st)
+    switch (x3_key(p.mb, p.nw, p.as, p.ks, p.ring, p.lnf)) {
+        SMK_X3(4, 8, false, 1, 4, false); SMK_X3(4, 4, false, 1, 4, false); SMK_X3(2, 4, false, 1, 4, false); SMK_X3(1, 4, false, 1, 4, false);
+        SMK_X3(2, 4, false, 2, 4, false); SMK_X3(1, 4, false, 2, 4, false); SMK_X3(1, 4, false, 4, 4, false); SMK_X3(1, 4, false, 1, 16, false);
+        SMK_X3(4, 8, true, 1, 4, false);  SMK_X3(4, 4, true, 1, 4, false);  SMK_X3(2, 4, true, 1, 4, false);  SMK_X3(1, 4, true, 1, 4, false);
+        SMK_X3(4, 8, false, 1, 4, true);  SMK_X3(4, 4, false, 1, 4, true);  SMK_X3(2, 4, false, 1, 4, true);  SMK_X3(1, 4, false, 1, 4, true);
+        SMK_X3(1, 4, false, 1, 16, true);
+    }
+#undef SMK_X3
+    return hipErrorInvalidValue;
+}
+
+LN_STAMPS(
+static unsigned long long *stamps_buffer(hipStream_t st) {
+    static unsigned long long *buf = nullptr;
+    if (!buf) (void)hipMalloc((void **)&buf, 8 * 8 * 4096);
+    (void)hipMemsetAsync(buf, 0, 8 * 8 * 4096, st);
+    return buf;
+}
+// wait, print the per-wave averages (cycles per tile; clock = core cycles / 100 MHz ticks)
+static void stamps_print(const LinearArgs &a, const LinearPlan &p, hipStream_t st) {
+    if (!getenv("SMK_LN_STAMPS_PRINT")) return;
+    static unsigned long long h[8 * 4096];
+    (void)hipStreamSynchronize(st);
+    (void)hipMemcpy(h, a.stamps, sizeof(h), hipMemcpyDeviceToHost);
+    double k = 0, ep = 0, tot = 0, real = 0, nt = 0, us[5] = {0, 0, 0, 0, 0}; int n = 0;
+    for (int w = 0; w < 4096; ++w) if (h[w * 8 + 4]) { ++n; k += h[w*8]; ep += h[w*8+1]; tot += h[w*8+2]; real += h[w*8+3]; nt += h[w*8+4];
+        us[0] += h[w*8+5] & 0xffffffffULL; us[1] += h[w*8+5] >> 32; us[2] += h[w*8+6] & 0xffffffffULL; us[3] += h[w*8+6] >> 32; us[4] += h[w*8+7]; }
+    const double nch = nt * (a.l.K / 64);
+    if (n) fprintf(stderr, "LN_KSTEPS per chunk: k0 %.0f k1 %.0f k2 %.0f k3(incl barrier) %.0f barrier %.0f\n", us[0] / nch, us[1] / nch, us[2] / nch, us[3] / nch, us[4] / nch);
+    if (n) fprintf(stderr, "LN_STAMPS M=%d K=%d N=%d mb=%d nw=%d split=%d waves=%d tiles/wave=%.1f | per tile: kloop %.0f epilogue %.0f | wave total %.0f cyc = %.1f us, clock %.0f MHz\n",
+                   a.c.M, a.l.K, a.l.N, p.mb, p.nw, a.c.x_split, n, nt / n, k / nt, ep / nt, tot / n, real / n / 100.0, tot / real * 100.0);
+})
+
 hipError_t launch_linear_x3(const LinearDev &l, const LinearCall &c, hipStream_t st) {
-    const int num_cu = device_num_cu();
-    LinearArgs a;
+    LinearArgs a{};
     a.l = l;
     a.c = c;
-    // 8-wave workgroups (128 x 256 tile) halve the per-MFMA staging work (split arithmetic, LDS writes) and the re-reads of A;
-    // 4-wave ones (x 128) serve narrow layers and small problems (more workgroups)
-    static int force_mb = -1, force_nw = -1;
-    if (force_mb < 0) { const char *s = getenv("SMK_LINEAR_MB"); force_mb = s ? atoi(s) : 0; }
-    if (force_nw < 0) { const char *s = getenv("SMK_LINEAR_NW"); force_nw = s ? atoi(s) : 0; }
-    static int dbg = -1;
-#ifdef SMK_LN_DIAG
-    if (dbg < 0) { const char *s = getenv("SMK_LINEAR_DBG"); dbg = s ? atoi(s) : 0; }
-#else
-    dbg = 0;
-#endif
-    a.dbg = dbg;
-    a.num_cu = num_cu;
-    a.swz = 0;
-    a.stagger = 0;
-    a.stamps = nullptr;
-    if (c.ln_wsum) {   // LayerNorm fused in front (k_linear_x3<.., LNF>): the tile shapes of the plain layer
-        if (c.x_split || c.y_split || c.nseg != 1 || c.res || (c.padd && c.rows_per_group % 32 != 0)) return hipErrorInvalidValue;
-        // 128 x 256 tiles (k_linear_b16<8>) from three quarters of a round on: the q | k | v layer at batch 4 is 192 such tiles -- ONE round on 75 %
-        // of the CUs, 34 us -- against three rounds of 64 x 128 tiles on k_linear_x3, 40 us (measured: 1.160 -> 1.111 ms per batch-4 forward)
-        int nwl = (l.N >= 256 && (long long)cdiv(c.M, 128) * cdiv(l.N, 256) * 4 >= 3LL * num_cu) ? 8 : 4;
-        if (force_nw == 4 || force_nw == 8) nwl = force_nw;
-        int mbl = 4;
-        // (the 8-wave form is built for 128-row tiles: chosen above, it keeps them)
-        while (nwl != 8 && mbl > 1 && (long long)cdiv(c.M, 32 * mbl) * cdiv(l.N, nwl * 32) < 2LL * num_cu) mbl >>= 1;
-        if (force_mb == 1 || force_mb == 2 || force_mb == 4) mbl = force_mb;
-        if (nwl == 8 && (mbl != 4 || (c.padd && c.rows_per_group % 128 != 0))) { nwl = 4; }
-        while (c.padd && mbl > 1 && c.rows_per_group % (32 * mbl) != 0) mbl >>= 1;
-        a.tiles_n = cdiv(l.N, nwl * 32);
-        a.tiles_m = cdiv(c.M, 32 * mbl);
-        // full 128-row tiles: the 16x16x32-shape kernel, as for the plain layer (SMK_LINEAR_SHAPE=32 keeps the 32x32x16 one)
-        static int shape_ln = -1;
-        if (shape_ln < 0) { const char *sv = getenv("SMK_LINEAR_SHAPE"); shape_ln = sv ? atoi(sv) : 16; }
-        if (shape_ln != 32 && mbl == 4 && (!c.padd || c.rows_per_group % 128 == 0) && (l.K / 64) % 2 == 0 && l.K >= 128)
-            return nwl == 8 ? launch_b16<8, 0, 2, true>(a, st) : launch_b16<4, 0, 2, true>(a, st);
-        if (nwl == 8) return launch_mb<4, 8, false, 1, LN_RING, true>(a, st);
-        if (mbl == 4) return launch_mb<4, 4, false, 1, LN_RING, true>(a, st);
-        if (mbl == 2) return launch_mb<2, 4, false, 1, LN_RING, true>(a, st);
-        // one 32-row tile per workgroup (a single frame): the deep weight ring when K allows it
-        const bool one = (long long)a.tiles_m * a.tiles_n <= 2LL * num_cu;
-        return (one && (l.K / 64) % 4 == 0) ? launch_mb<1, 4, false, 1, 16, true>(a, st) : launch_mb<1, 4, false, 1, LN_RING, true>(a, st);
-    }
-    int nw = (l.N >= 256 && (long long)cdiv(c.M, 128) * cdiv(l.N, 256) * c.nseg >= num_cu) ? 8 : 4;
-    if (force_nw == 4 || force_nw == 8) nw = force_nw;
-    a.tiles_n = cdiv(l.N, nw * 32);
-    // row-block count per tile: the largest that still gives every CU its share of workgroups (small M: finer tiles)
-    static int want_env = -1;
-    // workgroups per CU the tile choice aims at: 1 (measured round 4: batch 4 0.284 -> 0.276 ms per frame, batch 2 0.382 -> 0.375, larger
-    // batches unchanged -- 64-row tiles at one workgroup per CU beat 32-row tiles at two); SMK_LINEAR_WANT=2 restores round 3's rule
-    if (want_env < 0) { const char *sv = getenv("SMK_LINEAR_WANT"); want_env = sv ? atoi(sv) : 1; }
-    const long long want = (nw == 8 ? 1LL : (long long)want_env) * num_cu;
-    int mb = 4;
-    while (mb > 1 && (long long)cdiv(c.M, 32 * mb) * a.tiles_n * c.nseg < want) mb >>= 1;
-    if (force_mb == 1 || force_mb == 2 || force_mb == 4) mb = force_mb;
-    if (nw == 8) mb = 4;                                   // the 8-wave form is built for full 128-row tiles only
-    while (c.padd && mb > 1 && c.rows_per_group % (32 * mb) != 0) mb >>= 1;
-    if (c.padd && c.rows_per_group % (32 * mb) != 0) return hipErrorInvalidValue;   // api.hip checks rows_per_group % 32 == 0
-    if (c.padd && nw == 8 && mb != 4) { nw = 4; a.tiles_n = cdiv(l.N, 128); }
-    a.tiles_m = cdiv(c.M, 32 * mb);
-#ifdef SMK_LN_STAMPS
-    static unsigned long long *stamp_buf = nullptr;
-    if (!stamp_buf) (void)hipMalloc((void **)&stamp_buf, 8 * 8 * 4096);
-    (void)hipMemsetAsync(stamp_buf, 0, 8 * 8 * 4096, st);
-    a.stamps = stamp_buf;
-#endif
-    hipError_t e;
-    // full 128-row tiles of fp32 activations: the 16x16x32-shape kernel (SMK_LINEAR_SHAPE=32 keeps the 32x32x16 one for A/B runs)
-    static int shape_env = -1;
-    if (shape_env < 0) { const char *s = getenv("SMK_LINEAR_SHAPE"); shape_env = s ? atoi(s) : 16; }
-    if (shape_env != 32 && mb == 4 && !c.x_split && !c.y_split && c.nseg == 1 && !dbg && (!c.padd || c.rows_per_group % 128 == 0)) {
-        static int ring_env = -1;
-        if (ring_env < 0) { const char *s = getenv("SMK_LINEAR_RING"); ring_env = s ? atoi(s) : 4; }
-        if (ring_env == 4 && (l.K / 64) % 2 == 0 && l.K >= 128) e = nw == 8 ? launch_b16<8, 0, 4>(a, st) : launch_b16<4, 0, 4>(a, st);
-        else e = nw == 8 ? launch_b16<8>(a, st) : launch_b16<4>(a, st);
-    } else if (c.x_split) {
-        if (nw == 8) e = launch_mb<4, 8, true>(a, st);
-        else if (mb == 4) e = launch_mb<4, 4, true>(a, st);
-        else if (mb == 2) e = launch_mb<2, 4, true>(a, st);
-        else e = launch_mb<1, 4, true>(a, st);
-    } else {
-        static int ks2_env = -1;
-        if (ks2_env < 0) { const char *sv = getenv("SMK_LINEAR_KS2"); ks2_env = sv ? atoi(sv) : 1; }
-        if (nw == 8) e = launch_mb<4, 8, false>(a, st);
-        else if (mb == 4) e = launch_mb<4, 4, false>(a, st);
-        // 64-row tiles that leave every CU's second workgroup slot empty (batch 4: 256 tiles): two wave groups per workgroup split the K
-        // range instead (8 waves per CU either way; the serial K loop, which is what such a launch waits for, is half as long)
-        // (measured at M = 4,096: 2048 -> 512 33.3 -> 30.8 us; 512 -> 512 12.6 -> 13.5 us, where the merge outweighs four chunks less: K >= 2,048 only)
-        else if (mb == 2 && ks2_env && (long long)a.tiles_m * a.tiles_n * c.nseg <= num_cu && (l.K / 64) % 2 == 0 && l.K >= 2048)
-            e = launch_mb<2, 4, false, 2>(a, st);
-        else if (mb == 2) e = launch_mb<2, 4, false>(a, st);
-        else {
-            // few 32 x 128 tiles (batch 1: 128 for the 2048 -> 512 layer): split K over 2 or 4 wave groups per workgroup
-            static int force_ks = -1;
-            if (force_ks < 0) { const char *sv = getenv("SMK_LINEAR_KS"); force_ks = sv ? atoi(sv) : 0; }
-            const long long tiles = (long long)a.tiles_m * a.tiles_n;
-            const int nch = l.K / 64;
-            int ks = 1;
-            // measured at M = 1024: 2048 -> 512 (128 tiles, 32 chunks) 24.4 -> 19.3 us with 4 groups; neutral at 8 chunks; with
-            // 512 tiles already on the chip a split only adds the merge (+15 %)
-            if (tiles * c.nseg <= num_cu / 2 && nch % 4 == 0 && nch >= 16) ks = 4;
-            if (force_ks == 1 || ((force_ks == 2 || force_ks == 4) && nch % force_ks == 0 && nch / force_ks >= 1)) ks = force_ks;
-            // one tile per workgroup (a single frame's layers): the deep weight ring (see k_linear_x3) when K allows it
-            static int deep = -1;
-            if (deep < 0) { const char *sv = getenv("SMK_LINEAR_DEEP"); deep = sv ? atoi(sv) : 1; }
-            const bool dr = deep && (nch / ks) % 4 == 0 && tiles * c.nseg <= 2 * num_cu;
-            // (not with four wave groups: 1,024 threads leave 128 registers per wave, and the 16-slot ring then spills)
-            if (ks == 4) e = launch_mb<1, 4, false, 4>(a, st);
-            else if (ks == 2) e = launch_mb<1, 4, false, 2>(a, st);
-            else e = dr ? launch_mb<1, 4, false, 1, 16>(a, st) : launch_mb<1, 4, false>(a, st);
-        }
-    }
-#ifdef SMK_LN_STAMPS
-    if (getenv("SMK_LN_STAMPS_PRINT")) {   // diagnostic: wait, print the per-wave averages (cycles per tile; clock = core cycles / 100 MHz ticks)
-        static unsigned long long h[8 * 4096];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(h, a.stamps, sizeof(h), hipMemcpyDeviceToHost);
-        double k = 0, ep = 0, tot = 0, real = 0, nt = 0, us[5] = {0, 0, 0, 0, 0}; int n = 0;
-        for (int w = 0; w < 4096; ++w) if (h[w * 8 + 4]) { ++n; k += h[w*8]; ep += h[w*8+1]; tot += h[w*8+2]; real += h[w*8+3]; nt += h[w*8+4];
-            us[0] += h[w*8+5] & 0xffffffffULL; us[1] += h[w*8+5] >> 32; us[2] += h[w*8+6] & 0xffffffffULL; us[3] += h[w*8+6] >> 32; us[4] += h[w*8+7]; }
-        const double nch = nt * (l.K / 64);
-        if (n) fprintf(stderr, "LN_KSTEPS per chunk: k0 %.0f k1 %.0f k2 %.0f k3(incl barrier) %.0f barrier %.0f\n", us[0] / nch, us[1] / nch, us[2] / nch, us[3] / nch, us[4] / nch);
-        if (n) fprintf(stderr, "LN_STAMPS M=%d K=%d N=%d mb=%d nw=%d split=%d waves=%d tiles/wave=%.1f | per tile: kloop %.0f epilogue %.0f | wave total %.0f cyc = %.1f us, clock %.0f MHz\n",
-                       c.M, l.K, l.N, mb, nw, c.x_split, n, nt / n, k / nt, ep / nt, tot / n, real / n / 100.0, tot / real * 100.0);
-    }
-#endif
+    a.num_cu = device_num_cu();
+    LinearPlan p;
+    if (!plan_linear(l, c, a.num_cu, knobs(), p)) return hipErrorInvalidValue;
+    LN_STAMPS(a.stamps = stamps_buffer(st);)
+    const hipError_t e = launch_plan(p, a, st);
+    LN_STAMPS(stamps_print(a, p, st);)
     return e;
 }
 
@@ -1466,8 +1366,7 @@ __global__ __launch_bounds__(256, 2) void k_linear_wgrad_tr(WgradTrArgs a) {
 struct WgradTrPlan { bool ok; int nseg, tiles_m, tiles_n; long long rows_per_seg; size_t bytes; };
 static WgradTrPlan plan_wgrad_tr(long long rows, int out_f, int in_f, long long ld_dy, long long ldx) {
     WgradTrPlan p{};
-    static const bool off = [] { const char *e = getenv("SMK_LINEAR_WGRAD_TR"); return e && e[0] == '0'; }();
-    p.ok = !off && out_f % 128 == 0 && in_f % 128 == 0 && ld_dy % 4 == 0 && ldx % 4 == 0 && rows >= 32;
+    p.ok = knobs().wgrad_tr && out_f % 128 == 0 && in_f % 128 == 0 && ld_dy % 4 == 0 && ldx % 4 == 0 && rows >= 32;
     if (!p.ok) return p;
     p.tiles_m = out_f / 128; p.tiles_n = in_f / 128;
     const int tiles = p.tiles_m * p.tiles_n;

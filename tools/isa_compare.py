@@ -7,6 +7,10 @@ For every kernel of the old files: registers, scratch, LDS and occupancy as the 
 v_mfma*, ds_read_b128 and buffer_load_dwordx4, whether the whole instruction stream is identical (labels renumbered), and whether
 every K-loop block (a basic block that holds v_mfma and ends in a backward branch) has the same mnemonic sequence.
 Exit status 1 if a kernel is missing, a K-loop block differs, or scratch / occupancy / LDS / an instruction count changed.
+
+--mfma-blocks adds a column for kernels whose K loop spans several basic blocks (csrc/linear.hip: the chunk loop of k_linear_x3 /
+k_linear_b16 is not one block, so the K-loop column reads "none" for them): the ordered mnemonic sequences of EVERY basic block that
+holds a v_mfma, old against new; a difference is exit status 1 as well.
 """
 import argparse, re, sys
 
@@ -38,8 +42,9 @@ def kernels(path):
     return out
 
 
-def kloops(body):
-    """Mnemonic sequences of the blocks that hold v_mfma and end in a branch to their own or an earlier label."""
+def mfma_blocks(body, loops_only):
+    """Mnemonic sequences of the basic blocks that hold v_mfma, in order; loops_only: just those that end in a branch to their own or an
+    earlier label."""
     blocks, seen, cur, label = [], {}, [], None
     for l in body + [".LBB_end:"]:
         if l.endswith(":"):
@@ -53,7 +58,7 @@ def kloops(body):
         if not ins or not any(i.startswith("v_mfma") for i in ins):
             continue
         m = re.match(r"s_cbranch\w*\s+(\S+)", ins[-1]) or re.match(r"s_branch\s+(\S+)", ins[-1])
-        if m and m.group(1) in seen and seen[m.group(1)] <= idx:
+        if not loops_only or (m and m.group(1) in seen and seen[m.group(1)] <= idx):
             res.append([i.split()[0] for i in ins])
     return res
 
@@ -62,6 +67,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--old", nargs="+", required=True)
     ap.add_argument("--new", nargs="+", required=True)
+    ap.add_argument("--mfma-blocks", action="store_true", help="also compare every basic block that holds a v_mfma")
     a = ap.parse_args()
     old, new = {}, {}
     for p in a.old:
@@ -70,7 +76,7 @@ def main():
         new.update(kernels(p))
     bad = 0
     print("kernel | vgpr old/new | sgpr old/new | scratch | lds | occupancy | mfma ds_read_b128 buffer_load_x4 | instructions old/new | "
-          "stream | K-loop blocks")
+          "stream | K-loop blocks" + (" | MFMA blocks" if a.mfma_blocks else ""))
     for name in sorted(old):
         if name not in new:
             print(f"{name} | MISSING in new")
@@ -79,10 +85,15 @@ def main():
         (bo, mo), (bn, mn) = old[name], new[name]
         co = [sum(i.startswith(c) for i in bo) for c in COUNTED]
         cn = [sum(i.startswith(c) for i in bn) for c in COUNTED]
-        ko, kn = kloops(bo), kloops(bn)
+        ko, kn = mfma_blocks(bo, True), mfma_blocks(bn, True)
         same = bo == bn
         kl = "none" if not ko and not kn else f"{len(ko)} {'same' if ko == kn else 'DIFFER'}"
         ok = all(mo.get(k) == mn.get(k) for k in ("scratch", "occ", "lds")) and co == cn and ko == kn
+        if a.mfma_blocks:
+            ao, an = mfma_blocks(bo, False), mfma_blocks(bn, False)
+            nd = sum(x != y for x, y in zip(ao, an)) + abs(len(ao) - len(an))
+            kl += " | " + ("none" if not ao and not an else f"{len(ao)} same" if not nd else f"{len(ao)}/{len(an)} {nd} DIFFER")
+            ok = ok and not nd
         bad += not ok
         pair = lambda k: f"{mo.get(k)}/{mn.get(k)}" if mo.get(k) != mn.get(k) else f"{mo.get(k)}"
         print(f"{name} | {mo.get('vgpr')}/{mn.get('vgpr')} | {mo.get('sgpr')}/{mn.get('sgpr')} | {pair('scratch')} | {pair('lds')} | "
