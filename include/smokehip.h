@@ -282,8 +282,13 @@ int smk_encoder_destroy(smk_encoder *enc);
 
 /* SmokePhysNet.input_encoder + both adaptive pools (smokephys_net.py:87-91):
  * frames [B][H][W] fp32 (row pitch W, frame stride frame_stride floats) -> features [B][128][32][32] fp32.
- * Requires H == W, H % 32 == 0, and input_dim a multiple/divisor of H (then the two pools compose to an
- * (H/32)^2 block mean); anything else returns SMK_ERR_UNSUPPORTED.
+ * Requires H == W in {64, 128, 256, 512, 1024}, and input_dim a multiple of 32 that is a multiple/divisor of H (then the two pools
+ * compose to an (H/32)^2 block mean); anything else returns SMK_ERR_UNSUPPORTED.
+ * Frames of 512 and 1024 (every dtype, both layouts): a pooled cell spans 2 / 8 of the kernels' 8 x 16 tiles, so the main kernel
+ * writes per-tile partial sums into a buffer the handle owns ([B][H/8][W/16][128] fp32: 1 MB per 512^2 frame, 4 MB per 1024^2 frame)
+ * and one more small launch adds a cell's partials in a fixed order and stores the features.  The buffer is grown on demand and never
+ * inside a stream capture: a capture that finds it missing or too small returns SMK_ERR_UNSUPPORTED with a message that says so -- run
+ * one eager forward of the same shape first.  Like the tile-skip workspace below it is shared by the calls on one handle.
  * Tile skip (SMK_BF16X3, SMK_BF16, SMK_I8X3; both smk_encoder_forward and smk_encoder_forward_tokens): when a call has more 8 x 16
  * tiles than the device runs workgroups, a scan launch first finds the tiles whose 16 x 24 input window is all-zero words and leaves
  * one bit per tile; the main kernel's workgroups derive their tiles from those bits themselves and copy the features of the empty

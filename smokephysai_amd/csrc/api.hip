@@ -123,6 +123,7 @@ struct smk_encoder {
     unsigned short *blob16 = nullptr;
     int device = 0;
     EncoderSkip skip;     // tile-skip tables and workspace (lazy; a new handle starts without them)
+    EncoderPartials partials;   // per-tile partial sums of frames beyond 256^2 (lazy; independent of the skip state)
 };
 
 namespace {
@@ -875,14 +876,15 @@ int smk_encoder_destroy(smk_encoder *enc) {
     if (enc->blob) (void)hipFree(enc->blob);
     if (enc->blob16) (void)hipFree(enc->blob16);
     enc->skip.release();
+    enc->partials.release();
     delete enc;
     return SMK_OK;
 }
 
 static int encoder_shape_ok(int32_t B, int32_t H, int32_t W, int32_t input_dim) {
     SMK_REQUIRE(B >= 1, "B >= 1");
-    if (H != W || H % 32 != 0 || (H / 32 != 2 && H / 32 != 4 && H / 32 != 8)) {
-        set_error("encoder: HIP path is built for square frames of 64, 128 or 256");
+    if (H != W || (H != 64 && H != 128 && H != 256 && H != 512 && H != 1024)) {
+        set_error("encoder: HIP path is built for square frames of 64, 128, 256, 512 or 1024");
         return SMK_ERR_UNSUPPORTED;
     }
     if (input_dim <= 0 || input_dim % 32 != 0 || (input_dim % H != 0 && H % input_dim != 0)) {
@@ -890,6 +892,17 @@ static int encoder_shape_ok(int32_t B, int32_t H, int32_t W, int32_t input_dim) 
         return SMK_ERR_UNSUPPORTED;
     }
     return SMK_OK;
+}
+
+// The handle's partial buffer for this call (null in *out for H <= 256, where a pooled cell lies inside one tile).
+static int encoder_partials(smk_encoder *enc, int32_t B, int32_t H, int32_t W, void *stream, float **out) {
+    const hipError_t e = enc->partials.acquire(B, H, W, (hipStream_t)stream, out);
+    if (e == hipErrorStreamCaptureUnsupported) {
+        set_error("encoder: the stream is capturing and the handle's partial-sum buffer for frames of 512 or 1024 is missing or too small; "
+                  "run one eager forward of the same shape before the capture (nothing is allocated inside a capture)");
+        return SMK_ERR_UNSUPPORTED;
+    }
+    return check_launch(e, "encoder_partials");
 }
 
 int smk_encoder_forward(smk_encoder *enc, const float *frames, int64_t frame_stride, int32_t B, int32_t H, int32_t W,
@@ -901,13 +914,19 @@ int smk_encoder_forward(smk_encoder *enc, const float *frames, int64_t frame_str
     DeviceGuard guard(enc->device);
     rc = guard.rc;
     if (rc) return rc;
+    if (dtype != SMK_F32 && dtype != SMK_BF16X3 && dtype != SMK_BF16 && dtype != SMK_I8X3) {
+        set_error("unknown encoder dtype");
+        return SMK_ERR_INVALID;
+    }
+    float *part = nullptr;
+    if ((rc = encoder_partials(enc, B, H, W, stream, &part))) return rc;
     if (dtype == SMK_F32)
-        return check_launch(launch_encoder_f32(frames, frame_stride, B, H, W, enc->e, features, (hipStream_t)stream), "encoder_f32");
+        return check_launch(launch_encoder_f32(frames, frame_stride, B, H, W, enc->e, features, (hipStream_t)stream, part), "encoder_f32");
     if (dtype == SMK_BF16X3 || dtype == SMK_BF16)
         return check_launch(launch_encoder_bf16(frames, frame_stride, B, H, W, enc->e, features, dtype == SMK_BF16X3, false,
-                                                (hipStream_t)stream, &enc->skip), "encoder_bf16");
+                                                (hipStream_t)stream, &enc->skip, part), "encoder_bf16");
     if (dtype == SMK_I8X3)
-        return check_launch(launch_encoder_i8(frames, frame_stride, B, H, W, enc->e, features, false, (hipStream_t)stream, &enc->skip),
+        return check_launch(launch_encoder_i8(frames, frame_stride, B, H, W, enc->e, features, false, (hipStream_t)stream, &enc->skip, part),
                             "encoder_i8");
     set_error("unknown encoder dtype");
     return SMK_ERR_INVALID;
@@ -922,15 +941,17 @@ int smk_encoder_forward_tokens(smk_encoder *enc, const float *frames, int64_t fr
     DeviceGuard guard(enc->device);
     rc = guard.rc;
     if (rc) return rc;
-    if (dtype == SMK_I8X3)
-        return check_launch(launch_encoder_i8(frames, frame_stride, B, H, W, enc->e, tokens, true, (hipStream_t)stream, &enc->skip),
-                            "encoder_i8_tokens");
-    if (dtype != SMK_BF16X3 && dtype != SMK_BF16) {
+    if (dtype != SMK_BF16X3 && dtype != SMK_BF16 && dtype != SMK_I8X3) {
         set_error("token-major output is built for the MFMA kernels SMK_BF16X3, SMK_BF16, SMK_I8X3");
         return SMK_ERR_UNSUPPORTED;
     }
+    float *part = nullptr;
+    if ((rc = encoder_partials(enc, B, H, W, stream, &part))) return rc;
+    if (dtype == SMK_I8X3)
+        return check_launch(launch_encoder_i8(frames, frame_stride, B, H, W, enc->e, tokens, true, (hipStream_t)stream, &enc->skip, part),
+                            "encoder_i8_tokens");
     return check_launch(launch_encoder_bf16(frames, frame_stride, B, H, W, enc->e, tokens, dtype == SMK_BF16X3, true,
-                                            (hipStream_t)stream, &enc->skip), "encoder_bf16_tokens");
+                                            (hipStream_t)stream, &enc->skip, part), "encoder_bf16_tokens");
 }
 
 int smk_encoder_skip_stats(smk_encoder *enc, int64_t *tiles_total, int64_t *tiles_run, void *stream) {

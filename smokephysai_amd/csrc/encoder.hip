@@ -165,6 +165,103 @@ hipError_t launch_conv1_only(const float *frames, int64_t fstride, int B, int H,
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------- frames beyond 256^2: per-tile partial sums, pooled by a second kernel
+// The epilogues pool inside one 8 x 16 tile, which holds whole cells up to PS = H/32 = 8.  At 512^2 (PS = 16) a pooled cell spans
+// 2 x 1 tiles, at 1024^2 (PS = 32) 4 x 2.  There every main kernel (instantiated once as PS = 16: a tile's sum does not depend on the
+// cell size) writes, per tile and channel, the un-normalised fp32 sum of the tile's 128 bn_relu values into the handle's partial
+// buffer [B][H/8][W/16][128] -- a tile is 512 contiguous bytes, whichever output layout the call asked for -- and
+// k_encoder_pool_partials, launched behind it on the same stream, adds a cell's partials in ascending (tile row, tile column) order,
+// multiplies by 1/PS^2 once and stores the feature in the call's layout.  No atomics: two addends commute exactly, the eight of a
+// 1024^2 cell do not, and both layouts as well as skip-on and skip-off must stay bit-equal.  The pooling kernel does not know which
+// tiles ran: on the skip path skip_fill copies an empty tile's 128 partials from the zero-response table (the same kernel form's
+// partials of one all-zero frame) into the buffer, so skipping is invisible by construction.
+constexpr int POOL_THREADS = 256;
+
+// One thread per (cell, V channels): token-major stores are contiguous over channels (V = 4 when `features` is 16-byte aligned).
+template <int V>
+__global__ __launch_bounds__(POOL_THREADS) void k_encoder_pool_partials_tokens(const float *__restrict__ partials, float *__restrict__ features,
+                                                                               int ncells, int lg_tr, int lg_tc, float inv) {
+    typedef float vec_t __attribute__((ext_vector_type(V)));
+    constexpr int PER = 128 / V;
+    const int idx = blockIdx.x * POOL_THREADS + threadIdx.x, cell = idx / PER, o = (idx - cell * PER) * V;
+    if (cell >= ncells) return;
+    const int b = cell >> 10, pi = (cell >> 5) & 31, pj = cell & 31, tiles_x = 32 << lg_tc;
+    const float *p = partials + (((size_t)b * (32 << lg_tr) + ((size_t)pi << lg_tr)) * tiles_x + (pj << lg_tc)) * 128 + o;
+    vec_t sum = *reinterpret_cast<const vec_t *>(p);
+    for (int tr = 0; tr < (1 << lg_tr); ++tr)
+        for (int tc = (tr == 0); tc < (1 << lg_tc); ++tc) sum += *reinterpret_cast<const vec_t *>(p + ((size_t)tr * tiles_x + tc) * 128);
+    *reinterpret_cast<vec_t *>(features + (size_t)cell * 128 + o) = sum * inv;
+}
+
+// NCHW: one workgroup per cell row (b, pi): the same sums, one thread per (cell, 4 channels) with 16-byte loads, turned through LDS
+// so that a channel's 32 cells go out as one 128-byte row.
+__global__ __launch_bounds__(POOL_THREADS) void k_encoder_pool_partials(const float *__restrict__ partials, float *__restrict__ features,
+                                                                        int lg_tr, int lg_tc, float inv) {
+    __shared__ float cells[32][129];
+    const int tid = threadIdx.x, b = blockIdx.x >> 5, pi = blockIdx.x & 31, tiles_x = 32 << lg_tc;
+    const float *row = partials + ((size_t)b * (32 << lg_tr) + ((size_t)pi << lg_tr)) * tiles_x * 128;
+    for (int i = tid; i < 32 * 32; i += POOL_THREADS) {
+        const int pj = i >> 5, o = (i & 31) * 4;
+        const float *p = row + (size_t)(pj << lg_tc) * 128 + o;
+        float4 sum = *reinterpret_cast<const float4 *>(p);
+        for (int tr = 0; tr < (1 << lg_tr); ++tr)
+            for (int tc = (tr == 0); tc < (1 << lg_tc); ++tc) {
+                const float4 v = *reinterpret_cast<const float4 *>(p + ((size_t)tr * tiles_x + tc) * 128);
+                sum.x += v.x; sum.y += v.y; sum.z += v.z; sum.w += v.w;
+            }
+        cells[pj][o] = sum.x * inv; cells[pj][o + 1] = sum.y * inv; cells[pj][o + 2] = sum.z * inv; cells[pj][o + 3] = sum.w * inv;
+    }
+    __syncthreads();
+    for (int i = tid; i < 128 * 32; i += POOL_THREADS) {
+        const int o = i >> 5, pj = i & 31;
+        features[((size_t)b * 128 + o) * 1024 + pi * 32 + pj] = cells[pj][o];
+    }
+}
+
+// features [B][128][32][32] or [B][1024][128] from the partials of B frames of H x H, H = 512 or 1024
+static hipError_t launch_pool_partials(const float *partials, float *features, int B, int H, bool tokens, hipStream_t st) {
+    const int PS = H / 32, lg_tr = PS == 16 ? 1 : 2, lg_tc = lg_tr - 1;       // a cell is PS/8 x PS/16 tiles
+    const float inv = 1.0f / (float)(PS * PS);
+    if (!tokens) {
+        hipLaunchKernelGGL(k_encoder_pool_partials, dim3(B * 32), dim3(POOL_THREADS), 0, st, partials, features, lg_tr, lg_tc, inv);
+    } else if ((reinterpret_cast<uintptr_t>(features) & 15) == 0) {
+        hipLaunchKernelGGL(k_encoder_pool_partials_tokens<4>, dim3(B * 1024 * 32 / POOL_THREADS), dim3(POOL_THREADS), 0, st, partials,
+                           features, B * 1024, lg_tr, lg_tc, inv);
+    } else {
+        hipLaunchKernelGGL(k_encoder_pool_partials_tokens<1>, dim3(B * 1024 * 128 / POOL_THREADS), dim3(POOL_THREADS), 0, st, partials,
+                           features, B * 1024, lg_tr, lg_tc, inv);
+    }
+    return hipGetLastError();
+}
+
+void EncoderPartials::release() {
+    if (buf) (void)hipFree(buf);
+    for (void *p : retired) (void)hipFree(p);
+    retired.clear();
+    buf = nullptr;
+    floats = 0;
+}
+
+hipError_t EncoderPartials::acquire(int B, int H, int W, hipStream_t st, float **out) {
+    *out = nullptr;
+    if (H / 32 < 16) return hipSuccess;
+    const size_t need = (size_t)B * (H / B3_TH) * (W / B3_TW) * 128;
+    std::lock_guard<std::mutex> lk(mu);
+    if (floats < need) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
+        if (cs != hipStreamCaptureStatusNone) return hipErrorStreamCaptureUnsupported;
+        float *p = nullptr;
+        const hipError_t err = hipMalloc((void **)&p, need * sizeof(float));
+        if (err != hipSuccess) return err;
+        if (buf) retired.push_back(buf);
+        buf = p;
+        floats = need;
+    }
+    *out = buf;
+    return hipSuccess;
+}
+
 // ---------------------------------------------------------------- fused encoder, fp32 MFMA
 // LDS carve (floats): xs [16][40] | a1s [64][10][34] | w2s 2 x [64][128]  (= 2560 + 87040 + 65536 B = 155,136 B)
 // The epilogue reuses the a1s/w2s region as a2s [256 pixels][128+1 channels... see below].
@@ -276,32 +373,53 @@ __global__ __launch_bounds__(512) void k_encoder_f32(const float *__restrict__ f
         }
     }
     __syncthreads();
-    constexpr int CELLS_R = ENC_TH / PS, CELLS_C = ENC_TW / PS;   // pooled cells in this tile
-    const int OW = 32, OHW = 32 * 32;
-    for (int k = tid; k < CELLS_R * CELLS_C * 128; k += 512) {
-        const int o = k & 127, cell = k >> 7, cr = cell / CELLS_C, cc = cell % CELLS_C;
-        float sum = 0.f;
-        for (int rr = 0; rr < PS; ++rr)
-            for (int q = 0; q < PS; ++q) sum += a2s[((cr * PS + rr) * ENC_TW + cc * PS + q) * A2_PITCH + o];
-        const int pi = r0 / PS + cr, pj = c0 / PS + cc;
-        features[((size_t)b * 128 + o) * OHW + pi * OW + pj] = sum * (1.0f / (PS * PS));
+    if constexpr (PS >= 16) {
+        // frames beyond 256^2 (see below): `features` is the partial buffer [B][H/8][W/16][128]; this 8 x 32 tile is two of its
+        // 8 x 16 tiles, each the plain sum of its 128 activations, rows then columns
+        if (tid < 256) {
+            const int o = tid & 127, half = tid >> 7;
+            float sum = 0.f;
+            for (int rr = 0; rr < ENC_TH; ++rr)
+                for (int q = 0; q < B3_TW; ++q) sum += a2s[(rr * ENC_TW + half * B3_TW + q) * A2_PITCH + o];
+            const size_t tile = ((size_t)b * (H / B3_TH) + blockIdx.y) * (W / B3_TW) + 2 * blockIdx.x + half;
+            features[tile * 128 + o] = sum;
+        }
+    } else {
+        constexpr int CELLS_R = ENC_TH / PS, CELLS_C = ENC_TW / PS;   // pooled cells in this tile
+        const int OW = 32, OHW = 32 * 32;
+        for (int k = tid; k < CELLS_R * CELLS_C * 128; k += 512) {
+            const int o = k & 127, cell = k >> 7, cr = cell / CELLS_C, cc = cell % CELLS_C;
+            float sum = 0.f;
+            for (int rr = 0; rr < PS; ++rr)
+                for (int q = 0; q < PS; ++q) sum += a2s[((cr * PS + rr) * ENC_TW + cc * PS + q) * A2_PITCH + o];
+            const int pi = r0 / PS + cr, pj = c0 / PS + cc;
+            features[((size_t)b * 128 + o) * OHW + pi * OW + pj] = sum * (1.0f / (PS * PS));
+        }
     }
 }
 
 hipError_t launch_encoder_f32(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e,
-                              float *features, hipStream_t st) {
+                              float *features, hipStream_t st, float *partials) {
     const int PS = H / 32;
+    if (PS >= 16 && !partials) return hipErrorInvalidValue;
     dim3 grid(W / ENC_TW, H / ENC_TH, B), block(512);
     size_t lds_bytes = sizeof(float) * (size_t)(LDS_F32_TOTAL > 256 * A2_PITCH ? LDS_F32_TOTAL : 256 * A2_PITCH);
     once_per_device((const void *)k_encoder_f32<8>, [&] {
         (void)hipFuncSetAttribute((const void *)k_encoder_f32<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         (void)hipFuncSetAttribute((const void *)k_encoder_f32<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         (void)hipFuncSetAttribute((const void *)k_encoder_f32<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        (void)hipFuncSetAttribute((const void *)k_encoder_f32<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     });
     switch (PS) {
         case 2: hipLaunchKernelGGL(k_encoder_f32<2>, grid, block, lds_bytes, st, frames, fstride, H, W, e, features); break;
         case 4: hipLaunchKernelGGL(k_encoder_f32<4>, grid, block, lds_bytes, st, frames, fstride, H, W, e, features); break;
         case 8: hipLaunchKernelGGL(k_encoder_f32<8>, grid, block, lds_bytes, st, frames, fstride, H, W, e, features); break;
+        case 16:
+        case 32: {                                            // per-tile partials, then the pooling kernel
+            hipLaunchKernelGGL(k_encoder_f32<16>, grid, block, lds_bytes, st, frames, fstride, H, W, e, partials);
+            const hipError_t err = hipGetLastError();
+            return err != hipSuccess ? err : launch_pool_partials(partials, features, B, H, false, st);
+        }
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -367,7 +485,8 @@ struct SkipArgs {
     const float *table = nullptr;                             // the call's zero-response table: what an empty tile's cells hold
     int nbands = 0, lg_band_tiles = 0, bands_per_frame = 0;
 };
-constexpr int SCAN_ROWS = 4;                                  // tile rows per band: <= 64 tiles at W = 256 (one mask word)
+// Tile rows per band: a band is one 64-bit mask, so 64 / tiles_x rows, capped at 4: 4 for W <= 256, 2 at 512, 1 at 1024.
+constexpr int scan_rows_for(int tiles_x) { return tiles_x <= 16 ? 4 : 64 / tiles_x; }
 constexpr int ENC_FRAME_FEATS = 128 * 1024;                   // features per frame, either layout
 constexpr int SKIP_CHUNKS = 256, SKIP_SLATE = 16;
 struct SkipLds {
@@ -456,10 +575,12 @@ __device__ __forceinline__ int tile_at(SkipLds &s, const SkipArgs &sa, bool list
 // fragments come from L2.
 template <int PS, bool TOKENS>
 __device__ __forceinline__ void skip_fill(const SkipArgs &sa, int lg_tiles_x, float *__restrict__ features) {
-    constexpr int CR = B3_TH / PS, CC = B3_TW / PS;           // cells per tile: rows x columns
+    constexpr bool PART = PS >= 16;                           // frames beyond 256^2: `features` and the table hold per-tile partials
+    constexpr int CR = PART ? 1 : B3_TH / PS, CC = PART ? 1 : B3_TW / PS;   // cells per tile: rows x columns
     // token-major: a cell row of a tile is CC cells x 128 channels, contiguous (float4).  NCHW: a channel's CC cells of one row.
-    constexpr int VW = TOKENS ? 4 : (CC < 4 ? CC : 4), VPR = TOKENS ? 1 : CC / VW, ROWV = CC * 32;
-    constexpr int UPT = TOKENS ? CR * ROWV : 128 * CR * VPR;  // vectors per tile
+    // Partials: a tile's 128 sums, contiguous (32 x float4).
+    constexpr int VW = TOKENS || PART ? 4 : (CC < 4 ? CC : 4), VPR = TOKENS || PART ? 1 : CC / VW, ROWV = CC * 32;
+    constexpr int UPT = TOKENS || PART ? CR * ROWV : 128 * CR * VPR;  // vectors per tile
     constexpr int UNR = 4;
     typedef float vec_t __attribute__((ext_vector_type(VW)));
     const int tid = threadIdx.x, tiles_x = 1 << lg_tiles_x, band_tiles = 1 << sa.lg_band_tiles, total = band_tiles * UPT;
@@ -469,8 +590,9 @@ __device__ __forceinline__ void skip_fill(const SkipArgs &sa, int lg_tiles_x, fl
         const unsigned long long m = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned int)(mv >> 32)) << 32) |
                                      (unsigned int)__builtin_amdgcn_readfirstlane((unsigned int)mv);
         if (m == full) continue;
-        const int b = band / sa.bands_per_frame, ty0 = (band - b * sa.bands_per_frame) * SCAN_ROWS;
-        float *out = features + (size_t)b * ENC_FRAME_FEATS;
+        const int lg_rows = PART ? sa.lg_band_tiles - lg_tiles_x : 2;      // tile rows per band (scan_rows_for)
+        const int b = band / sa.bands_per_frame, ty0 = (band - b * sa.bands_per_frame) << lg_rows;
+        float *out = features + (size_t)b * (PART ? (size_t)sa.bands_per_frame << (sa.lg_band_tiles + 7) : (size_t)ENC_FRAME_FEATS);
         for (int i0 = tid; i0 < total; i0 += 256 * UNR) {
             vec_t v[UNR];
             int off[UNR];
@@ -480,7 +602,9 @@ __device__ __forceinline__ void skip_fill(const SkipArgs &sa, int lg_tiles_x, fl
                 off[j] = -1;
                 if (i >= total || ((m >> tl) & 1)) continue;
                 const int ty = ty0 + (tl >> lg_tiles_x), tx = tl & (tiles_x - 1);
-                if (TOKENS) {
+                if (PART) {
+                    off[j] = ((ty << lg_tiles_x) + tx) * 128 + u * 4;
+                } else if (TOKENS) {
                     const int a = u / ROWV, q = u - a * ROWV;
                     off[j] = ((ty * CR + a) * 32 + tx * CC) * 128 + q * 4;
                 } else {
@@ -665,8 +789,9 @@ __device__ __forceinline__ void conv1_one(const unsigned char *w1s, int cb, cons
 // Block-mean pool + store for the 32x32 accumulator layout (k_encoder_bf16, k_encoder_i8); val(mi, g) is the finished activation
 // of register g of M block mi: pixel p = (g&3) + 8(g>>2) + 4hi of the block -> tile row mi + 4(p>>4), col p & 15,
 // i.e. q = g>>2 = 2qr + qc: row mi + 4qr, cols 8qc + 4hi + (g&3).  o = the lane's output channel.
+// PS >= 16 (frames beyond 256^2): `features` is the partial buffer and the store is tile `tile`'s sum for channel o.
 template <int PS, bool TOKENS, class Val>
-__device__ __forceinline__ void pool_store_32(float *__restrict__ features, int b, int o, int r0, int c0, Val val) {
+__device__ __forceinline__ void pool_store_32(float *__restrict__ features, int b, int o, int r0, int c0, int tile, Val val) {
     const int hi = (threadIdx.x >> 5) & 1;
     auto out_index = [&](int pi, int pj) -> size_t {
         return TOKENS ? ((size_t)b * 1024 + pi * 32 + pj) * 128 + o : ((size_t)b * 128 + o) * 1024 + pi * 32 + pj;
@@ -699,6 +824,22 @@ __device__ __forceinline__ void pool_store_32(float *__restrict__ features, int 
                     for (int i = 0; i < 4; ++i) sum += val(mi, 4 * (2 * qr + qc) + i);
                 features[out_index((r0 + 4 * qr) / 4, (c0 + 8 * qc + 4 * hi) / 4)] = sum * (1.0f / 16);
             }
+    } else if (PS >= 16) {   // the PS == 8 sums, the two 8-column halves added, then the two lane halves: one sum per tile
+        float cell[2];
+#pragma unroll
+        for (int qc = 0; qc < 2; ++qc) {
+            float sum = 0.f;
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+                for (int qr = 0; qr < 2; ++qr)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) sum += val(mi, 4 * (2 * qr + qc) + i);
+            cell[qc] = sum;
+        }
+        const float mine = cell[0] + cell[1];
+        const float total = mine + __shfl_xor(mine, 32);     // a+b == b+a: both halves agree bitwise
+        if (hi == 0) features[(size_t)tile * 128 + o] = total;
     } else {   // PS == 8: two cells (qc); each is split over the two lane halves (hi)
         float cell[2];
 #pragma unroll
@@ -871,7 +1012,7 @@ __global__ __launch_bounds__(256, 2) void k_encoder_bf16(const float *__restrict
         }
 
         // ---- epilogue: BN2 + ReLU + block-mean pool
-        pool_store_32<PS, TOKENS>(features, b, o, r0, c0, [&](int mi, int g) { return bn_relu(acc[mi][g], s2, t2); });
+        pool_store_32<PS, TOKENS>(features, b, o, r0, c0, wk.t, [&](int mi, int g) { return bn_relu(acc[mi][g], s2, t2); });
 
         // next tile's x halo -> LDS (xs has been free since the barrier above); one barrier then covers both
         // "every wave is done reading a1" and "xs is visible"
@@ -1159,6 +1300,15 @@ __global__ __launch_bounds__(256, 2) void k_encoder_b16(const float *__restrict_
                         for (int i = 0; i < 4; ++i) sum += bn_relu(acc[mt][nt][i], s2, t2);
                     features[out_index((r0 + 4 * mq) / 4, (c0 + 4 * kg) / 4, o)] = sum * (1.0f / 16);
                 }
+            } else if (PS >= 16) {  // frames beyond 256^2: the PS == 8 sum, then one more step over kg for the whole tile's partial
+                float sum = 0.f;
+#pragma unroll
+                for (int mt = 0; mt < 8; ++mt)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) sum += bn_relu(acc[mt][nt][i], s2, t2);
+                const float half8 = sum + __shfl_xor(sum, 16);             // a+b == b+a at each step: all four lanes agree bitwise
+                const float total = half8 + __shfl_xor(half8, 32);
+                if (kg == 0) features[(size_t)wk.t * 128 + o] = total;
             } else {                // PS == 8: all 8 rows; columns 0-7 = kg 0,1, columns 8-15 = kg 2,3 (lane ^ 16 holds the other half)
                 float sum = 0.f;
 #pragma unroll
@@ -1204,7 +1354,7 @@ static const EncoderKnobs &enc_knobs() {
 // A tile's result depends on its 16 x 24 input window (tile + 4 pixels each way, outside the image = zero) and on its position in the
 // frame, nothing else.  A tile whose window is all zero therefore equals the same tile of an all-zero frame, bit for bit, and the
 // simulator's frames are mostly background.  Two launches per call:
-//   k_encoder_tile_scan       one workgroup per band of SCAN_ROWS tile rows of a frame.  Reads the band's 32 + 8 image rows once
+//   k_encoder_tile_scan       one workgroup per band of ROWS = scan_rows_for(tiles_x) tile rows of a frame.  Reads the band's 8 ROWS + 8 image rows once
 //          (16-byte loads when the frames allow), keeps one flag per 4 x 4 pixel block in LDS (window edges fall on multiples of 4),
 //          ORs 4 x 6 flags per tile.  EMPTY means every 32-bit word of the window inside the image is 0x00000000: bits are compared,
 //          so -0.0, denormals, NaN and Inf all keep a tile on the normal path.  The band's non-empty tiles go out as one 64-bit
@@ -1216,12 +1366,13 @@ static const EncoderKnobs &enc_knobs() {
 // Every word the main kernel reads is rewritten by the scan of the same call, so nothing needs a reset, nothing is read back by the
 // host, the walk is the same on every run, and both launches are capturable.  No workgroup waits for another one; the kernel
 // boundary orders scan and main kernel.
-constexpr int SCAN_BR = 2 * SCAN_ROWS + 2;                    // 4-row flag blocks per band (the band's rows + 4 each way)
-constexpr int SCAN_FW = 256 / 4 + 2;                          // flag columns: the widest frame's 4-pixel blocks + one pad each side
-
-template <bool VEC>
+template <bool VEC, int ROWS>
 __global__ __launch_bounds__(256) void k_encoder_tile_scan(const float *__restrict__ frames, int64_t fstride, int H, int W, int lg_tiles_x,
                                                            int bands_per_frame, unsigned long long *__restrict__ masks) {
+    constexpr int SCAN_ROWS = ROWS;
+    constexpr int SCAN_BR = 2 * ROWS + 2;                     // 4-row flag blocks per band (the band's rows + 4 each way)
+    constexpr int SCAN_FW = 1024 / ROWS / 4 + 2;              // flag columns: the 4-pixel blocks of the widest frame with ROWS rows per
+                                                              // band (W = 256, 512, 1024 for ROWS = 4, 2, 1) + one pad each side
     __shared__ unsigned int flag[SCAN_BR][SCAN_FW];
     const int tid = threadIdx.x;
     const int band = blockIdx.x, b = band / bands_per_frame, bi = band - b * bands_per_frame;
@@ -1305,20 +1456,26 @@ static hipError_t skip_prepare(EncoderSkip *sk, const float *frames, int64_t fst
     }
     const bool capturing = cs != hipStreamCaptureStatusNone;
     hipError_t err;
-    float *&tab = sk->table[FORM][H == 64 ? 0 : H == 128 ? 1 : 2][TOKENS ? 1 : 0];
+    const bool part = H / 32 >= 16;                           // `features` is the partial buffer: one table layout
+    const int hidx = H == 64 ? 0 : H == 128 ? 1 : H == 256 ? 2 : H == 512 ? 3 : 4;
+    if (H != 64 && H != 128 && H != 256 && H != 512 && H != 1024) return hipErrorInvalidValue;
+    float *&tab = sk->table[FORM][hidx][TOKENS && !part ? 1 : 0];
     if (!tab) {
         if (capturing) return hipSuccess;
-        float *p = nullptr;                                   // [table 1024 x 128][zero frame H x W]
-        if ((err = hipMalloc((void **)&p, ((size_t)ENC_FRAME_FEATS + (size_t)H * W) * sizeof(float))) != hipSuccess) return err;
-        err = hipMemsetAsync(p + ENC_FRAME_FEATS, 0, (size_t)H * W * sizeof(float), st);
-        if (err == hipSuccess) err = zero_launch(p + ENC_FRAME_FEATS, p);
+        // [table: 1024 x 128 features, or the frame's per-tile partials][zero frame H x W]
+        const size_t tfloats = part ? (size_t)(H / B3_TH) * (W / B3_TW) * 128 : (size_t)ENC_FRAME_FEATS;
+        float *p = nullptr;
+        if ((err = hipMalloc((void **)&p, (tfloats + (size_t)H * W) * sizeof(float))) != hipSuccess) return err;
+        err = hipMemsetAsync(p + tfloats, 0, (size_t)H * W * sizeof(float), st);
+        if (err == hipSuccess) err = zero_launch(p + tfloats, p);
         if (err != hipSuccess) {
             (void)hipFree(p);
             return err;
         }
         tab = p;
     }
-    const int bands_per_frame = H / B3_TH / SCAN_ROWS, nbands = B * bands_per_frame;
+    const int scan_rows = scan_rows_for(1 << lg_tx);
+    const int bands_per_frame = H / B3_TH / scan_rows, nbands = B * bands_per_frame;
     if (sk->ws_bands < (size_t)nbands) {
         if (capturing) return hipSuccess;
         int *p = nullptr;                                     // [tiles run + pad: 4][band masks: 2 per band]
@@ -1331,14 +1488,17 @@ static hipError_t skip_prepare(EncoderSkip *sk, const float *frames, int64_t fst
     unsigned long long *masks = reinterpret_cast<unsigned long long *>(sk->ws + 4);
     const bool vec = (reinterpret_cast<uintptr_t>(frames) & 15) == 0 && (fstride & 3) == 0;
     dim3 grid(nbands), block(256);
-    if (H != 64 && H != 128 && H != 256) return hipErrorInvalidValue;
-    if (vec) hipLaunchKernelGGL(k_encoder_tile_scan<true>, grid, block, 0, st, frames, fstride, H, W, lg_tx, bands_per_frame, masks);
-    else hipLaunchKernelGGL(k_encoder_tile_scan<false>, grid, block, 0, st, frames, fstride, H, W, lg_tx, bands_per_frame, masks);
+    auto scan = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, st, frames, fstride, H, W, lg_tx, bands_per_frame, masks); };
+    switch (scan_rows) {
+        case 4: vec ? scan(k_encoder_tile_scan<true, 4>) : scan(k_encoder_tile_scan<false, 4>); break;
+        case 2: vec ? scan(k_encoder_tile_scan<true, 2>) : scan(k_encoder_tile_scan<false, 2>); break;
+        default: vec ? scan(k_encoder_tile_scan<true, 1>) : scan(k_encoder_tile_scan<false, 1>); break;
+    }
     if ((err = hipGetLastError()) != hipSuccess) return err;
     plan.masks = masks;
     plan.count = count;
     plan.nbands = nbands;
-    plan.lg_band_tiles = lg_tx + 2;                           // SCAN_ROWS = 4 tile rows
+    plan.lg_band_tiles = lg_tx + 2 < 6 ? lg_tx + 2 : 6;      // scan_rows x tiles_x tiles, at most one mask word
     plan.table = tab;
     plan.bands_per_frame = bands_per_frame;
     sk->last_count = count;
@@ -1566,7 +1726,7 @@ __global__ __launch_bounds__(256, 2) void k_encoder_i8(const float *__restrict__
             const float y = fmaf(v, sc, t2);
             return y > 0.f ? y : 0.f;
         };
-        pool_store_32<PS, TOKENS>(features, b, o, r0, c0, val);
+        pool_store_32<PS, TOKENS>(features, b, o, r0, c0, wk.t, val);
 
         halo_to_lds(xs, xr0, xr1, [](float v) { return v; });
         // [stamp:T6]
@@ -1601,19 +1761,23 @@ struct FormI8 {
 
 template <class F, bool TOKENS>
 static hipError_t launch_persistent(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e, float *features,
-                                    hipStream_t st, EncoderSkip *skip) {
+                                    hipStream_t st, EncoderSkip *skip, float *partials) {
     const int PS = H / 32;
     const int tiles_x = W / B3_TW, tiles_per_frame = tiles_x * (H / B3_TH), ntiles = B * tiles_per_frame;
     int lg_tx = 0, lg_tpf = 0;
     while ((1 << lg_tx) < tiles_x) ++lg_tx;
     while ((1 << lg_tpf) < tiles_per_frame) ++lg_tpf;
-    if ((1 << lg_tx) != tiles_x || (1 << lg_tpf) != tiles_per_frame || (PS != 2 && PS != 4 && PS != 8)) return hipErrorInvalidValue;   // H = W in {64,128,256}
+    if ((1 << lg_tx) != tiles_x || (1 << lg_tpf) != tiles_per_frame || (PS != 2 && PS != 4 && PS != 8 && PS != 16 && PS != 32))
+        return hipErrorInvalidValue;                          // H = W in {64,128,256,512,1024}
+    const bool part = PS >= 16;                               // the main kernel writes per-tile partials, the pooling kernel the features
+    if (part && !partials) return hipErrorInvalidValue;
     const int stagger = enc_knobs().stagger;
     const int num_cu = device_num_cu();
     const int wgs_per_cu = device_cached_int((const void *)F::template kernel<8, TOKENS>, [] {
         (void)hipFuncSetAttribute((const void *)F::template kernel<8, TOKENS>, hipFuncAttributeMaxDynamicSharedMemorySize, F::LDS);
         (void)hipFuncSetAttribute((const void *)F::template kernel<4, TOKENS>, hipFuncAttributeMaxDynamicSharedMemorySize, F::LDS);
         (void)hipFuncSetAttribute((const void *)F::template kernel<2, TOKENS>, hipFuncAttributeMaxDynamicSharedMemorySize, F::LDS);
+        (void)hipFuncSetAttribute((const void *)F::template kernel<16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, F::LDS);
         int n = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)F::template kernel<8, TOKENS>, 256, F::LDS) != hipSuccess || n < 1) n = 2;
         return enc_knobs().wgs_per_cu ? enc_knobs().wgs_per_cu : n;
@@ -1630,41 +1794,44 @@ static hipError_t launch_persistent(const float *frames, int64_t fstride, int B,
         switch (PS) {
             case 2: go(F::template kernel<2, TOKENS>); break;
             case 4: go(F::template kernel<4, TOKENS>); break;
-            default: go(F::template kernel<8, TOKENS>); break;
+            case 8: go(F::template kernel<8, TOKENS>); break;
+            default: go(F::template kernel<16, false>); break;   // partials have one layout and do not depend on the cell size
         }
         return hipGetLastError();
     };
     SkipArgs plan;
     hipError_t err = skip_prepare<F::FORM, TOKENS>(
-        skip, frames, fstride, B, H, W, features, lg_tx, ntiles, num_cu * wgs_per_cu, st,
+        skip, frames, fstride, B, H, W, part ? partials : features, lg_tx, ntiles, num_cu * wgs_per_cu, st,
         [&](const float *zero_frame, float *table) { return run(zero_frame, (int64_t)H * W, tiles_per_frame, table, SkipArgs()); },
         plan);
     if (err != hipSuccess) return err;
-    return run(frames, fstride, ntiles, features, plan);
+    if (!part) return run(frames, fstride, ntiles, features, plan);
+    if ((err = run(frames, fstride, ntiles, partials, plan)) != hipSuccess) return err;
+    return launch_pool_partials(partials, features, B, H, TOKENS, st);
 }
 
 hipError_t launch_encoder_b16(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e, float *features,
-                              bool tokens, hipStream_t st, EncoderSkip *skip) {
-    return tokens ? launch_persistent<FormB16, true>(frames, fstride, B, H, W, e, features, st, skip)
-                  : launch_persistent<FormB16, false>(frames, fstride, B, H, W, e, features, st, skip);
+                              bool tokens, hipStream_t st, EncoderSkip *skip, float *partials) {
+    return tokens ? launch_persistent<FormB16, true>(frames, fstride, B, H, W, e, features, st, skip, partials)
+                  : launch_persistent<FormB16, false>(frames, fstride, B, H, W, e, features, st, skip, partials);
 }
 
 hipError_t launch_encoder_bf16(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e,
-                               float *features, bool x3, bool tokens, hipStream_t st, EncoderSkip *skip) {
+                               float *features, bool x3, bool tokens, hipStream_t st, EncoderSkip *skip, float *partials) {
     // split-bf16 runs on the 16x16x32 shape (k_encoder_b16: -7 % time, interleaved A/B); SMK_ENC_SHAPE=32 selects the
     // 32x32x16 kernel (k_encoder_bf16<true>) for comparison
     const int shape = enc_knobs().shape;
-    if (x3 && shape == 16) return launch_encoder_b16(frames, fstride, B, H, W, e, features, tokens, st, skip);
-    if (x3) return tokens ? launch_persistent<FormBf16<true>, true>(frames, fstride, B, H, W, e, features, st, skip)
-                          : launch_persistent<FormBf16<true>, false>(frames, fstride, B, H, W, e, features, st, skip);
-    return tokens ? launch_persistent<FormBf16<false>, true>(frames, fstride, B, H, W, e, features, st, skip)
-                  : launch_persistent<FormBf16<false>, false>(frames, fstride, B, H, W, e, features, st, skip);
+    if (x3 && shape == 16) return launch_encoder_b16(frames, fstride, B, H, W, e, features, tokens, st, skip, partials);
+    if (x3) return tokens ? launch_persistent<FormBf16<true>, true>(frames, fstride, B, H, W, e, features, st, skip, partials)
+                          : launch_persistent<FormBf16<true>, false>(frames, fstride, B, H, W, e, features, st, skip, partials);
+    return tokens ? launch_persistent<FormBf16<false>, true>(frames, fstride, B, H, W, e, features, st, skip, partials)
+                  : launch_persistent<FormBf16<false>, false>(frames, fstride, B, H, W, e, features, st, skip, partials);
 }
 
 hipError_t launch_encoder_i8(const float *frames, int64_t fstride, int B, int H, int W, const EncoderDev &e, float *features,
-                             bool tokens, hipStream_t st, EncoderSkip *skip) {
-    return tokens ? launch_persistent<FormI8, true>(frames, fstride, B, H, W, e, features, st, skip)
-                  : launch_persistent<FormI8, false>(frames, fstride, B, H, W, e, features, st, skip);
+                             bool tokens, hipStream_t st, EncoderSkip *skip, float *partials) {
+    return tokens ? launch_persistent<FormI8, true>(frames, fstride, B, H, W, e, features, st, skip, partials)
+                  : launch_persistent<FormI8, false>(frames, fstride, B, H, W, e, features, st, skip, partials);
 }
 
 }  // namespace smk

@@ -1,7 +1,10 @@
 """HIP front-end of SmokePhysNet.input_encoder + pooling (src/models/smokephys_net.py:24-32,87-91).
 
 `HipEncoder` folds eval-mode BatchNorm into per-channel scale/shift once, re-lays the conv weights out for the
-MFMA kernel (csrc/encoder.hip) and maps frames [B,1,H,W] -> features [B,128,32,32] in one fused launch.
+MFMA kernel (csrc/encoder.hip) and maps frames [B,1,H,W] -> features [B,128,32,32] in one fused launch
+(square frames of 64, 128 or 256), or, at 512 and 1024, where a pooled cell spans several of the kernel's
+8 x 16 tiles, in the fused launch plus a small pooling launch over per-tile partial sums.
+`hip_encoder_supported` states which frames and `input_dim` the fused path takes.
 """
 import ctypes as C
 
@@ -22,7 +25,23 @@ def encoder_weight_dict(input_encoder: nn.Sequential) -> dict:
                 bn2_mean=b2.running_mean, bn2_var=b2.running_var)
 
 
+HIP_ENCODER_SIZES = (64, 128, 256, 512, 1024)
+
+
+def hip_encoder_supported(H: int, W: int, input_dim: int) -> bool:
+    """The one statement of what the fused eval-mode encoder takes (encoder_shape_ok in csrc/api.hip checks the same): square frames
+    of HIP_ENCODER_SIZES, and an input_dim that is a multiple of 32 and a multiple or divisor of H, so that the two adaptive pools
+    (-> input_dim, -> 32) compose to one (H/32)^2 block mean.  Pure: no device, no library."""
+    H, W, input_dim = int(H), int(W), int(input_dim)
+    return (H == W and H in HIP_ENCODER_SIZES and input_dim > 0 and input_dim % 32 == 0
+            and (input_dim % H == 0 or H % input_dim == 0))
+
+
 class HipEncoder:
+    """Frames [B,1,H,W] or [B,H,W] with hip_encoder_supported(H, W, input_dim) -> features; anything else raises SmokeHipError.
+    Frames of 512 and 1024 use a per-handle buffer of per-tile partial sums (1 MB / 4 MB per frame), allocated on the first call
+    of a batch size and never inside a stream capture: capture a graph only after one eager call of the same shape."""
+
     def __init__(self, weights: dict, device="cuda"):
         self._dev = _lib.require_cuda(device, "HipEncoder")
         self._L = _lib.load()

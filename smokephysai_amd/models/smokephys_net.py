@@ -24,7 +24,7 @@ from .attention import hip_layernorm_supported, hip_layernorm_train
 from .chaos_attention import ChaosAttention
 from .decoder import HipDecoder, decoder_weight_dict, hip_decoder_supported
 from .decoder_train import hip_head_train, hip_head_train_supported
-from .encoder import HipEncoder, encoder_weight_dict
+from .encoder import HipEncoder, encoder_weight_dict, hip_encoder_supported
 from .hip_body import HipBody
 from .ffn import hip_dropout_add, hip_ffn_elementwise_supported, hip_gelu_dropout
 from .linear import TrainableHipLinear, hip_linear_supported
@@ -169,11 +169,10 @@ class SmokePhysNet(nn.Module):
                               "torch.no_grad() to use the fused libsmokehip kernels", stacklevel=3)
             return "modules"
         H, W = x.shape[-2:]
-        ok = H == W and H in (64, 128, 256) and self.input_dim % 32 == 0 and (self.input_dim % H == 0 or H % self.input_dim == 0)
-        if not ok:
+        if not hip_encoder_supported(H, W, self.input_dim):
             if not self.__dict__.get("_warned_shape"):
                 self.__dict__["_warned_shape"] = True
-                warnings.warn(f"SmokePhysNet: frames of {H}x{W} are outside the fused HIP encoder's shapes (square 64/128/256); "
+                warnings.warn(f"SmokePhysNet: frames of {H}x{W} are outside the fused HIP encoder's shapes (square 64/128/256/512/1024); "
                               "this call runs input_encoder on PyTorch-ROCm ops", stacklevel=3)
             return "modules"
         return "hip"
