@@ -480,10 +480,14 @@ int smk_bn_relu_pool_backward(const float *z, const float *dout, int32_t B, int3
  *   forward: x [B][H][W] (the single input channel), weight [64][7][7], bias [64] or NULL -> z1 [B][64][H][W]; W % 4 == 0;
  *   wgrad:   dz [B][64][H][W], x -> dW [64][7][7] and db [64] (unless NULL); H % 4 == 0, W % 64 == 0; per-workgroup partial sums added
  *            in a fixed order (deterministic); `workspace`: smk_conv1_train_wgrad_workspace() bytes.
- * (The input frames carry no gradient in train.py; a caller that needs dX keeps PyTorch-ROCm's.) */
+ *   dgrad:   dz [B][64][H][W], weight -> dx [B][H][W] = sum over c and taps of dz[b][c][i+3-ki][j+3-kj] * w[c][ki][kj] (zeros outside the
+ *            plane), for a caller that differentiates with respect to the frames (train.py's carry no gradient; PGD and saliency do):
+ *            1 <= B <= 65535, H >= 1, W % 4 == 0, dz / dx 16-byte aligned; no atomics and no workspace, every dx element is written
+ *            exactly once (deterministic). */
 int smk_conv1_train_forward(const float *x, const float *weight, const float *bias, int32_t B, int32_t H, int32_t W, float *z1, void *stream);
 int64_t smk_conv1_train_wgrad_workspace(void);
 int smk_conv1_train_wgrad(const float *dz, const float *x, int32_t B, int32_t H, int32_t W, float *dw, float *db, void *workspace, void *stream);
+int smk_conv1_train_dgrad(const float *dz, const float *weight, int32_t B, int32_t H, int32_t W, float *dx, void *stream);
 
 /* The encoder's second convolution alone, for training: z2 = Conv2d(64, 128, 3, padding = 1)(a1) + bias under autograd
  * (smokephys_net.py:28; train.py:88-89 -- train-mode BatchNorm needs the whole convolution output before it can normalise, so the
@@ -512,7 +516,10 @@ int smk_conv2_train_wgrad(const float *dz, const float *a1, int32_t B, int32_t H
  *   SMK_BN_STATS     z -> mean / var (biased) / rstd [C] of THIS process's batch (workspace as above);
  *   SMK_BN_APPLY     out = blockmean(relu(bn(z))) from the GIVEN mean / rstd;
  *   SMK_BN_BWD_SUMS  dout, z, given mean / rstd -> this process's dgamma = sum dy * zhat and dbeta = sum dy (workspace);
- *   SMK_BN_BWD_DZ    dz from the GIVEN (all-reduced) dgamma / dbeta and count = elements per channel of the GLOBAL batch. */
+ *   SMK_BN_BWD_DZ    dz from the GIVEN (all-reduced) dgamma / dbeta and count = elements per channel of the GLOBAL batch.
+ * Frozen (running) statistics under autograd are these two element-wise phases alone: SMK_BN_APPLY with mean / rstd from the running
+ * statistics, and SMK_BN_BWD_DZ with zero dgamma / dbeta and count = 1, which is exactly dz = gamma * rstd * dy * [y > 0].  At pool 1 they
+ * take any plane with H * W % 4 == 0 (the reductions keep whole 4,096-float chunks). */
 enum smk_bn_phase { SMK_BN_STATS = 0, SMK_BN_APPLY = 1, SMK_BN_BWD_SUMS = 2, SMK_BN_BWD_DZ = 3 };
 int smk_bn_relu_pool_phase(int32_t phase, const float *z, const float *dout, int32_t B, int32_t C, int32_t H, int32_t W, const float *gamma,
                            const float *beta, double eps, float *mean, float *var, float *rstd, int32_t pool, float *out, float *dz,

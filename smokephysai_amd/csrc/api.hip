@@ -1391,6 +1391,16 @@ int smk_conv1_train_wgrad(const float *dz, const float *x, int32_t B, int32_t H,
     return check_launch(launch_conv1_train_wgrad(dz, x, B, H, W, dw, db, workspace, (hipStream_t)stream), "conv1_train_wgrad");
 }
 
+int smk_conv1_train_dgrad(const float *dz, const float *weight, int32_t B, int32_t H, int32_t W, float *dx, void *stream) {
+    SMK_REQUIRE(dz && weight && dx, "null dz/weight/dx");
+    if (B < 1 || B > 65535 || H < 1 || H > 65535 * 32 || W < 4 || W % 4 != 0) {
+        set_error("conv1_train_dgrad: 1 <= B <= 65535, H >= 1, W a multiple of 4");
+        return SMK_ERR_UNSUPPORTED;
+    }
+    SMK_REQUIRE((((uintptr_t)dz | (uintptr_t)dx) & 15) == 0, "16-byte aligned dz / dx");
+    return check_launch(launch_conv1_train_dgrad(dz, weight, B, H, W, dx, (hipStream_t)stream), "conv1_train_dgrad");
+}
+
 int64_t smk_conv2_train_workspace(void) { return (int64_t)conv2_train_workspace_bytes(); }
 
 int smk_conv2_train_forward(const float *a1, const float *weight, const float *bias, int32_t B, int32_t H, int32_t W, float *z2,
@@ -1530,7 +1540,10 @@ int smk_bn_relu_pool_phase(int32_t phase, const float *z, const float *dout, int
                            const float *beta, double eps, float *mean, float *var, float *rstd, int32_t pool, float *out, float *dz,
                            float *dgamma, float *dbeta, double count, void *workspace, void *stream) {
     SMK_REQUIRE(z && gamma && beta && mean && rstd, "null pointer");
-    int rc = bn_check(B, C, H, W, pool);
+    // the two element-wise passes at pool 1 take any plane of whole float4s (frozen statistics on the 32 x 32 token grid); the reductions keep whole chunks
+    const bool elementwise = (phase == SMK_BN_APPLY || phase == SMK_BN_BWD_DZ) && pool == 1 && B >= 1 && C >= 1 && C <= 65535 && H >= 1 && W >= 1 &&
+                             ((int64_t)H * W) % 4 == 0 && (int64_t)H * W < (1LL << 31) - 4096 && (int64_t)B * (((int64_t)H * W + 4095) / 4096) < (1LL << 31);
+    int rc = elementwise ? SMK_OK : bn_check(B, C, H, W, pool);
     if (rc) return rc;
     SMK_REQUIRE(((uintptr_t)z & 15) == 0, "16-byte aligned z");
     BnTrainArgs a = {};

@@ -14,6 +14,8 @@ hipError_t launch_conv2_train_dgrad(const float *dz, const float *weight, int B,
 size_t conv1_wgrad_workspace_bytes();
 hipError_t launch_conv1_train_forward(const float *x, const float *weight, const float *bias, int B, int H, int W, float *z1, hipStream_t st);
 hipError_t launch_conv1_train_wgrad(const float *dz, const float *x, int B, int H, int W, float *dw, float *db, void *workspace, hipStream_t st);
+// dX [B][H][W] = the data gradient of the first convolution from dz [B][64][H][W] and weight [64][7][7] (W % 4 == 0, B <= 65535; no workspace)
+hipError_t launch_conv1_train_dgrad(const float *dz, const float *weight, int B, int H, int W, float *dx, hipStream_t st);
 // dW [128][64][3][3] (and db [128] unless NULL) of the same convolution from dz and a1; workspace: conv2_wgrad_workspace_bytes(conv2_wgrad_streams())
 size_t conv2_wgrad_workspace_bytes(int nstreams);
 int conv2_wgrad_streams();

@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void k_bn_finish(const BnTrainArgs a, int nchu
 template <int P>
 __global__ __launch_bounds__(256) void k_bn_relu_pool_fwd(const BnTrainArgs a) {
     constexpr int CHUNK = BnShape<P>::CHUNK, NK = BnShape<P>::NK;
-    const int c = blockIdx.y, cpp = a.H * a.W / CHUNK;
+    const int c = blockIdx.y, cpp = (a.H * a.W + CHUNK - 1) / CHUNK;       // (P == 1 from given statistics: the plane's last chunk may be partial)
     const int b = blockIdx.x / cpp, ch = blockIdx.x - b * cpp;
     const size_t plane = ((size_t)b * a.C + c) * a.H * a.W;
     const float *zp = a.z + plane + (size_t)ch * CHUNK;
@@ -96,6 +96,7 @@ __global__ __launch_bounds__(256) void k_bn_relu_pool_fwd(const BnTrainArgs a) {
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
         const int off = bn_off<P>(threadIdx.x, k, a.W);
+        if (P == 1 && ch * CHUNK + off >= a.H * a.W) break;
         const float4 v = *reinterpret_cast<const float4 *>(zp + off);
         float4 y = make_float4(fmaxf(v.x * sc + sh, 0.f), fmaxf(v.y * sc + sh, 0.f), fmaxf(v.z * sc + sh, 0.f), fmaxf(v.w * sc + sh, 0.f));
         if (P == 1) *reinterpret_cast<float4 *>(a.out + plane + (size_t)ch * CHUNK + off) = y;
@@ -112,7 +113,7 @@ __global__ __launch_bounds__(256) void k_bn_relu_pool_fwd(const BnTrainArgs a) {
 template <int P, int MODE>
 __global__ __launch_bounds__(256) void k_bn_relu_pool_bwd(const BnTrainArgs a) {
     constexpr int CHUNK = BnShape<P>::CHUNK, NK = BnShape<P>::NK;
-    const int c = blockIdx.y, cpp = a.H * a.W / CHUNK;
+    const int c = blockIdx.y, cpp = (a.H * a.W + CHUNK - 1) / CHUNK;
     const int b = blockIdx.x / cpp, ch = blockIdx.x - b * cpp;
     const size_t plane = ((size_t)b * a.C + c) * a.H * a.W;
     const float *zp = a.z + plane + (size_t)ch * CHUNK;
@@ -133,6 +134,7 @@ __global__ __launch_bounds__(256) void k_bn_relu_pool_bwd(const BnTrainArgs a) {
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
         const int off = bn_off<P>(threadIdx.x, k, a.W);
+        if (P == 1 && ch * CHUNK + off >= a.H * a.W) break;
         const float4 v = *reinterpret_cast<const float4 *>(zp + off);
         float4 go = make_float4(gcell, gcell, gcell, gcell);
         if (P == 1) go = *reinterpret_cast<const float4 *>(a.dout + plane + (size_t)ch * CHUNK + off);
@@ -155,7 +157,7 @@ __global__ __launch_bounds__(256) void k_bn_relu_pool_bwd(const BnTrainArgs a) {
 
 static int bn_chunks(const BnTrainArgs &a) {
     const int chunk = a.pool == 8 ? 16384 : 4096;
-    return a.B * (a.H * a.W / chunk);
+    return a.B * ((a.H * a.W + chunk - 1) / chunk);           // whole chunks, but for pool 1 from given statistics (smk_bn_relu_pool_phase)
 }
 
 long long bn_train_workspace_floats(int B, int C, int H, int W, int pool) {

@@ -79,7 +79,9 @@ class PerturbationTester:
 
     def adversarial_test(self, model: nn.Module, test_data: torch.Tensor, epsilon: float = 0.1, num_steps: int = 10) -> Dict:
         """PGD on the reconstruction error (perturbation_tests.py:54-98): {'adversarial_feature_stability',
-        'adversarial_perturbation_norm'}.  The gradient is taken with respect to the perturbation only (module docstring)."""
+        'adversarial_perturbation_norm'}.  The gradient is taken with respect to the perturbation only (module docstring): with every
+        parameter frozen, a SmokePhysNet with input_grad == "hip" serves 128^2 / 256^2 frames on its libsmokehip route (forward and
+        backward; no MIOpen call), and anything else on the PyTorch modules."""
         model.eval()
         delta = torch.zeros_like(test_data, requires_grad=True)
         params = [p for p in model.parameters() if p.requires_grad]

@@ -7,10 +7,14 @@ from torch import nn
 from .. import _lib
 
 
+def conv2_module_ok(conv: nn.Conv2d) -> bool:
+    return (conv.in_channels == 64 and conv.out_channels == 128 and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
+            and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros")
+
+
 def hip_conv2_train_supported(x: torch.Tensor, conv: nn.Conv2d) -> bool:
-    return (x.dim() == 4 and x.is_cuda and x.dtype == torch.float32 and conv.in_channels == 64 and conv.out_channels == 128
-            and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1)
-            and conv.groups == 1 and conv.padding_mode == "zeros" and x.shape[1] == 64 and x.shape[2] % 8 == 0 and x.shape[3] % 16 == 0)
+    return (x.dim() == 4 and x.is_cuda and x.dtype == torch.float32 and conv2_module_ok(conv) and x.shape[1] == 64 and x.shape[2] % 8 == 0
+            and x.shape[3] % 16 == 0)
 
 
 class _HipConv2Fn(torch.autograd.Function):
@@ -79,12 +83,28 @@ def hip_conv2_train(x: torch.Tensor, conv: nn.Conv2d, hip_forward: bool = True, 
     return _HipConv2Fn.apply(x, conv.weight, conv.bias, bool(hip_forward), bool(hip_wgrad))
 
 
+def hip_conv2_frozen(x: torch.Tensor, conv: nn.Conv2d) -> torch.Tensor:
+    """hip_conv2_train with the weight and bias as constants: the gradient flows to x only (k_conv2_dgrad_b16)."""
+    if not hip_conv2_train_supported(x, conv):
+        raise ValueError("hip_conv2_frozen: a float32 ROCm tensor [B, 64, H, W] with H % 8 == 0, W % 16 == 0 and Conv2d(64, 128, 3, padding=1)")
+    return _HipConv2Fn.apply(x, conv.weight.detach(), None if conv.bias is None else conv.bias.detach(), True, True)
+
+
 # ---------------------------------------------------------------- the first convolution: Conv2d(1, 64, 7, padding=3) (smokephys_net.py:25)
+def _conv1_module_ok(conv: nn.Conv2d) -> bool:
+    return (conv.in_channels == 1 and conv.out_channels == 64 and conv.kernel_size == (7, 7) and conv.stride == (1, 1)
+            and conv.padding == (3, 3) and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros")
+
+
+def hip_conv1_frozen_supported(x: torch.Tensor, conv: nn.Conv2d) -> bool:
+    """The forward and the data gradient (k_conv1_train_fwd / k_conv1_train_dgrad) take any H and W % 4 == 0."""
+    return (x.dim() == 4 and x.is_cuda and x.dtype == torch.float32 and _conv1_module_ok(conv) and x.shape[1] == 1 and x.shape[2] >= 1
+            and x.shape[3] >= 4 and x.shape[3] % 4 == 0 and 1 <= x.shape[0] <= 65535)
+
+
 def hip_conv1_train_supported(x: torch.Tensor, conv: nn.Conv2d) -> bool:
-    return (x.dim() == 4 and x.is_cuda and x.dtype == torch.float32 and conv.in_channels == 1 and conv.out_channels == 64
-            and conv.kernel_size == (7, 7) and conv.stride == (1, 1) and conv.padding == (3, 3) and conv.dilation == (1, 1)
-            and conv.groups == 1 and conv.padding_mode == "zeros" and x.shape[1] == 1 and x.shape[2] % 4 == 0 and x.shape[3] % 64 == 0
-            and x.shape[0] <= 65535)
+    """... and the weight gradient (k_conv1_train_wgrad) tiles of 4 rows x 64 columns."""
+    return hip_conv1_frozen_supported(x, conv) and x.shape[2] % 4 == 0 and x.shape[3] % 64 == 0
 
 
 class _HipConv1Fn(torch.autograd.Function):
@@ -118,15 +138,24 @@ class _HipConv1Fn(torch.autograd.Function):
                                                ws.data_ptr(), _lib.stream_ptr(x.device)))
             if not ctx.needs_input_grad[1]:
                 dw = None
-        if ctx.needs_input_grad[0]:                         # (train.py's frames carry no gradient; a caller that wants dX gets PyTorch-ROCm's)
-            dx = torch.ops.aten.convolution_backward(dz, x, weight, None, [1, 1], [3, 3], [1, 1], False, [0, 0], 1, [True, False, False])[0]
+        if ctx.needs_input_grad[0]:                         # train.py's frames carry no gradient; PGD / saliency callers do (k_conv1_train_dgrad)
+            dx = torch.empty_like(x)
+            _lib.check(L.smk_conv1_train_dgrad(dz.data_ptr(), weight.detach().contiguous().data_ptr(), B, H, W, dx.data_ptr(),
+                                               _lib.stream_ptr(x.device)))
         return dx, dw, db
 
 
 def hip_conv1_train(x: torch.Tensor, conv: nn.Conv2d) -> torch.Tensor:
-    """conv(x) for the encoder's 1 -> 64 7x7 convolution under autograd on libsmokehip (k_conv1_train_fwd / k_conv1_train_wgrad: plain fp32 on
-    the vector ALUs).  Raises off a ROCm device: no CPU fallback."""
+    """conv(x) for the encoder's 1 -> 64 7x7 convolution under autograd on libsmokehip (k_conv1_train_fwd / k_conv1_train_wgrad /
+    k_conv1_train_dgrad: plain fp32 on the vector ALUs).  Raises off a ROCm device: no CPU fallback."""
     if not hip_conv1_train_supported(x, conv):
         raise ValueError("hip_conv1_train: a float32 ROCm tensor [B, 1, H, W] with H % 4 == 0, W % 64 == 0 and Conv2d(1, 64, 7, padding=3)")
     return _HipConv1Fn.apply(x, conv.weight, conv.bias)
 
+
+def hip_conv1_frozen(x: torch.Tensor, conv: nn.Conv2d) -> torch.Tensor:
+    """conv(x) with the weight and bias as constants: the same node, the gradient flows to x only (k_conv1_train_dgrad), so the weight
+    gradient's tile rule does not apply -- any H, W % 4 == 0."""
+    if not hip_conv1_frozen_supported(x, conv):
+        raise ValueError("hip_conv1_frozen: a float32 ROCm tensor [B, 1, H, W] with W % 4 == 0, B <= 65535 and Conv2d(1, 64, 7, padding=3)")
+    return _HipConv1Fn.apply(x, conv.weight.detach(), None if conv.bias is None else conv.bias.detach())

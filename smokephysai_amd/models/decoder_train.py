@@ -7,7 +7,7 @@ import torch
 from torch import nn
 
 from .. import _lib
-from .norm import hip_bn_relu_pool, hip_sync_bn_relu_pool
+from .norm import hip_bn_relu_pool, hip_frozen_bn_relu_pool, hip_sync_bn_relu_pool
 from .sync_bn import SyncBatchNorm2d
 
 _TOKENS = 1024               # forward_tokens always reshapes to a 32 x 32 token grid
@@ -20,13 +20,7 @@ def _convt_ok(m, cin_mult: int, cout: int) -> bool:
             and m.padding_mode == "zeros" and m.bias is not None)
 
 
-def hip_head_train_supported(head: nn.Sequential, tokens) -> bool:
-    """Whether hip_head_train serves this call: the default head structure (ConvT(C0, 32) + BN + ReLU, ConvT(32, 16) + BN + ReLU,
-    Conv2d(16, 1, 3, padding 1) + Sigmoid) for any C0 that is a multiple of 16, both BatchNorms in the form the libsmokehip
-    BatchNorm kernels implement (smokephys_net._hip_bn_ok: training mode, affine, running statistics, fixed momentum), float32
-    parameters, and float32 ROCm tokens [B, 1024, C0] with 1 <= B <= 65535.  Anything else -- the float64 copies tests make, CPU
-    tensors, a frozen BatchNorm, another head -- runs the PyTorch modules."""
-    from .smokephys_net import _hip_bn_ok
+def _head_ok(head: nn.Sequential, tokens, bn_ok) -> bool:
     try:
         if len(head) != 8:
             return False
@@ -37,11 +31,33 @@ def hip_head_train_supported(head: nn.Sequential, tokens) -> bool:
           and (c3.in_channels, c3.out_channels) == (16, 1) and c3.kernel_size == (3, 3) and c3.stride == (1, 1) and c3.padding == (1, 1)
           and c3.dilation == (1, 1) and c3.groups == 1 and c3.padding_mode == "zeros" and c3.bias is not None
           and type(r1) is nn.ReLU and type(r2) is nn.ReLU and type(sg) is nn.Sigmoid
-          and _hip_bn_ok(b1) and _hip_bn_ok(b2) and b1.num_features == 32 and b2.num_features == 16)
+          and bn_ok(b1) and bn_ok(b2) and b1.num_features == 32 and b2.num_features == 16)
     if not ok or not all(p.dtype == torch.float32 for p in head.parameters()):
         return False
     return (bool(tokens.is_cuda) and tokens.dtype == torch.float32 and tokens.dim() == 3 and tokens.shape[1] == _TOKENS
             and tokens.shape[2] == c1.in_channels and 1 <= tokens.shape[0] <= 65535)
+
+
+def hip_head_train_supported(head: nn.Sequential, tokens) -> bool:
+    """Whether hip_head_train serves this call: the default head structure (ConvT(C0, 32) + BN + ReLU, ConvT(32, 16) + BN + ReLU,
+    Conv2d(16, 1, 3, padding 1) + Sigmoid) for any C0 that is a multiple of 16, both BatchNorms in the form the libsmokehip
+    BatchNorm kernels implement (smokephys_net._hip_bn_ok: training mode, affine, running statistics, fixed momentum), float32
+    parameters, and float32 ROCm tokens [B, 1024, C0] with 1 <= B <= 65535.  Anything else -- the float64 copies tests make, CPU
+    tensors, a frozen BatchNorm, another head -- runs the PyTorch modules."""
+    from .smokephys_net import _hip_bn_ok
+    return _head_ok(head, tokens, _hip_bn_ok)
+
+
+def frozen_bn_ok(bn) -> bool:
+    """An eval-mode plain affine nn.BatchNorm2d with running statistics: what hip_frozen_bn_relu_pool computes."""
+    return (type(bn) is nn.BatchNorm2d and not bn.training and bn.affine and bn.track_running_stats and bn.running_mean is not None
+            and bn.running_var is not None)
+
+
+def hip_head_frozen_supported(head: nn.Sequential, tokens) -> bool:
+    """Whether hip_head_frozen serves this call: the same head structure and tokens as hip_head_train_supported, both BatchNorms in eval
+    mode (frozen_bn_ok) and no head parameter asking for a gradient -- the gradient goes to the tokens only."""
+    return _head_ok(head, tokens, frozen_bn_ok) and not any(p.requires_grad for p in head.parameters())
 
 
 class _HipConvT4s2Fn(torch.autograd.Function):
@@ -144,3 +160,20 @@ def hip_head_train(head: nn.Sequential, tokens: torch.Tensor) -> torch.Tensor:
     a1 = _bn_relu(hip_convt4s2_train(tokens, c1, tokens=True), b1)
     a2 = _bn_relu(hip_convt4s2_train(a1, c2), b2)
     return hip_conv3_sigmoid_train(a2, c3)
+
+
+class _Detached:
+    """A convolution module seen with its weight and bias as constants (the nodes read .weight / .bias only)."""
+
+    def __init__(self, conv):
+        self.weight, self.bias = conv.weight.detach(), conv.bias.detach()
+
+
+def hip_head_frozen(head: nn.Sequential, tokens: torch.Tensor) -> torch.Tensor:
+    """reconstruction_head(tokens.transpose(1, 2).reshape(B, C0, 32, 32)) in eval mode under autograd on libsmokehip, differentiable with
+    respect to the tokens only: the three convolution nodes of hip_head_train with detached weights, the BatchNorms from their running
+    statistics (hip_frozen_bn_relu_pool).  Nothing of the head is updated.  Call only where hip_head_frozen_supported(head, tokens) holds."""
+    c1, b1, _, c2, b2, _, c3, _ = head
+    a1 = hip_frozen_bn_relu_pool(hip_convt4s2_train(tokens, _Detached(c1), tokens=True), b1, 1)
+    a2 = hip_frozen_bn_relu_pool(hip_convt4s2_train(a1, _Detached(c2)), b2, 1)
+    return hip_conv3_sigmoid_train(a2, _Detached(c3))

@@ -152,3 +152,56 @@ def hip_sync_bn_relu_pool(z: torch.Tensor, bn, pool: int = 1) -> torch.Tensor:
         bn.running_var.mul_(1 - m).add_(gstats[1], alpha=m * nn_ / max(nn_ - 1.0, 1.0))
         bn.num_batches_tracked += 1
     return out
+
+
+# ---------------------------------------------------------------- frozen statistics (eval mode) under autograd: gradients to z only
+def hip_frozen_bn_relu_pool_supported(z: torch.Tensor, pool: int) -> bool:
+    """The kernels' shape rule: pool in {1, 4, 8} and, when pooling, W == 32 * pool (whole 4,096- / 16,384-float chunks); at pool 1 the two
+    element-wise passes take any plane of whole float4s."""
+    if z.dim() != 4 or not z.is_cuda or z.dtype != torch.float32 or not 1 <= z.shape[1] <= 65535:
+        return False
+    H, W = z.shape[-2:]
+    if pool == 1:
+        return (H * W) % 4 == 0
+    return pool in (4, 8) and W == 32 * pool and H % pool == 0 and (H * W) % (16384 if pool == 8 else 4096) == 0
+
+
+class _HipFrozenBnReluPoolFn(torch.autograd.Function):
+    """blockmean(relu((z - mean) * rstd * gamma + beta)) with every per-channel tensor a constant: SMK_BN_APPLY forward, SMK_BN_BWD_DZ with zero
+    dgamma / dbeta and count 1 backward -- exactly dz = gamma * rstd * dy * [y > 0], dy = dout / P^2 spread over the P x P block."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, mean, rstd, pool):
+        dev = _lib.require_cuda(z.device, "hip_frozen_bn_relu_pool")
+        L = _lib.load()
+        z = z.contiguous()
+        B, C, H, W = z.shape
+        out = torch.empty(B, C, H // pool, W // pool, device=dev, dtype=torch.float32)
+        _phase(L, BN_APPLY, z, None, gamma, beta, 0.0, mean, None, rstd, pool, out, None, None, None, 0.0, None, dev)
+        ctx.save_for_backward(z, gamma, beta, mean, rstd)
+        ctx.pool = pool
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        z, gamma, beta, mean, rstd = ctx.saved_tensors
+        L = _lib.load()
+        dout = dout.contiguous()
+        dz = torch.empty_like(z)
+        zero = torch.zeros(z.shape[1], device=z.device, dtype=torch.float32)
+        _phase(L, BN_BWD_DZ, z, dout, gamma, beta, 0.0, mean, None, rstd, ctx.pool, None, dz, zero, zero, 1.0, None, z.device)
+        return dz, None, None, None, None, None
+
+
+def hip_frozen_bn_relu_pool(z: torch.Tensor, bn: nn.BatchNorm2d, pool: int = 1) -> torch.Tensor:
+    """blockmean_pool(relu(bn(z))) with bn's RUNNING statistics (what an eval-mode nn.BatchNorm2d computes), differentiable with respect to
+    z only: gamma, beta and the statistics are constants, and nothing of bn is updated.  z [B, C, H, W] float32 on a ROCm device."""
+    if not (bn.affine and bn.track_running_stats and bn.running_mean is not None):
+        raise ValueError("hip_frozen_bn_relu_pool: an affine BatchNorm2d with running statistics")
+    if not hip_frozen_bn_relu_pool_supported(z, pool):
+        raise ValueError("hip_frozen_bn_relu_pool: a float32 ROCm tensor [B, C, H, W] with pool in {1, 4, 8}, W == 32 * pool when pooling")
+    with torch.no_grad():
+        rstd = torch.rsqrt(bn.running_var.float() + bn.eps).contiguous()
+        mean = bn.running_mean.float().contiguous()
+        gamma, beta = bn.weight.detach().float().contiguous(), bn.bias.detach().float().contiguous()
+    return _HipFrozenBnReluPoolFn.apply(z, gamma, beta, mean, rstd, int(pool))

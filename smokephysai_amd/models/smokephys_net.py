@@ -11,6 +11,9 @@ token mean are PyTorch-ROCm ops.
 Training (train mode): the encoder runs as autograd-tracked PyTorch ops with batch-statistics BatchNorm, exactly the
 reference's op sequence (smokephys_net.py:87-91).  With head_train="hip" the reconstruction head trains on libsmokehip too
 (models/decoder_train.py): its three convolutions and two BatchNorms, forward and backward, with no MIOpen call.
+Input gradients (eval mode, autograd on, parameters frozen: PGD, saliency): with input_grad="hip" (default) 128^2 / 256^2 frames run the
+training route's convolution kernels with BatchNorm from the running statistics, and the head its three convolution nodes -- forward and
+backward on libsmokehip (_encoder_route's 'hip_grad').
 """
 import os
 import warnings
@@ -23,13 +26,14 @@ import torch.nn.functional as F
 from .attention import hip_layernorm_supported, hip_layernorm_train
 from .chaos_attention import ChaosAttention
 from .decoder import HipDecoder, decoder_weight_dict, hip_decoder_supported
-from .decoder_train import hip_head_train, hip_head_train_supported
+from .decoder_train import frozen_bn_ok, hip_head_frozen, hip_head_frozen_supported, hip_head_train, hip_head_train_supported
 from .encoder import HipEncoder, encoder_weight_dict, hip_encoder_supported
 from .hip_body import HipBody
 from .ffn import hip_dropout_add, hip_ffn_elementwise_supported, hip_gelu_dropout
 from .linear import TrainableHipLinear, hip_linear_supported
-from .conv import hip_conv1_train, hip_conv1_train_supported, hip_conv2_train, hip_conv2_train_supported
-from .norm import hip_bn_relu_pool, hip_sync_bn_relu_pool
+from .conv import (conv2_module_ok, hip_conv1_frozen, hip_conv1_frozen_supported, hip_conv1_train, hip_conv1_train_supported,
+                   hip_conv2_frozen, hip_conv2_train, hip_conv2_train_supported)
+from .norm import hip_bn_relu_pool, hip_frozen_bn_relu_pool, hip_sync_bn_relu_pool
 from .sync_bn import SyncBatchNorm2d
 from .physics_regularizer import PhysicsRegularizer
 
@@ -75,6 +79,18 @@ def _bn_relu_pool(z, bn, pool):
     return hip_sync_bn_relu_pool(z, bn, pool) if isinstance(bn, SyncBatchNorm2d) else hip_bn_relu_pool(z, bn, pool)
 
 
+def hip_input_grad_supported(H: int, W: int, input_dim: int, *, eval_mode: bool = True, on_device: bool = True, grad_enabled: bool = True,
+                             input_requires_grad: bool = True, params_require_grad: bool = False, frozen_bn: bool = True) -> bool:
+    """Whether the 'hip_grad' encoder route (eval mode, gradient with respect to the frames only) serves a call.  Pure: no device, no
+    library.  The frames are the ones the training route's kernels take -- square 128 or 256, one P x P block mean (P = H / 32) standing
+    for both adaptive pools (input_dim a multiple of 32 that divides H) -- as float32 on a ROCm device (on_device); autograd is on, the
+    frames want a gradient and no parameter of input_encoder does; both BatchNorms are eval-mode plain affine BatchNorm2d with
+    running statistics (frozen_bn)."""
+    H, W, input_dim = int(H), int(W), int(input_dim)
+    shape = H == W and H in (128, 256) and input_dim > 0 and input_dim % 32 == 0 and H % input_dim == 0
+    return bool(shape and eval_mode and on_device and grad_enabled and input_requires_grad and not params_require_grad and frozen_bn)
+
+
 def _mlp(din: int, dhid: int, dout: int, linear=nn.Linear) -> nn.Sequential:
     return nn.Sequential(linear(din, dhid), nn.ReLU(inplace=True), linear(dhid, dout))
 
@@ -82,7 +98,7 @@ def _mlp(din: int, dhid: int, dout: int, linear=nn.Linear) -> nn.Sequential:
 class SmokePhysNet(nn.Module):
     def __init__(self, input_dim: int = 128, hidden_dim: int = 512, num_layers: int = 6, num_heads: int = 8,
                  output_channels: int = 64, chaos_strength: float = 0.1, encoder_dtype: str = "bf16x3",
-                 linear_dtype: str = "bf16x3", head_train: str = "torch"):
+                 linear_dtype: str = "bf16x3", head_train: str = "torch", input_grad: Optional[str] = None):
         super().__init__()
         self.input_dim = input_dim
         self.hidden_dim = hidden_dim
@@ -92,6 +108,8 @@ class SmokePhysNet(nn.Module):
             raise ValueError("linear_dtype: 'bf16x3' (libsmokehip split-bf16 MFMA kernel) or 'f32' (PyTorch-ROCm GEMMs)")
         self.linear_dtype = linear_dtype
         self.head_train = head_train
+        if input_grad is not None:
+            self.input_grad = input_grad
         # Construction order and Sequential indices follow the reference exactly: that fixes both the state_dict keys
         # (input_encoder.{0,1,3,4}, reconstruction_head.{0,1,3,4,6}, ...) and the RNG stream of the default initialisation.
         self.input_encoder = nn.Sequential(*_conv_block(1, 64, 7), *_conv_block(64, 128, 3),
@@ -126,6 +144,22 @@ class SmokePhysNet(nn.Module):
             raise ValueError(f"head_train: 'torch' (PyTorch modules) or 'hip' (libsmokehip kernels), not {value!r}")
         self.__dict__["_head_train"] = value
 
+    # eval-mode forward under autograd with frozen parameters (PGD, saliency: d / d frames): "hip" the libsmokehip route -- conv1 / conv2 with
+    # their data-gradient kernels, BatchNorm from the running statistics, the head's three convolution nodes -- wherever
+    # hip_input_grad_supported / hip_head_frozen_supported hold; "torch" the PyTorch modules (MIOpen convolutions and BatchNorms).  Default
+    # "hip": a fresh-process adversarial_test(num_steps=10) at 8 x 128^2 takes 1.12 s on it against 4.59 s on the modules
+    INPUT_GRAD_DEFAULT = "hip"
+
+    @property
+    def input_grad(self) -> str:
+        return self.__dict__.get("_input_grad", type(self).INPUT_GRAD_DEFAULT)
+
+    @input_grad.setter
+    def input_grad(self, value: str) -> None:
+        if value not in ("torch", "hip"):
+            raise ValueError(f"input_grad: 'torch' (PyTorch modules) or 'hip' (libsmokehip kernels), not {value!r}")
+        self.__dict__["_input_grad"] = value
+
     # copy.deepcopy / pickling of the module: the libsmokehip handles are per-instance device mirrors, rebuilt on first use
     def __getstate__(self):
         d = self.__dict__.copy()
@@ -155,7 +189,9 @@ class SmokePhysNet(nn.Module):
     def _encoder_route(self, x: torch.Tensor) -> str:
         """Which implementation of input_encoder + pools serves this call:
         'train'   -- module in train mode: batch statistics (and their running update), as nn.BatchNorm2d does with or without grad;
-        'modules' -- eval mode, but a gradient is wanted through the encoder (the fused kernel is forward-only), or a frame shape the
+        'hip_grad'-- eval mode, autograd on, a gradient wanted with respect to the frames ONLY (every encoder parameter frozen), frames of
+                     128^2 / 256^2 and input_grad == "hip": the training route's convolution kernels with frozen-statistics BatchNorm;
+        'modules' -- eval mode, but any other gradient is wanted through the encoder (the fused kernel is forward-only), or a frame shape the
                      fused kernel is not built for on a ROCm device (a warning is issued once);
         'hip'     -- the fused libsmokehip encoder (eval, no gradient; raises off-GPU: no CPU fallback)."""
         if self.training:
@@ -163,6 +199,8 @@ class SmokePhysNet(nn.Module):
         if not x.is_cuda:
             return "hip"                           # eval off-GPU: the product refuses (no CPU fallback)
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.input_encoder.parameters())):
+            if self.input_grad == "hip" and self.linear_dtype == "bf16x3" and x.dim() == 4 and self._input_grad_ok(x):
+                return "hip_grad"
             if not self.__dict__.get("_warned_grad"):
                 self.__dict__["_warned_grad"] = True
                 warnings.warn("SmokePhysNet: eval forward with autograd enabled runs the differentiable PyTorch-ROCm route; wrap inference in "
@@ -177,11 +215,33 @@ class SmokePhysNet(nn.Module):
             return "modules"
         return "hip"
 
+    def _input_grad_ok(self, x: torch.Tensor) -> bool:
+        """hip_input_grad_supported for this call, plus the module structure the 'hip_grad' branch of encode_frames unpacks."""
+        enc = self.input_encoder
+        if len(enc) != 7 or not isinstance(enc[6], nn.AdaptiveAvgPool2d):
+            return False
+        conv1, bn1, _, conv2, bn2, _, pool = enc
+        size = pool.output_size if isinstance(pool.output_size, tuple) else (pool.output_size, pool.output_size)
+        H, W = x.shape[-2:]
+        return (size[0] == size[1] == self.input_dim
+                and hip_input_grad_supported(H, W, self.input_dim, eval_mode=not self.training,
+                                             on_device=x.is_cuda and x.dtype == torch.float32 and x.shape[1] == 1,
+                                             grad_enabled=torch.is_grad_enabled(), input_requires_grad=x.requires_grad,
+                                             params_require_grad=any(p.requires_grad for p in enc.parameters()),
+                                             frozen_bn=frozen_bn_ok(bn1) and frozen_bn_ok(bn2))
+                and type(conv1) is nn.Conv2d and type(conv2) is nn.Conv2d and bn1.num_features == 64 and bn2.num_features == 128
+                and hip_conv1_frozen_supported(x, conv1)
+                and conv2_module_ok(conv2))
+
     def encode_frames(self, x: torch.Tensor, dtype: Optional[str] = None) -> torch.Tensor:
         """input_encoder + both pools (smokephys_net.py:87-91): [B,1,H,W] -> [B,128,32,32]."""
         route = self._encoder_route(x)
         if route == "modules":                     # eval-mode BatchNorm through the PyTorch-ROCm modules (differentiable; any frame size)
             return F.adaptive_avg_pool2d(self.input_encoder(x), (32, 32))
+        if route == "hip_grad":                    # d / d frames with everything else a constant: no MIOpen call, no find pass
+            conv1, bn1, _, conv2, bn2, _, _ = self.input_encoder
+            a1 = hip_frozen_bn_relu_pool(hip_conv1_frozen(x, conv1), bn1, 1)
+            return hip_frozen_bn_relu_pool(hip_conv2_frozen(a1, conv2), bn2, x.shape[-1] // 32)
         if route == "train":
             conv1, bn1, _, conv2, bn2, _, pool = self.input_encoder
             H, W = x.shape[-2:]
@@ -348,6 +408,9 @@ class SmokePhysNet(nn.Module):
             output_features = self.output_decoder(features)
         if self.training and self.head_train == "hip" and hip_head_train_supported(self.reconstruction_head, output_features):
             reconstructed = hip_head_train(self.reconstruction_head, output_features)      # tokens read in place, no transpose
+        elif (not self.training and self.input_grad == "hip" and torch.is_grad_enabled() and output_features.requires_grad
+                and hip_head_frozen_supported(self.reconstruction_head, output_features)):
+            reconstructed = hip_head_frozen(self.reconstruction_head, output_features)     # d / d tokens only, BatchNorms from running statistics
         elif (not self.training and not torch.is_grad_enabled() and self.linear_dtype == "bf16x3" and output_features.is_cuda
                 and output_features.dtype == torch.float32 and output_features.shape[2] == 64
                 and hip_decoder_supported(self.reconstruction_head, pool_size)):

@@ -139,13 +139,14 @@ def validate_epoch(model: nn.Module, val_loader: DataLoader, physics_regularizer
 
 
 def build_model(config: dict):
-    """SmokePhysNet from the config's `model` section and the optional `mi355x` keys (encoder_dtype, recon_head), on the CPU."""
+    """SmokePhysNet from the config's `model` section and the optional `mi355x` keys (encoder_dtype, recon_head, input_grad), on the CPU."""
     from smokephysai_amd.models.smokephys_net import SmokePhysNet
     hw = config.get("mi355x", {}) or {}
     return SmokePhysNet(input_dim=config["model"]["input_dim"], hidden_dim=config["model"]["hidden_dim"],
                         num_layers=config["model"]["num_layers"], num_heads=config["model"]["num_heads"],
                         chaos_strength=config["model"]["chaos_strength"],
-                        encoder_dtype=hw.get("encoder_dtype", "bf16x3"), head_train=str(hw.get("recon_head", "torch")))
+                        encoder_dtype=hw.get("encoder_dtype", "bf16x3"), head_train=str(hw.get("recon_head", "torch")),
+                        input_grad=None if hw.get("input_grad") is None else str(hw["input_grad"]))
 
 
 def data_loader_kwargs(config: dict, rank: int = 0, world: int = 1) -> dict:
