@@ -388,6 +388,25 @@ constexpr bool jb_pipelined(int vec, int rpw, bool persist) { return !(persist &
 // (profiles/r07): one row ahead is the fastest split at 4 cells per lane; with none the stores are exposed, with all of them the reads.
 constexpr int jb_rows_before_barrier(int rpw) { return rpw > 2 ? 1 : 0; }
 
+// The keep buffer of the PERSIST && FOLD form: the diffused u2 / v2 rows a band owns wait in LDS between the prologue and the gradient
+// epilogue instead of going to HBM and back.  Beside `edge` (64 rows) and the flag word a workgroup, alone on its CU anyway, may declare
+// the rest of the 160 KiB: that many rows of 64 * vec floats, at most the 2 * 16 * rpw a band can own.
+constexpr int JB_LDS_BYTES = 163840;
+constexpr int jb_keep_rows(int vec, int rpw) {
+    if (vec == 4 && rpw == 8) return 0;                       // at the 128-VGPR cap already (see jb_pipelined): the slot arithmetic would add spills
+    const int row_bytes = 256 * vec, fit = (JB_LDS_BYTES - 64 * row_bytes - 16) / row_bytes;
+    return fit < 2 * JB_NW * rpw ? fit : 2 * JB_NW * rpw;
+}
+// A band's owned rows are numbered v(own0), u(own0), v(own0 + 1), ... (u row 0 of the grid, which the gradient leaves alone, has no
+// number): n of them.  With more rows than slots every (n / slots)-th row, in 16.16 fixed point, goes without one, so the rows that
+// stay on the HBM path are spread evenly over the waves of the band rather than falling on its last waves.  The scale is rounded up,
+// which for n <= 256 rows uses every slot and none twice.
+__host__ __device__ constexpr int jb_keep_scale(int n, int slots) { return n <= slots ? 65536 : (slots * 65536 + n - 1) / n; }
+__host__ __device__ constexpr int jb_keep_slot(int idx, int scale) {      // the row's slot, or -1: no slot
+    const int s = (idx * scale) >> 16;
+    return (((idx + 1) * scale) >> 16) > s ? s : -1;
+}
+
 template <int VEC, int RPW, int MODE, bool PERSIST = false, bool FOLD = false>
 __global__ __launch_bounds__(JB_NW * 64) void k_jacobi_band(Geom g, const float *__restrict__ p_in,
                                                             float *__restrict__ p_out, float *__restrict__ div,
@@ -396,6 +415,10 @@ __global__ __launch_bounds__(JB_NW * 64) void k_jacobi_band(Geom g, const float 
     constexpr int TR = JB_NW * RPW, ROWF = 64 * VEC;
     __shared__ float edge[2][JB_NW][2][ROWF];
     __shared__ int handoff_failed;                            // PERSIST: lane 0 saw a timed-out / aborted hand-off wait -> poison the band's results
+    constexpr bool KEEP = PERSIST && FOLD && jb_keep_rows(VEC, RPW) > 0;
+    constexpr int KROWS = KEEP ? jb_keep_rows(VEC, RPW) : 1;
+    __shared__ __attribute__((aligned(16))) float keep[KROWS][ROWF];      // KEEP: u2 / v2 rows between prologue and epilogue (slot: keep_of)
+    static_assert(sizeof(edge) + sizeof(keep) + 16 <= JB_LDS_BYTES, "edge + keep + the flag word exceed the CU's LDS");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // Bands own unequal row ranges: the first and last band of a grid need a halo only on their inner side (the other side is the
     // physical boundary), so they own TR - HALO rows and the middle bands TR - 2 HALO (HALO = BR here).  One band: the whole grid.
@@ -429,6 +452,15 @@ __global__ __launch_bounds__(JB_NW * 64) void k_jacobi_band(Geom g, const float 
     const size_t base = b * g.sc + (size_t)row0 * g.pc + j0;
     float pv[RPW][VEC], dv[RPW][VEC];
     const bool first_col = lane == 0, last_col = lane == 63;
+    // KEEP: slot of the owned u (field 1) / v (field 0) row gi, -1 when the row takes the HBM path.  Wave-uniform; only the wave that
+    // wrote a slot reads it, so no barrier orders the two.
+    const int u_first = own0 > 1 ? own0 : 1;
+    const int keep_scale = jb_keep_scale((own1 - u_first) + (own1 - own0), KROWS);
+    auto keep_of = [&](int gi, int field) {
+        const int first = field ? u_first : own0;
+        const int s = (gi >= first && gi < own1) ? jb_keep_slot(2 * (gi - first) + field, keep_scale) : -1;
+        return __builtin_amdgcn_readfirstlane(s);
+    };
     if constexpr (FOLD) {
         // ---- buoyancy + the three diffusions (navier_stokes.py:154-160; per cell the expression trees of k_buoy_diffuse4) for the
         // tile's rows, each wave for itself from the step's input state: u2 rows row0 .. row0+RPW, v2 / d2 rows row0 .. row0+RPW-1.
@@ -478,7 +510,12 @@ __global__ __launch_bounds__(JB_NW * 64) void k_jacobi_band(Geom g, const float 
                 const float sl = wave_shr1(uc[VEC - 1]), sr = wave_shl1(uc[0]);
                 lap(uc, um, un, first_col ? uc[0] : sl, last_col ? uc[VEC - 1] : sr, g.coef_uv, u2);
             }
-            if ((gi >= own0 && gi < own1) || (gi == H && band == nb - 1)) stv<VEC>(uo + (size_t)gi * g.pc + j0, u2);
+            // (rows 0 and H of u are final as they are: always to HBM.  The row after the wave's last, k = RPW, is the next wave's first:
+            // with KEEP that wave alone puts it away, so a slot has one writer, which is also its reader)
+            const bool mine = !KEEP || k < RPW;
+            const int ku = KEEP && k < RPW ? keep_of(gi, 1) : -1;
+            if (ku >= 0) stv<VEC>(&keep[ku][j0], u2);
+            else if ((mine && gi >= own0 && gi < own1) || (gi == H && band == nb - 1)) stv<VEC>(uo + (size_t)gi * g.pc + j0, u2);
             if (k > 0) {
 #pragma unroll
                 for (int c = 0; c < VEC; ++c) {
@@ -509,8 +546,10 @@ __global__ __launch_bounds__(JB_NW * 64) void k_jacobi_band(Geom g, const float 
                 const float v2W = vWc + g.coef_uv * lw;
                 if (gi >= own0 && gi < own1) {
                     stv<VEC>(dout + (size_t)gi * g.pc + j0, d2);
-                    stv<VEC>(vo + (size_t)gi * g.pv + j0, v2);
-                    if (last_col) vo[(size_t)gi * g.pv + W] = v2W;
+                    const int kv = KEEP ? keep_of(gi, 0) : -1;
+                    if (kv >= 0) stv<VEC>(&keep[kv][j0], v2);
+                    else stv<VEC>(vo + (size_t)gi * g.pv + j0, v2);
+                    if (last_col) vo[(size_t)gi * g.pv + W] = v2W;     // (column W is final as it is)
                 }
                 const float nx = wave_shl1(v2[0]);
 #pragma unroll
@@ -757,8 +796,11 @@ __global__ __launch_bounds__(JB_NW * 64) void k_jacobi_band(Geom g, const float 
                 // whole-row read-modify-write (VEC cells per lane as one load / one store; the untouched cells -- row 0 of u, column 0
                 // of v -- are written back unchanged)
                 float un[VEC], vn[VEC];
-                ldv<VEC>(un, ub + (size_t)k * g.pc);
-                ldv<VEC>(vn, vb + (size_t)k * g.pv);
+                const int ku = KEEP ? keep_of(gi, 1) : -1, kv = KEEP ? keep_of(gi, 0) : -1;
+                if (ku >= 0) ldv<VEC>(un, &keep[ku][j0]);
+                else ldv<VEC>(un, ub + (size_t)k * g.pc);
+                if (kv >= 0) ldv<VEC>(vn, &keep[kv][j0]);
+                else ldv<VEC>(vn, vb + (size_t)k * g.pv);
 #pragma unroll
                 for (int c = 0; c < VEC; ++c) {
                     if (gi >= 1) {                            // gi == row0 == 0 only in the first wave of band 0: skipped
@@ -1075,11 +1117,30 @@ hipError_t launch_buoy_project(const Geom &g, StateView in, StateView out, float
     return launch_project(g, out.u, out.v, p, out.p, div, iters, st, ps);
 }
 
+// The persistent launch with the folded prologue keeps a band's diffused u / v rows in LDS (k_jacobi_band, KEEP): slots per band, the
+// rows of one grid that get a slot, and the most rows any band leaves on the HBM path -- by the kernel's own numbering and slot function.
+struct KeepStats { int slots, kept_per_grid, max_overflow; };
+static KeepStats keep_stats(const Geom &g, const JacobiPlan &pl) {
+    KeepStats ks{jb_keep_rows(pl.vec, pl.rpw), 0, 0};
+    const int TR = JB_NW * pl.rpw, e_rows = TR - pl.halo, m_rows = TR - 2 * pl.halo;
+    for (int band = 0; band < pl.nb; ++band) {
+        const int own0 = band == 0 ? 0 : e_rows + (band - 1) * m_rows;
+        int own1 = band == pl.nb - 1 ? g.H : e_rows + band * m_rows;
+        own1 = own1 < g.H ? own1 : g.H;
+        const int n = (own1 - (own0 > 1 ? own0 : 1)) + (own1 - own0), scale = jb_keep_scale(n, ks.slots);
+        int kept = 0;
+        for (int idx = 0; idx < n; ++idx) kept += jb_keep_slot(idx, scale) >= 0;
+        ks.kept_per_grid += kept;
+        if (n - kept > ks.max_overflow) ks.max_overflow = n - kept;
+    }
+    return ks;
+}
+
 // What one projection launches for this geometry, as a JSON object (bench.py reports it as the stencil pass's on-chip bound: the
 // Jacobi sweeps never touch HBM, so what limits them is sweeps x rows per workgroup x vector-issue time, not bytes).
 std::string describe_projection(const Geom &g, int iters, const ProjectSync *ps) {
     JacobiPlan pl;
-    char buf[1792];
+    char buf[2048];
     int chunks = 0;
     const bool persist = use_persist(g, ps, iters, pl, chunks);
     if (!persist && (iters < 2 || !plan_jacobi(g, pl, iters) || pl.halo < 3)) {
@@ -1097,14 +1158,17 @@ std::string describe_projection(const Geom &g, int iters, const ProjectSync *ps)
     // software-pipelined under those rows; what the in-kernel stamps show beyond the estimate is the four waves of a SIMD taking turns at its
     // vector issue, the youngest last, with the others waiting for it at the sweep's barrier (profiles/r07)
     const double valu_us_per_sweep = rounds * (TR / 4.0) * 18.0 * 2.6 / 2100.0;
+    // (the keep buffer belongs to the form launch_buoy_project folds the step's first stage into: the conditions are its own)
+    const KeepStats ks = persist && pl.vec <= 4 && g.pv % 4 == 0 && g.pc % 4 == 0 ? keep_stats(g, pl) : KeepStats{0, 0, 0};
     snprintf(buf, sizeof buf,
              "{\"kernel\": \"k_jacobi_band<%d,%d>\", \"persistent\": %s, \"bands_per_grid\": %d, \"rows_per_workgroup\": %d, \"halo_rows\": %d, "
              "\"workgroups\": %d, \"launches\": %d, \"halo_handoffs\": %d, \"sweeps\": %d, \"sweeps_per_chunk\": %d, \"redundant_row_factor\": %.3f, "
+             "\"keep_rows_per_band\": %d, \"keep_overflow_rows_max\": %d, \"keep_rows_per_grid\": %d, "
              "\"vector_issue_us_per_sweep_estimate\": %.3f, \"vector_issue_us_total_estimate\": %.1f, "
              "\"bound\": \"on-chip: sweeps x vector issue of rows_per_workgroup rows, one barrier per sweep (%s); p and div are "
              "register-resident %s\"}",
              pl.vec, pl.rpw, persist ? "true" : "false", pl.nb, TR, pl.halo, (int)wgs, L, persist ? chunks - 1 : 0, iters, (iters + parts - 1) / parts,
-             (double)pl.nb * TR / g.H, valu_us_per_sweep, valu_us_per_sweep * iters,
+             (double)pl.nb * TR / g.H, ks.slots, ks.max_overflow, ks.kept_per_grid, valu_us_per_sweep, valu_us_per_sweep * iters,
              jb_pipelined(pl.vec, pl.rpw, persist)
                  ? "the LDS edge-row exchange is pipelined over two sweeps: a wave's two edge rows and their publish come first, the interior rows "
                    "cover the stores and the read of the next sweep's neighbour rows"
