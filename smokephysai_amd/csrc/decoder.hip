@@ -8,6 +8,13 @@
 // quad (2i+py, 2j+px).  y = 2 iy - 1 + ky, so row parity 0 takes (ky 1, iy i) and (ky 3, iy i-1), parity 1 takes (ky 0, iy i+1)
 // and (ky 2, iy i); columns likewise: 16 FMAs per (input channel, output channel) on the 3x3 neighbourhood of (i, j).
 // Weights are indexed by wave-uniform values only, so they travel through the scalar path (s_load -> SGPR FMA operands).
+//
+// launch_decoder picks one of three forms from (B, S) (S % 16 == 0: smk_decoder_forward) and the process-wide SMK_DECODER_SMALL:
+//   small        B <= 8 (and SMK_DECODER_SMALL not 0)    k_convt4s2_small<64,32,true>, k_convt4s2_small<32,16,false>
+//   tiled, OG 2  otherwise, (S/16)^2 * 4 * B < 256        k_convt4s2<64,32,2,true>,     k_convt4s2<32,16,2,false>
+//   tiled, OG 8  otherwise                                k_convt4s2<64,32,8,true>,     k_convt4s2<32,16,8,false>
+// k_conv3_sigmoid<8,32> follows in every form (4S is a multiple of 32).  All three forms run the same fmaf chain per output element:
+// their tmp1, tmp2 and recon are bit-identical (tests/test_hip_decoder.py reaches every row and holds them equal).
 #include "decoder.h"
 
 #include <stdlib.h>
@@ -224,8 +231,8 @@ hipError_t launch_decoder(const DecoderDev &d, const float *tokens, int B, int S
     }
     // (a no-LDS form of the last convolution for small batches -- every thread its 144 taps from L1 / L2 -- was built and measured 20 us
     //  SLOWER per batch-1 forward, interleaved on one box; removed)
-    if ((4 * S) % 32 == 0) hipLaunchKernelGGL((k_conv3_sigmoid<8, 32>), dim3(t3, 1, B), dim3(256), 0, st, tmp2, d.w3, d.b3, recon, 4 * S, 4 * S);
-    else hipLaunchKernelGGL((k_conv3_sigmoid<DC_T, DC_T>), dim3(t3, 1, B), dim3(256), 0, st, tmp2, d.w3, d.b3, recon, 4 * S, 4 * S);
+    // S % 16 == 0 (smk_decoder_forward): the 4S x 4S image is whole 8 x 32 tiles, t3 of them
+    hipLaunchKernelGGL((k_conv3_sigmoid<8, 32>), dim3(t3, 1, B), dim3(256), 0, st, tmp2, d.w3, d.b3, recon, 4 * S, 4 * S);
     return hipGetLastError();
 }
 

@@ -6,6 +6,7 @@ import torch
 from torch import nn
 
 from .. import _lib
+from .decoder_train import _convt_ok, frozen_bn_ok
 
 _KEYS = ("ct1_w", "ct1_b", "bn1_w", "bn1_b", "bn1_mean", "bn1_var", "ct2_w", "ct2_b", "bn2_w", "bn2_b", "bn2_mean", "bn2_var",
          "conv_w", "conv_b")
@@ -20,18 +21,32 @@ def decoder_weight_dict(head: nn.Sequential) -> dict:
 
 
 def hip_decoder_supported(head: nn.Sequential, S: int) -> bool:
-    """Shapes the HIP kernels are built for: the default head (64 -> 32 -> 16 -> 1 channels), token grid side % 16 == 0."""
+    """Whether smk_decoder_forward computes this head on an S x S token grid.  Pure: no device, no library.  Everything the kernels
+    hard-code is checked, as strictly as the training-side predicate (decoder_train._head_ok with frozen_bn_ok):
+      - exactly 8 modules: ConvTranspose2d, BatchNorm2d, ReLU, ConvTranspose2d, BatchNorm2d, ReLU, Conv2d, Sigmoid (exact types);
+      - both transposed convolutions kernel 4, stride 2, padding 1, output_padding 0, dilation 1, groups 1, zero padding, with bias,
+        64 -> 32 and 32 -> 16 channels;
+      - the last convolution 16 -> 1, kernel 3, stride 1, padding 1, dilation 1, groups 1, zero padding, with bias;
+      - both BatchNorms plain nn.BatchNorm2d in eval mode, affine, with running statistics (frozen_bn_ok), 32 and 16 features, and
+        eps == 1e-5 (k_fold_decoder folds with that constant);
+      - every parameter and buffer of the head float32;
+      - S >= 16 and S % 16 == 0 (the tiled kernels' 16 x 16 tiles).
+    Any other head runs the PyTorch modules (forward_tokens)."""
     try:
-        c1, c2, c3 = head[0], head[3], head[6]
-        ok = (isinstance(c1, nn.ConvTranspose2d) and isinstance(c2, nn.ConvTranspose2d) and isinstance(c3, nn.Conv2d)
-              and (c1.in_channels, c1.out_channels, c2.in_channels, c2.out_channels, c3.in_channels, c3.out_channels) == (64, 32, 32, 16, 16, 1)
-              and c1.kernel_size == (4, 4) and c1.stride == (2, 2) and c1.padding == (1, 1) and c1.output_padding == (0, 0)
-              and c2.kernel_size == (4, 4) and c2.stride == (2, 2) and c2.padding == (1, 1) and c2.output_padding == (0, 0)
-              and c3.kernel_size == (3, 3) and c3.padding == (1, 1) and c1.bias is not None and c2.bias is not None
-              and c3.bias is not None and isinstance(head[7], nn.Sigmoid))
-    except (IndexError, AttributeError):
+        if len(head) != 8:
+            return False
+        c1, b1, r1, c2, b2, r2, c3, sg = head
+    except (TypeError, ValueError):
         return False
-    return ok and S >= 16 and S % 16 == 0
+    ok = (_convt_ok(c1, 64, 32) and c1.in_channels == 64 and _convt_ok(c2, 32, 16) and c2.in_channels == 32 and type(c3) is nn.Conv2d
+          and (c3.in_channels, c3.out_channels) == (16, 1) and c3.kernel_size == (3, 3) and c3.stride == (1, 1) and c3.padding == (1, 1)
+          and c3.dilation == (1, 1) and c3.groups == 1 and c3.padding_mode == "zeros" and c3.bias is not None
+          and type(r1) is nn.ReLU and type(r2) is nn.ReLU and type(sg) is nn.Sigmoid
+          and frozen_bn_ok(b1) and frozen_bn_ok(b2) and b1.num_features == 32 and b2.num_features == 16
+          and b1.eps == 1e-5 and b2.eps == 1e-5)
+    if not ok or not all(t.dtype == torch.float32 for t in decoder_weight_dict(head).values()):
+        return False
+    return S >= 16 and S % 16 == 0
 
 
 class HipDecoder:
