@@ -464,9 +464,11 @@ int smk_reduce_shards(const void *shards, int32_t in_dtype, int32_t world, int64
  *   forward:  z [B][C][H][W], gamma / beta [C], eps -> out [B][C][H/pool][W/pool] = blockmean(relu(bn(z))), and the batch
  *             statistics mean / var (biased) / rstd [C] (the caller updates running_mean / running_var from them);
  *   backward: dout [B][C][H/pool][W/pool] -> dz [B][C][H][W], dgamma / dbeta [C]; the ReLU mask is recomputed from z.
- * pool in {1, 4, 8}; H * W a multiple of 4,096 (pool 8: 16,384); pool > 1 needs W == 32 * pool.  `workspace`:
- * smk_bn_train_workspace(B, C, H, W, pool) bytes of device memory (partial sums), caller-owned.  Reductions are two-stage
- * in a fixed order (deterministic).  Enqueued on `stream`. */
+ * pool in {1, 2, 4, 8, 16, 32} (frames of 64 .. 1024 pooled to 32 x 32); H * W a whole number of chunks -- 4,096 floats at pool 1, 2 and
+ * 4, 16,384 at pool 8, 8,192 at pool 16 and 32,768 at pool 32 (one row of cells) -- and pool > 1 needs W == 32 * pool; anything else is
+ * SMK_ERR_UNSUPPORTED.  `workspace`: smk_bn_train_workspace(B, C, H, W, pool) bytes of device memory (one pair of partial sums per chunk
+ * and channel), caller-owned.  Reductions are two-stage in a fixed order (deterministic; at pool 16 and 32 a cell's lanes are added by a
+ * fixed butterfly).  Enqueued on `stream`. */
 int64_t smk_bn_train_workspace(int32_t B, int32_t C, int32_t H, int32_t W, int32_t pool);
 int smk_bn_relu_pool_forward(const float *z, int32_t B, int32_t C, int32_t H, int32_t W, const float *gamma, const float *beta,
                              double eps, int32_t pool, float *out, float *mean, float *var, float *rstd, void *workspace,
@@ -519,7 +521,7 @@ int smk_conv2_train_wgrad(const float *dz, const float *a1, int32_t B, int32_t H
  *   SMK_BN_BWD_DZ    dz from the GIVEN (all-reduced) dgamma / dbeta and count = elements per channel of the GLOBAL batch.
  * Frozen (running) statistics under autograd are these two element-wise phases alone: SMK_BN_APPLY with mean / rstd from the running
  * statistics, and SMK_BN_BWD_DZ with zero dgamma / dbeta and count = 1, which is exactly dz = gamma * rstd * dy * [y > 0].  At pool 1 they
- * take any plane with H * W % 4 == 0 (the reductions keep whole 4,096-float chunks). */
+ * take any plane with H * W % 4 == 0 (the reductions keep whole 4,096-float chunks); every pool of the fused calls is served. */
 enum smk_bn_phase { SMK_BN_STATS = 0, SMK_BN_APPLY = 1, SMK_BN_BWD_SUMS = 2, SMK_BN_BWD_DZ = 3 };
 int smk_bn_relu_pool_phase(int32_t phase, const float *z, const float *dout, int32_t B, int32_t C, int32_t H, int32_t W, const float *gamma,
                            const float *beta, double eps, float *mean, float *var, float *rstd, int32_t pool, float *out, float *dz,

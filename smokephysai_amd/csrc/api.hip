@@ -1362,10 +1362,12 @@ int smk_attention_backward(const float *q, const float *k, const float *v, const
 // ------------------------------------------------------------------ training-mode BatchNorm + ReLU + pool
 static int bn_check(int32_t B, int32_t C, int32_t H, int32_t W, int32_t pool) {
     SMK_REQUIRE(B >= 1 && C >= 1 && H >= 1 && W >= 1, "positive sizes");
-    const int64_t chunk = pool == 8 ? 16384 : 4096;
-    if (!(pool == 1 || pool == 4 || pool == 8) || ((int64_t)H * W) % chunk != 0 || (pool > 1 && (W != 32 * pool || H % pool != 0)) ||
+    // the rule and the chunk are norm.h's (bn_pool_built / bn_chunk_floats): the grids and the workspace size derive from the same two
+    const int64_t chunk = bn_pool_built(pool) ? bn_chunk_floats(pool) : 1;
+    if (!bn_pool_built(pool) || ((int64_t)H * W) % chunk != 0 || (pool > 1 && (W != 32 * pool || H % pool != 0)) ||
         (int64_t)B * (H * (int64_t)W / chunk) >= (1LL << 31) || C > 65535) {
-        set_error("bn_relu_pool: HIP path is built for pool in {1, 4, 8}, H * W a multiple of 4096 (pool 8: 16384), W == 32 * pool when pooling");
+        set_error("bn_relu_pool: HIP path is built for pool in {1, 2, 4, 8, 16, 32}, H * W a multiple of 4096 (pool 8: 16384, pool 16: 8192, "
+                  "pool 32: 32768), W == 32 * pool when pooling");
         return SMK_ERR_UNSUPPORTED;
     }
     return SMK_OK;

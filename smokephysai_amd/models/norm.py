@@ -6,12 +6,18 @@ from torch import nn
 from .. import _lib
 
 
+# floats of one plane per workgroup, by pool (bn_chunk_floats in csrc/norm.h, which bn_check, the workspace and the grids derive from)
+BN_CHUNK_FLOATS = {1: 4096, 2: 4096, 4: 4096, 8: 16384, 16: 8192, 32: 32768}
+
+
 def hip_bn_relu_pool_supported(z: torch.Tensor, pool: int) -> bool:
+    """The training kernels' shape rule (bn_check in csrc/api.hip): a float32 ROCm tensor [B, C, H, W], pool in {1, 2, 4, 8, 16, 32}, planes of
+    whole chunks, and when pooling W == 32 * pool (the pooled map is 32 cells wide) with H a multiple of pool."""
     if z.dim() != 4 or not z.is_cuda or z.dtype != torch.float32:
         return False
     H, W = z.shape[-2:]
-    chunk = 16384 if pool == 8 else 4096
-    return pool in (1, 4, 8) and (H * W) % chunk == 0 and (pool == 1 or (W == 32 * pool and H % pool == 0))
+    chunk = BN_CHUNK_FLOATS.get(pool)
+    return chunk is not None and (H * W) % chunk == 0 and (pool == 1 or (W == 32 * pool and H % pool == 0))
 
 
 class _HipBnReluPoolFn(torch.autograd.Function):

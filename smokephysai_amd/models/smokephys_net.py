@@ -73,6 +73,8 @@ def _hip_bn_ok(bn) -> bool:
 # "0" the whole convolution on PyTorch-ROCm (diagnostic switches)
 _HIP_CONV2_TRAIN = os.environ.get("SMK_TRAIN_CONV2_HIP", "1")
 _HIP_CONV1_TRAIN = os.environ.get("SMK_TRAIN_CONV1_HIP", "1") != "0"      # diagnostic: 0 keeps the first convolution on PyTorch-ROCm
+# diagnostic: 0 sends the whole train-mode encoder down the generic PyTorch-ROCm branch (the A side of tools/train_sizes_probe.py)
+_HIP_ENCODER_TRAIN = os.environ.get("SMK_TRAIN_ENCODER_HIP", "1") != "0"
 
 
 def _bn_relu_pool(z, bn, pool):
@@ -89,6 +91,15 @@ def hip_input_grad_supported(H: int, W: int, input_dim: int, *, eval_mode: bool 
     H, W, input_dim = int(H), int(W), int(input_dim)
     shape = H == W and H in (128, 256) and input_dim > 0 and input_dim % 32 == 0 and H % input_dim == 0
     return bool(shape and eval_mode and on_device and grad_enabled and input_requires_grad and not params_require_grad and frozen_bn)
+
+
+def hip_train_encoder_supported(H: int, W: int, input_dim: int) -> bool:
+    """Whether the train-mode encoder route of encode_frames (conv1 / conv2 with their gradient kernels, batch-statistics BatchNorm + ReLU and
+    the P x P block mean, P = H / 32 in {2, 4, 8, 16, 32}, all on libsmokehip) serves frames of H x W.  Pure: no device, no library.  True
+    exactly where the fused eval-mode encoder takes the frames (hip_encoder_supported): square 64 / 128 / 256 / 512 / 1024 and an input_dim
+    that is a multiple of 32 and a divisor or a whole multiple of H -- in both cases the two adaptive pools (-> input_dim, -> 32) compose
+    to the one (H / 32)^2 block mean (input_dim = 128 on 64^2 frames: the first pool repeats every cell 2 x 2, the second averages that)."""
+    return hip_encoder_supported(H, W, input_dim)
 
 
 def _mlp(din: int, dhid: int, dout: int, linear=nn.Linear) -> nn.Sequential:
@@ -246,12 +257,12 @@ class SmokePhysNet(nn.Module):
             conv1, bn1, _, conv2, bn2, _, pool = self.input_encoder
             H, W = x.shape[-2:]
             P = H // 32
-            mid = pool.output_size[0]              # first pool target; no up-sampling stage and whole-number windows: one P x P mean
-            if (self.linear_dtype == "bf16x3" and x.is_cuda and x.dtype == torch.float32 and H == W and P in (4, 8) and W == 32 * P
-                    and _hip_bn_ok(bn1) and _hip_bn_ok(bn2)
-                    and pool.output_size[0] == pool.output_size[1] and H % mid == 0 and mid % 32 == 0):
+            mid = pool.output_size[0]              # first pool target: with the second (-> 32) one P x P mean wherever the predicate holds
+            if (_HIP_ENCODER_TRAIN and self.linear_dtype == "bf16x3" and x.is_cuda and x.dtype == torch.float32 and hip_train_encoder_supported(H, W, mid)
+                    and _hip_bn_ok(bn1) and _hip_bn_ok(bn2) and pool.output_size[0] == pool.output_size[1]):
                 # libsmokehip: BatchNorm (batch statistics) + ReLU as two passes over the conv output, and for the second block
-                # the two average pools (one P x P block mean) in the same pass -- the 256 x 256 x 128 maps are never written
+                # the two average pools (one P x P block mean, P = 2 .. 32 for frames of 64 .. 1024) in the same pass -- the full-size
+                # 128-channel maps are never written
                 z1 = hip_conv1_train(x, conv1) if (_HIP_CONV1_TRAIN and hip_conv1_train_supported(x, conv1)) else conv1(x)
                 a1 = _bn_relu_pool(z1, bn1, 1)
                 z2 = (hip_conv2_train(a1, conv2, hip_forward=_HIP_CONV2_TRAIN not in ("grads", "dgrad"), hip_wgrad=_HIP_CONV2_TRAIN != "dgrad")
