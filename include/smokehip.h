@@ -581,6 +581,23 @@ int smk_attention_backward(const float *q, const float *k, const float *v, const
 int smk_attention_delta(const float *dout, const float *out, int64_t rows, int32_t H, int32_t head_dim, int64_t ld_dout, int64_t ld_out,
                         float *delta, void *stream);
 
+/* The softmax weights of that attention, which the flash kernel keeps in registers only (chaos_attention.py:100-108: the `attn_weights`
+ * the reference's SmokeVisualizer.plot_attention_maps takes, visualization.py:80, 102).  From q and k as smk_attention takes them (fp32,
+ * the chaos term folded into q) and lse [B][L][H] as smk_attention_forward_lse writes it (log2 units):
+ *     p_ij = 2^(scale * log2(e) * q_i.k_j - lse_i)          (split-bf16 MFMA, the forward's products)
+ * smk_attention_received: recv [B][H][ld_recv], recv[b][h][j] = (1 / L) sum_i p_ij -- the attention key j receives (visualization.py:102,
+ * `attn.mean(axis=0)`), without any L x L tensor; columns 0 .. L-1 of a row are written, each exactly once, in a summation order that
+ * depends on (B, L, H) only (no atomics: a repeated call is bit-identical).
+ * smk_attention_probs: the matrices themselves for batches b0 .. b0+nb-1 and heads h0 .. h0+nh-1 of the B x H the tensors hold:
+ * probs [nb][nh][L][ld_probs], probs[..][i][j] = p_ij (visualization.py:80 plots [0, 0]); bit for bit the slice of the full call.
+ * Limits as smk_attention: head_dim == 64 and L % 128 == 0 (else SMK_ERR_UNSUPPORTED); B * L * ld < 2^29 floats for q and k, pitches
+ * multiples of 4 floats, 16-byte aligned q and k, ld_recv / ld_probs >= L (else SMK_ERR_INVALID).  Nothing is written on an error. */
+int smk_attention_received(const float *q, const float *k, const float *lse, float *recv, int32_t B, int32_t L, int32_t H,
+                           int32_t head_dim, int64_t ldq, int64_t ldk, int64_t ld_recv, double scale, void *stream);
+int smk_attention_probs(const float *q, const float *k, const float *lse, float *probs, int32_t B, int32_t L, int32_t H,
+                        int32_t head_dim, int32_t b0, int32_t nb, int32_t h0, int32_t nh, int64_t ldq, int64_t ldk, int64_t ld_probs,
+                        double scale, void *stream);
+
 /* nn.LayerNorm over the last dimension (smokephys_net.py:149-150, applied at :161,:165; biased variance, eps as given):
  * x [rows][ldx] -> y [rows][ldy], weight / bias [D].  D % 4 == 0, D <= 2048 (else SMK_ERR_UNSUPPORTED).
  * y_format: smk_format of y (split: D % 8 == 0, dense rows, ldy == D). */

@@ -8,7 +8,9 @@ Simulates the reference's 3-source test scene for 20 frames, runs the model over
   inference_metrics.json  per frame i: SSIM / PSNR / MSE of prediction i against ground-truth frame i+1 (RobustnessEvaluator's
                           image_quality, one launch); written only when the prediction and frame shapes match
   comparison.png          the reference's ground truth vs prediction figure (frames first, middle, last), unless --no_plots
-The reference's SmokeVisualizer plots (seaborn) are not drawn.
+  attention_maps.png      with --attention-maps [LAYER] (default layer: the last): SmokeVisualizer.plot_attention_maps of the first frame --
+                          the frame, the attention matrix of (batch 0, head 0) and the attention the tokens receive (head 0), both from
+                          SmokePhysNet.attention_maps (libsmokehip kernels: no [B, heads, L, L] tensor)
 """
 import argparse
 import json
@@ -77,13 +79,30 @@ def save_comparison(ground_truth: np.ndarray, predictions: np.ndarray, path: str
     plt.close(fig)
 
 
-def main():
+def save_attention_maps(model, sequence: torch.Tensor, layer: int, path: str):
+    """attention_maps.png for the first frame: layer `layer` (negative: from the last), the matrix of (batch 0, head 0) and head 0's received map."""
+    from smokephysai_amd.utils import SmokeVisualizer
+    import matplotlib.pyplot as plt
+    frame = sequence[:1, None].contiguous()
+    layer = layer % len(model.chaos_layers)
+    out = model.attention_maps(frame, layers=[layer], probs_for=(0, 1, 0, 1))
+    fig = SmokeVisualizer().plot_attention_maps(out["attention_probs"][layer], frame, save_path=path, received=out["attention_received"][layer])
+    plt.close(fig)
+
+
+def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(description="SmokePhysAI Inference Script")
     parser.add_argument("--config", type=str, default="config/config.yaml", help="Path to configuration file")
     parser.add_argument("--checkpoint", type=str, required=True, help="Path to model checkpoint")
     parser.add_argument("--output_dir", type=str, default=".", help="Directory the outputs are written to")
     parser.add_argument("--no_plots", action="store_true", help="Do not write comparison.png")
-    args = parser.parse_args()
+    parser.add_argument("--attention-maps", dest="attention_maps", type=int, nargs="?", const=-1, default=None, metavar="LAYER",
+                        help="Write attention_maps.png for transformer layer LAYER (default: the last one)")
+    return parser
+
+
+def main():
+    args = build_parser().parse_args()
     config = load_config(args.config)
     if not torch.cuda.is_available():
         raise RuntimeError("inference.py needs a ROCm GPU: smokephysai_amd has no CPU fallback")
@@ -109,6 +128,8 @@ def main():
         print(f"predictions {tuple(pred.shape[1:])} and frames {tuple(gt.shape[1:])} differ in shape: no inference_metrics.json")
     if not args.no_plots:
         save_comparison(gt, pred, os.path.join(args.output_dir, "comparison.png"))
+    if args.attention_maps is not None:
+        save_attention_maps(model, sequence, args.attention_maps, os.path.join(args.output_dir, "attention_maps.png"))
     print(f"Results have been saved to {args.output_dir}")
 
 

@@ -8,7 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SMOKEHIP_LIB") or os.path.join(_HERE, "libsmokehip.so")   # SMOKEHIP_LIB: diagnostic builds only
 
 ABI_VERSION = 17                 # include/smokehip.h SMK_ABI_VERSION this binding was written against (tests/test_abi.py holds them equal)
-SMK_ERR_TIMEOUT = -5
+SMK_OK, SMK_ERR_INVALID, SMK_ERR_HIP, SMK_ERR_UNSUPPORTED, SMK_ERR_NO_DEVICE, SMK_ERR_TIMEOUT = 0, -1, -2, -3, -4, -5      # smk_status
 SMK_F32, SMK_BF16X3, SMK_BF16, SMK_I8X3 = 0, 1, 2, 3
 SMK_ACT_NONE, SMK_ACT_GELU, SMK_ACT_RELU = 0, 1, 2
 SMK_FMT_F32, SMK_FMT_SPLIT_BF16, SMK_FMT_SPLIT4_INPLACE = 0, 1, 2
@@ -120,6 +120,8 @@ _SIGNATURES = {
                          C.c_int64, C.c_int64, C.c_double, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p],
     "smk_attention_forward_lse": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_void_p],
+    "smk_attention_received": [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_int64] * 3 + [C.c_double, C.c_void_p],
+    "smk_attention_probs": [C.c_void_p] * 4 + [C.c_int32] * 8 + [C.c_int64] * 3 + [C.c_double, C.c_void_p],
     "smk_attention_delta": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p],
     "smk_attention_backward": [C.c_void_p] * 9 + [C.c_int32] * 4 + [C.c_int64] * 7 + [C.c_double, C.c_void_p],
     "smk_lorenz_states": [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p],

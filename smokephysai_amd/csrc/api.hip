@@ -1320,6 +1320,43 @@ int smk_attention_forward_lse(const float *q, const float *k, const float *v, fl
     return check_launch(launch_attention_x3(a, (hipStream_t)stream), "attention_x3");
 }
 
+// the softmax weights from q, k and the forward's lse (AttnMapArgs)
+static int attention_maps(const float *q, const float *k, const float *lse, float *out, int32_t B, int32_t L, int32_t H, int32_t head_dim,
+                          int32_t b0, int32_t nb, int32_t h0, int32_t nh, int64_t ldq, int64_t ldk, int64_t ldo, double scale, bool probs,
+                          void *stream) {
+    SMK_REQUIRE(q && k && lse && out, "null q/k/lse/out");
+    SMK_REQUIRE(B >= 1 && H >= 1 && L >= 128, "B >= 1, H >= 1, L >= 128");
+    if (head_dim != 64 || L % 128 != 0) {
+        set_error("attention maps: HIP path is built for head_dim 64 and L a multiple of 128");
+        return SMK_ERR_UNSUPPORTED;
+    }
+    SMK_REQUIRE(b0 >= 0 && nb >= 1 && b0 <= B - nb && h0 >= 0 && nh >= 1 && h0 <= H - nh, "batch / head range inside B x H");
+    const int64_t cols = (int64_t)H * 64;
+    SMK_REQUIRE(ldq >= cols && ldk >= cols && ldo >= L, "row pitches >= H * head_dim (q, k) and >= L (output)");
+    SMK_REQUIRE(ldq % 4 == 0 && ldk % 4 == 0, "q / k row pitches multiples of 4 floats");
+    SMK_REQUIRE((((uintptr_t)q | (uintptr_t)k) & 15) == 0 && ((uintptr_t)out & 3) == 0 && ((uintptr_t)lse & 3) == 0, "16-byte aligned q and k");
+    SMK_REQUIRE((int64_t)B * L * ldq < (1LL << 29) && (int64_t)B * L * ldk < (1LL << 29) && (int64_t)nb * nh * (L / 128) < (1LL << 31),
+                "B * L * ld < 2^29 floats (32-bit buffer offsets)");
+    AttnMapArgs a;
+    a.q = q; a.k = k; a.lse = lse; a.out = out;
+    a.ldq = (int)ldq; a.ldk = (int)ldk; a.ldo = ldo;
+    a.B = B; a.L = L; a.H = H;
+    a.b0 = b0; a.nb = nb; a.h0 = h0; a.nh = nh;
+    a.scale_log2e = (float)(scale * 1.4426950408889634074);
+    return check_launch(launch_attention_maps(a, probs, (hipStream_t)stream), probs ? "attention_probs" : "attention_received");
+}
+
+int smk_attention_received(const float *q, const float *k, const float *lse, float *recv, int32_t B, int32_t L, int32_t H,
+                           int32_t head_dim, int64_t ldq, int64_t ldk, int64_t ld_recv, double scale, void *stream) {
+    return attention_maps(q, k, lse, recv, B, L, H, head_dim, 0, B, 0, H, ldq, ldk, ld_recv, scale, false, stream);
+}
+
+int smk_attention_probs(const float *q, const float *k, const float *lse, float *probs, int32_t B, int32_t L, int32_t H,
+                        int32_t head_dim, int32_t b0, int32_t nb, int32_t h0, int32_t nh, int64_t ldq, int64_t ldk, int64_t ld_probs,
+                        double scale, void *stream) {
+    return attention_maps(q, k, lse, probs, B, L, H, head_dim, b0, nb, h0, nh, ldq, ldk, ld_probs, scale, true, stream);
+}
+
 int smk_attention_delta(const float *dout, const float *out, int64_t rows, int32_t H, int32_t head_dim, int64_t ld_dout, int64_t ld_out,
                         float *delta, void *stream) {
     SMK_REQUIRE(dout && out && delta && rows >= 0 && H >= 1, "null pointer / rows < 0 / H < 1");

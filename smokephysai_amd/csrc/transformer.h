@@ -50,6 +50,22 @@ hipError_t launch_attention_x3(const AttnArgs &a, hipStream_t st);
 // bytes of workspace with which launch_attention_x3 splits the keys over workgroups for this problem on the current device (0: it would not)
 size_t attention_workspace_bytes(int B, int L, int H);
 
+// The softmax weights of the same attention, which the flash kernel never stores (chaos_attention.py:100-108; the reference's figure:
+// visualization.py:80, 102): p_ij = 2^(s_ij - lse_i) from q, k and the forward's lse.  probs == false: the attention every key RECEIVES,
+// out [B][H][ldo] = (1 / L) sum_i p_ij (no L x L tensor; b0 = h0 = 0, nb = B, nh = H).  probs == true: the matrices themselves for batches
+// b0 .. b0 + nb - 1 and heads h0 .. h0 + nh - 1, out [nb][nh][L][ldo].
+struct AttnMapArgs {
+    const float *q, *k;                  // [B][L][ld*]: head h = columns 64h .. 64h+63 of a token row
+    const float *lse;                    // [B][L][H], log2 units (AttnArgs::lse)
+    float *out;
+    int ldq, ldk;
+    long long ldo;                       // pitch of a row of keys in out (>= L)
+    int B, L, H;
+    int b0, nb, h0, nh;
+    float scale_log2e;
+};
+hipError_t launch_attention_maps(const AttnMapArgs &a, bool probs, hipStream_t st);
+
 // Backward of the same attention (autograd of chaos_attention.py:102-112 with the chaos term folded into q): dq, dk, dv from q, k, v,
 // the output gradient, the forward's log-sum-exp and delta = rowsum(dout * out).
 struct AttnBwdArgs {

@@ -567,6 +567,154 @@ hipError_t launch_attention_x3(const AttnArgs &a, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// The softmax weights the kernel above never stores (AttnMapArgs): p_ij = 2^(s_ij - lse_i), the forward's roles swapped.
+// Workgroup = 256 threads = one (batch, head, 128-key block); wave w owns keys 32w..32w+31 with K (split, NOT scaled) in registers
+// as the B operand.  Q tiles of 64 queries are scaled by scale*log2 e, split and staged through the LDS image the forward uses for K
+// (row-major [query][d], pitch 144 B, double buffered), the tile's 64 lse values behind them.
+//   S = mfma(Q, K): the key is the lane (column r), the queries 32qb + (g&3) + 8(g>>2) + 4hh sit in accumulator register g, the other
+//       16 queries of the block in lane ^ 32.  The products run in the forward's order (lo*hi, hi*lo, hi*hi per k-step).
+//   PROBS = false: register g of every 32-query block is added to running sum g (L / 32 additions each, in tile order); the 16 sums
+//       are reduced by a fixed tree, the two lane halves exchanged once, and lane half 0 stores (1/L) of the total: no atomics, every
+//       element written once, each term passes L / 32 + 6 roundings.
+//   PROBS = true: the same registers are stored instead, 32 consecutive keys per store instruction and lane half.
+constexpr int AM_QPLANE = 64 * AT_KPITCH;                                      // 9216
+constexpr int AM_BUF = 2 * AM_QPLANE + 64 * 4;                                 // 18,688 B per tile (Q hi | lo, lse)
+
+template <bool PROBS>
+__global__ __launch_bounds__(256) void k_attention_recv(const AttnMapArgs a) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * AM_BUF];    // 37,376 B
+    const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, hh = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // the L/128 key blocks of one (batch, head) read the same Q: consecutive ids on one XCD, as in the forward
+    const int vid = (gridDim.x & 7) == 0 ? (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+    const int nkb = a.L / 128;
+    const int kb = vid % nkb, bh = vid / nkb, hi = bh % a.nh, bi = bh / a.nh, head = a.h0 + hi, b = a.b0 + bi;
+    const int NT = a.L / 64;
+    const int key = kb * 128 + wave * 32 + r;
+
+    // ---- K fragments (B operand: column = key r, k = d 16s + 8hh + j), split
+    bf16x8 kh[4], kl[4];
+    {
+        const float *kp = a.k + ((size_t)b * a.L + key) * a.ldk + head * 64 + 8 * hh;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const float4 v0 = *reinterpret_cast<const float4 *>(kp + 16 * s), v1 = *reinterpret_cast<const float4 *>(kp + 16 * s + 4);
+            const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const __bf16 t = (__bf16)f[j];
+                kh[s][j] = t;
+                kl[s][j] = (__bf16)(f[j] - (float)t);
+            }
+        }
+    }
+
+    // ---- Q staging through a buffer resource (offsets < 2^31: api.hip); thread = rows rq + 16j, columns 4c4 .. 4c4+3 of the tile
+    const int c4 = tid & 15, rq = tid >> 4;
+    const __amdgpu_buffer_rsrc_t qrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.q), 0, (int)((size_t)a.B * a.L * a.ldq * 4), 0x00020000);
+    const int lane_q = (rq * a.ldq + head * 64 + c4 * 4) * 4;
+    float4 qst[4];
+    float lst = 0.f;
+    auto stage_load = [&](int t) {
+        const int tt = t < NT ? t : NT - 1;                                    // past the end: a harmless re-read
+        const unsigned row0 = (unsigned)b * a.L + tt * 64;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const u32x4 qv = __builtin_amdgcn_raw_buffer_load_b128(qrs, (int)((row0 + 16 * j) * (unsigned)a.ldq * 4u) + lane_q, 0, 0);
+            qst[j] = make_float4(__uint_as_float(qv.x), __uint_as_float(qv.y), __uint_as_float(qv.z), __uint_as_float(qv.w));
+        }
+        if (tid < 64) lst = a.lse[((size_t)row0 + tid) * a.H + head];
+    };
+    auto stage_store = [&](int buf) {
+        unsigned char *base = smem + buf * AM_BUF;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {                                         // Q[query rq + 16j][d 4c4..], scaled before the split
+            const float4 v = make_float4(qst[j].x * a.scale_log2e, qst[j].y * a.scale_log2e, qst[j].z * a.scale_log2e, qst[j].w * a.scale_log2e);
+            bf16x4 h, l;
+            at_split4(v, h, l);
+            unsigned char *p = base + (rq + 16 * j) * AT_KPITCH + c4 * 8;
+            *reinterpret_cast<bf16x4 *>(p) = h;
+            *reinterpret_cast<bf16x4 *>(p + AM_QPLANE) = l;
+        }
+        if (tid < 64) reinterpret_cast<float *>(base + 2 * AM_QPLANE)[tid] = lst;
+    };
+
+    stage_load(0);
+    stage_store(0);
+    stage_load(1);
+    __syncthreads();
+
+    f32x16 racc;
+#pragma unroll
+    for (int g = 0; g < 16; ++g) racc[g] = 0.f;
+    float *prow = PROBS ? a.out + ((size_t)(bi * a.nh + hi) * a.L) * a.ldo + key : nullptr;
+
+#pragma unroll 1
+    for (int t = 0; t < NT; ++t) {
+        const unsigned char *base = smem + (t & 1) * AM_BUF;
+        const unsigned char *qb_h = base + r * AT_KPITCH + hh * 16;
+        // ---- S = Q K^T (log2 units): sacc[qb][g] = score(query 64t + 32qb + (g&3) + 8(g>>2) + 4hh, key r)
+        f32x16 sacc[2];
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+            for (int g = 0; g < 16; ++g) sacc[qb][g] = 0.f;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            bf16x8 qh[2], ql[2];
+#pragma unroll
+            for (int qb = 0; qb < 2; ++qb) {
+                qh[qb] = *reinterpret_cast<const bf16x8 *>(qb_h + qb * 32 * AT_KPITCH + s * 32);
+                ql[qb] = *reinterpret_cast<const bf16x8 *>(qb_h + AM_QPLANE + qb * 32 * AT_KPITCH + s * 32);
+            }
+#pragma unroll
+            for (int qb = 0; qb < 2; ++qb) sacc[qb] = AT_MFMA(ql[qb], kh[s], sacc[qb]);
+#pragma unroll
+            for (int qb = 0; qb < 2; ++qb) sacc[qb] = AT_MFMA(qh[qb], kl[s], sacc[qb]);
+#pragma unroll
+            for (int qb = 0; qb < 2; ++qb) sacc[qb] = AT_MFMA(qh[qb], kh[s], sacc[qb]);
+        }
+        // the staged registers hold tile t+1: write it to the other buffer (its last reads ended before the barrier that closed tile
+        // t-1), then re-issue the loads for tile t+2
+        if (t + 1 < NT) stage_store((t + 1) & 1);
+        stage_load(t + 2);
+
+        // ---- p = 2^(s - lse): the queries of register quad q4 are 4 consecutive lse values of the tile
+        const float *lp = reinterpret_cast<const float *>(base + 2 * AM_QPLANE) + 4 * hh;
+#pragma unroll
+        for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) {
+                const float4 l4 = *reinterpret_cast<const float4 *>(lp + 32 * qb + 8 * q4);
+                const float lv[4] = {l4.x, l4.y, l4.z, l4.w};
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float p = __builtin_amdgcn_exp2f(sacc[qb][4 * q4 + i] - lv[i]);
+                    if (PROBS) prow[(size_t)(t * 64 + 32 * qb + 8 * q4 + 4 * hh + i) * a.ldo] = p;
+                    else racc[4 * q4 + i] += p;
+                }
+            }
+        __syncthreads();                                       // tile t+1 visible; every read of tile t's buffer has returned
+    }
+    if (PROBS) return;
+    float s8[8], s4[4];
+#pragma unroll
+    for (int g = 0; g < 8; ++g) s8[g] = racc[2 * g] + racc[2 * g + 1];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) s4[g] = s8[2 * g] + s8[2 * g + 1];
+    const float half = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+    const float tot = half + __shfl_xor(half, 32);
+    if (hh == 0) a.out[((size_t)b * a.H + head) * a.ldo + key] = tot / (float)a.L;
+}
+
+hipError_t launch_attention_maps(const AttnMapArgs &a, bool probs, hipStream_t st) {
+    const dim3 grid(a.nb * a.nh * (a.L / 128));
+    if (probs) hipLaunchKernelGGL(k_attention_recv<true>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_attention_recv<false>, grid, dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // Backward of the attention above, same split-bf16 arithmetic (every product hi*hi + hi*lo + lo*hi, fp32 accumulate).
 // With s_ij = scale q_i.k_j, P = softmax(s) (recomputed from the saved log-sum-exp) and delta_i = sum_d dO_id O_id:
 //     dP_ij = dO_i.v_j      dS_ij = P_ij (dP_ij - delta_i)      dq_i = scale sum_j dS_ij k_j

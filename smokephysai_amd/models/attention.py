@@ -49,6 +49,91 @@ def hip_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: 
     return out
 
 
+def hip_attention_maps_supported(L: int, head_dim: int) -> bool:
+    """Whether smk_attention_received / smk_attention_probs take the shape: the flash kernel's own limits."""
+    return hip_attention_supported(L, head_dim)
+
+
+def _maps_operand(t: torch.Tensor) -> torch.Tensor:
+    L = t.shape[1]
+    ok = t.stride(2) == 1 and t.stride(0) == L * t.stride(1) and t.stride(1) % 4 == 0 and t.data_ptr() % 16 == 0
+    return t if ok else t.contiguous()
+
+
+def hip_attention_lse(q: torch.Tensor, k: torch.Tensor, num_heads: int, scale: float) -> torch.Tensor:
+    """lse [B, L, H] (log2 units) of softmax(q k^T * scale) from one smk_attention_forward_lse call per batch chunk; its attention output
+    (with k standing in for v) goes to scratch."""
+    dev = _lib.require_cuda(q.device, "hip_attention_lse")
+    B, L, D = q.shape
+    q, k = _maps_operand(q), _maps_operand(k)
+    lse = torch.empty(B, L, num_heads, device=dev, dtype=torch.float32)
+    bmax = max(1, (MAX_QKV_ELEMS - 1) // (L * max(q.stride(1), k.stride(1), D)))
+    scratch = torch.empty(min(B, bmax), L, D, device=dev, dtype=torch.float32)
+    for b0 in range(0, B, bmax):
+        nb = min(bmax, B - b0)
+        _lib.check(_lib.load().smk_attention_forward_lse(q[b0:].data_ptr(), k[b0:].data_ptr(), k[b0:].data_ptr(), scratch.data_ptr(),
+                                                         lse[b0:].data_ptr(), nb, L, num_heads, D // num_heads, q.stride(1), k.stride(1),
+                                                         k.stride(1), D, float(scale), _lib.stream_ptr(dev)))
+    return lse
+
+
+def hip_attention_maps(q: torch.Tensor, k: torch.Tensor, num_heads: int, scale: float, lse: Optional[torch.Tensor] = None,
+                       probs_for: Optional[tuple] = None):
+    """The softmax weights of hip_attention(q, k, ., num_heads, scale), which that kernel never stores: q, k [B, L, H*64] float32 on a ROCm
+    device (pitched slices allowed); lse [B, L, H] as smk_attention_forward_lse writes it, or None to compute it here.
+    Returns received [B, H, L] = the mean over the queries of softmax(q k^T * scale), the attention each key receives (no L x L tensor is
+    formed); with probs_for = (b0, nb, h0, nh) returns (received, probs [nb, nh, L, L]) for that batch and head range."""
+    dev = _lib.require_cuda(q.device, "hip_attention_maps")
+    if q.dim() != 3 or q.shape != k.shape or q.dtype != torch.float32 or k.dtype != torch.float32 or k.device != q.device:
+        raise ValueError("hip_attention_maps: q and k must be float32 [B, L, H*64] tensors of one shape on one device")
+    B, L, D = q.shape
+    H = num_heads
+    if D % H != 0 or not hip_attention_maps_supported(L, D // H):
+        raise ValueError(f"hip_attention_maps: head_dim 64 and L a multiple of 128, not L = {L}, head_dim = {D / H:g}")
+    q, k = _maps_operand(q), _maps_operand(k)
+    if lse is None:
+        lse = hip_attention_lse(q, k, H, scale)
+    elif lse.shape != (B, L, H) or lse.dtype != torch.float32 or lse.device != q.device:
+        raise ValueError("hip_attention_maps: lse must be float32 [B, L, H] on q's device")
+    lse = lse.contiguous()
+    if probs_for is not None:
+        pb0, pnb, ph0, pnh = (int(v) for v in probs_for)
+        if not (0 <= pb0 and 1 <= pnb and pb0 + pnb <= B and 0 <= ph0 and 1 <= pnh and ph0 + pnh <= H):
+            raise ValueError(f"hip_attention_maps: probs_for = (b0, nb, h0, nh) = {tuple(probs_for)} outside B = {B}, H = {H}")
+    L_ = _lib.load()
+    st = _lib.stream_ptr(dev)
+    recv = torch.empty(B, H, L, device=dev, dtype=torch.float32)
+    probs = torch.empty(pnb, pnh, L, L, device=dev, dtype=torch.float32) if probs_for is not None else None
+    bmax = max(1, (MAX_QKV_ELEMS - 1) // (L * max(q.stride(1), k.stride(1))))       # larger batches go in batch chunks (independent problems)
+    for c0 in range(0, B, bmax):
+        cn = min(bmax, B - c0)
+        args = (q[c0:].data_ptr(), k[c0:].data_ptr(), lse[c0:].data_ptr())
+        _lib.check(L_.smk_attention_received(*args, recv[c0:].data_ptr(), cn, L, H, D // H, q.stride(1), k.stride(1), L, float(scale), st))
+        if probs is not None:
+            lo, hi = max(pb0, c0), min(pb0 + pnb, c0 + cn)
+            if lo < hi:
+                _lib.check(L_.smk_attention_probs(*args, probs[lo - pb0:].data_ptr(), cn, L, H, D // H, lo - c0, hi - lo, ph0, pnh,
+                                                  q.stride(1), k.stride(1), L, float(scale), st))
+    return recv if probs_for is None else (recv, probs)
+
+
+def attention_maps_torch(q: torch.Tensor, k: torch.Tensor, num_heads: int, scale: float, probs_for: Optional[tuple] = None,
+                         mask: Optional[torch.Tensor] = None):
+    """hip_attention_maps written out as PyTorch ops (an explicit [B, H, L, L] softmax; chaos_attention.py:100-108) -- any dtype, any
+    device, any head_dim, and a key mask [B, L] (0 = masked out).  The definition the libsmokehip route is tested against."""
+    B, L, D = q.shape
+    H, d = num_heads, D // num_heads
+    s = (q.view(B, L, H, d).transpose(1, 2) @ k.view(B, L, H, d).permute(0, 2, 3, 1)) * scale
+    if mask is not None:
+        s = s.masked_fill((mask == 0)[:, None, None, :], float("-inf"))
+    p = torch.softmax(s, dim=-1)
+    received = p.mean(dim=2)
+    if probs_for is None:
+        return received
+    b0, nb, h0, nh = probs_for
+    return received, p[b0:b0 + nb, h0:h0 + nh].contiguous()
+
+
 def hip_attention_delta(dout: torch.Tensor, out: torch.Tensor, num_heads: int) -> torch.Tensor:
     """delta [B, L, H] = (dout * out).view(B, L, H, 64).sum(-1) as one libsmokehip pass (smk_attention_delta)."""
     dev = _lib.require_cuda(dout.device, "hip_attention_delta")

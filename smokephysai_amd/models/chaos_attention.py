@@ -14,7 +14,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .attention import hip_attention_supported, hip_attention_train, hip_qkv_attention_train
+from .attention import (attention_maps_torch, hip_attention_maps, hip_attention_maps_supported, hip_attention_supported, hip_attention_train,
+                        hip_qkv_attention_train)
 from .linear import HipLinear, TrainableHipLinear, hip_linear_supported, hip_linear_wgrad_supported
 
 
@@ -152,6 +153,25 @@ class ChaosAttention(nn.Module):
                                                self.chaos_gate.bias.data_ptr(), float(self.chaos_strength), sg, rh, bt,
                                                0.01, out.data_ptr(), out.shape[2], _lib.stream_ptr(dev)))
         return out
+
+    @torch.no_grad()
+    def attention_maps(self, x: torch.Tensor, noise: Optional[torch.Tensor] = None, probs_for: Optional[tuple] = None,
+                       mask: Optional[torch.Tensor] = None):
+        """The softmax weights `forward(x, mask, noise)` attends with (chaos_attention.py:100-108: the reference's attn_weights, which
+        SmokeVisualizer.plot_attention_maps takes), chaos term folded into Q, scale 1 / (sqrt(d) * temperature).  x [B, L, D].
+        Returns received [B, H, L] = attn_weights.mean(2), the attention each key receives; with probs_for = (b0, nb, h0, nh) returns
+        (received, attn_weights[b0:b0+nb, h0:h0+nh]).  float32 x on a ROCm device without a mask and with a shape the flash kernel takes:
+        libsmokehip (hip_attention_maps: no [B, H, L, L] tensor); anything else: an explicit softmax (attention_maps_torch), in x's dtype, on any device."""
+        B, L, D = x.shape
+        H, d = self.num_heads, self.head_dim
+        q = self.q_proj(x)
+        add5 = self.chaos_addend(B, x.device, x.dtype, noise)                        # [B,5,D]
+        q = q + add5.repeat(1, (L + 4) // 5, 1)[:, :L]
+        k = self.k_proj(x)
+        scale = 1.0 / (math.sqrt(d) * self.temperature)
+        if mask is None and x.is_cuda and x.dtype == torch.float32 and hip_attention_maps_supported(L, d):
+            return hip_attention_maps(q, k, H, scale, probs_for=probs_for)
+        return attention_maps_torch(q, k, H, scale, probs_for=probs_for, mask=mask)
 
     def forward(self, x: torch.Tensor, mask: torch.Tensor = None, noise: Optional[torch.Tensor] = None,
                 residual: Optional[torch.Tensor] = None) -> torch.Tensor:

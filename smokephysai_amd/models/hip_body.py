@@ -10,7 +10,8 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .attention import hip_attention, hip_attention_supported, hip_layernorm, hip_layernorm_supported
+from .attention import (attention_maps_torch, hip_attention, hip_attention_lse, hip_attention_maps, hip_attention_maps_supported,
+                        hip_attention_supported, hip_layernorm, hip_layernorm_supported)
 from .linear import HipLinear, HipLinearLN, hip_linear_supported, to_split
 
 
@@ -121,9 +122,13 @@ class HipBody:
         _lib.check(_lib.load().smk_chaos_addend_batched(len(atts), ctypes.cast(arr, ctypes.c_void_p), B, D, sg, rh, bt, 0.01, _lib.stream_ptr(device)))
         return True
 
-    def layer(self, name: str, layer, x: torch.Tensor, noise: Optional[torch.Tensor] = None, addend_ready: bool = False) -> torch.Tensor:
+    def layer(self, name: str, layer, x: torch.Tensor, noise: Optional[torch.Tensor] = None, addend_ready: bool = False,
+              capture: Optional[dict] = None) -> torch.Tensor:
         """One ChaosTransformerLayer, eval mode, IN PLACE on x [B,L,D] (the residual stream).  noise: the layer's three
-        randn(B,1) draws [3,B,1] or None to draw them like the reference does.  addend_ready: chaos_addends() has filled this layer's buffer."""
+        randn(B,1) draws [3,B,1] or None to draw them like the reference does.  addend_ready: chaos_addends() has filled this layer's buffer.
+        capture (SmokePhysNet.attention_maps): a dict that receives this layer's softmax weights -- "received" [B, H, L] and, when it holds
+        "probs_for" = (b0, nb, h0, nh), "probs" [nb, nh, L, L].  The q | k | v launch then writes fp32 k | v (the maps kernels read fp32 k),
+        which leaves the attention output, and so x, bit for bit what it is without a capture."""
         B, L, D = x.shape
         att = layer.chaos_attention
         H, d = att.num_heads, att.head_dim
@@ -140,13 +145,19 @@ class HipBody:
         qkv_ln = self.linear_ln(name + "chaos_attention.qkv", (att.q_proj, att.k_proj, att.v_proj), layer.norm1) if fuse_ln else None
         kvs = False
         if qkv_ln is not None and qkv_ln.accepts(x):
-            kvs = self.kv_presplit and hip_attention_supported(L, d) and D % 32 == 0
+            kvs = self.kv_presplit and hip_attention_supported(L, d) and D % 32 == 0 and capture is None
             qkv = qkv_ln.forward_ln(x, periodic_add=add15, rows_per_group=L, split_from=D if kvs else None)
         else:
             h = self.layernorm(x, layer.norm1, out_split=sp)
             qkv = self.qkv(name + "chaos_attention.qkv", att)(h, periodic_add=add15, rows_per_group=L, x_split=sp)
         q, k, v = qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:]
         scale = 1.0 / (math.sqrt(d) * att.temperature)
+        if capture is not None:
+            if hip_attention_maps_supported(L, d):
+                maps = hip_attention_maps(q, k, H, scale, lse=hip_attention_lse(q, k, H, scale), probs_for=capture.get("probs_for"))
+            else:
+                maps = attention_maps_torch(q, k, H, scale, probs_for=capture.get("probs_for"))
+            capture["received"], capture["probs"] = maps if capture.get("probs_for") is not None else (maps, None)
         if hip_attention_supported(L, d):
             o = hip_attention(q, k, v, H, scale, out_split=sp, kv_split=kvs)      # [B, L, D]: heads already merged
         else:

@@ -337,7 +337,7 @@ class SmokePhysNet(nn.Module):
                 m.__dict__.pop("_hip_fwd_fp", None); m.__dict__.pop("_hip_bwd_fp", None)
         self.__dict__["_mirror_epoch"] = self.__dict__.get("_mirror_epoch", 0) + 1
 
-    def _body_hip(self, tokens: torch.Tensor, chaos_noise: Optional[torch.Tensor], pool_size: int):
+    def _body_hip(self, tokens: torch.Tensor, chaos_noise: Optional[torch.Tensor], pool_size: int, capture: Optional[dict] = None):
         """feature_proj + pos-embed, the pre-LN chaos transformer layers and output_decoder (smokephys_net.py:95-114,
         136-168; chaos_attention.py:68-114) with every token-wise nn.Linear as one fused libsmokehip launch:
         bias, the pos-embedding / chaos-term addend, GELU / ReLU and the residual add ride in the GEMM epilogue;
@@ -355,7 +355,7 @@ class SmokePhysNet(nn.Module):
         names = [f"chaos_layers.{li}." for li in range(len(self.chaos_layers))]
         ready = body.chaos_addends(names, list(self.chaos_layers), chaos_noise, B, tokens.device)        # all layers' chaos terms: one launch
         for li, layer in enumerate(self.chaos_layers):
-            body.layer(names[li], layer, x, chaos_noise[li], addend_ready=ready)
+            body.layer(names[li], layer, x, chaos_noise[li], addend_ready=ready, capture=None if capture is None else capture.get(li))
         dec = body.linear("output_decoder.0", self.output_decoder[0])(x, activation="relu")
         dec = body.linear("output_decoder.2", self.output_decoder[2])(dec)
         return x, dec
@@ -396,25 +396,36 @@ class SmokePhysNet(nn.Module):
                 encoder_dtype: Optional[str] = None) -> dict:
         """x: [B,1,H,W].  chaos_noise (optional): [num_layers,3,B,1] standard-normal draws replacing the reference's
         in-forward torch.randn (chaos_attention.py:50-52) so results can be pinned."""
+        return self.forward_tokens(self._frame_tokens(x, encoder_dtype), return_features, chaos_noise)
+
+    def _frame_tokens(self, x: torch.Tensor, encoder_dtype: Optional[str] = None) -> torch.Tensor:
+        """The encoder's output as the tokens [B, 1024, 128] forward_tokens takes."""
         dt = encoder_dtype or self.encoder_dtype
         if self._encoder_route(x) == "hip" and dt in ("bf16x3", "bf16"):
             # the bf16 MFMA kernels write the token-major layout feature_proj consumes (smokephys_net.py:95) directly
-            flattened = self.hip_encoder().tokens(x, input_dim=self.input_dim, dtype=dt)
-        else:
-            flattened = self.encode_frames(x, encoder_dtype).flatten(2).transpose(1, 2)
-        return self.forward_tokens(flattened, return_features, chaos_noise)
+            return self.hip_encoder().tokens(x, input_dim=self.input_dim, dtype=dt)
+        return self.encode_frames(x, encoder_dtype).flatten(2).transpose(1, 2)
 
-    def forward_tokens(self, flattened: torch.Tensor, return_features: bool = False, chaos_noise: Optional[torch.Tensor] = None) -> dict:
+    def forward_tokens(self, flattened: torch.Tensor, return_features: bool = False, chaos_noise: Optional[torch.Tensor] = None,
+                       capture: Optional[dict] = None) -> dict:
         """Everything behind the encoder (smokephys_net.py:95-122): tokens [B, 1024, input_channels] -> the forward's result dict.
-        forward() ends here; forward_volumes() enters here with the 3-D encoder's tokens."""
+        forward() ends here; forward_volumes() enters here with the 3-D encoder's tokens.  capture (attention_maps): {layer index: dict};
+        each dict receives that layer's "received" / "probs" (HipBody.layer)."""
         B = flattened.shape[0]
         pool_size = 32
+        if capture and chaos_noise is None:        # one set of draws for the layer and for its maps
+            chaos_noise = torch.randn(len(self.chaos_layers), 3, B, 1, device=flattened.device, dtype=torch.float32)
         if self._hip_body_ok(flattened):
-            features, output_features = self._body_hip(flattened.contiguous(), chaos_noise, pool_size)
+            features, output_features = self._body_hip(flattened.contiguous(), chaos_noise, pool_size, capture)
         else:
             features = self.feature_proj(flattened)
             features = features + self._pos_embed(pool_size)
             for li, layer in enumerate(self.chaos_layers):
+                if capture and li in capture:      # the module's own route (HIP maps kernels on a ROCm device, else the explicit softmax)
+                    c = capture[li]
+                    maps = layer.chaos_attention.attention_maps(layer._norm(layer.norm1, features), noise=chaos_noise[li],
+                                                                probs_for=c.get("probs_for"))
+                    c["received"], c["probs"] = maps if c.get("probs_for") is not None else (maps, None)
                 features = layer(features, noise=None if chaos_noise is None else chaos_noise[li])
             output_features = self.output_decoder(features)
         if self.training and self.head_train == "hip" and hip_head_train_supported(self.reconstruction_head, output_features):
@@ -437,6 +448,29 @@ class SmokePhysNet(nn.Module):
         results = {"reconstructed": reconstructed, "physics_features": physics_pred, "latent_features": pooled_features}
         if return_features:
             results["intermediate_features"] = features
+        return results
+
+    def attention_maps(self, x: torch.Tensor, layers=None, chaos_noise: Optional[torch.Tensor] = None,
+                       probs_for: Optional[tuple] = None) -> dict:
+        """The eval forward of x [B,1,H,W] plus the softmax weights of its ChaosAttention layers, which the flash kernel never stores
+        (the reference's SmokeVisualizer.plot_attention_maps panel, visualization.py:74-116).  Returns the forward's result dict -- bit for
+        bit what `model(x, chaos_noise=...)` returns under no_grad -- plus
+          "attention_received": {layer: [B, heads, 32, 32]}  the attention each token receives, averaged over the queries (token j at row
+                                j // 32, column j % 32: the reference's reshape(sqrt_len, sqrt_len));
+          "attention_probs":    {layer: [nb, nh, 1024, 1024]} the matrices themselves for probs_for = (b0, nb, h0, nh); empty without it.
+        layers: the layer indices wanted (default: all).  Eval mode only; runs under no_grad."""
+        if self.training:
+            raise RuntimeError("SmokePhysNet.attention_maps: eval mode only (call model.eval() first)")
+        n = len(self.chaos_layers)
+        sel = list(range(n)) if layers is None else [int(li) for li in layers]
+        if any(not 0 <= li < n for li in sel):
+            raise ValueError(f"attention_maps: layers {sel} outside 0 .. {n - 1}")
+        capture = {li: {"probs_for": probs_for} for li in sel}
+        with torch.no_grad():
+            results = self.forward_tokens(self._frame_tokens(x), chaos_noise=chaos_noise, capture=capture)
+        side = 32
+        results["attention_received"] = {li: c["received"].view(*c["received"].shape[:2], side, side) for li, c in capture.items()}
+        results["attention_probs"] = {li: c["probs"] for li, c in capture.items() if c.get("probs") is not None}
         return results
 
     def forward_volumes(self, volumes: torch.Tensor, encoder3d, return_features: bool = False,

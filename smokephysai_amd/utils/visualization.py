@@ -1,0 +1,111 @@
+"""Figures of the reference's src/utils/visualization.py (SmokeVisualizer: the same three methods and argument names), drawn with
+matplotlib alone.  The attention panel takes what SmokePhysNet.attention_maps returns: the full [B, heads, L, L] weights as in the
+reference, or the `received` map [B, heads, h, w] the libsmokehip kernels produce without ever forming an L x L tensor.
+Without a display the Agg backend is used; plt.show() is called only on an interactive backend."""
+import math
+import os
+import sys
+from typing import Dict, List, Optional
+
+import matplotlib
+
+if not (os.environ.get("DISPLAY") or os.environ.get("WAYLAND_DISPLAY") or os.environ.get("MPLBACKEND")
+        or sys.platform in ("win32", "darwin")):
+    matplotlib.use("Agg")
+import matplotlib.pyplot as plt      # noqa: E402
+import numpy as np                   # noqa: E402
+
+
+def _numpy(a) -> np.ndarray:
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+
+
+def _finish(fig, save_path: Optional[str]):
+    fig.tight_layout()
+    if save_path:
+        fig.savefig(save_path, dpi=150, bbox_inches="tight")
+    if matplotlib.get_backend().lower() in (b.lower() for b in _interactive_backends()):
+        plt.show()
+    return fig
+
+
+def _interactive_backends():
+    try:
+        from matplotlib.backends import backend_registry, BackendFilter
+        return backend_registry.list_builtin(BackendFilter.INTERACTIVE)
+    except ImportError:                                      # matplotlib < 3.9
+        from matplotlib import rcsetup
+        return rcsetup.interactive_bk
+
+
+class SmokeVisualizer:
+    def __init__(self, figsize: tuple = (12, 8)):
+        self.figsize = figsize
+        plt.style.use("dark_background")
+
+    def plot_smoke_evolution(self, density_sequence: List, save_path: Optional[str] = None):
+        """One 'hot' panel per frame, at most 8 per row, titled 'Frame i'; the cells past the last frame stay empty.  Returns the figure."""
+        n = len(density_sequence)
+        cols = max(1, min(8, n))
+        rows = max(1, (n + cols - 1) // cols)
+        fig, axes = plt.subplots(rows, cols, figsize=(cols * 2, rows * 2), squeeze=False)
+        for ax in axes.flat:
+            ax.axis("off")
+        for i, density in enumerate(density_sequence):
+            ax = axes[i // cols, i % cols]
+            ax.imshow(_numpy(density), cmap="hot", interpolation="bilinear")
+            ax.set_title(f"Frame {i}")
+        return _finish(fig, save_path)
+
+    def plot_chaos_features(self, chaos_metrics: Dict[str, List[float]], save_path: Optional[str] = None):
+        """Lyapunov exponent, fractal dimension and entropy over the time steps, side by side; a metric the dict lacks leaves its panel blank."""
+        fig, axes = plt.subplots(1, 3, figsize=self.figsize)
+        for ax, key, title in zip(axes, ("lyapunov_exponent", "fractal_dimension", "entropy"),
+                                  ("Lyapunov Exponent", "Fractal Dimension", "Entropy")):
+            if key in chaos_metrics:
+                ax.plot(_numpy(chaos_metrics[key]), "o-", linewidth=2, markersize=4)
+                ax.set_title(title)
+                ax.set_xlabel("Time Step")
+                ax.grid(True, alpha=0.3)
+        return _finish(fig, save_path)
+
+    def plot_attention_maps(self, attention_weights, input_image, save_path: Optional[str] = None, received=None):
+        """The frame, the attention matrix of (batch 0, head 0) and the attention its keys receive, laid out as an image.
+        attention_weights: [B, heads, L, L], or None when received [B, heads, h, w] is given (the matrix panel is then left out).
+        Without `received` the third panel is attention_weights[0, 0].mean(0) reshaped to sqrt(L) x sqrt(L) when L is a perfect square
+        (the reference's rule); another L leaves that panel out.  input_image: [B, 1, H, W] tensor, or a 2-D array."""
+        if attention_weights is None and received is None:
+            raise ValueError("plot_attention_maps: attention_weights or received")
+        attn = None if attention_weights is None else _numpy(attention_weights[0, 0])
+        recv = None
+        if received is not None:
+            recv = _numpy(received[0, 0])
+        elif attn is not None:
+            avg = attn.mean(axis=0)
+            side = math.isqrt(len(avg))
+            if side * side == len(avg):
+                recv = avg.reshape(side, side)
+        img = _numpy(input_image)
+        while img.ndim > 2:
+            img = img[0]
+        n = 1 + (attn is not None) + (recv is not None)
+        fig, axes = plt.subplots(1, n, figsize=(5 * n, 5), squeeze=False)
+        axes = list(axes[0])
+        ax = axes.pop(0)
+        ax.imshow(img, cmap="hot")
+        ax.set_title("Input Smoke")
+        ax.axis("off")
+        if attn is not None:
+            ax = axes.pop(0)
+            im = ax.imshow(attn, cmap="viridis")
+            ax.set_title("Attention Matrix")
+            ax.set_xlabel("Key Position")
+            ax.set_ylabel("Query Position")
+            fig.colorbar(im, ax=ax)
+        if recv is not None:
+            ax = axes.pop(0)
+            im = ax.imshow(recv, cmap="plasma")
+            ax.set_title("Average Attention")
+            ax.axis("off")
+            fig.colorbar(im, ax=ax)
+        return _finish(fig, save_path)
