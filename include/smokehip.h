@@ -658,6 +658,56 @@ int64_t smk_conv3_sigmoid_train_workspace(int32_t B, int32_t H, int32_t W);
 int smk_conv3_sigmoid_train_backward(const float *dy, const float *y, const float *x, const float *weight, int32_t B, int32_t H, int32_t W,
                                      float *dx, float *dw, float *db, void *workspace, void *stream);
 
+/* ------------------------------------------------------------------ train step tail: gradient clip, AdamW, loss terms */
+/* One row of the HOST table the next three functions take: device pointers of one parameter's fp32 tensors of n elements each (dense;
+ * 4-byte aligned, 16-byte accesses where all of a row's pointers are 16-byte aligned).  n == 0 is legal and does nothing.  The table is
+ * read before the call returns: its descriptors travel in the kernel arguments, 64 rows per launch; nothing is allocated or copied. */
+typedef struct smk_opt_tensor {
+    float *param, *grad, *exp_avg, *exp_avg_sq;
+    int64_t n;
+} smk_opt_tensor;
+
+/* The total 2-norm of every row's `grad` (the other pointers are not read) and torch's clip coefficient (clip_grads_with_norm_):
+ * out[0] = norm, out[1] = clamp(max_norm / (norm + 1e-6), max = 1), both fp32; a NaN norm gives a NaN coefficient.  Work is cut into
+ * chunks of 8192 elements counted from element 0 of each tensor; each chunk's sum of squares is one fp64 partial whose value depends on
+ * the chunk's values only (not on the pointer's alignment), and one workgroup adds the partials in a fixed order: no atomics, repeated
+ * calls are bit-identical.  workspace: device memory of at least smk_grad_norm_workspace(t, n_tensors) bytes, 8-byte aligned. */
+int64_t smk_grad_norm_workspace(const smk_opt_tensor *t, int32_t n_tensors);
+int smk_grad_norm(const smk_opt_tensor *t, int32_t n_tensors, double max_norm, float *out, void *workspace, int64_t workspace_bytes,
+                  void *stream);
+/* torch.optim.AdamW's update (decoupled weight decay, the single-tensor order) of every row, per element in fp32:
+ *   g' = g * scale;  p *= 1 - lr * weight_decay;  m += (1 - beta1) (g' - m);  v = beta2 v + (1 - beta2) g'^2;
+ *   p -= (lr / bias_correction1) * m / (sqrt(v) / sqrt(bias_correction2) + eps)
+ * p takes one rounding per step: the two lines that touch it are evaluated as p - (lr weight_decay p + (lr / bias_correction1) m / (...)),
+ * which is the same value.  The coefficients are rounded to fp32 once on the host.  scale = *grad_scale, read on the device (smk_grad_norm's out + 1: no host
+ * synchronisation between the two), or 1 when grad_scale is NULL.  write_grad != 0 also stores g'.  param, exp_avg and exp_avg_sq are
+ * read once and written once. */
+int smk_adamw_step(const smk_opt_tensor *t, int32_t n_tensors, double lr, double beta1, double beta2, double eps, double weight_decay,
+                   double bias_correction1, double bias_correction2, const float *grad_scale, int32_t write_grad, void *stream);
+
+/* The loss of train.py's batch_losses: pred / target [planes][plane_elems], chaos_pred / chaos_target [n_chaos], and sequence
+ * [seq_batch][seq_T][seq_plane] (or NULL), all dense fp32.  out [6] =
+ *   total      = recon + w_chaos chaos + w_physics physics
+ *   recon      = mean (pred - target)^2
+ *   physics    = w_mass mass + w_continuity continuity
+ *   chaos      = mean (chaos_pred - chaos_target)^2
+ *   mass       = mean over planes of (sum pred - sum target)^2
+ *   continuity = mean |sequence[:, t+1] - sequence[:, t]|; exactly 0 for seq_T < 2 or a NULL sequence
+ * and mass_diff [planes] = sum pred - sum target, which the backward reads.  fp64 partial sums in `workspace`
+ * (smk_train_loss_workspace(...) bytes, 16-byte aligned) added in a fixed order: repeated calls are bit-identical.
+ * Backward, one launch, with g = grad_out [6] read on the device:
+ *   d_pred  = (g[0] + g[1]) 2/N (pred - target) + (g[0] w_physics w_mass + g[2] w_mass + g[4]) 2/planes mass_diff[plane]
+ *   d_chaos = (g[0] w_chaos + g[3]) 2/n_chaos (chaos_pred - chaos_target)
+ * Either output may be NULL. */
+int64_t smk_train_loss_workspace(int32_t planes, int32_t plane_elems, int32_t seq_batch, int32_t seq_T, int64_t seq_plane);
+int smk_train_loss_forward(const float *pred, const float *target, int32_t planes, int32_t plane_elems, const float *chaos_pred,
+                           const float *chaos_target, int32_t n_chaos, const float *sequence, int32_t seq_batch, int32_t seq_T,
+                           int64_t seq_plane, double w_chaos, double w_physics, double w_mass, double w_continuity, float *out,
+                           float *mass_diff, void *workspace, int64_t workspace_bytes, void *stream);
+int smk_train_loss_backward(const float *pred, const float *target, int32_t planes, int32_t plane_elems, const float *mass_diff,
+                            const float *chaos_pred, const float *chaos_target, int32_t n_chaos, const float *grad_out, double w_chaos,
+                            double w_physics, double w_mass, float *d_pred, float *d_chaos, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,11 @@ class SmkDecoderWeights(C.Structure):
                  "ct2_w", "ct2_b", "bn2_w", "bn2_b", "bn2_mean", "bn2_var", "conv_w", "conv_b")]
 
 
+class SmkOptTensor(C.Structure):
+    """smk_opt_tensor (include/smokehip.h): one row of the HOST table of smk_grad_norm / smk_adamw_step."""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("n", C.c_int64)]
+
+
 # name -> (argtypes); every function returns int status except the two noted below
 _SIGNATURES = {
     "smk_sim_create": [C.POINTER(SmkSimDesc), C.POINTER(C.c_void_p)],
@@ -146,6 +151,12 @@ _SIGNATURES = {
                       C.c_int32, C.c_void_p],
     "smk_layernorm_backward": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_double, C.c_void_p,
                                C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "smk_grad_norm": [C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    "smk_adamw_step": [C.c_void_p, C.c_int32] + [C.c_double] * 7 + [C.c_void_p, C.c_int32, C.c_void_p],
+    "smk_train_loss_forward": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                               C.c_int64] + [C.c_double] * 4 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    "smk_train_loss_backward": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p] +
+                               [C.c_double] * 3 + [C.c_void_p, C.c_void_p, C.c_void_p],
     "smk_decoder_create": [C.POINTER(SmkDecoderWeights), C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)],
     "smk_decoder_destroy": [C.c_void_p],
     "smk_decoder_forward": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
@@ -158,7 +169,7 @@ _SIGNATURES = {
                            C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p],
 }
 EXPORTS = ["smk_abi_version", "smk_last_error", "smk_linear_wgrad_workspace", "smk_bn_train_workspace", "smk_layernorm_bwd_workspace", "smk_conv2_train_workspace", "smk_conv2_train_wgrad_workspace", "smk_conv1_train_wgrad_workspace", "smk_attention_workspace_bytes", "smk_linear_ln_max_rows", "smk_image_quality_workspace", "smk_convt4s2_train_wgrad_workspace",
-           "smk_volume_stats_workspace",
+           "smk_volume_stats_workspace", "smk_grad_norm_workspace", "smk_train_loss_workspace",
            "smk_conv3_sigmoid_train_workspace"] + list(_SIGNATURES)
 
 _lib = None
@@ -215,6 +226,10 @@ def load():
         L.smk_convt4s2_train_wgrad_workspace.restype = C.c_int64
         L.smk_conv3_sigmoid_train_workspace.argtypes = [C.c_int32] * 3
         L.smk_conv3_sigmoid_train_workspace.restype = C.c_int64
+        L.smk_grad_norm_workspace.argtypes = [C.c_void_p, C.c_int32]          # (host table of SmkOptTensor, rows)
+        L.smk_grad_norm_workspace.restype = C.c_int64
+        L.smk_train_loss_workspace.argtypes = [C.c_int32] * 4 + [C.c_int64]
+        L.smk_train_loss_workspace.restype = C.c_int64
         for name, args in _SIGNATURES.items():
             fn = getattr(L, name)
             fn.argtypes = args

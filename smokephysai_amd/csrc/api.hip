@@ -15,7 +15,9 @@
 #include "encoder.h"
 #include "encoder_train.h"
 #include "linear.h"
+#include "loss.h"
 #include "norm.h"
+#include "optim.h"
 #include "quality.h"
 #include "stencil.h"
 #include "stencil3d.h"
@@ -825,6 +827,105 @@ int smk_image_quality(const float *pred, int64_t pred_stride, const float *targe
     return check_launch(launch_image_quality(pred, pred_stride, target, target_stride, n, H, W, window, (float)c1, (float)c2, workspace,
                                              ssim_sum, sqerr_sum, (hipStream_t)stream),
                         "image_quality");
+}
+
+// ------------------------------------------------------------------ train step tail: gradient norm, AdamW, loss terms
+namespace {
+int check_opt_table(const smk_opt_tensor *t, int32_t n_tensors, bool adam) {
+    SMK_REQUIRE(n_tensors >= 0 && (t || n_tensors == 0), "tensor table: n_tensors >= 0 and a non-null host array");
+    for (int32_t i = 0; i < n_tensors; ++i) {
+        SMK_REQUIRE(t[i].n >= 0, "tensor table: n >= 0");
+        if (t[i].n == 0) continue;
+        SMK_REQUIRE(t[i].grad && ((uintptr_t)t[i].grad & 3) == 0, "tensor table: non-null, 4-byte aligned grad");
+        if (adam)
+            SMK_REQUIRE(t[i].param && t[i].exp_avg && t[i].exp_avg_sq &&
+                            (((uintptr_t)t[i].param | (uintptr_t)t[i].exp_avg | (uintptr_t)t[i].exp_avg_sq) & 3) == 0,
+                        "tensor table: non-null, 4-byte aligned param, exp_avg, exp_avg_sq");
+    }
+    const int64_t chunks = opt_chunks(t, n_tensors);
+    SMK_REQUIRE(chunks >= 0 && chunks < (int64_t)1 << 30, "tensor table: fewer than 2^30 chunks of 8192 elements");
+    return SMK_OK;
+}
+}  // namespace
+
+int64_t smk_grad_norm_workspace(const smk_opt_tensor *t, int32_t n_tensors) {
+    if (!t || n_tensors < 1) return (int64_t)sizeof(double);
+    const int64_t chunks = opt_chunks(t, n_tensors);
+    return (chunks < 1 ? 1 : chunks) * (int64_t)sizeof(double);
+}
+
+int smk_grad_norm(const smk_opt_tensor *t, int32_t n_tensors, double max_norm, float *out, void *workspace, int64_t workspace_bytes,
+                  void *stream) {
+    if (int rc = check_opt_table(t, n_tensors, false)) return rc;
+    SMK_REQUIRE(out && workspace && ((uintptr_t)workspace & 7) == 0 && ((uintptr_t)out & 3) == 0, "non-null out, 8-byte aligned workspace");
+    SMK_REQUIRE(workspace_bytes >= smk_grad_norm_workspace(t, n_tensors), "workspace smaller than smk_grad_norm_workspace(t, n_tensors)");
+    return check_launch(launch_grad_norm(t, n_tensors, (float)max_norm, out, (double *)workspace, (hipStream_t)stream), "grad_norm");
+}
+
+int smk_adamw_step(const smk_opt_tensor *t, int32_t n_tensors, double lr, double beta1, double beta2, double eps, double weight_decay,
+                   double bias_correction1, double bias_correction2, const float *grad_scale, int32_t write_grad, void *stream) {
+    if (int rc = check_opt_table(t, n_tensors, true)) return rc;
+    SMK_REQUIRE(bias_correction1 > 0.0 && bias_correction2 > 0.0, "bias corrections > 0 (step >= 1)");
+    AdamCoef c;
+    c.lr_wd = (float)(lr * weight_decay);
+    c.w1 = (float)(1.0 - beta1);
+    c.beta2 = (float)beta2;
+    c.w2 = (float)(1.0 - beta2);
+    c.step = (float)(lr / bias_correction1);
+    c.rsq_bc2 = (float)sqrt(bias_correction2);
+    c.eps = (float)eps;
+    return check_launch(launch_adamw(t, n_tensors, c, grad_scale, write_grad, (hipStream_t)stream), "adamw_step");
+}
+
+namespace {
+int loss_shape(LossShape &s, int32_t planes, int32_t plane_elems, int32_t n_chaos, int32_t seq_batch, int32_t seq_T, int64_t seq_plane) {
+    SMK_REQUIRE(planes >= 1 && plane_elems >= 1 && n_chaos >= 1, "planes, plane_elems, n_chaos >= 1");
+    SMK_REQUIRE(seq_batch >= 0 && seq_T >= 0 && seq_plane >= 0, "sequence dimensions >= 0");
+    s.planes = planes;
+    s.plane_elems = plane_elems;
+    s.n_chaos = n_chaos;
+    s.seq_batch = seq_batch;
+    s.seq_T = seq_T;
+    s.seq_plane = seq_plane;
+    SMK_REQUIRE((int64_t)planes * loss_plane_chunks(plane_elems) < (int64_t)1 << 30, "pred: fewer than 2^30 chunks of 2048 elements");
+    SMK_REQUIRE((int64_t)seq_batch * loss_seq_chunks(seq_plane) < (int64_t)1 << 30, "sequence: fewer than 2^30 chunks of 1024 pixels");
+    return SMK_OK;
+}
+}  // namespace
+
+int64_t smk_train_loss_workspace(int32_t planes, int32_t plane_elems, int32_t seq_batch, int32_t seq_T, int64_t seq_plane) {
+    LossShape s;
+    if (loss_shape(s, planes, plane_elems, 1, seq_batch, seq_T, seq_plane) != SMK_OK) return 0;
+    return loss_workspace_doubles(s) * (int64_t)sizeof(double);
+}
+
+int smk_train_loss_forward(const float *pred, const float *target, int32_t planes, int32_t plane_elems, const float *chaos_pred,
+                           const float *chaos_target, int32_t n_chaos, const float *sequence, int32_t seq_batch, int32_t seq_T,
+                           int64_t seq_plane, double w_chaos, double w_physics, double w_mass, double w_continuity, float *out,
+                           float *mass_diff, void *workspace, int64_t workspace_bytes, void *stream) {
+    LossShape s;
+    if (int rc = loss_shape(s, planes, plane_elems, n_chaos, sequence ? seq_batch : 0, seq_T, seq_plane)) return rc;
+    SMK_REQUIRE(pred && target && chaos_pred && chaos_target && out && mass_diff && workspace, "null pointer");
+    SMK_REQUIRE((((uintptr_t)pred | (uintptr_t)target | (uintptr_t)chaos_pred | (uintptr_t)chaos_target | (uintptr_t)sequence |
+                  (uintptr_t)out | (uintptr_t)mass_diff) & 3) == 0 && ((uintptr_t)workspace & 15) == 0,
+                "4-byte aligned tensors, 16-byte aligned workspace");
+    SMK_REQUIRE(workspace_bytes >= loss_workspace_doubles(s) * (int64_t)sizeof(double), "workspace smaller than smk_train_loss_workspace(...)");
+    return check_launch(launch_train_loss_forward(pred, target, chaos_pred, chaos_target, sequence, s, w_chaos, w_physics, w_mass,
+                                                  w_continuity, out, mass_diff, (double *)workspace, (hipStream_t)stream),
+                        "train_loss_forward");
+}
+
+int smk_train_loss_backward(const float *pred, const float *target, int32_t planes, int32_t plane_elems, const float *mass_diff,
+                            const float *chaos_pred, const float *chaos_target, int32_t n_chaos, const float *grad_out, double w_chaos,
+                            double w_physics, double w_mass, float *d_pred, float *d_chaos, void *stream) {
+    LossShape s;
+    if (int rc = loss_shape(s, planes, plane_elems, n_chaos, 0, 0, 0)) return rc;
+    SMK_REQUIRE(pred && target && mass_diff && chaos_pred && chaos_target && grad_out, "null pointer");
+    SMK_REQUIRE((((uintptr_t)pred | (uintptr_t)target | (uintptr_t)chaos_pred | (uintptr_t)chaos_target | (uintptr_t)mass_diff |
+                  (uintptr_t)grad_out | (uintptr_t)d_pred | (uintptr_t)d_chaos) & 3) == 0, "4-byte aligned tensors");
+    return check_launch(launch_train_loss_backward(pred, target, mass_diff, chaos_pred, chaos_target, s, grad_out, w_chaos, w_physics,
+                                                   w_mass, d_pred, d_chaos, (hipStream_t)stream),
+                        "train_loss_backward");
 }
 
 // ------------------------------------------------------------------ encoder

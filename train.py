@@ -10,6 +10,7 @@ TensorBoard logging is optional (the module is not required).
 """
 import argparse
 import os
+import warnings
 from datetime import datetime
 from typing import Dict
 
@@ -59,8 +60,38 @@ def setup_experiment(config: dict, rank: int = 0, local_rank: int = 0):
     return exp_dir, writer, device
 
 
-def batch_losses(model, physics_regularizer, batch, device, chaos_noise=None):
-    """Forward + the reference's loss decomposition (train.py:59-85). Returns (total, recon, physics, chaos)."""
+LOSS_ROUTES = ("torch", "hip")
+OPTIMIZER_ROUTES = ("torch", "hip")
+_warned_losses = False
+
+
+def _route(value, choices, key: str) -> str:
+    value = str(value)
+    if value not in choices:
+        raise ValueError(f"{key} must be one of {', '.join(repr(c) for c in choices)}, not {value!r}")
+    return value
+
+
+def loss_route(config: dict) -> str:
+    """The config's `mi355x.losses` ('torch', the default, or 'hip': models/losses.py)."""
+    return _route((config.get("mi355x", {}) or {}).get("losses", "torch"), LOSS_ROUTES, "mi355x.losses")
+
+
+def build_optimizer(config: dict, params) -> optim.Optimizer:
+    """AdamW from the config's `training` section; `mi355x.optimizer: hip` makes it smokephysai_amd.optim.HipAdamW (same state,
+    same state_dict: a checkpoint resumes across the switch)."""
+    route = _route((config.get("mi355x", {}) or {}).get("optimizer", "torch"), OPTIMIZER_ROUTES, "mi355x.optimizer")
+    kwargs = dict(lr=config["training"]["learning_rate"], weight_decay=config["training"]["weight_decay"])
+    if route == "hip":
+        from smokephysai_amd.optim import HipAdamW
+        return HipAdamW(params, **kwargs)
+    return optim.AdamW(params, **kwargs)
+
+
+def _batch_loss_terms(model, physics_regularizer, batch, device, chaos_noise=None, losses="torch"):
+    """batch_losses' four values and, on the hip route, the device vector they are views of (else None)."""
+    global _warned_losses
+    _route(losses, LOSS_ROUTES, "losses")
     inputs = batch["input"].to(device)
     targets = batch["target"].to(device)
     chaos_targets = batch["chaos_features"].to(device)
@@ -70,13 +101,30 @@ def batch_losses(model, physics_regularizer, batch, device, chaos_noise=None):
         # F.mse_loss raises for any other grid size.  For BASELINE config 4 (256^2 grids) the target is block-averaged
         # to the head's resolution (2x2 mean at 256^2); at 128^2 this branch is never taken.
         targets = F.adaptive_avg_pool2d(targets, outputs["reconstructed"].shape[-2:])
+    if losses == "hip":
+        from smokephysai_amd.models.losses import hip_train_losses, hip_train_losses_supported
+        sequence = batch["sequence"].to(device)
+        if hip_train_losses_supported(outputs["reconstructed"], targets, outputs["physics_features"], chaos_targets, sequence):
+            vec = hip_train_losses(outputs["reconstructed"], targets, outputs["physics_features"], chaos_targets, sequence,
+                                   physics_regularizer, w_chaos=0.1, w_physics=0.05)
+            return (vec[0], vec[1], vec[2], vec[3]), vec
+        if outputs["reconstructed"].device.type == "cuda" and not _warned_losses:      # CPU tensors take the torch formulas silently
+            _warned_losses = True
+            warnings.warn("losses='hip': tensors outside the HIP loss kernels' domain (float32, contiguous, one ROCm device, equal shapes, "
+                          "no gradient into targets or sequence): the torch formulas run")
     recon_loss = F.mse_loss(outputs["reconstructed"], targets)
     chaos_loss = F.mse_loss(outputs["physics_features"], chaos_targets)
     physics_losses = physics_regularizer({"density": outputs["reconstructed"],
                                           "density_sequence": batch["sequence"].to(device)}, {"density": targets})
     physics_loss = physics_losses["total_physics_loss"]
     total = recon_loss + 0.1 * chaos_loss + 0.05 * physics_loss
-    return total, recon_loss, physics_loss, chaos_loss
+    return (total, recon_loss, physics_loss, chaos_loss), None
+
+
+def batch_losses(model, physics_regularizer, batch, device, chaos_noise=None, losses="torch"):
+    """Forward + the reference's loss decomposition (train.py:59-85). Returns (total, recon, physics, chaos); with losses="hip" the four
+    are views of the one device vector smokephysai_amd.models.losses.hip_train_losses computes."""
+    return _batch_loss_terms(model, physics_regularizer, batch, device, chaos_noise, losses)[0]
 
 
 def _rank_invariant_batches(loader: DataLoader, device):
@@ -96,18 +144,25 @@ def _rank_invariant_batches(loader: DataLoader, device):
 
 
 def train_epoch(model: nn.Module, train_loader: DataLoader, optimizer: optim.Optimizer,
-                physics_regularizer: PhysicsRegularizer, device, epoch: int, writer) -> Dict[str, float]:
+                physics_regularizer: PhysicsRegularizer, device, epoch: int, writer, losses: str = "torch") -> Dict[str, float]:
+    """One epoch.  A HipAdamW clips inside its step (`step(clip_max_norm=1.0)`: smk_grad_norm + smk_adamw_step); any other optimizer gets
+    clip_grad_norm_ and step() as before.  losses="hip": the four logged values come from one .tolist() of the loss vector."""
+    from smokephysai_amd.optim import HipAdamW
+    fused_clip = isinstance(optimizer, HipAdamW)
     model.train()
     sums, seen = [0.0, 0.0, 0.0, 0.0], 0
     steps = max_over_ranks(len(train_loader), device)
     pbar = tqdm(_rank_invariant_batches(train_loader, device), total=steps, desc=f"Training Epoch {epoch+1}", leave=True)
     for batch_idx, batch in enumerate(pbar):
         optimizer.zero_grad()
-        total, recon, phys, chaos = batch_losses(model, physics_regularizer, batch, device)
+        (total, recon, phys, chaos), vec = _batch_loss_terms(model, physics_regularizer, batch, device, losses=losses)
         total.backward()                      # DDP: bucketed RCCL all-reduce (mean over ranks) overlaps this backward
-        clip_grad_norm_(model.parameters(), max_norm=1.0)     # (= torch's; layout-independent under DDP's bucket views)
-        optimizer.step()
-        vals = [total.item(), recon.item(), phys.item(), chaos.item()]
+        if fused_clip:
+            optimizer.step(clip_max_norm=1.0)
+        else:
+            clip_grad_norm_(model.parameters(), max_norm=1.0)     # (= torch's; layout-independent under DDP's bucket views)
+            optimizer.step()
+        vals = [total.item(), recon.item(), phys.item(), chaos.item()] if vec is None else vec.tolist()[:4]
         n = int(batch["input"].shape[0])
         sums = [s + v * n for s, v in zip(sums, vals)]
         seen += n
@@ -121,15 +176,15 @@ def train_epoch(model: nn.Module, train_loader: DataLoader, optimizer: optim.Opt
 
 
 def validate_epoch(model: nn.Module, val_loader: DataLoader, physics_regularizer: PhysicsRegularizer,
-                   device) -> Dict[str, float]:
+                   device, losses: str = "torch") -> Dict[str, float]:
     """No collective inside the loop (the unwrapped model, eval-mode BatchNorm), so ranks may run different batch counts."""
     model.eval()
     sums, seen = [0.0, 0.0, 0.0, 0.0], 0
     with torch.no_grad():
         pbar = tqdm(val_loader, desc="Validation", leave=True)
         for batch in pbar:
-            losses = batch_losses(model, physics_regularizer, batch, device)
-            vals = [v.item() if torch.is_tensor(v) else float(v) for v in losses]
+            terms, vec = _batch_loss_terms(model, physics_regularizer, batch, device, losses=losses)
+            vals = [v.item() if torch.is_tensor(v) else float(v) for v in terms] if vec is None else vec.tolist()[:4]
             n = int(batch["input"].shape[0])
             sums = [s + v * n for s, v in zip(sums, vals)]
             seen += n
@@ -196,8 +251,8 @@ def main():
         model = ddp_model.module
         if rank == 0:
             print(f"DDP gradient exchange: {ddp_bucket_report(ddp_model)}")
-    optimizer = optim.AdamW(ddp_model.parameters(), lr=config["training"]["learning_rate"],
-                            weight_decay=config["training"]["weight_decay"])
+    optimizer = build_optimizer(config, ddp_model.parameters())
+    losses = loss_route(config)
     scheduler = optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=config["training"]["num_epochs"])
     if ckpt is not None:
         optimizer.load_state_dict(ckpt["optimizer_state_dict"])
@@ -206,8 +261,8 @@ def main():
     best_val_loss = float("inf")
     for epoch in range(start_epoch, config["training"]["num_epochs"]):
         print(f"\nEpoch {epoch + 1}/{config['training']['num_epochs']}")
-        train_metrics = train_epoch(ddp_model, train_loader, optimizer, physics_regularizer, device, epoch, writer)
-        val_metrics = validate_epoch(model, val_loader, physics_regularizer, device)
+        train_metrics = train_epoch(ddp_model, train_loader, optimizer, physics_regularizer, device, epoch, writer, losses=losses)
+        val_metrics = validate_epoch(model, val_loader, physics_regularizer, device, losses=losses)
         scheduler.step()
         writer.add_scalar("Train/Epoch_Loss", train_metrics["total_loss"], epoch)
         writer.add_scalar("Val/Epoch_Loss", val_metrics["total_loss"], epoch)
