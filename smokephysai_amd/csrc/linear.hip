@@ -1236,10 +1236,13 @@ __global__ __launch_bounds__(256, 2) void k_linear_wgrad_tr(WgradTrArgs a) {
         voy[j] = (unsigned)(((size_t)(srow + 8 * j) * a.ld_dy + 4 * sq) * sizeof(float));
         vox[j] = (unsigned)(((size_t)(srow + 8 * j) * a.ldx + 4 * sq) * sizeof(float));
     }
+    const unsigned vo0 = (unsigned)(4 * sq * sizeof(float));   // this thread's feature quad in the chunk's FIRST row (both operands)
     float4 ry[4], rx[4];
     float dbs[4] = {0.f, 0.f, 0.f, 0.f};
     // FULL chunks (all 32 rows inside the segment) load and split unconditionally; only a segment's last, partial chunk clamps its addresses and
-    // zeroes the rows past the end (at the split: overwriting a loaded register under a condition makes the compiler wait for that load on the spot)
+    // zeroes the rows past the end (at the split: overwriting a loaded register under a condition makes the compiler wait for that load on the spot).
+    // The clamp goes to the chunk's first row r0 -- the only row every partial chunk has (a 1-row tail: rows r0 + 1 .. r0 + 7 are past the
+    // caller's buffer) -- and the zero is a select, not a product: what lies past the end may be NaN or Inf.
     auto fetch = [&](long long r0, bool partial) {
         const unsigned char *cy = reinterpret_cast<const unsigned char *>(dyb) + (size_t)r0 * a.ld_dy * sizeof(float);
         const unsigned char *cx = reinterpret_cast<const unsigned char *>(xb) + (size_t)r0 * a.ldx * sizeof(float);
@@ -1253,8 +1256,8 @@ __global__ __launch_bounds__(256, 2) void k_linear_wgrad_tr(WgradTrArgs a) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const bool ok = r0 + srow + 8 * j < row1;
-                ry[j] = *reinterpret_cast<const float4 *>(cy + (ok ? voy[j] : voy[0]));      // (row r0 itself is inside)
-                rx[j] = *reinterpret_cast<const float4 *>(cx + (ok ? vox[j] : vox[0]));
+                ry[j] = *reinterpret_cast<const float4 *>(cy + (ok ? voy[j] : vo0));         // (row r0 itself is inside)
+                rx[j] = *reinterpret_cast<const float4 *>(cx + (ok ? vox[j] : vo0));
             }
         }
     };
@@ -1263,11 +1266,11 @@ __global__ __launch_bounds__(256, 2) void k_linear_wgrad_tr(WgradTrArgs a) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int off = (srow + 8 * j) * WT_PITCH + 8 * sq;
-            const float keep = (!partial || (r0 + srow + 8 * j) < row1) ? 1.f : 0.f;
+            const bool keep = !partial || (r0 + srow + 8 * j) < row1;
             float fy[4] = {ry[j].x, ry[j].y, ry[j].z, ry[j].w}, fx[4] = {rx[j].x, rx[j].y, rx[j].z, rx[j].w};
             if (partial) {
 #pragma unroll
-                for (int c = 0; c < 4; ++c) { fy[c] *= keep; fx[c] *= keep; }
+                for (int c = 0; c < 4; ++c) { fy[c] = keep ? fy[c] : 0.f; fx[c] = keep ? fx[c] : 0.f; }
             }
             bf16x4 yh, yl, xh, xl;
 #pragma unroll

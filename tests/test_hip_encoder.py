@@ -297,7 +297,8 @@ def test_sync_bn_relu_pool_phases_equal_the_fused_call_and_full_batch_statistics
     assert torch.allclose(tot[1], gb_ref, rtol=1e-4, atol=1e-4 * float(gb_ref.abs().max()))
 
 
-@pytest.mark.parametrize("shape", [(2, 64, 64), (3, 40, 48), (1, 8, 16), (4, 256, 256)])
+# (5, 128, 128): 640 tiles on 512 resident workgroups -- some workgroups walk two tiles and some one (the others: 0 or exactly 4 rounds)
+@pytest.mark.parametrize("shape", [(2, 64, 64), (3, 40, 48), (1, 8, 16), (4, 256, 256), (5, 128, 128)])
 def test_training_conv2_forward_vs_fp64_and_gradients_vs_autograd(shape):
     """smk_conv2_train_forward (k_conv2_fwd_b16): input_encoder's Conv2d(64, 128, 3, padding=1) under autograd (smokephys_net.py:28):
     the forward within 2e-6 (max-norm) of an fp64 convolution, incl. frames that are not square, one tile only, and borders on every
