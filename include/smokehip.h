@@ -120,6 +120,16 @@ int smk_sim_divergence(smk_sim *sim, float *out, void *stream);
  * 115-123): which = 0 (field=u), 1 (field=v), 2 (field=density). x0,y0: int32 [B][R][C] contiguous. */
 int smk_sim_backtrace(smk_sim *sim, int32_t which, int32_t *x0, int32_t *y0, void *stream);
 
+/* Diagnostic for tests and tools (it synchronises `stream` and copies; smk_sim_step never reads anything back): which of the two
+ * bit-identical forms of the Jacobi cell the sweeps of the handle's LATEST projection took, per grid and band of rows -- 1: three adds and
+ * one fma with -div / 4 formed once per launch, taken where every divergence value of the band is +-0 or has 2^-100 <= |div| <= 2^100;
+ * 0: the reference's five operations (navier_stokes.py:141-145), which is also all that most kernels have: only the one-launch step of the
+ * 256 x 256 x 64 plan (4 cells per lane, 6 rows per wave) carries both forms; every other answers 0 here.  *bands_per_grid receives the bands per grid of that projection (0: no
+ * projection yet, or one on the per-sweep kernel, which has the exact form only) and out[b * bands_per_grid + band] the words; capacity
+ * (in words) must be at least batch * bands_per_grid -- batch * max(64, height / 8) always suffices.  smk_sim_describe's
+ * "cell_forms_of_a_step" says whether this handle's step kernel has both forms (2) or the exact one only (1). */
+int smk_sim_sweep_forms(smk_sim *sim, int32_t *out, int32_t capacity, int32_t *bands_per_grid, void *stream);
+
 /* Device pointer to the fractal constants, [W][H] fp32 each (fractal_generator.py:12-51):
  * kind 0 = perlin, 1 = mandelbrot escape counts/100, 2 = 0.7*perlin+0.3*mandelbrot. Square grids only. */
 int smk_sim_fractal(smk_sim *sim, int32_t kind, const float **dev_ptr);

@@ -419,6 +419,23 @@ int smk_sim_backtrace(smk_sim *sim, int32_t which, int32_t *x0, int32_t *y0, voi
                                       (hipStream_t)stream), "backtrace");
 }
 
+int smk_sim_sweep_forms(smk_sim *sim, int32_t *out, int32_t capacity, int32_t *bands_per_grid, void *stream) {
+    SMK_REQUIRE(sim && out && bands_per_grid && capacity >= 0, "null sim / out / bands_per_grid or negative capacity");
+    DeviceGuard guard(sim->device);
+    if (guard.rc) return guard.rc;
+    const ProjectSync &ps = sim->psync;
+    const int n = sim->g.B * ps.forms_nb;
+    *bands_per_grid = ps.forms_nb;
+    if (n > capacity) {
+        set_error("smk_sim_sweep_forms: out holds fewer than batch * bands_per_grid words");
+        return SMK_ERR_INVALID;
+    }
+    SMK_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    if (n > 0 && ps.forms_two) SMK_HIP_TRY(hipMemcpy(out, ps.forms, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost));
+    else if (n > 0) memset(out, 0, (size_t)n * sizeof(int32_t));      // (a kernel with the exact cell only)
+    return SMK_OK;
+}
+
 int smk_sim_fractal(smk_sim *sim, int32_t kind, const float **dev_ptr) {
     SMK_REQUIRE(sim && dev_ptr && kind >= 0 && kind <= 2, "null sim/dev_ptr or kind not in 0..2");
     if (!sim->fractal) {

@@ -1,4 +1,47 @@
 #pragma once
+// The two forms of a Jacobi cell and the guard that chooses between them (k_jacobi_band, stencil.hip).  Plain C++ with no HIP type in
+// it: a host program that defines SMK_CELL_FORMS_ONLY before including this file compiles exactly this text (tests/test_jacobi_cell_forms.py).
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define SMK_CELL_HD __host__ __device__ inline __attribute__((always_inline))
+#else
+#define SMK_CELL_HD inline
+#endif
+namespace smk {
+// navier_stokes.py:141-145: p_new = 0.25 * (up + dn + l + r - div), one rounding per operation, in this order.
+SMK_CELL_HD float jacobi_cell_exact(float up, float dn, float l, float r, float d) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    float sm = up + dn;
+    sm = sm + l;
+    sm = sm + r;
+    sm = sm - d;
+    return 0.25f * sm;
+}
+// The same cell with nd = jacobi_cell_nd(d) formed once per launch: three adds and one fused multiply-add.  Scaling by 0.25 is exact in the
+// normal range, so the single rounding of fma(S, 0.25, -d/4) is that of 0.25 * fl(S - d) -- as long as -0.25 * d is exact and the result
+// cannot be rounded twice on its way into the denormal range.  jacobi_cell_guard(d) holds for exactly the d where both are certain:
+// d = +-0 (both forms round S / 4 once; the signs of zero agree), or 2^-100 <= |d| <= 2^100 (a result below 2^-124 then needs S within a
+// factor 2 of d, where S - d is exact by Sterbenz).  NaN and Inf fail it.  Without it the forms differ: S = 2^-149, d = -2^-148 gives
+// 2^-149 exactly and 0 fused.
+SMK_CELL_HD float jacobi_cell_nd(float d) { return -0.25f * d; }
+SMK_CELL_HD float jacobi_cell_fused(float up, float dn, float l, float r, float nd) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    float sm = up + dn;
+    sm = sm + l;
+    sm = sm + r;
+    return __builtin_fmaf(sm, 0.25f, nd);
+}
+SMK_CELL_HD bool jacobi_cell_guard(float d) {
+    constexpr unsigned LO = (127u - 100u) << 23, HI = (127u + 100u) << 23;     // the bits of 2^-100 and 2^100
+    const unsigned a = __builtin_bit_cast(unsigned, d) & 0x7fffffffu;
+    return a == 0u || a - LO <= HI - LO;
+}
+}  // namespace smk
+
+#ifndef SMK_CELL_FORMS_ONLY
 #include "common.h"
 
 namespace smk {
@@ -23,6 +66,12 @@ struct ProjectSync {
     unsigned seq = 0;
     int flags_len = 0;
     bool disabled = false;
+    // which cell form the sweeps of each (grid, band) took in the handle's latest projection (device; 1 fused, 0 exact: see the cell
+    // forms above), rewritten by every launch of a kernel that has both forms (forms_two; the others take the exact cell and write nothing);
+    // forms_nb: bands per grid of that projection, 0 when it ran without the band kernel
+    unsigned *forms = nullptr;    // (inside the flags allocation, behind the abort word)
+    int forms_nb = 0;
+    bool forms_two = false;
 };
 hipError_t project_sync_create(ProjectSync &ps, int B);
 void project_sync_destroy(ProjectSync &ps);
@@ -56,3 +105,4 @@ hipError_t launch_apply_fractal(const float *in, float *out, const float *fracta
                                 hipStream_t st);
 
 }  // namespace smk
+#endif  // SMK_CELL_FORMS_ONLY

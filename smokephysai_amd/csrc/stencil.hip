@@ -329,7 +329,8 @@ __device__ __forceinline__ void stv(float *dst, const float (&src)[VEC]) {
 //   whose neighbour never arrives sets *status and the abort word and runs on, so the grid always drains; the host reports it on the
 //   next call.  All bands x grids of one launch must be co-resident (the launcher sizes the grid to the CU count).
 struct JacobiSync {
-    unsigned *flags;          // [B * nb + 1]: per band the number of hand-offs it has published (monotonic over the handle's life); last = abort
+    unsigned *flags;          // [B * nb + 1]: per band the number of hand-offs it has published (monotonic over the handle's life); last = abort;
+                              // behind the abort word, per (grid, band): 1 when the launch's sweeps took the fused cell (stencil.h), 0 the exact one
     unsigned *status;         // host-visible word, set non-zero when a wait timed out
     float *x0, *x1;           // exchange buffers, laid out like p (div and p2 of the handle)
     unsigned base;            // flag value before this projection's first hand-off
@@ -388,13 +389,20 @@ constexpr bool jb_pipelined(int vec, int rpw, bool persist) { return !(persist &
 // (profiles/r07): one row ahead is the fastest split at 4 cells per lane; with none the stores are exposed, with all of them the reads.
 constexpr int jb_rows_before_barrier(int rpw) { return rpw > 2 ? 1 : 0; }
 
+// Whether an instantiation carries both forms of the cell (stencil.h) and the guard that picks one per launch and workgroup: the form of
+// the 256^2 x 64 step alone (persistent with the prologue, 4 cells per lane, 6 rows per wave), whose registers, scratch and occupancy stay
+// where they were with the second sweep loop (125 -> 126 VGPRs) and which has been timed with it.  Every other instantiation has the
+// exact cell only and compiles to the instructions it had before: with two loops the multi-launch forms took 4 - 28 more registers (three
+// of them past the 64 that let two workgroups share a CU), 8 x 3 and 4 x 6 persistent went to the 128 cap, and the 32-cell forms spilled
+// more.
+constexpr bool jb_two_forms(int vec, int rpw, bool persist, bool fold) { return persist && fold && vec == 4 && rpw == 6; }
 // The keep buffer of the PERSIST && FOLD form: the diffused u2 / v2 rows a band owns wait in LDS between the prologue and the gradient
 // epilogue instead of going to HBM and back.  Beside `edge` (64 rows) and the flag word a workgroup, alone on its CU anyway, may declare
 // the rest of the 160 KiB: that many rows of 64 * vec floats, at most the 2 * 16 * rpw a band can own.
 constexpr int JB_LDS_BYTES = 163840;
 constexpr int jb_keep_rows(int vec, int rpw) {
     if (vec == 4 && rpw == 8) return 0;                       // at the 128-VGPR cap already (see jb_pipelined): the slot arithmetic would add spills
-    const int row_bytes = 256 * vec, fit = (JB_LDS_BYTES - 64 * row_bytes - 16) / row_bytes;
+    const int row_bytes = 256 * vec, fit = (JB_LDS_BYTES - 64 * row_bytes - 4 * JB_NW - 16) / row_bytes;
     return fit < 2 * JB_NW * rpw ? fit : 2 * JB_NW * rpw;
 }
 // A band's owned rows are numbered v(own0), u(own0), v(own0 + 1), ... (u row 0 of the grid, which the gradient leaves alone, has no
@@ -415,10 +423,11 @@ __global__ __launch_bounds__(JB_NW * 64) void k_jacobi_band(Geom g, const float 
     constexpr int TR = JB_NW * RPW, ROWF = 64 * VEC;
     __shared__ float edge[2][JB_NW][2][ROWF];
     __shared__ int handoff_failed;                            // PERSIST: lane 0 saw a timed-out / aborted hand-off wait -> poison the band's results
+    __shared__ int guard_failed[JB_NW];                       // per wave: some divergence value of it fails jacobi_cell_guard
     constexpr bool KEEP = PERSIST && FOLD && jb_keep_rows(VEC, RPW) > 0;
     constexpr int KROWS = KEEP ? jb_keep_rows(VEC, RPW) : 1;
     __shared__ __attribute__((aligned(16))) float keep[KROWS][ROWF];      // KEEP: u2 / v2 rows between prologue and epilogue (slot: keep_of)
-    static_assert(sizeof(edge) + sizeof(keep) + 16 <= JB_LDS_BYTES, "edge + keep + the flag word exceed the CU's LDS");
+    static_assert(sizeof(edge) + sizeof(keep) + sizeof(guard_failed) + 16 <= JB_LDS_BYTES, "edge + keep + the flag word exceed the CU's LDS");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // Bands own unequal row ranges: the first and last band of a grid need a halo only on their inner side (the other side is the
     // physical boundary), so they own TR - HALO rows and the middle bands TR - 2 HALO (HALO = BR here).  One band: the whole grid.
@@ -596,227 +605,33 @@ __global__ __launch_bounds__(JB_NW * 64) void k_jacobi_band(Geom g, const float 
     // ring rows (grid row 0 / H-1) exist only in the first wave of the first band and the last wave of the last band
     const int ring_k = __builtin_amdgcn_readfirstlane(row0 == 0 ? 0 : (row0 + RPW == g.H ? RPW - 1 : -1));   // wave-uniform
     static_assert(RPW >= 2, "the sweep keeps a wave's first and last row apart");
-    // one row of a sweep src -> dst; up / dn: the rows above and below (registers, or the neighbour wave's edge row)
-    auto row = [&](const float (&src)[RPW][VEC], float (&dst)[RPW][VEC], int k, const float (&up)[VEC], const float (&dn)[VEC]) {
-        const float lin = wave_shr1(src[k][VEC - 1]), rin = wave_shl1(src[k][0]);
+    // Which cell the sweeps of this launch take (stencil.h): the divergence is the same in all of them, so where every value of the
+    // workgroup passes jacobi_cell_guard, dv becomes -0.25 * div once and a cell is three adds and one fma -- the same words as the exact
+    // cell's five operations.  One verdict per workgroup (the waves meet at the sweeps' barriers and must run the same code); the bands
+    // of a grid may differ.  Nothing reads dv after the sweeps.
+    constexpr bool CAN_FUSE = jb_two_forms(VEC, RPW, PERSIST, FOLD);
+    bool fused = false;
+    if constexpr (CAN_FUSE) {
+        bool lane_bad = false;
 #pragma unroll
-        for (int c = 0; c < VEC; ++c) {
-            const float l = c > 0 ? src[k][c - 1] : lin;
-            const float r = c < VEC - 1 ? src[k][c + 1] : rin;
-            float sm = up[c] + dn[c];
-            sm = sm + l;
-            sm = sm + r;
-            sm = sm - dv[k][c];
-            dst[k][c] = 0.25f * sm;
-        }
-        dst[k][0] = first_col ? 0.f : dst[k][0];              // column ring: only the two edge cells need a select
-        dst[k][VEC - 1] = last_col ? 0.f : dst[k][VEC - 1];
-    };
-    // a wave's first and last row go to edge buffer `par`; the neighbour waves' facing rows come back from it (after a barrier)
-    auto publish = [&](const float (&r)[RPW][VEC], int par) {
+        for (int k = 0; k < RPW; ++k)
 #pragma unroll
-        for (int c = 0; c < VEC; ++c) {
-            edge[par][wave][0][j0 + c] = r[0][c];
-            edge[par][wave][1][j0 + c] = r[RPW - 1][c];
-        }
-    };
-    float above[VEC], below[VEC];
-    auto fetch = [&](int par) {
-        const float *eu = &edge[par][wave > 0 ? wave - 1 : 0][1][j0];            // top wave: value unused (ring or halo row)
-        const float *ed = &edge[par][wave < JB_NW - 1 ? wave + 1 : JB_NW - 1][0][j0];
-#pragma unroll
-        for (int c = 0; c < VEC; ++c) {
-            above[c] = eu[c];
-            below[c] = ed[c];
-        }
-    };
-    // the two rows that need `above` / `below`, with the row ring (grid row 0 / H-1: 2 waves of a grid) as wave-uniform selects -- as
-    // scalar branches they cost more in register copies at the control-flow merges (16 v_mov per sweep) than the 2 * VEC v_cndmask
-    // they save
-    auto edge_rows = [&](const float (&src)[RPW][VEC], float (&dst)[RPW][VEC]) {
-        row(src, dst, 0, above, src[1]);
-        row(src, dst, RPW - 1, src[RPW - 2], below);
-#pragma unroll
-        for (int c = 0; c < VEC; ++c) {
-            dst[0][c] = ring_k == 0 ? 0.f : dst[0][c];
-            dst[RPW - 1][c] = ring_k == RPW - 1 ? 0.f : dst[RPW - 1][c];
-        }
-    };
-    // One sweep src -> dst (register ping-pong: no row copies); par selects the LDS edge buffer.  The order is software-pipelined over two
-    // sweeps (PIPE): `above` / `below` of src are already in registers when a sweep starts (run() primes them); the wave first computes the
-    // two rows that need them and publishes those rows of dst -- the NEXT sweep's edge rows -- into the other buffer, covers the stores with
-    // NA interior rows, passes the barrier, issues the reads of the next sweep's `above` / `below`, and covers those with the remaining
-    // interior rows: no wave waits on an LDS trip with nothing to issue.  What a sweep then costs is the vector issue of its rows, which the
-    // four waves of a SIMD take in turns, the youngest last, the others waiting for it at the barrier (stamps: DESIGN 3.1, profiles/r07).
-    // Buffer s & 1 is rewritten in sweep s + 2, after barrier s + 1, which every wave passes only after it has consumed (in sweep
-    // s + 1's first two rows) what it read from buffer s.  RPW 2 / 3 have 0 / 1 interior rows: the same chain as the plain order.
-    // Plain order (PIPE false): publish src's edge rows, interior rows, barrier, read, the two edge rows.
-    constexpr bool PIPE = jb_pipelined(VEC, RPW, PERSIST);
-    constexpr int NA = jb_rows_before_barrier(RPW);           // interior rows ahead of the barrier (cover the stores); the rest follow the reads
-    auto sweep = [&](const float (&src)[RPW][VEC], float (&dst)[RPW][VEC], int par) {
-        if constexpr (PIPE) {
-            edge_rows(src, dst);
-            publish(dst, par);
-            __builtin_amdgcn_sched_barrier(0);                // first: the neighbours' next sweep waits on these stores
-#pragma unroll
-            for (int k = 1; k < 1 + NA; ++k) row(src, dst, k, src[k - 1], src[k + 1]);
-            __builtin_amdgcn_sched_barrier(0);                // (hipcc otherwise sinks these rows below the barrier)
-            __syncthreads();
-            fetch(par);
-            __builtin_amdgcn_sched_barrier(0);                // reads in flight before the rows that cover them
-#pragma unroll
-            for (int k = 1 + NA; k < RPW - 1; ++k) row(src, dst, k, src[k - 1], src[k + 1]);
-            __builtin_amdgcn_sched_barrier(0);                // (the wait for the reads belongs to the next sweep's first rows)
-        } else {
-            publish(src, par);
-            __builtin_amdgcn_sched_barrier(0);                // publish first: the neighbours' edge rows wait on these stores
-#pragma unroll
-            for (int k = 1; k < RPW - 1; ++k) row(src, dst, k, src[k - 1], src[k + 1]);
-            __builtin_amdgcn_sched_barrier(0);                // (hipcc otherwise sinks these rows below the barrier)
-            __syncthreads();
-            fetch(par);
-            edge_rows(src, dst);
-        }
-    };
-    float pw[RPW][VEC];
-    auto run = [&](int n) {                                   // n sweeps, result in pv
-        if constexpr (PIPE) {
-            // prime the pipeline: pv's own edge rows (after a hand-off: with the halo rows just reloaded) through buffer 1, which the
-            // first sweep leaves alone.  Every caller has a workgroup barrier between a run's last reads and this store.
-            publish(pv, 1);
-            __syncthreads();
-            fetch(1);
-        }
-        int it = 0;
-        for (; it + 2 <= n; it += 2) {
-            sweep(pv, pw, 0);
-            sweep(pw, pv, 1);
-        }
-        if (it < n) {
-            sweep(pv, pw, 0);
-#pragma unroll
-            for (int k = 0; k < RPW; ++k)
-#pragma unroll
-                for (int c = 0; c < VEC; ++c) pv[k][c] = pw[k][c];
-        }
-    };
-    if constexpr (!PERSIST) {
-        run(iters);
-    } else {
-        const int me = b * nb + band;
-        const unsigned row_off = (unsigned)(base * sizeof(float));          // byte offset of this lane's cells of tile row row0 in x0 / x1
-        const unsigned pitch_b = (unsigned)(g.pc * sizeof(float));
-        const unsigned xbytes = (unsigned)((size_t)(sy.grid0 + sy.ngrids) * g.sc * sizeof(float));
-        const __amdgpu_buffer_rsrc_t rx0 = __builtin_amdgcn_make_buffer_rsrc(sy.x0, 0, xbytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rx1 = __builtin_amdgcn_make_buffer_rsrc(sy.x1, 0, xbytes, 0x00020000);
-        int done = 0;
-        if (threadIdx.x == 0) handoff_failed = 0;             // (read only after a hand-off: at least two workgroup barriers later)
-        for (int c = 0; c < sy.chunks; ++c) {
-            const int n = (iters - done + (sy.chunks - c) - 1) / (sy.chunks - c);
-            run(n);
-            done += n;
-            if (c == sy.chunks - 1) break;
-            const __amdgpu_buffer_rsrc_t rx = (c & 1) ? rx1 : rx0;
-            // publish: the `halo` owned rows next to each inner boundary
-#pragma unroll
-            for (int k = 0; k < RPW; ++k) {
-                const int gi = row0 + k;
-                const bool pub = (band > 0 && gi >= own0 && gi < own0 + halo) || (band < nb - 1 && gi >= own1 - halo && gi < own1);
-                if (pub) stv_sc1<VEC>(rx, row_off + k * pitch_b, pv[k]);
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its stores before the barrier
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                const unsigned tgt = sy.base + (unsigned)c + 1u;
-                if (!(sy.fault && me == sy.grid0 * nb))       // (fault injection for the time-out test: one band never publishes)
-                    __hip_atomic_store(sy.flags + me, tgt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const long long t0 = wall_clock64();
-                for (;;) {
-                    const bool up = band == 0 ||
-                        (int)(__hip_atomic_load(sy.flags + me - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - tgt) >= 0;
-                    const bool dn = band == nb - 1 ||
-                        (int)(__hip_atomic_load(sy.flags + me + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - tgt) >= 0;
-                    if (up && dn) break;
-                    if (__hip_atomic_load(sy.flags + sy.abort_slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-                        handoff_failed = 1;                   // another band gave up: this band's halo rows are stale too
-                        break;
-                    }
-                    if (wall_clock64() - t0 > sy.timeout_ticks) {
-                        __hip_atomic_store(sy.flags + sy.abort_slot, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __hip_atomic_store(sy.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                        handoff_failed = 1;
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(2);
-                }
-            }
-            __syncthreads();
-            // refresh: the halo rows (the neighbours' published rows; rows of the tile beyond them stay stale, which `halo` sweeps
-            // cannot carry into the owned range)
-#pragma unroll
-            for (int k = 0; k < RPW; ++k) {
-                const int gi = row0 + k;
-                const bool need = (gi >= own0 - halo && gi < own0) || (gi >= own1 && gi < own1 + halo);
-                if (need) ldv_sc1<VEC>(pv[k], rx, row_off + k * pitch_b);
-            }
-        }
-        // A hand-off that did not complete leaves stale halo rows, and p, u, v are updated in place: results that cannot be right must not
-        // look like data.  The band's p becomes NaN (so do its u, v through the gradient below, and every frame of the grid from here on);
-        // the host reads *status at its next synchronising call (smk_sim_status) and reports the time-out for THIS projection.
-        if (sy.chunks > 1 && handoff_failed) {
-#pragma unroll
-            for (int k = 0; k < RPW; ++k)
-#pragma unroll
-                for (int c = 0; c < VEC; ++c) pv[k][c] = __builtin_nanf("");
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < RPW; ++k) {
-        const int gi = row0 + k;
-        if (gi >= own0 && gi < own1) {
-#pragma unroll
-            for (int c = 0; c < VEC; ++c) p_out[base + (size_t)k * g.pc + c] = pv[k][c];
-        }
-    }
-    if (MODE & 2) {
-        // u[i,:] -= dt*(p[i,:] - p[i-1,:]) for 1 <= i <= H-1;  v[:,j] -= dt*(p[:,j] - p[:,j-1]) for 1 <= j <= W-1
-        __syncthreads();                                      // all reads of the last sweep's edges are done
-#pragma unroll
-        for (int c = 0; c < VEC; ++c) edge[0][wave][1][j0 + c] = pv[RPW - 1][c];
+            for (int c = 0; c < VEC; ++c) lane_bad |= !jacobi_cell_guard(dv[k][c]);
+        const bool wave_bad = __builtin_amdgcn_ballot_w64(lane_bad) != 0ull;       // (all lanes active here: the vote covers the wave)
+        if (lane == 0) guard_failed[wave] = wave_bad;
         __syncthreads();
-        float above[VEC];
-#pragma unroll
-        for (int c = 0; c < VEC; ++c) above[c] = edge[0][wave > 0 ? wave - 1 : 0][1][j0 + c];
-        float *ub = u + b * g.su + (size_t)row0 * g.pc + j0, *vb = v + b * g.sv + (size_t)row0 * g.pv + j0;
-#pragma unroll
-        for (int k = 0; k < RPW; ++k) {
-            const int gi = row0 + k;
-            const float lin = wave_shr1(pv[k][VEC - 1]);
-            if (gi >= own0 && gi < own1) {
-                // whole-row read-modify-write (VEC cells per lane as one load / one store; the untouched cells -- row 0 of u, column 0
-                // of v -- are written back unchanged)
-                float un[VEC], vn[VEC];
-                const int ku = KEEP ? keep_of(gi, 1) : -1, kv = KEEP ? keep_of(gi, 0) : -1;
-                if (ku >= 0) ldv<VEC>(un, &keep[ku][j0]);
-                else ldv<VEC>(un, ub + (size_t)k * g.pc);
-                if (kv >= 0) ldv<VEC>(vn, &keep[kv][j0]);
-                else ldv<VEC>(vn, vb + (size_t)k * g.pv);
-#pragma unroll
-                for (int c = 0; c < VEC; ++c) {
-                    if (gi >= 1) {                            // gi == row0 == 0 only in the first wave of band 0: skipped
-                        const float pu = k > 0 ? pv[k - 1][c] : above[c];
-                        const float gr = pv[k][c] - pu;
-                        un[c] = un[c] - g.dt * gr;
-                    }
-                    const float pl = c > 0 ? pv[k][c - 1] : lin;
-                    const float gr = pv[k][c] - pl;
-                    const float nv = vn[c] - g.dt * gr;
-                    vn[c] = (c == 0 && first_col) ? vn[c] : nv;   // j >= 1 (j <= W-1 always holds here)
-                }
-                if (gi >= 1) stv<VEC>(ub + (size_t)k * g.pc, un);
-                stv<VEC>(vb + (size_t)k * g.pv, vn);
-            }
-        }
+        static_assert(JB_NW <= 64, "one lane per wave's word");
+        fused = __builtin_amdgcn_ballot_w64(guard_failed[lane < JB_NW ? lane : 0] != 0) == 0ull;    // the same words in every wave
+        if (threadIdx.x == 0) sy.flags[sy.abort_slot + 1 + b * nb + band] = fused ? 1u : 0u;      // (a plain store: tests and tools read it)
+        auto rest = [&](auto form) {                          // once per cell form, behind one scalar branch
+            constexpr bool FUSED = decltype(form)::value;
+#include "jacobi_band_tail.h"
+        };
+        if (fused) rest(std::true_type{});
+        else rest(std::false_type{});
+    } else {
+        constexpr bool FUSED = false;
+#include "jacobi_band_tail.h"
     }
 }
 
@@ -985,8 +800,10 @@ hipError_t launch_jacobi(const Geom &g, float *p, float *p2, const float *div, i
 // With a band plan the divergence is computed inside the first Jacobi launch and the gradient subtraction inside the last.
 hipError_t project_sync_create(ProjectSync &ps, int B) {
     ps.flags_len = B * 64 + 1;
-    hipError_t e = hipMalloc((void **)&ps.flags, ps.flags_len * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMemset(ps.flags, 0, ps.flags_len * sizeof(unsigned));
+    // (behind the flags: one cell-form word per (grid, band) of a persistent plan, which has at most 64 bands)
+    hipError_t e = hipMalloc((void **)&ps.flags, (ps.flags_len + B * 64) * sizeof(unsigned));
+    if (e == hipSuccess) e = hipMemset(ps.flags, 0, (ps.flags_len + B * 64) * sizeof(unsigned));
+    ps.forms = ps.flags ? ps.flags + ps.flags_len : nullptr;
     if (e == hipSuccess) e = hipHostMalloc((void **)&ps.status, sizeof(unsigned), hipHostMallocMapped);
     if (e == hipSuccess) *ps.status = 0u;
     return e;
@@ -994,9 +811,14 @@ hipError_t project_sync_create(ProjectSync &ps, int B) {
 void project_sync_destroy(ProjectSync &ps) {
     if (ps.flags) (void)hipFree(ps.flags);
     if (ps.status) (void)hipHostFree((void *)ps.status);
+    ps.forms = nullptr;
     ps.flags = nullptr;
     ps.status = nullptr;
 }
+
+// Can the step's buoyancy + diffusion stage run as the persistent launch's prologue (16-byte row accesses: pitches in multiples of 4; up to
+// 4 cells per lane)?  One place for the launchers and for describe_projection.
+static bool prologue_folds(const Geom &g, const JacobiPlan &pl) { return pl.vec <= 4 && g.pv % 4 == 0 && g.pc % 4 == 0; }
 
 static bool use_persist(const Geom &g, const ProjectSync *ps, int iters, JacobiPlan &pl, int &chunks) {
     if (!ps || !ps->flags || ps->disabled || !knobs().persist || iters < 2) return false;
@@ -1060,14 +882,16 @@ hipError_t launch_project(const Geom &g, float *u, float *v, float *p, float *p2
         sy.flags = ps->flags; sy.status = const_cast<unsigned *>(ps->status); sy.x0 = div; sy.x1 = p2;
         sy.base = ps->seq; sy.chunks = chunks; sy.nb = pl.nb; sy.abort_slot = ps->flags_len - 1; sy.fault = knobs().fault ? 1 : 0;
         sy.timeout_ticks = knobs().fault ? 200000ll : 50000000ll;      // 100 MHz wall clock: 2 ms under fault injection, 0.5 s otherwise
+        ps->forms_nb = pl.nb;
         ps->seq += (unsigned)chunks;
         const std::unique_lock<std::mutex> launch_order = order_persistent_launch(st);
         // the buoyancy + diffusion stage as this launch's prologue (16-byte row accesses: pitches in multiples of 4; up to 4 cells per lane)
-        const bool fold = fold_in && fold_d_out && pl.vec <= 4 && g.pv % 4 == 0 && g.pc % 4 == 0;
+        const bool fold = fold_in && fold_d_out && prologue_folds(g, pl);
         if (fold) {
             sy.u_in = fold_in->u; sy.v_in = fold_in->v; sy.d_in = fold_in->d; sy.d_out = fold_d_out;
             if (folded) *folded = true;
         }
+        ps->forms_two = jb_two_forms(pl.vec, pl.rpw, true, fold);      // (otherwise no workgroup writes its word: all exact)
         for (int g0 = 0; g0 < g.B; g0 += per) {
             sy.grid0 = g0;
             sy.ngrids = g.B - g0 < per ? g.B - g0 : per;
@@ -1077,6 +901,7 @@ hipError_t launch_project(const Geom &g, float *u, float *v, float *p, float *p2
         return hipGetLastError();
     }
     if (iters < 2 || !plan_jacobi(g, pl, iters) || pl.halo < 3) {
+        if (ps) { ps->forms_nb = 0; ps->forms_two = false; }  // (no band kernel in this form)
         hipError_t e = launch_divergence(g, u, v, div, g.pc, g.sc, st);
         if (e != hipSuccess) return e;
         e = launch_jacobi(g, p, p2, div, iters, st);
@@ -1087,6 +912,7 @@ hipError_t launch_project(const Geom &g, float *u, float *v, float *p, float *p2
     const int L = 2 * ((iters + 2 * cap - 1) / (2 * cap));
     float *cur = p, *nxt = p2;
     int done = 0;
+    if (ps) { ps->forms_nb = pl.nb; ps->forms_two = false; }  // (the multi-launch forms have the exact cell only: jb_two_forms)
     for (int c = 0; c < L; ++c) {
         const int n = (iters - done + (L - c) - 1) / (L - c);
         if (c == 0) launch_band_vec<1>(g, pl, cur, nxt, div, u, v, n, st);
@@ -1107,7 +933,7 @@ hipError_t launch_buoy_project(const Geom &g, StateView in, StateView out, float
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     const bool capturing = hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
     const bool pending_error = ps && ps->status && *ps->status != 0u;
-    if (!capturing && !pending_error && use_persist(g, ps, iters, pl, chunks) && pl.vec <= 4 && g.pv % 4 == 0 && g.pc % 4 == 0) {
+    if (!capturing && !pending_error && use_persist(g, ps, iters, pl, chunks) && prologue_folds(g, pl)) {
         const hipError_t e = launch_project(g, out.u, out.v, p, out.p, div, iters, st, ps, &in, out.d, &folded);
         if (e != hipSuccess || folded) return e;
         return hipErrorUnknown;                               // (unreachable: the conditions above are launch_project's own)
@@ -1153,22 +979,26 @@ std::string describe_projection(const Geom &g, int iters, const ProjectSync *ps)
     const int L = persist ? (g.B + per - 1) / per : 2 * ((iters + 2 * cap - 1) / (2 * cap));
     const int parts = persist ? chunks : L;                   // runs of sweeps between two refreshes of the halo rows
     const double wgs = (double)pl.nb * g.B, rounds = ceil(wgs / device_num_cu());
+    const bool step_folds = persist && prologue_folds(g, pl);
+    const bool two_forms = jb_two_forms(pl.vec, pl.rpw, persist, step_folds);   // (of the kernel a whole step launches)
     // measured (tools/probes/valu_probe, 4 waves per SIMD): a sweep row of 64 VEC-cell lanes = ~18 vector instructions of which 2 are DPP
     // wave shifts, ~2.6 cycles per instruction and SIMD -> TR rows on 4 SIMDs.  The edge-row exchange (publish -> s_barrier -> read) is
     // software-pipelined under those rows; what the in-kernel stamps show beyond the estimate is the four waves of a SIMD taking turns at its
     // vector issue, the youngest last, with the others waiting for it at the sweep's barrier (profiles/r07)
-    const double valu_us_per_sweep = rounds * (TR / 4.0) * 18.0 * 2.6 / 2100.0;
+    // (with both cell forms a row is one instruction per cell shorter on the fused cell, which all but a trajectory's first steps take)
+    const double valu_us_per_sweep = rounds * (TR / 4.0) * (18.0 - (two_forms ? pl.vec : 0)) * 2.6 / 2100.0;
     // (the keep buffer belongs to the form launch_buoy_project folds the step's first stage into: the conditions are its own)
-    const KeepStats ks = persist && pl.vec <= 4 && g.pv % 4 == 0 && g.pc % 4 == 0 ? keep_stats(g, pl) : KeepStats{0, 0, 0};
+    const KeepStats ks = step_folds ? keep_stats(g, pl) : KeepStats{0, 0, 0};
     snprintf(buf, sizeof buf,
              "{\"kernel\": \"k_jacobi_band<%d,%d>\", \"persistent\": %s, \"bands_per_grid\": %d, \"rows_per_workgroup\": %d, \"halo_rows\": %d, "
              "\"workgroups\": %d, \"launches\": %d, \"halo_handoffs\": %d, \"sweeps\": %d, \"sweeps_per_chunk\": %d, \"redundant_row_factor\": %.3f, "
-             "\"keep_rows_per_band\": %d, \"keep_overflow_rows_max\": %d, \"keep_rows_per_grid\": %d, "
+             "\"keep_rows_per_band\": %d, \"keep_overflow_rows_max\": %d, \"keep_rows_per_grid\": %d, \"cell_forms_of_a_step\": %d, "
              "\"vector_issue_us_per_sweep_estimate\": %.3f, \"vector_issue_us_total_estimate\": %.1f, "
              "\"bound\": \"on-chip: sweeps x vector issue of rows_per_workgroup rows, one barrier per sweep (%s); p and div are "
              "register-resident %s\"}",
              pl.vec, pl.rpw, persist ? "true" : "false", pl.nb, TR, pl.halo, (int)wgs, L, persist ? chunks - 1 : 0, iters, (iters + parts - 1) / parts,
-             (double)pl.nb * TR / g.H, ks.slots, ks.max_overflow, ks.kept_per_grid, valu_us_per_sweep, valu_us_per_sweep * iters,
+             (double)pl.nb * TR / g.H, ks.slots, ks.max_overflow, ks.kept_per_grid,
+             two_forms ? 2 : 1, valu_us_per_sweep, valu_us_per_sweep * iters,
              jb_pipelined(pl.vec, pl.rpw, persist)
                  ? "the LDS edge-row exchange is pipelined over two sweeps: a wave's two edge rows and their publish come first, the interior rows "
                    "cover the stores and the read of the next sweep's neighbour rows"

@@ -211,6 +211,15 @@ class NavierStokesSimulator(nn.Module):
         _lib.check(self._L.smk_sim_describe(self._handle, buf, 4096))
         return json.loads(buf.value.decode())
 
+    def sweep_forms(self):
+        """Which form of the Jacobi cell the latest projection's sweeps took: a [B, bands_per_grid] list of lists, 1 = three adds and one
+        fma (every divergence value of the band passed the guard), 0 = the reference's five operations (always so where the kernel has that form only: jacobi_plan()'s cell_forms_of_a_step); both give the same words.
+        Synchronises the current stream: for tests and tools.  Empty rows when no projection has run on the band kernel."""
+        cap = self._B * max(64, self.h // 8)
+        out, nb = (C.c_int32 * cap)(), C.c_int32(0)
+        _lib.check(self._L.smk_sim_sweep_forms(self._handle, out, cap, C.byref(nb), self._st()))
+        return [[int(out[b * nb.value + k]) for k in range(nb.value)] for b in range(self._B)]
+
     def step(self) -> torch.Tensor:
         """navier_stokes.py:151-173 -- one time step; returns a copy of the density."""
         out = torch.empty(self._B, self.h, self.w, device=self._dev)
