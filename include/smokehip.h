@@ -273,6 +273,56 @@ int smk_image_quality(const float *pred, int64_t pred_stride, const float *targe
                       int32_t W, int32_t window, double c1, double c2, void *workspace, int64_t workspace_bytes, double *ssim_sum,
                       double *sqerr_sum, void *stream);
 
+/* ------------------------------------------------------------------ optical-flow baselines
+ * The reference's benchmark.py compares the model with cv2.calcOpticalFlowFarneback, cv2.goodFeaturesToTrack +
+ * cv2.calcOpticalFlowPyrLK and cv2.remap.  These entry points implement the published algorithms with the reference's call parameters
+ * (DESIGN.md "Optical-flow baselines" is the specification; equality with cv2's own output is unmeasured).  Frames are n dense uint8
+ * planes [n][H][W], 32 <= H, W <= 1024, n <= 65535; flows are [n][H][W][2] fp32 (dx, dy).  Everything runs on `stream`; scratch is the
+ * caller's workspace (256-byte aligned device memory of at least the matching *_workspace bytes, passed with its size); nothing is
+ * allocated and the host never waits, so a sequence can be captured into a hipGraph.  Results repeat bit for bit.  A shape outside the
+ * limits returns SMK_ERR_INVALID (the workspace queries return 0, the level count 0).
+ *
+ * Farneback (pyr_scale 0.5, 3 levels, window 15, 3 iterations, poly_n 5, poly_sigma 1.2, flags 0), also stage by stage:
+ *   levels K: the largest K <= 3 with min(H, W) * 0.5^(K-1) >= 32; level k has size (round(H 0.5^k), round(W 0.5^k)), half to even
+ *   level_image: frames -> out [n][h_k][w_k] fp32 (Gaussian blur of the full frame, then bilinear resize)
+ *   poly_exp: img [n][h][w] -> coef [n][5][h][w] = (bx, by, axx, ayy, axy)
+ *   farneback_iteration: one matrix update + 15 x 15 box mean + solve; flow [n][h][w][2] is read and overwritten
+ * smk_flow_farneback_workspace(n, H, W) serves all four (for a stage call on a level, (n, h, w) of that level is enough). */
+int32_t smk_flow_levels(int32_t H, int32_t W);
+int64_t smk_flow_farneback_workspace(int32_t n, int32_t H, int32_t W);
+int smk_flow_level_image(const uint8_t *frames, int32_t n, int32_t H, int32_t W, int32_t level, float *out, void *workspace,
+                         int64_t workspace_bytes, void *stream);
+int smk_flow_poly_exp(const float *img, int32_t n, int32_t h, int32_t w, float *coef, void *stream);
+int smk_flow_farneback_iteration(const float *coef0, const float *coef1, float *flow, int32_t n, int32_t h, int32_t w, void *workspace,
+                                 int64_t workspace_bytes, void *stream);
+int smk_flow_farneback(const uint8_t *prev, const uint8_t *next, int32_t n, int32_t H, int32_t W, float *flow, void *workspace,
+                       int64_t workspace_bytes, void *stream);
+
+/* predict_next_frame: pred(y, x) = bilinear sample of prev at (x + dx, y + dy), taps outside the image read 0, rounded half to even and
+ * saturated to uint8.  With next and mse (both or neither): mse [n] = fp64 mean of (next - pred)^2 on the 0..255 scale (exact integer
+ * sums); the workspace is needed only then. */
+int64_t smk_warp_workspace(int32_t n, int32_t H, int32_t W);
+int smk_warp_frames(const uint8_t *prev, const float *flow, const uint8_t *next, int32_t n, int32_t H, int32_t W, uint8_t *pred,
+                    double *mse, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* Lucas-Kanade as the reference builds it: Shi-Tomasi corners (100 corners, quality 0.3, distance 7, block 7), pyramidal tracking
+ * (window 15 x 15, maxLevel 2, 30 iterations or |delta| < 0.01), and a flow field that is zero except at the tracked corners.
+ *   min_eigen: frames -> eig [n][H][W], the smaller eigenvalue of the 7 x 7 structure tensor of the Sobel derivatives
+ *   good_features: eig -> pts [n][100][2] (x, y) in order of selection, counts [n]; unused slots are 0
+ *   lk_track: pts, counts -> out_pts [n][100][2], status [n][100] (1 = tracked)
+ *   lk_scatter: zeroes flow, then flow[int(y0), int(x0)] = out - pt for every tracked point
+ * smk_flow_lk_workspace(n, H, W) serves good_features, lk_track and the whole method. */
+int64_t smk_flow_lk_workspace(int32_t n, int32_t H, int32_t W);
+int smk_flow_min_eigen(const uint8_t *frames, int32_t n, int32_t H, int32_t W, float *eig, void *stream);
+int smk_good_features(const float *eig, int32_t n, int32_t H, int32_t W, float *pts, int32_t *counts, void *workspace,
+                      int64_t workspace_bytes, void *stream);
+int smk_flow_lk_track(const uint8_t *prev, const uint8_t *next, int32_t n, int32_t H, int32_t W, const float *pts, const int32_t *counts,
+                      float *out_pts, uint8_t *status, void *workspace, int64_t workspace_bytes, void *stream);
+int smk_flow_lk_scatter(const float *pts, const float *out_pts, const uint8_t *status, const int32_t *counts, int32_t n, int32_t H,
+                        int32_t W, float *flow, void *stream);
+int smk_flow_lucas_kanade(const uint8_t *prev, const uint8_t *next, int32_t n, int32_t H, int32_t W, float *flow, void *workspace,
+                          int64_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ CNN encoder */
 /* SMK_F32: fp32 MFMA; SMK_BF16X3: split-bf16 MFMA (fp32-class accuracy); SMK_BF16: single-pass bf16;
  * SMK_I8X3: 16-bit fixed point as two int8 limbs on int8 MFMA (per-tile activation scale, exact i32 accumulation). */

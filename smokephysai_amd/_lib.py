@@ -101,6 +101,16 @@ _SIGNATURES = {
                            C.c_void_p, C.c_void_p],
     "smk_image_quality": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                           C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "smk_flow_level_image": [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    "smk_flow_poly_exp": [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p],
+    "smk_flow_farneback_iteration": [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p, C.c_int64, C.c_void_p],
+    "smk_flow_farneback": [C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    "smk_warp_frames": [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    "smk_flow_min_eigen": [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p],
+    "smk_good_features": [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    "smk_flow_lk_track": [C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p],
+    "smk_flow_lk_scatter": [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p],
+    "smk_flow_lucas_kanade": [C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
     "smk_encoder_create": [C.POINTER(SmkEncoderWeights), C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)],
     "smk_encoder_destroy": [C.c_void_p],
     "smk_encoder_forward": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -171,7 +181,8 @@ _SIGNATURES = {
 }
 EXPORTS = ["smk_abi_version", "smk_last_error", "smk_linear_wgrad_workspace", "smk_bn_train_workspace", "smk_layernorm_bwd_workspace", "smk_conv2_train_workspace", "smk_conv2_train_wgrad_workspace", "smk_conv1_train_wgrad_workspace", "smk_attention_workspace_bytes", "smk_linear_ln_max_rows", "smk_image_quality_workspace", "smk_convt4s2_train_wgrad_workspace",
            "smk_volume_stats_workspace", "smk_grad_norm_workspace", "smk_train_loss_workspace",
-           "smk_conv3_sigmoid_train_workspace"] + list(_SIGNATURES)
+           "smk_conv3_sigmoid_train_workspace", "smk_flow_levels", "smk_flow_farneback_workspace", "smk_warp_workspace",
+           "smk_flow_lk_workspace"] + list(_SIGNATURES)
 
 _lib = None
 
@@ -231,6 +242,11 @@ def load():
         L.smk_grad_norm_workspace.restype = C.c_int64
         L.smk_train_loss_workspace.argtypes = [C.c_int32] * 4 + [C.c_int64]
         L.smk_train_loss_workspace.restype = C.c_int64
+        L.smk_flow_levels.argtypes = [C.c_int32] * 2
+        L.smk_flow_levels.restype = C.c_int32                     # a level count, not a status
+        for name in ("smk_flow_farneback_workspace", "smk_warp_workspace", "smk_flow_lk_workspace"):
+            getattr(L, name).argtypes = [C.c_int32] * 3
+            getattr(L, name).restype = C.c_int64
         for name, args in _SIGNATURES.items():
             fn = getattr(L, name)
             fn.argtypes = args

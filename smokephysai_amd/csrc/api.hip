@@ -14,6 +14,7 @@
 #include "elementwise.h"
 #include "encoder.h"
 #include "encoder_train.h"
+#include "flow.h"
 #include "linear.h"
 #include "loss.h"
 #include "norm.h"
@@ -844,6 +845,124 @@ int smk_image_quality(const float *pred, int64_t pred_stride, const float *targe
     return check_launch(launch_image_quality(pred, pred_stride, target, target_stride, n, H, W, window, (float)c1, (float)c2, workspace,
                                              ssim_sum, sqerr_sum, (hipStream_t)stream),
                         "image_quality");
+}
+
+// ------------------------------------------------------------------ optical-flow baselines (Farneback, Lucas-Kanade, warp)
+namespace {
+int check_flow_shape(int32_t n, int32_t H, int32_t W) {
+    SMK_REQUIRE(n >= 1 && n <= 65535, "1 <= n <= 65535 frame pairs");
+    SMK_REQUIRE(H >= FLOW_MIN_DIM && H <= FLOW_MAX_DIM && W >= FLOW_MIN_DIM && W <= FLOW_MAX_DIM, "32 <= H, W <= 1024");
+    return SMK_OK;
+}
+bool flow_shape_ok(int32_t n, int32_t H, int32_t W) {
+    return n >= 1 && n <= 65535 && H >= FLOW_MIN_DIM && H <= FLOW_MAX_DIM && W >= FLOW_MIN_DIM && W <= FLOW_MAX_DIM;
+}
+}  // namespace
+
+int32_t smk_flow_levels(int32_t H, int32_t W) { return flow_levels(H, W); }
+
+int64_t smk_flow_farneback_workspace(int32_t n, int32_t H, int32_t W) {
+    return flow_shape_ok(n, H, W) ? (int64_t)farneback_workspace_bytes(n, H, W) : 0;
+}
+int64_t smk_warp_workspace(int32_t n, int32_t H, int32_t W) {
+    return flow_shape_ok(n, H, W) ? (int64_t)warp_workspace_bytes(n, H, W) : 0;
+}
+int64_t smk_flow_lk_workspace(int32_t n, int32_t H, int32_t W) {
+    return flow_shape_ok(n, H, W) ? (int64_t)lk_workspace_bytes(n, H, W) : 0;
+}
+
+int smk_flow_level_image(const uint8_t *frames, int32_t n, int32_t H, int32_t W, int32_t level, float *out, void *workspace,
+                         int64_t workspace_bytes, void *stream) {
+    SMK_REQUIRE(frames && out && workspace, "null pointer");
+    if (int rc = check_flow_shape(n, H, W)) return rc;
+    SMK_REQUIRE(level >= 0 && level < flow_levels(H, W), "level: 0 .. smk_flow_levels(H, W) - 1");
+    SMK_REQUIRE(((uintptr_t)out & 3) == 0 && ((uintptr_t)workspace & 7) == 0, "4-byte aligned out, 8-byte aligned workspace");
+    SMK_REQUIRE(workspace_bytes >= smk_flow_farneback_workspace(n, H, W), "workspace smaller than smk_flow_farneback_workspace(n, H, W)");
+    return check_launch(launch_flow_level_image(frames, n, H, W, level, out, workspace, (hipStream_t)stream), "flow_level_image");
+}
+
+int smk_flow_poly_exp(const float *img, int32_t n, int32_t h, int32_t w, float *coef, void *stream) {
+    SMK_REQUIRE(img && coef, "null pointer");
+    if (int rc = check_flow_shape(n, h, w)) return rc;
+    SMK_REQUIRE((((uintptr_t)img | (uintptr_t)coef) & 3) == 0, "4-byte aligned img, coef");
+    return check_launch(launch_flow_poly_exp(img, n, h, w, coef, (hipStream_t)stream), "flow_poly_exp");
+}
+
+int smk_flow_farneback_iteration(const float *coef0, const float *coef1, float *flow, int32_t n, int32_t h, int32_t w, void *workspace,
+                                 int64_t workspace_bytes, void *stream) {
+    SMK_REQUIRE(coef0 && coef1 && flow && workspace, "null pointer");
+    if (int rc = check_flow_shape(n, h, w)) return rc;
+    SMK_REQUIRE((((uintptr_t)coef0 | (uintptr_t)coef1) & 3) == 0 && ((uintptr_t)flow & 7) == 0 && ((uintptr_t)workspace & 7) == 0,
+                "4-byte aligned coefficients, 8-byte aligned flow and workspace");
+    SMK_REQUIRE(workspace_bytes >= smk_flow_farneback_workspace(n, h, w), "workspace smaller than smk_flow_farneback_workspace(n, h, w)");
+    return check_launch(launch_flow_iteration(coef0, coef1, flow, n, h, w, workspace, (hipStream_t)stream), "flow_farneback_iteration");
+}
+
+int smk_flow_farneback(const uint8_t *prev, const uint8_t *next, int32_t n, int32_t H, int32_t W, float *flow, void *workspace,
+                       int64_t workspace_bytes, void *stream) {
+    SMK_REQUIRE(prev && next && flow && workspace, "null pointer");
+    if (int rc = check_flow_shape(n, H, W)) return rc;
+    SMK_REQUIRE(((uintptr_t)flow & 7) == 0 && ((uintptr_t)workspace & 255) == 0, "8-byte aligned flow, 256-byte aligned workspace");
+    SMK_REQUIRE(workspace_bytes >= smk_flow_farneback_workspace(n, H, W), "workspace smaller than smk_flow_farneback_workspace(n, H, W)");
+    return check_launch(launch_flow_farneback(prev, next, n, H, W, flow, workspace, (hipStream_t)stream), "flow_farneback");
+}
+
+int smk_warp_frames(const uint8_t *prev, const float *flow, const uint8_t *next, int32_t n, int32_t H, int32_t W, uint8_t *pred,
+                    double *mse, void *workspace, int64_t workspace_bytes, void *stream) {
+    SMK_REQUIRE(prev && flow && pred, "null pointer");
+    SMK_REQUIRE((next == nullptr) == (mse == nullptr), "next and mse: both or neither");
+    if (int rc = check_flow_shape(n, H, W)) return rc;
+    SMK_REQUIRE(((uintptr_t)flow & 7) == 0, "8-byte aligned flow");
+    if (next) {
+        SMK_REQUIRE(workspace && ((uintptr_t)workspace & 3) == 0 && ((uintptr_t)mse & 7) == 0, "workspace and 8-byte aligned mse");
+        SMK_REQUIRE(workspace_bytes >= smk_warp_workspace(n, H, W), "workspace smaller than smk_warp_workspace(n, H, W)");
+    }
+    return check_launch(launch_warp_frames(prev, flow, next, n, H, W, pred, mse, workspace, (hipStream_t)stream), "warp_frames");
+}
+
+int smk_flow_min_eigen(const uint8_t *frames, int32_t n, int32_t H, int32_t W, float *eig, void *stream) {
+    SMK_REQUIRE(frames && eig, "null pointer");
+    if (int rc = check_flow_shape(n, H, W)) return rc;
+    SMK_REQUIRE(((uintptr_t)eig & 3) == 0, "4-byte aligned eig");
+    return check_launch(launch_flow_min_eigen(frames, n, H, W, eig, (hipStream_t)stream), "flow_min_eigen");
+}
+
+int smk_good_features(const float *eig, int32_t n, int32_t H, int32_t W, float *pts, int32_t *counts, void *workspace,
+                      int64_t workspace_bytes, void *stream) {
+    SMK_REQUIRE(eig && pts && counts && workspace, "null pointer");
+    if (int rc = check_flow_shape(n, H, W)) return rc;
+    SMK_REQUIRE((((uintptr_t)eig | (uintptr_t)pts | (uintptr_t)counts) & 3) == 0 && ((uintptr_t)workspace & 255) == 0,
+                "4-byte aligned eig, pts, counts; 256-byte aligned workspace");
+    SMK_REQUIRE(workspace_bytes >= smk_flow_lk_workspace(n, H, W), "workspace smaller than smk_flow_lk_workspace(n, H, W)");
+    return check_launch(launch_good_features(eig, n, H, W, pts, counts, workspace, (hipStream_t)stream), "good_features");
+}
+
+int smk_flow_lk_track(const uint8_t *prev, const uint8_t *next, int32_t n, int32_t H, int32_t W, const float *pts, const int32_t *counts,
+                      float *out_pts, uint8_t *status, void *workspace, int64_t workspace_bytes, void *stream) {
+    SMK_REQUIRE(prev && next && pts && counts && out_pts && status && workspace, "null pointer");
+    if (int rc = check_flow_shape(n, H, W)) return rc;
+    SMK_REQUIRE((((uintptr_t)pts | (uintptr_t)counts | (uintptr_t)out_pts) & 3) == 0 && ((uintptr_t)workspace & 255) == 0,
+                "4-byte aligned pts, counts, out_pts; 256-byte aligned workspace");
+    SMK_REQUIRE(workspace_bytes >= smk_flow_lk_workspace(n, H, W), "workspace smaller than smk_flow_lk_workspace(n, H, W)");
+    return check_launch(launch_lk_track(prev, next, n, H, W, pts, counts, out_pts, status, workspace, (hipStream_t)stream), "flow_lk_track");
+}
+
+int smk_flow_lk_scatter(const float *pts, const float *out_pts, const uint8_t *status, const int32_t *counts, int32_t n, int32_t H,
+                        int32_t W, float *flow, void *stream) {
+    SMK_REQUIRE(pts && out_pts && status && counts && flow, "null pointer");
+    if (int rc = check_flow_shape(n, H, W)) return rc;
+    SMK_REQUIRE((((uintptr_t)pts | (uintptr_t)counts | (uintptr_t)out_pts) & 3) == 0 && ((uintptr_t)flow & 7) == 0,
+                "4-byte aligned pts, counts, out_pts; 8-byte aligned flow");
+    return check_launch(launch_lk_scatter(pts, out_pts, status, counts, n, H, W, flow, (hipStream_t)stream), "flow_lk_scatter");
+}
+
+int smk_flow_lucas_kanade(const uint8_t *prev, const uint8_t *next, int32_t n, int32_t H, int32_t W, float *flow, void *workspace,
+                          int64_t workspace_bytes, void *stream) {
+    SMK_REQUIRE(prev && next && flow && workspace, "null pointer");
+    if (int rc = check_flow_shape(n, H, W)) return rc;
+    SMK_REQUIRE(((uintptr_t)flow & 7) == 0 && ((uintptr_t)workspace & 255) == 0, "8-byte aligned flow, 256-byte aligned workspace");
+    SMK_REQUIRE(workspace_bytes >= smk_flow_lk_workspace(n, H, W), "workspace smaller than smk_flow_lk_workspace(n, H, W)");
+    return check_launch(launch_flow_lucas_kanade(prev, next, n, H, W, flow, workspace, (hipStream_t)stream), "flow_lucas_kanade");
 }
 
 // ------------------------------------------------------------------ train step tail: gradient norm, AdamW, loss terms
