@@ -122,7 +122,7 @@
         int done = 0;
         if (threadIdx.x == 0) handoff_failed = 0;             // (read only after a hand-off: at least two workgroup barriers later)
         for (int c = 0; c < sy.chunks; ++c) {
-            const int n = (iters - done + (sy.chunks - c) - 1) / (sy.chunks - c);
+            const int n = jb_run_sweeps(iters, done, sy.chunks, c);
             run(n);
             done += n;
             if (c == sy.chunks - 1) break;

@@ -8,6 +8,7 @@
 #include <mutex>
 
 #include "stencil.h"
+#include "jacobi_plan.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -280,8 +281,6 @@ __device__ __forceinline__ float wave_shl1(float x) {   // lane i <- lane i+1 (l
     return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x130, 0xf, 0xf, true));
 }
 
-constexpr int JB_NW = 16;
-
 template <int VEC> struct VecT;
 template <> struct VecT<1> { using type = float; };
 template <> struct VecT<2> { using type = float2; };
@@ -382,39 +381,6 @@ __device__ __forceinline__ void stv_sc1(__amdgpu_buffer_rsrc_t rs, unsigned byte
     }
 }
 
-// Which order a sweep of k_jacobi_band takes (see `sweep` there), and how its interior rows split around the barrier.
-// The persistent 4 x 8 instantiations sit at the 128-VGPR cap of a 1024-thread workgroup and would spill more in the pipelined order.
-constexpr bool jb_pipelined(int vec, int rpw, bool persist) { return !(persist && vec == 4 && rpw == 8); }
-// Interior rows computed ahead of the barrier (they cover the publish); the others follow the reads.  Measured at 6 and 8 rows per wave
-// (profiles/r07): one row ahead is the fastest split at 4 cells per lane; with none the stores are exposed, with all of them the reads.
-constexpr int jb_rows_before_barrier(int rpw) { return rpw > 2 ? 1 : 0; }
-
-// Whether an instantiation carries both forms of the cell (stencil.h) and the guard that picks one per launch and workgroup: the form of
-// the 256^2 x 64 step alone (persistent with the prologue, 4 cells per lane, 6 rows per wave), whose registers, scratch and occupancy stay
-// where they were with the second sweep loop (125 -> 126 VGPRs) and which has been timed with it.  Every other instantiation has the
-// exact cell only and compiles to the instructions it had before: with two loops the multi-launch forms took 4 - 28 more registers (three
-// of them past the 64 that let two workgroups share a CU), 8 x 3 and 4 x 6 persistent went to the 128 cap, and the 32-cell forms spilled
-// more.
-constexpr bool jb_two_forms(int vec, int rpw, bool persist, bool fold) { return persist && fold && vec == 4 && rpw == 6; }
-// The keep buffer of the PERSIST && FOLD form: the diffused u2 / v2 rows a band owns wait in LDS between the prologue and the gradient
-// epilogue instead of going to HBM and back.  Beside `edge` (64 rows) and the flag word a workgroup, alone on its CU anyway, may declare
-// the rest of the 160 KiB: that many rows of 64 * vec floats, at most the 2 * 16 * rpw a band can own.
-constexpr int JB_LDS_BYTES = 163840;
-constexpr int jb_keep_rows(int vec, int rpw) {
-    if (vec == 4 && rpw == 8) return 0;                       // at the 128-VGPR cap already (see jb_pipelined): the slot arithmetic would add spills
-    const int row_bytes = 256 * vec, fit = (JB_LDS_BYTES - 64 * row_bytes - 4 * JB_NW - 16) / row_bytes;
-    return fit < 2 * JB_NW * rpw ? fit : 2 * JB_NW * rpw;
-}
-// A band's owned rows are numbered v(own0), u(own0), v(own0 + 1), ... (u row 0 of the grid, which the gradient leaves alone, has no
-// number): n of them.  With more rows than slots every (n / slots)-th row, in 16.16 fixed point, goes without one, so the rows that
-// stay on the HBM path are spread evenly over the waves of the band rather than falling on its last waves.  The scale is rounded up,
-// which for n <= 256 rows uses every slot and none twice.
-__host__ __device__ constexpr int jb_keep_scale(int n, int slots) { return n <= slots ? 65536 : (slots * 65536 + n - 1) / n; }
-__host__ __device__ constexpr int jb_keep_slot(int idx, int scale) {      // the row's slot, or -1: no slot
-    const int s = (idx * scale) >> 16;
-    return (((idx + 1) * scale) >> 16) > s ? s : -1;
-}
-
 template <int VEC, int RPW, int MODE, bool PERSIST = false, bool FOLD = false>
 __global__ __launch_bounds__(JB_NW * 64) void k_jacobi_band(Geom g, const float *__restrict__ p_in,
                                                             float *__restrict__ p_out, float *__restrict__ div,
@@ -429,8 +395,6 @@ __global__ __launch_bounds__(JB_NW * 64) void k_jacobi_band(Geom g, const float 
     __shared__ __attribute__((aligned(16))) float keep[KROWS][ROWF];      // KEEP: u2 / v2 rows between prologue and epilogue (slot: keep_of)
     static_assert(sizeof(edge) + sizeof(keep) + sizeof(guard_failed) + 16 <= JB_LDS_BYTES, "edge + keep + the flag word exceed the CU's LDS");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // Bands own unequal row ranges: the first and last band of a grid need a halo only on their inner side (the other side is the
-    // physical boundary), so they own TR - HALO rows and the middle bands TR - 2 HALO (HALO = BR here).  One band: the whole grid.
     int band_, grid_, nb_;
     if constexpr (PERSIST) {
         // 1-D launch.  Blocks i and i + 8 share an XCD (round-robin dispatch: observed, not promised -- only the hand-off's speed depends
@@ -450,6 +414,8 @@ __global__ __launch_bounds__(JB_NW * 64) void k_jacobi_band(Geom g, const float 
         band_ = blockIdx.x; grid_ = blockIdx.y; nb_ = gridDim.x;
     }
     const int band = band_, b = grid_, nb = nb_, halo = BR;
+    // The rows this band owns and its tile's first row: the lines of jb_band_rows (jacobi_plan.h), which the host side calls.  Here they
+    // stay as text: behind the call the same arithmetic is scheduled differently in every instantiation.
     const int e_rows = TR - halo, m_rows = TR - 2 * halo;
     const int own0 = band == 0 ? 0 : e_rows + (band - 1) * m_rows;
     int own1 = band == nb - 1 ? g.H : e_rows + band * m_rows;
@@ -464,7 +430,7 @@ __global__ __launch_bounds__(JB_NW * 64) void k_jacobi_band(Geom g, const float 
     // KEEP: slot of the owned u (field 1) / v (field 0) row gi, -1 when the row takes the HBM path.  Wave-uniform; only the wave that
     // wrote a slot reads it, so no barrier orders the two.
     const int u_first = own0 > 1 ? own0 : 1;
-    const int keep_scale = jb_keep_scale((own1 - u_first) + (own1 - own0), KROWS);
+    const int keep_scale = jb_keep_scale((own1 - u_first) + (own1 - own0), KROWS);      // (jb_keep_rows_numbered)
     auto keep_of = [&](int gi, int field) {
         const int first = field ? u_first : own0;
         const int s = (gi >= first && gi < own1) ? jb_keep_slot(2 * (gi - first) + field, keep_scale) : -1;
@@ -651,141 +617,82 @@ static const StencilKnobs &knobs() {
     return k;
 }
 
-// Band plan for the register-resident kernel; false -> use the generic per-sweep kernel.
-struct JacobiPlan { int vec, rpw, br, nb, halo; };
-// persist: cost the plan for the single-launch form (a hand-off between chunks instead of a relaunch)
-static bool plan_jacobi(const Geom &g, JacobiPlan &pl, int iters = 100, bool persist = false) {
-    if (g.W % 64 != 0 || g.W / 64 > 8 || (g.W / 64 & (g.W / 64 - 1)) || g.pc % 4 != 0) return false;
-    pl.vec = g.W / 64;
-    // candidates: rows/wave; pick the plan with the least estimated time ~ launches*(t0 + iters*waves_of_work)
-    const int rpws[] = {2, 3, 4, 6, 8};
-    double best = 1e30;
-    bool ok = false;
-    for (int rpw : rpws) {
-        if (pl.vec * rpw > 32) continue;                      // register budget (p + div)
-        const int TR = JB_NW * rpw;
-        if (TR > g.H) continue;
-        for (int nb = 1; nb <= g.H / 8; ++nb) {
-            // nb bands of TR rows cover H owned rows with a halo on every inner side: 2 (TR - h) + (nb - 2)(TR - 2h) >= H
-            int halo = nb == 1 ? 1 << 20 : (nb * TR - g.H) / (2 * nb - 2);
-            if (nb == 1 && TR != g.H) continue;
-            if (nb * TR < g.H || halo < 2) continue;
-            if (nb > 1) {
-                if (halo > 64) halo = 64;
-                if (halo > (TR - 1) / 2) halo = (TR - 1) / 2;          // middle bands keep at least one owned row
-                if ((TR - halo) + (nb - 2) * (TR - 2 * halo) >= g.H) continue;   // a smaller halo than the cover needs: the last band would own nothing
-            }
-            if (persist && nb > 1) {                          // every band must own more rows than the halo (persist_chunks)
-                const int e_rows = TR - halo, m_rows = TR - 2 * halo, last = g.H - (e_rows + (nb - 2) * m_rows);
-                if (e_rows <= halo || last <= halo || (nb > 2 && m_rows <= halo) || nb > 64) continue;
-            }
-            const int br = halo;                              // handed to the kernel (it derives the owned ranges from it)
-            const double wgs = (double)nb * g.B, rounds = ceil(wgs / 256.0);
-            // measured on MI355X with the pipelined sweep (profiles/r07/planner_fit.json: 256 rows x 64 grids at 6 rows per wave, J = 20 / 40 /
-            // 60 / 100, and the nearest plans of 128^2 x 32 / x 64 at J = 20): a sweep of a 96-row workgroup takes 0.32 / 0.51 / 0.83 us at 1 / 2 /
-            // 4 cells per lane, roughly linear in the rows a CU owns; prologue, loads and the gradient cost a row about 13 sweeps' worth; a
-            // hand-off inside the persistent launch (2 * halo rows per band through sc1 stores / flag / sc1 loads) 2.8 us; a launch ~6 us, and
-            // a relaunch reloads the band's p and div (~6 us with the boundary)
-            const double cost_per_sweep = rounds * TR * ((0.15 + 0.17 * pl.vec) / 96.0), launch = 6.0, handoff = 2.8, fixed_sweeps = 13.0;
-            int chunks = 1;                                   // as persist_chunks() will cut the sweeps
-            if (persist && nb > 1) {
-                chunks = (iters + halo - 1) / halo;
-                if (chunks < 2) chunks = 2;
-                while (chunks < iters && ((iters + chunks - 1) / chunks > halo || iters / chunks > halo - 1)) ++chunks;
-            }
-            const double cost = persist ? launch + (chunks - 1) * handoff + (iters + fixed_sweeps) * cost_per_sweep
-                                        : 2 * ceil(0.5 * iters / halo) * launch + iters * cost_per_sweep;
-            if (cost < best) { best = cost; pl.rpw = rpw; pl.br = br; pl.nb = nb; pl.halo = halo; ok = true; }
+static PlanGeom plan_geom(const Geom &g) { return PlanGeom{g.H, g.W, g.B, g.pc, g.pv, g.sc}; }
+
+// A plan's (vec, rpw) as compile-time constants: f(VEC, RPW), two std::integral_constant, for every pair that has a kernel -- 6 and 8
+// rows per wave only up to 4 cells per lane (the register budget of jb_search_bands).
+template <class F>
+static void with_band_shape(const ProjectionPlan &pp, F &&f) {
+    auto call = [&](auto vec, auto rpw) {
+        if constexpr (decltype(rpw)::value <= 4 || decltype(vec)::value <= 4) f(vec, rpw);
+    };
+    auto with_rpw = [&](auto vec) {
+        switch (pp.rpw) {
+            case 2: call(vec, std::integral_constant<int, 2>{}); break;
+            case 3: call(vec, std::integral_constant<int, 3>{}); break;
+            case 4: call(vec, std::integral_constant<int, 4>{}); break;
+            case 6: call(vec, std::integral_constant<int, 6>{}); break;
+            case 8: call(vec, std::integral_constant<int, 8>{}); break;
         }
+    };
+    switch (pp.vec) {
+        case 1: with_rpw(std::integral_constant<int, 1>{}); break;
+        case 2: with_rpw(std::integral_constant<int, 2>{}); break;
+        case 4: with_rpw(std::integral_constant<int, 4>{}); break;
+        case 8: with_rpw(std::integral_constant<int, 8>{}); break;
     }
-    return ok;
 }
 
-
-template <int VEC, int MODE>
-static void launch_band(const Geom &g, const JacobiPlan &pl, const float *pin, float *pout, float *div, float *u, float *v,
-                        int iters, hipStream_t st) {
-    dim3 grid(pl.nb, g.B), block(JB_NW * 64);
+// The multi-launch form: pp.parts launches of k_jacobi_band, each a run of sweeps, ping-pong between p and p2; returns the one that holds
+// the result (p after an even number).  With u and v the divergence is computed inside the first launch and the gradient subtraction
+// inside the last (MODE 1, 2).
+static float *launch_band_runs(const Geom &g, const ProjectionPlan &pp, float *p, float *p2, float *div, float *u, float *v, int iters,
+                             hipStream_t st) {
+    dim3 grid(pp.nb, g.B), block(JB_NW * 64);
     const JacobiSync none{};
-    switch (pl.rpw) {
-        case 2: hipLaunchKernelGGL((k_jacobi_band<VEC, 2, MODE>), grid, block, 0, st, g, pin, pout, div, u, v, iters, pl.br, none); break;
-        case 3: hipLaunchKernelGGL((k_jacobi_band<VEC, 3, MODE>), grid, block, 0, st, g, pin, pout, div, u, v, iters, pl.br, none); break;
-        case 4: hipLaunchKernelGGL((k_jacobi_band<VEC, 4, MODE>), grid, block, 0, st, g, pin, pout, div, u, v, iters, pl.br, none); break;
-        case 6: if constexpr (VEC <= 4) hipLaunchKernelGGL((k_jacobi_band<VEC, 6, MODE>), grid, block, 0, st, g, pin, pout, div, u, v, iters, pl.br, none); break;
-        case 8: if constexpr (VEC <= 4) hipLaunchKernelGGL((k_jacobi_band<VEC, 8, MODE>), grid, block, 0, st, g, pin, pout, div, u, v, iters, pl.br, none); break;
+    float *cur = p, *nxt = p2;
+    int done = 0;
+    for (int c = 0; c < pp.parts; ++c) {
+        const int n = jb_run_sweeps(iters, done, pp.parts, c), mode = !u ? 0 : (c == 0 ? 1 : (c == pp.parts - 1 ? 2 : 0));
+        with_band_shape(pp, [&](auto vec, auto rpw) {
+            constexpr int VEC = decltype(vec)::value, RPW = decltype(rpw)::value;
+            auto go = [&](auto m) {
+                hipLaunchKernelGGL((k_jacobi_band<VEC, RPW, decltype(m)::value>), grid, block, 0, st, g, cur, nxt, div, u, v, n, pp.halo, none);
+            };
+            if (mode == 0) go(std::integral_constant<int, 0>{});
+            else if (mode == 1) go(std::integral_constant<int, 1>{});
+            else go(std::integral_constant<int, 2>{});
+        });
+        done += n;
+        float *t = cur; cur = nxt; nxt = t;
     }
+    return cur;
 }
 
-// the whole projection (FOLD: with the step's buoyancy + diffusion stage as its prologue) as one persistent launch per group of
+// the whole projection (fold: with the step's buoyancy + diffusion stage as its prologue) as one persistent launch per group of
 // co-resident grids
-template <int VEC, bool FOLD>
-static void launch_persist(const Geom &g, const JacobiPlan &pl, float *p, float *u, float *v, int iters, const JacobiSync &sy, hipStream_t st) {
-    dim3 grid(pl.nb * sy.ngrids), block(JB_NW * 64);
-    switch (pl.rpw) {
-        case 2: hipLaunchKernelGGL((k_jacobi_band<VEC, 2, 3, true, FOLD>), grid, block, 0, st, g, p, p, nullptr, u, v, iters, pl.br, sy); break;
-        case 3: hipLaunchKernelGGL((k_jacobi_band<VEC, 3, 3, true, FOLD>), grid, block, 0, st, g, p, p, nullptr, u, v, iters, pl.br, sy); break;
-        case 4: hipLaunchKernelGGL((k_jacobi_band<VEC, 4, 3, true, FOLD>), grid, block, 0, st, g, p, p, nullptr, u, v, iters, pl.br, sy); break;
-        case 6: if constexpr (VEC <= 4) hipLaunchKernelGGL((k_jacobi_band<VEC, 6, 3, true, FOLD>), grid, block, 0, st, g, p, p, nullptr, u, v, iters, pl.br, sy); break;
-        case 8: if constexpr (VEC <= 4) hipLaunchKernelGGL((k_jacobi_band<VEC, 8, 3, true, FOLD>), grid, block, 0, st, g, p, p, nullptr, u, v, iters, pl.br, sy); break;
-    }
-}
-template <bool FOLD>
-static void launch_persist_vec(const Geom &g, const JacobiPlan &pl, float *p, float *u, float *v, int iters, const JacobiSync &sy, hipStream_t st) {
-    switch (pl.vec) {
-        case 1: launch_persist<1, FOLD>(g, pl, p, u, v, iters, sy, st); break;
-        case 2: launch_persist<2, FOLD>(g, pl, p, u, v, iters, sy, st); break;
-        case 4: launch_persist<4, FOLD>(g, pl, p, u, v, iters, sy, st); break;
-        case 8: launch_persist<8, false>(g, pl, p, u, v, iters, sy, st); break;       // (8 cells per lane: the prologue's row windows do not fit)
-    }
-}
-
-// Can this plan run as one persistent launch, and in how many chunks?  Every band must own more rows than the halo (a band's halo rows
-// then lie in its direct neighbour's owned range, and the u / v rows a neighbour's divergence reads are not rewritten before it has
-// published once); chunk sizes are ceil / floor of iters / chunks: the largest <= halo, the last <= halo - 1 (the fused gradient needs
-// the row above the owned range exact); two or more bands need two or more chunks (the first hand-off orders the final stores
-// behind the neighbours' initial loads).
-static bool persist_chunks(const Geom &g, const JacobiPlan &pl, int iters, int &chunks) {
-    const int TR = JB_NW * pl.rpw;
-    if (pl.nb == 1) { chunks = 1; return true; }
-    if (pl.nb > 64 || (size_t)g.B * g.sc * sizeof(float) >= (1ull << 31)) return false;
-    const int e_rows = TR - pl.halo, m_rows = TR - 2 * pl.halo, last = g.H - (e_rows + (pl.nb - 2) * m_rows);
-    int min_owned = e_rows < last ? e_rows : last;
-    if (pl.nb > 2 && m_rows < min_owned) min_owned = m_rows;
-    if (min_owned < pl.halo + 1) return false;
-    chunks = (iters + pl.halo - 1) / pl.halo;
-    if (chunks < 2) chunks = 2;
-    while ((iters + chunks - 1) / chunks > pl.halo || iters / chunks > pl.halo - 1) ++chunks;
-    return chunks <= iters;
-}
-
-template <int MODE>
-static void launch_band_vec(const Geom &g, const JacobiPlan &pl, const float *pin, float *pout, float *div, float *u, float *v,
-                            int iters, hipStream_t st) {
-    switch (pl.vec) {
-        case 1: launch_band<1, MODE>(g, pl, pin, pout, div, u, v, iters, st); break;
-        case 2: launch_band<2, MODE>(g, pl, pin, pout, div, u, v, iters, st); break;
-        case 4: launch_band<4, MODE>(g, pl, pin, pout, div, u, v, iters, st); break;
-        case 8: launch_band<8, MODE>(g, pl, pin, pout, div, u, v, iters, st); break;
-    }
+static void launch_persist(const Geom &g, const ProjectionPlan &pp, bool fold, float *p, float *u, float *v, int iters, const JacobiSync &sy,
+                           hipStream_t st) {
+    dim3 grid(pp.nb * sy.ngrids), block(JB_NW * 64);
+    with_band_shape(pp, [&](auto vec, auto rpw) {
+        constexpr int VEC = decltype(vec)::value, RPW = decltype(rpw)::value;
+        auto go = [&](auto f) {
+            constexpr bool FOLD = decltype(f)::value && VEC <= 4;     // (8 cells per lane: the prologue's row windows do not fit, no plan folds)
+            hipLaunchKernelGGL((k_jacobi_band<VEC, RPW, 3, true, FOLD>), grid, block, 0, st, g, p, p, nullptr, u, v, iters, pp.halo, sy);
+        };
+        if (fold) go(std::true_type{});
+        else go(std::false_type{});
+    });
 }
 
 // `iters` Jacobi sweeps on a given divergence field (result in p; p2 scratch).
 hipError_t launch_jacobi(const Geom &g, float *p, float *p2, const float *div, int iters, hipStream_t st) {
     if (iters <= 0) return hipSuccess;
     dim3 grid(cdiv(g.W, TX), cdiv(g.H, TY), g.B), block(TX, TY);
-    JacobiPlan pl;
+    const ProjectionPlan pp = plan_projection(plan_geom(g), iters, 0, false, false);    // (never persistent: the CU count is not read)
     float *cur = p, *nxt = p2;
-    if (plan_jacobi(g, pl, iters)) {
-        // an even number of nearly equal chunks (global ping-pong ends back in p); each chunk <= halo sweeps
-        int L = 2 * ((iters + 2 * pl.halo - 1) / (2 * pl.halo));
-        if (iters == 1) L = 1;
-        int done = 0;
-        for (int c = 0; c < L; ++c) {
-            const int n = (iters - done + (L - c) - 1) / (L - c);
-            launch_band_vec<0>(g, pl, cur, nxt, const_cast<float *>(div), nullptr, nullptr, n, st);
-            done += n;
-            float *t = cur; cur = nxt; nxt = t;
-        }
+    if (pp.form == ProjectionForm::bands) {
+        cur = launch_band_runs(g, pp, p, p2, const_cast<float *>(div), nullptr, nullptr, iters, st);
     } else {
         for (int it = 0; it < iters; ++it) {
             hipLaunchKernelGGL(k_jacobi_sweep, grid, block, 0, st, g, cur, nxt, div);
@@ -796,8 +703,6 @@ hipError_t launch_jacobi(const Geom &g, float *p, float *p2, const float *div, i
     return hipGetLastError();
 }
 
-// pressure_projection (navier_stokes.py:133-149) on (u, v, p): divergence, `iters` Jacobi sweeps, gradient subtraction.
-// With a band plan the divergence is computed inside the first Jacobi launch and the gradient subtraction inside the last.
 hipError_t project_sync_create(ProjectSync &ps, int B) {
     ps.flags_len = B * 64 + 1;
     // (behind the flags: one cell-form word per (grid, band) of a persistent plan, which has at most 64 bands)
@@ -816,15 +721,16 @@ void project_sync_destroy(ProjectSync &ps) {
     ps.status = nullptr;
 }
 
-// Can the step's buoyancy + diffusion stage run as the persistent launch's prologue (16-byte row accesses: pitches in multiples of 4; up to
-// 4 cells per lane)?  One place for the launchers and for describe_projection.
-static bool prologue_folds(const Geom &g, const JacobiPlan &pl) { return pl.vec <= 4 && g.pv % 4 == 0 && g.pc % 4 == 0; }
+// What of the run-time state the persistent form needs: a handle with hand-off flags that has seen no time-out, and the switch.
+static bool handle_allows_persist(const ProjectSync *ps) { return ps && ps->flags && !ps->disabled && knobs().persist; }
 
-static bool use_persist(const Geom &g, const ProjectSync *ps, int iters, JacobiPlan &pl, int &chunks) {
-    if (!ps || !ps->flags || ps->disabled || !knobs().persist || iters < 2) return false;
-    if (!plan_jacobi(g, pl, iters, true) || pl.halo < 3) return false;
-    if (pl.nb > device_num_cu()) return false;
-    return persist_chunks(g, pl, iters, chunks);
+// The plan of a projection enqueued on `st` now.  A captured launch would replay with the hand-off count of capture time: under stream
+// capture the multi-launch form is recorded.  So it is while a time-out of an earlier launch waits to be reported.
+static ProjectionPlan plan_call(const Geom &g, int iters, hipStream_t st, const ProjectSync *ps) {
+    hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
+    const bool capturing = hipStreamIsCapturing(st, &cap_status) == hipSuccess && cap_status != hipStreamCaptureStatusNone;
+    const bool pending_error = ps && ps->status && *ps->status != 0u;
+    return plan_projection(plan_geom(g), iters, device_num_cu(), handle_allows_persist(ps) && !capturing && !pending_error, true);
 }
 
 // Two persistent projections cannot share the device: each needs all of its workgroups resident at once, and two half-resident grids
@@ -862,152 +768,69 @@ bool project_sync_take_timeout(ProjectSync &ps) {
     return true;
 }
 
-hipError_t launch_project(const Geom &g, float *u, float *v, float *p, float *p2, float *div, int iters, hipStream_t st, ProjectSync *ps,
-                          const StateView *fold_in, float *fold_d_out, bool *folded) {
-    JacobiPlan pl;
-    if (folded) *folded = false;
-    if (ps && project_sync_take_timeout(*ps)) {
-        // a wait inside an earlier persistent launch timed out (its workgroups were not co-resident within the limit): that projection's
-        // result is invalid (NaN).  Say so once, loudly, and use the multi-launch form from here on.
-        return hipErrorLaunchTimeOut;
-    }
-    int chunks = 0;
-    // (a captured launch would replay with the hand-off count of capture time: under stream capture the multi-launch form is recorded)
-    hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
-    const bool capturing = hipStreamIsCapturing(st, &cap_status) == hipSuccess && cap_status != hipStreamCaptureStatusNone;
-    if (!capturing && use_persist(g, ps, iters, pl, chunks)) {
-        int per = device_num_cu() / pl.nb;                    // grids whose bands are all co-resident (one 1024-thread workgroup per CU)
-        if (per >= 8) per &= ~7;
+// The projection as the plan says.  fold_in / fold_d_out (persistent plans that fold only): the step's buoyancy + diffusion stage
+// (fold_in -> u, v, fold_d_out) runs as the launch's prologue; otherwise u, v hold the diffused fields.
+static hipError_t run_projection(const Geom &g, const ProjectionPlan &pp, float *u, float *v, float *p, float *p2, float *div, int iters,
+                                 hipStream_t st, ProjectSync *ps, const StateView *fold_in = nullptr, float *fold_d_out = nullptr) {
+    if (pp.form == ProjectionForm::persistent) {
         JacobiSync sy{};
         sy.flags = ps->flags; sy.status = const_cast<unsigned *>(ps->status); sy.x0 = div; sy.x1 = p2;
-        sy.base = ps->seq; sy.chunks = chunks; sy.nb = pl.nb; sy.abort_slot = ps->flags_len - 1; sy.fault = knobs().fault ? 1 : 0;
+        sy.base = ps->seq; sy.chunks = pp.parts; sy.nb = pp.nb; sy.abort_slot = ps->flags_len - 1; sy.fault = knobs().fault ? 1 : 0;
         sy.timeout_ticks = knobs().fault ? 200000ll : 50000000ll;      // 100 MHz wall clock: 2 ms under fault injection, 0.5 s otherwise
-        ps->forms_nb = pl.nb;
-        ps->seq += (unsigned)chunks;
+        ps->forms_nb = pp.nb;
+        ps->seq += (unsigned)pp.parts;
         const std::unique_lock<std::mutex> launch_order = order_persistent_launch(st);
-        // the buoyancy + diffusion stage as this launch's prologue (16-byte row accesses: pitches in multiples of 4; up to 4 cells per lane)
-        const bool fold = fold_in && fold_d_out && prologue_folds(g, pl);
-        if (fold) {
-            sy.u_in = fold_in->u; sy.v_in = fold_in->v; sy.d_in = fold_in->d; sy.d_out = fold_d_out;
-            if (folded) *folded = true;
-        }
-        ps->forms_two = jb_two_forms(pl.vec, pl.rpw, true, fold);      // (otherwise no workgroup writes its word: all exact)
-        for (int g0 = 0; g0 < g.B; g0 += per) {
+        const bool fold = fold_in != nullptr;
+        if (fold) { sy.u_in = fold_in->u; sy.v_in = fold_in->v; sy.d_in = fold_in->d; sy.d_out = fold_d_out; }
+        ps->forms_two = fold && pp.two_forms;                 // (otherwise no workgroup writes its word: all exact)
+        for (int g0 = 0; g0 < g.B; g0 += pp.grids_per_launch) {
             sy.grid0 = g0;
-            sy.ngrids = g.B - g0 < per ? g.B - g0 : per;
-            if (fold) launch_persist_vec<true>(g, pl, p, u, v, iters, sy, st);
-            else launch_persist_vec<false>(g, pl, p, u, v, iters, sy, st);
+            sy.ngrids = g.B - g0 < pp.grids_per_launch ? g.B - g0 : pp.grids_per_launch;
+            launch_persist(g, pp, fold, p, u, v, iters, sy, st);
         }
         return hipGetLastError();
     }
-    if (iters < 2 || !plan_jacobi(g, pl, iters) || pl.halo < 3) {
-        if (ps) { ps->forms_nb = 0; ps->forms_two = false; }  // (no band kernel in this form)
+    // (forms_nb 0: no band kernel in this form; the multi-launch forms have the exact cell only: jb_two_forms)
+    if (ps) { ps->forms_nb = pp.nb; ps->forms_two = false; }
+    if (pp.form == ProjectionForm::sweeps) {
         hipError_t e = launch_divergence(g, u, v, div, g.pc, g.sc, st);
         if (e != hipSuccess) return e;
         e = launch_jacobi(g, p, p2, div, iters, st);
         if (e != hipSuccess) return e;
         return launch_grad_subtract(g, u, v, p, st);
     }
-    const int cap = pl.halo - 1;                              // the fused gradient needs the row above the owned range exact
-    const int L = 2 * ((iters + 2 * cap - 1) / (2 * cap));
-    float *cur = p, *nxt = p2;
-    int done = 0;
-    if (ps) { ps->forms_nb = pl.nb; ps->forms_two = false; }  // (the multi-launch forms have the exact cell only: jb_two_forms)
-    for (int c = 0; c < L; ++c) {
-        const int n = (iters - done + (L - c) - 1) / (L - c);
-        if (c == 0) launch_band_vec<1>(g, pl, cur, nxt, div, u, v, n, st);
-        else if (c == L - 1) launch_band_vec<2>(g, pl, cur, nxt, div, u, v, n, st);
-        else launch_band_vec<0>(g, pl, cur, nxt, div, u, v, n, st);
-        done += n;
-        float *t = cur; cur = nxt; nxt = t;
-    }
-    return hipGetLastError();                                 // L is even: the result is back in p
+    launch_band_runs(g, pp, p, p2, div, u, v, iters, st);
+    return hipGetLastError();                                 // (an even number of launches: the result is back in p)
+}
+
+// pressure_projection (navier_stokes.py:133-149) on (u, v, p): divergence, `iters` Jacobi sweeps, gradient subtraction.
+// With a band plan the divergence is computed inside the first Jacobi launch and the gradient subtraction inside the last.
+hipError_t launch_project(const Geom &g, float *u, float *v, float *p, float *p2, float *div, int iters, hipStream_t st, ProjectSync *ps) {
+    // a wait inside an earlier persistent launch timed out (its workgroups were not co-resident within the limit): that projection's
+    // result is invalid (NaN).  Say so once, loudly, and use the multi-launch form from here on.
+    if (ps && project_sync_take_timeout(*ps)) return hipErrorLaunchTimeOut;
+    return run_projection(g, plan_call(g, iters, st, ps), u, v, p, p2, div, iters, st, ps);
 }
 
 // Stages 1-3 of a time step (navier_stokes.py:154-163): buoyancy + diffusion (in -> out.u, out.v, out.d) and the projection of
 // (out.u, out.v) with the pressure p.  One persistent launch where the plan allows, otherwise the two stages as before.
 hipError_t launch_buoy_project(const Geom &g, StateView in, StateView out, float *p, float *div, int iters, hipStream_t st, ProjectSync *ps) {
-    bool folded = false;
-    JacobiPlan pl;
-    int chunks = 0;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    const bool capturing = hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-    const bool pending_error = ps && ps->status && *ps->status != 0u;
-    if (!capturing && !pending_error && use_persist(g, ps, iters, pl, chunks) && prologue_folds(g, pl)) {
-        const hipError_t e = launch_project(g, out.u, out.v, p, out.p, div, iters, st, ps, &in, out.d, &folded);
-        if (e != hipSuccess || folded) return e;
-        return hipErrorUnknown;                               // (unreachable: the conditions above are launch_project's own)
+    const ProjectionPlan pp = plan_call(g, iters, st, ps);
+    const bool fold = pp.form == ProjectionForm::persistent && pp.folds;
+    if (!fold) {
+        const hipError_t e = launch_buoy_diffuse(g, in, out, st);
+        if (e != hipSuccess) return e;
     }
-    hipError_t e = launch_buoy_diffuse(g, in, out, st);
-    if (e != hipSuccess) return e;
-    return launch_project(g, out.u, out.v, p, out.p, div, iters, st, ps);
+    if (ps && project_sync_take_timeout(*ps)) return hipErrorLaunchTimeOut;       // (as launch_project reports it)
+    return run_projection(g, pp, out.u, out.v, p, out.p, div, iters, st, ps, fold ? &in : nullptr, out.d);
 }
 
-// The persistent launch with the folded prologue keeps a band's diffused u / v rows in LDS (k_jacobi_band, KEEP): slots per band, the
-// rows of one grid that get a slot, and the most rows any band leaves on the HBM path -- by the kernel's own numbering and slot function.
-struct KeepStats { int slots, kept_per_grid, max_overflow; };
-static KeepStats keep_stats(const Geom &g, const JacobiPlan &pl) {
-    KeepStats ks{jb_keep_rows(pl.vec, pl.rpw), 0, 0};
-    const int TR = JB_NW * pl.rpw, e_rows = TR - pl.halo, m_rows = TR - 2 * pl.halo;
-    for (int band = 0; band < pl.nb; ++band) {
-        const int own0 = band == 0 ? 0 : e_rows + (band - 1) * m_rows;
-        int own1 = band == pl.nb - 1 ? g.H : e_rows + band * m_rows;
-        own1 = own1 < g.H ? own1 : g.H;
-        const int n = (own1 - (own0 > 1 ? own0 : 1)) + (own1 - own0), scale = jb_keep_scale(n, ks.slots);
-        int kept = 0;
-        for (int idx = 0; idx < n; ++idx) kept += jb_keep_slot(idx, scale) >= 0;
-        ks.kept_per_grid += kept;
-        if (n - kept > ks.max_overflow) ks.max_overflow = n - kept;
-    }
-    return ks;
-}
-
-// What one projection launches for this geometry, as a JSON object (bench.py reports it as the stencil pass's on-chip bound: the
-// Jacobi sweeps never touch HBM, so what limits them is sweeps x rows per workgroup x vector-issue time, not bytes).
+// What one projection launches for this geometry, as a JSON object (describe_plan).
 std::string describe_projection(const Geom &g, int iters, const ProjectSync *ps) {
-    JacobiPlan pl;
-    char buf[2048];
-    int chunks = 0;
-    const bool persist = use_persist(g, ps, iters, pl, chunks);
-    if (!persist && (iters < 2 || !plan_jacobi(g, pl, iters) || pl.halo < 3)) {
-        snprintf(buf, sizeof buf, "{\"kernel\": \"k_jacobi_sweep\", \"launches\": %d, \"sweeps\": %d, \"bound\": \"hbm (one pass over p and div per sweep)\"}",
-                 iters + 2, iters);
-        return buf;
-    }
-    const int cap = pl.halo - 1, TR = JB_NW * pl.rpw;
-    const int per = persist ? (device_num_cu() / pl.nb >= 8 ? (device_num_cu() / pl.nb) & ~7 : device_num_cu() / pl.nb) : 0;
-    const int L = persist ? (g.B + per - 1) / per : 2 * ((iters + 2 * cap - 1) / (2 * cap));
-    const int parts = persist ? chunks : L;                   // runs of sweeps between two refreshes of the halo rows
-    const double wgs = (double)pl.nb * g.B, rounds = ceil(wgs / device_num_cu());
-    const bool step_folds = persist && prologue_folds(g, pl);
-    const bool two_forms = jb_two_forms(pl.vec, pl.rpw, persist, step_folds);   // (of the kernel a whole step launches)
-    // measured (tools/probes/valu_probe, 4 waves per SIMD): a sweep row of 64 VEC-cell lanes = ~18 vector instructions of which 2 are DPP
-    // wave shifts, ~2.6 cycles per instruction and SIMD -> TR rows on 4 SIMDs.  The edge-row exchange (publish -> s_barrier -> read) is
-    // software-pipelined under those rows; what the in-kernel stamps show beyond the estimate is the four waves of a SIMD taking turns at its
-    // vector issue, the youngest last, with the others waiting for it at the sweep's barrier (profiles/r07)
-    // (with both cell forms a row is one instruction per cell shorter on the fused cell, which all but a trajectory's first steps take)
-    const double valu_us_per_sweep = rounds * (TR / 4.0) * (18.0 - (two_forms ? pl.vec : 0)) * 2.6 / 2100.0;
-    // (the keep buffer belongs to the form launch_buoy_project folds the step's first stage into: the conditions are its own)
-    const KeepStats ks = step_folds ? keep_stats(g, pl) : KeepStats{0, 0, 0};
-    snprintf(buf, sizeof buf,
-             "{\"kernel\": \"k_jacobi_band<%d,%d>\", \"persistent\": %s, \"bands_per_grid\": %d, \"rows_per_workgroup\": %d, \"halo_rows\": %d, "
-             "\"workgroups\": %d, \"launches\": %d, \"halo_handoffs\": %d, \"sweeps\": %d, \"sweeps_per_chunk\": %d, \"redundant_row_factor\": %.3f, "
-             "\"keep_rows_per_band\": %d, \"keep_overflow_rows_max\": %d, \"keep_rows_per_grid\": %d, \"cell_forms_of_a_step\": %d, "
-             "\"vector_issue_us_per_sweep_estimate\": %.3f, \"vector_issue_us_total_estimate\": %.1f, "
-             "\"bound\": \"on-chip: sweeps x vector issue of rows_per_workgroup rows, one barrier per sweep (%s); p and div are "
-             "register-resident %s\"}",
-             pl.vec, pl.rpw, persist ? "true" : "false", pl.nb, TR, pl.halo, (int)wgs, L, persist ? chunks - 1 : 0, iters, (iters + parts - 1) / parts,
-             (double)pl.nb * TR / g.H, ks.slots, ks.max_overflow, ks.kept_per_grid,
-             two_forms ? 2 : 1, valu_us_per_sweep, valu_us_per_sweep * iters,
-             jb_pipelined(pl.vec, pl.rpw, persist)
-                 ? "the LDS edge-row exchange is pipelined over two sweeps: a wave's two edge rows and their publish come first, the interior rows "
-                   "cover the stores and the read of the next sweep's neighbour rows"
-                 : "plain order at the register cap: publish, interior rows, barrier, read of the neighbour rows, the two edge rows",
-             persist ? "for the whole projection; bands hand halo rows to their neighbours through HBM between chunks" : "within a launch");
-    return buf;
+    const PlanGeom pg = plan_geom(g);
+    return describe_plan(plan_projection(pg, iters, device_num_cu(), handle_allows_persist(ps), true), iters, pg, device_num_cu());
 }
 
-// u[1:-1,:] -= dt*(p[1:]-p[:-1]);  v[:,1:-1] -= dt*(p[:,1:]-p[:,:-1])   (:148-149)
 __global__ void k_grad_subtract(Geom g, float *u, float *v, const float *p) {
     int b = blockIdx.z;
     int j = blockIdx.x * TX + threadIdx.x, i = blockIdx.y * TY + threadIdx.y;
