@@ -262,6 +262,33 @@ int64_t smk_volume_stats_workspace(int32_t n, int32_t D, int32_t H, int32_t W);
 int smk_volume_stats(const float *vols, int64_t vol_stride, int32_t n, int32_t D, int32_t H, int32_t W, float *means,
                      int32_t *box_counts, int32_t *hist, float *norms, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* Front-view render of n volumes rho [D][H][W] (dense, `vol_stride` floats apart, 64-bit) to images [H][W]: SPEC_3D.md section 10.  No
+ * reference counterpart (the reference is 2-D).  The camera looks along +z, plane z = 0 is nearest; single scattering from one
+ * directional light:
+ *   tau[z,y,x] = sum_{z' < z} rho[z',y,x]
+ *   A[z,y,x]   = exclusive prefix of rho along the light's direction of travel:
+ *                SMK_LIGHT_POS_Y sum_{y' < y} rho[z,y',x], SMK_LIGHT_NEG_Y sum_{y' > y} rho[z,y',x], SMK_LIGHT_POS_Z tau, SMK_LIGHT_NONE 0
+ *   image[y,x]         = gain * sum_z -expm1(-sigma_view rho) * (ambient + (1 - ambient) exp(-sigma_light A)) * exp(-sigma_view tau)
+ *   transmittance[y,x] = exp(-sigma_view * sum_z rho[z,y,x])                                   (not written when NULL)
+ * z ascending; fp32, every sum in one fixed order, no atomics: results are bit-identical from call to call and the result of a volume
+ * does not depend on the others of the batch.  Negative densities follow the formula (no clamp).  The settings are doubles, cast once
+ * (1 - ambient is formed in double).  image / transmittance planes are `image_stride` / `trans_stride` floats apart (>= H*W).
+ * Limits: 1 <= D <= 64, any H, W >= 1, D*H*W <= 2^31 - 2^16; anything else returns SMK_ERR_UNSUPPORTED.  sigma_view, sigma_light >= 0,
+ * 0 <= ambient <= 1, gain > 0 (else SMK_ERR_INVALID).  workspace: device memory of at least smk_volume_render_workspace(n, D, H, W, light)
+ * bytes (0 for SMK_LIGHT_NONE / SMK_LIGHT_POS_Z and for H <= 16: NULL is accepted then; -1 for an unsupported shape or light), 4-byte
+ * aligned, passed with its size.  Caller-owned memory, the caller's stream, nothing allocated, no synchronisation; SMK_LIGHT_NONE /
+ * SMK_LIGHT_POS_Z read the volumes once (one launch), SMK_LIGHT_POS_Y / SMK_LIGHT_NEG_Y twice (three launches). */
+typedef enum smk_light { SMK_LIGHT_NONE = 0, SMK_LIGHT_POS_Y = 1, SMK_LIGHT_NEG_Y = 2, SMK_LIGHT_POS_Z = 3 } smk_light;
+typedef struct smk_render_desc {
+    double sigma_view, sigma_light;   /* extinction per unit density along the view ray / the light ray */
+    double ambient, gain;             /* unshadowed share of the light; scale of the image */
+    int32_t light;                    /* smk_light */
+} smk_render_desc;
+int64_t smk_volume_render_workspace(int32_t n, int32_t D, int32_t H, int32_t W, int32_t light);
+int smk_volume_render(const float *vols, int64_t vol_stride, int32_t n, int32_t D, int32_t H, int32_t W, const smk_render_desc *desc,
+                      float *image, int64_t image_stride, float *transmittance, int64_t trans_stride, void *workspace,
+                      int64_t workspace_bytes, void *stream);
+
 /* RobustnessEvaluator.compute_ssim's SSIM map and F.mse_loss's squared error (robustness_metrics.py:76-103) for n fp32 planes [H][W]
  * (dense rows; plane strides pred_stride / target_stride floats), summed per plane in fp64 in a fixed order (bit-reproducible):
  * ssim_sum [n], sqerr_sum [n].  avg_pool2d(window, stride 1, padding window/2, count_include_pad) with zeros outside the plane;

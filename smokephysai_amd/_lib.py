@@ -12,6 +12,7 @@ SMK_OK, SMK_ERR_INVALID, SMK_ERR_HIP, SMK_ERR_UNSUPPORTED, SMK_ERR_NO_DEVICE, SM
 SMK_F32, SMK_BF16X3, SMK_BF16, SMK_I8X3 = 0, 1, 2, 3
 SMK_ACT_NONE, SMK_ACT_GELU, SMK_ACT_RELU = 0, 1, 2
 SMK_FMT_F32, SMK_FMT_SPLIT_BF16, SMK_FMT_SPLIT4_INPLACE = 0, 1, 2
+SMK_LIGHT_NONE, SMK_LIGHT_POS_Y, SMK_LIGHT_NEG_Y, SMK_LIGHT_POS_Z = 0, 1, 2, 3      # smk_light
 STAGE_BUOY_DIFFUSE, STAGE_PROJECT, STAGE_ADVECT_U, STAGE_ADVECT_V, STAGE_ADVECT_D = range(5)
 DTYPES = {"f32": SMK_F32, "fp32": SMK_F32, "float32": SMK_F32, "bf16x3": SMK_BF16X3, "bf16": SMK_BF16, "i8x3": SMK_I8X3}
 
@@ -50,6 +51,12 @@ class SmkDecoderWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in
                 ("ct1_w", "ct1_b", "bn1_w", "bn1_b", "bn1_mean", "bn1_var",
                  "ct2_w", "ct2_b", "bn2_w", "bn2_b", "bn2_mean", "bn2_var", "conv_w", "conv_b")]
+
+
+class SmkRenderDesc(C.Structure):
+    """smk_render_desc (include/smokehip.h): the settings of smk_volume_render; light is one of SMK_LIGHT_*."""
+    _fields_ = [("sigma_view", C.c_double), ("sigma_light", C.c_double), ("ambient", C.c_double), ("gain", C.c_double),
+                ("light", C.c_int32)]
 
 
 class SmkOptTensor(C.Structure):
@@ -97,6 +104,8 @@ _SIGNATURES = {
     "smk_frame_diff_norms": [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p],
     "smk_volume_stats": [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                          C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    "smk_volume_render": [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SmkRenderDesc), C.c_void_p, C.c_int64,
+                          C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p],
     "smk_chaos_features": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                            C.c_void_p, C.c_void_p],
     "smk_image_quality": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
@@ -182,7 +191,7 @@ _SIGNATURES = {
 EXPORTS = ["smk_abi_version", "smk_last_error", "smk_linear_wgrad_workspace", "smk_bn_train_workspace", "smk_layernorm_bwd_workspace", "smk_conv2_train_workspace", "smk_conv2_train_wgrad_workspace", "smk_conv1_train_wgrad_workspace", "smk_attention_workspace_bytes", "smk_linear_ln_max_rows", "smk_image_quality_workspace", "smk_convt4s2_train_wgrad_workspace",
            "smk_volume_stats_workspace", "smk_grad_norm_workspace", "smk_train_loss_workspace",
            "smk_conv3_sigmoid_train_workspace", "smk_flow_levels", "smk_flow_farneback_workspace", "smk_warp_workspace",
-           "smk_flow_lk_workspace"] + list(_SIGNATURES)
+           "smk_flow_lk_workspace", "smk_volume_render_workspace"] + list(_SIGNATURES)
 
 _lib = None
 
@@ -234,6 +243,8 @@ def load():
         L.smk_image_quality_workspace.restype = C.c_int64
         L.smk_volume_stats_workspace.argtypes = [C.c_int32] * 4
         L.smk_volume_stats_workspace.restype = C.c_int64
+        L.smk_volume_render_workspace.argtypes = [C.c_int32] * 5
+        L.smk_volume_render_workspace.restype = C.c_int64        # a byte count; -1 = unsupported shape or light
         L.smk_convt4s2_train_wgrad_workspace.argtypes = [C.c_int32] * 5
         L.smk_convt4s2_train_wgrad_workspace.restype = C.c_int64
         L.smk_conv3_sigmoid_train_workspace.argtypes = [C.c_int32] * 3

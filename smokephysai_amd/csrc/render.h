@@ -1,0 +1,19 @@
+#pragma once
+#include "common.h"
+
+namespace smk {
+
+constexpr int RENDER_MAX_DEPTH = 64;      // planes one lane keeps a running light sum for (registers)
+constexpr int RENDER_SEG_ROWS = 16;       // rows per segment of the +-y light prefix (render.py: SEGMENT_ROWS)
+
+// the settings of smk_render_desc, cast once on the host
+struct RenderParams {
+    float neg_sigma_view, neg_sigma_light, ambient, one_minus_ambient, gain;
+};
+
+// bytes of the segment-total workspace: 0 unless the light travels along y and the rows span more than one segment
+int64_t render_workspace(int64_t n, int D, int H, int W, int light);
+hipError_t launch_volume_render(const float *vols, int64_t stride, int64_t n, int D, int H, int W, int light, const RenderParams &p,
+                                float *image, int64_t image_stride, float *trans, int64_t trans_stride, float *workspace, hipStream_t st);
+
+}  // namespace smk

@@ -1,0 +1,285 @@
+// Front-view single-scattering render of n volumes [D][H][W] to images [H][W] (SPEC_3D.md section 10; smk_volume_render).
+//   tau[z]  = sum_{z' < z} rho[z']                       exclusive prefix toward the camera (plane 0 is nearest)
+//   A[z,y]  = exclusive prefix of rho along the light's direction of travel (+y, -y, +z = tau, none = 0)
+//   image   = gain * sum_z  -expm1(-sv rho) * (a + (1 - a) exp(-sl A)) * exp(-sv tau),   z ascending
+//   trans   = exp(-sv * sum_z rho)
+// fp32, one fixed order per sum, no atomics: bit-reproducible, and a volume's result does not depend on its neighbours in the batch.
+//
+// Light "none" and "+z" couple nothing across pixels: k_render_view, one pixel per lane (lanes along x), z marched in a loop, the
+// volumes read once.
+// Light "+y" / "-y": the prefix along y serialises a column.  One lane owns one column x and keeps the running sum of every plane in
+// registers (D <= 64 floats); a wave owns 64 consecutive columns and RENDER_SEG_ROWS rows, so every load is 256 contiguous bytes.  The rows
+// are cut into segments so that a volume gives (W / 64) * (H / 16) waves instead of W / 64:
+//   k_render_seg_totals : per (segment, z, x) the sum of the segment's rows, in the light's order of travel      (read 1 of the volumes)
+//   k_render_seg_scan   : exclusive scan of those totals over the segments, in place, in the order of travel     (workspace only)
+//   k_render_lit<DMAX>  : starts every plane's sum from its scanned total and marches the segment's rows         (read 2 of the volumes)
+// The workspace is [n][segments][D][W] floats = 1 / RENDER_SEG_ROWS of the volumes.  H <= RENDER_SEG_ROWS needs none (one segment).
+#include "render.h"
+
+namespace smk {
+
+namespace {
+
+constexpr int RV_NT = 256;                 // threads per workgroup of the three flat kernels
+constexpr int SEG = RENDER_SEG_ROWS;
+
+enum { LIGHT_NONE = 0, LIGHT_POS_Y = 1, LIGHT_NEG_Y = 2, LIGHT_POS_Z = 3 };
+
+// Smoke volumes are mostly empty (the stepper's are 99.9 % zeros after 20 steps).  A voxel with rho == 0 adds (0 * L) * T = 0 exactly as
+// long as L and T are finite, which A >= 0 and tau >= 0 guarantee (both factors are then in [0, 1]); with negative or NaN sums behind it the
+// term is formed as written.  A wave whose 64 voxels are all of that kind skips the term: same bits, no exp.
+__device__ __forceinline__ bool wave_has_term(float rho, float A, float tau) {
+    return __builtin_amdgcn_ballot_w64(!(rho == 0.f && A >= 0.f && tau >= 0.f)) != 0;
+}
+
+// one term of the image sum
+__device__ __forceinline__ float render_term(float rho, float A, float tau, const RenderParams &p, bool lit) {
+    const float alpha = -expm1f(p.neg_sigma_view * rho);
+    const float L = lit ? p.ambient + p.one_minus_ambient * __expf(p.neg_sigma_light * A) : 1.0f;
+    return (alpha * L) * __expf(p.neg_sigma_view * tau);
+}
+
+// ---- light none / +z: one pixel per lane, nothing shared
+template <bool LIT_Z>
+__global__ __launch_bounds__(RV_NT) void k_render_view(const float *__restrict__ vols, int64_t stride, int D, int HW, int bpv, RenderParams p,
+                                                       float *__restrict__ image, int64_t istride, float *__restrict__ trans,
+                                                       int64_t tstride) {
+    const int v = blockIdx.x / bpv, pix = (blockIdx.x % bpv) * RV_NT + threadIdx.x;
+    const bool ok = pix < HW;                                   // lanes past the plane read its last pixel and store nothing
+    const float *f = vols + (size_t)v * stride + (ok ? pix : HW - 1);
+    float tau = 0.f, img = 0.f;
+    constexpr int U = 8;                                        // planes loaded ahead of their terms
+    for (int z0 = 0; z0 < D; z0 += U) {
+        float r[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) r[j] = z0 + j < D ? f[(size_t)(z0 + j) * HW] : 0.f;      // z * HW + pix < D * H * W
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            if (z0 + j < D) {                                   // wave-uniform
+                if (wave_has_term(r[j], tau, tau)) img += render_term(r[j], tau, tau, p, LIT_Z);
+                tau += r[j];
+            }
+        }
+    }
+    if (!ok) return;
+    image[(size_t)v * istride + pix] = p.gain * img;
+    if (trans != nullptr) trans[(size_t)v * tstride + pix] = __expf(p.neg_sigma_view * tau);
+}
+
+// rows [y0, y1) of segment s, and row i of it in the light's order of travel
+__device__ __forceinline__ int seg_row(int s, int i, int H, int up, int *rows) {
+    const int y0 = s * SEG, y1 = y0 + SEG < H ? y0 + SEG : H;
+    *rows = y1 - y0;
+    return up ? y0 + i : y1 - 1 - i;
+}
+
+// ---- light +-y, pass 1: ws[v][s][z][x] = sum of rho[z][y][x] over the rows of segment s, in the order of travel
+__global__ __launch_bounds__(RV_NT) void k_render_seg_totals(const float *__restrict__ vols, int64_t stride, int D, int H, int W, int nseg,
+                                                             int bpp, int up, float *__restrict__ ws) {
+    unsigned id = blockIdx.x;
+    const int q = (id % bpp) * RV_NT + threadIdx.x; id /= bpp;
+    const int s = id % nseg, v = id / nseg;
+    const int DW = D * W;
+    if (q >= DW) return;
+    const int z = q / W, x = q - z * W;
+    const float *f = vols + (size_t)v * stride + (size_t)z * H * W + x;
+    int rows;
+    (void)seg_row(s, 0, H, up, &rows);
+    float r[SEG];
+#pragma unroll
+    for (int i = 0; i < SEG; ++i) {
+        int dummy;
+        r[i] = i < rows ? f[(size_t)seg_row(s, i, H, up, &dummy) * W] : 0.f;
+    }
+    float t = 0.f;
+#pragma unroll
+    for (int i = 0; i < SEG; ++i)
+        if (i < rows) t += r[i];
+    ws[((size_t)v * nseg + s) * DW + q] = t;
+}
+
+// ---- pass 2: exclusive scan over the segments, in place, in the order of travel
+__global__ __launch_bounds__(RV_NT) void k_render_seg_scan(int DW, int nseg, int bpp, int up, float *__restrict__ ws) {
+    const int v = blockIdx.x / bpp, q = (blockIdx.x % bpp) * RV_NT + threadIdx.x;
+    if (q >= DW) return;
+    float *w = ws + (size_t)v * nseg * DW + q;
+    float run = 0.f;
+    constexpr int U = 8;                                       // loads in flight (the stores alias them: read a group first)
+    for (int k0 = 0; k0 < nseg; k0 += U) {
+        float t[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            const int k = k0 + j, s = up ? k : nseg - 1 - k;
+            t[j] = k < nseg ? w[(size_t)s * DW] : 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            const int k = k0 + j, s = up ? k : nseg - 1 - k;
+            if (k < nseg) {
+                w[(size_t)s * DW] = run;
+                run += t[j];
+            }
+        }
+    }
+}
+
+// ---- pass 3: one wave = 64 columns x one segment; A[z] lives in registers (the z loops are unrolled: static indices)
+template <int DMAX>
+__global__ __launch_bounds__(64, 2) void k_render_lit(const float *__restrict__ vols, int64_t stride, int D, int H, int W, int nseg, int nxc,
+                                                   int up, RenderParams p, const float *__restrict__ ws, float *__restrict__ image,
+                                                   int64_t istride, float *__restrict__ trans, int64_t tstride) {
+    unsigned id = blockIdx.x;
+    const int xc = id % nxc; id /= nxc;
+    const int s = id % nseg, v = id / nseg;
+    const int x = xc * 64 + threadIdx.x;
+    const bool ok = x < W;
+    // Every load is a wave-uniform 64-bit row address plus this lane's byte offset (at most 252): one register per lane serves all planes.
+    // Lanes past the row load its last column and store nothing.
+    const unsigned lane_b = 4u * (unsigned)(ok ? (int)threadIdx.x : W - 1 - xc * 64);
+    const char *f = reinterpret_cast<const char *>(vols + (size_t)v * stride + xc * 64);
+    float A[DMAX];
+    const char *wrow = reinterpret_cast<const char *>(ws + ((size_t)v * nseg + s) * D * W + xc * 64);
+#pragma unroll
+    for (int z = 0; z < DMAX; ++z)
+        A[z] = (ws != nullptr && z < D) ? *reinterpret_cast<const float *>(wrow + (size_t)z * W * 4 + lane_b) : 0.f;
+    int rows;
+    (void)seg_row(s, 0, H, up, &rows);
+    for (int i = 0; i < rows; ++i) {
+        int dummy;
+        const int y = seg_row(s, i, H, up, &dummy);
+        int Dr = D;
+        asm volatile("" : "+s"(Dr));                           // D again, opaque per row: 64 scalar compares, not 64 saved lane masks
+        const char *row = f + (size_t)y * W * 4;               // (z * H + y) * W + x < D * H * W
+        float tau = 0.f, img = 0.f;
+        constexpr int RC = DMAX < 16 ? DMAX : 16;              // planes loaded ahead of their terms
+#pragma unroll
+        for (int z0 = 0; z0 < DMAX; z0 += RC) {
+            float r[RC];
+#pragma unroll
+            for (int j = 0; j < RC; ++j) {                     // planes past D load plane D - 1 again (never used)
+                r[j] = *reinterpret_cast<const float *>(row + lane_b);
+                row += z0 + j + 1 < Dr ? (size_t)H * W * 4 : 0;
+            }
+#pragma unroll
+            for (int j = 0; j < RC; ++j) {
+                if (z0 + j < Dr) {                             // wave-uniform
+                    if (wave_has_term(r[j], A[z0 + j], tau)) img += render_term(r[j], A[z0 + j], tau, p, true);
+                    tau += r[j];
+                    A[z0 + j] += r[j];
+                }
+            }
+        }
+        if (ok) {
+            image[(size_t)v * istride + (size_t)y * W + x] = p.gain * img;
+            if (trans != nullptr) trans[(size_t)v * tstride + (size_t)y * W + x] = __expf(p.neg_sigma_view * tau);
+        }
+    }
+}
+
+inline int render_segments(int H) { return (H + SEG - 1) / SEG; }
+
+}  // namespace
+
+int64_t render_workspace(int64_t n, int D, int H, int W, int light) {
+    if (light != LIGHT_POS_Y && light != LIGHT_NEG_Y) return 0;
+    const int nseg = render_segments(H);
+    if (nseg <= 1) return 0;
+    return n * nseg * (int64_t)D * W * (int64_t)sizeof(float);
+}
+
+hipError_t launch_volume_render(const float *vols, int64_t stride, int64_t n, int D, int H, int W, int light, const RenderParams &p,
+                                float *image, int64_t image_stride, float *trans, int64_t trans_stride, float *workspace, hipStream_t st) {
+    const int64_t HW = (int64_t)H * W, DW = (int64_t)D * W;
+    if (light == LIGHT_NONE || light == LIGHT_POS_Z) {
+        const int64_t bpv = (HW + RV_NT - 1) / RV_NT, grid = n * bpv;
+        if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
+        if (light == LIGHT_POS_Z)
+            hipLaunchKernelGGL(k_render_view<true>, dim3((unsigned)grid), dim3(RV_NT), 0, st, vols, stride, D, (int)HW, (int)bpv, p, image,
+                               image_stride, trans, trans_stride);
+        else
+            hipLaunchKernelGGL(k_render_view<false>, dim3((unsigned)grid), dim3(RV_NT), 0, st, vols, stride, D, (int)HW, (int)bpv, p, image,
+                               image_stride, trans, trans_stride);
+        return hipGetLastError();
+    }
+    const int up = light == LIGHT_POS_Y;
+    const int nseg = render_segments(H), nxc = (W + 63) / 64;
+    const int64_t bpp = (DW + RV_NT - 1) / RV_NT;
+    const int64_t g1 = n * nseg * bpp, g2 = n * bpp, g3 = n * nseg * nxc;
+    if (g1 > 0x7fffffffLL || g3 > 0x7fffffffLL) return hipErrorInvalidValue;
+    float *ws = nseg > 1 ? workspace : nullptr;
+    if (ws != nullptr) {
+        hipLaunchKernelGGL(k_render_seg_totals, dim3((unsigned)g1), dim3(RV_NT), 0, st, vols, stride, D, H, W, nseg, (int)bpp, up, ws);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_render_seg_scan, dim3((unsigned)g2), dim3(RV_NT), 0, st, (int)DW, nseg, (int)bpp, up, ws);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+#define SMK_RENDER_LIT(DMAX)                                                                                                            \
+    hipLaunchKernelGGL(k_render_lit<DMAX>, dim3((unsigned)g3), dim3(64), 0, st, vols, stride, D, H, W, nseg, nxc, up, p, ws, image, \
+                       image_stride, trans, trans_stride)
+    if (D <= 8) SMK_RENDER_LIT(8);
+    else if (D <= 16) SMK_RENDER_LIT(16);
+    else if (D <= 32) SMK_RENDER_LIT(32);
+    else SMK_RENDER_LIT(64);
+#undef SMK_RENDER_LIT
+    return hipGetLastError();
+}
+
+}  // namespace smk
+
+using namespace smk;
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+static const int64_t RENDER_MAX_CELLS = (1LL << 31) - (1LL << 16);     // smk_volume_stats' limit: 32-bit offsets inside a volume
+
+static bool render_shape_ok(int32_t n, int32_t D, int32_t H, int32_t W) {
+    return n >= 1 && D >= 1 && D <= RENDER_MAX_DEPTH && H >= 1 && W >= 1 && (int64_t)D * H * W <= RENDER_MAX_CELLS;
+}
+
+int64_t smk_volume_render_workspace(int32_t n, int32_t D, int32_t H, int32_t W, int32_t light) {
+    if (!render_shape_ok(n, D, H, W) || light < SMK_LIGHT_NONE || light > SMK_LIGHT_POS_Z) return -1;
+    return render_workspace(n, D, H, W, light);
+}
+
+int smk_volume_render(const float *vols, int64_t vol_stride, int32_t n, int32_t D, int32_t H, int32_t W, const smk_render_desc *desc,
+                      float *image, int64_t image_stride, float *transmittance, int64_t trans_stride, void *workspace,
+                      int64_t workspace_bytes, void *stream) {
+    SMK_REQUIRE(vols && desc && image, "null pointer");
+    SMK_REQUIRE(n >= 1 && D >= 1 && H >= 1 && W >= 1, "n, D, H, W >= 1");
+    if (!render_shape_ok(n, D, H, W)) {
+        set_error("volume_render: D <= 64 and D*H*W <= 2^31 - 2^16 are built (got D=" + std::to_string(D) + ", H=" + std::to_string(H) +
+                  ", W=" + std::to_string(W) + ")");
+        return SMK_ERR_UNSUPPORTED;
+    }
+    SMK_REQUIRE(desc->light >= SMK_LIGHT_NONE && desc->light <= SMK_LIGHT_POS_Z, "light: one of smk_light");
+    SMK_REQUIRE(desc->sigma_view >= 0 && desc->sigma_light >= 0 && desc->ambient >= 0 && desc->ambient <= 1 && desc->gain > 0,
+                "sigma_view, sigma_light >= 0; 0 <= ambient <= 1; gain > 0");
+    const int64_t cells = (int64_t)D * H * W, HW = (int64_t)H * W;
+    SMK_REQUIRE(vol_stride >= cells || n == 1, "vol_stride >= D*H*W");
+    SMK_REQUIRE(image_stride >= HW || n == 1, "image_stride >= H*W");
+    SMK_REQUIRE(transmittance == nullptr || trans_stride >= HW || n == 1, "trans_stride >= H*W");
+    SMK_REQUIRE(((uintptr_t)vols & 3) == 0 && ((uintptr_t)image & 3) == 0 && ((uintptr_t)transmittance & 3) == 0 &&
+                    ((uintptr_t)workspace & 3) == 0, "4-byte aligned pointers");
+    const int64_t need = render_workspace(n, D, H, W, desc->light);
+    SMK_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need),
+                "workspace smaller than smk_volume_render_workspace(n, D, H, W, light)");
+    RenderParams p;
+    p.neg_sigma_view = (float)-desc->sigma_view;
+    p.neg_sigma_light = (float)-desc->sigma_light;
+    p.ambient = (float)desc->ambient;
+    p.one_minus_ambient = (float)(1.0 - desc->ambient);
+    p.gain = (float)desc->gain;
+    const hipError_t e = launch_volume_render(vols, vol_stride, n, D, H, W, desc->light, p, image, image_stride, transmittance,
+                                              trans_stride, (float *)workspace, (hipStream_t)stream);
+    if (e != hipSuccess) {
+        set_error(std::string("volume_render: ") + hipGetErrorString(e));
+        return SMK_ERR_HIP;
+    }
+    return SMK_OK;
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

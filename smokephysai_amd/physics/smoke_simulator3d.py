@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 
 from .navier_stokes3d import NavierStokesSimulator3D
+from .render import RenderSettings, render_volumes, render_workspace
 from .smoke_simulator import (chaos_features_device, entropy_from_hist, fractal_dimension_from_counts, lyapunov_from_norms, volume_stats,
                               volume_stats_workspace)
 
@@ -80,6 +81,43 @@ class SmokeSimulator3D(nn.Module):
         if out is None:
             out = torch.empty(ns._B, n_steps, *ns.grid_size, device=ns._dev)
         ns.step_into(out, n_steps, add_fractal=add_fractal, fractal_intensity=0.05)
+        return out
+
+    # ---- rendered frames (SPEC_3D.md section 10; csrc/render.hip) ------------------------------------------------------------
+    def render(self, settings: Optional[RenderSettings] = None, transmittance: bool = False):
+        """The front-view image of the newest emitted volume(s): [B,H,W] batched / [H,W] un-batched, or (image, transmittance).
+        Reads the simulator's own copy of that volume; changes no state."""
+        if self.history_len == 0:
+            raise RuntimeError("render: no volume has been emitted yet (call simulate_step first)")
+        res = render_volumes(self._pair[:, self._slot], settings, transmittance=transmittance)
+        if self.batch_size is not None:
+            return res
+        return (res[0][0], res[1][0]) if transmittance else res[0]
+
+    def simulate_frames(self, n_steps: int, settings: Optional[RenderSettings] = None, add_fractal: bool = True,
+                        out: Optional[torch.Tensor] = None, chunk: int = 4) -> torch.Tensor:
+        """simulate_sequence followed by render_volumes, without the sequence: n_steps rendered frames per grid in one
+        [B, n_steps, H, W] tensor, bit-equal to render_volumes(simulate_sequence(n_steps)).  At most `chunk` steps of volumes exist at
+        a time.  No history bookkeeping, and the chaos-feature state is left alone."""
+        if chunk < 1:
+            raise ValueError("simulate_frames: chunk >= 1")
+        ns = self.ns_solver
+        B, (D, H, W) = ns._B, ns.grid_size
+        settings = RenderSettings() if settings is None else settings
+        if out is None:
+            out = torch.empty(B, n_steps, H, W, device=ns._dev)
+        elif (tuple(out.shape) != (B, n_steps, H, W) or out.dtype != torch.float32 or out.device != ns._dev
+              or not all(out[b].is_contiguous() for b in range(B))):
+            raise ValueError(f"simulate_frames: out must be float32 [B={B}, n_steps={n_steps}, {H}, {W}] on the simulator's device, "
+                             "the frames of one grid contiguous")
+        c = min(chunk, max(n_steps, 1))
+        vols = torch.empty(B, c, D, H, W, device=ns._dev)
+        ws = render_workspace(c, ns.grid_size, settings.light, ns._dev)
+        for t0 in range(0, n_steps, c):
+            k = min(c, n_steps - t0)
+            ns.step_into(vols[:, :k], k, add_fractal=add_fractal, fractal_intensity=0.05)
+            for b in range(B):                                           # out[b, t0:t0+k] is contiguous whatever out's batch stride
+                render_volumes(vols[b, :k], settings, out=out[b, t0:t0 + k], workspace=ws)
         return out
 
     # ---- chaos statistics (smoke_simulator.py:47-140 on the list of emitted volumes) ------------------------------------

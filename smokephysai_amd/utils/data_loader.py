@@ -18,6 +18,7 @@ from torch.utils.data import DataLoader, Dataset
 from .. import _lib
 from ..physics.smoke_simulator import (SmokeSimulator, chaos_features_device, chaos_stats, entropy_from_hist,
                                        fractal_dimension_from_counts, frame_diff_norms, lyapunov_from_norms, volume_stats)
+from ..physics.render import RenderSettings, render_supported, render_volumes
 from ..physics.smoke_simulator3d import SmokeSimulator3D
 from .distributed import shard_range
 
@@ -356,8 +357,9 @@ class SyntheticSmokeDataset3D(Dataset):
             seqs = buf[HIST_TAIL:].view(n, T, *self.grid_size)
             sim.simulate_sequence(T, add_fractal=True, out=seqs)
             chunk_labels.append(chunk_chaos_labels_device3d(buf, n, T, valid_head)[max(lo - c0, 0):])
+            stored = self._stored_sequences(seqs)
             for i in range(max(c0, lo), c1):
-                seq = seqs[i - c0]
+                seq = stored[i - c0]
                 data.append({"sequence": seq if in_place else seq.to(self.storage_device).clone(), "chaos_features": None,
                              "source_config": cfgs[i]})
             tail = buf[HIST_TAIL - valid_head:][-HIST_TAIL:].clone()
@@ -366,6 +368,10 @@ class SyntheticSmokeDataset3D(Dataset):
             for d, row in zip(data, torch.cat(chunk_labels).cpu().tolist()):     # the one device-to-host copy of the labels
                 d["chaos_features"] = dict(zip(_LABEL_KEYS, row))
         return data
+
+    def _stored_sequences(self, seqs: torch.Tensor) -> torch.Tensor:
+        """What a sample keeps of its chunk's volumes [n, T, D, H, W]: here the volumes themselves (views of the chunk buffer)."""
+        return seqs
 
     def __len__(self) -> int:
         return len(self.data)
@@ -379,19 +385,61 @@ class SyntheticSmokeDataset3D(Dataset):
                 "sequence": sample["sequence"]}
 
 
+def as_render_settings(render) -> RenderSettings:
+    """None (the defaults), a RenderSettings, or a mapping of its fields (the `mi355x.render` section of a config)."""
+    if render is None:
+        return RenderSettings()
+    if isinstance(render, RenderSettings):
+        return render
+    return RenderSettings(**dict(render))
+
+
+class RenderedSmokeDataset(SyntheticSmokeDataset3D):
+    """Camera frames of simulated 3-D smoke with the labels of the 3-D flow, in SyntheticSmokeDataset's 2-D item schema (input / target
+    [1,H,W], chaos_features [3], sequence [T,H,W]): what SmokePhysNet and train.py consume.  Draws, chunks, stepper calls and device
+    labels are SyntheticSmokeDataset3D's, so the frames are the render (SPEC_3D.md section 10) of that dataset's volumes bit for bit and
+    the labels are its labels.  A sample keeps its T frames, never its volumes: one render_volumes call per chunk buffer, which is then
+    dropped.  grid_size is (D, H, W); render: RenderSettings, a mapping of its fields, or None for the defaults."""
+
+    def __init__(self, num_samples: int = 100, grid_size: Tuple[int, int, int] = (64, 128, 128), sequence_length: int = 20,
+                 device: str = "cuda", cache_path: Optional[str] = None, *, render=None, **kwargs):
+        self.render = as_render_settings(render)                            # a bad value raises here, before any device work
+        if len(tuple(grid_size)) != 3:
+            raise ValueError("grid_size must be (D, H, W)")
+        if not render_supported(*(int(s) for s in grid_size)):
+            raise ValueError(f"RenderedSmokeDataset: grid_size={tuple(grid_size)} cannot be rendered (1 <= D <= 64)")
+        super().__init__(num_samples, grid_size, sequence_length, device, cache_path, **kwargs)
+
+    def _stored_sequences(self, seqs: torch.Tensor) -> torch.Tensor:
+        return render_volumes(seqs, self.render)                            # [n, T, D, H, W] -> [n, T, H, W], a tensor of its own
+
+
 def create_data_loaders(batch_size: int = 16, num_train: int = 800, num_val: int = 200,
                         grid_size: Tuple[int, int] = (128, 128), device: str = "cuda", cache_dir: Optional[str] = None,
-                        **dataset_kwargs) -> Tuple[DataLoader, DataLoader]:
+                        render_depth: int = 0, render=None, **dataset_kwargs) -> Tuple[DataLoader, DataLoader]:
     """data_loader.py:126-184.  Sequences live on the device, so the loaders run in-process (num_workers=0): the
-    reference forks workers only after generation, and forking after HIP initialisation is not allowed here."""
+    reference forks workers only after generation, and forking after HIP initialisation is not allowed here.
+    render_depth = D > 0: the samples are RenderedSmokeDataset((D, H, W)) -- camera frames of 3-D smoke under the settings `render`, same
+    item schema; its labels are computed on the device (`labels` is not forwarded), and its caches carry their own names."""
     rank, world = dataset_kwargs.get("rank", 0), dataset_kwargs.get("world", 1)
     suffix = "" if world == 1 else f".rank{rank}of{world}"
-    train_cache = os.path.join(cache_dir, f"train_data{suffix}.pkl") if cache_dir else None
-    val_cache = os.path.join(cache_dir, f"val_data{suffix}.pkl") if cache_dir else None
-    train_dataset = SyntheticSmokeDataset(num_samples=num_train, grid_size=grid_size, device=device,
-                                          cache_path=train_cache, **dataset_kwargs)
-    val_dataset = SyntheticSmokeDataset(num_samples=num_val, grid_size=grid_size, device=device,
-                                        cache_path=val_cache, **dataset_kwargs)
+    if render_depth:
+        if render_depth < 0:
+            raise ValueError(f"render_depth={render_depth}: 0 (2-D simulator) or the depth D of the rendered grid")
+        rs = as_render_settings(render)
+        tag = f".render{int(render_depth)}_{rs.light}_{rs.sigma_view:g}_{rs.sigma_light:g}_{rs.ambient:g}_{rs.gain:g}"
+        kw = {k: v for k, v in dataset_kwargs.items() if k != "labels"}
+        grid3 = (int(render_depth),) + tuple(grid_size)
+
+        def make(num, name):
+            return RenderedSmokeDataset(num_samples=num, grid_size=grid3, device=device, render=rs,
+                                        cache_path=os.path.join(cache_dir, f"{name}{tag}{suffix}.pkl") if cache_dir else None, **kw)
+    else:
+        def make(num, name):
+            return SyntheticSmokeDataset(num_samples=num, grid_size=grid_size, device=device,
+                                         cache_path=os.path.join(cache_dir, f"{name}{suffix}.pkl") if cache_dir else None, **dataset_kwargs)
+    train_dataset = make(num_train, "train_data")
+    val_dataset = make(num_val, "val_data")
     train_loader = DataLoader(train_dataset, batch_size=batch_size, shuffle=True, num_workers=0)
     val_loader = DataLoader(val_dataset, batch_size=batch_size, shuffle=False, num_workers=0)
     return train_loader, val_loader

@@ -206,11 +206,14 @@ def build_model(config: dict):
 
 def data_loader_kwargs(config: dict, rank: int = 0, world: int = 1) -> dict:
     """create_data_loaders' keyword arguments (all but `device`) from the config's `training` / `data` sections and the optional
-    `mi355x` keys (sim_batch, jacobi_iters, dataset_labels); a missing key or a missing section means the reference-equivalent default."""
+    `mi355x` keys (sim_batch, jacobi_iters, dataset_labels, render_depth + render); a missing key or a missing section means the reference-equivalent default."""
     hw = config.get("mi355x", {}) or {}
-    return dict(batch_size=config["training"]["batch_size"], num_train=config["data"]["num_train"], num_val=config["data"]["num_val"],
-                grid_size=tuple(config["data"]["grid_size"]), cache_dir=config["data"]["cache_dir"], sim_batch=hw.get("sim_batch", 64),
-                jacobi_iters=hw.get("jacobi_iters", 20), labels=str(hw.get("dataset_labels", "host")), rank=rank, world=world)
+    kw = dict(batch_size=config["training"]["batch_size"], num_train=config["data"]["num_train"], num_val=config["data"]["num_val"],
+              grid_size=tuple(config["data"]["grid_size"]), cache_dir=config["data"]["cache_dir"], sim_batch=hw.get("sim_batch", 64),
+              jacobi_iters=hw.get("jacobi_iters", 20), labels=str(hw.get("dataset_labels", "host")), rank=rank, world=world)
+    if hw.get("render_depth", 0):           # camera frames of 3-D smoke (RenderedSmokeDataset); nothing is added without the key
+        kw.update(render_depth=int(hw["render_depth"]), render=dict(hw.get("render") or {}))
+    return kw
 
 
 def main():
