@@ -502,6 +502,43 @@ int smk_conv3d_cl_zsum_forward(smk_linear *lin, const float *src, int32_t D, int
  * H % 8 == 0, W % 16 == 0, H * W * 256 < 2^31. */
 int smk_conv3d_s7_march_forward(smk_linear *lin, const float *src, int32_t D, int32_t H, int32_t W, float *a1, int32_t activation, void *stream);
 
+/* ------------------------------------------------------------------ training passes of the 3-D encoder (SPEC_3D.md section 11)
+ * All activations channels-last: volume [B][D][H][W], a1 / z1 / da1 [B][D][H][W][64], z2 / dz2 [B][D][H][W][128], fp32, 16-byte aligned.
+ * Weights in torch's layout: conv1 [64][1][7][7][7], conv2 [128][64][3][3][3]; they are re-laid on the device in the same call, so an
+ * optimizer step needs no other notification.  H % 8 == 0 and W % 16 == 0 (a workgroup's tile is 8 x 16 voxels of one plane), B, D >= 1;
+ * anything else is SMK_ERR_UNSUPPORTED.  Every pass runs on the exact fp32-input MFMA with fp32 accumulation; every reduction has a fixed
+ * order and there are no atomics, so a repeated call is bit-identical.  Enqueued on `stream`.
+ *   smk_conv3d_s7_train_forward  z1 = conv1(volume) + bias (bias may be NULL), raw: no activation.
+ *   smk_conv3d_cl_train_forward  z2 = conv2(a1) + bias, raw.
+ *   smk_conv3d_cl_dgrad          da1 = the data gradient of conv2 from dz2 (the 3 x 3 x 3 convolution 128 -> 64 with the flipped kernel).
+ *   smk_conv3d_cl_wgrad          dw [128][64][3][3][3] and db [128] (may be NULL) from dz2 and a1, implicit (no patch matrix): the voxels are
+ *                                the MFMA k dimension, a workgroup owns 32 output channels x one kz slice and one voxel stream, the streams'
+ *                                partials are added in stream order.
+ * `workspace`: smk_conv3d_train_workspace() bytes for the first three (their own contents: do not share one buffer between calls that may
+ * overlap), smk_conv3d_cl_wgrad_workspace(B, D, H, W) bytes (negative: unsupported shape) for the weight gradient; caller-owned device memory. */
+int64_t smk_conv3d_train_workspace(void);
+int64_t smk_conv3d_cl_wgrad_workspace(int32_t B, int32_t D, int32_t H, int32_t W);
+int smk_conv3d_s7_train_forward(const float *volume, const float *weight, const float *bias, int32_t B, int32_t D, int32_t H, int32_t W, float *z1,
+                                void *workspace, void *stream);
+int smk_conv3d_cl_train_forward(const float *a1, const float *weight, const float *bias, int32_t B, int32_t D, int32_t H, int32_t W, float *z2,
+                                void *workspace, void *stream);
+int smk_conv3d_cl_dgrad(const float *dz2, const float *weight, int32_t B, int32_t D, int32_t H, int32_t W, float *da1, void *workspace, void *stream);
+int smk_conv3d_cl_wgrad(const float *dz2, const float *a1, int32_t B, int32_t D, int32_t H, int32_t W, float *dw, float *db, void *workspace,
+                        void *stream);
+/* Train-mode BatchNorm3d + ReLU on a channels-last matrix z [B*D*H*W][C], C = 64 or 128, in the four phases of smk_bn_relu_pool_phase
+ * (enum smk_bn_phase; unused pointers may be NULL):
+ *   SMK_BN_STATS     z -> mean / var (biased) / rstd [C] (the caller updates the running statistics from them);
+ *   SMK_BN_APPLY     pooled = 0: out [B*D*H*W][C] = relu(bn(z)).  pooled = 1 (H, W multiples of 32): out [B][1024][C] = the token SUMS of
+ *                    relu(bn(z)) over D x (H/32) x (W/32) -- the caller divides by that block size once; the activation is not written;
+ *   SMK_BN_BWD_SUMS  dout, z -> dgamma = sum dy zhat, dbeta = sum dy; the ReLU mask is recomputed from z.  pooled = 0: dout [B*D*H*W][C];
+ *                    pooled = 1: dout [B][1024][C] is the gradient of the token MEANS, broadcast over each block and divided by its size;
+ *   SMK_BN_BWD_DZ    dz [B*D*H*W][C] from the given dgamma / dbeta and count = elements per channel.
+ * Sums are fp64, two-stage, in a fixed order.  `workspace`: smk_bn_cl_workspace(B, D, H, W, C) bytes. */
+int64_t smk_bn_cl_workspace(int32_t B, int32_t D, int32_t H, int32_t W, int32_t C);
+int smk_bn_cl_phase(int32_t phase, const float *z, const float *dout, int32_t B, int32_t D, int32_t H, int32_t W, int32_t C, int32_t pooled,
+                    const float *gamma, const float *beta, double eps, float *mean, float *var, float *rstd, float *out, float *dz, float *dgamma,
+                    float *dbeta, double count, void *workspace, void *stream);
+
 /* smk_chaos_addend for up to 8 layers in ONE launch (a model's layers draw their noise up front; six launches of one workgroup per batch
  * element are six launch latencies at batch 1).  Each layer: its own noise [3][B], weights, output and strength; B, D and the Lorenz constants
  * are shared. */

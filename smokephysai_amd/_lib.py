@@ -81,6 +81,12 @@ _SIGNATURES = {
     "smk_conv3d_s7_forward": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p],
     "smk_conv3d_cl_zsum_forward": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p],
     "smk_conv3d_s7_march_forward": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p],
+    "smk_conv3d_s7_train_forward": [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p] * 3,
+    "smk_conv3d_cl_train_forward": [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p] * 3,
+    "smk_conv3d_cl_dgrad": [C.c_void_p] * 2 + [C.c_int32] * 4 + [C.c_void_p] * 3,
+    "smk_conv3d_cl_wgrad": [C.c_void_p] * 2 + [C.c_int32] * 4 + [C.c_void_p] * 4,
+    "smk_bn_cl_phase": [C.c_int32, C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p, C.c_void_p, C.c_double] + [C.c_void_p] * 7 +
+                       [C.c_double, C.c_void_p, C.c_void_p],
     "smk_pool3d_accumulate": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p],
     "smk_sim_reset": [C.c_void_p, C.c_char_p, C.c_void_p],
     "smk_sim_add_sources": [C.c_void_p, C.POINTER(SmkSource), C.c_int32, C.c_void_p],
@@ -191,7 +197,8 @@ _SIGNATURES = {
 EXPORTS = ["smk_abi_version", "smk_last_error", "smk_linear_wgrad_workspace", "smk_bn_train_workspace", "smk_layernorm_bwd_workspace", "smk_conv2_train_workspace", "smk_conv2_train_wgrad_workspace", "smk_conv1_train_wgrad_workspace", "smk_attention_workspace_bytes", "smk_linear_ln_max_rows", "smk_image_quality_workspace", "smk_convt4s2_train_wgrad_workspace",
            "smk_volume_stats_workspace", "smk_grad_norm_workspace", "smk_train_loss_workspace",
            "smk_conv3_sigmoid_train_workspace", "smk_flow_levels", "smk_flow_farneback_workspace", "smk_warp_workspace",
-           "smk_flow_lk_workspace", "smk_volume_render_workspace"] + list(_SIGNATURES)
+           "smk_flow_lk_workspace", "smk_volume_render_workspace", "smk_conv3d_train_workspace", "smk_conv3d_cl_wgrad_workspace",
+           "smk_bn_cl_workspace"] + list(_SIGNATURES)
 
 _lib = None
 
@@ -253,6 +260,12 @@ def load():
         L.smk_grad_norm_workspace.restype = C.c_int64
         L.smk_train_loss_workspace.argtypes = [C.c_int32] * 4 + [C.c_int64]
         L.smk_train_loss_workspace.restype = C.c_int64
+        L.smk_conv3d_train_workspace.argtypes = []
+        L.smk_conv3d_train_workspace.restype = C.c_int64
+        L.smk_conv3d_cl_wgrad_workspace.argtypes = [C.c_int32] * 4
+        L.smk_conv3d_cl_wgrad_workspace.restype = C.c_int64      # a byte count; -1 = unsupported shape
+        L.smk_bn_cl_workspace.argtypes = [C.c_int32] * 5
+        L.smk_bn_cl_workspace.restype = C.c_int64
         L.smk_flow_levels.argtypes = [C.c_int32] * 2
         L.smk_flow_levels.restype = C.c_int32                     # a level count, not a status
         for name in ("smk_flow_farneback_workspace", "smk_warp_workspace", "smk_flow_lk_workspace"):

@@ -9,6 +9,7 @@
 
 #include "chaos.h"
 #include "conv3d.h"
+#include "conv3d_train.h"
 #include "decoder.h"
 #include "decoder_train.h"
 #include "elementwise.h"
@@ -1707,6 +1708,79 @@ int smk_conv2_train_wgrad(const float *dz, const float *a1, int32_t B, int32_t H
         return SMK_ERR_UNSUPPORTED;
     }
     return check_launch(launch_conv2_train_wgrad(dz, a1, B, H, W, dw, db, workspace, (hipStream_t)stream), "conv2_train_wgrad");
+}
+
+// ------------------------------------------------------------------ 3-D encoder, training (csrc/conv3d_train.hip)
+static int conv3d_train_check(int32_t B, int32_t D, int32_t H, int32_t W, const char *what) {
+    if (!conv3d_train_shape_ok(B, D, H, W)) {
+        set_error(std::string(what) + ": B, D >= 1, H a multiple of 8, W a multiple of 16");
+        return SMK_ERR_UNSUPPORTED;
+    }
+    return SMK_OK;
+}
+#define SMK_ALIGNED16(p) (((uintptr_t)(p) & 15) == 0)
+
+int64_t smk_conv3d_train_workspace(void) { return (int64_t)C3T_W2_BYTES; }
+int64_t smk_conv3d_cl_wgrad_workspace(int32_t B, int32_t D, int32_t H, int32_t W) {
+    return conv3d_train_shape_ok(B, D, H, W) ? (int64_t)conv3d_wgrad_workspace_bytes(B, D, H, W) : -1;
+}
+
+int smk_conv3d_s7_train_forward(const float *volume, const float *weight, const float *bias, int32_t B, int32_t D, int32_t H, int32_t W, float *z1,
+                                void *workspace, void *stream) {
+    SMK_REQUIRE(volume && weight && z1 && workspace, "null volume/weight/z1/workspace");
+    if (int rc = conv3d_train_check(B, D, H, W, "conv3d_s7_train_forward")) return rc;
+    SMK_REQUIRE(SMK_ALIGNED16(z1) && SMK_ALIGNED16(workspace), "16-byte aligned z1 / workspace");
+    return check_launch(launch_conv3d_s7_train_forward(volume, weight, bias, B, D, H, W, z1, workspace, (hipStream_t)stream), "conv3d_s7_train_forward");
+}
+
+int smk_conv3d_cl_train_forward(const float *a1, const float *weight, const float *bias, int32_t B, int32_t D, int32_t H, int32_t W, float *z2,
+                                void *workspace, void *stream) {
+    SMK_REQUIRE(a1 && weight && z2 && workspace, "null a1/weight/z2/workspace");
+    if (int rc = conv3d_train_check(B, D, H, W, "conv3d_cl_train_forward")) return rc;
+    SMK_REQUIRE(SMK_ALIGNED16(a1) && SMK_ALIGNED16(z2) && SMK_ALIGNED16(workspace), "16-byte aligned a1 / z2 / workspace");
+    return check_launch(launch_conv3d_cl_train_forward(a1, weight, bias, B, D, H, W, z2, workspace, (hipStream_t)stream), "conv3d_cl_train_forward");
+}
+
+int smk_conv3d_cl_dgrad(const float *dz2, const float *weight, int32_t B, int32_t D, int32_t H, int32_t W, float *da1, void *workspace, void *stream) {
+    SMK_REQUIRE(dz2 && weight && da1 && workspace, "null dz2/weight/da1/workspace");
+    if (int rc = conv3d_train_check(B, D, H, W, "conv3d_cl_dgrad")) return rc;
+    SMK_REQUIRE(SMK_ALIGNED16(dz2) && SMK_ALIGNED16(da1) && SMK_ALIGNED16(workspace), "16-byte aligned dz2 / da1 / workspace");
+    return check_launch(launch_conv3d_cl_dgrad(dz2, weight, B, D, H, W, da1, workspace, (hipStream_t)stream), "conv3d_cl_dgrad");
+}
+
+int smk_conv3d_cl_wgrad(const float *dz2, const float *a1, int32_t B, int32_t D, int32_t H, int32_t W, float *dw, float *db, void *workspace,
+                        void *stream) {
+    SMK_REQUIRE(dz2 && a1 && dw && workspace, "null dz2/a1/dw/workspace");
+    if (int rc = conv3d_train_check(B, D, H, W, "conv3d_cl_wgrad")) return rc;
+    SMK_REQUIRE(SMK_ALIGNED16(dz2) && SMK_ALIGNED16(a1) && SMK_ALIGNED16(workspace), "16-byte aligned dz2 / a1 / workspace");
+    return check_launch(launch_conv3d_cl_wgrad(dz2, a1, B, D, H, W, dw, db, workspace, (hipStream_t)stream), "conv3d_cl_wgrad");
+}
+
+static bool bn_cl_shape_ok(int32_t B, int32_t D, int32_t H, int32_t W, int32_t C, int32_t pooled) {
+    if (B < 1 || D < 1 || H < 1 || W < 1 || (C != 64 && C != 128) || (int64_t)B * D * H * W >= (1ll << 40)) return false;
+    return !pooled || (H % 32 == 0 && W % 32 == 0);
+}
+int64_t smk_bn_cl_workspace(int32_t B, int32_t D, int32_t H, int32_t W, int32_t C) {
+    return bn_cl_shape_ok(B, D, H, W, C, 0) ? (int64_t)bn_cl_workspace_bytes((long long)B * D * H * W, C) : -1;
+}
+
+int smk_bn_cl_phase(int32_t phase, const float *z, const float *dout, int32_t B, int32_t D, int32_t H, int32_t W, int32_t C, int32_t pooled,
+                    const float *gamma, const float *beta, double eps, float *mean, float *var, float *rstd, float *out, float *dz, float *dgamma,
+                    float *dbeta, double count, void *workspace, void *stream) {
+    if (!bn_cl_shape_ok(B, D, H, W, C, pooled)) {
+        set_error("bn_cl_phase: C 64 or 128, B, D, H, W >= 1, and H, W multiples of 32 when pooled");
+        return SMK_ERR_UNSUPPORTED;
+    }
+    SMK_REQUIRE(z && mean && rstd && SMK_ALIGNED16(z), "null or unaligned z / mean / rstd");
+    switch (phase) {
+    case SMK_BN_STATS: SMK_REQUIRE(var && workspace, "STATS: null var/workspace"); break;
+    case SMK_BN_APPLY: SMK_REQUIRE(gamma && beta && out && SMK_ALIGNED16(out), "APPLY: null gamma/beta/out"); break;
+    case SMK_BN_BWD_SUMS: SMK_REQUIRE(gamma && beta && dout && dgamma && dbeta && workspace && SMK_ALIGNED16(dout), "BWD_SUMS: null gamma/beta/dout/dgamma/dbeta/workspace"); break;
+    case SMK_BN_BWD_DZ: SMK_REQUIRE(gamma && beta && dout && dgamma && dbeta && dz && count > 0 && SMK_ALIGNED16(dout) && SMK_ALIGNED16(dz), "BWD_DZ: null gamma/beta/dout/dgamma/dbeta/dz, or count <= 0"); break;
+    default: SMK_REQUIRE(false, "unknown phase");
+    }
+    return check_launch(launch_bn_cl_phase(phase, z, dout, B, D, H, W, C, pooled, gamma, beta, eps, mean, var, rstd, out, dz, dgamma, dbeta, count,
+                                           workspace, (hipStream_t)stream), "bn_cl_phase");
 }
 
 // ------------------------------------------------------------------ reconstruction head, training (csrc/decoder_train.hip)

@@ -12,8 +12,15 @@ once into a table of ready MFMA fragments in LDS.  conv2 (`smk_conv3d_cl_zsum_fo
 never written; `smk_pool3d_accumulate` reduces the depth sums to the 32 x 32 token sums.
 `conv2_mode="implicit"` keeps the first form built (both convolutions as implicit GEMMs on the layer kernel: `smk_conv3d_cl_forward`,
 `smk_conv3d_s7_forward`), `"im2col"` the explicit one (`smk_conv3d_im2col` -> [voxels, taps x channels] -> `smk_linear_forward`), for A/B runs.
+
+Training (SPEC_3D.md section 11; csrc/conv3d_train.hip): `Encoder3D` is the nn.Module form of the same chain with train-mode BatchNorm3d.
+Its autograd functions keep the activations channels-last [B, D, H, W, C] from the volume to the tokens: `hip_conv3d_s7_train` (conv1;
+weight gradient through the explicit patch matrix), `hip_conv3d_cl_train` (conv2: forward, data gradient and implicit weight gradient
+kernels) and `hip_bn3d_cl` (batch statistics + ReLU, for the second block fused with the token pooling).
 """
 import torch
+import torch.nn.functional as F
+from torch import nn
 
 from .. import _lib
 from .linear import HipLinear
@@ -143,3 +150,281 @@ class HipEncoder3D:
     def tokens(self, x: torch.Tensor) -> torch.Tensor:
         """Same features token-major [B, 1024, 128] (= features.flatten(2).transpose(1, 2), smokephys_net.py:95)."""
         return self(x).flatten(2).transpose(1, 2).contiguous()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Training: autograd functions over csrc/conv3d_train.hip, channels-last activations
+def pool_shape_ok(H: int, W: int) -> bool:
+    """The pool rule of SPEC_3D.md section 8: H, W in {32, 64} or multiples of 128 (the two adaptive pools are then one uniform block mean)."""
+    return all(n >= 32 and n % 32 == 0 and (n % 128 == 0 or 128 % n == 0) for n in (int(H), int(W)))
+
+
+def hip_conv3d_train_supported(B: int, D: int, H: int, W: int) -> bool:
+    """The shape rule of the training convolution kernels (conv3d_train_shape_ok in csrc/conv3d_train.h)."""
+    return B >= 1 and D >= 1 and H >= 8 and W >= 16 and H % 8 == 0 and W % 16 == 0 and B * D * (H // 8) * (W // 16) < (1 << 31)
+
+
+def _ws(nbytes, dev):
+    return torch.empty(int(nbytes), device=dev, dtype=torch.uint8)             # torch's caching allocator: stream-ordered reuse
+
+
+CONV1_WGRAD_SLAB_ROWS = 1 << 17      # voxels per patch-matrix slab of conv1's weight gradient (384 floats each: 192 MB)
+
+
+def hip_conv3d_s7_wgrad(vol: torch.Tensor, dz1: torch.Tensor):
+    """dW1 [64, 1, 7, 7, 7] and db1 [64] of conv1 from the volumes [B, D, H, W] and dz1 [B, D, H, W, 64]: the explicit route -- smk_conv3d_im2col
+    (C = 1, k = 7, 384 columns) in slabs of whole planes, then smk_linear_wgrad, the slabs added in order (deterministic)."""
+    from .linear import hip_linear_wgrad
+    L = _lib.load()
+    dev = vol.device
+    B, D, H, W = vol.shape
+    nz = max(1, min(D, CONV1_WGRAD_SLAB_ROWS // (H * W)))
+    dw = db = None
+    for b in range(B):
+        for z0 in range(0, D, nz):
+            n = min(nz, D - z0)
+            cols = torch.empty(n * H * W, 384, device=dev, dtype=torch.float32)
+            _lib.check(L.smk_conv3d_im2col(vol[b].data_ptr(), 1, D, H, W, 7, z0, n, cols.data_ptr(), 384, _lib.stream_ptr(dev)))
+            w, g = hip_linear_wgrad(dz1[b, z0:z0 + n].reshape(n * H * W, 64), cols, want_db=True)
+            dw, db = (w, g) if dw is None else (dw.add_(w), db.add_(g))
+    return dw[:, :343].reshape(64, 1, 7, 7, 7).contiguous(), db
+
+
+class _HipConv3dS7TrainFn(torch.autograd.Function):
+    """z1 [B, D, H, W, 64] = conv1(volumes [B, D, H, W]) + bias on smk_conv3d_s7_train_forward.  The volumes take no gradient."""
+
+    @staticmethod
+    def forward(ctx, vol, weight, bias):
+        dev = _lib.require_cuda(vol.device, "hip_conv3d_s7_train")
+        L = _lib.load()
+        vol = vol.contiguous()
+        B, D, H, W = vol.shape
+        w, b = weight.detach().contiguous(), bias.detach().contiguous()
+        z1 = torch.empty(B, D, H, W, 64, device=dev, dtype=torch.float32)
+        ws = _ws(L.smk_conv3d_train_workspace(), dev)
+        _lib.check(L.smk_conv3d_s7_train_forward(vol.data_ptr(), w.data_ptr(), b.data_ptr(), B, D, H, W, z1.data_ptr(), ws.data_ptr(),
+                                                 _lib.stream_ptr(dev)))
+        ctx.save_for_backward(vol)
+        return z1
+
+    @staticmethod
+    def backward(ctx, dz1):
+        vol, = ctx.saved_tensors
+        dw, db = hip_conv3d_s7_wgrad(vol, dz1.contiguous())
+        return None, dw, db
+
+
+def hip_conv3d_cl_forward_raw(a1, weight, bias):
+    L = _lib.load()
+    dev = a1.device
+    B, D, H, W, _ = a1.shape
+    z2 = torch.empty(B, D, H, W, 128, device=dev, dtype=torch.float32)
+    ws = _ws(L.smk_conv3d_train_workspace(), dev)
+    _lib.check(L.smk_conv3d_cl_train_forward(a1.data_ptr(), weight.data_ptr(), None if bias is None else bias.data_ptr(), B, D, H, W,
+                                             z2.data_ptr(), ws.data_ptr(), _lib.stream_ptr(dev)))
+    return z2
+
+
+def hip_conv3d_cl_dgrad(dz2, weight):
+    L = _lib.load()
+    dev = dz2.device
+    B, D, H, W, _ = dz2.shape
+    da1 = torch.empty(B, D, H, W, 64, device=dev, dtype=torch.float32)
+    ws = _ws(L.smk_conv3d_train_workspace(), dev)
+    _lib.check(L.smk_conv3d_cl_dgrad(dz2.data_ptr(), weight.data_ptr(), B, D, H, W, da1.data_ptr(), ws.data_ptr(), _lib.stream_ptr(dev)))
+    return da1
+
+
+def hip_conv3d_cl_wgrad(dz2, a1):
+    L = _lib.load()
+    dev = dz2.device
+    B, D, H, W, _ = dz2.shape
+    dw = torch.empty(128, 64, 3, 3, 3, device=dev, dtype=torch.float32)
+    db = torch.empty(128, device=dev, dtype=torch.float32)
+    nbytes = int(L.smk_conv3d_cl_wgrad_workspace(B, D, H, W))
+    if nbytes < 0:
+        raise ValueError("hip_conv3d_cl_wgrad: H must be a multiple of 8 and W of 16")
+    ws = _ws(nbytes, dev)
+    _lib.check(L.smk_conv3d_cl_wgrad(dz2.data_ptr(), a1.data_ptr(), B, D, H, W, dw.data_ptr(), db.data_ptr(), ws.data_ptr(), _lib.stream_ptr(dev)))
+    return dw, db
+
+
+class _HipConv3dClTrainFn(torch.autograd.Function):
+    """z2 [B, D, H, W, 128] = conv2(a1 [B, D, H, W, 64]) + bias: smk_conv3d_cl_train_forward / _dgrad / _wgrad."""
+
+    @staticmethod
+    def forward(ctx, a1, weight, bias):
+        _lib.require_cuda(a1.device, "hip_conv3d_cl_train")
+        a1 = a1.contiguous()
+        w, b = weight.detach().contiguous(), bias.detach().contiguous()
+        ctx.save_for_backward(a1, w)
+        return hip_conv3d_cl_forward_raw(a1, w, b)
+
+    @staticmethod
+    def backward(ctx, dz2):
+        a1, w = ctx.saved_tensors
+        dz2 = dz2.contiguous()
+        da1 = hip_conv3d_cl_dgrad(dz2, w) if ctx.needs_input_grad[0] else None
+        dw, db = hip_conv3d_cl_wgrad(dz2, a1)
+        return da1, dw, db
+
+
+def hip_conv3d_s7_train(vol: torch.Tensor, conv: nn.Conv3d) -> torch.Tensor:
+    return _HipConv3dS7TrainFn.apply(vol, conv.weight, conv.bias)
+
+
+def hip_conv3d_cl_train(a1: torch.Tensor, conv: nn.Conv3d) -> torch.Tensor:
+    return _HipConv3dClTrainFn.apply(a1, conv.weight, conv.bias)
+
+
+BN_STATS, BN_APPLY, BN_BWD_SUMS, BN_BWD_DZ = 0, 1, 2, 3
+
+
+def _bn_cl_phase(L, phase, z, dout, pooled, gamma, beta, eps, stats, out, dz, dwb, count, ws, dev):
+    B, D, H, W, C = z.shape
+    ptr = lambda t: None if t is None else t.data_ptr()
+    _lib.check(L.smk_bn_cl_phase(phase, z.data_ptr(), ptr(dout), B, D, H, W, C, int(pooled), gamma.data_ptr(), beta.data_ptr(), float(eps),
+                                 stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(), ptr(out), ptr(dz),
+                                 None if dwb is None else dwb[0].data_ptr(), None if dwb is None else dwb[1].data_ptr(), float(count), ptr(ws),
+                                 _lib.stream_ptr(dev)))
+
+
+class _HipBn3dClFn(torch.autograd.Function):
+    """relu(bn(z)) on batch statistics for z [B, D, H, W, C] (C 64 or 128).  pooled: the output is the token means [B, 1024, C] over
+    D x H/32 x W/32 and the activation is never written.  Returns (out, stats = mean | biased var | rstd)."""
+
+    @staticmethod
+    def forward(ctx, z, weight, bias, eps, pooled):
+        dev = _lib.require_cuda(z.device, "hip_bn3d_cl")
+        L = _lib.load()
+        z = z.contiguous()
+        B, D, H, W, C = z.shape
+        w, b = weight.detach().contiguous(), bias.detach().contiguous()
+        stats = torch.empty(3, C, device=dev, dtype=torch.float32)
+        nbytes = int(L.smk_bn_cl_workspace(B, D, H, W, C))
+        if nbytes < 0:
+            raise ValueError("hip_bn3d_cl: z must be [B, D, H, W, C] with C 64 or 128")
+        ws = _ws(nbytes, dev)
+        _bn_cl_phase(L, BN_STATS, z, None, pooled, w, b, eps, stats, None, None, None, 0.0, ws, dev)
+        if pooled:
+            out = torch.empty(B, 1024, C, device=dev, dtype=torch.float32)
+            _bn_cl_phase(L, BN_APPLY, z, None, 1, w, b, eps, stats, out, None, None, 0.0, None, dev)
+            out.mul_(1.0 / (D * (H // 32) * (W // 32)))
+        else:
+            out = torch.empty_like(z)
+            _bn_cl_phase(L, BN_APPLY, z, None, 0, w, b, eps, stats, out, None, None, 0.0, None, dev)
+        ctx.save_for_backward(z, w, b, stats)
+        ctx.pooled, ctx.eps = pooled, eps
+        ctx.mark_non_differentiable(stats)
+        return out, stats
+
+    @staticmethod
+    def backward(ctx, dout, _dstats):
+        z, w, b, stats = ctx.saved_tensors
+        L = _lib.load()
+        dev = z.device
+        B, D, H, W, C = z.shape
+        dout = dout.contiguous()
+        dwb = torch.empty(2, C, device=dev, dtype=torch.float32)          # dgamma | dbeta
+        ws = _ws(L.smk_bn_cl_workspace(B, D, H, W, C), dev)
+        _bn_cl_phase(L, BN_BWD_SUMS, z, dout, ctx.pooled, w, b, ctx.eps, stats, None, None, dwb, 0.0, ws, dev)
+        dz = torch.empty_like(z)
+        _bn_cl_phase(L, BN_BWD_DZ, z, dout, ctx.pooled, w, b, ctx.eps, stats, None, dz, dwb, float(B * D * H * W), None, dev)
+        return dz, dwb[0], dwb[1], None, None
+
+
+def _bn3d_hip_ok(bn) -> bool:
+    return type(bn) is nn.BatchNorm3d and bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None
+
+
+def hip_bn3d_cl(z: torch.Tensor, bn: nn.BatchNorm3d, pooled: bool = False) -> torch.Tensor:
+    """relu(bn(z)) (pooled: its token means) with bn in training mode on channels-last z [B, D, H, W, C]; the running statistics are updated
+    exactly like nn.BatchNorm3d's: momentum, unbiased variance, num_batches_tracked."""
+    if not _bn3d_hip_ok(bn):
+        raise ValueError("hip_bn3d_cl: a training-mode affine BatchNorm3d with running statistics and a fixed momentum")
+    out, stats = _HipBn3dClFn.apply(z, bn.weight, bn.bias, bn.eps, bool(pooled))
+    with torch.no_grad():
+        n = z.numel() // z.shape[-1]
+        m = bn.momentum
+        bn.running_mean.mul_(1 - m).add_(stats[0], alpha=m)
+        bn.running_var.mul_(1 - m).add_(stats[1], alpha=m * n / max(n - 1, 1))
+        bn.num_batches_tracked += 1
+    return out
+
+
+class Encoder3D(nn.Module):
+    """The trainable 3-D encoder (SPEC_3D.md section 11): Conv3d(1, 64, 7, padding 3) -> BatchNorm3d -> ReLU -> Conv3d(64, 128, 3, padding 1)
+    -> BatchNorm3d -> ReLU -> block mean over D x H/32 x W/32 -> tokens [B, 1024, 128].  route: "hip" (libsmokehip wherever a call allows
+    it) or "torch" (always the PyTorch modules: the reference of the tests and the A/B partner of tools/train3d_probe.py)."""
+
+    def __init__(self, route: str = "hip"):
+        super().__init__()
+        if route not in ("hip", "torch"):
+            raise ValueError(f"Encoder3D route: 'hip' (libsmokehip kernels) or 'torch' (PyTorch modules), not {route!r}")
+        self.route = route
+        self.net = nn.Sequential(nn.Conv3d(1, 64, 7, padding=3), nn.BatchNorm3d(64), nn.ReLU(inplace=True),
+                                 nn.Conv3d(64, 128, 3, padding=1), nn.BatchNorm3d(128), nn.ReLU(inplace=True))
+        self.__dict__["_hip_eval"] = None                      # (HipEncoder3D, weight fingerprint)
+
+    def __getstate__(self):                                    # copy.deepcopy / pickling: the eval mirror is per instance, rebuilt on use
+        d = self.__dict__.copy()
+        d["_hip_eval"] = None
+        return d
+
+    def weight_dict(self) -> dict:
+        """The 12 tensors under HipEncoder3D's key names (its constructor takes this dict)."""
+        c1, b1, _, c2, b2, _ = self.net
+        return dict(conv1_w=c1.weight, conv1_b=c1.bias, bn1_w=b1.weight, bn1_b=b1.bias, bn1_mean=b1.running_mean, bn1_var=b1.running_var,
+                    conv2_w=c2.weight, conv2_b=c2.bias, bn2_w=b2.weight, bn2_b=b2.bias, bn2_mean=b2.running_mean, bn2_var=b2.running_var)
+
+    def hip_eval_encoder(self) -> HipEncoder3D:
+        """The folded eval encoder for the current weights (rebuilt when a weight or a running statistic changes)."""
+        ws = self.weight_dict()
+        fp = tuple((t.data_ptr(), t._version) for t in ws.values())
+        cur = self.__dict__.get("_hip_eval")
+        if cur is None or cur[1] != fp:
+            cur = (HipEncoder3D(ws, device=ws["conv1_w"].device, eps=self.net[1].eps), fp)
+            self.__dict__["_hip_eval"] = cur
+        return cur[0]
+
+    def _route(self, x: torch.Tensor) -> str:
+        """'train': training mode, fp32 volumes of a supported shape on a ROCm device -> the training kernels (batch statistics);
+        'eval': eval mode under no_grad on the device -> the folded HipEncoder3D; 'torch': everything else."""
+        B, D, H, W = x.shape
+        c1, b1, _, c2, b2, _ = self.net
+        if self.route != "hip" or not x.is_cuda or x.dtype != torch.float32 or c1.weight.dtype != torch.float32 or not pool_shape_ok(H, W):
+            return "torch"
+        if self.training:
+            ok = (_bn3d_hip_ok(b1) and _bn3d_hip_ok(b2) and b1.eps == b2.eps and hip_conv3d_train_supported(B, D, H, W)
+                  and c1.bias is not None and c2.bias is not None)
+            return "train" if ok else "torch"
+        return "eval" if not torch.is_grad_enabled() and b1.eps == b2.eps else "torch"
+
+    def tokens(self, volumes: torch.Tensor) -> torch.Tensor:
+        """volumes [B, 1, D, H, W] or [B, D, H, W] -> tokens [B, 1024, 128]."""
+        x = volumes
+        if x.dim() == 5:
+            if x.shape[1] != 1:
+                raise ValueError("the 3-D encoder takes one channel")
+            x = x[:, 0]
+        if x.dim() != 4:
+            raise ValueError("volumes must be [B, 1, D, H, W] or [B, D, H, W]")
+        route = self._route(x)
+        if route == "train":
+            c1, b1, _, c2, b2, _ = self.net
+            a1 = hip_bn3d_cl(hip_conv3d_s7_train(x, c1), b1)
+            return hip_bn3d_cl(hip_conv3d_cl_train(a1, c2), b2, pooled=True)
+        if route == "eval":
+            return self.hip_eval_encoder().tokens(x)
+        B, D, H, W = x.shape
+        y = self.net(x[:, None])                               # [B, 128, D, H, W]
+        if pool_shape_ok(H, W):                                # the two adaptive pools as the one block mean they compose to
+            y = y.mean(dim=2)
+            k = (H // 32, W // 32)
+            y = y if k == (1, 1) else F.avg_pool2d(y, k)
+        else:
+            y = F.adaptive_avg_pool3d(F.adaptive_avg_pool3d(y, (1, 128, 128)), (1, 32, 32))[:, :, 0]
+        return y.flatten(2).transpose(1, 2)
+
+    def forward(self, volumes: torch.Tensor) -> torch.Tensor:
+        return self.tokens(volumes)

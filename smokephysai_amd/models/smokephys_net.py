@@ -480,6 +480,31 @@ class SmokePhysNet(nn.Module):
         return self.forward_tokens(encoder3d.tokens(volumes), return_features, chaos_noise)
 
 
+class SmokePhysNet3D(SmokePhysNet):
+    """SmokePhysNet fed with volumes (BASELINE configs[4]; SPEC_3D.md section 11): a trainable Encoder3D in front of the unchanged network.
+    forward takes volumes [B, 1, D, H, W] (through forward_volumes and self.encoder3d) or frames [B, 1, H, W] (the parent's route).  The 2-D
+    input_encoder stays in the module -- the state dict is SmokePhysNet's keys plus encoder3d.*, so a 2-D checkpoint loads with strict=False --
+    but its parameters are frozen: a volume step gives them no gradient, and DistributedDataParallel must not wait for one.
+    volume_encoder: Encoder3D's route, "hip" or "torch"."""
+
+    def __init__(self, *args, volume_encoder: str = "hip", **kwargs):
+        from .encoder3d import Encoder3D
+        super().__init__(*args, **kwargs)
+        self.encoder3d = Encoder3D(route=volume_encoder)
+        for p in self.input_encoder.parameters():
+            p.requires_grad_(False)
+
+    def forward(self, x: torch.Tensor, return_features: bool = False, chaos_noise: Optional[torch.Tensor] = None,
+                encoder_dtype: Optional[str] = None) -> dict:
+        if x.dim() == 5:
+            return self.forward_volumes(x, self.encoder3d, return_features, chaos_noise)
+        return super().forward(x, return_features, chaos_noise, encoder_dtype)
+
+    def invalidate_hip_mirrors(self) -> None:
+        super().invalidate_hip_mirrors()
+        self.encoder3d.__dict__["_hip_eval"] = None
+
+
 class ChaosTransformerLayer(nn.Module):
     """smokephys_net.py:136-168 (pre-LN block)."""
 

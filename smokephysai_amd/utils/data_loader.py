@@ -414,25 +414,72 @@ class RenderedSmokeDataset(SyntheticSmokeDataset3D):
         return render_volumes(seqs, self.render)                            # [n, T, D, H, W] -> [n, T, H, W], a tensor of its own
 
 
+class VolumeFrameDataset(SyntheticSmokeDataset3D):
+    """Volumes in, camera frames out: the samples SmokePhysNet3D trains on (SPEC_3D.md section 11).  Draws, chunks, stepper calls and device
+    labels are SyntheticSmokeDataset3D's, the frames RenderedSmokeDataset's.  Item: input [1,D,H,W] the emitted volume t, target [1,H,W] the
+    render (section 10) of volume t + 1, sequence [T,H,W] the rendered frames, chaos_features [3] -- a 2-D target, so the loss, the physics
+    regulariser and the HIP loss kernels apply unchanged.  A sample keeps its T frames and only the volumes __getitem__ can draw,
+    sequence[5 : T - 5] (randint(5, T - 5)), as a copy of their own: the chunk buffer of all T volumes is dropped."""
+
+    def __init__(self, num_samples: int = 100, grid_size: Tuple[int, int, int] = (64, 128, 128), sequence_length: int = 20,
+                 device: str = "cuda", cache_path: Optional[str] = None, *, render=None, **kwargs):
+        self.render = as_render_settings(render)
+        if len(tuple(grid_size)) != 3:
+            raise ValueError("grid_size must be (D, H, W)")
+        if not render_supported(*(int(s) for s in grid_size)):
+            raise ValueError(f"VolumeFrameDataset: grid_size={tuple(grid_size)} cannot be rendered (1 <= D <= 64)")
+        if sequence_length < 11:
+            raise ValueError("VolumeFrameDataset: sequence_length >= 11 (an item is drawn from volumes 5 .. T - 6)")
+        super().__init__(num_samples, grid_size, sequence_length, device, cache_path, **kwargs)
+
+    def _generate_synthetic_data(self) -> List[Dict]:
+        self._chunk_volumes = []
+        data = super()._generate_synthetic_data()
+        rows = [v for chunk in self._chunk_volumes for v in chunk]          # one entry per simulated sample, the history seed included
+        del self._chunk_volumes
+        for d, v in zip(data, rows[len(rows) - len(data):]):
+            d["volumes"] = v
+        return data
+
+    def _stored_sequences(self, seqs: torch.Tensor) -> torch.Tensor:
+        T = self.sequence_length
+        self._chunk_volumes.append(seqs[:, 5:T - 5].to(self.storage_device).clone())       # [n, T - 10, D, H, W]
+        return render_volumes(seqs, self.render)
+
+    def __getitem__(self, idx: int) -> Dict:
+        sample = self.data[idx]
+        frame_idx = np.random.randint(5, self.sequence_length - 5)         # data_loader.py:108
+        return {"input": sample["volumes"][frame_idx - 5].unsqueeze(0),
+                "target": sample["sequence"][frame_idx + 1].unsqueeze(0),
+                "chaos_features": torch.tensor([sample["chaos_features"][k] for k in _LABEL_KEYS], dtype=torch.float32),
+                "sequence": sample["sequence"]}
+
+
 def create_data_loaders(batch_size: int = 16, num_train: int = 800, num_val: int = 200,
                         grid_size: Tuple[int, int] = (128, 128), device: str = "cuda", cache_dir: Optional[str] = None,
-                        render_depth: int = 0, render=None, **dataset_kwargs) -> Tuple[DataLoader, DataLoader]:
+                        render_depth: int = 0, render=None, volume_depth: int = 0, **dataset_kwargs) -> Tuple[DataLoader, DataLoader]:
     """data_loader.py:126-184.  Sequences live on the device, so the loaders run in-process (num_workers=0): the
     reference forks workers only after generation, and forking after HIP initialisation is not allowed here.
     render_depth = D > 0: the samples are RenderedSmokeDataset((D, H, W)) -- camera frames of 3-D smoke under the settings `render`, same
-    item schema; its labels are computed on the device (`labels` is not forwarded), and its caches carry their own names."""
+    item schema; its labels are computed on the device (`labels` is not forwarded), and its caches carry their own names.
+    volume_depth = D > 0: the samples are VolumeFrameDataset((D, H, W)) -- the volume as the input, the rendered next frame as the target
+    (SmokePhysNet3D's training data); caches again under names of their own.  Both depths at once is an error."""
     rank, world = dataset_kwargs.get("rank", 0), dataset_kwargs.get("world", 1)
     suffix = "" if world == 1 else f".rank{rank}of{world}"
-    if render_depth:
-        if render_depth < 0:
-            raise ValueError(f"render_depth={render_depth}: 0 (2-D simulator) or the depth D of the rendered grid")
+    if render_depth and volume_depth:
+        raise ValueError("render_depth (frames of 3-D smoke into the 2-D model) and volume_depth (volumes into the 3-D model) exclude each other")
+    if render_depth or volume_depth:
+        depth = int(render_depth or volume_depth)
+        if depth < 0:
+            raise ValueError(f"render_depth / volume_depth = {depth}: 0 (2-D simulator) or the depth D of the simulated grid")
         rs = as_render_settings(render)
-        tag = f".render{int(render_depth)}_{rs.light}_{rs.sigma_view:g}_{rs.sigma_light:g}_{rs.ambient:g}_{rs.gain:g}"
+        tag = f".{'volume' if volume_depth else 'render'}{depth}_{rs.light}_{rs.sigma_view:g}_{rs.sigma_light:g}_{rs.ambient:g}_{rs.gain:g}"
         kw = {k: v for k, v in dataset_kwargs.items() if k != "labels"}
-        grid3 = (int(render_depth),) + tuple(grid_size)
+        grid3 = (depth,) + tuple(grid_size)
+        cls = VolumeFrameDataset if volume_depth else RenderedSmokeDataset
 
         def make(num, name):
-            return RenderedSmokeDataset(num_samples=num, grid_size=grid3, device=device, render=rs,
+            return cls(num_samples=num, grid_size=grid3, device=device, render=rs,
                                         cache_path=os.path.join(cache_dir, f"{name}{tag}{suffix}.pkl") if cache_dir else None, **kw)
     else:
         def make(num, name):

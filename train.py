@@ -62,6 +62,8 @@ def setup_experiment(config: dict, rank: int = 0, local_rank: int = 0):
 
 LOSS_ROUTES = ("torch", "hip")
 OPTIMIZER_ROUTES = ("torch", "hip")
+VOLUME_ENCODER_ROUTES = ("hip", "torch")
+VOLUME_ENCODER_DEFAULT = "hip"
 _warned_losses = False
 
 
@@ -194,25 +196,36 @@ def validate_epoch(model: nn.Module, val_loader: DataLoader, physics_regularizer
 
 
 def build_model(config: dict):
-    """SmokePhysNet from the config's `model` section and the optional `mi355x` keys (encoder_dtype, recon_head, input_grad), on the CPU."""
-    from smokephysai_amd.models.smokephys_net import SmokePhysNet
+    """SmokePhysNet from the config's `model` section and the optional `mi355x` keys (encoder_dtype, recon_head, input_grad), on the CPU.
+    `mi355x.volume_depth: D > 0` makes it a SmokePhysNet3D (volumes through a trainable Encoder3D; `mi355x.volume_encoder`: hip | torch)."""
+    from smokephysai_amd.models.smokephys_net import SmokePhysNet, SmokePhysNet3D
     hw = config.get("mi355x", {}) or {}
-    return SmokePhysNet(input_dim=config["model"]["input_dim"], hidden_dim=config["model"]["hidden_dim"],
-                        num_layers=config["model"]["num_layers"], num_heads=config["model"]["num_heads"],
-                        chaos_strength=config["model"]["chaos_strength"],
-                        encoder_dtype=hw.get("encoder_dtype", "bf16x3"), head_train=str(hw.get("recon_head", "torch")),
-                        input_grad=None if hw.get("input_grad") is None else str(hw["input_grad"]))
+    cls, extra = SmokePhysNet, {}
+    if int(hw.get("volume_depth", 0) or 0) > 0:
+        if hw.get("sync_bn", False):
+            raise ValueError("mi355x.volume_depth with mi355x.sync_bn: the 3-D encoder's BatchNorm statistics are per process; set sync_bn: false")
+        cls, extra = SmokePhysNet3D, dict(volume_encoder=_route(hw.get("volume_encoder", VOLUME_ENCODER_DEFAULT), VOLUME_ENCODER_ROUTES,
+                                                                "mi355x.volume_encoder"))
+    return cls(**extra, input_dim=config["model"]["input_dim"], hidden_dim=config["model"]["hidden_dim"],
+               num_layers=config["model"]["num_layers"], num_heads=config["model"]["num_heads"],
+               chaos_strength=config["model"]["chaos_strength"],
+               encoder_dtype=hw.get("encoder_dtype", "bf16x3"), head_train=str(hw.get("recon_head", "torch")),
+               input_grad=None if hw.get("input_grad") is None else str(hw["input_grad"]))
 
 
 def data_loader_kwargs(config: dict, rank: int = 0, world: int = 1) -> dict:
     """create_data_loaders' keyword arguments (all but `device`) from the config's `training` / `data` sections and the optional
-    `mi355x` keys (sim_batch, jacobi_iters, dataset_labels, render_depth + render); a missing key or a missing section means the reference-equivalent default."""
+    `mi355x` keys (sim_batch, jacobi_iters, dataset_labels, render_depth or volume_depth + render); a missing key or a missing section means the reference-equivalent default."""
     hw = config.get("mi355x", {}) or {}
     kw = dict(batch_size=config["training"]["batch_size"], num_train=config["data"]["num_train"], num_val=config["data"]["num_val"],
               grid_size=tuple(config["data"]["grid_size"]), cache_dir=config["data"]["cache_dir"], sim_batch=hw.get("sim_batch", 64),
               jacobi_iters=hw.get("jacobi_iters", 20), labels=str(hw.get("dataset_labels", "host")), rank=rank, world=world)
     if hw.get("render_depth", 0):           # camera frames of 3-D smoke (RenderedSmokeDataset); nothing is added without the key
         kw.update(render_depth=int(hw["render_depth"]), render=dict(hw.get("render") or {}))
+    if hw.get("volume_depth", 0):           # volumes in, rendered next frame out (VolumeFrameDataset, for SmokePhysNet3D)
+        if hw.get("render_depth", 0):
+            raise ValueError("mi355x.render_depth and mi355x.volume_depth exclude each other")
+        kw.update(volume_depth=int(hw["volume_depth"]), render=dict(hw.get("render") or {}))
     return kw
 
 
