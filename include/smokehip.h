@@ -514,7 +514,10 @@ int smk_conv3d_s7_march_forward(smk_linear *lin, const float *src, int32_t D, in
  *   smk_conv3d_cl_wgrad          dw [128][64][3][3][3] and db [128] (may be NULL) from dz2 and a1, implicit (no patch matrix): the voxels are
  *                                the MFMA k dimension, a workgroup owns 32 output channels x one kz slice and one voxel stream, the streams'
  *                                partials are added in stream order.
- * `workspace`: smk_conv3d_train_workspace() bytes for the first three (their own contents: do not share one buffer between calls that may
+ *   smk_conv3d_s7_dgrad          dvol [B][D][H][W] = the data gradient of conv1 from dz1 [B][D][H][W][64]:
+ *                                dvol[z][y][x] = sum over c, kz, ky, kx of dz1[z+3-kz][y+3-ky][x+3-kx][c] w[c][0][kz][ky][kx], out-of-volume
+ *                                terms zero (F.conv_transpose3d with padding 3).  A sample's result does not depend on its batch mates.
+ * `workspace`: smk_conv3d_train_workspace() bytes for all but the weight gradient (their own contents: do not share one buffer between calls that may
  * overlap), smk_conv3d_cl_wgrad_workspace(B, D, H, W) bytes (negative: unsupported shape) for the weight gradient; caller-owned device memory. */
 int64_t smk_conv3d_train_workspace(void);
 int64_t smk_conv3d_cl_wgrad_workspace(int32_t B, int32_t D, int32_t H, int32_t W);
@@ -525,6 +528,7 @@ int smk_conv3d_cl_train_forward(const float *a1, const float *weight, const floa
 int smk_conv3d_cl_dgrad(const float *dz2, const float *weight, int32_t B, int32_t D, int32_t H, int32_t W, float *da1, void *workspace, void *stream);
 int smk_conv3d_cl_wgrad(const float *dz2, const float *a1, int32_t B, int32_t D, int32_t H, int32_t W, float *dw, float *db, void *workspace,
                         void *stream);
+int smk_conv3d_s7_dgrad(const float *dz1, const float *weight, int32_t B, int32_t D, int32_t H, int32_t W, float *dvol, void *workspace, void *stream);
 /* Train-mode BatchNorm3d + ReLU on a channels-last matrix z [B*D*H*W][C], C = 64 or 128, in the four phases of smk_bn_relu_pool_phase
  * (enum smk_bn_phase; unused pointers may be NULL):
  *   SMK_BN_STATS     z -> mean / var (biased) / rstd [C] (the caller updates the running statistics from them);

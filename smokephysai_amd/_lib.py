@@ -85,6 +85,7 @@ _SIGNATURES = {
     "smk_conv3d_cl_train_forward": [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p] * 3,
     "smk_conv3d_cl_dgrad": [C.c_void_p] * 2 + [C.c_int32] * 4 + [C.c_void_p] * 3,
     "smk_conv3d_cl_wgrad": [C.c_void_p] * 2 + [C.c_int32] * 4 + [C.c_void_p] * 4,
+    "smk_conv3d_s7_dgrad": [C.c_void_p] * 2 + [C.c_int32] * 4 + [C.c_void_p] * 3,
     "smk_bn_cl_phase": [C.c_int32, C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p, C.c_void_p, C.c_double] + [C.c_void_p] * 7 +
                        [C.c_double, C.c_void_p, C.c_void_p],
     "smk_pool3d_accumulate": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p],

@@ -1733,6 +1733,13 @@ int smk_conv3d_s7_train_forward(const float *volume, const float *weight, const 
     return check_launch(launch_conv3d_s7_train_forward(volume, weight, bias, B, D, H, W, z1, workspace, (hipStream_t)stream), "conv3d_s7_train_forward");
 }
 
+int smk_conv3d_s7_dgrad(const float *dz1, const float *weight, int32_t B, int32_t D, int32_t H, int32_t W, float *dvol, void *workspace, void *stream) {
+    SMK_REQUIRE(dz1 && weight && dvol && workspace, "null dz1/weight/dvol/workspace");
+    if (int rc = conv3d_train_check(B, D, H, W, "conv3d_s7_dgrad")) return rc;
+    SMK_REQUIRE(SMK_ALIGNED16(dz1) && SMK_ALIGNED16(dvol) && SMK_ALIGNED16(workspace), "16-byte aligned dz1 / dvol / workspace");
+    return check_launch(launch_conv3d_s7_dgrad(dz1, weight, B, D, H, W, dvol, workspace, (hipStream_t)stream), "conv3d_s7_dgrad");
+}
+
 int smk_conv3d_cl_train_forward(const float *a1, const float *weight, const float *bias, int32_t B, int32_t D, int32_t H, int32_t W, float *z2,
                                 void *workspace, void *stream) {
     SMK_REQUIRE(a1 && weight && z2 && workspace, "null a1/weight/z2/workspace");

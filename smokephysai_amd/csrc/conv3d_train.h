@@ -24,6 +24,8 @@ hipError_t launch_conv3d_cl_dgrad(const float *dz2, const float *w2, int B, int 
 hipError_t launch_conv3d_cl_wgrad(const float *dz2, const float *a1, int B, int D, int H, int W, float *dw, float *db, void *ws, hipStream_t st);
 hipError_t launch_conv3d_s7_train_forward(const float *vol, const float *w1, const float *bias, int B, int D, int H, int W, float *z1, void *ws,
                                           hipStream_t st);
+// dvol [B][D][H][W] = the data gradient of conv1 from dz1 [B][D][H][W][64]; ws holds the re-laid weights [343 taps][64] (87,808 B)
+hipError_t launch_conv3d_s7_dgrad(const float *dz1, const float *w1, int B, int D, int H, int W, float *dvol, void *ws, hipStream_t st);
 
 size_t bn_cl_workspace_bytes(long long M, int C);
 // phase: smk_bn_phase.  pooled = 0: out / dout are [M][C]; pooled = 1: out = token SUMS [B][1024][C], dout = token gradients [B][1024][C]

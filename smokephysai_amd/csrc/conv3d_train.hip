@@ -13,6 +13,8 @@
 //                           that k_c3t_prep_w2 writes in the same call (so an optimizer step needs no other notification).
 //   k_c3t_conv1             7 x 7 x 7 convolution 1 -> 64 of a scalar volume, same tiling: the 7 x 14 x 24 halo block in LDS, K = 49 window
 //                           rows x 8 kx slots (slot 7 carries zero weights).
+//   k_c3t_conv1_dgrad       the data gradient of conv1 (64 -> 1 with the flipped 7 x 7 x 7 kernel): Toeplitz in y, two output planes per
+//                           workgroup, one dz1 halo plane in LDS at a time (its own section below).
 //   k_c3t_wgrad             dW2[o][tap][c] = sum over voxels of dz2[voxel][o] a1[voxel + tap][c] with the VOXELS as the MFMA k dimension.
 //                           A workgroup owns 32 output channels x one kz slice (9 taps x 64 channels: 72 accumulator registers per lane) and
 //                           one of S voxel streams (tiles s, s + S, ...: a function of the shape alone); per tile the dz2 rows and the a1
@@ -172,6 +174,111 @@ __global__ __launch_bounds__(256) void k_c3t_conv1(const float *__restrict__ vol
         for (int i = 0; i < 4; ++i) dp[((size_t)(r0 + mt) * W + c0 + 4 * kg + i) * 64 + o] = acc[mt][i];
 }
 
+// ------------------------------------------------------------------------------------------------------------------ conv1 data gradient
+// dvol[z][y][x] = sum over c, kz, ky, kx of dz1[z + 3 - kz][y + 3 - ky][x + 3 - kx][c] w[c][kz][ky][kx] (out-of-volume terms zero): one output
+// channel, so a plain implicit GEMM would have N = 1.  The MFMA is filled instead with a Toeplitz operand in y and a pair of output planes:
+// a workgroup owns the 8 x 16 tile of the planes z0, z0 + 1 and marches over the eight dz1 planes zz = z0 - 3 .. z0 + 4 that reach them.  Per
+// staged plane (its 14 x 22 halo tile, 64 channels, in LDS) and per kx
+//     M = the 16 output columns x          A[x][(hr, c)]      = dz1[zz][halo row hr][halo column x + 6 - kx][c]
+//     N = 8 output rows r x 2 planes dp     B[(hr, c)][(r, dp)] = w[c][kz = z0 + dp + 3 - zz][ky = r + 6 - hr][kx], zero outside the kernel
+//     K = 14 halo rows x 64 channels
+// i.e. 8 x 7 x 14 x 16 = 12,544 MFMAs per 256 voxels, 2.3 x the counted FLOP (the zeros of B).  B is never stored expanded: a lane reads the one
+// weight row its (r, dp, hr) selects from the plane's two kz slices in LDS, or takes zero.  Wave w owns channels 16 w .. 16 w + 15 (lane group kg:
+// 16 w + 4 kg + s, MFMA s takes element s of one 16-byte read); the four waves' partial tiles are added in wave order through LDS.  Every plane's
+// products go to fresh accumulators (four, one per s: independent MFMA chains) that join the running sum once, as in k_c3t_conv.  No atomics;
+// every dvol element is written once; the order of every sum is fixed by the shape alone.
+constexpr int D1_ROWS = C3T_TH + 6, D1_COLS = C3T_TW + 6, D1_PIX = D1_ROWS * D1_COLS;        // halo tile 14 x 22 = 308 voxels
+constexpr int D1_WROWS = 2 * 49;                              // staged weight rows: [dp][ky * 7 + kx], 64 channels each
+constexpr int D1_SM_FLOATS = (D1_PIX + D1_WROWS) * C3T_VS;    // 110,432 B: one workgroup per CU
+
+__global__ void k_c3t_prep_w1_dgrad(const float *__restrict__ w1, float *__restrict__ wk) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;      // index into wk [343 taps][64]
+    if (i >= 343 * 64) return;
+    wk[i] = w1[(i & 63) * 343 + (i >> 6)];
+}
+
+__global__ __launch_bounds__(256) void k_c3t_conv1_dgrad(const float *__restrict__ dz1, const float *__restrict__ wk, float *__restrict__ dvol, int D,
+                                                         int H, int W, int tiles_x, int tiles_plane, int zpairs) {
+    __shared__ __attribute__((aligned(16))) float sm[D1_SM_FLOATS];
+    float *wl = sm + D1_PIX * C3T_VS;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, px = lane & 15, kg = lane >> 4;
+    const int t = blockIdx.x % tiles_plane, bz = blockIdx.x / tiles_plane, z0 = 2 * (bz % zpairs), b = bz / zpairs;
+    const int ty = t / tiles_x, tx = t - ty * tiles_x, r0 = ty * C3T_TH, c0 = tx * C3T_TW;
+    const int r = px & 7, dp = px >> 3, ch = 16 * wave + 4 * kg;
+    const size_t plane = (size_t)H * W;
+
+    // the planes that exist (block-uniform: a plane outside the volume adds nothing); plane p + 1 is loaded into registers under plane p's MFMAs
+    const int p_lo = z0 < 3 ? 3 - z0 : 0, p_hi = D + 2 - z0 < 7 ? D + 2 - z0 : 7;
+    constexpr int NA = (D1_PIX * 16 + 255) / 256, NW = (D1_WROWS * 16 + 255) / 256;
+    float4 pre[NA], wpre[NW];
+    auto fetch = [&](int p) {
+        const float *sp = dz1 + ((size_t)b * D + (z0 - 3 + p)) * plane * 64;
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+            const int idx = tid + 256 * i, q = idx & 15, v = idx >> 4, row = v / D1_COLS, col = v - row * D1_COLS;
+            const int yy = r0 - 3 + row, xx = c0 - 3 + col;
+            pre[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (v < D1_PIX && yy >= 0 && yy < H && xx >= 0 && xx < W) pre[i] = *reinterpret_cast<const float4 *>(sp + ((size_t)yy * W + xx) * 64 + 4 * q);
+        }
+#pragma unroll
+        for (int i = 0; i < NW; ++i) {                        // the two kz slices this plane carries: kz = 6 - p (plane z0), 7 - p (z0 + 1)
+            const int idx = tid + 256 * i, q = idx & 15, row = idx >> 4, kz = 6 - p + row / 49;
+            wpre[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (row < D1_WROWS && kz >= 0 && kz < 7) wpre[i] = *reinterpret_cast<const float4 *>(wk + ((size_t)kz * 49 + row % 49) * 64 + 4 * q);
+        }
+    };
+    c3t_f32x4 acc = c3t_f32x4{0.f, 0.f, 0.f, 0.f};
+    fetch(p_lo);
+    for (int p = p_lo; p <= p_hi; ++p) {
+        __syncthreads();                                      // the previous plane's readers are done
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+            const int idx = tid + 256 * i;
+            if (idx < D1_PIX * 16) *reinterpret_cast<float4 *>(sm + (idx >> 4) * C3T_VS + 4 * (idx & 15)) = pre[i];
+        }
+#pragma unroll
+        for (int i = 0; i < NW; ++i) {
+            const int idx = tid + 256 * i;
+            if (idx < D1_WROWS * 16) *reinterpret_cast<float4 *>(wl + (idx >> 4) * C3T_VS + 4 * (idx & 15)) = wpre[i];
+        }
+        __syncthreads();
+        if (p < p_hi) fetch(p + 1);                           // in flight until the next plane's LDS writes: no barrier in between
+        c3t_f32x4 part[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) part[s] = c3t_f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 2
+        for (int hr = 0; hr < D1_ROWS; ++hr) {
+            const int ky = r + 6 - hr;
+            const bool in = ky >= 0 && ky < 7;                // outside: this lane's B column is zero for the whole halo row
+            const float *ap = sm + (hr * D1_COLS + px + 6) * C3T_VS + ch;
+            const float *bp = wl + ((dp * 49 + (in ? ky : 0) * 7)) * C3T_VS + ch;
+#pragma unroll
+            for (int kx = 0; kx < 7; ++kx) {
+                const float4 a = *reinterpret_cast<const float4 *>(ap - kx * C3T_VS);
+                float4 w = *reinterpret_cast<const float4 *>(bp + kx * C3T_VS);
+                if (!in) w = make_float4(0.f, 0.f, 0.f, 0.f);
+                part[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w.x, part[0], 0, 0, 0);
+                part[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w.y, part[1], 0, 0, 0);
+                part[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, w.z, part[2], 0, 0, 0);
+                part[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, w.w, part[3], 0, 0, 0);
+            }
+        }
+        acc += (part[0] + part[1]) + (part[2] + part[3]);
+    }
+    __syncthreads();                                          // the last plane's readers are done: its space takes the four waves' tiles
+    *reinterpret_cast<float4 *>(sm + (wave * 64 + lane) * 4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    __syncthreads();
+    if (tid < 64 && z0 + dp < D) {                            // lane (px, kg) holds dvol[z0 + dp][r0 + r][c0 + 4 kg .. + 3]
+        float4 o = *reinterpret_cast<const float4 *>(sm + tid * 4);
+#pragma unroll
+        for (int wv = 1; wv < 4; ++wv) {
+            const float4 v = *reinterpret_cast<const float4 *>(sm + (wv * 64 + tid) * 4);
+            o.x += v.x; o.y += v.y; o.z += v.z; o.w += v.w;
+        }
+        *reinterpret_cast<float4 *>(dvol + ((size_t)b * D + z0 + dp) * plane + (size_t)(r0 + r) * W + c0 + 4 * kg) = o;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------------ weight gradient
 constexpr int WG_DZS = 48, WG_AS = 80;                        // floats per staged dz2 row (32 + 16) and a1 voxel (64 + 16): the four k groups of a read fall on disjoint banks
 constexpr int WG_PART = 128 * 27 * 64;                        // one stream's partial [o][tap][c]
@@ -309,6 +416,16 @@ hipError_t launch_conv3d_s7_train_forward(const float *vol, const float *w1, con
     hipLaunchKernelGGL(k_c3t_prep_w1, dim3((49 * 8 * 64 + 255) / 256), dim3(256), 0, st, w1, wk);
     const int tiles_x = W / C3T_TW, tiles_plane = tiles_x * (H / C3T_TH);
     hipLaunchKernelGGL(k_c3t_conv1, dim3((unsigned)((long long)B * D * tiles_plane)), dim3(256), 0, st, vol, wk, bias, z1, D, H, W, tiles_x, tiles_plane);
+    return hipGetLastError();
+}
+
+hipError_t launch_conv3d_s7_dgrad(const float *dz1, const float *w1, int B, int D, int H, int W, float *dvol, void *ws, hipStream_t st) {
+    if (!conv3d_train_shape_ok(B, D, H, W)) return hipErrorInvalidValue;
+    float *wk = static_cast<float *>(ws);
+    hipLaunchKernelGGL(k_c3t_prep_w1_dgrad, dim3((343 * 64 + 255) / 256), dim3(256), 0, st, w1, wk);
+    const int tiles_x = W / C3T_TW, tiles_plane = tiles_x * (H / C3T_TH), zpairs = (D + 1) / 2;
+    hipLaunchKernelGGL(k_c3t_conv1_dgrad, dim3((unsigned)((long long)B * zpairs * tiles_plane)), dim3(256), 0, st, dz1, wk, dvol, D, H, W, tiles_x,
+                       tiles_plane, zpairs);
     return hipGetLastError();
 }
 

@@ -11,9 +11,14 @@ Same methods, arguments, defaults and result keys; the work underneath is batche
   adversarial_test: the reference's PGD loop, with the gradient taken by torch.autograd.grad with respect to the perturbation
       only, the parameters' requires_grad switched off for the attack (and restored): no weight-gradient GEMMs run and no .grad
       is left on the model's parameters (the reference's loss.backward() accumulates them there).
+
+Volumes.  gaussian_noise_test takes what `model(x)` takes: on a SmokePhysNet3D, volumes [B, 1, D, H, W] run as they are (so does
+RobustnessEvaluator.evaluate_reconstruction_quality, given a 2-D target such as the rendered volume).  adversarial_test compares the 2-D
+reconstruction with the front view of the clean volume (SPEC_3D.md section 10) and perturbs the volume; with input_grad == "hip" the
+gradient reaches the volume through Encoder3D's 'frozen' route (smk_conv3d_s7_dgrad).  physics_perturbation_test is 2-D only.
 """
 import warnings
-from typing import Dict, List
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
@@ -77,12 +82,32 @@ class PerturbationTester:
             }
         return results
 
-    def adversarial_test(self, model: nn.Module, test_data: torch.Tensor, epsilon: float = 0.1, num_steps: int = 10) -> Dict:
+    def adversarial_test(self, model: nn.Module, test_data: torch.Tensor, epsilon: float = 0.1, num_steps: int = 10, *,
+                         target: Optional[torch.Tensor] = None) -> Dict:
         """PGD on the reconstruction error (perturbation_tests.py:54-98): {'adversarial_feature_stability',
         'adversarial_perturbation_norm'}.  The gradient is taken with respect to the perturbation only (module docstring): with every
         parameter frozen, a SmokePhysNet with input_grad == "hip" serves 128^2 / 256^2 frames on its libsmokehip route (forward and
-        backward; no MIOpen call), and anything else on the PyTorch modules."""
+        backward; no MIOpen call), a SmokePhysNet3D volumes of the training kernels' shapes, and anything else the PyTorch modules.
+        target: the image the reconstruction is compared with in the loss -mse(reconstructed, target).  Default: test_data itself for
+        frames [B, 1, H, W] (the reference's line); for volumes [B, 1, D, H, W] the front view of the clean volume,
+        render_volumes(test_data[:, 0])[:, None] with the default RenderSettings.  An image of another size than the reconstruction (the
+        head always emits 128 x 128) is brought there with F.adaptive_avg_pool2d, as train.py does with its targets."""
         model.eval()
+        if target is None:
+            target = test_data
+            if test_data.dim() == 5:
+                from ..physics.render import render_volumes
+                if test_data.shape[1] != 1:
+                    raise ValueError("adversarial_test: volumes must be [B, 1, D, H, W]")
+                target = render_volumes(test_data[:, 0].detach().float().contiguous())[:, None]
+        sized = {}                           # the comparison image at the reconstruction's size, made once
+
+        def compare_image(like):
+            if target.shape[-2:] == like.shape[-2:]:
+                return target
+            if "t" not in sized:
+                sized["t"] = F.adaptive_avg_pool2d(target, like.shape[-2:])
+            return sized["t"]
         delta = torch.zeros_like(test_data, requires_grad=True)
         params = [p for p in model.parameters() if p.requires_grad]
         warned = model.__dict__.get("_warned_grad")
@@ -95,7 +120,7 @@ class PerturbationTester:
                 for _ in range(num_steps):
                     with torch.enable_grad():
                         output = model(torch.clamp(test_data + delta, 0, 1))
-                        loss = -F.mse_loss(output['reconstructed'], test_data)      # maximise the reconstruction error
+                        loss = -F.mse_loss(output['reconstructed'], compare_image(output['reconstructed']))      # maximise the reconstruction error
                         (grad,) = torch.autograd.grad(loss, delta)
                     with torch.no_grad():
                         delta += epsilon / num_steps * torch.sign(grad)

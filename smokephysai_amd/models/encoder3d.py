@@ -17,6 +17,10 @@ Training (SPEC_3D.md section 11; csrc/conv3d_train.hip): `Encoder3D` is the nn.M
 Its autograd functions keep the activations channels-last [B, D, H, W, C] from the volume to the tokens: `hip_conv3d_s7_train` (conv1;
 weight gradient through the explicit patch matrix), `hip_conv3d_cl_train` (conv2: forward, data gradient and implicit weight gradient
 kernels) and `hip_bn3d_cl` (batch statistics + ReLU, for the second block fused with the token pooling).
+
+Input gradients: a volume that requires a gradient gets it from `hip_conv3d_s7_dgrad` (smk_conv3d_s7_dgrad).  In eval mode under autograd with
+every parameter frozen (PGD, saliency) `Encoder3D` takes its 'frozen' route: the same two convolutions with `hip_bn3d_cl_frozen` (BatchNorm3d
+from the running statistics, gradient to its input only); `hip_volume_input_grad_supported` is the route's pure predicate.
 """
 import torch
 import torch.nn.functional as F
@@ -190,8 +194,24 @@ def hip_conv3d_s7_wgrad(vol: torch.Tensor, dz1: torch.Tensor):
     return dw[:, :343].reshape(64, 1, 7, 7, 7).contiguous(), db
 
 
+def hip_conv3d_s7_dgrad(dz1: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """dvol [B, D, H, W] = the data gradient of conv1 from dz1 [B, D, H, W, 64] and the weight [64, 1, 7, 7, 7] (smk_conv3d_s7_dgrad:
+    F.conv_transpose3d with padding 3, on the fp32 MFMA; deterministic, no atomics)."""
+    L = _lib.load()
+    dev = _lib.require_cuda(dz1.device, "hip_conv3d_s7_dgrad")
+    if dz1.dim() != 5 or dz1.shape[-1] != 64 or tuple(weight.shape) != (64, 1, 7, 7, 7) or dz1.dtype != torch.float32 or weight.dtype != torch.float32:
+        raise ValueError("hip_conv3d_s7_dgrad: float32 dz1 [B, D, H, W, 64] and weight [64, 1, 7, 7, 7]")
+    B, D, H, W, _ = dz1.shape
+    dz1, weight = dz1.contiguous(), weight.detach().contiguous()
+    dvol = torch.empty(B, D, H, W, device=dev, dtype=torch.float32)
+    ws = _ws(L.smk_conv3d_train_workspace(), dev)
+    _lib.check(L.smk_conv3d_s7_dgrad(dz1.data_ptr(), weight.data_ptr(), B, D, H, W, dvol.data_ptr(), ws.data_ptr(), _lib.stream_ptr(dev)))
+    return dvol
+
+
 class _HipConv3dS7TrainFn(torch.autograd.Function):
-    """z1 [B, D, H, W, 64] = conv1(volumes [B, D, H, W]) + bias on smk_conv3d_s7_train_forward.  The volumes take no gradient."""
+    """z1 [B, D, H, W, 64] = conv1(volumes [B, D, H, W]) + bias on smk_conv3d_s7_train_forward; the volumes' gradient on smk_conv3d_s7_dgrad.
+    Only the gradients a call wants are computed (a PGD step does no weight-gradient work)."""
 
     @staticmethod
     def forward(ctx, vol, weight, bias):
@@ -204,14 +224,18 @@ class _HipConv3dS7TrainFn(torch.autograd.Function):
         ws = _ws(L.smk_conv3d_train_workspace(), dev)
         _lib.check(L.smk_conv3d_s7_train_forward(vol.data_ptr(), w.data_ptr(), b.data_ptr(), B, D, H, W, z1.data_ptr(), ws.data_ptr(),
                                                  _lib.stream_ptr(dev)))
-        ctx.save_for_backward(vol)
+        ctx.save_for_backward(vol, w)
         return z1
 
     @staticmethod
     def backward(ctx, dz1):
-        vol, = ctx.saved_tensors
-        dw, db = hip_conv3d_s7_wgrad(vol, dz1.contiguous())
-        return None, dw, db
+        vol, w = ctx.saved_tensors
+        dz1 = dz1.contiguous()
+        dvol = hip_conv3d_s7_dgrad(dz1, w) if ctx.needs_input_grad[0] else None
+        dw = db = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dw, db = hip_conv3d_s7_wgrad(vol, dz1)
+        return dvol, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None
 
 
 def hip_conv3d_cl_forward_raw(a1, weight, bias):
@@ -265,8 +289,10 @@ class _HipConv3dClTrainFn(torch.autograd.Function):
         a1, w = ctx.saved_tensors
         dz2 = dz2.contiguous()
         da1 = hip_conv3d_cl_dgrad(dz2, w) if ctx.needs_input_grad[0] else None
-        dw, db = hip_conv3d_cl_wgrad(dz2, a1)
-        return da1, dw, db
+        dw = db = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dw, db = hip_conv3d_cl_wgrad(dz2, a1)
+        return da1, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None
 
 
 def hip_conv3d_s7_train(vol: torch.Tensor, conv: nn.Conv3d) -> torch.Tensor:
@@ -352,6 +378,69 @@ def hip_bn3d_cl(z: torch.Tensor, bn: nn.BatchNorm3d, pooled: bool = False) -> to
     return out
 
 
+class _HipBn3dClFrozenFn(torch.autograd.Function):
+    """relu((z - mean) * rstd * gamma + beta) (pooled: its token means) with every per-channel tensor a constant: SMK_BN_APPLY forward,
+    SMK_BN_BWD_DZ with zero dgamma / dbeta and count 1 backward -- exactly dz = gamma * rstd * dy * [y > 0]."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, stats, pooled):
+        dev = _lib.require_cuda(z.device, "hip_bn3d_cl_frozen")
+        L = _lib.load()
+        z = z.contiguous()
+        B, D, H, W, C = z.shape
+        if pooled:
+            out = torch.empty(B, 1024, C, device=dev, dtype=torch.float32)
+            _bn_cl_phase(L, BN_APPLY, z, None, 1, gamma, beta, 0.0, stats, out, None, None, 0.0, None, dev)
+            out.mul_(1.0 / (D * (H // 32) * (W // 32)))
+        else:
+            out = torch.empty_like(z)
+            _bn_cl_phase(L, BN_APPLY, z, None, 0, gamma, beta, 0.0, stats, out, None, None, 0.0, None, dev)
+        ctx.save_for_backward(z, gamma, beta, stats)
+        ctx.pooled = pooled
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        z, gamma, beta, stats = ctx.saved_tensors
+        L = _lib.load()
+        dz = torch.empty_like(z)
+        zero = torch.zeros(2, z.shape[-1], device=z.device, dtype=torch.float32)
+        _bn_cl_phase(L, BN_BWD_DZ, z, dout.contiguous(), ctx.pooled, gamma, beta, 0.0, stats, None, dz, zero, 1.0, None, z.device)
+        return dz, None, None, None, None
+
+
+def _bn3d_frozen_ok(bn) -> bool:
+    """An eval-mode plain affine nn.BatchNorm3d with running statistics: what hip_bn3d_cl_frozen computes."""
+    return (type(bn) is nn.BatchNorm3d and not bn.training and bn.affine and bn.track_running_stats and bn.running_mean is not None
+            and bn.running_var is not None)
+
+
+def hip_bn3d_cl_frozen(z: torch.Tensor, bn: nn.BatchNorm3d, pooled: bool = False) -> torch.Tensor:
+    """relu(bn(z)) (pooled: its token means [B, 1024, C]) from bn's RUNNING statistics on channels-last z [B, D, H, W, C], differentiable
+    with respect to z only: gamma, beta and the statistics are constants, and nothing of bn is updated (SPEC_3D.md section 11)."""
+    if not _bn3d_frozen_ok(bn):
+        raise ValueError("hip_bn3d_cl_frozen: an eval-mode affine BatchNorm3d with running statistics")
+    if z.dim() != 5 or z.shape[-1] not in (64, 128) or z.shape[-1] != bn.num_features or z.dtype != torch.float32:
+        raise ValueError("hip_bn3d_cl_frozen: z must be float32 [B, D, H, W, C] with C = bn.num_features in (64, 128)")
+    if pooled and not (z.shape[2] % 32 == 0 and z.shape[3] % 32 == 0):
+        raise ValueError("hip_bn3d_cl_frozen: pooled needs H and W multiples of 32")
+    with torch.no_grad():
+        stats = torch.stack([bn.running_mean.float(), bn.running_var.float(), (bn.running_var.double() + bn.eps).rsqrt().float()]).contiguous()
+        gamma, beta = bn.weight.detach().float().contiguous(), bn.bias.detach().float().contiguous()
+    return _HipBn3dClFrozenFn.apply(z, gamma, beta, stats, bool(pooled))
+
+
+def hip_volume_input_grad_supported(B: int, D: int, H: int, W: int, *, eval_mode: bool = True, on_device: bool = True,
+                                    grad_enabled: bool = True, input_requires_grad: bool = True, params_require_grad: bool = False,
+                                    frozen_bn: bool = True) -> bool:
+    """Whether Encoder3D's 'frozen' route (eval mode, gradient with respect to the volumes only) serves a call.  Pure: no device, no library.
+    The volumes are the ones the training kernels take (pool_shape_ok, hip_conv3d_train_supported) as float32 on a ROCm device (on_device);
+    autograd is on, the volumes want a gradient and no parameter of the encoder does; both BatchNorms are eval-mode plain affine
+    BatchNorm3d with running statistics (frozen_bn)."""
+    shape = pool_shape_ok(H, W) and hip_conv3d_train_supported(int(B), int(D), int(H), int(W))
+    return bool(shape and eval_mode and on_device and grad_enabled and input_requires_grad and not params_require_grad and frozen_bn)
+
+
 class Encoder3D(nn.Module):
     """The trainable 3-D encoder (SPEC_3D.md section 11): Conv3d(1, 64, 7, padding 3) -> BatchNorm3d -> ReLU -> Conv3d(64, 128, 3, padding 1)
     -> BatchNorm3d -> ReLU -> block mean over D x H/32 x W/32 -> tokens [B, 1024, 128].  route: "hip" (libsmokehip wherever a call allows
@@ -387,9 +476,13 @@ class Encoder3D(nn.Module):
             self.__dict__["_hip_eval"] = cur
         return cur[0]
 
-    def _route(self, x: torch.Tensor) -> str:
-        """'train': training mode, fp32 volumes of a supported shape on a ROCm device -> the training kernels (batch statistics);
-        'eval': eval mode under no_grad on the device -> the folded HipEncoder3D; 'torch': everything else."""
+    def _route(self, x: torch.Tensor, input_grad: str = "hip") -> str:
+        """'train': training mode, fp32 volumes of a supported shape on a ROCm device -> the training kernels (batch statistics; a volume
+        that requires a gradient gets it from smk_conv3d_s7_dgrad);
+        'eval': eval mode under no_grad on the device -> the folded HipEncoder3D;
+        'frozen': eval mode, autograd on, a gradient wanted with respect to the volumes ONLY (every encoder parameter frozen) and
+        input_grad == "hip" -> the training convolutions with BatchNorm from the running statistics (hip_volume_input_grad_supported);
+        'torch': everything else."""
         B, D, H, W = x.shape
         c1, b1, _, c2, b2, _ = self.net
         if self.route != "hip" or not x.is_cuda or x.dtype != torch.float32 or c1.weight.dtype != torch.float32 or not pool_shape_ok(H, W):
@@ -398,10 +491,18 @@ class Encoder3D(nn.Module):
             ok = (_bn3d_hip_ok(b1) and _bn3d_hip_ok(b2) and b1.eps == b2.eps and hip_conv3d_train_supported(B, D, H, W)
                   and c1.bias is not None and c2.bias is not None)
             return "train" if ok else "torch"
-        return "eval" if not torch.is_grad_enabled() and b1.eps == b2.eps else "torch"
+        if not torch.is_grad_enabled():
+            return "eval" if b1.eps == b2.eps else "torch"
+        ok = (input_grad == "hip" and b1.eps == b2.eps and c1.bias is not None and c2.bias is not None
+              and hip_volume_input_grad_supported(B, D, H, W, eval_mode=True, on_device=True, grad_enabled=True,
+                                                  input_requires_grad=x.requires_grad,
+                                                  params_require_grad=any(p.requires_grad for p in self.parameters()),
+                                                  frozen_bn=_bn3d_frozen_ok(b1) and _bn3d_frozen_ok(b2)))
+        return "frozen" if ok else "torch"
 
-    def tokens(self, volumes: torch.Tensor) -> torch.Tensor:
-        """volumes [B, 1, D, H, W] or [B, D, H, W] -> tokens [B, 1024, 128]."""
+    def tokens(self, volumes: torch.Tensor, input_grad: str = "hip") -> torch.Tensor:
+        """volumes [B, 1, D, H, W] or [B, D, H, W] -> tokens [B, 1024, 128].  input_grad: "torch" keeps an eval-mode call under autograd on
+        the PyTorch modules (SmokePhysNet3D passes its own switch: the A/B partner of the 'frozen' route)."""
         x = volumes
         if x.dim() == 5:
             if x.shape[1] != 1:
@@ -409,11 +510,15 @@ class Encoder3D(nn.Module):
             x = x[:, 0]
         if x.dim() != 4:
             raise ValueError("volumes must be [B, 1, D, H, W] or [B, D, H, W]")
-        route = self._route(x)
+        route = self._route(x, input_grad)
         if route == "train":
             c1, b1, _, c2, b2, _ = self.net
             a1 = hip_bn3d_cl(hip_conv3d_s7_train(x, c1), b1)
             return hip_bn3d_cl(hip_conv3d_cl_train(a1, c2), b2, pooled=True)
+        if route == "frozen":                                  # d / d volumes with everything else a constant: no MIOpen call, no find pass
+            c1, b1, _, c2, b2, _ = self.net
+            a1 = hip_bn3d_cl_frozen(hip_conv3d_s7_train(x, c1), b1)
+            return hip_bn3d_cl_frozen(hip_conv3d_cl_train(a1, c2), b2, pooled=True)
         if route == "eval":
             return self.hip_eval_encoder().tokens(x)
         B, D, H, W = x.shape

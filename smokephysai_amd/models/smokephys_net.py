@@ -485,7 +485,8 @@ class SmokePhysNet3D(SmokePhysNet):
     forward takes volumes [B, 1, D, H, W] (through forward_volumes and self.encoder3d) or frames [B, 1, H, W] (the parent's route).  The 2-D
     input_encoder stays in the module -- the state dict is SmokePhysNet's keys plus encoder3d.*, so a 2-D checkpoint loads with strict=False --
     but its parameters are frozen: a volume step gives them no gradient, and DistributedDataParallel must not wait for one.
-    volume_encoder: Encoder3D's route, "hip" or "torch"."""
+    volume_encoder: Encoder3D's route, "hip" or "torch".  Input gradients (eval mode, autograd on, parameters frozen) follow input_grad as
+    for frames: "hip" (default) takes Encoder3D's 'frozen' route and the frozen head, "torch" the PyTorch modules."""
 
     def __init__(self, *args, volume_encoder: str = "hip", **kwargs):
         from .encoder3d import Encoder3D
@@ -497,7 +498,7 @@ class SmokePhysNet3D(SmokePhysNet):
     def forward(self, x: torch.Tensor, return_features: bool = False, chaos_noise: Optional[torch.Tensor] = None,
                 encoder_dtype: Optional[str] = None) -> dict:
         if x.dim() == 5:
-            return self.forward_volumes(x, self.encoder3d, return_features, chaos_noise)
+            return self.forward_tokens(self.encoder3d.tokens(x, input_grad=self.input_grad), return_features, chaos_noise)
         return super().forward(x, return_features, chaos_noise, encoder_dtype)
 
     def invalidate_hip_mirrors(self) -> None:
