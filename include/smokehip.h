@@ -289,6 +289,30 @@ int smk_volume_render(const float *vols, int64_t vol_stride, int32_t n, int32_t 
                       float *image, int64_t image_stride, float *transmittance, int64_t trans_stride, void *workspace,
                       int64_t workspace_bytes, void *stream);
 
+/* The gradient of smk_volume_render: given the upstream gradients G = grad_image and Gt = grad_trans of its two outputs ([H][W] planes
+ * `grad_image_stride` / `grad_trans_stride` floats apart; either may be NULL, which means zero; both NULL is SMK_ERR_INVALID), writes
+ * d(loss)/d(rho) for the same n volumes into grad_vols (dense [D][H][W] each, `grad_vol_stride` floats apart).  SPEC_3D.md section 10,
+ * "Gradient": with T = exp(-sigma_view tau), alpha and L as above, c = alpha L T,
+ *   drho[z,y,x] = gain G[y,x] sigma_view (exp(-sigma_view rho) L T - sum_{z' > z} c[z',y,x]) - sigma_view Gt[y,x] transmittance[y,x]
+ *                 + the sum of S = gain G alpha T (-sigma_light (1 - ambient) exp(-sigma_light A)) over the voxels this voxel shadows
+ *                   (+z: z' > z on the pixel's ray; +y: y' > y, -y: y' < y in the voxel's column of its plane, where G of other rows
+ *                   enters; none: nothing).
+ * A voxel with rho = 0 has a gradient (sigma_view (gain G - Gt) in an empty volume); negative densities follow the formula.  fp32, one
+ * fixed order per sum, no atomics: bit-identical from call to call, independent of the other volumes of the batch, and every element of
+ * grad_vols is written exactly once (no need to zero it).  Limits, the checks of desc and the status codes are smk_volume_render's; on
+ * any error grad_vols is untouched.  workspace: device memory of at least smk_volume_render_backward_workspace(n, D, H, W, light) bytes
+ * (0 for SMK_LIGHT_NONE / SMK_LIGHT_POS_Z: NULL is accepted then; three arrays [n][ceil(H/16)][D][W] and one [n][H][W] of floats for SMK_LIGHT_POS_Y /
+ * SMK_LIGHT_NEG_Y, whatever H; -1 for an unsupported shape or light), 4-byte aligned, passed with its size.  Caller-owned memory, the
+ * caller's stream, nothing allocated, no synchronisation.  The volumes are read once under SMK_LIGHT_NONE (one launch), twice under
+ * SMK_LIGHT_POS_Z (one launch) and three times under SMK_LIGHT_POS_Y / SMK_LIGHT_NEG_Y (five launches). */
+int64_t smk_volume_render_backward_workspace(int32_t n, int32_t D, int32_t H, int32_t W, int32_t light);
+int smk_volume_render_backward(const float *vols, int64_t vol_stride, int32_t n, int32_t D, int32_t H, int32_t W,
+                               const smk_render_desc *desc,
+                               const float *grad_image, int64_t grad_image_stride,      /* NULL: zero */
+                               const float *grad_trans, int64_t grad_trans_stride,      /* NULL: zero */
+                               float *grad_vols, int64_t grad_vol_stride,               /* dense [D][H][W] each */
+                               void *workspace, int64_t workspace_bytes, void *stream);
+
 /* RobustnessEvaluator.compute_ssim's SSIM map and F.mse_loss's squared error (robustness_metrics.py:76-103) for n fp32 planes [H][W]
  * (dense rows; plane strides pred_stride / target_stride floats), summed per plane in fp64 in a fixed order (bit-reproducible):
  * ssim_sum [n], sqerr_sum [n].  avg_pool2d(window, stride 1, padding window/2, count_include_pad) with zeros outside the plane;

@@ -14,6 +14,9 @@
 //   k_render_seg_scan   : exclusive scan of those totals over the segments, in place, in the order of travel     (workspace only)
 //   k_render_lit<DMAX>  : starts every plane's sum from its scanned total and marches the segment's rows         (read 2 of the volumes)
 // The workspace is [n][segments][D][W] floats = 1 / RENDER_SEG_ROWS of the volumes.  H <= RENDER_SEG_ROWS needs none (one segment).
+//
+// The gradient of both outputs with respect to the volumes (SPEC_3D.md section 10, "Gradient"; smk_volume_render_backward) is in the
+// second half of this file: the same two mappings, the same segment kernels, every element of the result written exactly once.
 #include "render.h"
 
 namespace smk {
@@ -226,6 +229,268 @@ hipError_t launch_volume_render(const float *vols, int64_t stride, int64_t n, in
     return hipGetLastError();
 }
 
+// ================================================================================================================================
+// The gradient.  With G / Gt the upstream gradients of image / transmittance (absent = zero), per voxel
+//   T = exp(-sv tau), X = exp(-sl A), L = a + (1 - a) X, alpha = -expm1(-sv rho), c = alpha L T, E = (1 - alpha) L T,
+//   S = g G alpha T (-sl (1 - a) X)                                        (what the voxel's image term gives back per unit of A)
+//   drho[z,y,x] = g G sv (E - sum_{z' > z} c) - sv Gt trans + sum of S over the voxels this voxel shadows.
+// Every suffix sum is formed as (total - inclusive prefix) in the forward's own direction, so tau and A are the forward's sums (a march
+// in reverse would have to subtract them down from their end values, and sl * A then carries the rounding of the END value into the
+// first, brightest voxels).  What a total costs is one rounding at the size of one term.  No wave skips a term here: rho = 0 has a
+// gradient.
+//   none : the first bracket telescopes to trans: drho = sv trans (g G - Gt) for every z.  k_render_grad_none, one read.
+//   +z   : k_render_grad_view, one pixel per lane: march 1 for the totals of c and S, march 2 writes.  Two reads, one launch.
+//   +-y  : k_render_seg_totals + k_render_seg_scan give A at every segment's start as in the forward (read 1);
+//          k_render_grad_lit<DMAX, false> marches every segment and writes its total of S per (z, x), and per pixel
+//          K = g G sv (sum_z c) + sv Gt trans, which every plane of the pixel subtracts and only the last plane completes (read 2);
+//          k_render_grad_seg_scan sums those totals over the segments AFTER each one in the order of travel (workspace only);
+//          k_render_grad_lit<DMAX, true> marches every segment again with, per plane, A and the S still to come in registers, and
+//          writes drho = g G sv (E + prefix of c) + S to come - K plane by plane (read 3).
+// Workspace of +-y: three arrays [n][segments][D][W] (A at the start, S totals, S of the later segments), also for a single segment, and
+// K [n][H][W].
+namespace {
+
+struct GradTerm {
+    float c, E, S;
+};
+
+__device__ __forceinline__ GradTerm grad_term(float rho, float A, float tau, float gG, const RenderParams &p) {
+    const float alpha = -expm1f(p.neg_sigma_view * rho);
+    const float T = __expf(p.neg_sigma_view * tau);
+    const float X = __expf(p.neg_sigma_light * A);
+    const float LT = (p.ambient + p.one_minus_ambient * X) * T;
+    GradTerm t;
+    t.c = alpha * LT;
+    t.E = (1.0f - alpha) * LT;
+    t.S = ((gG * alpha) * T) * ((p.neg_sigma_light * p.one_minus_ambient) * X);
+    return t;
+}
+
+// the upstream pair of one pixel: gain * G and Gt (a null pointer is a zero gradient)
+__device__ __forceinline__ void grad_upstream(const float *G, int64_t gstride, const float *Gt, int64_t tstride, int v, size_t pix, float gain,
+                                              float *gG, float *gt) {
+    *gG = G != nullptr ? gain * G[(size_t)v * gstride + pix] : 0.f;
+    *gt = Gt != nullptr ? Gt[(size_t)v * tstride + pix] : 0.f;
+}
+
+// ---- light none: one pixel per lane, one read
+__global__ __launch_bounds__(RV_NT) void k_render_grad_none(const float *__restrict__ vols, int64_t stride, int D, int HW, int bpv, RenderParams p,
+                                                            const float *__restrict__ G, int64_t gstride, const float *__restrict__ Gt,
+                                                            int64_t tstride, float *__restrict__ out, int64_t ostride) {
+    const int v = blockIdx.x / bpv, pix = (blockIdx.x % bpv) * RV_NT + threadIdx.x;
+    const bool ok = pix < HW;                                   // lanes past the plane read its last pixel and store nothing
+    const float *f = vols + (size_t)v * stride + (ok ? pix : HW - 1);
+    float tau = 0.f;
+    constexpr int U = 8;
+    for (int z0 = 0; z0 < D; z0 += U) {
+        float r[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) r[j] = z0 + j < D ? f[(size_t)(z0 + j) * HW] : 0.f;
+#pragma unroll
+        for (int j = 0; j < U; ++j)
+            if (z0 + j < D) tau += r[j];                        // the forward's order: the forward's transmittance
+    }
+    if (!ok) return;
+    float gG, gt;
+    grad_upstream(G, gstride, Gt, tstride, v, (size_t)pix, p.gain, &gG, &gt);
+    const float d = (-p.neg_sigma_view * __expf(p.neg_sigma_view * tau)) * (gG - gt);
+    float *o = out + (size_t)v * ostride + pix;
+    for (int z = 0; z < D; ++z) o[(size_t)z * HW] = d;          // z * HW + pix < D * H * W
+}
+
+// ---- light +z: one pixel per lane, A = tau; two marches over z
+__global__ __launch_bounds__(RV_NT) void k_render_grad_view(const float *__restrict__ vols, int64_t stride, int D, int HW, int bpv, RenderParams p,
+                                                            const float *__restrict__ G, int64_t gstride, const float *__restrict__ Gt,
+                                                            int64_t tstride, float *__restrict__ out, int64_t ostride) {
+    const int v = blockIdx.x / bpv, pix = (blockIdx.x % bpv) * RV_NT + threadIdx.x;
+    const bool ok = pix < HW;
+    const int pc = ok ? pix : HW - 1;                           // lanes past the plane work on its last pixel and store nothing
+    const float *f = vols + (size_t)v * stride + pc;
+    float gG, gt;
+    grad_upstream(G, gstride, Gt, tstride, v, (size_t)pc, p.gain, &gG, &gt);
+    const float sv = -p.neg_sigma_view, gs = gG * sv;
+    constexpr int U = 8;
+    float tau = 0.f, C = 0.f, St = 0.f;
+    for (int z0 = 0; z0 < D; z0 += U) {
+        float r[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) r[j] = z0 + j < D ? f[(size_t)(z0 + j) * HW] : 0.f;
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            if (z0 + j < D) {                                   // wave-uniform
+                const GradTerm t = grad_term(r[j], tau, tau, gG, p);
+                C += t.c;
+                St += t.S;
+                tau += r[j];
+            }
+        }
+    }
+    const float kt = (sv * gt) * __expf(p.neg_sigma_view * tau);
+    float *o = out + (size_t)v * ostride + pc;
+    float P = 0.f, Q = 0.f;
+    tau = 0.f;
+    for (int z0 = 0; z0 < D; z0 += U) {
+        float r[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) r[j] = z0 + j < D ? f[(size_t)(z0 + j) * HW] : 0.f;
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            if (z0 + j < D) {
+                const GradTerm t = grad_term(r[j], tau, tau, gG, p);       // the same bits as in march 1
+                P += t.c;
+                Q += t.S;
+                tau += r[j];
+                const float d = (gs * ((t.E + P) - C) - kt) + (St - Q);
+                if (ok) o[(size_t)(z0 + j) * HW] = d;
+            }
+        }
+    }
+}
+
+// ---- light +-y: sum of in[s'] over the segments s' after s in the order of travel (out of place: the totals are used again)
+__global__ __launch_bounds__(RV_NT) void k_render_grad_seg_scan(int DW, int nseg, int bpp, int up, const float *__restrict__ in,
+                                                                float *__restrict__ out) {
+    const int v = blockIdx.x / bpp, q = (blockIdx.x % bpp) * RV_NT + threadIdx.x;
+    if (q >= DW) return;
+    const size_t base = (size_t)v * nseg * DW + q;
+    float run = 0.f;
+#pragma unroll 4
+    for (int k = 0; k < nseg; ++k) {
+        const int s = up ? nseg - 1 - k : k;                   // against the order of travel
+        out[base + (size_t)s * DW] = run;
+        run += in[base + (size_t)s * DW];
+    }
+}
+
+// ---- light +-y: one wave = 64 columns x one segment, as k_render_lit.  FINAL = false: wsS[v][s][z][x] = the segment's sum of S.
+// and wsK[v][y][x] = K.  FINAL = true: drho of the segment's rows; Sl[z] is the S of everything the row's voxel shadows (the rows after
+// it in this segment and all later segments).
+template <int DMAX, bool FINAL>
+__global__ __launch_bounds__(64) void k_render_grad_lit(const float *__restrict__ vols, int64_t stride, int D, int H, int W, int nseg, int nxc,
+                                                        int up, RenderParams p, const float *__restrict__ wsA, float *wsS, const float *wsR,
+                                                        float *wsK, const float *__restrict__ G, int64_t gstride, const float *__restrict__ Gt,
+                                                        int64_t tstride, float *out, int64_t ostride) {
+    unsigned id = blockIdx.x;
+    const int xc = id % nxc; id /= nxc;
+    const int s = id % nseg, v = id / nseg;
+    const int x = xc * 64 + threadIdx.x;
+    const bool ok = x < W;
+    const int xl = ok ? (int)threadIdx.x : W - 1 - xc * 64;    // lanes past the row work on its last column and store nothing
+    const unsigned lane_b = 4u * (unsigned)xl;
+    const char *f = reinterpret_cast<const char *>(vols + (size_t)v * stride + xc * 64);
+    const size_t wofs = ((size_t)v * nseg + s) * D * W + xc * 64;          // + z * W + xl < n * nseg * D * W
+    float A[DMAX], Sl[DMAX];
+#pragma unroll
+    for (int z = 0; z < DMAX; ++z) {
+        A[z] = z < D ? wsA[wofs + (size_t)z * W + xl] : 0.f;
+        Sl[z] = (FINAL && z < D) ? wsS[wofs + (size_t)z * W + xl] + wsR[wofs + (size_t)z * W + xl] : 0.f;
+    }
+    const float sv = -p.neg_sigma_view;
+    int rows;
+    (void)seg_row(s, 0, H, up, &rows);
+    for (int i = 0; i < rows; ++i) {
+        int dummy;
+        const int y = seg_row(s, i, H, up, &dummy);
+        int Dr = D;
+        asm volatile("" : "+s"(Dr));                           // D again, opaque per row (k_render_lit)
+        float gG, gt;
+        grad_upstream(G, gstride, Gt, tstride, v, (size_t)y * W + xc * 64 + xl, p.gain, &gG, &gt);
+        const float gs = gG * sv;
+        const char *row = f + (size_t)y * W * 4;               // (z * H + y) * W + x < D * H * W
+        float tau = 0.f, P = 0.f;
+        const size_t kofs = (size_t)v * H * W + (size_t)y * W + xc * 64 + xl;      // < n * H * W
+        float K = 0.f;
+        if constexpr (FINAL) K = wsK[kofs];
+        float *o = out + (size_t)v * ostride + (size_t)y * W + x;
+        constexpr int RC = DMAX < 16 ? DMAX : 16;              // planes loaded ahead of their terms
+#pragma unroll
+        for (int z0 = 0; z0 < DMAX; z0 += RC) {
+            float r[RC];
+#pragma unroll
+            for (int j = 0; j < RC; ++j) {                     // planes past D load plane D - 1 again (never used)
+                r[j] = *reinterpret_cast<const float *>(row + lane_b);
+                row += z0 + j + 1 < Dr ? (size_t)H * W * 4 : 0;
+            }
+#pragma unroll
+            for (int j = 0; j < RC; ++j) {
+                if (z0 + j < Dr) {                             // wave-uniform
+                    const GradTerm t = grad_term(r[j], A[z0 + j], tau, gG, p);
+                    P += t.c;
+                    if constexpr (FINAL) {
+                        Sl[z0 + j] -= t.S;
+                        if (ok) o[(size_t)(z0 + j) * H * W] = (gs * (t.E + P) + Sl[z0 + j]) - K;
+                    } else {
+                        Sl[z0 + j] += t.S;
+                    }
+                    tau += r[j];
+                    A[z0 + j] += r[j];
+                }
+            }
+        }
+        if constexpr (!FINAL) {                                // what every plane of this pixel subtracts: known after the last plane only
+            if (ok) wsK[kofs] = gs * P + (sv * gt) * __expf(p.neg_sigma_view * tau);
+        }
+    }
+    if constexpr (!FINAL) {
+#pragma unroll
+        for (int z = 0; z < DMAX; ++z)
+            if (z < D && ok) wsS[wofs + (size_t)z * W + xl] = Sl[z];
+    }
+}
+
+}  // namespace
+
+int64_t render_backward_workspace(int64_t n, int D, int H, int W, int light) {
+    if (light != LIGHT_POS_Y && light != LIGHT_NEG_Y) return 0;
+    return (3 * n * render_segments(H) * (int64_t)D * W + n * (int64_t)H * W) * (int64_t)sizeof(float);
+}
+
+hipError_t launch_volume_render_backward(const float *vols, int64_t stride, int64_t n, int D, int H, int W, int light, const RenderParams &p,
+                                         const float *G, int64_t gstride, const float *Gt, int64_t tstride, float *out, int64_t ostride,
+                                         float *workspace, hipStream_t st) {
+    const int64_t HW = (int64_t)H * W, DW = (int64_t)D * W;
+    if (light == LIGHT_NONE || light == LIGHT_POS_Z) {
+        const int64_t bpv = (HW + RV_NT - 1) / RV_NT, grid = n * bpv;
+        if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
+        if (light == LIGHT_POS_Z)
+            hipLaunchKernelGGL(k_render_grad_view, dim3((unsigned)grid), dim3(RV_NT), 0, st, vols, stride, D, (int)HW, (int)bpv, p, G, gstride, Gt,
+                               tstride, out, ostride);
+        else
+            hipLaunchKernelGGL(k_render_grad_none, dim3((unsigned)grid), dim3(RV_NT), 0, st, vols, stride, D, (int)HW, (int)bpv, p, G, gstride, Gt,
+                               tstride, out, ostride);
+        return hipGetLastError();
+    }
+    const int up = light == LIGHT_POS_Y;
+    const int nseg = render_segments(H), nxc = (W + 63) / 64;
+    const int64_t bpp = (DW + RV_NT - 1) / RV_NT;
+    const int64_t g1 = n * nseg * bpp, g2 = n * bpp, g3 = n * nseg * nxc;
+    if (g1 > 0x7fffffffLL || g3 > 0x7fffffffLL) return hipErrorInvalidValue;
+    float *wsA = workspace, *wsS = wsA + n * nseg * DW, *wsR = wsS + n * nseg * DW, *wsK = wsR + n * nseg * DW;
+    hipError_t e;
+    hipLaunchKernelGGL(k_render_seg_totals, dim3((unsigned)g1), dim3(RV_NT), 0, st, vols, stride, D, H, W, nseg, (int)bpp, up, wsA);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_render_seg_scan, dim3((unsigned)g2), dim3(RV_NT), 0, st, (int)DW, nseg, (int)bpp, up, wsA);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+#define SMK_RENDER_GRAD_LIT(DMAX, FINAL)                                                                                                  \
+    hipLaunchKernelGGL((k_render_grad_lit<DMAX, FINAL>), dim3((unsigned)g3), dim3(64), 0, st, vols, stride, D, H, W, nseg, nxc, up, p, wsA, wsS, \
+                       wsR, wsK, G, gstride, Gt, tstride, out, ostride)
+#define SMK_RENDER_GRAD_PASS(FINAL)                                                                                                       \
+    do {                                                                                                                                  \
+        if (D <= 8) SMK_RENDER_GRAD_LIT(8, FINAL);                                                                                        \
+        else if (D <= 16) SMK_RENDER_GRAD_LIT(16, FINAL);                                                                                 \
+        else if (D <= 32) SMK_RENDER_GRAD_LIT(32, FINAL);                                                                                 \
+        else SMK_RENDER_GRAD_LIT(64, FINAL);                                                                                              \
+    } while (0)
+    SMK_RENDER_GRAD_PASS(false);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_render_grad_seg_scan, dim3((unsigned)g2), dim3(RV_NT), 0, st, (int)DW, nseg, (int)bpp, up, wsS, wsR);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    SMK_RENDER_GRAD_PASS(true);
+#undef SMK_RENDER_GRAD_PASS
+#undef SMK_RENDER_GRAD_LIT
+    return hipGetLastError();
+}
+
 }  // namespace smk
 
 using namespace smk;
@@ -276,6 +541,50 @@ int smk_volume_render(const float *vols, int64_t vol_stride, int32_t n, int32_t 
                                               trans_stride, (float *)workspace, (hipStream_t)stream);
     if (e != hipSuccess) {
         set_error(std::string("volume_render: ") + hipGetErrorString(e));
+        return SMK_ERR_HIP;
+    }
+    return SMK_OK;
+}
+
+int64_t smk_volume_render_backward_workspace(int32_t n, int32_t D, int32_t H, int32_t W, int32_t light) {
+    if (!render_shape_ok(n, D, H, W) || light < SMK_LIGHT_NONE || light > SMK_LIGHT_POS_Z) return -1;
+    return render_backward_workspace(n, D, H, W, light);
+}
+
+int smk_volume_render_backward(const float *vols, int64_t vol_stride, int32_t n, int32_t D, int32_t H, int32_t W, const smk_render_desc *desc,
+                               const float *grad_image, int64_t grad_image_stride, const float *grad_trans, int64_t grad_trans_stride,
+                               float *grad_vols, int64_t grad_vol_stride, void *workspace, int64_t workspace_bytes, void *stream) {
+    SMK_REQUIRE(vols && desc && grad_vols, "null pointer");
+    SMK_REQUIRE(grad_image || grad_trans, "grad_image and grad_trans are both null: there is no gradient to carry back");
+    SMK_REQUIRE(n >= 1 && D >= 1 && H >= 1 && W >= 1, "n, D, H, W >= 1");
+    if (!render_shape_ok(n, D, H, W)) {
+        set_error("volume_render_backward: D <= 64 and D*H*W <= 2^31 - 2^16 are built (got D=" + std::to_string(D) + ", H=" +
+                  std::to_string(H) + ", W=" + std::to_string(W) + ")");
+        return SMK_ERR_UNSUPPORTED;
+    }
+    SMK_REQUIRE(desc->light >= SMK_LIGHT_NONE && desc->light <= SMK_LIGHT_POS_Z, "light: one of smk_light");
+    SMK_REQUIRE(desc->sigma_view >= 0 && desc->sigma_light >= 0 && desc->ambient >= 0 && desc->ambient <= 1 && desc->gain > 0,
+                "sigma_view, sigma_light >= 0; 0 <= ambient <= 1; gain > 0");
+    const int64_t cells = (int64_t)D * H * W, HW = (int64_t)H * W;
+    SMK_REQUIRE(vol_stride >= cells || n == 1, "vol_stride >= D*H*W");
+    SMK_REQUIRE(grad_vol_stride >= cells || n == 1, "grad_vol_stride >= D*H*W");
+    SMK_REQUIRE(grad_image == nullptr || grad_image_stride >= HW || n == 1, "grad_image_stride >= H*W");
+    SMK_REQUIRE(grad_trans == nullptr || grad_trans_stride >= HW || n == 1, "grad_trans_stride >= H*W");
+    SMK_REQUIRE(((uintptr_t)vols & 3) == 0 && ((uintptr_t)grad_image & 3) == 0 && ((uintptr_t)grad_trans & 3) == 0 &&
+                    ((uintptr_t)grad_vols & 3) == 0 && ((uintptr_t)workspace & 3) == 0, "4-byte aligned pointers");
+    const int64_t need = render_backward_workspace(n, D, H, W, desc->light);
+    SMK_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need),
+                "workspace smaller than smk_volume_render_backward_workspace(n, D, H, W, light)");
+    RenderParams p;
+    p.neg_sigma_view = (float)-desc->sigma_view;
+    p.neg_sigma_light = (float)-desc->sigma_light;
+    p.ambient = (float)desc->ambient;
+    p.one_minus_ambient = (float)(1.0 - desc->ambient);
+    p.gain = (float)desc->gain;
+    const hipError_t e = launch_volume_render_backward(vols, vol_stride, n, D, H, W, desc->light, p, grad_image, grad_image_stride, grad_trans,
+                                                       grad_trans_stride, grad_vols, grad_vol_stride, (float *)workspace, (hipStream_t)stream);
+    if (e != hipSuccess) {
+        set_error(std::string("volume_render_backward: ") + hipGetErrorString(e));
         return SMK_ERR_HIP;
     }
     return SMK_OK;

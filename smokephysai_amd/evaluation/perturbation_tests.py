@@ -15,7 +15,9 @@ Same methods, arguments, defaults and result keys; the work underneath is batche
 Volumes.  gaussian_noise_test takes what `model(x)` takes: on a SmokePhysNet3D, volumes [B, 1, D, H, W] run as they are (so does
 RobustnessEvaluator.evaluate_reconstruction_quality, given a 2-D target such as the rendered volume).  adversarial_test compares the 2-D
 reconstruction with the front view of the clean volume (SPEC_3D.md section 10) and perturbs the volume; with input_grad == "hip" the
-gradient reaches the volume through Encoder3D's 'frozen' route (smk_conv3d_s7_dgrad).  physics_perturbation_test is 2-D only.
+gradient reaches the volume through Encoder3D's 'frozen' route (smk_conv3d_s7_dgrad).  With render=RenderSettings(...) the model is an
+IMAGE model that is shown the render of the perturbed volume: the perturbation lives on the smoke, the gradient reaches it through the
+render's backward (smk_volume_render_backward).  physics_perturbation_test is 2-D only.
 """
 import warnings
 from typing import Dict, List, Optional
@@ -83,7 +85,7 @@ class PerturbationTester:
         return results
 
     def adversarial_test(self, model: nn.Module, test_data: torch.Tensor, epsilon: float = 0.1, num_steps: int = 10, *,
-                         target: Optional[torch.Tensor] = None) -> Dict:
+                         target: Optional[torch.Tensor] = None, render=None) -> Dict:
         """PGD on the reconstruction error (perturbation_tests.py:54-98): {'adversarial_feature_stability',
         'adversarial_perturbation_norm'}.  The gradient is taken with respect to the perturbation only (module docstring): with every
         parameter frozen, a SmokePhysNet with input_grad == "hip" serves 128^2 / 256^2 frames on its libsmokehip route (forward and
@@ -91,9 +93,25 @@ class PerturbationTester:
         target: the image the reconstruction is compared with in the loss -mse(reconstructed, target).  Default: test_data itself for
         frames [B, 1, H, W] (the reference's line); for volumes [B, 1, D, H, W] the front view of the clean volume,
         render_volumes(test_data[:, 0])[:, None] with the default RenderSettings.  An image of another size than the reconstruction (the
-        head always emits 128 x 128) is brought there with F.adaptive_avg_pool2d, as train.py does with its targets."""
+        head always emits 128 x 128) is brought there with F.adaptive_avg_pool2d, as train.py does with its targets.
+        render: a RenderSettings; test_data is then volumes [B, 1, D, H, W] and `model` an image model, which sees
+        render_volumes(clamp(test_data + delta, 0, 1)[:, 0], render)[:, None] -- which change to the SMOKE changes the model's answer.  The
+        perturbation (and its norm) is the volume's; the default comparison image is the render of the clean volume under the same
+        settings; the closing forwards run on the rendered frames.  None: the code path without it."""
         model.eval()
-        if target is None:
+        shown = lambda x: x                  # noqa: E731  what the model sees of the (perturbed) data
+        if render is not None:
+            from ..physics.render import RenderSettings, render_volumes
+            if not isinstance(render, RenderSettings):
+                raise TypeError("adversarial_test: render must be a RenderSettings")
+            if test_data.dim() != 5 or test_data.shape[1] != 1:
+                raise ValueError("adversarial_test: with render=, test_data must be volumes [B, 1, D, H, W]")
+            test_data = test_data.detach().float().contiguous()
+            shown = lambda v: render_volumes(v[:, 0], render)[:, None]          # noqa: E731
+            if target is None:
+                with torch.no_grad():
+                    target = shown(test_data)
+        elif target is None:
             target = test_data
             if test_data.dim() == 5:
                 from ..physics.render import render_volumes
@@ -119,7 +137,7 @@ class PerturbationTester:
                 warnings.filterwarnings("ignore", message="SmokePhysNet: eval forward with autograd")
                 for _ in range(num_steps):
                     with torch.enable_grad():
-                        output = model(torch.clamp(test_data + delta, 0, 1))
+                        output = model(shown(torch.clamp(test_data + delta, 0, 1)))
                         loss = -F.mse_loss(output['reconstructed'], compare_image(output['reconstructed']))      # maximise the reconstruction error
                         (grad,) = torch.autograd.grad(loss, delta)
                     with torch.no_grad():
@@ -131,8 +149,8 @@ class PerturbationTester:
             if warned is None:
                 model.__dict__.pop("_warned_grad", None)        # a later, unintended autograd forward still gets its hint
         with torch.no_grad():
-            baseline = model(test_data)
-            adversarial_output = model(torch.clamp(test_data + delta, 0, 1))
+            baseline = model(shown(test_data))
+            adversarial_output = model(shown(torch.clamp(test_data + delta, 0, 1)))
             feature_stability = F.cosine_similarity(baseline['latent_features'], adversarial_output['latent_features'],
                                                     dim=1).mean().item()
         return {'adversarial_feature_stability': feature_stability,

@@ -2,7 +2,8 @@
 
 The camera looks along +z (plane 0 nearest); single scattering from one directional light.  No reference counterpart: the reference is
 2-D, and its frames are what this operator makes of a 3-D density field.  No CPU path: the numpy form of the rule is the test oracle
-(tests/render_oracle.py).
+(tests/render_oracle.py).  render_volumes is differentiable with respect to the volumes: smk_volume_render_backward, the closed-form
+transpose of the rule (section 10, "Gradient"; oracle: tests/render_grad_oracle.py).
 """
 import ctypes as C
 import math
@@ -95,12 +96,96 @@ def _runs(lead_shape, lead_stride, cells):
     return [(r[0], dims[-1][0], dims[-1][1]) for r in runs]
 
 
+def render_backward_workspace(n: int, shape, light: str, device) -> Optional[torch.Tensor]:
+    """The scratch buffer smk_volume_render_backward wants for n volumes of `shape` = (D, H, W) under `light` (None when it wants none:
+    "none" and "+z"); reusable across calls on one stream."""
+    if light not in LIGHTS:
+        raise ValueError(f"light={light!r}: one of {sorted(LIGHTS)}")
+    d, h, w = shape
+    if n < 1 or not render_supported(int(d), int(h), int(w)):
+        raise ValueError(f"render_volumes: n={n}, shape={tuple(shape)} is not supported (n >= 1, 1 <= D <= {MAX_DEPTH}, H, W >= 1, "
+                         f"at most 2^31 - 2^16 cells)")
+    nbytes = _lib.load().smk_volume_render_backward_workspace(n, d, h, w, LIGHTS[light])
+    if nbytes < 0:
+        raise ValueError(f"render_volumes: n={n}, shape={tuple(shape)}, light={light!r} is not supported")
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device) if nbytes else None
+
+
+def _render_backward(vols: torch.Tensor, settings: RenderSettings, grad_image, grad_trans) -> torch.Tensor:
+    """smk_volume_render_backward over the runs of `vols` (checked by render_volumes): the gradient in vols' shape, contiguous.
+    grad_image / grad_trans: the leading dimensions + [H, W], or None (= zero); not both None."""
+    dev = vols.device
+    D, H, W = (int(s) for s in vols.shape[-3:])
+    lead = tuple(vols.shape[:-3])
+    cells, HW = D * H * W, H * W
+    gi = None if grad_image is None else grad_image.to(torch.float32).contiguous()
+    gt = None if grad_trans is None else grad_trans.to(torch.float32).contiguous()
+    grad = torch.empty(lead + (D, H, W), dtype=torch.float32, device=dev)           # every element is written exactly once
+    runs = _runs(lead, vols.stride()[:-3], cells)
+    biggest = max(r[1] for r in runs)
+    L = _lib.load()
+    need = L.smk_volume_render_backward_workspace(biggest, D, H, W, LIGHTS[settings.light])
+    if need < 0:
+        raise ValueError(f"render_volumes: {biggest} volumes of {(D, H, W)} are not supported")
+    ws = torch.empty(need // 4, dtype=torch.float32, device=dev) if need else None
+    desc = settings.desc()
+    st = _lib.stream_ptr(dev)
+    base, gbase = vols.data_ptr(), grad.data_ptr()
+    ibase, tbase = (0 if gi is None else gi.data_ptr()), (0 if gt is None else gt.data_ptr())
+    done = 0
+    for off, count, stride in runs:
+        _lib.check(L.smk_volume_render_backward(base + 4 * off, stride if count > 1 else cells, count, D, H, W, C.byref(desc),
+                                                (ibase + 4 * done * HW) if gi is not None else None, HW,
+                                                (tbase + 4 * done * HW) if gt is not None else None, HW,
+                                                gbase + 4 * done * cells, cells, ws.data_ptr() if need else None, need, st))
+        done += count
+    return grad
+
+
+class _RenderVolumes(torch.autograd.Function):
+    """render_volumes with a backward: the forward is the plain call (the same values bit for bit), the backward is
+    smk_volume_render_backward on the saved volumes.  Differentiable once."""
+
+    @staticmethod
+    def forward(ctx, vols, settings, transmittance, workspace):
+        ctx.settings = settings
+        ctx.set_materialize_grads(False)           # an unused output's gradient arrives as None: the NULL of the entry point
+        ctx.save_for_backward(vols)
+        return _render(vols, settings, transmittance=transmittance, out=None, workspace=workspace)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_image, grad_trans=None):
+        (vols,) = ctx.saved_tensors
+        if grad_image is None and grad_trans is None:
+            return None, None, None, None
+        return _render_backward(vols, ctx.settings, grad_image, grad_trans), None, None, None
+
+
 def render_volumes(vols: torch.Tensor, settings: Optional[RenderSettings] = None, *, transmittance: bool = False,
                    out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
     """Render [D,H,W], [n,D,H,W] or [B,T,D,H,W] float32 volumes on the device.  The batch dimensions may have any non-negative strides;
     every volume must be dense.  Returns the image with the leading dimensions kept ([H,W], [n,H,W], [B,T,H,W]), or
     (image, transmittance).  out: a contiguous float32 tensor of the image's shape to write into.  workspace: render_workspace(...) of at
-    least this call's size, to reuse across calls."""
+    least this call's size, to reuse across calls.
+
+    Differentiable with respect to the volumes (SPEC_3D.md section 10, "Gradient"; smk_volume_render_backward): when autograd is on and
+    `vols.requires_grad`, the outputs carry a backward that takes the gradients of the image and, with transmittance=True, of the
+    transmittance, and returns a gradient of vols' shape.  `out=` raises ValueError then (an autograd output cannot be the caller's
+    buffer), and a second derivative is not supported (RuntimeError from autograd).  Every other call is the plain path."""
+    if torch.is_grad_enabled() and isinstance(vols, torch.Tensor) and vols.requires_grad:
+        if out is not None:
+            raise ValueError("render_volumes: out= cannot be used when the volumes require a gradient (an autograd output cannot be the "
+                             "caller's buffer); call under torch.no_grad() or detach the volumes")
+        settings = RenderSettings() if settings is None else settings
+        if not isinstance(settings, RenderSettings):
+            raise TypeError("render_volumes: settings must be a RenderSettings")
+        return _RenderVolumes.apply(vols, settings, bool(transmittance), workspace)
+    return _render(vols, settings, transmittance=transmittance, out=out, workspace=workspace)
+
+
+def _render(vols, settings, *, transmittance, out, workspace):
+    """The plain path of render_volumes (its checks and the calls of smk_volume_render)."""
     settings = RenderSettings() if settings is None else settings
     if not isinstance(settings, RenderSettings):
         raise TypeError("render_volumes: settings must be a RenderSettings")
