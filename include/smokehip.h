@@ -313,6 +313,31 @@ int smk_volume_render_backward(const float *vols, int64_t vol_stride, int32_t n,
                                float *grad_vols, int64_t grad_vol_stride,               /* dense [D][H][W] each */
                                void *workspace, int64_t workspace_bytes, void *stream);
 
+/* Orbit views of the same n volumes: an orthographic camera turned about the vertical axis y (SPEC_3D.md section 10, "Orbit views").
+ * azimuths: n * n_views doubles in HOST memory, degrees, volume-major (view k of volume v at [v * n_views + k]); positive turns the
+ * viewing direction from +z toward +x.  (cos, sin) are formed on the host: r = remainder(azimuth, 360); a multiple of 90 gives exactly
+ * (1,0), (0,1), (-1,0) or (0,-1), anything else cos / sin of r * pi / 180 in double; both cast to fp32 once.  Image row y is the volume's
+ * row y and the image has the volume's W columns.  With S the smallest integer >= hypot(D, W) of D's parity, c_z = (D-1)/2,
+ * c_x = (W-1)/2, a = x' - c_x and t = s - (S-1)/2 for s in [0, S):
+ *   x = c_x + (a cos + t sin),  z = c_z + (t cos - a sin)                                                      (fp32, one rounding per operation)
+ *   rho_s[s,y,x'] = (1-fz) ((1-fx) v00 + fx v01) + fz ((1-fx) v10 + fx v11), the bilinear interpolation of rho[.,y,.] at (z, x) with
+ *                   z0 = floor(z), fz = z - z0, x0 = floor(x), fx = x - x0; a neighbour outside the volume counts as 0
+ * and smk_volume_render's rule runs over rho_s with s in the role of z (sample 0 nearest the camera).  A[s,y,x'] is the same
+ * interpolation of the voxel-grid prefix along y (equal to the prefix of the samples: the interpolation is linear).  Lights:
+ * SMK_LIGHT_NONE, SMK_LIGHT_POS_Y, SMK_LIGHT_NEG_Y; SMK_LIGHT_POS_Z returns SMK_ERR_UNSUPPORTED.  Plane v * n_views + k of image /
+ * transmittance (planes `image_stride` / `trans_stride` floats apart, >= H*W; transmittance may be NULL) is view k of volume v.  fp32,
+ * every sum in one fixed order, no atomics: bit-identical from call to call, and a plane depends on its own volume and azimuth only.
+ * Limits: 1 <= D <= 64, H >= 1, 1 <= W <= 1024, D*H*W <= 2^31 - 2^16 (else SMK_ERR_UNSUPPORTED); n * n_views <= 2^20, finite azimuths
+ * and smk_volume_render's checks of desc (else SMK_ERR_INVALID).  workspace: device memory of at least
+ * smk_volume_render_orbit_workspace(n, D, H, W, light) bytes (0 for SMK_LIGHT_NONE: NULL is accepted then; n*D*H*W floats, the prefix
+ * along y, for SMK_LIGHT_POS_Y / SMK_LIGHT_NEG_Y; -1 for an unsupported shape or light), 4-byte aligned, passed with its size.
+ * Caller-owned memory, the caller's stream, nothing allocated on the device, no synchronisation; on any error the outputs are
+ * untouched.  One launch per 16 planes, plus one for the prefix. */
+int64_t smk_volume_render_orbit_workspace(int32_t n, int32_t D, int32_t H, int32_t W, int32_t light);
+int smk_volume_render_orbit(const float *vols, int64_t vol_stride, int32_t n, int32_t D, int32_t H, int32_t W, const smk_render_desc *desc,
+                            const double *azimuths, int32_t n_views, float *image, int64_t image_stride, float *transmittance,
+                            int64_t trans_stride, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* RobustnessEvaluator.compute_ssim's SSIM map and F.mse_loss's squared error (robustness_metrics.py:76-103) for n fp32 planes [H][W]
  * (dense rows; plane strides pred_stride / target_stride floats), summed per plane in fp64 in a fixed order (bit-reproducible):
  * ssim_sum [n], sqerr_sum [n].  avg_pool2d(window, stride 1, padding window/2, count_include_pad) with zeros outside the plane;

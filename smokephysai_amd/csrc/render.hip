@@ -28,20 +28,6 @@ constexpr int SEG = RENDER_SEG_ROWS;
 
 enum { LIGHT_NONE = 0, LIGHT_POS_Y = 1, LIGHT_NEG_Y = 2, LIGHT_POS_Z = 3 };
 
-// Smoke volumes are mostly empty (the stepper's are 99.9 % zeros after 20 steps).  A voxel with rho == 0 adds (0 * L) * T = 0 exactly as
-// long as L and T are finite, which A >= 0 and tau >= 0 guarantee (both factors are then in [0, 1]); with negative or NaN sums behind it the
-// term is formed as written.  A wave whose 64 voxels are all of that kind skips the term: same bits, no exp.
-__device__ __forceinline__ bool wave_has_term(float rho, float A, float tau) {
-    return __builtin_amdgcn_ballot_w64(!(rho == 0.f && A >= 0.f && tau >= 0.f)) != 0;
-}
-
-// one term of the image sum
-__device__ __forceinline__ float render_term(float rho, float A, float tau, const RenderParams &p, bool lit) {
-    const float alpha = -expm1f(p.neg_sigma_view * rho);
-    const float L = lit ? p.ambient + p.one_minus_ambient * __expf(p.neg_sigma_light * A) : 1.0f;
-    return (alpha * L) * __expf(p.neg_sigma_view * tau);
-}
-
 // ---- light none / +z: one pixel per lane, nothing shared
 template <bool LIT_Z>
 __global__ __launch_bounds__(RV_NT) void k_render_view(const float *__restrict__ vols, int64_t stride, int D, int HW, int bpv, RenderParams p,

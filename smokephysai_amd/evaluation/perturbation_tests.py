@@ -17,7 +17,9 @@ RobustnessEvaluator.evaluate_reconstruction_quality, given a 2-D target such as 
 reconstruction with the front view of the clean volume (SPEC_3D.md section 10) and perturbs the volume; with input_grad == "hip" the
 gradient reaches the volume through Encoder3D's 'frozen' route (smk_conv3d_s7_dgrad).  With render=RenderSettings(...) the model is an
 IMAGE model that is shown the render of the perturbed volume: the perturbation lives on the smoke, the gradient reaches it through the
-render's backward (smk_volume_render_backward).  physics_perturbation_test is 2-D only.
+render's backward (smk_volume_render_backward).  viewpoint_test shows an IMAGE model the same volumes from a ring of camera azimuths
+(physics.render_orbit, SPEC_3D.md section 10 "Orbit views") and reports how far its physics features move with the viewpoint.
+physics_perturbation_test is 2-D only.
 """
 import warnings
 from typing import Dict, List, Optional
@@ -83,6 +85,36 @@ class PerturbationTester:
                 'reconstruction_mse': F.mse_loss(rec, base_rec).item(),
             }
         return results
+
+    def viewpoint_test(self, model: nn.Module, volumes: torch.Tensor, azimuths=tuple(range(0, 360, 30)), *, settings=None,
+                       batch_size: int = 64) -> Dict:
+        """Does the model's answer depend on where the camera stood?  model: an image model; volumes: [B, 1, D, H, W].  Every volume is
+        rendered from every azimuth (degrees) by ONE render_orbit call, and the B x V frames go through the model in chunks of
+        `batch_size` (eval, no_grad).  Returns
+          'viewpoint_feature_stability': the mean over the further views and the volumes of the cosine similarity between the
+              physics_features of that view and of the first view (as gaussian_noise_test forms its feature_stability; 1.0 with one view),
+          'viewpoint_feature_variance': the variance of physics_features over the views (population), averaged over volumes and features,
+          'per_azimuth': {azimuth in degrees: that view's stability against the first; 1.0 for the first itself},
+          'num_views': V."""
+        from ..physics import render_orbit
+        if volumes.dim() != 5 or volumes.shape[1] != 1:
+            raise ValueError(f"viewpoint_test: volumes [B, 1, D, H, W], got {tuple(volumes.shape)}")
+        angles = [float(a) for a in azimuths]
+        if not angles:
+            raise ValueError("viewpoint_test: at least one azimuth")
+        model.eval()
+        B, V = volumes.shape[0], len(angles)
+        with torch.no_grad():
+            frames = render_orbit(volumes[:, 0].detach(), angles, settings)                  # [B, V, H, W]
+        H, W = frames.shape[-2:]
+        feats = _chunked_forward(model, frames.view(B * V, 1, H, W), batch_size, ('physics_features',))['physics_features'].view(B, V, -1)
+        further = [F.cosine_similarity(feats[:, 0], feats[:, k], dim=1).mean().item() for k in range(1, V)]
+        return {
+            'viewpoint_feature_stability': float(np.mean(further)) if further else 1.0,
+            'viewpoint_feature_variance': feats.var(dim=1, unbiased=False).mean().item(),
+            'per_azimuth': dict(zip(angles, [1.0] + further)),
+            'num_views': V,
+        }
 
     def adversarial_test(self, model: nn.Module, test_data: torch.Tensor, epsilon: float = 0.1, num_steps: int = 10, *,
                          target: Optional[torch.Tensor] = None, render=None) -> Dict:

@@ -4,6 +4,9 @@ The camera looks along +z (plane 0 nearest); single scattering from one directio
 2-D, and its frames are what this operator makes of a 3-D density field.  No CPU path: the numpy form of the rule is the test oracle
 (tests/render_oracle.py).  render_volumes is differentiable with respect to the volumes: smk_volume_render_backward, the closed-form
 transpose of the rule (section 10, "Gradient"; oracle: tests/render_grad_oracle.py).
+
+render_orbit turns that camera about the vertical axis y (section 10, "Orbit views"; csrc/render_orbit.hip, smk_volume_render_orbit;
+oracle: tests/render_orbit_oracle.py): any azimuth, several views per call, forward only.
 """
 import ctypes as C
 import math
@@ -226,5 +229,133 @@ def _render(vols, settings, *, transmittance, out, workspace):
         _lib.check(L.smk_volume_render(base + 4 * off, stride if count > 1 else cells, count, D, H, W, C.byref(desc),
                                        obase + 4 * done * HW, HW, (tbase + 4 * done * HW) if transmittance else None, HW,
                                        workspace.data_ptr() if need else None, workspace.numel() * workspace.element_size() if need else 0, st))
+        done += count
+    return (out, trans) if transmittance else out
+
+
+# ---- orbit views (SPEC_3D.md section 10, "Orbit views"; csrc/render_orbit.hip, smk_volume_render_orbit) ------------------------------
+ORBIT_MAX_WIDTH = 1024     # csrc/orbit_plan.h ORBIT_MAX_WIDTH
+ORBIT_LIGHTS = ("none", "+y", "-y")
+
+
+def orbit_supported(D: int, H: int, W: int) -> bool:
+    """Whether smk_volume_render_orbit takes volumes of this shape: 1 <= D <= 64, H >= 1, 1 <= W <= 1024, D*H*W <= 2^31 - 2^16."""
+    for v in (D, H, W):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise TypeError(f"orbit_supported: integer extents, got {v!r}")
+    return 1 <= D <= MAX_DEPTH and H >= 1 and 1 <= W <= ORBIT_MAX_WIDTH and D * H * W <= MAX_CELLS
+
+
+def orbit_samples(D: int, W: int) -> int:
+    """S, the samples on a ray of an orbit view: the smallest integer >= hypot(D, W) with the parity of D (csrc/orbit_plan.h)."""
+    if D < 1 or W < 1:
+        raise ValueError(f"orbit_samples: D, W >= 1, got {(D, W)}")
+    q = D * D + W * W
+    s = math.isqrt(q)
+    s += s * s < q
+    return s + ((s - D) & 1)
+
+
+def orbit_workspace(n: int, shape, light: str, device) -> Optional[torch.Tensor]:
+    """The scratch buffer smk_volume_render_orbit wants for n volumes of `shape` = (D, H, W) under `light` (None when it wants none:
+    "none"; the prefix along y, n*D*H*W floats, under "+y" / "-y"); the same for any number of views; reusable on one stream."""
+    if light not in ORBIT_LIGHTS:
+        raise ValueError(f"render_orbit: light={light!r}: one of {list(ORBIT_LIGHTS)} (a world-fixed '+z' light is not built for orbit views)")
+    d, h, w = (int(s) for s in shape)
+    if n < 1 or not orbit_supported(d, h, w):
+        raise ValueError(f"render_orbit: n={n}, shape={tuple(shape)} is not supported (n >= 1, 1 <= D <= {MAX_DEPTH}, H >= 1, "
+                         f"1 <= W <= {ORBIT_MAX_WIDTH}, at most 2^31 - 2^16 cells)")
+    nbytes = _lib.load().smk_volume_render_orbit_workspace(n, d, h, w, LIGHTS[light])
+    if nbytes < 0:
+        raise ValueError(f"render_orbit: n={n}, shape={tuple(shape)}, light={light!r} is not supported")
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device) if nbytes else None
+
+
+def _azimuths(azimuth, n: int):
+    """azimuth in one of its three forms -> ([n][V] doubles on the host as a float64 tensor, whether the result has a view dimension)."""
+    if isinstance(azimuth, bool):
+        raise ValueError("render_orbit: azimuth is a number of degrees, a sequence of them or an [n, V] array")
+    try:
+        t = azimuth.detach().to("cpu", torch.float64) if isinstance(azimuth, torch.Tensor) else torch.as_tensor(azimuth, dtype=torch.float64)
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise ValueError(f"render_orbit: azimuth is a number of degrees, a sequence of them or an [n, V] array ({e})") from None
+    if t.dim() == 0:
+        table, views = t.reshape(1, 1).expand(n, 1), False
+    elif t.dim() == 1 and t.numel() >= 1:
+        table, views = t.reshape(1, -1).expand(n, t.numel()), True
+    elif t.dim() == 2 and t.shape[0] == n and t.shape[1] >= 1:
+        table, views = t, True
+    else:
+        raise ValueError(f"render_orbit: azimuth of shape {tuple(t.shape)}: a number, a sequence of V >= 1 numbers or an [n={n}, V] array")
+    if not bool(torch.isfinite(table).all()):
+        raise ValueError("render_orbit: azimuths must be finite numbers of degrees")
+    return table.contiguous(), views
+
+
+def render_orbit(vols: torch.Tensor, azimuth, settings: Optional[RenderSettings] = None, *, transmittance: bool = False,
+                 out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """Render [n,D,H,W] or [D,H,W] float32 volumes from an orthographic camera that orbits the vertical axis y (SPEC_3D.md section 10,
+    "Orbit views").  azimuth, in degrees (0: the front view of render_volumes; positive turns the viewing direction from +z toward +x):
+      a number                  -> [n,H,W]    ([H,W] for one [D,H,W] volume)
+      a sequence of V numbers   -> [n,V,H,W]  ([V,H,W]), the same views of every volume
+      an [n,V] array or tensor  -> [n,V,H,W], one list per volume
+    Returns the image, or (image, transmittance).  The batch may have any non-negative stride; every volume must be dense.  Lights:
+    "none", "+y", "-y" ("+z" raises ValueError).  out: a contiguous float32 tensor of the image's shape to write into.  workspace:
+    orbit_workspace(...) of at least this call's size.  One call renders all the views.  There is no backward yet: volumes that require a
+    gradient raise RuntimeError (call under torch.no_grad() or detach them)."""
+    settings = RenderSettings() if settings is None else settings
+    if not isinstance(settings, RenderSettings):
+        raise TypeError("render_orbit: settings must be a RenderSettings")
+    if settings.light not in ORBIT_LIGHTS:
+        raise ValueError(f"render_orbit: light={settings.light!r} is not built for orbit views (a world-fixed +z light seen obliquely is "
+                         f"another prefix); one of {list(ORBIT_LIGHTS)}")
+    if not isinstance(vols, torch.Tensor) or vols.dim() not in (3, 4) or vols.dtype != torch.float32:
+        raise ValueError("render_orbit: float32 [D,H,W] or [n,D,H,W]")
+    D, H, W = (int(s) for s in vols.shape[-3:])
+    lead = tuple(vols.shape[:-3])
+    n = math.prod(lead)
+    if n < 1:
+        raise ValueError(f"render_orbit: shape {tuple(vols.shape)}: at least one volume")
+    table, views = _azimuths(azimuth, n)
+    V = int(table.shape[1])
+    if torch.is_grad_enabled() and vols.requires_grad:
+        raise RuntimeError("render_orbit: the orbit render has no backward yet, and the volumes require a gradient; call under "
+                           "torch.no_grad() or detach them (render_volumes, the front view, is differentiable)")
+    dev = _lib.require_cuda(vols.device, "render_orbit")
+    if not orbit_supported(D, H, W):
+        raise ValueError(f"render_orbit: shape {tuple(vols.shape)} is not supported (1 <= D <= {MAX_DEPTH}, H >= 1, 1 <= W <= {ORBIT_MAX_WIDTH}, "
+                         f"at most 2^31 - 2^16 cells per volume)")
+    if not _dense(vols):
+        raise ValueError("render_orbit: every volume must be dense ([D][H][W] with strides (H*W, W, 1)); only the batch may be strided")
+    if any(st < 0 for st in vols.stride()[:-3]):
+        raise ValueError("render_orbit: negative batch strides")
+    shape = lead + ((V,) if views else ()) + (H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"render_orbit: out must be a contiguous float32 tensor of shape {shape} on {dev}")
+    trans = torch.empty(shape, dtype=torch.float32, device=dev) if transmittance else None
+    cells, HW = D * H * W, H * W
+    runs = _runs(lead, vols.stride()[:-3], cells)
+    biggest = max(r[1] for r in runs)
+    L = _lib.load()
+    need = L.smk_volume_render_orbit_workspace(biggest, D, H, W, LIGHTS[settings.light])
+    if need < 0:
+        raise ValueError(f"render_orbit: {biggest} volumes of {(D, H, W)} are not supported")
+    if need and workspace is None:
+        workspace = torch.empty(need // 4, dtype=torch.float32, device=dev)
+    if need and (workspace.device != dev or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need):
+        raise ValueError(f"render_orbit: workspace of {need} bytes needed on {dev} (orbit_workspace)")
+    desc = settings.desc()
+    st = _lib.stream_ptr(dev)
+    base, obase, tbase = vols.data_ptr(), out.data_ptr(), trans.data_ptr() if transmittance else 0
+    flat = table.reshape(-1).tolist()
+    done = 0
+    for off, count, stride in runs:
+        az = (C.c_double * (count * V))(*flat[done * V:(done + count) * V])
+        _lib.check(L.smk_volume_render_orbit(base + 4 * off, stride if count > 1 else cells, count, D, H, W, C.byref(desc), az, V,
+                                             obase + 4 * done * V * HW, HW, (tbase + 4 * done * V * HW) if transmittance else None, HW,
+                                             workspace.data_ptr() if need else None, workspace.numel() * workspace.element_size() if need else 0,
+                                             st))
         done += count
     return (out, trans) if transmittance else out

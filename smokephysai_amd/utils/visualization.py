@@ -1,5 +1,5 @@
 """Figures of the reference's src/utils/visualization.py (SmokeVisualizer: the same three methods and argument names), drawn with
-matplotlib alone.  The attention panel takes what SmokePhysNet.attention_maps returns: the full [B, heads, L, L] weights as in the
+matplotlib alone, and plot_turntable, a row of orbit views of one volume (physics.render_orbit), which the reference has no like of.  The attention panel takes what SmokePhysNet.attention_maps returns: the full [B, heads, L, L] weights as in the
 reference, or the `received` map [B, heads, h, w] the libsmokehip kernels produce without ever forming an L x L tensor.
 Without a display the Agg backend is used; plt.show() is called only on an interactive backend."""
 import math
@@ -108,4 +108,24 @@ class SmokeVisualizer:
             ax.set_title("Average Attention")
             ax.axis("off")
             fig.colorbar(im, ax=ax)
+        return _finish(fig, save_path)
+
+    def plot_turntable(self, frames, azimuths, save_path: Optional[str] = None):
+        """One 'hot' panel per orbit view (render_orbit's [V, H, W] frames of one volume), at most 8 per row, titled by the view's azimuth in
+        degrees; all panels share one colour scale, so a view that sees less smoke looks dimmer.  Returns the figure."""
+        views = _numpy(frames)
+        angles = [float(a) for a in _numpy(azimuths).reshape(-1)]
+        if views.ndim != 3 or len(angles) != views.shape[0] or not angles:
+            raise ValueError(f"plot_turntable: frames [V, H, W] and V azimuths, got {views.shape} and {len(angles)}")
+        n = len(angles)
+        cols = min(8, n)
+        rows = (n + cols - 1) // cols
+        fig, axes = plt.subplots(rows, cols, figsize=(cols * 2, rows * 2), squeeze=False)
+        for ax in axes.flat:
+            ax.axis("off")
+        top = max(float(views.max()), 1e-12)
+        for i, (view, angle) in enumerate(zip(views, angles)):
+            ax = axes[i // cols, i % cols]
+            ax.imshow(view, cmap="hot", interpolation="bilinear", vmin=0.0, vmax=top)
+            ax.set_title(f"{angle:g}\N{DEGREE SIGN}")
         return _finish(fig, save_path)
