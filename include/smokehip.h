@@ -338,6 +338,34 @@ int smk_volume_render_orbit(const float *vols, int64_t vol_stride, int32_t n, in
                             const double *azimuths, int32_t n_views, float *image, int64_t image_stride, float *transmittance,
                             int64_t trans_stride, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* Free-camera views of the same n volumes: the orthographic camera of smk_volume_render_orbit with an elevation as well (SPEC_3D.md
+ * section 10, "Free camera").  azimuths, elevations: n * n_views doubles each in HOST memory, degrees, volume-major (view k of volume v
+ * at [v * n_views + k]); the azimuth is the orbit's, a positive elevation in [-90, 90] raises the camera toward larger y (it looks down).
+ * (c, s) = (cos, sin) of the azimuth by the orbit's rule, cast to fp32 and read back; (ce, se) of the elevation are exactly (1,0), (0,1),
+ * (0,-1) at 0, 90, -90 and cos / sin of radians in double otherwise; the coefficients are formed in double and cast to fp32 once:
+ *   right r = (c, 0, -s),  up e = (s se, ce, c se) (increasing image row),  view d = (s ce, -se, c ce)            in (x, y, z)
+ * The image has the volume's H rows and W columns.  With S the smallest integer >= sqrt(D^2 + H^2 + W^2) of D's parity, c_z = (D-1)/2,
+ * c_y = (H-1)/2, c_x = (W-1)/2, a = x' - c_x, b = y' - c_y and t = s - (S-1)/2 for s in [0, S):
+ *   x = c_x + ((a r_x + b e_x) + t d_x),  y = c_y + (b e_y + t d_y),  z = c_z + ((a r_z + b e_z) + t d_z)  (fp32, one rounding per operation)
+ *   rho_s[s,y',x'] = (1-fz) P(z0) + fz P(z0+1),  P(k) = (1-fy) ((1-fx) v[k,y0,x0] + fx v[k,y0,x0+1]) + fy ((1-fx) v[k,y0+1,x0] + fx v[k,y0+1,x0+1]),
+ *                    i0 = floor, f = position - i0 per axis; a tap outside the volume counts as 0
+ * and smk_volume_render's rule runs over rho_s with s in the role of z (sample 0 nearest the camera).  A[s,y',x'] is the same
+ * interpolation of the voxel-grid exclusive prefix along y (with pitch this is the definition, not a prefix of the samples).  At
+ * elevation 0 the samples are the orbit's, on a longer ray: the images agree to the fringe samples the orbit's ray drops, not bit for bit.
+ * Lights: SMK_LIGHT_NONE, SMK_LIGHT_POS_Y, SMK_LIGHT_NEG_Y; SMK_LIGHT_POS_Z returns SMK_ERR_UNSUPPORTED.  Plane v * n_views + k of
+ * image / transmittance (planes `image_stride` / `trans_stride` floats apart, >= H*W; transmittance may be NULL) is view k of volume v.
+ * fp32, every sum in one fixed order, no atomics: bit-identical from call to call, and a plane depends on its own volume, azimuth and
+ * elevation only.  Limits: 1 <= D <= 64, 1 <= H <= 65536 (the image row enters the fp32 positions), 1 <= W <= 1024,
+ * D*H*W <= 2^31 - 2^16 (else SMK_ERR_UNSUPPORTED); n * n_views <= 2^20, finite angles, |elevation| <= 90 and smk_volume_render's checks
+ * of desc (else SMK_ERR_INVALID).  workspace: as smk_volume_render_orbit's, sized by smk_volume_render_camera_workspace(n, D, H, W, light)
+ * (0 for SMK_LIGHT_NONE; n*D*H*W floats for SMK_LIGHT_POS_Y / SMK_LIGHT_NEG_Y; -1 for an unsupported shape or light).  Caller-owned
+ * memory, the caller's stream, nothing allocated on the device, no synchronisation; on any error the outputs are untouched.  One launch
+ * per 16 planes, plus one for the prefix. */
+int64_t smk_volume_render_camera_workspace(int32_t n, int32_t D, int32_t H, int32_t W, int32_t light);
+int smk_volume_render_camera(const float *vols, int64_t vol_stride, int32_t n, int32_t D, int32_t H, int32_t W, const smk_render_desc *desc,
+                             const double *azimuths, const double *elevations, int32_t n_views, float *image, int64_t image_stride,
+                             float *transmittance, int64_t trans_stride, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* RobustnessEvaluator.compute_ssim's SSIM map and F.mse_loss's squared error (robustness_metrics.py:76-103) for n fp32 planes [H][W]
  * (dense rows; plane strides pred_stride / target_stride floats), summed per plane in fp64 in a fixed order (bit-reproducible):
  * ssim_sum [n], sqerr_sum [n].  avg_pool2d(window, stride 1, padding window/2, count_include_pad) with zeros outside the plane;

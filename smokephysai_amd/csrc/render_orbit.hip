@@ -164,6 +164,13 @@ int64_t render_orbit_workspace(int64_t n, int D, int H, int W, int light) {
     return n * (int64_t)D * H * W * (int64_t)sizeof(float);
 }
 
+hipError_t launch_orbit_prefix(const float *vols, int64_t stride, int64_t n, int D, int H, int W, bool up, float *workspace, hipStream_t st) {
+    const int64_t bpp = ((int64_t)D * W + OP_NT - 1) / OP_NT, grid = n * bpp;
+    if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_orbit_prefix, dim3((unsigned)grid), dim3(OP_NT), 0, st, vols, stride, D, H, W, (int)bpp, up ? 1 : 0, workspace);
+    return hipGetLastError();
+}
+
 hipError_t launch_volume_render_orbit(const float *vols, int64_t stride, int64_t n, int D, int H, int W, int light, const RenderParams &p,
                                       const float *cs, int n_views, float *image, int64_t image_stride, float *trans, int64_t trans_stride,
                                       float *workspace, hipStream_t st) {
@@ -172,13 +179,7 @@ hipError_t launch_volume_render_orbit(const float *vols, int64_t stride, int64_t
     const int64_t pairs = n * n_views, per_pair = (int64_t)nstrips * nyg;
     if (per_pair * ORBIT_VIEWS_PER_LAUNCH > 0x7fffffffLL || pairs > 0x7fffffffLL) return hipErrorInvalidValue;
     hipError_t e;
-    if (lit) {
-        const int64_t bpp = ((int64_t)D * W + OP_NT - 1) / OP_NT, grid = n * bpp;
-        if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(k_orbit_prefix, dim3((unsigned)grid), dim3(OP_NT), 0, st, vols, stride, D, H, W, (int)bpp, light == LIGHT_POS_Y ? 1 : 0,
-                           workspace);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
+    if (lit && (e = launch_orbit_prefix(vols, stride, n, D, H, W, light == LIGHT_POS_Y, workspace, st)) != hipSuccess) return e;
     for (int64_t p0 = 0; p0 < pairs; p0 += ORBIT_VIEWS_PER_LAUNCH) {
         const int np = (int)(pairs - p0 < ORBIT_VIEWS_PER_LAUNCH ? pairs - p0 : ORBIT_VIEWS_PER_LAUNCH);
         OrbitViews views = {};

@@ -18,9 +18,11 @@ reconstruction with the front view of the clean volume (SPEC_3D.md section 10) a
 gradient reaches the volume through Encoder3D's 'frozen' route (smk_conv3d_s7_dgrad).  With render=RenderSettings(...) the model is an
 IMAGE model that is shown the render of the perturbed volume: the perturbation lives on the smoke, the gradient reaches it through the
 render's backward (smk_volume_render_backward).  viewpoint_test shows an IMAGE model the same volumes from a ring of camera azimuths
-(physics.render_orbit, SPEC_3D.md section 10 "Orbit views") and reports how far its physics features move with the viewpoint.
+(physics.render_orbit, SPEC_3D.md section 10 "Orbit views") and reports how far its physics features move with the viewpoint; with
+elevation=... the ring is seen from above or below (physics.render_camera, "Free camera").
 physics_perturbation_test is 2-D only.
 """
+import numbers
 import warnings
 from typing import Dict, List, Optional
 
@@ -87,7 +89,7 @@ class PerturbationTester:
         return results
 
     def viewpoint_test(self, model: nn.Module, volumes: torch.Tensor, azimuths=tuple(range(0, 360, 30)), *, settings=None,
-                       batch_size: int = 64) -> Dict:
+                       batch_size: int = 64, elevation=None) -> Dict:
         """Does the model's answer depend on where the camera stood?  model: an image model; volumes: [B, 1, D, H, W].  Every volume is
         rendered from every azimuth (degrees) by ONE render_orbit call, and the B x V frames go through the model in chunks of
         `batch_size` (eval, no_grad).  Returns
@@ -95,8 +97,11 @@ class PerturbationTester:
               physics_features of that view and of the first view (as gaussian_noise_test forms its feature_stability; 1.0 with one view),
           'viewpoint_feature_variance': the variance of physics_features over the views (population), averaged over volumes and features,
           'per_azimuth': {azimuth in degrees: that view's stability against the first; 1.0 for the first itself},
-          'num_views': V."""
-        from ..physics import render_orbit
+          'num_views': V.
+        elevation: None renders the horizontal ring with render_orbit.  A number of degrees in [-90, 90] renders the same ring of
+        azimuths from that elevation (positive: looking down on the smoke) with ONE render_camera call, and the result carries
+        'elevation' as well."""
+        from ..physics import render_camera, render_orbit
         if volumes.dim() != 5 or volumes.shape[1] != 1:
             raise ValueError(f"viewpoint_test: volumes [B, 1, D, H, W], got {tuple(volumes.shape)}")
         angles = [float(a) for a in azimuths]
@@ -104,17 +109,27 @@ class PerturbationTester:
             raise ValueError("viewpoint_test: at least one azimuth")
         model.eval()
         B, V = volumes.shape[0], len(angles)
+        if elevation is not None:
+            if isinstance(elevation, bool) or not isinstance(elevation, numbers.Real):
+                raise ValueError(f"viewpoint_test: elevation is None or a number of degrees, got {elevation!r}")
+            elevation = float(elevation)
         with torch.no_grad():
-            frames = render_orbit(volumes[:, 0].detach(), angles, settings)                  # [B, V, H, W]
+            if elevation is None:
+                frames = render_orbit(volumes[:, 0].detach(), angles, settings)              # [B, V, H, W]
+            else:
+                frames = render_camera(volumes[:, 0].detach(), angles, elevation, settings)  # [B, V, H, W]
         H, W = frames.shape[-2:]
         feats = _chunked_forward(model, frames.view(B * V, 1, H, W), batch_size, ('physics_features',))['physics_features'].view(B, V, -1)
         further = [F.cosine_similarity(feats[:, 0], feats[:, k], dim=1).mean().item() for k in range(1, V)]
-        return {
+        result = {
             'viewpoint_feature_stability': float(np.mean(further)) if further else 1.0,
             'viewpoint_feature_variance': feats.var(dim=1, unbiased=False).mean().item(),
             'per_azimuth': dict(zip(angles, [1.0] + further)),
             'num_views': V,
         }
+        if elevation is not None:
+            result['elevation'] = elevation
+        return result
 
     def adversarial_test(self, model: nn.Module, test_data: torch.Tensor, epsilon: float = 0.1, num_steps: int = 10, *,
                          target: Optional[torch.Tensor] = None, render=None) -> Dict:

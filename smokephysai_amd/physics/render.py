@@ -7,6 +7,9 @@ transpose of the rule (section 10, "Gradient"; oracle: tests/render_grad_oracle.
 
 render_orbit turns that camera about the vertical axis y (section 10, "Orbit views"; csrc/render_orbit.hip, smk_volume_render_orbit;
 oracle: tests/render_orbit_oracle.py): any azimuth, several views per call, forward only.
+
+render_camera adds an elevation to that camera (section 10, "Free camera"; csrc/render_camera.hip, smk_volume_render_camera; oracle:
+tests/render_camera_oracle.py): azimuth and elevation paired view by view, trilinear samples, forward only.
 """
 import ctypes as C
 import math
@@ -357,5 +360,150 @@ def render_orbit(vols: torch.Tensor, azimuth, settings: Optional[RenderSettings]
                                              obase + 4 * done * V * HW, HW, (tbase + 4 * done * V * HW) if transmittance else None, HW,
                                              workspace.data_ptr() if need else None, workspace.numel() * workspace.element_size() if need else 0,
                                              st))
+        done += count
+    return (out, trans) if transmittance else out
+
+
+# ---- free camera (SPEC_3D.md section 10, "Free camera"; csrc/render_camera.hip, smk_volume_render_camera) -----------------------------
+CAMERA_MAX_WIDTH = 1024    # csrc/camera_plan.h CAMERA_MAX_WIDTH
+CAMERA_MAX_HEIGHT = 65536  # csrc/camera_plan.h CAMERA_MAX_HEIGHT: the image row enters the fp32 positions
+CAMERA_LIGHTS = ORBIT_LIGHTS
+
+
+def camera_supported(D: int, H: int, W: int) -> bool:
+    """Whether smk_volume_render_camera takes volumes of this shape: 1 <= D <= 64, 1 <= H <= 65536, 1 <= W <= 1024,
+    D*H*W <= 2^31 - 2^16."""
+    for v in (D, H, W):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise TypeError(f"camera_supported: integer extents, got {v!r}")
+    return 1 <= D <= MAX_DEPTH and 1 <= H <= CAMERA_MAX_HEIGHT and 1 <= W <= CAMERA_MAX_WIDTH and D * H * W <= MAX_CELLS
+
+
+def camera_samples(D: int, H: int, W: int) -> int:
+    """S, the samples on a ray of a free-camera view: the smallest integer >= sqrt(D^2 + H^2 + W^2) with the parity of D
+    (csrc/camera_plan.h)."""
+    if D < 1 or H < 1 or W < 1:
+        raise ValueError(f"camera_samples: D, H, W >= 1, got {(D, H, W)}")
+    q = D * D + H * H + W * W
+    s = math.isqrt(q)
+    s += s * s < q
+    return s + ((s - D) & 1)
+
+
+def camera_workspace(n: int, shape, light: str, device) -> Optional[torch.Tensor]:
+    """The scratch buffer smk_volume_render_camera wants for n volumes of `shape` = (D, H, W) under `light` (None when it wants none:
+    "none"; the prefix along y, n*D*H*W floats, under "+y" / "-y"); the same for any number of views; reusable on one stream."""
+    if light not in CAMERA_LIGHTS:
+        raise ValueError(f"render_camera: light={light!r}: one of {list(CAMERA_LIGHTS)} (a world-fixed '+z' light is not built for a "
+                         f"moving camera)")
+    d, h, w = (int(s) for s in shape)
+    if n < 1 or not camera_supported(d, h, w):
+        raise ValueError(f"render_camera: n={n}, shape={tuple(shape)} is not supported (n >= 1, 1 <= D <= {MAX_DEPTH}, "
+                         f"1 <= H <= {CAMERA_MAX_HEIGHT}, 1 <= W <= {CAMERA_MAX_WIDTH}, at most 2^31 - 2^16 cells)")
+    nbytes = _lib.load().smk_volume_render_camera_workspace(n, d, h, w, LIGHTS[light])
+    if nbytes < 0:
+        raise ValueError(f"render_camera: n={n}, shape={tuple(shape)}, light={light!r} is not supported")
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device) if nbytes else None
+
+
+def _angle(value, n: int, name: str):
+    """One angle argument in one of its three forms -> a float64 host tensor of 0, 1 ([V]) or 2 ([n, V]) dimensions."""
+    forms = f"render_camera: {name} is a number of degrees, a sequence of them or an [n, V] array"
+    if isinstance(value, bool):
+        raise ValueError(forms)
+    try:
+        t = value.detach().to("cpu", torch.float64) if isinstance(value, torch.Tensor) else torch.as_tensor(value, dtype=torch.float64)
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise ValueError(f"{forms} ({e})") from None
+    if not (t.dim() == 0 or (t.dim() == 1 and t.numel() >= 1) or (t.dim() == 2 and t.shape[0] == n and t.shape[1] >= 1)):
+        raise ValueError(f"render_camera: {name} of shape {tuple(t.shape)}: a number, a sequence of V >= 1 numbers or an [n={n}, V] array")
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError(f"render_camera: {name}s must be finite numbers of degrees")
+    return t
+
+
+def _camera_angles(azimuth, elevation, n: int):
+    """The two angle arguments, paired -> ([n][V] azimuths, [n][V] elevations as float64 host tensors, whether the result has a view
+    dimension)."""
+    az, el = _angle(azimuth, n, "azimuth"), _angle(elevation, n, "elevation")
+    if bool(((el < -90.0) | (el > 90.0)).any()):
+        raise ValueError("render_camera: elevations must lie in [-90, 90] degrees")
+    counts = {int(t.shape[-1]) for t in (az, el) if t.dim() > 0}
+    if len(counts) > 1:
+        raise ValueError(f"render_camera: azimuth and elevation are paired view by view: {tuple(az.shape)} against {tuple(el.shape)}")
+    V = counts.pop() if counts else 1
+    tables = [(t.reshape(1, -1) if t.dim() < 2 else t).expand(n, V).contiguous() for t in (az, el)]
+    return tables[0], tables[1], az.dim() > 0 or el.dim() > 0
+
+
+def render_camera(vols: torch.Tensor, azimuth, elevation, settings: Optional[RenderSettings] = None, *, transmittance: bool = False,
+                  out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """Render [n,D,H,W] or [D,H,W] float32 volumes from an orthographic camera with an azimuth and an elevation (SPEC_3D.md section 10,
+    "Free camera").  azimuth: render_orbit's, in degrees.  elevation, in degrees in [-90, 90]: positive raises the camera toward larger
+    y, so that it looks down on the smoke (90: the top view).  Each of the two is
+      a number                  the same for every view
+      a sequence of V numbers   the same views of every volume
+      an [n,V] array or tensor  one list per volume
+    and they are paired view by view (two sequences have the same V), not multiplied out.  The result is [n,H,W] ([H,W] for one [D,H,W]
+    volume) when both are numbers and [n,V,H,W] ([V,H,W]) otherwise.  Returns the image, or (image, transmittance).  The batch may have
+    any non-negative stride; every volume must be dense.  Lights: "none", "+y", "-y", fixed to the world ("+z" raises ValueError).  out: a
+    contiguous float32 tensor of the image's shape to write into.  workspace: camera_workspace(...) of at least this call's size.  One
+    call renders all the views.  elevation=0 is the orbit's view on a longer ray: close to render_orbit's image, not equal to it.  There is
+    no backward yet: volumes that require a gradient raise RuntimeError (call under torch.no_grad() or detach them)."""
+    settings = RenderSettings() if settings is None else settings
+    if not isinstance(settings, RenderSettings):
+        raise TypeError("render_camera: settings must be a RenderSettings")
+    if settings.light not in CAMERA_LIGHTS:
+        raise ValueError(f"render_camera: light={settings.light!r} is not built for a moving camera (a world-fixed +z light seen obliquely "
+                         f"is another prefix); one of {list(CAMERA_LIGHTS)}")
+    if not isinstance(vols, torch.Tensor) or vols.dim() not in (3, 4) or vols.dtype != torch.float32:
+        raise ValueError("render_camera: float32 [D,H,W] or [n,D,H,W]")
+    D, H, W = (int(s) for s in vols.shape[-3:])
+    lead = tuple(vols.shape[:-3])
+    n = math.prod(lead)
+    if n < 1:
+        raise ValueError(f"render_camera: shape {tuple(vols.shape)}: at least one volume")
+    az_table, el_table, views = _camera_angles(azimuth, elevation, n)
+    V = int(az_table.shape[1])
+    if torch.is_grad_enabled() and vols.requires_grad:
+        raise RuntimeError("render_camera: the free-camera render has no backward yet, and the volumes require a gradient; call under "
+                           "torch.no_grad() or detach them (render_volumes, the front view, is differentiable)")
+    dev = _lib.require_cuda(vols.device, "render_camera")
+    if not camera_supported(D, H, W):
+        raise ValueError(f"render_camera: shape {tuple(vols.shape)} is not supported (1 <= D <= {MAX_DEPTH}, 1 <= H <= {CAMERA_MAX_HEIGHT}, "
+                         f"1 <= W <= {CAMERA_MAX_WIDTH}, at most 2^31 - 2^16 cells per volume)")
+    if not _dense(vols):
+        raise ValueError("render_camera: every volume must be dense ([D][H][W] with strides (H*W, W, 1)); only the batch may be strided")
+    if any(st < 0 for st in vols.stride()[:-3]):
+        raise ValueError("render_camera: negative batch strides")
+    shape = lead + ((V,) if views else ()) + (H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"render_camera: out must be a contiguous float32 tensor of shape {shape} on {dev}")
+    trans = torch.empty(shape, dtype=torch.float32, device=dev) if transmittance else None
+    cells, HW = D * H * W, H * W
+    runs = _runs(lead, vols.stride()[:-3], cells)
+    biggest = max(r[1] for r in runs)
+    L = _lib.load()
+    need = L.smk_volume_render_camera_workspace(biggest, D, H, W, LIGHTS[settings.light])
+    if need < 0:
+        raise ValueError(f"render_camera: {biggest} volumes of {(D, H, W)} are not supported")
+    if need and workspace is None:
+        workspace = torch.empty(need // 4, dtype=torch.float32, device=dev)
+    if need and (workspace.device != dev or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need):
+        raise ValueError(f"render_camera: workspace of {need} bytes needed on {dev} (camera_workspace)")
+    desc = settings.desc()
+    st = _lib.stream_ptr(dev)
+    base, obase, tbase = vols.data_ptr(), out.data_ptr(), trans.data_ptr() if transmittance else 0
+    flat_az, flat_el = az_table.reshape(-1).tolist(), el_table.reshape(-1).tolist()
+    done = 0
+    for off, count, stride in runs:
+        az = (C.c_double * (count * V))(*flat_az[done * V:(done + count) * V])
+        el = (C.c_double * (count * V))(*flat_el[done * V:(done + count) * V])
+        _lib.check(L.smk_volume_render_camera(base + 4 * off, stride if count > 1 else cells, count, D, H, W, C.byref(desc), az, el, V,
+                                              obase + 4 * done * V * HW, HW, (tbase + 4 * done * V * HW) if transmittance else None, HW,
+                                              workspace.data_ptr() if need else None,
+                                              workspace.numel() * workspace.element_size() if need else 0, st))
         done += count
     return (out, trans) if transmittance else out

@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from .navier_stokes3d import NavierStokesSimulator3D
-from .render import RenderSettings, render_orbit, render_volumes, render_workspace
+from .render import RenderSettings, render_camera, render_orbit, render_volumes, render_workspace
 from .smoke_simulator import (chaos_features_device, entropy_from_hist, fractal_dimension_from_counts, lyapunov_from_norms, volume_stats,
                               volume_stats_workspace)
 
@@ -101,6 +101,17 @@ class SmokeSimulator3D(nn.Module):
         if self.history_len == 0:
             raise RuntimeError("render_orbit: no volume has been emitted yet (call simulate_step first)")
         res = render_orbit(self._pair[:, self._slot], azimuth, settings, transmittance=transmittance)
+        if self.batch_size is not None:
+            return res
+        return (res[0][0], res[1][0]) if transmittance else res[0]
+
+    def render_camera(self, azimuth, elevation, settings: Optional[RenderSettings] = None, transmittance: bool = False):
+        """The newest emitted volume(s) seen from a camera with an azimuth and an elevation (physics.render_camera; degrees, each a number,
+        a sequence of V numbers, or [B, V], paired view by view): [B,H,W] or [B,V,H,W] batched, [H,W] or [V,H,W] un-batched, or (image,
+        transmittance).  Reads the simulator's own copy of that volume; changes no state."""
+        if self.history_len == 0:
+            raise RuntimeError("render_camera: no volume has been emitted yet (call simulate_step first)")
+        res = render_camera(self._pair[:, self._slot], azimuth, elevation, settings, transmittance=transmittance)
         if self.batch_size is not None:
             return res
         return (res[0][0], res[1][0]) if transmittance else res[0]
