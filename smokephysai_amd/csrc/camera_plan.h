@@ -11,14 +11,9 @@
 // Every position is formed in fp32 by camera_sample_x / _y / _z and nowhere else.  Each is monotone in a, in b and in t with the other two
 // fixed (every operation rounds monotonically), so over a brick of (a, b, t) the extremes are at its eight corners: no margin is needed.
 #pragma once
-#include <math.h>
 #include <stdint.h>
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define CAMERA_HD __host__ __device__ inline
-#else
-#define CAMERA_HD inline
-#endif
+#include "view_plan.h"                     // the azimuth rule (orbit_cos_sin), ray_samples
 
 namespace smk {
 
@@ -39,24 +34,13 @@ struct CameraView {
     float dx, dy, dz;                      // view   d = ( s ce, -se,  c ce )
 };
 
-// The angle rule.  Azimuth: r = remainder(azimuth, 360) in double; a multiple of 90 gives exactly (1,0), (0,1), (-1,0) or (0,-1), anything
-// else cos / sin of r * pi / 180 in double; both cast to fp32 once (the orbit's rule, orbit_plan.h) and read back as doubles.  Elevation:
-// 0, 90, -90 give exactly (1,0), (0,1), (0,-1), anything else cos / sin of radians in double.  The nine coefficients are formed in double
-// and cast to fp32 once.  false: a non-finite angle or |elevation| > 90 (*v untouched).  Host only.
+// The angle rule.  Azimuth: the orbit's rule (orbit_cos_sin, view_plan.h: exact at multiples of 90, cast to fp32 once), read back as
+// doubles.  Elevation: 0, 90, -90 give exactly (1,0), (0,1), (0,-1), anything else cos / sin of radians in double.  The nine coefficients
+// are formed in double and cast to fp32 once.  false: a non-finite angle or |elevation| > 90 (*v untouched).  Host only.
 inline bool camera_view(double azimuth_deg, double elevation_deg, CameraView *v) {
     if (!isfinite(azimuth_deg) || !isfinite(elevation_deg) || elevation_deg < -90.0 || elevation_deg > 90.0) return false;
-    const double r = remainder(azimuth_deg, 360.0);            // [-180, 180]
-    const double q = r / 90.0;
     float cf, sf;
-    if (q == -2.0 || q == 2.0) { cf = -1.f; sf = 0.f; }
-    else if (q == -1.0) { cf = 0.f; sf = -1.f; }
-    else if (q == 0.0) { cf = 1.f; sf = 0.f; }
-    else if (q == 1.0) { cf = 0.f; sf = 1.f; }
-    else {
-        const double rad = r * (3.14159265358979323846 / 180.0);
-        cf = (float)cos(rad);
-        sf = (float)sin(rad);
-    }
+    orbit_cos_sin(azimuth_deg, &cf, &sf);
     double ce, se;
     if (elevation_deg == 0.0) { ce = 1.0; se = 0.0; }
     else if (elevation_deg == 90.0) { ce = 0.0; se = 1.0; }
@@ -73,22 +57,15 @@ inline bool camera_view(double azimuth_deg, double elevation_deg, CameraView *v)
     return true;
 }
 
-// S: the smallest integer >= sqrt(D^2 + H^2 + W^2) with the parity of D (integer arithmetic: no rounding to argue about)
-CAMERA_HD int camera_samples(int D, int H, int W) {
-    const long long q = (long long)D * D + (long long)H * H + (long long)W * W;
-    long long s = (long long)sqrt((double)q);
-    while (s * s < q) ++s;
-    while (s > 0 && (s - 1) * (s - 1) >= q) --s;
-    if (((s - D) & 1) != 0) ++s;
-    return (int)s;
-}
+// S: the smallest integer >= sqrt(D^2 + H^2 + W^2) with the parity of D
+VIEW_HD int camera_samples(int D, int H, int W) { return ray_samples((long long)D * D + (long long)H * H + (long long)W * W, D); }
 
 struct CameraGeom {
     int D, H, W, S;
     float cz, cy, cx, tc;                  // (D - 1) / 2, (H - 1) / 2, (W - 1) / 2, (S - 1) / 2: half-integers, exact
 };
 
-CAMERA_HD CameraGeom camera_geom(int D, int H, int W) {
+VIEW_HD CameraGeom camera_geom(int D, int H, int W) {
     CameraGeom g;
     g.D = D; g.H = H; g.W = W; g.S = camera_samples(D, H, W);
     g.cz = 0.5f * (float)(D - 1); g.cy = 0.5f * (float)(H - 1); g.cx = 0.5f * (float)(W - 1); g.tc = 0.5f * (float)(g.S - 1);
@@ -97,16 +74,16 @@ CAMERA_HD CameraGeom camera_geom(int D, int H, int W) {
 
 // a = x' - c_x, b = y' - c_y, t = s - (S - 1) / 2 (all exact); one rounding per operation: compile with -ffp-contract=off (csrc/Makefile
 // does, and so does the host check)
-CAMERA_HD float camera_sample_x(float a, float b, float t, const CameraView &v, float cx) { return cx + ((a * v.rx + b * v.ex) + t * v.dx); }
-CAMERA_HD float camera_sample_y(float b, float t, const CameraView &v, float cy) { return cy + (b * v.ey + t * v.dy); }
-CAMERA_HD float camera_sample_z(float a, float b, float t, const CameraView &v, float cz) { return cz + ((a * v.rz + b * v.ez) + t * v.dz); }
+VIEW_HD float camera_sample_x(float a, float b, float t, const CameraView &v, float cx) { return cx + ((a * v.rx + b * v.ex) + t * v.dx); }
+VIEW_HD float camera_sample_y(float b, float t, const CameraView &v, float cy) { return cy + (b * v.ey + t * v.dy); }
+VIEW_HD float camera_sample_z(float a, float b, float t, const CameraView &v, float cz) { return cz + ((a * v.rz + b * v.ez) + t * v.dz); }
 
 // the extremes of the positions of image columns [xa, xb], rows [ya, yb] and samples [s0, s1], per axis
 struct CameraBrick {
     float zmin, zmax, ymin, ymax, xmin, xmax;
 };
 
-CAMERA_HD CameraBrick camera_brick(const CameraGeom &g, const CameraView &v, int xa, int xb, int ya, int yb, int s0, int s1) {
+VIEW_HD CameraBrick camera_brick(const CameraGeom &g, const CameraView &v, int xa, int xb, int ya, int yb, int s0, int s1) {
     const float a0 = (float)xa - g.cx, a1 = (float)xb - g.cx, b0 = (float)ya - g.cy, b1 = (float)yb - g.cy;
     const float t0 = (float)s0 - g.tc, t1 = (float)s1 - g.tc;
     CameraBrick k = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -125,12 +102,12 @@ CAMERA_HD CameraBrick camera_brick(const CameraGeom &g, const CameraView &v, int
 
 // A position p has the taps floor(p) and floor(p) + 1; one of them is in [0, N) exactly when -1 <= p < N.  A brick is live when, on
 // every axis, its interval of positions meets [-1, N); a brick that is not live has no tap inside the volume.
-CAMERA_HD bool camera_brick_live(const CameraGeom &g, const CameraBrick &k) {
+VIEW_HD bool camera_brick_live(const CameraGeom &g, const CameraBrick &k) {
     return k.zmax >= -1.0f && k.zmin < (float)g.D && k.ymax >= -1.0f && k.ymin < (float)g.H && k.xmax >= -1.0f && k.xmin < (float)g.W;
 }
 
 // the offset of voxel (z, y, x) inside its volume, in [0, D*H*W) (below 2^31 - 2^16), or -1 for a tap outside the volume
-CAMERA_HD int32_t camera_tap_offset(const CameraGeom &g, int z, int y, int x) {
+VIEW_HD int32_t camera_tap_offset(const CameraGeom &g, int z, int y, int x) {
     const bool in = (unsigned)z < (unsigned)g.D && (unsigned)y < (unsigned)g.H && (unsigned)x < (unsigned)g.W;
     return in ? (int32_t)(((int64_t)z * g.H + y) * g.W + x) : -1;
 }
@@ -139,7 +116,7 @@ CAMERA_HD int32_t camera_tap_offset(const CameraGeom &g, int z, int y, int x) {
 // camera_tap_offset of that tap, formed from one base offset.  The base is formed in unsigned arithmetic (it wraps for floors far outside
 // the volume and is then never used); for a tap inside the volume the sum is the tap's own offset, below 2^31.  This is what the kernel
 // calls; the host check holds it equal to camera_tap_offset tap by tap.
-CAMERA_HD void camera_taps(const CameraGeom &g, int iz, int iy, int ix, int32_t off[8]) {
+VIEW_HD void camera_taps(const CameraGeom &g, int iz, int iy, int ix, int32_t off[8]) {
     const bool zin[2] = {(unsigned)iz < (unsigned)g.D, (unsigned)(iz + 1) < (unsigned)g.D};
     const bool yin[2] = {(unsigned)iy < (unsigned)g.H, (unsigned)(iy + 1) < (unsigned)g.H};
     const bool xin[2] = {(unsigned)ix < (unsigned)g.W, (unsigned)(ix + 1) < (unsigned)g.W};
@@ -153,7 +130,7 @@ CAMERA_HD void camera_taps(const CameraGeom &g, int iz, int iy, int ix, int32_t 
 }
 
 // the trilinear combination in the spec's order; v[n]: tap n of camera_taps (0 for a tap outside the volume)
-CAMERA_HD float camera_trilinear(const float v[8], float fz, float fy, float fx) {
+VIEW_HD float camera_trilinear(const float v[8], float fz, float fy, float fx) {
     const float gx = 1.0f - fx, gy = 1.0f - fy;
     const float p0 = gy * (gx * v[0] + fx * v[1]) + fy * (gx * v[2] + fx * v[3]);
     const float p1 = gy * (gx * v[4] + fx * v[5]) + fy * (gx * v[6] + fx * v[7]);

@@ -11,13 +11,7 @@
 // Every position is formed in fp32 by orbit_sample_z / orbit_sample_x and nowhere else.  Both are monotone in a for fixed t and in t for
 // fixed a (each operation rounds monotonically), so over a rectangle of (a, t) the extremes are at its corners: the box needs no margin.
 #pragma once
-#include <math.h>
-
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define ORBIT_HD __host__ __device__ inline
-#else
-#define ORBIT_HD inline
-#endif
+#include "view_plan.h"                     // the angle rule (orbit_cos_sin), ray_samples
 
 namespace smk {
 
@@ -34,31 +28,10 @@ struct OrbitGeom {
     float cz, cx, tc;                      // (D - 1) / 2, (W - 1) / 2, (S - 1) / 2: half-integers, exact
 };
 
-// The angle rule: r = remainder(azimuth, 360) in double; a multiple of 90 gives exactly (1,0), (0,1), (-1,0) or (0,-1), anything else
-// cos / sin of r * pi / 180 in double; both cast to fp32 once.  Host only.
-inline void orbit_cos_sin(double azimuth_deg, float *c, float *s) {
-    const double r = remainder(azimuth_deg, 360.0);            // [-180, 180]
-    const double q = r / 90.0;
-    if (q == -2.0 || q == 2.0) { *c = -1.f; *s = 0.f; return; }
-    if (q == -1.0) { *c = 0.f; *s = -1.f; return; }
-    if (q == 0.0) { *c = 1.f; *s = 0.f; return; }
-    if (q == 1.0) { *c = 0.f; *s = 1.f; return; }
-    const double rad = r * (3.14159265358979323846 / 180.0);
-    *c = (float)cos(rad);
-    *s = (float)sin(rad);
-}
+// S: the smallest integer >= hypot(D, W) with the parity of D
+VIEW_HD int orbit_samples(int D, int W) { return ray_samples((long long)D * D + (long long)W * W, D); }
 
-// S: the smallest integer >= hypot(D, W) with the parity of D (integer arithmetic: no rounding to argue about)
-ORBIT_HD int orbit_samples(int D, int W) {
-    const long long q = (long long)D * D + (long long)W * W;
-    long long s = (long long)sqrt((double)q);
-    while (s * s < q) ++s;
-    while (s > 0 && (s - 1) * (s - 1) >= q) --s;
-    if (((s - D) & 1) != 0) ++s;
-    return (int)s;
-}
-
-ORBIT_HD OrbitGeom orbit_geom(int D, int W) {
+VIEW_HD OrbitGeom orbit_geom(int D, int W) {
     OrbitGeom g;
     g.D = D; g.W = W; g.S = orbit_samples(D, W);
     g.cz = 0.5f * (float)(D - 1); g.cx = 0.5f * (float)(W - 1); g.tc = 0.5f * (float)(g.S - 1);
@@ -67,18 +40,18 @@ ORBIT_HD OrbitGeom orbit_geom(int D, int W) {
 
 // a = x' - c_x, t = s - (S - 1) / 2 (both exact); one rounding per operation: compile with -ffp-contract=off (csrc/Makefile does, and
 // so does the host check)
-ORBIT_HD float orbit_sample_x(float a, float t, float c, float s, float cx) { return cx + (a * c + t * s); }
-ORBIT_HD float orbit_sample_z(float a, float t, float c, float s, float cz) { return cz + (t * c - a * s); }
+VIEW_HD float orbit_sample_x(float a, float t, float c, float s, float cx) { return cx + (a * c + t * s); }
+VIEW_HD float orbit_sample_z(float a, float t, float c, float s, float cz) { return cz + (t * c - a * s); }
 
 struct OrbitBox {
     int z0, z1, x0, x1;                    // inclusive, clipped to the volume; empty when z0 > z1 or x0 > x1
-    ORBIT_HD bool empty() const { return z0 > z1 || x0 > x1; }
-    ORBIT_HD int nz() const { return z1 - z0 + 1; }
-    ORBIT_HD int nx() const { return x1 - x0 + 1; }
+    VIEW_HD bool empty() const { return z0 > z1 || x0 > x1; }
+    VIEW_HD int nz() const { return z1 - z0 + 1; }
+    VIEW_HD int nx() const { return x1 - x0 + 1; }
 };
 
 // the box of image columns [xa, xb] and samples [s0, s1]
-ORBIT_HD OrbitBox orbit_box(const OrbitGeom &g, float c, float s, int xa, int xb, int s0, int s1) {
+VIEW_HD OrbitBox orbit_box(const OrbitGeom &g, float c, float s, int xa, int xb, int s0, int s1) {
     const float a0 = (float)xa - g.cx, a1 = (float)xb - g.cx, t0 = (float)s0 - g.tc, t1 = (float)s1 - g.tc;
     float zmin = 0.f, zmax = 0.f, xmin = 0.f, xmax = 0.f;
     for (int k = 0; k < 4; ++k) {
@@ -101,6 +74,6 @@ ORBIT_HD OrbitBox orbit_box(const OrbitGeom &g, float c, float s, int xa, int xb
 
 // element e of a box with rows of nx floats -> its row; inv_nx = 1.0f / nx.  Exact for the boxes built here: (e + 0.5) / nx is at least
 // 0.5 / ORBIT_BOX_SIDE away from an integer, far more than the rounding of one fp32 product (the host check walks every e and nx).
-ORBIT_HD int orbit_box_row(int e, float inv_nx) { return (int)(((float)e + 0.5f) * inv_nx); }
+VIEW_HD int orbit_box_row(int e, float inv_nx) { return (int)(((float)e + 0.5f) * inv_nx); }
 
 }  // namespace smk

@@ -17,6 +17,9 @@
 //
 // The gradient of both outputs with respect to the volumes (SPEC_3D.md section 10, "Gradient"; smk_volume_render_backward) is in the
 // second half of this file: the same two mappings, the same segment kernels, every element of the result written exactly once.
+//
+// What the moving cameras share with the front view is here too (render.h): k_render_prefix, the whole +-y prefix on the voxel grid, which
+// render_orbit.hip and render_camera.hip interpolate, and, at the end, the host-side checks of all four entry points.
 #include "render.h"
 
 namespace smk {
@@ -25,8 +28,6 @@ namespace {
 
 constexpr int RV_NT = 256;                 // threads per workgroup of the three flat kernels
 constexpr int SEG = RENDER_SEG_ROWS;
-
-enum { LIGHT_NONE = 0, LIGHT_POS_Y = 1, LIGHT_NEG_Y = 2, LIGHT_POS_Z = 3 };
 
 // ---- light none / +z: one pixel per lane, nothing shared
 template <bool LIT_Z>
@@ -167,10 +168,52 @@ __global__ __launch_bounds__(64, 2) void k_render_lit(const float *__restrict__ 
 
 inline int render_segments(int H) { return (H + SEG - 1) / SEG; }
 
+// ---- light +-y for the moving cameras: ws[v][z][y][x] = sum of rho[z][y'][x] over the rows y' the light crosses before y, in the order
+// of travel.  The whole prefix on the voxel grid, which they interpolate: one read and one write of the volumes, lanes along x.
+__global__ __launch_bounds__(RV_NT) void k_render_prefix(const float *__restrict__ vols, int64_t stride, int D, int H, int W, int bpp, int up,
+                                                         float *__restrict__ ws) {
+    const int v = blockIdx.x / bpp, q = (blockIdx.x % bpp) * RV_NT + threadIdx.x;
+    if (q >= D * W) return;
+    const int z = q / W, x = q - z * W;
+    const size_t base = (size_t)z * H * W + x;                 // + y * W < D * H * W
+    const float *f = vols + (size_t)v * stride + base;
+    float *o = ws + (size_t)v * D * H * W + base;
+    float run = 0.f;
+    constexpr int U = 8;                                       // rows loaded ahead of their sums
+    for (int i0 = 0; i0 < H; i0 += U) {
+        float r[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            const int i = i0 + j, y = up ? i : H - 1 - i;
+            r[j] = i < H ? f[(size_t)y * W] : 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            const int i = i0 + j, y = up ? i : H - 1 - i;
+            if (i < H) {
+                o[(size_t)y * W] = run;
+                run += r[j];
+            }
+        }
+    }
+}
+
 }  // namespace
 
+int64_t render_prefix_workspace(int64_t n, int D, int H, int W, int light) {
+    if (light != SMK_LIGHT_POS_Y && light != SMK_LIGHT_NEG_Y) return 0;
+    return n * (int64_t)D * H * W * (int64_t)sizeof(float);
+}
+
+hipError_t launch_render_prefix(const float *vols, int64_t stride, int64_t n, int D, int H, int W, bool up, float *workspace, hipStream_t st) {
+    const int64_t bpp = ((int64_t)D * W + RV_NT - 1) / RV_NT, grid = n * bpp;
+    if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_render_prefix, dim3((unsigned)grid), dim3(RV_NT), 0, st, vols, stride, D, H, W, (int)bpp, up ? 1 : 0, workspace);
+    return hipGetLastError();
+}
+
 int64_t render_workspace(int64_t n, int D, int H, int W, int light) {
-    if (light != LIGHT_POS_Y && light != LIGHT_NEG_Y) return 0;
+    if (light != SMK_LIGHT_POS_Y && light != SMK_LIGHT_NEG_Y) return 0;
     const int nseg = render_segments(H);
     if (nseg <= 1) return 0;
     return n * nseg * (int64_t)D * W * (int64_t)sizeof(float);
@@ -179,10 +222,10 @@ int64_t render_workspace(int64_t n, int D, int H, int W, int light) {
 hipError_t launch_volume_render(const float *vols, int64_t stride, int64_t n, int D, int H, int W, int light, const RenderParams &p,
                                 float *image, int64_t image_stride, float *trans, int64_t trans_stride, float *workspace, hipStream_t st) {
     const int64_t HW = (int64_t)H * W, DW = (int64_t)D * W;
-    if (light == LIGHT_NONE || light == LIGHT_POS_Z) {
+    if (light == SMK_LIGHT_NONE || light == SMK_LIGHT_POS_Z) {
         const int64_t bpv = (HW + RV_NT - 1) / RV_NT, grid = n * bpv;
         if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
-        if (light == LIGHT_POS_Z)
+        if (light == SMK_LIGHT_POS_Z)
             hipLaunchKernelGGL(k_render_view<true>, dim3((unsigned)grid), dim3(RV_NT), 0, st, vols, stride, D, (int)HW, (int)bpv, p, image,
                                image_stride, trans, trans_stride);
         else
@@ -190,7 +233,7 @@ hipError_t launch_volume_render(const float *vols, int64_t stride, int64_t n, in
                                image_stride, trans, trans_stride);
         return hipGetLastError();
     }
-    const int up = light == LIGHT_POS_Y;
+    const int up = light == SMK_LIGHT_POS_Y;
     const int nseg = render_segments(H), nxc = (W + 63) / 64;
     const int64_t bpp = (DW + RV_NT - 1) / RV_NT;
     const int64_t g1 = n * nseg * bpp, g2 = n * bpp, g3 = n * nseg * nxc;
@@ -427,7 +470,7 @@ __global__ __launch_bounds__(64) void k_render_grad_lit(const float *__restrict_
 }  // namespace
 
 int64_t render_backward_workspace(int64_t n, int D, int H, int W, int light) {
-    if (light != LIGHT_POS_Y && light != LIGHT_NEG_Y) return 0;
+    if (light != SMK_LIGHT_POS_Y && light != SMK_LIGHT_NEG_Y) return 0;
     return (3 * n * render_segments(H) * (int64_t)D * W + n * (int64_t)H * W) * (int64_t)sizeof(float);
 }
 
@@ -435,10 +478,10 @@ hipError_t launch_volume_render_backward(const float *vols, int64_t stride, int6
                                          const float *G, int64_t gstride, const float *Gt, int64_t tstride, float *out, int64_t ostride,
                                          float *workspace, hipStream_t st) {
     const int64_t HW = (int64_t)H * W, DW = (int64_t)D * W;
-    if (light == LIGHT_NONE || light == LIGHT_POS_Z) {
+    if (light == SMK_LIGHT_NONE || light == SMK_LIGHT_POS_Z) {
         const int64_t bpv = (HW + RV_NT - 1) / RV_NT, grid = n * bpv;
         if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
-        if (light == LIGHT_POS_Z)
+        if (light == SMK_LIGHT_POS_Z)
             hipLaunchKernelGGL(k_render_grad_view, dim3((unsigned)grid), dim3(RV_NT), 0, st, vols, stride, D, (int)HW, (int)bpv, p, G, gstride, Gt,
                                tstride, out, ostride);
         else
@@ -446,7 +489,7 @@ hipError_t launch_volume_render_backward(const float *vols, int64_t stride, int6
                                tstride, out, ostride);
         return hipGetLastError();
     }
-    const int up = light == LIGHT_POS_Y;
+    const int up = light == SMK_LIGHT_POS_Y;
     const int nseg = render_segments(H), nxc = (W + 63) / 64;
     const int64_t bpp = (DW + RV_NT - 1) / RV_NT;
     const int64_t g1 = n * nseg * bpp, g2 = n * bpp, g3 = n * nseg * nxc;
@@ -477,6 +520,68 @@ hipError_t launch_volume_render_backward(const float *vols, int64_t stride, int6
     return hipGetLastError();
 }
 
+
+// ================================================================================================================================
+// The host-side checks of the four entry points (render.h).
+bool render_query_ok(const RenderLimits &lim, int32_t n, int32_t D, int32_t H, int32_t W, int32_t light) {
+    return n >= 1 && D >= 1 && D <= lim.max_depth && H >= 1 && (lim.max_height == 0 || H <= lim.max_height) && W >= 1 &&
+           (lim.max_width == 0 || W <= lim.max_width) && (int64_t)D * H * W <= RENDER_MAX_CELLS && light >= SMK_LIGHT_NONE &&
+           light <= (lim.moving ? SMK_LIGHT_NEG_Y : SMK_LIGHT_POS_Z);
+}
+
+int render_check(const char *name, const RenderLimits &lim, int32_t n, int32_t D, int32_t H, int32_t W, int32_t n_views,
+                 const smk_render_desc *desc, const void *vols, int64_t vol_stride, std::initializer_list<RenderBuffer> bufs,
+                 const void *workspace, RenderParams *p) {
+    if (lim.moving) {
+        SMK_REQUIRE(n >= 1 && D >= 1 && H >= 1 && W >= 1 && n_views >= 1, "n, D, H, W, n_views >= 1");
+        SMK_REQUIRE((int64_t)n * n_views <= RENDER_MAX_PLANES, "n * n_views <= 2^20");
+    } else {
+        SMK_REQUIRE(n >= 1 && D >= 1 && H >= 1 && W >= 1, "n, D, H, W >= 1");
+    }
+    if (!render_query_ok(lim, n, D, H, W, SMK_LIGHT_NONE)) {
+        set_error(std::string(name) + ": D <= " + std::to_string(lim.max_depth) +
+                  (lim.max_height ? ", H <= " + std::to_string(lim.max_height) : "") +
+                  (lim.max_width ? ", W <= " + std::to_string(lim.max_width) : "") + " and D*H*W <= 2^31 - 2^16 are built (got D=" +
+                  std::to_string(D) + ", H=" + std::to_string(H) + ", W=" + std::to_string(W) + ")");
+        return SMK_ERR_UNSUPPORTED;
+    }
+    SMK_REQUIRE(desc->light >= SMK_LIGHT_NONE && desc->light <= SMK_LIGHT_POS_Z, "light: one of smk_light");
+    if (lim.moving && desc->light == SMK_LIGHT_POS_Z) {
+        set_error(std::string(name) + ": SMK_LIGHT_POS_Z is not built for " + lim.moving + " (a world-fixed +z light seen obliquely is "
+                  "another prefix); SMK_LIGHT_NONE, SMK_LIGHT_POS_Y and SMK_LIGHT_NEG_Y are");
+        return SMK_ERR_UNSUPPORTED;
+    }
+    SMK_REQUIRE(desc->sigma_view >= 0 && desc->sigma_light >= 0 && desc->ambient >= 0 && desc->ambient <= 1 && desc->gain > 0,
+                "sigma_view, sigma_light >= 0; 0 <= ambient <= 1; gain > 0");
+    const int64_t cells = (int64_t)D * H * W, HW = (int64_t)H * W, planes = lim.moving ? (int64_t)n * n_views : n;
+    SMK_REQUIRE(vol_stride >= cells || n == 1, "vol_stride >= D*H*W");
+    uintptr_t low_bits = (uintptr_t)vols | (uintptr_t)workspace;
+    for (const RenderBuffer &b : bufs) {
+        SMK_REQUIRE(b.ptr == nullptr || b.stride >= (b.volume ? cells : HW) || (b.volume ? n : planes) == 1,
+                    std::string(b.stride_name) + (b.volume ? " >= D*H*W" : " >= H*W"));
+        low_bits |= (uintptr_t)b.ptr;
+    }
+    SMK_REQUIRE((low_bits & 3) == 0, "4-byte aligned pointers");
+    p->neg_sigma_view = (float)-desc->sigma_view;
+    p->neg_sigma_light = (float)-desc->sigma_light;
+    p->ambient = (float)desc->ambient;
+    p->one_minus_ambient = (float)(1.0 - desc->ambient);
+    p->gain = (float)desc->gain;
+    return SMK_OK;
+}
+
+int render_check_workspace(const char *name, int64_t need, const void *workspace, int64_t workspace_bytes) {
+    SMK_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need),
+                std::string("workspace smaller than smk_") + name + "_workspace(n, D, H, W, light)");
+    return SMK_OK;
+}
+
+int render_launch_status(const char *name, hipError_t e) {
+    if (e == hipSuccess) return SMK_OK;
+    set_error(std::string(name) + ": " + hipGetErrorString(e));
+    return SMK_ERR_HIP;
+}
+
 }  // namespace smk
 
 using namespace smk;
@@ -484,57 +589,27 @@ using namespace smk;
 #pragma GCC visibility push(default)
 extern "C" {
 
-static const int64_t RENDER_MAX_CELLS = (1LL << 31) - (1LL << 16);     // smk_volume_stats' limit: 32-bit offsets inside a volume
-
-static bool render_shape_ok(int32_t n, int32_t D, int32_t H, int32_t W) {
-    return n >= 1 && D >= 1 && D <= RENDER_MAX_DEPTH && H >= 1 && W >= 1 && (int64_t)D * H * W <= RENDER_MAX_CELLS;
-}
+static constexpr RenderLimits FRONT = {RENDER_MAX_DEPTH, 0, 0, nullptr};
 
 int64_t smk_volume_render_workspace(int32_t n, int32_t D, int32_t H, int32_t W, int32_t light) {
-    if (!render_shape_ok(n, D, H, W) || light < SMK_LIGHT_NONE || light > SMK_LIGHT_POS_Z) return -1;
-    return render_workspace(n, D, H, W, light);
+    return render_query_ok(FRONT, n, D, H, W, light) ? render_workspace(n, D, H, W, light) : -1;
 }
 
 int smk_volume_render(const float *vols, int64_t vol_stride, int32_t n, int32_t D, int32_t H, int32_t W, const smk_render_desc *desc,
                       float *image, int64_t image_stride, float *transmittance, int64_t trans_stride, void *workspace,
                       int64_t workspace_bytes, void *stream) {
     SMK_REQUIRE(vols && desc && image, "null pointer");
-    SMK_REQUIRE(n >= 1 && D >= 1 && H >= 1 && W >= 1, "n, D, H, W >= 1");
-    if (!render_shape_ok(n, D, H, W)) {
-        set_error("volume_render: D <= 64 and D*H*W <= 2^31 - 2^16 are built (got D=" + std::to_string(D) + ", H=" + std::to_string(H) +
-                  ", W=" + std::to_string(W) + ")");
-        return SMK_ERR_UNSUPPORTED;
-    }
-    SMK_REQUIRE(desc->light >= SMK_LIGHT_NONE && desc->light <= SMK_LIGHT_POS_Z, "light: one of smk_light");
-    SMK_REQUIRE(desc->sigma_view >= 0 && desc->sigma_light >= 0 && desc->ambient >= 0 && desc->ambient <= 1 && desc->gain > 0,
-                "sigma_view, sigma_light >= 0; 0 <= ambient <= 1; gain > 0");
-    const int64_t cells = (int64_t)D * H * W, HW = (int64_t)H * W;
-    SMK_REQUIRE(vol_stride >= cells || n == 1, "vol_stride >= D*H*W");
-    SMK_REQUIRE(image_stride >= HW || n == 1, "image_stride >= H*W");
-    SMK_REQUIRE(transmittance == nullptr || trans_stride >= HW || n == 1, "trans_stride >= H*W");
-    SMK_REQUIRE(((uintptr_t)vols & 3) == 0 && ((uintptr_t)image & 3) == 0 && ((uintptr_t)transmittance & 3) == 0 &&
-                    ((uintptr_t)workspace & 3) == 0, "4-byte aligned pointers");
-    const int64_t need = render_workspace(n, D, H, W, desc->light);
-    SMK_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need),
-                "workspace smaller than smk_volume_render_workspace(n, D, H, W, light)");
     RenderParams p;
-    p.neg_sigma_view = (float)-desc->sigma_view;
-    p.neg_sigma_light = (float)-desc->sigma_light;
-    p.ambient = (float)desc->ambient;
-    p.one_minus_ambient = (float)(1.0 - desc->ambient);
-    p.gain = (float)desc->gain;
-    const hipError_t e = launch_volume_render(vols, vol_stride, n, D, H, W, desc->light, p, image, image_stride, transmittance,
-                                              trans_stride, (float *)workspace, (hipStream_t)stream);
-    if (e != hipSuccess) {
-        set_error(std::string("volume_render: ") + hipGetErrorString(e));
-        return SMK_ERR_HIP;
-    }
-    return SMK_OK;
+    int rc = render_check("volume_render", FRONT, n, D, H, W, 0, desc, vols, vol_stride,
+                          {{image, image_stride, false, "image_stride"}, {transmittance, trans_stride, false, "trans_stride"}}, workspace, &p);
+    if (rc == SMK_OK) rc = render_check_workspace("volume_render", render_workspace(n, D, H, W, desc->light), workspace, workspace_bytes);
+    if (rc != SMK_OK) return rc;
+    return render_launch_status("volume_render", launch_volume_render(vols, vol_stride, n, D, H, W, desc->light, p, image, image_stride,
+                                                                      transmittance, trans_stride, (float *)workspace, (hipStream_t)stream));
 }
 
 int64_t smk_volume_render_backward_workspace(int32_t n, int32_t D, int32_t H, int32_t W, int32_t light) {
-    if (!render_shape_ok(n, D, H, W) || light < SMK_LIGHT_NONE || light > SMK_LIGHT_POS_Z) return -1;
-    return render_backward_workspace(n, D, H, W, light);
+    return render_query_ok(FRONT, n, D, H, W, light) ? render_backward_workspace(n, D, H, W, light) : -1;
 }
 
 int smk_volume_render_backward(const float *vols, int64_t vol_stride, int32_t n, int32_t D, int32_t H, int32_t W, const smk_render_desc *desc,
@@ -542,38 +617,18 @@ int smk_volume_render_backward(const float *vols, int64_t vol_stride, int32_t n,
                                float *grad_vols, int64_t grad_vol_stride, void *workspace, int64_t workspace_bytes, void *stream) {
     SMK_REQUIRE(vols && desc && grad_vols, "null pointer");
     SMK_REQUIRE(grad_image || grad_trans, "grad_image and grad_trans are both null: there is no gradient to carry back");
-    SMK_REQUIRE(n >= 1 && D >= 1 && H >= 1 && W >= 1, "n, D, H, W >= 1");
-    if (!render_shape_ok(n, D, H, W)) {
-        set_error("volume_render_backward: D <= 64 and D*H*W <= 2^31 - 2^16 are built (got D=" + std::to_string(D) + ", H=" +
-                  std::to_string(H) + ", W=" + std::to_string(W) + ")");
-        return SMK_ERR_UNSUPPORTED;
-    }
-    SMK_REQUIRE(desc->light >= SMK_LIGHT_NONE && desc->light <= SMK_LIGHT_POS_Z, "light: one of smk_light");
-    SMK_REQUIRE(desc->sigma_view >= 0 && desc->sigma_light >= 0 && desc->ambient >= 0 && desc->ambient <= 1 && desc->gain > 0,
-                "sigma_view, sigma_light >= 0; 0 <= ambient <= 1; gain > 0");
-    const int64_t cells = (int64_t)D * H * W, HW = (int64_t)H * W;
-    SMK_REQUIRE(vol_stride >= cells || n == 1, "vol_stride >= D*H*W");
-    SMK_REQUIRE(grad_vol_stride >= cells || n == 1, "grad_vol_stride >= D*H*W");
-    SMK_REQUIRE(grad_image == nullptr || grad_image_stride >= HW || n == 1, "grad_image_stride >= H*W");
-    SMK_REQUIRE(grad_trans == nullptr || grad_trans_stride >= HW || n == 1, "grad_trans_stride >= H*W");
-    SMK_REQUIRE(((uintptr_t)vols & 3) == 0 && ((uintptr_t)grad_image & 3) == 0 && ((uintptr_t)grad_trans & 3) == 0 &&
-                    ((uintptr_t)grad_vols & 3) == 0 && ((uintptr_t)workspace & 3) == 0, "4-byte aligned pointers");
-    const int64_t need = render_backward_workspace(n, D, H, W, desc->light);
-    SMK_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need),
-                "workspace smaller than smk_volume_render_backward_workspace(n, D, H, W, light)");
     RenderParams p;
-    p.neg_sigma_view = (float)-desc->sigma_view;
-    p.neg_sigma_light = (float)-desc->sigma_light;
-    p.ambient = (float)desc->ambient;
-    p.one_minus_ambient = (float)(1.0 - desc->ambient);
-    p.gain = (float)desc->gain;
-    const hipError_t e = launch_volume_render_backward(vols, vol_stride, n, D, H, W, desc->light, p, grad_image, grad_image_stride, grad_trans,
-                                                       grad_trans_stride, grad_vols, grad_vol_stride, (float *)workspace, (hipStream_t)stream);
-    if (e != hipSuccess) {
-        set_error(std::string("volume_render_backward: ") + hipGetErrorString(e));
-        return SMK_ERR_HIP;
-    }
-    return SMK_OK;
+    int rc = render_check("volume_render_backward", FRONT, n, D, H, W, 0, desc, vols, vol_stride,
+                          {{grad_vols, grad_vol_stride, true, "grad_vol_stride"},
+                           {grad_image, grad_image_stride, false, "grad_image_stride"},
+                           {grad_trans, grad_trans_stride, false, "grad_trans_stride"}}, workspace, &p);
+    if (rc == SMK_OK)
+        rc = render_check_workspace("volume_render_backward", render_backward_workspace(n, D, H, W, desc->light), workspace, workspace_bytes);
+    if (rc != SMK_OK) return rc;
+    return render_launch_status("volume_render_backward",
+                                launch_volume_render_backward(vols, vol_stride, n, D, H, W, desc->light, p, grad_image, grad_image_stride,
+                                                              grad_trans, grad_trans_stride, grad_vols, grad_vol_stride, (float *)workspace,
+                                                              (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -11,7 +11,7 @@
 // There is no LDS and no barrier: the waves of a workgroup are independent.  Every offset comes from camera_taps, which tests each tap
 // against the volume; a tap outside it is not read (its lane reads cell 0 of its own volume and discards it).
 //
-// Light "+y" / "-y": A_s is the same interpolation of the voxel-grid prefix A[z][y][x], which k_orbit_prefix (render_orbit.hip) writes into
+// Light "+y" / "-y": A_s is the same interpolation of the voxel-grid prefix A[z][y][x], which k_render_prefix (render.hip) writes into
 // the workspace once per call; the main kernel reads it beside rho at the same offsets.
 //
 // Views: the coefficients travel as launch arguments, CAMERA_VIEWS_PER_LAUNCH per launch; a launch orders its workgroups view-fastest.
@@ -21,16 +21,12 @@
 #include <new>
 #include <vector>
 
-#include "render_orbit.h"
-
 namespace smk {
 
 namespace {
 
 constexpr int CV_NT = 64 * CAMERA_WAVES;
 static_assert(CAMERA_TILE_W * CAMERA_TILE_H == 64, "a tile is one wave");
-
-enum { LIGHT_NONE = 0, LIGHT_POS_Y = 1, LIGHT_NEG_Y = 2, LIGHT_POS_Z = 3 };
 
 struct CameraViews {
     CameraView v[CAMERA_VIEWS_PER_LAUNCH];
@@ -95,21 +91,16 @@ __global__ __launch_bounds__(CV_NT) void k_render_camera(const float *__restrict
 
 }  // namespace
 
-int64_t render_camera_workspace(int64_t n, int D, int H, int W, int light) {
-    if (light != LIGHT_POS_Y && light != LIGHT_NEG_Y) return 0;
-    return n * (int64_t)D * H * W * (int64_t)sizeof(float);
-}
-
 hipError_t launch_volume_render_camera(const float *vols, int64_t stride, int64_t n, int D, int H, int W, int light, const RenderParams &p,
                                        const CameraView *cvs, int n_views, float *image, int64_t image_stride, float *trans,
                                        int64_t trans_stride, float *workspace, hipStream_t st) {
-    const bool lit = light == LIGHT_POS_Y || light == LIGHT_NEG_Y;
+    const bool lit = light == SMK_LIGHT_POS_Y || light == SMK_LIGHT_NEG_Y;
     const int rows = CAMERA_WAVES * CAMERA_TILE_H;
     const int nstrips = (W + CAMERA_TILE_W - 1) / CAMERA_TILE_W, nyg = (H + rows - 1) / rows;
     const int64_t pairs = n * n_views, per_pair = (int64_t)nstrips * nyg;
     if (per_pair * CAMERA_VIEWS_PER_LAUNCH > 0x7fffffffLL || pairs > 0x7fffffffLL) return hipErrorInvalidValue;
     hipError_t e;
-    if (lit && (e = launch_orbit_prefix(vols, stride, n, D, H, W, light == LIGHT_POS_Y, workspace, st)) != hipSuccess) return e;
+    if (lit && (e = launch_render_prefix(vols, stride, n, D, H, W, light == SMK_LIGHT_POS_Y, workspace, st)) != hipSuccess) return e;
     for (int64_t p0 = 0; p0 < pairs; p0 += CAMERA_VIEWS_PER_LAUNCH) {
         const int np = (int)(pairs - p0 < CAMERA_VIEWS_PER_LAUNCH ? pairs - p0 : CAMERA_VIEWS_PER_LAUNCH);
         CameraViews views = {};
@@ -133,52 +124,28 @@ using namespace smk;
 #pragma GCC visibility push(default)
 extern "C" {
 
-static const int64_t CAMERA_MAX_CELLS = (1LL << 31) - (1LL << 16);     // smk_volume_render's limit: 32-bit offsets inside a volume
-static const int64_t CAMERA_MAX_PLANES = 1 << 20;                      // n * n_views of one call (the host forms a coefficient set for each)
-
-static bool camera_shape_ok(int32_t D, int32_t H, int32_t W) {
-    return D >= 1 && D <= CAMERA_MAX_DEPTH && H >= 1 && H <= CAMERA_MAX_HEIGHT && W >= 1 && W <= CAMERA_MAX_WIDTH &&
-           (int64_t)D * H * W <= CAMERA_MAX_CELLS;
-}
+static constexpr RenderLimits CAMERA = {CAMERA_MAX_DEPTH, CAMERA_MAX_HEIGHT, CAMERA_MAX_WIDTH, "a moving camera"};
 
 int64_t smk_volume_render_camera_workspace(int32_t n, int32_t D, int32_t H, int32_t W, int32_t light) {
-    if (n < 1 || !camera_shape_ok(D, H, W) || light < SMK_LIGHT_NONE || light > SMK_LIGHT_NEG_Y) return -1;
-    return render_camera_workspace(n, D, H, W, light);
+    return render_query_ok(CAMERA, n, D, H, W, light) ? render_prefix_workspace(n, D, H, W, light) : -1;
 }
 
 int smk_volume_render_camera(const float *vols, int64_t vol_stride, int32_t n, int32_t D, int32_t H, int32_t W, const smk_render_desc *desc,
                              const double *azimuths, const double *elevations, int32_t n_views, float *image, int64_t image_stride,
                              float *transmittance, int64_t trans_stride, void *workspace, int64_t workspace_bytes, void *stream) {
     SMK_REQUIRE(vols && desc && image && azimuths && elevations, "null pointer");
-    SMK_REQUIRE(n >= 1 && D >= 1 && H >= 1 && W >= 1 && n_views >= 1, "n, D, H, W, n_views >= 1");
-    SMK_REQUIRE((int64_t)n * n_views <= CAMERA_MAX_PLANES, "n * n_views <= 2^20");
-    if (!camera_shape_ok(D, H, W)) {
-        set_error("volume_render_camera: D <= 64, H <= 65536, W <= 1024 and D*H*W <= 2^31 - 2^16 are built (got D=" + std::to_string(D) +
-                  ", H=" + std::to_string(H) + ", W=" + std::to_string(W) + ")");
-        return SMK_ERR_UNSUPPORTED;
-    }
-    SMK_REQUIRE(desc->light >= SMK_LIGHT_NONE && desc->light <= SMK_LIGHT_POS_Z, "light: one of smk_light");
-    if (desc->light == SMK_LIGHT_POS_Z) {
-        set_error("volume_render_camera: SMK_LIGHT_POS_Z is not built for a moving camera (a world-fixed +z light seen obliquely is another "
-                  "prefix); SMK_LIGHT_NONE, SMK_LIGHT_POS_Y and SMK_LIGHT_NEG_Y are");
-        return SMK_ERR_UNSUPPORTED;
-    }
-    SMK_REQUIRE(desc->sigma_view >= 0 && desc->sigma_light >= 0 && desc->ambient >= 0 && desc->ambient <= 1 && desc->gain > 0,
-                "sigma_view, sigma_light >= 0; 0 <= ambient <= 1; gain > 0");
-    const int64_t cells = (int64_t)D * H * W, HW = (int64_t)H * W, planes = (int64_t)n * n_views;
-    SMK_REQUIRE(vol_stride >= cells || n == 1, "vol_stride >= D*H*W");
-    SMK_REQUIRE(image_stride >= HW || planes == 1, "image_stride >= H*W");
-    SMK_REQUIRE(transmittance == nullptr || trans_stride >= HW || planes == 1, "trans_stride >= H*W");
-    SMK_REQUIRE(((uintptr_t)vols & 3) == 0 && ((uintptr_t)image & 3) == 0 && ((uintptr_t)transmittance & 3) == 0 &&
-                    ((uintptr_t)workspace & 3) == 0, "4-byte aligned pointers");
+    RenderParams p;
+    int rc = render_check("volume_render_camera", CAMERA, n, D, H, W, n_views, desc, vols, vol_stride,
+                          {{image, image_stride, false, "image_stride"}, {transmittance, trans_stride, false, "trans_stride"}}, workspace, &p);
+    if (rc != SMK_OK) return rc;
+    const int64_t planes = (int64_t)n * n_views;
     for (int64_t i = 0; i < planes; ++i) {
         SMK_REQUIRE(std::isfinite(azimuths[i]), "azimuths: finite numbers of degrees");
         SMK_REQUIRE(std::isfinite(elevations[i]) && elevations[i] >= -90.0 && elevations[i] <= 90.0,
                     "elevations: finite numbers of degrees in [-90, 90]");
     }
-    const int64_t need = render_camera_workspace(n, D, H, W, desc->light);
-    SMK_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need),
-                "workspace smaller than smk_volume_render_camera_workspace(n, D, H, W, light)");
+    rc = render_check_workspace("volume_render_camera", render_prefix_workspace(n, D, H, W, desc->light), workspace, workspace_bytes);
+    if (rc != SMK_OK) return rc;
     std::vector<CameraView> cvs;
     try {
         cvs.resize((size_t)planes);                            // up to 2^20 coefficient sets, 32 MB: no exception may cross the C boundary
@@ -187,19 +154,9 @@ int smk_volume_render_camera(const float *vols, int64_t vol_stride, int32_t n, i
         return SMK_ERR_INVALID;
     }
     for (int64_t i = 0; i < planes; ++i) SMK_REQUIRE(camera_view(azimuths[i], elevations[i], &cvs[i]), "angles");
-    RenderParams p;
-    p.neg_sigma_view = (float)-desc->sigma_view;
-    p.neg_sigma_light = (float)-desc->sigma_light;
-    p.ambient = (float)desc->ambient;
-    p.one_minus_ambient = (float)(1.0 - desc->ambient);
-    p.gain = (float)desc->gain;
-    const hipError_t e = launch_volume_render_camera(vols, vol_stride, n, D, H, W, desc->light, p, cvs.data(), n_views, image, image_stride,
-                                                     transmittance, trans_stride, (float *)workspace, (hipStream_t)stream);
-    if (e != hipSuccess) {
-        set_error(std::string("volume_render_camera: ") + hipGetErrorString(e));
-        return SMK_ERR_HIP;
-    }
-    return SMK_OK;
+    return render_launch_status("volume_render_camera",
+                                launch_volume_render_camera(vols, vol_stride, n, D, H, W, desc->light, p, cvs.data(), n_views, image,
+                                                            image_stride, transmittance, trans_stride, (float *)workspace, (hipStream_t)stream));
 }
 
 }  // extern "C"

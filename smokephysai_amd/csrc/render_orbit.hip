@@ -12,8 +12,8 @@
 // all the rows.
 //
 // Light "+y" / "-y": interpolation is linear and the positions do not depend on y, so the prefix of the samples along y is the
-// interpolation of the voxel-grid prefix A[z][y][x].  k_orbit_prefix writes that prefix into the workspace (one read and one write of the
-// volumes, lanes along x), and the main kernel stages it beside rho and interpolates both with the same weights.
+// interpolation of the voxel-grid prefix A[z][y][x].  k_render_prefix (render.hip) writes that prefix into the workspace (one read and one
+// write of the volumes, lanes along x), and the main kernel stages it beside rho and interpolates both with the same weights.
 //
 // Views: the (cos, sin) pairs travel as launch arguments, ORBIT_VIEWS_PER_LAUNCH per launch; a launch orders its workgroups view-fastest,
 // so the views of one (rows, strip) run together and meet in L2.  The prefix pass runs once per call, whatever the number of views.
@@ -27,43 +27,11 @@ namespace smk {
 namespace {
 
 constexpr int OV_NT = ORBIT_STRIP * ORBIT_ROWS;       // 128 threads
-constexpr int OP_NT = 256;
 constexpr int STAGE_U = 4;                            // box cells a lane loads ahead of their LDS stores
-
-enum { LIGHT_NONE = 0, LIGHT_POS_Y = 1, LIGHT_NEG_Y = 2, LIGHT_POS_Z = 3 };
 
 struct OrbitViews {
     float c[ORBIT_VIEWS_PER_LAUNCH], s[ORBIT_VIEWS_PER_LAUNCH];
 };
-
-// ---- light +-y: ws[v][z][y][x] = sum of rho[z][y'][x] over the rows y' the light crosses before y, in the order of travel
-__global__ __launch_bounds__(OP_NT) void k_orbit_prefix(const float *__restrict__ vols, int64_t stride, int D, int H, int W, int bpp, int up,
-                                                        float *__restrict__ ws) {
-    const int v = blockIdx.x / bpp, q = (blockIdx.x % bpp) * OP_NT + threadIdx.x;
-    if (q >= D * W) return;
-    const int z = q / W, x = q - z * W;
-    const size_t base = (size_t)z * H * W + x;                 // + y * W < D * H * W
-    const float *f = vols + (size_t)v * stride + base;
-    float *o = ws + (size_t)v * D * H * W + base;
-    float run = 0.f;
-    constexpr int U = 8;                                       // rows loaded ahead of their sums
-    for (int i0 = 0; i0 < H; i0 += U) {
-        float r[U];
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            const int i = i0 + j, y = up ? i : H - 1 - i;
-            r[j] = i < H ? f[(size_t)y * W] : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < U; ++j) {
-            const int i = i0 + j, y = up ? i : H - 1 - i;
-            if (i < H) {
-                o[(size_t)y * W] = run;
-                run += r[j];
-            }
-        }
-    }
-}
 
 // the four neighbours of one sample out of a staged box (rows of nx floats); a neighbour outside the box counts as 0
 __device__ __forceinline__ float orbit_bilinear(const float *box, int iz, int ix, int nz, int nx, float fz, float fx) {
@@ -159,27 +127,15 @@ __global__ __launch_bounds__(OV_NT) void k_render_orbit(const float *__restrict_
 
 }  // namespace
 
-int64_t render_orbit_workspace(int64_t n, int D, int H, int W, int light) {
-    if (light != LIGHT_POS_Y && light != LIGHT_NEG_Y) return 0;
-    return n * (int64_t)D * H * W * (int64_t)sizeof(float);
-}
-
-hipError_t launch_orbit_prefix(const float *vols, int64_t stride, int64_t n, int D, int H, int W, bool up, float *workspace, hipStream_t st) {
-    const int64_t bpp = ((int64_t)D * W + OP_NT - 1) / OP_NT, grid = n * bpp;
-    if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_orbit_prefix, dim3((unsigned)grid), dim3(OP_NT), 0, st, vols, stride, D, H, W, (int)bpp, up ? 1 : 0, workspace);
-    return hipGetLastError();
-}
-
 hipError_t launch_volume_render_orbit(const float *vols, int64_t stride, int64_t n, int D, int H, int W, int light, const RenderParams &p,
                                       const float *cs, int n_views, float *image, int64_t image_stride, float *trans, int64_t trans_stride,
                                       float *workspace, hipStream_t st) {
-    const bool lit = light == LIGHT_POS_Y || light == LIGHT_NEG_Y;
+    const bool lit = light == SMK_LIGHT_POS_Y || light == SMK_LIGHT_NEG_Y;
     const int nstrips = (W + ORBIT_STRIP - 1) / ORBIT_STRIP, nyg = (H + ORBIT_ROWS - 1) / ORBIT_ROWS;
     const int64_t pairs = n * n_views, per_pair = (int64_t)nstrips * nyg;
     if (per_pair * ORBIT_VIEWS_PER_LAUNCH > 0x7fffffffLL || pairs > 0x7fffffffLL) return hipErrorInvalidValue;
     hipError_t e;
-    if (lit && (e = launch_orbit_prefix(vols, stride, n, D, H, W, light == LIGHT_POS_Y, workspace, st)) != hipSuccess) return e;
+    if (lit && (e = launch_render_prefix(vols, stride, n, D, H, W, light == SMK_LIGHT_POS_Y, workspace, st)) != hipSuccess) return e;
     for (int64_t p0 = 0; p0 < pairs; p0 += ORBIT_VIEWS_PER_LAUNCH) {
         const int np = (int)(pairs - p0 < ORBIT_VIEWS_PER_LAUNCH ? pairs - p0 : ORBIT_VIEWS_PER_LAUNCH);
         OrbitViews views = {};
@@ -206,62 +162,29 @@ using namespace smk;
 #pragma GCC visibility push(default)
 extern "C" {
 
-static const int64_t ORBIT_MAX_CELLS = (1LL << 31) - (1LL << 16);      // smk_volume_render's limit: 32-bit offsets inside a volume
-static const int64_t ORBIT_MAX_PLANES = 1 << 20;                       // n * n_views of one call (the host forms a (cos, sin) pair for each)
-
-static bool orbit_shape_ok(int32_t D, int32_t H, int32_t W) {
-    return D >= 1 && D <= ORBIT_MAX_DEPTH && H >= 1 && W >= 1 && W <= ORBIT_MAX_WIDTH && (int64_t)D * H * W <= ORBIT_MAX_CELLS;
-}
+static constexpr RenderLimits ORBIT = {ORBIT_MAX_DEPTH, 0, ORBIT_MAX_WIDTH, "orbit views"};
 
 int64_t smk_volume_render_orbit_workspace(int32_t n, int32_t D, int32_t H, int32_t W, int32_t light) {
-    if (n < 1 || !orbit_shape_ok(D, H, W) || light < SMK_LIGHT_NONE || light > SMK_LIGHT_NEG_Y) return -1;
-    return render_orbit_workspace(n, D, H, W, light);
+    return render_query_ok(ORBIT, n, D, H, W, light) ? render_prefix_workspace(n, D, H, W, light) : -1;
 }
 
 int smk_volume_render_orbit(const float *vols, int64_t vol_stride, int32_t n, int32_t D, int32_t H, int32_t W, const smk_render_desc *desc,
                             const double *azimuths, int32_t n_views, float *image, int64_t image_stride, float *transmittance,
                             int64_t trans_stride, void *workspace, int64_t workspace_bytes, void *stream) {
     SMK_REQUIRE(vols && desc && image && azimuths, "null pointer");
-    SMK_REQUIRE(n >= 1 && D >= 1 && H >= 1 && W >= 1 && n_views >= 1, "n, D, H, W, n_views >= 1");
-    SMK_REQUIRE((int64_t)n * n_views <= ORBIT_MAX_PLANES, "n * n_views <= 2^20");
-    if (!orbit_shape_ok(D, H, W)) {
-        set_error("volume_render_orbit: D <= 64, W <= 1024 and D*H*W <= 2^31 - 2^16 are built (got D=" + std::to_string(D) + ", H=" +
-                  std::to_string(H) + ", W=" + std::to_string(W) + ")");
-        return SMK_ERR_UNSUPPORTED;
-    }
-    SMK_REQUIRE(desc->light >= SMK_LIGHT_NONE && desc->light <= SMK_LIGHT_POS_Z, "light: one of smk_light");
-    if (desc->light == SMK_LIGHT_POS_Z) {
-        set_error("volume_render_orbit: SMK_LIGHT_POS_Z is not built for orbit views (a world-fixed +z light seen obliquely is another "
-                  "prefix); SMK_LIGHT_NONE, SMK_LIGHT_POS_Y and SMK_LIGHT_NEG_Y are");
-        return SMK_ERR_UNSUPPORTED;
-    }
-    SMK_REQUIRE(desc->sigma_view >= 0 && desc->sigma_light >= 0 && desc->ambient >= 0 && desc->ambient <= 1 && desc->gain > 0,
-                "sigma_view, sigma_light >= 0; 0 <= ambient <= 1; gain > 0");
-    const int64_t cells = (int64_t)D * H * W, HW = (int64_t)H * W, planes = (int64_t)n * n_views;
-    SMK_REQUIRE(vol_stride >= cells || n == 1, "vol_stride >= D*H*W");
-    SMK_REQUIRE(image_stride >= HW || planes == 1, "image_stride >= H*W");
-    SMK_REQUIRE(transmittance == nullptr || trans_stride >= HW || planes == 1, "trans_stride >= H*W");
-    SMK_REQUIRE(((uintptr_t)vols & 3) == 0 && ((uintptr_t)image & 3) == 0 && ((uintptr_t)transmittance & 3) == 0 &&
-                    ((uintptr_t)workspace & 3) == 0, "4-byte aligned pointers");
+    RenderParams p;
+    int rc = render_check("volume_render_orbit", ORBIT, n, D, H, W, n_views, desc, vols, vol_stride,
+                          {{image, image_stride, false, "image_stride"}, {transmittance, trans_stride, false, "trans_stride"}}, workspace, &p);
+    if (rc != SMK_OK) return rc;
+    const int64_t planes = (int64_t)n * n_views;
     for (int64_t i = 0; i < planes; ++i) SMK_REQUIRE(std::isfinite(azimuths[i]), "azimuths: finite numbers of degrees");
-    const int64_t need = render_orbit_workspace(n, D, H, W, desc->light);
-    SMK_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need),
-                "workspace smaller than smk_volume_render_orbit_workspace(n, D, H, W, light)");
+    rc = render_check_workspace("volume_render_orbit", render_prefix_workspace(n, D, H, W, desc->light), workspace, workspace_bytes);
+    if (rc != SMK_OK) return rc;
     std::vector<float> cs((size_t)planes * 2);
     for (int64_t i = 0; i < planes; ++i) orbit_cos_sin(azimuths[i], &cs[2 * i], &cs[2 * i + 1]);
-    RenderParams p;
-    p.neg_sigma_view = (float)-desc->sigma_view;
-    p.neg_sigma_light = (float)-desc->sigma_light;
-    p.ambient = (float)desc->ambient;
-    p.one_minus_ambient = (float)(1.0 - desc->ambient);
-    p.gain = (float)desc->gain;
-    const hipError_t e = launch_volume_render_orbit(vols, vol_stride, n, D, H, W, desc->light, p, cs.data(), n_views, image, image_stride,
-                                                    transmittance, trans_stride, (float *)workspace, (hipStream_t)stream);
-    if (e != hipSuccess) {
-        set_error(std::string("volume_render_orbit: ") + hipGetErrorString(e));
-        return SMK_ERR_HIP;
-    }
-    return SMK_OK;
+    return render_launch_status("volume_render_orbit",
+                                launch_volume_render_orbit(vols, vol_stride, n, D, H, W, desc->light, p, cs.data(), n_views, image, image_stride,
+                                                           transmittance, trans_stride, (float *)workspace, (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -15,7 +15,7 @@ import ctypes as C
 import math
 import numbers
 from dataclasses import dataclass
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -55,27 +55,134 @@ class RenderSettings:
         return _lib.SmkRenderDesc(float(self.sigma_view), float(self.sigma_light), float(self.ambient), float(self.gain), LIGHTS[self.light])
 
 
-def render_supported(D: int, H: int, W: int) -> bool:
-    """Whether smk_volume_render takes volumes of this shape: 1 <= D <= 64, H, W >= 1, D*H*W <= 2^31 - 2^16."""
+
+
+# ---- what the three renderers share: limits, workspaces, the checked call ------------------------------------------------------------
+ORBIT_MAX_WIDTH = 1024     # csrc/orbit_plan.h ORBIT_MAX_WIDTH
+ORBIT_LIGHTS = ("none", "+y", "-y")
+CAMERA_MAX_WIDTH = 1024    # csrc/camera_plan.h CAMERA_MAX_WIDTH
+CAMERA_MAX_HEIGHT = 65536  # csrc/camera_plan.h CAMERA_MAX_HEIGHT: the image row enters the fp32 positions
+CAMERA_LIGHTS = ORBIT_LIGHTS
+
+
+class _Kind(NamedTuple):
+    """One entry point of the library as this module sees it."""
+    fn: str                 # the public function that error messages name
+    stem: str               # <stem>_supported, <stem>_workspace
+    entry: str              # the entry point ...
+    query: str              # ... and its workspace query
+    max_h: Optional[int]    # None: no limit of its own
+    max_w: Optional[int]
+    lights: tuple
+    forms: str              # the shapes of `vols` it takes
+    dims: tuple
+    what: str = ""          # a moving camera: what a world-fixed light is not built for, and what has no backward yet
+    render: str = ""
+
+    def limits(self) -> str:
+        h = "H >= 1" if self.max_h is None else f"1 <= H <= {self.max_h}"
+        w = "W >= 1" if self.max_w is None else f"1 <= W <= {self.max_w}"
+        return f"1 <= D <= {MAX_DEPTH}, {h}, {w}, at most 2^31 - 2^16 cells"
+
+
+_FRONT = _Kind("render_volumes", "render", "smk_volume_render", "smk_volume_render_workspace", None, None, tuple(sorted(LIGHTS)),
+               "float32 [D,H,W], [n,D,H,W] or [B,T,D,H,W]", (3, 4, 5))
+_BACKWARD = _FRONT._replace(stem="render_backward", entry="smk_volume_render_backward",
+                           query="smk_volume_render_backward_workspace")
+_ORBIT = _Kind("render_orbit", "orbit", "smk_volume_render_orbit", "smk_volume_render_orbit_workspace", None, ORBIT_MAX_WIDTH, ORBIT_LIGHTS,
+               "float32 [D,H,W] or [n,D,H,W]", (3, 4), "orbit views", "orbit")
+_CAMERA = _Kind("render_camera", "camera", "smk_volume_render_camera", "smk_volume_render_camera_workspace", CAMERA_MAX_HEIGHT,
+                CAMERA_MAX_WIDTH, CAMERA_LIGHTS, "float32 [D,H,W] or [n,D,H,W]", (3, 4), "a moving camera", "free-camera")
+
+
+def _within(kind: _Kind, D: int, H: int, W: int) -> bool:
+    return 1 <= D <= MAX_DEPTH and 1 <= H <= (kind.max_h or H) and 1 <= W <= (kind.max_w or W) and D * H * W <= MAX_CELLS
+
+
+def _supported(kind: _Kind, D, H, W) -> bool:
     for v in (D, H, W):
         if isinstance(v, bool) or not isinstance(v, int):
-            raise TypeError(f"render_supported: integer extents, got {v!r}")
-    return 1 <= D <= MAX_DEPTH and H >= 1 and W >= 1 and D * H * W <= MAX_CELLS
+            raise TypeError(f"{kind.stem}_supported: integer extents, got {v!r}")
+    return _within(kind, D, H, W)
+
+
+def _bad_light(kind: _Kind, light) -> ValueError:
+    why = f" is not built for {kind.what} (a world-fixed +z light seen obliquely is another prefix);" if kind.what else ":"
+    return ValueError(f"{kind.fn}: light={light!r}{why} one of {list(kind.lights)}")
+
+
+def _workspace(kind: _Kind, n: int, shape, light: str, device) -> Optional[torch.Tensor]:
+    if light not in kind.lights:
+        raise _bad_light(kind, light)
+    d, h, w = (int(s) for s in shape)
+    if n < 1 or not _within(kind, d, h, w):
+        raise ValueError(f"{kind.fn}: n={n}, shape={tuple(shape)} is not supported (n >= 1, {kind.limits()})")
+    nbytes = getattr(_lib.load(), kind.query)(n, d, h, w, LIGHTS[light])
+    if nbytes < 0:
+        raise ValueError(f"{kind.fn}: n={n}, shape={tuple(shape)}, light={light!r} is not supported")
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device) if nbytes else None
+
+
+def render_supported(D: int, H: int, W: int) -> bool:
+    """Whether smk_volume_render takes volumes of this shape: 1 <= D <= 64, H, W >= 1, D*H*W <= 2^31 - 2^16."""
+    return _supported(_FRONT, D, H, W)
+
+
+def orbit_supported(D: int, H: int, W: int) -> bool:
+    """Whether smk_volume_render_orbit takes volumes of this shape: 1 <= D <= 64, H >= 1, 1 <= W <= 1024, D*H*W <= 2^31 - 2^16."""
+    return _supported(_ORBIT, D, H, W)
+
+
+def camera_supported(D: int, H: int, W: int) -> bool:
+    """Whether smk_volume_render_camera takes volumes of this shape: 1 <= D <= 64, 1 <= H <= 65536, 1 <= W <= 1024,
+    D*H*W <= 2^31 - 2^16."""
+    return _supported(_CAMERA, D, H, W)
 
 
 def render_workspace(n: int, shape, light: str, device) -> Optional[torch.Tensor]:
     """The scratch buffer smk_volume_render wants for n volumes of `shape` = (D, H, W) under `light` (None when it wants none);
     reusable across calls on one stream."""
-    if light not in LIGHTS:
-        raise ValueError(f"light={light!r}: one of {sorted(LIGHTS)}")
-    d, h, w = shape
-    if n < 1 or not render_supported(int(d), int(h), int(w)):
-        raise ValueError(f"render_volumes: n={n}, shape={tuple(shape)} is not supported (n >= 1, 1 <= D <= {MAX_DEPTH}, H, W >= 1, "
-                         f"at most 2^31 - 2^16 cells)")
-    nbytes = _lib.load().smk_volume_render_workspace(n, d, h, w, LIGHTS[light])
-    if nbytes < 0:
-        raise ValueError(f"render_volumes: n={n}, shape={tuple(shape)}, light={light!r} is not supported")
-    return torch.empty(nbytes // 4, dtype=torch.float32, device=device) if nbytes else None
+    return _workspace(_FRONT, n, shape, light, device)
+
+
+def render_backward_workspace(n: int, shape, light: str, device) -> Optional[torch.Tensor]:
+    """The scratch buffer smk_volume_render_backward wants for n volumes of `shape` = (D, H, W) under `light` (None when it wants none:
+    "none" and "+z"); reusable across calls on one stream."""
+    return _workspace(_BACKWARD, n, shape, light, device)
+
+
+def orbit_workspace(n: int, shape, light: str, device) -> Optional[torch.Tensor]:
+    """The scratch buffer smk_volume_render_orbit wants for n volumes of `shape` = (D, H, W) under `light` (None when it wants none:
+    "none"; the prefix along y, n*D*H*W floats, under "+y" / "-y"); the same for any number of views; reusable on one stream."""
+    return _workspace(_ORBIT, n, shape, light, device)
+
+
+def camera_workspace(n: int, shape, light: str, device) -> Optional[torch.Tensor]:
+    """The scratch buffer smk_volume_render_camera wants for n volumes of `shape` = (D, H, W) under `light` (None when it wants none:
+    "none"; the prefix along y, n*D*H*W floats, under "+y" / "-y"); the same for any number of views; reusable on one stream."""
+    return _workspace(_CAMERA, n, shape, light, device)
+
+
+def _ray_samples(q: int, D: int) -> int:
+    """The smallest integer >= sqrt(q) with the parity of D (csrc/view_plan.h ray_samples)."""
+    s = math.isqrt(q)
+    s += s * s < q
+    return s + ((s - D) & 1)
+
+
+def orbit_samples(D: int, W: int) -> int:
+    """S, the samples on a ray of an orbit view: the smallest integer >= hypot(D, W) with the parity of D (csrc/orbit_plan.h)."""
+    if D < 1 or W < 1:
+        raise ValueError(f"orbit_samples: D, W >= 1, got {(D, W)}")
+    return _ray_samples(D * D + W * W, D)
+
+
+def camera_samples(D: int, H: int, W: int) -> int:
+    """S, the samples on a ray of a free-camera view: the smallest integer >= sqrt(D^2 + H^2 + W^2) with the parity of D
+    (csrc/camera_plan.h)."""
+    if D < 1 or H < 1 or W < 1:
+        raise ValueError(f"camera_samples: D, H, W >= 1, got {(D, H, W)}")
+    return _ray_samples(D * D + H * H + W * W, D)
 
 
 def _dense(v: torch.Tensor) -> bool:
@@ -102,49 +209,138 @@ def _runs(lead_shape, lead_stride, cells):
     return [(r[0], dims[-1][0], dims[-1][1]) for r in runs]
 
 
-def render_backward_workspace(n: int, shape, light: str, device) -> Optional[torch.Tensor]:
-    """The scratch buffer smk_volume_render_backward wants for n volumes of `shape` = (D, H, W) under `light` (None when it wants none:
-    "none" and "+z"); reusable across calls on one stream."""
-    if light not in LIGHTS:
-        raise ValueError(f"light={light!r}: one of {sorted(LIGHTS)}")
-    d, h, w = shape
-    if n < 1 or not render_supported(int(d), int(h), int(w)):
-        raise ValueError(f"render_volumes: n={n}, shape={tuple(shape)} is not supported (n >= 1, 1 <= D <= {MAX_DEPTH}, H, W >= 1, "
-                         f"at most 2^31 - 2^16 cells)")
-    nbytes = _lib.load().smk_volume_render_backward_workspace(n, d, h, w, LIGHTS[light])
-    if nbytes < 0:
-        raise ValueError(f"render_volumes: n={n}, shape={tuple(shape)}, light={light!r} is not supported")
-    return torch.empty(nbytes // 4, dtype=torch.float32, device=device) if nbytes else None
+def _angle(value, n: int, name: str, fn: str = "render_camera"):
+    """One angle argument in one of its three forms -> a float64 host tensor of 0, 1 ([V]) or 2 ([n, V]) dimensions."""
+    forms = f"{fn}: {name} is a number of degrees, a sequence of them or an [n, V] array"
+    if isinstance(value, bool):
+        raise ValueError(forms)
+    try:
+        t = value.detach().to("cpu", torch.float64) if isinstance(value, torch.Tensor) else torch.as_tensor(value, dtype=torch.float64)
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise ValueError(f"{forms} ({e})") from None
+    if not (t.dim() == 0 or (t.dim() == 1 and t.numel() >= 1) or (t.dim() == 2 and t.shape[0] == n and t.shape[1] >= 1)):
+        raise ValueError(f"{fn}: {name} of shape {tuple(t.shape)}: a number, a sequence of V >= 1 numbers or an [n={n}, V] array")
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError(f"{fn}: {name}s must be finite numbers of degrees")
+    return t
+
+
+def _tables(angles, n: int, fn: str):
+    """Angle arguments out of _angle, paired -> (an [n][V] float64 host tensor of each, whether the result has a view dimension)."""
+    counts = {int(t.shape[-1]) for t in angles if t.dim() > 0}
+    if len(counts) > 1:
+        raise ValueError(f"{fn}: azimuth and elevation are paired view by view: " + " against ".join(str(tuple(t.shape)) for t in angles))
+    views, V = bool(counts), counts.pop() if counts else 1
+    return [(t.reshape(1, -1) if t.dim() < 2 else t).expand(n, V).contiguous() for t in angles], views
+
+
+def _camera_angles(azimuth, elevation, n: int):
+    """The two angle arguments, paired -> ([n][V] azimuths, [n][V] elevations as float64 host tensors, whether the result has a view
+    dimension)."""
+    az, el = _angle(azimuth, n, "azimuth"), _angle(elevation, n, "elevation")
+    if bool(((el < -90.0) | (el > 90.0)).any()):
+        raise ValueError("render_camera: elevations must lie in [-90, 90] degrees")
+    (az, el), views = _tables((az, el), n, "render_camera")
+    return az, el, views
+
+
+def _call_workspace(kind: _Kind, biggest: int, shape, light: str, workspace, dev):
+    """The workspace of one call whose longest run has `biggest` volumes: (tensor or None, its bytes or 0); `workspace`: the caller's."""
+    need = getattr(_lib.load(), kind.query)(biggest, *shape, LIGHTS[light])
+    if need < 0:
+        raise ValueError(f"{kind.fn}: {biggest} volumes of {tuple(shape)} are not supported")
+    if not need:
+        return None, 0
+    if workspace is None:
+        workspace = torch.empty(need // 4, dtype=torch.float32, device=dev)
+    if workspace.device != dev or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need:
+        raise ValueError(f"{kind.fn}: workspace of {need} bytes needed on {dev} ({kind.stem}_workspace)")
+    return workspace, workspace.numel() * workspace.element_size()
+
+
+def _each_run(kind: _Kind, vols, runs, shape, settings, middle, workspace, nbytes):
+    """Hand every run of equally spaced volumes to the entry point.  middle(done, count): the arguments between desc and the workspace
+    for the run's `count` volumes, `done` volumes into the call: angles, and the (pointer, stride) of every buffer."""
+    D, H, W = shape
+    cells = D * H * W
+    entry = getattr(_lib.load(), kind.entry)
+    desc = C.byref(settings.desc())
+    tail = (workspace.data_ptr() if nbytes else None, nbytes, _lib.stream_ptr(vols.device))
+    base = vols.data_ptr()
+    done = 0
+    for off, count, stride in runs:
+        _lib.check(entry(base + 4 * off, stride if count > 1 else cells, count, D, H, W, desc, *middle(done, count), *tail))
+        done += count
+
+
+def _forward(kind: _Kind, vols, settings, angles, *, transmittance, out, workspace):
+    """The call path of the three forward renders.  angles: None (the front view) or n -> (the [n][V] tables that the entry point takes,
+    whether the result has a view dimension); it runs where the moving cameras parse their angles."""
+    settings = RenderSettings() if settings is None else settings
+    if not isinstance(settings, RenderSettings):
+        raise TypeError(f"{kind.fn}: settings must be a RenderSettings")
+    if settings.light not in kind.lights:
+        raise _bad_light(kind, settings.light)
+    if angles is None:
+        dev = _lib.require_cuda(vols.device, kind.fn)
+    if not isinstance(vols, torch.Tensor) or vols.dim() not in kind.dims or vols.dtype != torch.float32:
+        raise ValueError(f"{kind.fn}: {kind.forms}")
+    shape = D, H, W = tuple(int(s) for s in vols.shape[-3:])
+    lead = tuple(vols.shape[:-3])
+    n = math.prod(lead)
+    if n < 1:
+        raise ValueError(f"{kind.fn}: shape {tuple(vols.shape)}: at least one volume")
+    tables, views = ((), False) if angles is None else angles(n)
+    if angles is not None:
+        if torch.is_grad_enabled() and vols.requires_grad:
+            raise RuntimeError(f"{kind.fn}: the {kind.render} render has no backward yet, and the volumes require a gradient; call under "
+                               "torch.no_grad() or detach them (render_volumes, the front view, is differentiable)")
+        dev = _lib.require_cuda(vols.device, kind.fn)
+    if not _within(kind, D, H, W):
+        raise ValueError(f"{kind.fn}: shape {tuple(vols.shape)} is not supported ({kind.limits()} per volume)")
+    if vols.is_contiguous():                       # the usual case: nothing to check, and what _runs makes of it
+        runs = [(0, n, D * H * W)]
+    else:
+        if not _dense(vols):
+            raise ValueError(f"{kind.fn}: every volume must be dense ([D][H][W] with strides (H*W, W, 1)); only the batch may be strided")
+        if any(st < 0 for st in vols.stride()[:-3]):
+            raise ValueError(f"{kind.fn}: negative batch strides")
+        runs = _runs(lead, vols.stride()[:-3], D * H * W)
+    V = int(tables[0].shape[1]) if tables else 1
+    oshape = lead + ((V,) if views else ()) + (H, W)
+    if out is None:
+        out = torch.empty(oshape, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != oshape or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"{kind.fn}: out must be a contiguous float32 tensor of shape {oshape} on {dev}")
+    trans = torch.empty(oshape, dtype=torch.float32, device=dev) if transmittance else None
+    workspace, nbytes = _call_workspace(kind, max(r[1] for r in runs), shape, settings.light, workspace, dev)
+    flat, n_views = [t.reshape(-1).tolist() for t in tables], (V,) if tables else ()
+    HW, obase, tbase = H * W, out.data_ptr(), trans.data_ptr() if transmittance else None
+
+    def middle(done, count):                       # the run's angles and V (nothing for the front view), image, transmittance
+        angles = [(C.c_double * (count * V))(*f[done * V:(done + count) * V]) for f in flat]
+        at = 4 * done * V * HW
+        return (*angles, *n_views, obase + at, HW, tbase and tbase + at, HW)
+    _each_run(kind, vols, runs, shape, settings, middle, workspace, nbytes)
+    return (out, trans) if transmittance else out
 
 
 def _render_backward(vols: torch.Tensor, settings: RenderSettings, grad_image, grad_trans) -> torch.Tensor:
     """smk_volume_render_backward over the runs of `vols` (checked by render_volumes): the gradient in vols' shape, contiguous.
     grad_image / grad_trans: the leading dimensions + [H, W], or None (= zero); not both None."""
-    dev = vols.device
-    D, H, W = (int(s) for s in vols.shape[-3:])
+    shape = D, H, W = tuple(int(s) for s in vols.shape[-3:])
     lead = tuple(vols.shape[:-3])
     cells, HW = D * H * W, H * W
     gi = None if grad_image is None else grad_image.to(torch.float32).contiguous()
     gt = None if grad_trans is None else grad_trans.to(torch.float32).contiguous()
-    grad = torch.empty(lead + (D, H, W), dtype=torch.float32, device=dev)           # every element is written exactly once
+    grad = torch.empty(lead + shape, dtype=torch.float32, device=vols.device)      # every element is written exactly once
     runs = _runs(lead, vols.stride()[:-3], cells)
-    biggest = max(r[1] for r in runs)
-    L = _lib.load()
-    need = L.smk_volume_render_backward_workspace(biggest, D, H, W, LIGHTS[settings.light])
-    if need < 0:
-        raise ValueError(f"render_volumes: {biggest} volumes of {(D, H, W)} are not supported")
-    ws = torch.empty(need // 4, dtype=torch.float32, device=dev) if need else None
-    desc = settings.desc()
-    st = _lib.stream_ptr(dev)
-    base, gbase = vols.data_ptr(), grad.data_ptr()
-    ibase, tbase = (0 if gi is None else gi.data_ptr()), (0 if gt is None else gt.data_ptr())
-    done = 0
-    for off, count, stride in runs:
-        _lib.check(L.smk_volume_render_backward(base + 4 * off, stride if count > 1 else cells, count, D, H, W, C.byref(desc),
-                                                (ibase + 4 * done * HW) if gi is not None else None, HW,
-                                                (tbase + 4 * done * HW) if gt is not None else None, HW,
-                                                gbase + 4 * done * cells, cells, ws.data_ptr() if need else None, need, st))
-        done += count
+    ws, nbytes = _call_workspace(_BACKWARD, max(r[1] for r in runs), shape, settings.light, None, vols.device)
+    ibase, tbase, gbase = gi is not None and gi.data_ptr(), gt is not None and gt.data_ptr(), grad.data_ptr()
+
+    def middle(done, count):                       # the upstream gradients (None: zero) and the result
+        return (ibase and ibase + 4 * done * HW, HW, tbase and tbase + 4 * done * HW, HW, gbase + 4 * done * cells, cells)
+    _each_run(_BACKWARD, vols, runs, shape, settings, middle, ws, nbytes)
     return grad
 
 
@@ -192,107 +388,7 @@ def render_volumes(vols: torch.Tensor, settings: Optional[RenderSettings] = None
 
 def _render(vols, settings, *, transmittance, out, workspace):
     """The plain path of render_volumes (its checks and the calls of smk_volume_render)."""
-    settings = RenderSettings() if settings is None else settings
-    if not isinstance(settings, RenderSettings):
-        raise TypeError("render_volumes: settings must be a RenderSettings")
-    dev = _lib.require_cuda(vols.device, "render_volumes")
-    if vols.dim() not in (3, 4, 5) or vols.dtype != torch.float32:
-        raise ValueError("render_volumes: float32 [D,H,W], [n,D,H,W] or [B,T,D,H,W]")
-    D, H, W = (int(s) for s in vols.shape[-3:])
-    lead = tuple(vols.shape[:-3])
-    n = math.prod(lead)
-    if n < 1 or not render_supported(D, H, W):
-        raise ValueError(f"render_volumes: shape {tuple(vols.shape)} is not supported (at least one volume, 1 <= D <= {MAX_DEPTH}, H, W >= 1, "
-                         f"at most 2^31 - 2^16 cells per volume)")
-    if not _dense(vols):
-        raise ValueError("render_volumes: every volume must be dense ([D][H][W] with strides (H*W, W, 1)); only the batch may be strided")
-    if any(st < 0 for st in vols.stride()[:-3]):
-        raise ValueError("render_volumes: negative batch strides")
-    if out is None:
-        out = torch.empty(lead + (H, W), dtype=torch.float32, device=dev)
-    elif out.dtype != torch.float32 or tuple(out.shape) != lead + (H, W) or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"render_volumes: out must be a contiguous float32 tensor of shape {lead + (H, W)} on {dev}")
-    trans = torch.empty(lead + (H, W), dtype=torch.float32, device=dev) if transmittance else None
-    cells, HW = D * H * W, H * W
-    runs = _runs(lead, vols.stride()[:-3], cells)
-    biggest = max(r[1] for r in runs)
-    L = _lib.load()
-    need = L.smk_volume_render_workspace(biggest, D, H, W, LIGHTS[settings.light])
-    if need < 0:
-        raise ValueError(f"render_volumes: {biggest} volumes of {(D, H, W)} are not supported")
-    if need and workspace is None:
-        workspace = torch.empty(need // 4, dtype=torch.float32, device=dev)
-    if need and (workspace.device != dev or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need):
-        raise ValueError(f"render_volumes: workspace of {need} bytes needed on {dev} (render_workspace)")
-    desc = settings.desc()
-    st = _lib.stream_ptr(dev)
-    base, obase, tbase = vols.data_ptr(), out.data_ptr(), trans.data_ptr() if transmittance else 0
-    done = 0
-    for off, count, stride in runs:
-        _lib.check(L.smk_volume_render(base + 4 * off, stride if count > 1 else cells, count, D, H, W, C.byref(desc),
-                                       obase + 4 * done * HW, HW, (tbase + 4 * done * HW) if transmittance else None, HW,
-                                       workspace.data_ptr() if need else None, workspace.numel() * workspace.element_size() if need else 0, st))
-        done += count
-    return (out, trans) if transmittance else out
-
-
-# ---- orbit views (SPEC_3D.md section 10, "Orbit views"; csrc/render_orbit.hip, smk_volume_render_orbit) ------------------------------
-ORBIT_MAX_WIDTH = 1024     # csrc/orbit_plan.h ORBIT_MAX_WIDTH
-ORBIT_LIGHTS = ("none", "+y", "-y")
-
-
-def orbit_supported(D: int, H: int, W: int) -> bool:
-    """Whether smk_volume_render_orbit takes volumes of this shape: 1 <= D <= 64, H >= 1, 1 <= W <= 1024, D*H*W <= 2^31 - 2^16."""
-    for v in (D, H, W):
-        if isinstance(v, bool) or not isinstance(v, int):
-            raise TypeError(f"orbit_supported: integer extents, got {v!r}")
-    return 1 <= D <= MAX_DEPTH and H >= 1 and 1 <= W <= ORBIT_MAX_WIDTH and D * H * W <= MAX_CELLS
-
-
-def orbit_samples(D: int, W: int) -> int:
-    """S, the samples on a ray of an orbit view: the smallest integer >= hypot(D, W) with the parity of D (csrc/orbit_plan.h)."""
-    if D < 1 or W < 1:
-        raise ValueError(f"orbit_samples: D, W >= 1, got {(D, W)}")
-    q = D * D + W * W
-    s = math.isqrt(q)
-    s += s * s < q
-    return s + ((s - D) & 1)
-
-
-def orbit_workspace(n: int, shape, light: str, device) -> Optional[torch.Tensor]:
-    """The scratch buffer smk_volume_render_orbit wants for n volumes of `shape` = (D, H, W) under `light` (None when it wants none:
-    "none"; the prefix along y, n*D*H*W floats, under "+y" / "-y"); the same for any number of views; reusable on one stream."""
-    if light not in ORBIT_LIGHTS:
-        raise ValueError(f"render_orbit: light={light!r}: one of {list(ORBIT_LIGHTS)} (a world-fixed '+z' light is not built for orbit views)")
-    d, h, w = (int(s) for s in shape)
-    if n < 1 or not orbit_supported(d, h, w):
-        raise ValueError(f"render_orbit: n={n}, shape={tuple(shape)} is not supported (n >= 1, 1 <= D <= {MAX_DEPTH}, H >= 1, "
-                         f"1 <= W <= {ORBIT_MAX_WIDTH}, at most 2^31 - 2^16 cells)")
-    nbytes = _lib.load().smk_volume_render_orbit_workspace(n, d, h, w, LIGHTS[light])
-    if nbytes < 0:
-        raise ValueError(f"render_orbit: n={n}, shape={tuple(shape)}, light={light!r} is not supported")
-    return torch.empty(nbytes // 4, dtype=torch.float32, device=device) if nbytes else None
-
-
-def _azimuths(azimuth, n: int):
-    """azimuth in one of its three forms -> ([n][V] doubles on the host as a float64 tensor, whether the result has a view dimension)."""
-    if isinstance(azimuth, bool):
-        raise ValueError("render_orbit: azimuth is a number of degrees, a sequence of them or an [n, V] array")
-    try:
-        t = azimuth.detach().to("cpu", torch.float64) if isinstance(azimuth, torch.Tensor) else torch.as_tensor(azimuth, dtype=torch.float64)
-    except (TypeError, ValueError, RuntimeError) as e:
-        raise ValueError(f"render_orbit: azimuth is a number of degrees, a sequence of them or an [n, V] array ({e})") from None
-    if t.dim() == 0:
-        table, views = t.reshape(1, 1).expand(n, 1), False
-    elif t.dim() == 1 and t.numel() >= 1:
-        table, views = t.reshape(1, -1).expand(n, t.numel()), True
-    elif t.dim() == 2 and t.shape[0] == n and t.shape[1] >= 1:
-        table, views = t, True
-    else:
-        raise ValueError(f"render_orbit: azimuth of shape {tuple(t.shape)}: a number, a sequence of V >= 1 numbers or an [n={n}, V] array")
-    if not bool(torch.isfinite(table).all()):
-        raise ValueError("render_orbit: azimuths must be finite numbers of degrees")
-    return table.contiguous(), views
+    return _forward(_FRONT, vols, settings, None, transmittance=transmittance, out=out, workspace=workspace)
 
 
 def render_orbit(vols: torch.Tensor, azimuth, settings: Optional[RenderSettings] = None, *, transmittance: bool = False,
@@ -306,134 +402,8 @@ def render_orbit(vols: torch.Tensor, azimuth, settings: Optional[RenderSettings]
     "none", "+y", "-y" ("+z" raises ValueError).  out: a contiguous float32 tensor of the image's shape to write into.  workspace:
     orbit_workspace(...) of at least this call's size.  One call renders all the views.  There is no backward yet: volumes that require a
     gradient raise RuntimeError (call under torch.no_grad() or detach them)."""
-    settings = RenderSettings() if settings is None else settings
-    if not isinstance(settings, RenderSettings):
-        raise TypeError("render_orbit: settings must be a RenderSettings")
-    if settings.light not in ORBIT_LIGHTS:
-        raise ValueError(f"render_orbit: light={settings.light!r} is not built for orbit views (a world-fixed +z light seen obliquely is "
-                         f"another prefix); one of {list(ORBIT_LIGHTS)}")
-    if not isinstance(vols, torch.Tensor) or vols.dim() not in (3, 4) or vols.dtype != torch.float32:
-        raise ValueError("render_orbit: float32 [D,H,W] or [n,D,H,W]")
-    D, H, W = (int(s) for s in vols.shape[-3:])
-    lead = tuple(vols.shape[:-3])
-    n = math.prod(lead)
-    if n < 1:
-        raise ValueError(f"render_orbit: shape {tuple(vols.shape)}: at least one volume")
-    table, views = _azimuths(azimuth, n)
-    V = int(table.shape[1])
-    if torch.is_grad_enabled() and vols.requires_grad:
-        raise RuntimeError("render_orbit: the orbit render has no backward yet, and the volumes require a gradient; call under "
-                           "torch.no_grad() or detach them (render_volumes, the front view, is differentiable)")
-    dev = _lib.require_cuda(vols.device, "render_orbit")
-    if not orbit_supported(D, H, W):
-        raise ValueError(f"render_orbit: shape {tuple(vols.shape)} is not supported (1 <= D <= {MAX_DEPTH}, H >= 1, 1 <= W <= {ORBIT_MAX_WIDTH}, "
-                         f"at most 2^31 - 2^16 cells per volume)")
-    if not _dense(vols):
-        raise ValueError("render_orbit: every volume must be dense ([D][H][W] with strides (H*W, W, 1)); only the batch may be strided")
-    if any(st < 0 for st in vols.stride()[:-3]):
-        raise ValueError("render_orbit: negative batch strides")
-    shape = lead + ((V,) if views else ()) + (H, W)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=dev)
-    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"render_orbit: out must be a contiguous float32 tensor of shape {shape} on {dev}")
-    trans = torch.empty(shape, dtype=torch.float32, device=dev) if transmittance else None
-    cells, HW = D * H * W, H * W
-    runs = _runs(lead, vols.stride()[:-3], cells)
-    biggest = max(r[1] for r in runs)
-    L = _lib.load()
-    need = L.smk_volume_render_orbit_workspace(biggest, D, H, W, LIGHTS[settings.light])
-    if need < 0:
-        raise ValueError(f"render_orbit: {biggest} volumes of {(D, H, W)} are not supported")
-    if need and workspace is None:
-        workspace = torch.empty(need // 4, dtype=torch.float32, device=dev)
-    if need and (workspace.device != dev or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need):
-        raise ValueError(f"render_orbit: workspace of {need} bytes needed on {dev} (orbit_workspace)")
-    desc = settings.desc()
-    st = _lib.stream_ptr(dev)
-    base, obase, tbase = vols.data_ptr(), out.data_ptr(), trans.data_ptr() if transmittance else 0
-    flat = table.reshape(-1).tolist()
-    done = 0
-    for off, count, stride in runs:
-        az = (C.c_double * (count * V))(*flat[done * V:(done + count) * V])
-        _lib.check(L.smk_volume_render_orbit(base + 4 * off, stride if count > 1 else cells, count, D, H, W, C.byref(desc), az, V,
-                                             obase + 4 * done * V * HW, HW, (tbase + 4 * done * V * HW) if transmittance else None, HW,
-                                             workspace.data_ptr() if need else None, workspace.numel() * workspace.element_size() if need else 0,
-                                             st))
-        done += count
-    return (out, trans) if transmittance else out
-
-
-# ---- free camera (SPEC_3D.md section 10, "Free camera"; csrc/render_camera.hip, smk_volume_render_camera) -----------------------------
-CAMERA_MAX_WIDTH = 1024    # csrc/camera_plan.h CAMERA_MAX_WIDTH
-CAMERA_MAX_HEIGHT = 65536  # csrc/camera_plan.h CAMERA_MAX_HEIGHT: the image row enters the fp32 positions
-CAMERA_LIGHTS = ORBIT_LIGHTS
-
-
-def camera_supported(D: int, H: int, W: int) -> bool:
-    """Whether smk_volume_render_camera takes volumes of this shape: 1 <= D <= 64, 1 <= H <= 65536, 1 <= W <= 1024,
-    D*H*W <= 2^31 - 2^16."""
-    for v in (D, H, W):
-        if isinstance(v, bool) or not isinstance(v, int):
-            raise TypeError(f"camera_supported: integer extents, got {v!r}")
-    return 1 <= D <= MAX_DEPTH and 1 <= H <= CAMERA_MAX_HEIGHT and 1 <= W <= CAMERA_MAX_WIDTH and D * H * W <= MAX_CELLS
-
-
-def camera_samples(D: int, H: int, W: int) -> int:
-    """S, the samples on a ray of a free-camera view: the smallest integer >= sqrt(D^2 + H^2 + W^2) with the parity of D
-    (csrc/camera_plan.h)."""
-    if D < 1 or H < 1 or W < 1:
-        raise ValueError(f"camera_samples: D, H, W >= 1, got {(D, H, W)}")
-    q = D * D + H * H + W * W
-    s = math.isqrt(q)
-    s += s * s < q
-    return s + ((s - D) & 1)
-
-
-def camera_workspace(n: int, shape, light: str, device) -> Optional[torch.Tensor]:
-    """The scratch buffer smk_volume_render_camera wants for n volumes of `shape` = (D, H, W) under `light` (None when it wants none:
-    "none"; the prefix along y, n*D*H*W floats, under "+y" / "-y"); the same for any number of views; reusable on one stream."""
-    if light not in CAMERA_LIGHTS:
-        raise ValueError(f"render_camera: light={light!r}: one of {list(CAMERA_LIGHTS)} (a world-fixed '+z' light is not built for a "
-                         f"moving camera)")
-    d, h, w = (int(s) for s in shape)
-    if n < 1 or not camera_supported(d, h, w):
-        raise ValueError(f"render_camera: n={n}, shape={tuple(shape)} is not supported (n >= 1, 1 <= D <= {MAX_DEPTH}, "
-                         f"1 <= H <= {CAMERA_MAX_HEIGHT}, 1 <= W <= {CAMERA_MAX_WIDTH}, at most 2^31 - 2^16 cells)")
-    nbytes = _lib.load().smk_volume_render_camera_workspace(n, d, h, w, LIGHTS[light])
-    if nbytes < 0:
-        raise ValueError(f"render_camera: n={n}, shape={tuple(shape)}, light={light!r} is not supported")
-    return torch.empty(nbytes // 4, dtype=torch.float32, device=device) if nbytes else None
-
-
-def _angle(value, n: int, name: str):
-    """One angle argument in one of its three forms -> a float64 host tensor of 0, 1 ([V]) or 2 ([n, V]) dimensions."""
-    forms = f"render_camera: {name} is a number of degrees, a sequence of them or an [n, V] array"
-    if isinstance(value, bool):
-        raise ValueError(forms)
-    try:
-        t = value.detach().to("cpu", torch.float64) if isinstance(value, torch.Tensor) else torch.as_tensor(value, dtype=torch.float64)
-    except (TypeError, ValueError, RuntimeError) as e:
-        raise ValueError(f"{forms} ({e})") from None
-    if not (t.dim() == 0 or (t.dim() == 1 and t.numel() >= 1) or (t.dim() == 2 and t.shape[0] == n and t.shape[1] >= 1)):
-        raise ValueError(f"render_camera: {name} of shape {tuple(t.shape)}: a number, a sequence of V >= 1 numbers or an [n={n}, V] array")
-    if not bool(torch.isfinite(t).all()):
-        raise ValueError(f"render_camera: {name}s must be finite numbers of degrees")
-    return t
-
-
-def _camera_angles(azimuth, elevation, n: int):
-    """The two angle arguments, paired -> ([n][V] azimuths, [n][V] elevations as float64 host tensors, whether the result has a view
-    dimension)."""
-    az, el = _angle(azimuth, n, "azimuth"), _angle(elevation, n, "elevation")
-    if bool(((el < -90.0) | (el > 90.0)).any()):
-        raise ValueError("render_camera: elevations must lie in [-90, 90] degrees")
-    counts = {int(t.shape[-1]) for t in (az, el) if t.dim() > 0}
-    if len(counts) > 1:
-        raise ValueError(f"render_camera: azimuth and elevation are paired view by view: {tuple(az.shape)} against {tuple(el.shape)}")
-    V = counts.pop() if counts else 1
-    tables = [(t.reshape(1, -1) if t.dim() < 2 else t).expand(n, V).contiguous() for t in (az, el)]
-    return tables[0], tables[1], az.dim() > 0 or el.dim() > 0
+    return _forward(_ORBIT, vols, settings, lambda n: _tables((_angle(azimuth, n, "azimuth", "render_orbit"),), n, "render_orbit"),
+                    transmittance=transmittance, out=out, workspace=workspace)
 
 
 def render_camera(vols: torch.Tensor, azimuth, elevation, settings: Optional[RenderSettings] = None, *, transmittance: bool = False,
@@ -450,60 +420,7 @@ def render_camera(vols: torch.Tensor, azimuth, elevation, settings: Optional[Ren
     contiguous float32 tensor of the image's shape to write into.  workspace: camera_workspace(...) of at least this call's size.  One
     call renders all the views.  elevation=0 is the orbit's view on a longer ray: close to render_orbit's image, not equal to it.  There is
     no backward yet: volumes that require a gradient raise RuntimeError (call under torch.no_grad() or detach them)."""
-    settings = RenderSettings() if settings is None else settings
-    if not isinstance(settings, RenderSettings):
-        raise TypeError("render_camera: settings must be a RenderSettings")
-    if settings.light not in CAMERA_LIGHTS:
-        raise ValueError(f"render_camera: light={settings.light!r} is not built for a moving camera (a world-fixed +z light seen obliquely "
-                         f"is another prefix); one of {list(CAMERA_LIGHTS)}")
-    if not isinstance(vols, torch.Tensor) or vols.dim() not in (3, 4) or vols.dtype != torch.float32:
-        raise ValueError("render_camera: float32 [D,H,W] or [n,D,H,W]")
-    D, H, W = (int(s) for s in vols.shape[-3:])
-    lead = tuple(vols.shape[:-3])
-    n = math.prod(lead)
-    if n < 1:
-        raise ValueError(f"render_camera: shape {tuple(vols.shape)}: at least one volume")
-    az_table, el_table, views = _camera_angles(azimuth, elevation, n)
-    V = int(az_table.shape[1])
-    if torch.is_grad_enabled() and vols.requires_grad:
-        raise RuntimeError("render_camera: the free-camera render has no backward yet, and the volumes require a gradient; call under "
-                           "torch.no_grad() or detach them (render_volumes, the front view, is differentiable)")
-    dev = _lib.require_cuda(vols.device, "render_camera")
-    if not camera_supported(D, H, W):
-        raise ValueError(f"render_camera: shape {tuple(vols.shape)} is not supported (1 <= D <= {MAX_DEPTH}, 1 <= H <= {CAMERA_MAX_HEIGHT}, "
-                         f"1 <= W <= {CAMERA_MAX_WIDTH}, at most 2^31 - 2^16 cells per volume)")
-    if not _dense(vols):
-        raise ValueError("render_camera: every volume must be dense ([D][H][W] with strides (H*W, W, 1)); only the batch may be strided")
-    if any(st < 0 for st in vols.stride()[:-3]):
-        raise ValueError("render_camera: negative batch strides")
-    shape = lead + ((V,) if views else ()) + (H, W)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=dev)
-    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"render_camera: out must be a contiguous float32 tensor of shape {shape} on {dev}")
-    trans = torch.empty(shape, dtype=torch.float32, device=dev) if transmittance else None
-    cells, HW = D * H * W, H * W
-    runs = _runs(lead, vols.stride()[:-3], cells)
-    biggest = max(r[1] for r in runs)
-    L = _lib.load()
-    need = L.smk_volume_render_camera_workspace(biggest, D, H, W, LIGHTS[settings.light])
-    if need < 0:
-        raise ValueError(f"render_camera: {biggest} volumes of {(D, H, W)} are not supported")
-    if need and workspace is None:
-        workspace = torch.empty(need // 4, dtype=torch.float32, device=dev)
-    if need and (workspace.device != dev or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need):
-        raise ValueError(f"render_camera: workspace of {need} bytes needed on {dev} (camera_workspace)")
-    desc = settings.desc()
-    st = _lib.stream_ptr(dev)
-    base, obase, tbase = vols.data_ptr(), out.data_ptr(), trans.data_ptr() if transmittance else 0
-    flat_az, flat_el = az_table.reshape(-1).tolist(), el_table.reshape(-1).tolist()
-    done = 0
-    for off, count, stride in runs:
-        az = (C.c_double * (count * V))(*flat_az[done * V:(done + count) * V])
-        el = (C.c_double * (count * V))(*flat_el[done * V:(done + count) * V])
-        _lib.check(L.smk_volume_render_camera(base + 4 * off, stride if count > 1 else cells, count, D, H, W, C.byref(desc), az, el, V,
-                                              obase + 4 * done * V * HW, HW, (tbase + 4 * done * V * HW) if transmittance else None, HW,
-                                              workspace.data_ptr() if need else None,
-                                              workspace.numel() * workspace.element_size() if need else 0, st))
-        done += count
-    return (out, trans) if transmittance else out
+    def angles(n):
+        az, el, views = _camera_angles(azimuth, elevation, n)
+        return (az, el), views
+    return _forward(_CAMERA, vols, settings, angles, transmittance=transmittance, out=out, workspace=workspace)
