@@ -377,6 +377,17 @@ int smk_image_quality(const float *pred, int64_t pred_stride, const float *targe
                       int32_t W, int32_t window, double c1, double c2, void *workspace, int64_t workspace_bytes, double *ssim_sum,
                       double *sqerr_sum, void *stream);
 
+/* The gradient of smk_image_quality's SSIM with respect to pred (DESIGN.md 8.1 "Gradient"): with plane_grad [n] the upstream gradient
+ * of each plane's MEAN SSIM (ssim_sum / (H W)), dpred [n][H][W] (dense rows, plane stride dpred_stride floats) receives
+ * d(sum_i plane_grad[i] mean_ssim[i]) / d pred.  Same planes, strides, window and stabilisers as the forward; fp32 per pixel, direct
+ * k-term sums in a fixed order, no atomics: every element of dpred is written exactly once (no need to zero it), results repeat bit for
+ * bit and a plane's result does not depend on the others of its call.  workspace: device memory of at least
+ * smk_image_quality_backward_workspace(n, H, W) bytes (3 n H W floats), passed with its size.  No gradient for target. */
+int64_t smk_image_quality_backward_workspace(int32_t n, int32_t H, int32_t W);
+int smk_image_quality_backward(const float *pred, int64_t pred_stride, const float *target, int64_t target_stride, int32_t n, int32_t H,
+                               int32_t W, int32_t window, double c1, double c2, const float *plane_grad, void *workspace,
+                               int64_t workspace_bytes, float *dpred, int64_t dpred_stride, void *stream);
+
 /* ------------------------------------------------------------------ optical-flow baselines
  * The reference's benchmark.py compares the model with cv2.calcOpticalFlowFarneback, cv2.goodFeaturesToTrack +
  * cv2.calcOpticalFlowPyrLK and cv2.remap.  These entry points implement the published algorithms with the reference's call parameters

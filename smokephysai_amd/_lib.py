@@ -124,6 +124,8 @@ _SIGNATURES = {
                            C.c_void_p, C.c_void_p],
     "smk_image_quality": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                           C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "smk_image_quality_backward": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                                   C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p],
     "smk_flow_level_image": [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
     "smk_flow_poly_exp": [C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p, C.c_void_p],
     "smk_flow_farneback_iteration": [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p, C.c_int64, C.c_void_p],
@@ -202,7 +204,7 @@ _SIGNATURES = {
     "smk_linear_forward": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                            C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p],
 }
-EXPORTS = ["smk_abi_version", "smk_last_error", "smk_linear_wgrad_workspace", "smk_bn_train_workspace", "smk_layernorm_bwd_workspace", "smk_conv2_train_workspace", "smk_conv2_train_wgrad_workspace", "smk_conv1_train_wgrad_workspace", "smk_attention_workspace_bytes", "smk_linear_ln_max_rows", "smk_image_quality_workspace", "smk_convt4s2_train_wgrad_workspace",
+EXPORTS = ["smk_abi_version", "smk_last_error", "smk_linear_wgrad_workspace", "smk_bn_train_workspace", "smk_layernorm_bwd_workspace", "smk_conv2_train_workspace", "smk_conv2_train_wgrad_workspace", "smk_conv1_train_wgrad_workspace", "smk_attention_workspace_bytes", "smk_linear_ln_max_rows", "smk_image_quality_workspace", "smk_image_quality_backward_workspace", "smk_convt4s2_train_wgrad_workspace",
            "smk_volume_stats_workspace", "smk_grad_norm_workspace", "smk_train_loss_workspace",
            "smk_conv3_sigmoid_train_workspace", "smk_flow_levels", "smk_flow_farneback_workspace", "smk_warp_workspace",
            "smk_flow_lk_workspace", "smk_volume_render_workspace", "smk_volume_render_backward_workspace", "smk_volume_render_orbit_workspace", "smk_volume_render_camera_workspace", "smk_conv3d_train_workspace", "smk_conv3d_cl_wgrad_workspace",
@@ -256,6 +258,8 @@ def load():
         L.smk_linear_ln_max_rows.restype = C.c_int64
         L.smk_image_quality_workspace.argtypes = [C.c_int32] * 3
         L.smk_image_quality_workspace.restype = C.c_int64
+        L.smk_image_quality_backward_workspace.argtypes = [C.c_int32] * 3
+        L.smk_image_quality_backward_workspace.restype = C.c_int64
         L.smk_volume_stats_workspace.argtypes = [C.c_int32] * 4
         L.smk_volume_stats_workspace.restype = C.c_int64
         L.smk_volume_render_workspace.argtypes = [C.c_int32] * 5

@@ -848,6 +848,27 @@ int smk_image_quality(const float *pred, int64_t pred_stride, const float *targe
                         "image_quality");
 }
 
+int64_t smk_image_quality_backward_workspace(int32_t n, int32_t H, int32_t W) {
+    if (n < 1 || H < 1 || W < 1) return 0;
+    return (int64_t)n * H * W * 3 * (int64_t)sizeof(float);
+}
+
+int smk_image_quality_backward(const float *pred, int64_t pred_stride, const float *target, int64_t target_stride, int32_t n, int32_t H,
+                               int32_t W, int32_t window, double c1, double c2, const float *plane_grad, void *workspace,
+                               int64_t workspace_bytes, float *dpred, int64_t dpred_stride, void *stream) {
+    SMK_REQUIRE(pred && target && plane_grad && workspace && dpred, "null pointer");
+    SMK_REQUIRE(n >= 1 && n <= 65535 && H >= 1 && W >= 1, "1 <= n <= 65535, H, W >= 1");
+    SMK_REQUIRE(pred_stride >= (int64_t)H * W && target_stride >= (int64_t)H * W && dpred_stride >= (int64_t)H * W,
+                "plane strides >= H*W");
+    SMK_REQUIRE(window >= 1 && window <= QUALITY_MAX_WINDOW && window % 2 == 1, "window: odd, 1..31");
+    SMK_REQUIRE(quality_tiles(H, W) <= INT32_MAX, "plane too large");
+    SMK_REQUIRE(workspace_bytes >= smk_image_quality_backward_workspace(n, H, W),
+                "workspace smaller than smk_image_quality_backward_workspace(n, H, W)");
+    return check_launch(launch_image_quality_backward(pred, pred_stride, target, target_stride, n, H, W, window, (float)c1, (float)c2,
+                                                      plane_grad, workspace, dpred, dpred_stride, (hipStream_t)stream),
+                        "image_quality_backward");
+}
+
 // ------------------------------------------------------------------ optical-flow baselines (Farneback, Lucas-Kanade, warp)
 namespace {
 int check_flow_shape(int32_t n, int32_t H, int32_t W) {

@@ -5,6 +5,9 @@ ROCm device as one HIP kernel (csrc/quality.hip: the five pooled moments, the ma
 tiny launch that sums each plane's tiles in a fixed order).  Inputs the kernel does not take -- tensors off the GPU or not fp32,
 mismatched shapes, an even window or one above 31 -- run the reference's torch formula (`ssim_torch`), which gives its
 results.  Both routes return Python floats, as the reference does.
+
+`plane_ssim` is the same SSIM as a tensor under autograd (the training side: models/losses.py `ssim_loss`): on the kernel route its
+backward is smk_image_quality_backward, the closed-form gradient of DESIGN.md 8.1.
 """
 import math
 from typing import Dict
@@ -43,6 +46,13 @@ def kernel_supported(pred: torch.Tensor, target: torch.Tensor, window_size: int)
             and pred.dim() >= 2 and pred.shape == target.shape and pred.numel() > 0)
 
 
+def _dense_planes(t: torch.Tensor) -> torch.Tensor:
+    """[n, H, W] view of the trailing planes with dense rows (a copy only where the layout needs one)."""
+    H, W = t.shape[-2:]
+    t = t.reshape(-1, H, W)
+    return t if t.stride(2) == 1 and t.stride(1) == W else t.contiguous()
+
+
 def plane_quality_sums(pred: torch.Tensor, target: torch.Tensor, window_size: int = 11, c1: float = C1, c2: float = C2):
     """Per-plane fp64 sums of the SSIM map and of the squared error over the trailing [H, W] planes of two fp32 tensors of one
     shape on a ROCm device (one kernel launch + one summing launch; bit-identical from call to call).
@@ -54,10 +64,7 @@ def plane_quality_sums(pred: torch.Tensor, target: torch.Tensor, window_size: in
                          f"window {window_size}")
     H, W = pred.shape[-2:]
     lead = tuple(pred.shape[:-2])
-    a = pred.reshape(-1, H, W)
-    b = target.reshape(-1, H, W)
-    a = a if a.stride(2) == 1 and a.stride(1) == W else a.contiguous()
-    b = b if b.stride(2) == 1 and b.stride(1) == W else b.contiguous()
+    a, b = _dense_planes(pred), _dense_planes(target)
     n = a.shape[0]
     L = _lib.load()
     ssim = torch.empty(n, dtype=torch.float64, device=dev)
@@ -71,6 +78,50 @@ def plane_quality_sums(pred: torch.Tensor, target: torch.Tensor, window_size: in
                                            float(c1), float(c2), ws.data_ptr(), ws_bytes, ssim[s].data_ptr(), sqerr[s].data_ptr(),
                                            _lib.stream_ptr(dev)))
     return ssim.reshape(lead), sqerr.reshape(lead)
+
+
+class _PlaneSsim(torch.autograd.Function):
+    """Mean SSIM of n planes on csrc/quality.hip: smk_image_quality forward, smk_image_quality_backward for d/d pred."""
+
+    @staticmethod
+    def forward(ctx, pred, target, window_size):
+        H, W = pred.shape[-2:]
+        a, b = _dense_planes(pred), _dense_planes(target)
+        ssim_sum, _ = plane_quality_sums(a, b, window_size)
+        ctx.save_for_backward(a, b)
+        ctx.window_size, ctx.pred_shape = window_size, pred.shape
+        return (ssim_sum / (H * W)).to(torch.float32).reshape(pred.shape[:-2])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        a, b = ctx.saved_tensors
+        n, H, W = a.shape
+        dev = a.device
+        g = grad_out.to(torch.float32).reshape(n).contiguous()
+        dpred = torch.empty(n, H, W, dtype=torch.float32, device=dev)          # the kernel writes every element
+        L = _lib.load()
+        with torch.cuda.device(dev):
+            for s in range(0, n, 65535):                  # the kernel takes up to 65535 planes per call
+                m = min(65535, n - s)
+                ws_bytes = L.smk_image_quality_backward_workspace(m, H, W)
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+                _lib.check(L.smk_image_quality_backward(a[s].data_ptr(), a.stride(0), b[s].data_ptr(), b.stride(0), m, H, W,
+                                                        ctx.window_size, float(C1), float(C2), g[s].data_ptr(), ws.data_ptr(), ws_bytes,
+                                                        dpred[s].data_ptr(), dpred.stride(0), _lib.stream_ptr(dev)))
+        return dpred.reshape(ctx.pred_shape), None, None
+
+
+def plane_ssim(pred: torch.Tensor, target: torch.Tensor, window_size: int = 11) -> torch.Tensor:
+    """Mean SSIM of every trailing [H, W] plane: an fp32 tensor of shape pred.shape[:-2] (the inputs' dtype on the torch route),
+    differentiable with respect to pred.  Tensors the kernel serves (`kernel_supported`) with a target that wants no gradient run
+    csrc/quality.hip forward and backward (first order only: a second derivative raises; ask `ssim_torch` for it); everything else
+    -- CPU tensors, fp64, an even window, a target that requires a gradient -- runs `ssim_torch` under torch's autograd."""
+    if kernel_supported(pred, target, window_size) and not target.requires_grad:
+        return _PlaneSsim.apply(pred, target, window_size)
+    H, W = pred.shape[-2:]
+    ssim_map = ssim_torch(pred.reshape(-1, 1, H, W), target.reshape(-1, 1, H, W), window_size)
+    return ssim_map.mean((-2, -1)).reshape(pred.shape[:-2])
 
 
 def _psnr(mse):

@@ -3,13 +3,16 @@ mass-conservation and continuity terms from smk_train_loss_forward / smk_train_l
 
 `hip_train_losses` returns one device vector [total, recon, physics, chaos, mass, continuity]; a gradient on any of the six is honoured.
 Inputs the kernels do not take (`hip_train_losses_supported`) keep the torch formulas (`torch_train_losses`).
+
+`ssim_loss` is the opt-in SSIM term of train.py (`mi355x.ssim_weight`), on the image-quality kernels of csrc/quality.hip.
 """
 import torch
 import torch.nn.functional as F
 
 from .. import _lib
+from ..evaluation.robustness_metrics import plane_ssim
 
-__all__ = ["LOSS_NAMES", "hip_train_losses", "hip_train_losses_supported", "torch_train_losses"]
+__all__ = ["LOSS_NAMES", "hip_train_losses", "hip_train_losses_supported", "ssim_loss", "torch_train_losses"]
 
 LOSS_NAMES = ("total", "recon", "physics", "chaos", "mass", "continuity")
 
@@ -45,6 +48,12 @@ def torch_train_losses(pred, target, chaos_pred, chaos_target, sequence, regular
     physics = regularizer.conservation_weight * mass + regularizer.continuity_weight * cont
     total = recon + w_chaos * chaos + w_physics * physics
     return torch.stack([total, recon, physics, chaos, mass, cont.to(total.dtype)])
+
+
+def ssim_loss(pred, target, window_size: int = 11):
+    """1 - the mean over planes of the SSIM that RobustnessEvaluator reports (evaluation.plane_ssim: csrc/quality.hip forward and
+    backward for fp32 tensors on a ROCm device, the torch formula under autograd for everything else)."""
+    return 1 - plane_ssim(pred, target, window_size).mean()
 
 
 class _HipTrainLosses(torch.autograd.Function):

@@ -79,6 +79,17 @@ def loss_route(config: dict) -> str:
     return _route((config.get("mi355x", {}) or {}).get("losses", "torch"), LOSS_ROUTES, "mi355x.losses")
 
 
+def ssim_settings(config: dict):
+    """(weight, window) of the opt-in SSIM term from `mi355x.ssim_weight` (0.0, the default: no term) and `mi355x.ssim_window` (11)."""
+    hw = config.get("mi355x", {}) or {}
+    weight, window = float(hw.get("ssim_weight", 0.0)), hw.get("ssim_window", 11)
+    if not weight >= 0.0:
+        raise ValueError(f"mi355x.ssim_weight must be >= 0, not {weight!r}")
+    if isinstance(window, bool) or not isinstance(window, int) or window < 1 or window % 2 == 0:
+        raise ValueError(f"mi355x.ssim_window must be an odd positive integer, not {window!r}")
+    return weight, window
+
+
 def build_optimizer(config: dict, params) -> optim.Optimizer:
     """AdamW from the config's `training` section; `mi355x.optimizer: hip` makes it smokephysai_amd.optim.HipAdamW (same state,
     same state_dict: a checkpoint resumes across the switch)."""
@@ -90,8 +101,9 @@ def build_optimizer(config: dict, params) -> optim.Optimizer:
     return optim.AdamW(params, **kwargs)
 
 
-def _batch_loss_terms(model, physics_regularizer, batch, device, chaos_noise=None, losses="torch"):
-    """batch_losses' four values and, on the hip route, the device vector they are views of (else None)."""
+def _batch_loss_terms(model, physics_regularizer, batch, device, chaos_noise=None, losses="torch", ssim_weight=0.0, ssim_window=11):
+    """batch_losses' four values and, on the hip route, the device vector they are views of (else None).  ssim_weight > 0 adds
+    ssim_weight * ssim_loss(reconstructed, targets, ssim_window) to the total (models/losses.py); the other three keep their values."""
     global _warned_losses
     _route(losses, LOSS_ROUTES, "losses")
     inputs = batch["input"].to(device)
@@ -109,6 +121,9 @@ def _batch_loss_terms(model, physics_regularizer, batch, device, chaos_noise=Non
         if hip_train_losses_supported(outputs["reconstructed"], targets, outputs["physics_features"], chaos_targets, sequence):
             vec = hip_train_losses(outputs["reconstructed"], targets, outputs["physics_features"], chaos_targets, sequence,
                                    physics_regularizer, w_chaos=0.1, w_physics=0.05)
+            if ssim_weight > 0:                                    # one add: the SSIM term into slot 0 of the vector
+                from smokephysai_amd.models.losses import ssim_loss
+                vec = vec + F.pad((ssim_weight * ssim_loss(outputs["reconstructed"], targets, ssim_window)).reshape(1), (0, vec.numel() - 1))
             return (vec[0], vec[1], vec[2], vec[3]), vec
         if outputs["reconstructed"].device.type == "cuda" and not _warned_losses:      # CPU tensors take the torch formulas silently
             _warned_losses = True
@@ -120,13 +135,16 @@ def _batch_loss_terms(model, physics_regularizer, batch, device, chaos_noise=Non
                                           "density_sequence": batch["sequence"].to(device)}, {"density": targets})
     physics_loss = physics_losses["total_physics_loss"]
     total = recon_loss + 0.1 * chaos_loss + 0.05 * physics_loss
+    if ssim_weight > 0:
+        from smokephysai_amd.models.losses import ssim_loss
+        total = total + ssim_weight * ssim_loss(outputs["reconstructed"], targets, ssim_window)
     return (total, recon_loss, physics_loss, chaos_loss), None
 
 
-def batch_losses(model, physics_regularizer, batch, device, chaos_noise=None, losses="torch"):
+def batch_losses(model, physics_regularizer, batch, device, chaos_noise=None, losses="torch", ssim_weight=0.0, ssim_window=11):
     """Forward + the reference's loss decomposition (train.py:59-85). Returns (total, recon, physics, chaos); with losses="hip" the four
     are views of the one device vector smokephysai_amd.models.losses.hip_train_losses computes."""
-    return _batch_loss_terms(model, physics_regularizer, batch, device, chaos_noise, losses)[0]
+    return _batch_loss_terms(model, physics_regularizer, batch, device, chaos_noise, losses, ssim_weight, ssim_window)[0]
 
 
 def _rank_invariant_batches(loader: DataLoader, device):
@@ -146,7 +164,8 @@ def _rank_invariant_batches(loader: DataLoader, device):
 
 
 def train_epoch(model: nn.Module, train_loader: DataLoader, optimizer: optim.Optimizer,
-                physics_regularizer: PhysicsRegularizer, device, epoch: int, writer, losses: str = "torch") -> Dict[str, float]:
+                physics_regularizer: PhysicsRegularizer, device, epoch: int, writer, losses: str = "torch",
+                ssim_weight: float = 0.0, ssim_window: int = 11) -> Dict[str, float]:
     """One epoch.  A HipAdamW clips inside its step (`step(clip_max_norm=1.0)`: smk_grad_norm + smk_adamw_step); any other optimizer gets
     clip_grad_norm_ and step() as before.  losses="hip": the four logged values come from one .tolist() of the loss vector."""
     from smokephysai_amd.optim import HipAdamW
@@ -157,7 +176,8 @@ def train_epoch(model: nn.Module, train_loader: DataLoader, optimizer: optim.Opt
     pbar = tqdm(_rank_invariant_batches(train_loader, device), total=steps, desc=f"Training Epoch {epoch+1}", leave=True)
     for batch_idx, batch in enumerate(pbar):
         optimizer.zero_grad()
-        (total, recon, phys, chaos), vec = _batch_loss_terms(model, physics_regularizer, batch, device, losses=losses)
+        (total, recon, phys, chaos), vec = _batch_loss_terms(model, physics_regularizer, batch, device, losses=losses,
+                                                             ssim_weight=ssim_weight, ssim_window=ssim_window)
         total.backward()                      # DDP: bucketed RCCL all-reduce (mean over ranks) overlaps this backward
         if fused_clip:
             optimizer.step(clip_max_norm=1.0)
@@ -178,14 +198,15 @@ def train_epoch(model: nn.Module, train_loader: DataLoader, optimizer: optim.Opt
 
 
 def validate_epoch(model: nn.Module, val_loader: DataLoader, physics_regularizer: PhysicsRegularizer,
-                   device, losses: str = "torch") -> Dict[str, float]:
+                   device, losses: str = "torch", ssim_weight: float = 0.0, ssim_window: int = 11) -> Dict[str, float]:
     """No collective inside the loop (the unwrapped model, eval-mode BatchNorm), so ranks may run different batch counts."""
     model.eval()
     sums, seen = [0.0, 0.0, 0.0, 0.0], 0
     with torch.no_grad():
         pbar = tqdm(val_loader, desc="Validation", leave=True)
         for batch in pbar:
-            terms, vec = _batch_loss_terms(model, physics_regularizer, batch, device, losses=losses)
+            terms, vec = _batch_loss_terms(model, physics_regularizer, batch, device, losses=losses, ssim_weight=ssim_weight,
+                                           ssim_window=ssim_window)
             vals = [v.item() if torch.is_tensor(v) else float(v) for v in terms] if vec is None else vec.tolist()[:4]
             n = int(batch["input"].shape[0])
             sums = [s + v * n for s, v in zip(sums, vals)]
@@ -235,6 +256,7 @@ def main():
     parser.add_argument("--resume", type=str, default=None, help="Path to checkpoint to resume from")
     args = parser.parse_args()
     config = load_config(args.config)
+    ssim_weight, ssim_window = ssim_settings(config)               # a bad value stops here, before any data is generated
     hw = config.get("mi355x", {}) or {}
     if hw.get("deterministic", False):
         # run-to-run reproducible steps: MIOpen's default backward-weights solvers for the reconstruction head's three convolutions
@@ -277,8 +299,10 @@ def main():
     best_val_loss = float("inf")
     for epoch in range(start_epoch, config["training"]["num_epochs"]):
         print(f"\nEpoch {epoch + 1}/{config['training']['num_epochs']}")
-        train_metrics = train_epoch(ddp_model, train_loader, optimizer, physics_regularizer, device, epoch, writer, losses=losses)
-        val_metrics = validate_epoch(model, val_loader, physics_regularizer, device, losses=losses)
+        train_metrics = train_epoch(ddp_model, train_loader, optimizer, physics_regularizer, device, epoch, writer, losses=losses,
+                                    ssim_weight=ssim_weight, ssim_window=ssim_window)
+        val_metrics = validate_epoch(model, val_loader, physics_regularizer, device, losses=losses, ssim_weight=ssim_weight,
+                                     ssim_window=ssim_window)
         scheduler.step()
         writer.add_scalar("Train/Epoch_Loss", train_metrics["total_loss"], epoch)
         writer.add_scalar("Val/Epoch_Loss", val_metrics["total_loss"], epoch)
