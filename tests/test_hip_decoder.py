@@ -59,12 +59,11 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from conftest import rel_err      # noqa: E402
+from guarded_arena import FILL_NAN, FILL_ZERO, GUARD, Arena      # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
-GUARD = 4096                      # words of guard on both sides of every arena buffer
-FILL_NAN, FILL_ZERO = -1, 0       # int32 fill words: 0xFFFFFFFF (a NaN as float32) and 0x00000000
 
 SMALL = ("k_convt4s2_small<64,32,true>", "k_convt4s2_small<32,16,false>")
 OG2 = ("k_convt4s2<64,32,2,true>", "k_convt4s2<32,16,2,false>")
@@ -197,44 +196,7 @@ def make_head(device, seed=7):
     return head.to(device)
 
 
-# ------------------------------------------------------------------------------------------------ the guarded arena
-class Arena:
-    """One int32 allocation holding named float32 buffers, GUARD words of guard before, between and behind them.  `phase` is the
-    buffer's word offset modulo 4: 0 = 16-byte aligned, 2 = 8-byte but not 16-byte aligned, 1 = 4-byte aligned only."""
-
-    def __init__(self, buffers, device="cuda"):
-        total = sum(n for _, n, _ in buffers) + (len(buffers) + 1) * (GUARD + 4)
-        self.buf = torch.empty(total, dtype=torch.int32, device=device)
-        assert self.buf.data_ptr() % 16 == 0
-        self.span, cur = {}, 0
-        for name, n, phase in buffers:
-            off = cur + GUARD
-            off += (phase - off) % 4
-            self.span[name] = (off, n)
-            cur = off + n
-        assert cur + GUARD <= total
-
-    def fill(self, word):
-        self.buf.fill_(word)
-
-    def view(self, name):
-        off, n = self.span[name]
-        return self.buf[off:off + n].view(torch.float32)
-
-    def ptr(self, name):
-        return self.buf.data_ptr() + 4 * self.span[name][0]
-
-    def guard_damage(self, word, also=()) -> int:
-        """Words outside every buffer (and inside the buffers named in `also`) that no longer hold the fill word, compared as int32."""
-        bad, cur = 0, 0
-        for name, (off, n) in sorted(self.span.items(), key=lambda kv: kv[1][0]):
-            bad += int((self.buf[cur:off] != word).sum())
-            if name in also:
-                bad += int((self.buf[off:off + n] != word).sum())
-            cur = off + n
-        return bad + int((self.buf[cur:] != word).sum())
-
-
+# ------------------------------------------------------------------------------------------------ the guarded arena (tests/guarded_arena.py)
 def decoder_arena(B, S):
     return Arena([("tokens", B * S * S * 64, 0), ("tmp1", B * 32 * 4 * S * S, 2), ("tmp2", B * 16 * 16 * S * S, 2),
                   ("recon", B * 16 * S * S, 1)])
