@@ -528,7 +528,10 @@ int smk_linear_update(smk_linear *lin, const float *weight, int32_t transposed, 
  * caller and free for reuse once the enqueued work has run.  Requires in_features % 32 == 0, out_features % 4 == 0,
  * (out_features + 256) * (rows + 4096) < 2^30 (longer inputs: call per row chunk and add).  db (may be NULL): the bias gradient
  * [out_features] = column sums of dy (partials per row segment, added in a fixed order).  With out_features and in_features multiples of 128
- * neither operand is copied: both are staged as they lie and read back transposed from LDS (ds_read_b64_tr_b16).  Enqueued on `stream`. */
+ * neither operand is copied: both are staged as they lie and read back transposed from LDS (ds_read_b64_tr_b16) -- that form also needs
+ * rows >= 32, ld_dy and ldx multiples of 4 and dy and x 16-byte aligned; a call that misses one of these runs the copying form, which
+ * takes any 4-byte aligned dy and x and any pitch.  Each form repeats bit for bit; the two agree to rounding (4e-6 of the largest
+ * element at 512 x 128 x 128), not bit for bit, so a caller that compares runs keeps pitch and alignment fixed.  Enqueued on `stream`. */
 int64_t smk_linear_wgrad_workspace(int64_t rows, int32_t out_features, int32_t in_features);
 int smk_linear_wgrad(const float *dy, int64_t ld_dy, const float *x, int64_t ldx, int64_t rows, int32_t out_features,
                      int32_t in_features, float *dw, float *db, void *workspace, int64_t workspace_bytes, void *stream);
@@ -625,7 +628,8 @@ int smk_conv3d_s7_dgrad(const float *dz1, const float *weight, int32_t B, int32_
  *   SMK_BN_BWD_SUMS  dout, z -> dgamma = sum dy zhat, dbeta = sum dy; the ReLU mask is recomputed from z.  pooled = 0: dout [B*D*H*W][C];
  *                    pooled = 1: dout [B][1024][C] is the gradient of the token MEANS, broadcast over each block and divided by its size;
  *   SMK_BN_BWD_DZ    dz [B*D*H*W][C] from the given dgamma / dbeta and count = elements per channel.
- * Sums are fp64, two-stage, in a fixed order.  `workspace`: smk_bn_cl_workspace(B, D, H, W, C) bytes. */
+ * Sums are fp64, two-stage, in a fixed order.  `workspace` (SMK_BN_STATS and SMK_BN_BWD_SUMS; the other phases take none): smk_bn_cl_workspace(B, D, H, W, C)
+ * bytes, 8-byte aligned (it holds the fp64 partial sums; else SMK_ERR_INVALID).  z, out, dout and dz are 16-byte aligned. */
 int64_t smk_bn_cl_workspace(int32_t B, int32_t D, int32_t H, int32_t W, int32_t C);
 int smk_bn_cl_phase(int32_t phase, const float *z, const float *dout, int32_t B, int32_t D, int32_t H, int32_t W, int32_t C, int32_t pooled,
                     const float *gamma, const float *beta, double eps, float *mean, float *var, float *rstd, float *out, float *dz, float *dgamma,

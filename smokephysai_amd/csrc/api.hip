@@ -1801,9 +1801,9 @@ int smk_bn_cl_phase(int32_t phase, const float *z, const float *dout, int32_t B,
     }
     SMK_REQUIRE(z && mean && rstd && SMK_ALIGNED16(z), "null or unaligned z / mean / rstd");
     switch (phase) {
-    case SMK_BN_STATS: SMK_REQUIRE(var && workspace, "STATS: null var/workspace"); break;
+    case SMK_BN_STATS: SMK_REQUIRE(var && workspace && ((uintptr_t)workspace & 7) == 0, "STATS: null var/workspace, or a workspace that is not 8-byte aligned (fp64 partial sums)"); break;
     case SMK_BN_APPLY: SMK_REQUIRE(gamma && beta && out && SMK_ALIGNED16(out), "APPLY: null gamma/beta/out"); break;
-    case SMK_BN_BWD_SUMS: SMK_REQUIRE(gamma && beta && dout && dgamma && dbeta && workspace && SMK_ALIGNED16(dout), "BWD_SUMS: null gamma/beta/dout/dgamma/dbeta/workspace"); break;
+    case SMK_BN_BWD_SUMS: SMK_REQUIRE(gamma && beta && dout && dgamma && dbeta && workspace && SMK_ALIGNED16(dout) && ((uintptr_t)workspace & 7) == 0, "BWD_SUMS: null gamma/beta/dout/dgamma/dbeta/workspace, or a workspace that is not 8-byte aligned (fp64 partial sums)"); break;
     case SMK_BN_BWD_DZ: SMK_REQUIRE(gamma && beta && dout && dgamma && dbeta && dz && count > 0 && SMK_ALIGNED16(dout) && SMK_ALIGNED16(dz), "BWD_DZ: null gamma/beta/dout/dgamma/dbeta/dz, or count <= 0"); break;
     default: SMK_REQUIRE(false, "unknown phase");
     }

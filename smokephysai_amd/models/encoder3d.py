@@ -307,6 +307,8 @@ BN_STATS, BN_APPLY, BN_BWD_SUMS, BN_BWD_DZ = 0, 1, 2, 3
 
 
 def _bn_cl_phase(L, phase, z, dout, pooled, gamma, beta, eps, stats, out, dz, dwb, count, ws, dev):
+    """One phase of smk_bn_cl_phase.  z, out, dout and dz 16-byte aligned; ws (BN_STATS and BN_BWD_SUMS only): smk_bn_cl_workspace bytes,
+    8-byte aligned -- it holds fp64 partial sums, and the entry point refuses a weaker alignment (a torch allocation always has it)."""
     B, D, H, W, C = z.shape
     ptr = lambda t: None if t is None else t.data_ptr()
     _lib.check(L.smk_bn_cl_phase(phase, z.data_ptr(), ptr(dout), B, D, H, W, C, int(pooled), gamma.data_ptr(), beta.data_ptr(), float(eps),

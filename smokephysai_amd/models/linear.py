@@ -229,7 +229,11 @@ MAX_WGRAD_ROWS = 1 << 17     # rows per smk_linear_wgrad call ((out + 256) * (ro
 
 def hip_linear_wgrad(dy: torch.Tensor, x: torch.Tensor, want_db: bool = False):
     """dW [out, in] = dy^T x over the token rows (dy [rows, out], x [rows, in], fp32 on one ROCm device) -- smk_linear_wgrad.
-    want_db: also return the bias gradient db [out] = dy.sum(0) (from the transposed copy of dy the call makes anyway)."""
+    want_db: also return the bias gradient db [out] = dy.sum(0) (from the transposed copy of dy the call makes anyway).
+    The entry point has two forms and chooses by shape, pitch and pointer: with out and in multiples of 128, rows >= 32, both row pitches
+    multiples of 4 and dy and x 16-byte aligned it reads both operands as they lie (transposed from LDS); anything else -- a view that starts
+    4 bytes into its storage, an odd pitch -- takes the copying form.  Each form repeats bit for bit, the two agree to rounding only, so a
+    caller that compares runs keeps pitch and alignment fixed (include/smokehip.h, smk_linear_wgrad)."""
     dev = _lib.require_cuda(dy.device, "hip_linear_wgrad")
     L = _lib.load()
     if dy.dim() != 2 or x.dim() != 2 or dy.shape[0] != x.shape[0] or dy.dtype != torch.float32 or x.dtype != torch.float32 or x.device != dev:

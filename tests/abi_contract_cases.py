@@ -611,7 +611,8 @@ def conv3d_cases():
 # ------------------------------------------------------------------------------------------------ the table
 @functools.lru_cache(maxsize=None)
 def all_cases():
-    cases = render_cases() + quality_cases() + stats_cases() + flow_cases() + optimizer_cases() + loss_cases() + conv3d_cases()
+    from abi_contract_cases_train import train_cases                 # (imported here: that module takes Case and dense_reference from this one)
+    cases = render_cases() + quality_cases() + stats_cases() + flow_cases() + optimizer_cases() + loss_cases() + conv3d_cases() + train_cases()
     assert len({c.id for c in cases}) == len(cases)
     return tuple(cases)
 
@@ -619,4 +620,11 @@ def all_cases():
 ENTRY_POINTS = ("smk_volume_render", "smk_volume_render_backward", "smk_volume_render_orbit", "smk_volume_render_camera", "smk_image_quality",
                 "smk_image_quality_backward", "smk_chaos_stats", "smk_frame_diff_norms", "smk_volume_stats", "smk_flow_farneback",
                 "smk_flow_lucas_kanade", "smk_warp_frames", "smk_grad_norm", "smk_adamw_step", "smk_train_loss_forward", "smk_train_loss_backward",
-                "smk_conv3d_s7_train_forward", "smk_conv3d_cl_train_forward", "smk_conv3d_cl_dgrad", "smk_conv3d_cl_wgrad", "smk_conv3d_s7_dgrad")
+                "smk_conv3d_s7_train_forward", "smk_conv3d_cl_train_forward", "smk_conv3d_cl_dgrad", "smk_conv3d_cl_wgrad", "smk_conv3d_s7_dgrad",
+                # the training step's calls: tests/abi_contract_cases_train.py
+                "smk_conv1_train_forward", "smk_conv1_train_wgrad", "smk_conv1_train_dgrad", "smk_conv2_train_forward", "smk_conv2_train_dgrad",
+                "smk_conv2_train_wgrad", "smk_bn_relu_pool_forward", "smk_bn_relu_pool_backward", "smk_bn_relu_pool_phase", "smk_bn_cl_phase",
+                "smk_convt4s2_train_forward", "smk_convt4s2_train_dgrad", "smk_convt4s2_train_wgrad", "smk_conv3_sigmoid_train_forward",
+                "smk_conv3_sigmoid_train_backward", "smk_layernorm", "smk_layernorm_backward", "smk_attention_forward_lse", "smk_attention_backward",
+                "smk_attention_delta", "smk_linear_wgrad", "smk_ffn_elementwise", "smk_lorenz_states", "smk_chaos_addend", "smk_chaos_addend_batched",
+                "smk_reduce_shards")

@@ -20,7 +20,7 @@ import torch
 GUARD = 4096                      # words of guard on both sides of every arena buffer
 FILL_NAN, FILL_ZERO = -1, 0       # int32 fill words: 0xFFFFFFFF (a NaN as float32; 0xFF bytes) and 0x00000000
 
-ITEMSIZE = {torch.float32: 4, torch.int32: 4, torch.uint8: 1, torch.float64: 8}
+ITEMSIZE = {torch.float32: 4, torch.int32: 4, torch.uint8: 1, torch.float64: 8, torch.bfloat16: 2}
 ALIGNMENTS = (4, 8, 16, 256)      # bytes
 
 
@@ -86,7 +86,8 @@ class Arena:
     """One int32 allocation holding named buffers, at least GUARD words of guard before, between and behind them.  `buffers`: Buf
     entries, or the older (name, float32 elements, phase) triples, where `phase` is the buffer's word offset modulo 4 (0 = 16-byte
     aligned, 2 = 8-byte but not 16-byte aligned, 1 = 4-byte aligned only).  Every buffer occupies whole 32-bit words; bytes of those
-    words that are not the buffer's (a uint8 buffer's tail, the gaps between strided planes) are guard like the words between buffers."""
+    words that are not the buffer's (a uint8 or bfloat16 buffer's tail, the gaps between strided planes) are guard like the words between
+    buffers."""
 
     def __init__(self, buffers, device="cuda"):
         bufs = [b if isinstance(b, Buf) else Buf(b[0], torch.float32, b[1], align=4, phase=4 * (b[2] % 4), role="inout") for b in buffers]
@@ -228,14 +229,15 @@ def run_guarded(case, fill, stream=None, delay_cycles=0) -> Run:
 
 
 def bits(t: torch.Tensor) -> torch.Tensor:
-    """A tensor's bits for exact comparison: int32 words for 4-byte types, int64 for float64, the bytes of uint8."""
+    """A tensor's bits for exact comparison: int32 words for 4-byte types, int64 for float64, int16 for bfloat16, the bytes of uint8."""
     t = t.contiguous()
-    return t.view({4: torch.int32, 8: torch.int64, 1: torch.uint8}[t.element_size()])
+    return t.view({4: torch.int32, 8: torch.int64, 2: torch.int16, 1: torch.uint8}[t.element_size()])
 
 
 def holds_fill(t: torch.Tensor, fill: int) -> int:
-    """How many elements of an output still hold the fill word (float64: both of its words).  uint8 outputs have no recognisable fill --
-    0xFF and 0x00 are pixel values -- and answer 0: an unwritten byte of theirs differs between the two fills instead."""
+    """How many elements of an output still hold the fill word (float64: both of its words; bfloat16: its half of one, 0xFFFF being a
+    NaN no finite sum rounds to).  uint8 outputs have no recognisable fill -- 0xFF and 0x00 are pixel values -- and answer 0: an unwritten
+    byte of theirs differs between the two fills instead."""
     if t.dtype == torch.uint8:
         return 0
     return int((bits(t) == fill).sum())

@@ -1,9 +1,12 @@
 """The stateless C ABI (include/smokehip.h) held to what it promises about memory and streams -- "caller-owned memory", "the caller's
 stream", "nothing allocated, no synchronisation", "workspace: at least smk_*_workspace(...) bytes", "every element written exactly once",
 "planes *_stride floats apart" -- for the volume renders and their gradient, the SSIM forward and backward, the statistics, the
-optical-flow methods, the train-step tail and the 3-D training convolutions.  The cases are tests/abi_contract_cases.py, the harness is
-tests/guarded_arena.py: every buffer of a call lies in one arena the test owns, planes strided, pointers no better aligned than the header
-asks, the workspace exactly as large as its query says, and every other byte a guard.
+optical-flow methods, the train-step tail, the 3-D training convolutions (tests/abi_contract_cases.py) and the calls of a training step:
+the 2-D training convolutions, the BatchNorm passes, the reconstruction head's convolutions, LayerNorm, the attention forward / backward /
+delta, the linear weight gradient, the FFN's element-wise chain, the chaos term and the gradient exchange
+(tests/abi_contract_cases_train.py).  The harness is tests/guarded_arena.py: every buffer of a call lies in one arena the test owns,
+planes strided, pointers no better aligned than the header asks, the workspace exactly as large as its query says, and every other byte a
+guard.
 
 For every case:
   1. buffers         the call runs with the arena filled with 0xFFFFFFFF (NaN) and with 0: no guard byte changes under either -- the gaps
@@ -19,10 +22,16 @@ For every case:
                      run while the side stream sleeps, on NaN inputs or ahead of its predecessors.
 What this cannot see: a stray read that lands on equal data under both fills (inside another buffer of the same call, say).
 
+Where an entry point demands an alignment, a call with one pointer aligned half as well comes back with SMK_ERR_INVALID and leaves the
+whole arena as it was, under both fills (test_a_weaker_alignment_is_refused).
+
 Two controls use torch ops alone and show that the harness catches what it is for.
 
-Out of scope here: the handle-owning objects (the steppers, the encoder, linear and decoder handles, attention), the BatchNorm phase entry
-points and the 2-D training convolutions.  smk_decoder_forward and smk_pooled_head are held to the same arena in tests/test_hip_decoder.py."""
+Out of scope here: the handle-owning objects (the steppers, the encoder, linear and decoder handles), the eval attention calls
+(smk_attention / _ws / _kv / _received / _probs: their sentinel buffers are tests/attention_variant_cases.py), the eval 3-D convolutions with
+smk_conv3d_im2col / smk_pool3d_accumulate, and the stateless 2-D physics helpers.  smk_decoder_forward and smk_pooled_head are held to the
+same arena in tests/test_hip_decoder.py."""
+import dataclasses
 import functools
 import os
 import sys
@@ -35,7 +44,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from abi_contract_cases import ENTRY_POINTS, all_cases                                                      # noqa: E402
-from guarded_arena import FILL_NAN, FILL_ZERO, Arena, Buf, bits, holds_fill, run_guarded                   # noqa: E402
+from abi_contract_cases_train import APPLY, BF16, BWD_DZ, BWD_SUMS, F32, REFUSED_ALIGNMENTS, STATS         # noqa: E402
+from guarded_arena import FILL_NAN, FILL_ZERO, Arena, Binder, Buf, bits, holds_fill, run_guarded           # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -78,6 +88,33 @@ def test_the_table_reaches_every_entry_point():
                           ("smk_volume_render_orbit", ("none", "+y", "-y")), ("smk_volume_render_camera", ("none", "+y", "-y"))):
         for light in lights:
             assert sum(c.entry == entry and c.id.endswith("-" + light) for c in CASES) == 2, (entry, light)      # both shapes
+    assert len(ENTRY_POINTS) == len(set(ENTRY_POINTS)) == 21 + 26
+
+    def variants(entry, *keys):
+        """The set of tag tuples the cases of an entry point carry (tests/abi_contract_cases_train.py gives every case its tags)."""
+        return {tuple(c.tags[k] for k in keys) for c in CASES if c.entry == entry}
+    phases = (STATS, APPLY, BWD_SUMS, BWD_DZ)
+    for entry in ("smk_conv1_train_forward", "smk_conv2_train_forward", "smk_conv3_sigmoid_train_forward"):
+        assert variants(entry, "bias") == {(True,), (False,)}, entry
+    for entry in ("smk_conv1_train_wgrad", "smk_conv2_train_wgrad", "smk_linear_wgrad"):
+        assert variants(entry, "db") == {(True,), (False,)}, entry
+    for entry in ("smk_bn_relu_pool_forward", "smk_bn_relu_pool_backward"):
+        assert variants(entry, "pool") == {(p,) for p in (1, 2, 4, 8, 16, 32)}, entry
+    assert variants("smk_bn_relu_pool_phase", "pool", "phase", "frozen") == \
+        {(p, ph, False) for p in (1, 2, 4, 8, 16, 32) for ph in phases} | {(1, APPLY, True), (1, BWD_DZ, True)}
+    assert variants("smk_bn_cl_phase", "C", "pooled", "phase") == {(c, p, ph) for c in (64, 128) for p in (0, 1) for ph in phases}
+    assert variants("smk_convt4s2_train_forward", "COUT", "tok") == variants("smk_convt4s2_train_dgrad", "COUT", "tok") == \
+        variants("smk_convt4s2_train_wgrad", "COUT", "tok") == {(32, 0), (16, 0), (32, 1), (16, 1)}
+    assert variants("smk_convt4s2_train_forward", "bias") == variants("smk_convt4s2_train_wgrad", "db") == {(True,), (False,)}
+    assert variants("smk_conv3_sigmoid_train_backward", "grads") == {(True,), (False,)}
+    assert variants("smk_layernorm", "split") == {(0,), (1,)}
+    assert variants("smk_linear_wgrad", "form") == {("tr",), ("copy",)}
+    assert variants("smk_ffn_elementwise", "op", "p") == {(op, p) for op in range(4) for p in (0.0, 0.25)}
+    assert variants("smk_chaos_addend_batched", "layers") == {(2,)}
+    assert variants("smk_reduce_shards", "world", "formats") >= {(w, f) for w in (1, 3) for f in ((F32, F32), (F32, BF16), (BF16, BF16))}
+    assert (3, True) in variants("smk_reduce_shards", "world", "in_place")
+    for entry in ENTRY_POINTS[21:]:                       # the training step's calls: two shapes or more each
+        assert len({tuple(b.elems * b.planes for b in c.bufs if b.role != "out") for c in CASES if c.entry == entry}) >= 2, entry
 
 
 @case_param
@@ -171,6 +208,32 @@ def test_runs_on_the_callers_stream_without_waiting(case):
     assert run.damage == 0, f"{case.id}, side stream: {run.damage}"
     for name, out in run.outputs.items():
         assert _same_bits(out, nan.outputs[name]), f"{case.id}: '{name}' differs on a side stream: part of the call left the caller's stream"
+
+
+BY_ID = {c.id: c for c in CASES}
+
+
+@pytest.mark.parametrize("case_id,name", REFUSED_ALIGNMENTS, ids=[f"{c}-{n}" for c, n in REFUSED_ALIGNMENTS])
+def test_a_weaker_alignment_is_refused(case_id, name):
+    """The case's own call with `name` aligned half as well as the entry point demands (16 -> 8, 8 -> 4 bytes): the status comes back
+    and no byte of the arena -- buffers, workspace and guards -- changes, under either fill.  Nothing is copied in: a refused call reads
+    nothing."""
+    from smokephysai_amd import _lib
+    lib, case = _lib.load(), BY_ID[case_id]
+    bufs = case.buffers(lib)
+    (asked,) = [b.align for b in bufs if b.name == name]
+    assert asked in (8, 16), (case_id, name, asked)
+    bufs = [dataclasses.replace(b, align=asked // 2, phase=None) if b.name == name else b for b in bufs]
+    arena = Arena(bufs)
+    assert arena.ptr(name) % asked == asked // 2
+    for fill in (FILL_NAN, FILL_ZERO):
+        arena.fill(fill)
+        torch.cuda.synchronize()
+        rc = getattr(lib, case.entry)(*case.args(Binder(arena, _lib.stream_ptr(torch.device("cuda", torch.cuda.current_device())))))
+        torch.cuda.synchronize()
+        assert rc == _lib.SMK_ERR_INVALID, f"{case_id}: '{name}' at {asked // 2}-byte alignment was not refused (status {rc})"
+        damage = arena.guard_damage(fill, also=tuple(arena.bufs))
+        assert damage == 0, f"{case_id}, refused for '{name}': {damage}"
 
 
 # ------------------------------------------------------------------------------------------------ controls (torch ops only)
