@@ -338,6 +338,36 @@ int smk_volume_render_orbit(const float *vols, int64_t vol_stride, int32_t n, in
                             const double *azimuths, int32_t n_views, float *image, int64_t image_stride, float *transmittance,
                             int64_t trans_stride, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* The gradient of smk_volume_render_orbit: given the upstream gradients G = grad_image and Gt = grad_trans of its two outputs (plane
+ * v * n_views + k is view k of volume v, planes `grad_image_stride` / `grad_trans_stride` floats apart, >= H*W; either may be NULL,
+ * which means zero; both NULL is SMK_ERR_INVALID), writes d(loss)/d(rho) of the same n volumes, summed over each volume's n_views views,
+ * into grad_vols (dense [D][H][W] each, `grad_vol_stride` floats apart).  SPEC_3D.md section 10, "Orbit views -- Gradient": with rho_s,
+ * A the samples of smk_volume_render_orbit, tau their exclusive prefix over s, T = exp(-sigma_view tau), alpha = -expm1(-sigma_view rho_s),
+ * X = exp(-sigma_light A), L = ambient + (1 - ambient) X (1 unlit), c = alpha L T,
+ *   Q[s,y,x'] = gain G sigma_view (exp(-sigma_view rho_s) L T - sum_{s' > s} c[s',y,x']) - sigma_view Gt transmittance[y,x']
+ *   R[s,y,x'] = gain G alpha T (-sigma_light (1 - ambient) X)                                               (0 under SMK_LIGHT_NONE)
+ *   drho[z,y,x] = sum over the views of ( (B^T Q)[z,y,x] + the sum of (B^T R)[z,y',x] over the rows y' that y shadows )
+ * (+y: y' > y, -y: y' < y), where (B^T F)[z,y,x] = sum over (s, x') of w(s,x'; z,x) F[s,y,x'] and w is the total weight with which voxel
+ * (z, x) entered sample (s, x') in the forward (its four taps; a tap outside the volume drops out).  Positions and weights are the
+ * forward's, formed by the same fp32 expressions, so this is the transpose of the interpolation the forward used.  A voxel with rho = 0
+ * has a gradient; a voxel no ray's taps touch (possible at D > W) gets 0.  fp32, every sum in one fixed order, the views in ascending
+ * order, no atomics: bit-identical from call to call, independent of the other volumes of the batch, and every element of grad_vols is
+ * written (no need to zero it).  Limits, the checks of desc, the angle rule and the status codes are smk_volume_render_orbit's
+ * (SMK_LIGHT_POS_Z: SMK_ERR_UNSUPPORTED); on any error grad_vols is untouched.  workspace: device memory of at least
+ * smk_volume_render_orbit_backward_workspace(n, D, H, W, light) bytes, the same for any n_views (-1 for an unsupported shape or light):
+ * under SMK_LIGHT_NONE min(n, 16) * H * W floats (one value per ray), under SMK_LIGHT_POS_Y / SMK_LIGHT_NEG_Y two arrays of n*D*H*W
+ * floats (the prefix along y; the sum of B^T R) and min(n, 16) * H rows of (2 S + 1) * W floats of per-sample scratch; either scratch is cut
+ * to 256 MiB, and the call then walks the batch in smaller units.  4-byte aligned, passed with its size.  Caller-owned memory, the
+ * caller's stream, nothing allocated on the device, no synchronisation.  Launches: two per view and unit (a unit: up to 16 volumes,
+ * fewer where the scratch is cut), plus two under SMK_LIGHT_POS_Y / SMK_LIGHT_NEG_Y. */
+int64_t smk_volume_render_orbit_backward_workspace(int32_t n, int32_t D, int32_t H, int32_t W, int32_t light);
+int smk_volume_render_orbit_backward(const float *vols, int64_t vol_stride, int32_t n, int32_t D, int32_t H, int32_t W,
+                                     const smk_render_desc *desc, const double *azimuths, int32_t n_views,
+                                     const float *grad_image, int64_t grad_image_stride,      /* planes v*n_views+k; NULL: zero */
+                                     const float *grad_trans, int64_t grad_trans_stride,      /* NULL: zero; both NULL: SMK_ERR_INVALID */
+                                     float *grad_vols, int64_t grad_vol_stride,               /* dense [D][H][W] each */
+                                     void *workspace, int64_t workspace_bytes, void *stream);
+
 /* Free-camera views of the same n volumes: the orthographic camera of smk_volume_render_orbit with an elevation as well (SPEC_3D.md
  * section 10, "Free camera").  azimuths, elevations: n * n_views doubles each in HOST memory, degrees, volume-major (view k of volume v
  * at [v * n_views + k]); the azimuth is the orbit's, a positive elevation in [-90, 90] raises the camera toward larger y (it looks down).

@@ -6,7 +6,9 @@ The camera looks along +z (plane 0 nearest); single scattering from one directio
 transpose of the rule (section 10, "Gradient"; oracle: tests/render_grad_oracle.py).
 
 render_orbit turns that camera about the vertical axis y (section 10, "Orbit views"; csrc/render_orbit.hip, smk_volume_render_orbit;
-oracle: tests/render_orbit_oracle.py): any azimuth, several views per call, forward only.
+oracle: tests/render_orbit_oracle.py): any azimuth, several views per call.  With differentiable=True it carries a backward with respect to
+the volumes: smk_volume_render_orbit_backward (csrc/render_orbit_grad.hip), the front view's gradient rule over the samples followed by the
+transpose of the interpolation, summed over the views (section 10, "Orbit views -- Gradient"; oracle: tests/render_orbit_grad_oracle.py).
 
 render_camera adds an elevation to that camera (section 10, "Free camera"; csrc/render_camera.hip, smk_volume_render_camera; oracle:
 tests/render_camera_oracle.py): azimuth and elevation paired view by view, trilinear samples, forward only.
@@ -76,7 +78,7 @@ class _Kind(NamedTuple):
     lights: tuple
     forms: str              # the shapes of `vols` it takes
     dims: tuple
-    what: str = ""          # a moving camera: what a world-fixed light is not built for, and what has no backward yet
+    what: str = ""          # a moving camera: what a world-fixed light is not built for, and what has no backward by default
     render: str = ""
 
     def limits(self) -> str:
@@ -91,6 +93,8 @@ _BACKWARD = _FRONT._replace(stem="render_backward", entry="smk_volume_render_bac
                            query="smk_volume_render_backward_workspace")
 _ORBIT = _Kind("render_orbit", "orbit", "smk_volume_render_orbit", "smk_volume_render_orbit_workspace", None, ORBIT_MAX_WIDTH, ORBIT_LIGHTS,
                "float32 [D,H,W] or [n,D,H,W]", (3, 4), "orbit views", "orbit")
+_ORBIT_BACKWARD = _ORBIT._replace(stem="orbit_backward", entry="smk_volume_render_orbit_backward",
+                                 query="smk_volume_render_orbit_backward_workspace")
 _CAMERA = _Kind("render_camera", "camera", "smk_volume_render_camera", "smk_volume_render_camera_workspace", CAMERA_MAX_HEIGHT,
                 CAMERA_MAX_WIDTH, CAMERA_LIGHTS, "float32 [D,H,W] or [n,D,H,W]", (3, 4), "a moving camera", "free-camera")
 
@@ -155,6 +159,13 @@ def orbit_workspace(n: int, shape, light: str, device) -> Optional[torch.Tensor]
     """The scratch buffer smk_volume_render_orbit wants for n volumes of `shape` = (D, H, W) under `light` (None when it wants none:
     "none"; the prefix along y, n*D*H*W floats, under "+y" / "-y"); the same for any number of views; reusable on one stream."""
     return _workspace(_ORBIT, n, shape, light, device)
+
+
+def orbit_backward_workspace(n: int, shape, light: str, device) -> Optional[torch.Tensor]:
+    """The scratch buffer smk_volume_render_orbit_backward wants for n volumes of `shape` = (D, H, W) under `light`: one value per ray of
+    at most 16 volumes under "none"; the prefix along y and the shadow sums (n*D*H*W floats each) and at most 256 MiB of per-sample
+    scratch under "+y" / "-y"; the same for any number of views; reusable on one stream."""
+    return _workspace(_ORBIT_BACKWARD, n, shape, light, device)
 
 
 def camera_workspace(n: int, shape, light: str, device) -> Optional[torch.Tensor]:
@@ -273,9 +284,10 @@ def _each_run(kind: _Kind, vols, runs, shape, settings, middle, workspace, nbyte
         done += count
 
 
-def _forward(kind: _Kind, vols, settings, angles, *, transmittance, out, workspace):
+def _forward(kind: _Kind, vols, settings, angles, *, transmittance, out, workspace, differentiable=False, tables_out=None):
     """The call path of the three forward renders.  angles: None (the front view) or n -> (the [n][V] tables that the entry point takes,
-    whether the result has a view dimension); it runs where the moving cameras parse their angles."""
+    whether the result has a view dimension); it runs where the moving cameras parse their angles.  differentiable: the caller carries
+    the backward (no refusal of volumes that require a gradient); tables_out: a list that receives the angle tables."""
     settings = RenderSettings() if settings is None else settings
     if not isinstance(settings, RenderSettings):
         raise TypeError(f"{kind.fn}: settings must be a RenderSettings")
@@ -292,9 +304,14 @@ def _forward(kind: _Kind, vols, settings, angles, *, transmittance, out, workspa
         raise ValueError(f"{kind.fn}: shape {tuple(vols.shape)}: at least one volume")
     tables, views = ((), False) if angles is None else angles(n)
     if angles is not None:
-        if torch.is_grad_enabled() and vols.requires_grad:
+        if not differentiable and torch.is_grad_enabled() and vols.requires_grad:
+            if kind is _ORBIT:
+                raise RuntimeError("render_orbit: the orbit render has no backward unless it is asked for, and the volumes require a "
+                                   "gradient; pass differentiable=True, call under torch.no_grad() or detach them")
             raise RuntimeError(f"{kind.fn}: the {kind.render} render has no backward yet, and the volumes require a gradient; call under "
                                "torch.no_grad() or detach them (render_volumes, the front view, is differentiable)")
+        if tables_out is not None:
+            tables_out.extend(tables)
         dev = _lib.require_cuda(vols.device, kind.fn)
     if not _within(kind, D, H, W):
         raise ValueError(f"{kind.fn}: shape {tuple(vols.shape)} is not supported ({kind.limits()} per volume)")
@@ -391,8 +408,58 @@ def _render(vols, settings, *, transmittance, out, workspace):
     return _forward(_FRONT, vols, settings, None, transmittance=transmittance, out=out, workspace=workspace)
 
 
+def _orbit_angles(azimuth):
+    return lambda n: _tables((_angle(azimuth, n, "azimuth", "render_orbit"),), n, "render_orbit")
+
+
+def _orbit_backward(vols: torch.Tensor, settings: RenderSettings, table: torch.Tensor, grad_image, grad_trans) -> torch.Tensor:
+    """smk_volume_render_orbit_backward over the runs of `vols` (checked by render_orbit): the gradient in vols' shape, contiguous.
+    table: the [n][V] azimuths of the forward; grad_image / grad_trans: the image's shape, or None (= zero); not both None."""
+    shape = D, H, W = tuple(int(s) for s in vols.shape[-3:])
+    lead = tuple(vols.shape[:-3])
+    cells, HW, V = D * H * W, H * W, int(table.shape[1])
+    gi = None if grad_image is None else grad_image.to(torch.float32).contiguous()
+    gt = None if grad_trans is None else grad_trans.to(torch.float32).contiguous()
+    grad = torch.empty(lead + shape, dtype=torch.float32, device=vols.device)      # every element is written
+    runs = _runs(lead, vols.stride()[:-3], cells)
+    ws, nbytes = _call_workspace(_ORBIT_BACKWARD, max(r[1] for r in runs), shape, settings.light, None, vols.device)
+    ibase, tbase, gbase = gi is not None and gi.data_ptr(), gt is not None and gt.data_ptr(), grad.data_ptr()
+    flat = table.reshape(-1).tolist()
+
+    def middle(done, count):                       # the run's azimuths and V, the upstream gradients (None: zero) and the result
+        at = 4 * done * V * HW
+        return ((C.c_double * (count * V))(*flat[done * V:(done + count) * V]), V, ibase and ibase + at, HW, tbase and tbase + at, HW,
+                gbase + 4 * done * cells, cells)
+    _each_run(_ORBIT_BACKWARD, vols, runs, shape, settings, middle, ws, nbytes)
+    return grad
+
+
+class _RenderOrbit(torch.autograd.Function):
+    """render_orbit with a backward: the forward is the plain call (the same values bit for bit), the backward is
+    smk_volume_render_orbit_backward on the saved volumes and the forward's angle table.  Differentiable once."""
+
+    @staticmethod
+    def forward(ctx, vols, azimuth, settings, transmittance, workspace):
+        ctx.settings = settings
+        ctx.set_materialize_grads(False)           # an unused output's gradient arrives as None: the NULL of the entry point
+        ctx.save_for_backward(vols)
+        tables = []
+        res = _forward(_ORBIT, vols, settings, _orbit_angles(azimuth), transmittance=transmittance, out=None, workspace=workspace,
+                       differentiable=True, tables_out=tables)
+        ctx.table = tables[0]
+        return res
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_image, grad_trans=None):
+        (vols,) = ctx.saved_tensors
+        if grad_image is None and grad_trans is None:
+            return None, None, None, None, None
+        return _orbit_backward(vols, ctx.settings, ctx.table, grad_image, grad_trans), None, None, None, None
+
+
 def render_orbit(vols: torch.Tensor, azimuth, settings: Optional[RenderSettings] = None, *, transmittance: bool = False,
-                 out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+                 out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, differentiable: bool = False):
     """Render [n,D,H,W] or [D,H,W] float32 volumes from an orthographic camera that orbits the vertical axis y (SPEC_3D.md section 10,
     "Orbit views").  azimuth, in degrees (0: the front view of render_volumes; positive turns the viewing direction from +z toward +x):
       a number                  -> [n,H,W]    ([H,W] for one [D,H,W] volume)
@@ -400,10 +467,24 @@ def render_orbit(vols: torch.Tensor, azimuth, settings: Optional[RenderSettings]
       an [n,V] array or tensor  -> [n,V,H,W], one list per volume
     Returns the image, or (image, transmittance).  The batch may have any non-negative stride; every volume must be dense.  Lights:
     "none", "+y", "-y" ("+z" raises ValueError).  out: a contiguous float32 tensor of the image's shape to write into.  workspace:
-    orbit_workspace(...) of at least this call's size.  One call renders all the views.  There is no backward yet: volumes that require a
-    gradient raise RuntimeError (call under torch.no_grad() or detach them)."""
-    return _forward(_ORBIT, vols, settings, lambda n: _tables((_angle(azimuth, n, "azimuth", "render_orbit"),), n, "render_orbit"),
-                    transmittance=transmittance, out=out, workspace=workspace)
+    orbit_workspace(...) of at least this call's size.  One call renders all the views.
+
+    differentiable=False (the default): there is no backward, and volumes that require a gradient raise RuntimeError (call under
+    torch.no_grad(), detach them, or pass differentiable=True).  differentiable=True: when autograd is on and `vols.requires_grad`, the
+    outputs carry a backward with respect to the volumes (SPEC_3D.md section 10, "Orbit views -- Gradient";
+    smk_volume_render_orbit_backward): it takes the gradient of the image ([n,(V),H,W]) and, with transmittance=True, of the
+    transmittance, and returns a gradient of vols' shape, the views summed.  The forward values are the plain call's bit for bit.
+    `out=` raises ValueError then (an autograd output cannot be the caller's buffer), and a second derivative is not supported
+    (RuntimeError from autograd).  With nothing that requires a gradient it is the plain path."""
+    if differentiable and torch.is_grad_enabled() and isinstance(vols, torch.Tensor) and vols.requires_grad:
+        if out is not None:
+            raise ValueError("render_orbit: out= cannot be used when the volumes require a gradient (an autograd output cannot be the "
+                             "caller's buffer); call under torch.no_grad() or detach the volumes")
+        settings = RenderSettings() if settings is None else settings
+        if not isinstance(settings, RenderSettings):
+            raise TypeError("render_orbit: settings must be a RenderSettings")
+        return _RenderOrbit.apply(vols, azimuth, settings, bool(transmittance), workspace)
+    return _forward(_ORBIT, vols, settings, _orbit_angles(azimuth), transmittance=transmittance, out=out, workspace=workspace)
 
 
 def render_camera(vols: torch.Tensor, azimuth, elevation, settings: Optional[RenderSettings] = None, *, transmittance: bool = False,
