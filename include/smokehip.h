@@ -499,7 +499,9 @@ int smk_encoder_destroy(smk_encoder *enc);
  * one bit per tile; the main kernel's workgroups derive their tiles from those bits themselves and copy the features of the empty
  * tiles from the handle's zero-response table (the same kernel's output for an all-zero frame: bit-identical to computing them).
  * Two launches per call; dense input keeps the cost of the scan (about 0.5 %); SMK_ENC_SKIP=0
- * (read once per process) runs every tile.  Table and workspace live in the handle, are built on the first eligible call outside
+ * (read once per process) runs every tile.  At 256^2 under SMK_BF16X3 the decision is per pooled cell: a tile is two 8 x 8 cells with
+ * a 16 x 16 window each, and a tile with one all-zero window computes the other cell only (same bits; SMK_ENC_CELLS=0, read once per
+ * process, keeps whole tiles; smk_encoder_skip_stats counts tiles either way).  Table and workspace live in the handle, are built on the first eligible call outside
  * stream capture, and are reused by every later call: CALLS ON ONE HANDLE MUST BE STREAM-ORDERED (one stream, or ordered by events);
  * two forwards of one handle running concurrently on different streams would share the tile bits.  Nothing in the forward copies
  * to the host or synchronises, and every launch can be captured into a graph. */

@@ -27,6 +27,7 @@
 #include <stdlib.h>
 
 #include "encoder_tile.h"
+#include "encoder_cells.h"
 
 namespace smk {
 
@@ -479,8 +480,16 @@ template <bool X3> constexpr int b3_lds_total() { return b3_lds_bytes<X3>() + (X
 //                 once: one lookup's latency per SKIP_SLATE tiles, paid in the prologue beside the weight loads; inside the tile loop
 //                 tile_at is one LDS word.  A launch of more rounds refills the slate every SKIP_SLATE rounds.
 // All masks full (dense input): the list is the identity, nothing is looked up.
+// Per pooled cell (CELLS: k_encoder_b16 at PS == 8, where a tile is two 8 x 8 cells with a 16 x 16 window each; encoder_cells.h): the
+// scan also writes, per band, which tiles have a live left cell and which a live right cell (tile live = left | right).  The list is
+// then two segments, walked as one: every tile with both cells live in ascending order, then every tile with exactly one, in ascending
+// order; an entry carries the tile and which cell to run (enc_entry).  A one-cell tile costs about half a tile, and a launch ends with its
+// slowest workgroup: in a mixed list some workgroups would draw whole tiles only.  Segmented, every workgroup also changes bodies in
+// the same round.  Each segment has its own popcount prefix array; nothing else changes, and a kernel without CELLS reads the tile
+// masks as before.
 struct SkipArgs {
     const unsigned long long *masks = nullptr;              // null: direct path
+    const unsigned long long *cell_l = nullptr, *cell_r = nullptr;   // CELLS kernels: the bands' cell words (both = masks: whole tiles)
     int *count = nullptr;                                     // workgroup 0 stores the number of tiles run (smk_encoder_skip_stats)
     const float *table = nullptr;                             // the call's zero-response table: what an empty tile's cells hold
     int nbands = 0, lg_band_tiles = 0, bands_per_frame = 0;
@@ -489,23 +498,36 @@ struct SkipArgs {
 constexpr int scan_rows_for(int tiles_x) { return tiles_x <= 16 ? 4 : 64 / tiles_x; }
 constexpr int ENC_FRAME_FEATS = 128 * 1024;                   // features per frame, either layout
 constexpr int SKIP_CHUNKS = 256, SKIP_SLATE = 16;
+template <bool CELLS>
 struct SkipLds {
-    int cpre[SKIP_CHUNKS + 1];                                // tiles to run before chunk c; [SKIP_CHUNKS] = all of them
-    int wsum[4];
-    int slate[SKIP_SLATE];                                    // tile of round (r0 + i), r0 a multiple of SKIP_SLATE
+    static constexpr int SEGS = CELLS ? 2 : 1;
+    int cpre[SEGS][SKIP_CHUNKS + 1];                          // entries of segment s before chunk c; [SKIP_CHUNKS] = all of them
+    int wsum[SEGS][4];
+    int slate[SKIP_SLATE];                                    // entry of round (r0 + i), r0 a multiple of SKIP_SLATE
 };
+// Band j's mask of segment seg: the tile mask, or with CELLS the both-cells (seg 0) and exactly-one-cell (seg 1) masks.
+template <bool CELLS>
+__device__ __forceinline__ unsigned long long skip_mask(const SkipArgs &sa, int seg, int j) {
+    if (!CELLS) return sa.masks[j];
+    const unsigned long long l = sa.cell_l[j], r = sa.cell_r[j];
+    return seg ? enc_cells_one(l, r) : enc_cells_both(l, r);
+}
 
-__device__ __forceinline__ int skip_lookup(const SkipLds &s, const SkipArgs &sa, int k) {
+template <bool CELLS>
+__device__ __forceinline__ int skip_lookup(const SkipLds<CELLS> &s, const SkipArgs &sa, int k) {
+    const int seg = CELLS && k >= s.cpre[0][SKIP_CHUNKS];     // ranks beyond the first segment index the second
+    if (seg) k -= s.cpre[0][SKIP_CHUNKS];
+    const int *cpre = s.cpre[seg];
     int c = 0;                                                // the largest c with cpre[c] <= k: chunk c holds rank k (k < total)
 #pragma unroll
     for (int step = SKIP_CHUNKS / 2; step >= 1; step >>= 1)
-        if (s.cpre[c + step] <= k) c += step;
-    int n = k - s.cpre[c];
+        if (cpre[c + step] <= k) c += step;
+    int n = k - cpre[c];
     int j = c * ((sa.nbands + SKIP_CHUNKS - 1) / SKIP_CHUNKS);
-    unsigned long long m = sa.masks[j];
+    unsigned long long m = skip_mask<CELLS>(sa, seg, j);
     for (int pc = __popcll(m); n >= pc; pc = __popcll(m)) {   // ends inside the chunk: it holds rank k
         n -= pc;
-        m = sa.masks[++j];
+        m = skip_mask<CELLS>(sa, seg, ++j);
     }
     int pos = 0;                                              // the n-th set bit of m (n < popcount)
 #pragma unroll
@@ -516,11 +538,14 @@ __device__ __forceinline__ int skip_lookup(const SkipLds &s, const SkipArgs &sa,
             pos += w;
         }
     }
-    return (j << sa.lg_band_tiles) + pos;
+    const int tile = (j << sa.lg_band_tiles) + pos;
+    if (!CELLS) return tile;
+    return enc_entry(tile, seg, (int)(~sa.cell_l[j] >> pos) & 1);   // one cell: the right one iff the left is dead
 }
 
 // rounds r0 .. r0 + SKIP_SLATE - 1 of this workgroup -> s.slate (the caller's barrier publishes it)
-__device__ __forceinline__ void skip_slate(SkipLds &s, const SkipArgs &sa, int r0, int nrun) {
+template <bool CELLS>
+__device__ __forceinline__ void skip_slate(SkipLds<CELLS> &s, const SkipArgs &sa, int r0, int nrun) {
     const int i = threadIdx.x;
     if (i < SKIP_SLATE) {
         const long long k = (long long)blockIdx.x + (long long)(r0 + i) * gridDim.x;
@@ -529,29 +554,40 @@ __device__ __forceinline__ void skip_slate(SkipLds &s, const SkipArgs &sa, int r
 }
 
 // Number of work-list entries (workgroup-uniform; all 256 threads call it, it holds barriers); leaves the chunk sums and, unless
-// the list is the identity, the slate of rounds 0 .. SKIP_SLATE - 1 in LDS.
-__device__ __forceinline__ int tiles_to_run(SkipLds &s, const SkipArgs &sa, int ntiles) {
+// the list is the identity (`listed`), the slate of rounds 0 .. SKIP_SLATE - 1 in LDS.
+template <bool CELLS>
+__device__ __forceinline__ int tiles_to_run(SkipLds<CELLS> &s, const SkipArgs &sa, int ntiles, bool &listed) {
+    listed = false;
     if (!sa.masks) return ntiles;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int cs = (sa.nbands + SKIP_CHUNKS - 1) / SKIP_CHUNKS;
-    int c = 0;
-    for (int j = tid * cs, je = min(j + cs, sa.nbands); j < je; ++j) c += __popcll(sa.masks[j]);
-    int inc = c;
+    int c[SkipLds<CELLS>::SEGS], inc[SkipLds<CELLS>::SEGS];
 #pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int v = __shfl_up(inc, d);
-        if (lane >= d) inc += v;
+    for (int seg = 0; seg < SkipLds<CELLS>::SEGS; ++seg) {
+        c[seg] = 0;
+        for (int j = tid * cs, je = min(j + cs, sa.nbands); j < je; ++j) c[seg] += __popcll(skip_mask<CELLS>(sa, seg, j));
+        inc[seg] = c[seg];
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int v = __shfl_up(inc[seg], d);
+            if (lane >= d) inc[seg] += v;
+        }
+        if (lane == 63) s.wsum[seg][wave] = inc[seg];
     }
-    if (lane == 63) s.wsum[wave] = inc;
     __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += s.wsum[w];
-    s.cpre[tid] = base + inc - c;
-    if (tid == SKIP_CHUNKS - 1) s.cpre[SKIP_CHUNKS] = base + inc;
+#pragma unroll
+    for (int seg = 0; seg < SkipLds<CELLS>::SEGS; ++seg) {
+        int base = 0;
+        for (int w = 0; w < wave; ++w) base += s.wsum[seg][w];
+        s.cpre[seg][tid] = base + inc[seg] - c[seg];
+        if (tid == SKIP_CHUNKS - 1) s.cpre[seg][SKIP_CHUNKS] = base + inc[seg];
+    }
     __syncthreads();
-    const int nrun = __builtin_amdgcn_readfirstlane(s.cpre[SKIP_CHUNKS]);
+    const int nfirst = __builtin_amdgcn_readfirstlane(s.cpre[0][SKIP_CHUNKS]);
+    const int nrun = CELLS ? nfirst + __builtin_amdgcn_readfirstlane(s.cpre[SkipLds<CELLS>::SEGS - 1][SKIP_CHUNKS]) : nfirst;
     if (blockIdx.x == 0 && tid == 0) *sa.count = nrun;
-    if (nrun != ntiles) {
+    listed = nfirst != ntiles;                                // a complete first segment is ascending, i.e. the identity: no lookups
+    if (listed) {
         skip_slate(s, sa, 0, nrun);
         __syncthreads();
     }
@@ -559,7 +595,8 @@ __device__ __forceinline__ int tiles_to_run(SkipLds &s, const SkipArgs &sa, int 
 }
 // Entry k = blockIdx.x + round * gridDim.x of the list (k < nrun).  Workgroup-uniform; at a multiple of SKIP_SLATE > 0 it refills
 // the slate behind a barrier, so every thread of the workgroup calls it at the same place.
-__device__ __forceinline__ int tile_at(SkipLds &s, const SkipArgs &sa, bool listed, int round, int k, int nrun) {
+template <bool CELLS>
+__device__ __forceinline__ int tile_at(SkipLds<CELLS> &s, const SkipArgs &sa, bool listed, int round, int k, int nrun) {
     if (!listed) return k;
     if (round > 0 && (round & (SKIP_SLATE - 1)) == 0) {
         skip_slate(s, sa, round, nrun);                       // the slate's last reader is one barrier back at least
@@ -573,8 +610,11 @@ __device__ __forceinline__ int tile_at(SkipLds &s, const SkipArgs &sa, bool list
 // copy needs no ordering against the tile loop; it runs outside it (four loads in flight per thread, nothing live across a tile).
 // The stores are non-temporal: 31 MB per headline launch that nothing in the launch reads again, beside a K loop whose weight
 // fragments come from L2.
-template <int PS, bool TOKENS>
+// CELLS (PS == 8: CR = 1, CC = 2): the dead cell of a one-cell tile is copied too.  Token-major a vector lies inside one cell; NCHW a
+// vector is a channel's two cells, of which a one-cell tile gets the dead one as a single word.
+template <int PS, bool TOKENS, bool CELLS>
 __device__ __forceinline__ void skip_fill(const SkipArgs &sa, int lg_tiles_x, float *__restrict__ features) {
+    static_assert(!CELLS || PS == 8, "cells are the two halves of a tile at PS == 8 only");
     constexpr bool PART = PS >= 16;                           // frames beyond 256^2: `features` and the table hold per-tile partials
     constexpr int CR = PART ? 1 : B3_TH / PS, CC = PART ? 1 : B3_TW / PS;   // cells per tile: rows x columns
     // token-major: a cell row of a tile is CC cells x 128 channels, contiguous (float4).  NCHW: a channel's CC cells of one row.
@@ -585,37 +625,49 @@ __device__ __forceinline__ void skip_fill(const SkipArgs &sa, int lg_tiles_x, fl
     typedef float vec_t __attribute__((ext_vector_type(VW)));
     const int tid = threadIdx.x, tiles_x = 1 << lg_tiles_x, band_tiles = 1 << sa.lg_band_tiles, total = band_tiles * UPT;
     const unsigned long long full = band_tiles == 64 ? ~0ull : (1ull << band_tiles) - 1;
+    auto uniform = [](unsigned long long mv) -> unsigned long long {
+        return ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned int)(mv >> 32)) << 32) |
+               (unsigned int)__builtin_amdgcn_readfirstlane((unsigned int)mv);
+    };
     for (int band = blockIdx.x; band < sa.nbands; band += gridDim.x) {
-        const unsigned long long mv = sa.masks[band];
-        const unsigned long long m = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned int)(mv >> 32)) << 32) |
-                                     (unsigned int)__builtin_amdgcn_readfirstlane((unsigned int)mv);
+        // ml, mr: tiles whose left / right cell the tile loop writes (without CELLS both are the tile mask)
+        const unsigned long long ml = uniform(CELLS ? sa.cell_l[band] : sa.masks[band]), mr = CELLS ? uniform(sa.cell_r[band]) : ml;
+        const unsigned long long m = ml & mr;
         if (m == full) continue;
         const int lg_rows = PART ? sa.lg_band_tiles - lg_tiles_x : 2;      // tile rows per band (scan_rows_for)
         const int b = band / sa.bands_per_frame, ty0 = (band - b * sa.bands_per_frame) << lg_rows;
         float *out = features + (size_t)b * (PART ? (size_t)sa.bands_per_frame << (sa.lg_band_tiles + 7) : (size_t)ENC_FRAME_FEATS);
         for (int i0 = tid; i0 < total; i0 += 256 * UNR) {
             vec_t v[UNR];
-            int off[UNR];
+            int off[UNR], word[UNR];                          // word: -1 the whole vector, else the one word of it to copy (CELLS, NCHW)
 #pragma unroll
             for (int j = 0; j < UNR; ++j) {
                 const int i = i0 + 256 * j, tl = i / UPT, u = i - tl * UPT;
                 off[j] = -1;
+                word[j] = -1;
                 if (i >= total || ((m >> tl) & 1)) continue;
                 const int ty = ty0 + (tl >> lg_tiles_x), tx = tl & (tiles_x - 1);
+                const bool lrun = CELLS && ((ml >> tl) & 1), rrun = CELLS && ((mr >> tl) & 1);   // at most one of them
                 if (PART) {
                     off[j] = ((ty << lg_tiles_x) + tx) * 128 + u * 4;
                 } else if (TOKENS) {
                     const int a = u / ROWV, q = u - a * ROWV;
+                    if (CELLS && (q >= 32 ? rrun : lrun)) continue;       // this vector is of the cell the tile loop writes
                     off[j] = ((ty * CR + a) * 32 + tx * CC) * 128 + q * 4;
                 } else {
                     const int vv = u % VPR, a = (u / VPR) % CR, o = u / (VPR * CR);
                     off[j] = o * 1024 + (ty * CR + a) * 32 + tx * CC + vv * VW;
+                    if (CELLS && (lrun || rrun)) word[j] = lrun ? 1 : 0;
                 }
                 v[j] = *reinterpret_cast<const vec_t *>(sa.table + off[j]);
             }
 #pragma unroll
-            for (int j = 0; j < UNR; ++j)
-                if (off[j] >= 0) __builtin_nontemporal_store(v[j], reinterpret_cast<vec_t *>(out + off[j]));
+            for (int j = 0; j < UNR; ++j) {
+                if (off[j] < 0) continue;
+                if (CELLS && !TOKENS && word[j] >= 0)
+                    __builtin_nontemporal_store(word[j] ? v[j][VW - 1] : v[j][0], out + off[j] + word[j]);
+                else __builtin_nontemporal_store(v[j], reinterpret_cast<vec_t *>(out + off[j]));
+            }
         }
     }
 }
@@ -682,37 +734,48 @@ __device__ __forceinline__ void halo_to_lds(T *xs, float v0, float v1, Word word
 //   the kernel's loop tail puts those registers into LDS (halo_to_lds), holds its barrier and sets t = tn
 //   end     the trailing fill
 // tiles_to_run and tile_at hold barriers: every thread of the workgroup calls begin and next, at the same place.
+// CELLS: the list's entries say which cells of the tile to run (cell / celln, as enc_entry_cell gives them; 0 = the whole tile).
+template <bool CELLS = false>
 struct TileWalk {
-    int k, nrun, round, t, tn;
+    int k, nrun, round, t, tn, cell, celln;
     bool listed;
 
+    __device__ __forceinline__ int entry(SkipLds<CELLS> &skl, const SkipArgs &sa, int kk, int &what) {
+        const int e = tile_at(skl, sa, listed, round, kk, nrun);
+        what = CELLS && listed ? enc_entry_cell(e) : 0;
+        return CELLS && listed ? enc_entry_tile(e) : e;
+    }
     template <int PS, bool TOKENS, class T, class Word>
-    __device__ __forceinline__ void begin(SkipLds &skl, const SkipArgs &sa, const TileSrc &src, int ntiles, int stagger,
+    __device__ __forceinline__ void begin(SkipLds<CELLS> &skl, const SkipArgs &sa, const TileSrc &src, int ntiles, int stagger,
                                           float *__restrict__ features, T *xs, Word word) {
         k = blockIdx.x;
-        nrun = tiles_to_run(skl, sa, ntiles);
-        listed = nrun != ntiles;                              // a complete list is ascending, i.e. the identity: no lookups
+        nrun = tiles_to_run(skl, sa, ntiles, listed);
         round = 0;
-        t = k < nrun ? tile_at(skl, sa, listed, 0, k, nrun) : 0;
+        cell = 0;
+        t = k < nrun ? entry(skl, sa, k, cell) : 0;
         // Workgroups that share a CU run the same program with the same period; started together they stay in lockstep
         // (both in the VALU-heavy conv1 phase, then both in the MFMA loop).  Delay every other dispatch round by about
         // half a tile so that one workgroup's conv1 overlaps the other's K loop (speed only, never correctness).
         // On the skip path that round copies its share of the empty tiles' cells instead (skip_fill_first): the same shift, not idle.
-        if (listed && skip_fill_first()) skip_fill<PS, TOKENS>(sa, src.lg_tiles_x, features);
+        if (listed && skip_fill_first()) skip_fill<PS, TOKENS, CELLS>(sa, src.lg_tiles_x, features);
         else if (stagger > 0 && ((blockIdx.x / 256) & 1))
             for (int i = 0; i < stagger; ++i) __builtin_amdgcn_s_sleep(127);
         const int tid = threadIdx.x;
         if (k < nrun) halo_to_lds(xs, src.fetch(t, tid), src.fetch(t, tid + 256), word);
         __syncthreads();
     }
-    __device__ __forceinline__ void next(SkipLds &skl, const SkipArgs &sa, const TileSrc &src, float &xr0, float &xr1) {
+    __device__ __forceinline__ void next(SkipLds<CELLS> &skl, const SkipArgs &sa, const TileSrc &src, float &xr0, float &xr1) {
         const int kn = k + gridDim.x;
         ++round;
-        tn = kn < nrun ? tile_at(skl, sa, listed, round, kn, nrun) : 0;
+        celln = 0;
+        tn = kn < nrun ? entry(skl, sa, kn, celln) : 0;
         xr0 = 0.f;
         xr1 = 0.f;
         if (kn < nrun) {
-            const int tid = threadIdx.x;
+            int tid = threadIdx.x;
+            // CELLS: the element's row and column are formed here, per tile, instead of living through both tile bodies' K loops
+            // (k_encoder_b16's whole-tile loop has no registers to spare)
+            if (CELLS) asm volatile("" : "+v"(tid));
             xr0 = src.fetch(tn, tid);
             xr1 = src.fetch(tn, tid + 256);
         }
@@ -721,8 +784,13 @@ struct TileWalk {
     __device__ __forceinline__ void end(const SkipArgs &sa, const TileSrc &src, float *__restrict__ features) const {
         if (listed && !skip_fill_first()) {
             __builtin_amdgcn_s_setprio(0);
-            skip_fill<PS, TOKENS>(sa, src.lg_tiles_x, features);
+            skip_fill<PS, TOKENS, CELLS>(sa, src.lg_tiles_x, features);
         }
+    }
+    // the loop tail's step to the next entry
+    __device__ __forceinline__ void advance() {
+        t = tn;
+        cell = celln;
     }
 };
 
@@ -900,8 +968,8 @@ __global__ __launch_bounds__(256, 2) void k_encoder_bf16(const float *__restrict
     const int lane_off = (r >> 4) * 4 * B3_A1_ROW + (r & 15) * B3_A1_PITCH + 8 * hi * 2;
 
     const TileSrc src{frames, fstride, H, W, lg_tiles_x, lg_tiles_per_frame};
-    __shared__ SkipLds skl;
-    TileWalk wk;
+    __shared__ SkipLds<false> skl;
+    TileWalk<> wk;
     wk.begin<PS, TOKENS>(skl, sa, src, ntiles, stagger, features, xs, [](float v) { return v; });
 
     for (; wk.k < wk.nrun; wk.k += gridDim.x) {
@@ -1018,7 +1086,7 @@ __global__ __launch_bounds__(256, 2) void k_encoder_bf16(const float *__restrict
         // "every wave is done reading a1" and "xs is visible"
         halo_to_lds(xs, xr0, xr1, [](float v) { return v; });
         __syncthreads();
-        wk.t = wk.tn;
+        wk.advance();
     }
     wk.end<PS, TOKENS>(sa, src, features);
 }
@@ -1047,6 +1115,7 @@ __global__ __launch_bounds__(256, 2) void k_encoder_b16(const float *__restrict_
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // x tile kept already split: one word per pixel, hi bf16 in the low half, lo bf16 in the high half (split once by the staging
     // thread; every wave's fragment builder then needs one v_perm_b32 per element pair instead of two 3-instruction splits)
+    constexpr bool CELLS = PS == 8;                           // a tile is two pooled cells: one-cell tiles run the second body below
     unsigned int *xs = reinterpret_cast<unsigned int *>(smem);
     unsigned char *a1h = smem + B3_XS_BYTES, *a1l = a1h + S16_A1_BYTES;
     unsigned char *w1s = a1l + S16_A1_BYTES;
@@ -1088,13 +1157,17 @@ __global__ __launch_bounds__(256, 2) void k_encoder_b16(const float *__restrict_
         return (unsigned int)__builtin_bit_cast(unsigned short, vh) | ((unsigned int)__builtin_bit_cast(unsigned short, vl) << 16);
     };
     const TileSrc src{frames, fstride, H, W, lg_tiles_x, lg_tiles_per_frame};
-    __shared__ SkipLds skl;
-    TileWalk wk;
-    wk.begin<PS, TOKENS>(skl, sa, src, ntiles, stagger, features, xs, pack_split);
+    __shared__ SkipLds<CELLS> skl;
+    TileWalk<CELLS> wk;
+    wk.template begin<PS, TOKENS>(skl, sa, src, ntiles, stagger, features, xs, pack_split);
 
     for (; wk.k < wk.nrun; wk.k += gridDim.x) {
         int b, r0, c0;
         src.decode(wk.t, b, r0, c0);
+        // CELLS: conv1's lane constants (pixel, halo coordinates, a1 store offsets of every unit) are formed per tile from an opaque copy of
+        // the lane's pixel index: kept across tiles they would live through both K loops, and the whole-tile loop has no registers to spare
+        int rt = r;
+        if (CELLS) asm volatile("" : "+v"(rt));
 
         __builtin_amdgcn_s_setprio(S16_PRIO_CONV1);
 #ifdef SMK_ENC_ABLATE      // timing ablations (tools/enc_ablate.sh; never a product build): 1 conv1 only on a workgroup's first tile,
@@ -1104,26 +1177,35 @@ __global__ __launch_bounds__(256, 2) void k_encoder_b16(const float *__restrict_
         constexpr bool abl_conv1 = true;
 #endif
         // ---- conv1 on MFMA (32x32x16, as k_encoder_bf16): results stored into the swizzled a1 image
-        auto x_frags = [&](int pb, bf16x8 (&xh)[4], bf16x8 (&xl)[4], int &pix, bool &valid, bool &inimg) {
-            const int pp = pb * 32 + r;
-            valid = pp < B3_APIX;
-            pix = valid ? pp : B3_APIX - 1;
-            const int ar = pix / B3_AW, ac = pix - ar * B3_AW;
-            const int ii = r0 - 1 + ar, jj = c0 - 1 + ac;
-            inimg = valid && ii >= 0 && ii < H && jj >= 0 && jj < W;
+        // the B fragments of the a1 halo pixel at (ar, ac): 8 rows x 8 columns of the x tile from there on, this lane's 4 rows
+        // K = 64 holds the 7 x 7 patch as 8 x 8: row 7 and column 7 carry zero weights.  Their x operands are zeros too, not the pixels
+        // that lie there (the column is not read, the row is the tile's zero row): 0 x NaN and 0 x Inf are NaN, and a pixel must not reach
+        // an activation 4 columns to its left or 4 rows above, outside the window the tile skip tests.  Finite frames: the same bits.
+        auto x_build = [&](int ar, int ac, bf16x8 (&xh)[4], bf16x8 (&xl)[4]) {
             const unsigned int *xp = xs + (ar + hi) * B3_XW + ac;
+            const unsigned int *xz = hi ? xs + (B3_XH - 1) * B3_XW + ac : xp + 6 * B3_XW;      // patch row 6 (hi 0) or 7 (hi 1: zeros)
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 unsigned int wh[4], wl[4];
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) {
-                    const unsigned int e0 = xp[s * 2 * B3_XW + 2 * jj], e1 = xp[s * 2 * B3_XW + 2 * jj + 1];
+                    const unsigned int *row = s == 3 ? xz : xp + s * 2 * B3_XW;
+                    const unsigned int e0 = row[2 * jj], e1 = jj == 3 ? 0u : row[2 * jj + 1];
                     wh[jj] = __builtin_amdgcn_perm(e1, e0, 0x05040100u);          // low halves: the two hi parts
                     wl[jj] = __builtin_amdgcn_perm(e1, e0, 0x07060302u);          // high halves: the two lo parts
                 }
                 xh[s] = __builtin_bit_cast(bf16x8, make_uint4(wh[0], wh[1], wh[2], wh[3]));
                 xl[s] = __builtin_bit_cast(bf16x8, make_uint4(wl[0], wl[1], wl[2], wl[3]));
             }
+        };
+        auto x_frags = [&](int pb, bf16x8 (&xh)[4], bf16x8 (&xl)[4], int &pix, bool &valid, bool &inimg) {
+            const int pp = pb * 32 + rt;
+            valid = pp < B3_APIX;
+            pix = valid ? pp : B3_APIX - 1;
+            const int ar = pix / B3_AW, ac = pix - ar * B3_AW;
+            const int ii = r0 - 1 + ar, jj = c0 - 1 + ac;
+            inimg = valid && ii >= 0 && ii < H && jj >= 0 && jj < W;
+            x_build(ar, ac, xh, xl);
         };
         auto conv1_store = [&](const f32x16 &acc, int cb, int pix, bool valid, bool inimg) {
             const int sw = pix & 7;
@@ -1148,176 +1230,320 @@ __global__ __launch_bounds__(256, 2) void k_encoder_b16(const float *__restrict_
                 }
             }
         };
-        if (abl_conv1) {
-            bf16x8 xh[4], xl[4];
-            int pix; bool valid, inimg;
-            x_frags(wave, xh, xl, pix, valid, inimg);
-            f32x16 acc0, acc1;
-            conv1_both<true>(w1s, xh, xl, acc0, acc1);
-            conv1_store(acc0, 0, pix, valid, inimg);
-            conv1_store(acc1, 1, pix, valid, inimg);
-        }
-        if (abl_conv1) {
-            bf16x8 xh[4], xl[4];
-            int pix; bool valid, inimg;
-            const int cb = wave & 1;
-            x_frags(4 + (wave >> 1), xh, xl, pix, valid, inimg);
-            f32x16 acc;
-            conv1_one<true>(w1s, cb, xh, xl, acc);
-            conv1_store(acc, cb, pix, valid, inimg);
-        }
-#if !defined(SMK_ENC_ABLATE) || !(SMK_ENC_ABLATE & 4)
-        __syncthreads();                                      // a1 complete; xs is free again
-#endif
-        __builtin_amdgcn_s_setprio(S16_PRIO_KLOOP);
-
-        float xr0, xr1;                                       // next tile's x halo -> registers (lands under the K loop)
-        wk.next(skl, sa, src, xr0, xr1);
-
-        // ---- conv2: acc[mt][nt][reg] = D(pixel row mt, column 4 kg + reg; channel 16 nt + px of the wave's 32)
-        f32x4v acc[8][2];
-#pragma unroll
-        for (int mt = 0; mt < 8; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) acc[mt][nt][g] = 0.f;
-        // unit k (0..35) = tap * 4 + half * 2 + hm: M tiles 4hm .. 4hm+3 of k-step ks = k >> 1 = tap * 2 + half.  The loop runs over
-        // the 9 taps (runtime) x 4 unrolled units.  Per tap four lane registers om[m] = pixel base ^ swizzle term of row m + ki
-        // are formed once (the base is a multiple of 128 and the term < 128, so base + (c ^ t) = base ^ t ^ c): a fragment pair then
-        // costs ONE xor, and the row offsets ki * 2304 (scalar) and 4hm * 2304 + m * 2304 (ds_read immediate) are free.
-        const int c16[2] = {kg << 4, (4 + kg) << 4};
-        auto tap_consts = [&](int ki, int kj, int (&om)[4]) {
-#pragma unroll
-            for (int m = 0; m < 4; ++m) om[m] = ((px + kj) << 7) ^ (((px + kj + 2 * (m + ki)) & 7) << 4);
-        };
-        auto load_a = [&](int ki, int half, int hm, const int (&om)[4], bf16x8 (&ah)[4], bf16x8 (&al)[4]) {
-            const unsigned char *ph = a1h + ki * (B3_AW * 128), *pl = a1l + ki * (B3_AW * 128);      // wave-uniform part
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const int off = om[m] ^ c16[half];
-                ah[m] = *reinterpret_cast<const bf16x8 *>(ph + off + (4 * hm + m) * (B3_AW * 128));
-                al[m] = *reinterpret_cast<const bf16x8 *>(pl + off + (4 * hm + m) * (B3_AW * 128));
-            }
-        };
-        bf16x8 ahA[4], alA[4], ahB[4], alB[4];
-        int om[4];
-        tap_consts(0, 0, om);
-        load_a(0, 0, 0, om, ahA, alA);
-        int ki = 0, kj = 0;
-#pragma unroll 1
-        for (int tap = 0; tap < 9; ++tap) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int half = u >> 1, hm = u & 1, slot = half % RING;
-                if (hm == 0) {
-                    // refill: k-step ks + 1 into the slot consumed one k-step ago.  All four fragments (both N tiles, hi and lo) are
-                    // requested in the FIRST unit of the k-step, right at its start: two units (768 cycles) before their first use.
-                    // Measured placements of the ring loads within a unit: early 1.06 ms, middle 1.075, late 1.11.
-                    int kn = tap * 2 + half + RING - 1;
-                    kn = kn >= 18 ? kn - 18 : kn;
-                    kn = __builtin_amdgcn_readfirstlane(kn);
-#pragma unroll
-                    for (int nt = 0; nt < 2; ++nt) {
-                        bq[(slot + RING - 1) % RING][nt][0] = load_b(kn, 0, nt);
-                        bq[(slot + RING - 1) % RING][nt][1] = load_b(kn, 1, nt);
-                    }
-                }
-                if (u < 3) {                                   // next unit: same tap
-                    if (u & 1) load_a(ki, (u + 1) >> 1, (u + 1) & 1, om, ahA, alA);
-                    else load_a(ki, (u + 1) >> 1, (u + 1) & 1, om, ahB, alB);
-                } else if (tap < 8) {                          // first unit of the next tap (u = 3 is odd: set A)
-                    kj = kj == 2 ? 0 : kj + 1;
-                    ki = kj == 0 ? ki + 1 : ki;
-                    tap_consts(ki, kj, om);
-                    load_a(ki, 0, 0, om, ahA, alA);
-                }
-                // product-major emission: consecutive MFMAs go to different accumulators (dependency distance 8 instead of 1); each
-                // accumulator still sums lo*hi, hi*lo, hi*hi in that order, so results are bitwise those of the chain-major form
-#pragma unroll
-                for (int pr = 0; pr < 3; ++pr)
-#pragma unroll
-                    for (int m = 0; m < 4; ++m)
-#pragma unroll
-                        for (int nt = 0; nt < 2; ++nt) {
-                            const bf16x8 bh = __builtin_bit_cast(bf16x8, bq[slot][nt][0]);
-                            const bf16x8 bl = __builtin_bit_cast(bf16x8, bq[slot][nt][1]);
-                            f32x4v &c = acc[4 * hm + m][nt];
-                            const bf16x8 ah = (u & 1) ? ahB[m] : ahA[m], al = (u & 1) ? alB[m] : alA[m];
-#if defined(SMK_ENC_ABLATE) && (SMK_ENC_ABLATE & 8)
-                            asm volatile("" :: "v"(al), "v"(ah), "v"(bh), "v"(bl), "v"(c));      // operands stay live, no MFMA
-#else
-                            if (pr == 0) c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, c, 0, 0, 0);
-                            else if (pr == 1) c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, c, 0, 0, 0);
-                            else c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, c, 0, 0, 0);
-#endif
-                        }
-                // 24 MFMAs of 16 cycles.  The next unit's 8 fragment reads are spread evenly, one after every third MFMA; the ring loads
-                // go right behind the first MFMAs.  (One read per second MFMA in the first 16 -- what hipcc also does unpinned -- is
-                // 4 % slower; see DESIGN.md 3.2 for the placements measured.)
-#pragma unroll
-                for (int i = 0; i < 24; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    if (i % 3 == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    else if (hm == 0 && (i == 1 || i == 2 || i == 4 || i == 5)) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-
-        // ---- epilogue: BN2 + ReLU + block-mean pool.  Lane: channel o0 (nt 0) / o0 + 16 (nt 1), pixels (row mt, cols 4kg .. 4kg+3)
         auto out_index = [&](int pi, int pj, int o) -> size_t {
             return TOKENS ? ((size_t)b * 1024 + pi * 32 + pj) * 128 + o : ((size_t)b * 128 + o) * 1024 + pi * 32 + pj;
         };
+        float xr0, xr1;                                       // the next tile's x halo (TileWalk::next)
+        if (CELLS && wk.cell != 0) {
+            // ---- a one-cell tile (encoder_cells.h): only cell `side` has a non-zero window; skip_fill writes the other one.  The same
+            // a1 image, swizzle and K order per output as below, over half the pixels: every accumulator holds the bits the whole
+            // tile would give it.
+            //   conv1: the 10 x 10 a1 pixels the cell's conv2 reads, 4 pixel blocks of 32 (one per wave, both channel blocks) for 6.
+            //   conv2: 4 M blocks (block m = cell rows 2m, 2m + 1 x 8 columns) for 8; a unit is a whole k-step, 24 MFMAs as below.
+            //          The rows of a block are 18 pixels = 2 (mod 8) apart, so in a ds_read_b128 lane group two lane pairs share a
+            //          16-byte unit (2-way) where the whole tile's 16 consecutive pixels are conflict-free: half the reads at twice
+            //          the cost each.
+            //   B ring: the same 18 k-steps, consumed twice as fast.  A third slot (its registers are free: half the accumulators)
+            //          keeps the loads two units ahead as below; it enters and leaves with slot 0 = k-step 0 like the whole tile.
+            const int side = wk.cell & 1;
+            // This body's lane constants are formed per tile from opaque copies: hoisted out of the tile loop they would stay live
+            // through the whole tile's K loop, which has no registers to spare (scratch 0 there is worth more than these few adds).
+            int cpx = px, ckg = kg;
+            asm volatile("" : "+v"(cpx), "+v"(ckg));
+            uint4 bqx[2][2];
+            auto ring_load = [&](uint4 (&slot)[2][2], int ks) {
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt) {
+                    slot[nt][0] = load_b(ks, 0, nt);
+                    slot[nt][1] = load_b(ks, 1, nt);
+                }
+            };
+            ring_load(bq[1], 1);                              // lands under conv1
+            if (abl_conv1) {
+                bf16x8 xh[4], xl[4];
+                const int pp = wave * 32 + rt;
+                const bool valid = pp < ENC_CELL_A1_PIX;
+                int ar, ac;
+                enc_cell_conv1_pixel(valid ? pp : ENC_CELL_A1_PIX - 1, side, ar, ac);
+                const int pix = ar * B3_AW + ac, ii = r0 - 1 + ar, jj = c0 - 1 + ac;
+                const bool inimg = valid && ii >= 0 && ii < H && jj >= 0 && jj < W;
+                x_build(ar, ac, xh, xl);
+                f32x16 acc0, acc1;
+                conv1_both<true>(w1s, xh, xl, acc0, acc1);
+                conv1_store(acc0, 0, pix, valid, inimg);
+                conv1_store(acc1, 1, pix, valid, inimg);
+            }
+            __syncthreads();                                  // a1 complete; xs is free again
+            __builtin_amdgcn_s_setprio(S16_PRIO_KLOOP);
+            wk.next(skl, sa, src, xr0, xr1);
+
+            // acc[m][nt][reg] = D(cell row 2m + (ckg >> 1), cell column 4 (ckg & 1) + reg; channel 16 nt + cpx of the wave's 32)
+            f32x4v acc[4][2];
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) acc[m][nt][g] = 0.f;
+            // A addressing as below with p = pl + kj + (2m + ki) * 18: the swizzle term (p & 7) depends on m & 1 only
+            const int c16[2] = {ckg << 4, (4 + ckg) << 4};
+            const int pl = enc_cell_a1_pixel(0, cpx, 0, 0, side);
+            auto tap_consts = [&](int ki, int kj, int (&om)[2]) {
+#pragma unroll
+                for (int m = 0; m < 2; ++m) om[m] = ((pl + kj) << 7) ^ (((pl + kj + 2 * (2 * m + ki)) & 7) << 4);
+            };
+            auto load_a = [&](int ki, int half, const int (&om)[2], bf16x8 (&ah)[4], bf16x8 (&al)[4]) {
+                const unsigned char *ph = a1h + ki * (B3_AW * 128), *pw = a1l + ki * (B3_AW * 128);      // wave-uniform part
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+                    const int off = om[m & 1] ^ c16[half];
+                    ah[m] = *reinterpret_cast<const bf16x8 *>(ph + off + 2 * m * (B3_AW * 128));
+                    al[m] = *reinterpret_cast<const bf16x8 *>(pw + off + 2 * m * (B3_AW * 128));
+                }
+            };
+            bf16x8 ahA[4], alA[4], ahB[4], alB[4];
+            int om[2];
+            tap_consts(0, 0, om);
+            load_a(0, 0, om, ahA, alA);
+            // unit u of tap row ki = k-step ks = 6 ki + u: tap (ki, kj = u >> 1), channel half u & 1, ring slot u % 3
+#pragma unroll 1
+            for (int ki = 0; ki < 3; ++ki) {
+#pragma unroll
+                for (int u = 0; u < 6; ++u) {
+                    const int kj = u >> 1, half = u & 1;
+                    uint4 (&bs)[2][2] = u % 3 == 0 ? bq[0] : u % 3 == 1 ? bq[1] : bqx;
+                    uint4 (&bn)[2][2] = (u + 2) % 3 == 0 ? bq[0] : (u + 2) % 3 == 1 ? bq[1] : bqx;
+                    // refill: k-step ks + 2 into the slot consumed one unit ago; the tile's last two units leave k-step 0 in slot 0
+                    if (u < 4) ring_load(bn, __builtin_amdgcn_readfirstlane(6 * ki + u + 2));
+                    else if (u == 4) ring_load(bn, __builtin_amdgcn_readfirstlane(ki < 2 ? 6 * ki + 6 : 0));
+                    else if (ki < 2) ring_load(bn, __builtin_amdgcn_readfirstlane(6 * ki + 7));
+                    if (u < 5) {                               // next unit: same tap row
+                        if (u & 1) {
+                            tap_consts(ki, kj + 1, om);
+                            load_a(ki, 0, om, ahA, alA);
+                        } else {
+                            load_a(ki, 1, om, ahB, alB);
+                        }
+                    } else if (ki < 2) {                       // first unit of the next tap row (u = 5 is odd: set A)
+                        tap_consts(ki + 1, 0, om);
+                        load_a(ki + 1, 0, om, ahA, alA);
+                    }
+#pragma unroll
+                    for (int pr = 0; pr < 3; ++pr)
+#pragma unroll
+                        for (int m = 0; m < 4; ++m)
+#pragma unroll
+                            for (int nt = 0; nt < 2; ++nt) {
+                                const bf16x8 bh = __builtin_bit_cast(bf16x8, bs[nt][0]);
+                                const bf16x8 bl = __builtin_bit_cast(bf16x8, bs[nt][1]);
+                                f32x4v &c = acc[m][nt];
+                                const bf16x8 ah = half ? ahB[m] : ahA[m], al = half ? alB[m] : alA[m];
+                                if (pr == 0) c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, c, 0, 0, 0);
+                                else if (pr == 1) c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, c, 0, 0, 0);
+                                else c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, c, 0, 0, 0);
+                            }
+#pragma unroll
+                    for (int i = 0; i < 24; ++i) {             // the whole tile's placement of the 8 fragment reads and 4 ring loads
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                        if (i % 3 == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                        else if (i == 1 || i == 2 || i == 4 || i == 5) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+
+            // epilogue.  The whole tile's lane sums rows 0 .. 7 x its 4 columns in order, then adds lane ^ 16.  Here lanes ckg 0/1 hold
+            // the even rows and ckg 2/3 the odd rows of those columns: bn_relu where the value lives, then one v_permlane32_swap per
+            // register pair (nt 0, nt 1) leaves the low half-wave with both row parities of channel o0 and the high one with those
+            // of o0 + 16 -- ev = rows 2m, od = rows 2m + 1 -- and the adds run in the whole tile's order.
+            float sum = 0.f;
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                float ev[4], od[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const unsigned int va = __builtin_bit_cast(unsigned int, bn_relu(acc[m][0][i], s2a, t2a));
+                    const unsigned int vb = __builtin_bit_cast(unsigned int, bn_relu(acc[m][1][i], s2b, t2b));
+                    const auto sw = __builtin_amdgcn_permlane32_swap(va, vb, false, false);   // va's high lanes <-> vb's low lanes
+                    ev[i] = __builtin_bit_cast(float, (unsigned int)sw[0]);
+                    od[i] = __builtin_bit_cast(float, (unsigned int)sw[1]);
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i) sum += ev[i];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) sum += od[i];
+            }
+            const float other = __shfl_xor(sum, 16);
+            const float total = (ckg & 1) == 0 ? sum + other : other + sum;       // a+b == b+a: both lanes agree bitwise
+            if ((ckg & 1) == 0) features[out_index(r0 / 8, c0 / 8 + side, o0 + 16 * (ckg >> 1))] = total * (1.0f / 64);
+        } else {
+            if (abl_conv1) {
+                bf16x8 xh[4], xl[4];
+                int pix; bool valid, inimg;
+                x_frags(wave, xh, xl, pix, valid, inimg);
+                f32x16 acc0, acc1;
+                conv1_both<true>(w1s, xh, xl, acc0, acc1);
+                conv1_store(acc0, 0, pix, valid, inimg);
+                conv1_store(acc1, 1, pix, valid, inimg);
+            }
+            if (abl_conv1) {
+                bf16x8 xh[4], xl[4];
+                int pix; bool valid, inimg;
+                const int cb = wave & 1;
+                x_frags(4 + (wave >> 1), xh, xl, pix, valid, inimg);
+                f32x16 acc;
+                conv1_one<true>(w1s, cb, xh, xl, acc);
+                conv1_store(acc, cb, pix, valid, inimg);
+            }
+#if !defined(SMK_ENC_ABLATE) || !(SMK_ENC_ABLATE & 4)
+            __syncthreads();                                      // a1 complete; xs is free again
+#endif
+            __builtin_amdgcn_s_setprio(S16_PRIO_KLOOP);
+
+            wk.next(skl, sa, src, xr0, xr1);                      // next tile's x halo -> registers (lands under the K loop)
+
+            // ---- conv2: acc[mt][nt][reg] = D(pixel row mt, column 4 kg + reg; channel 16 nt + px of the wave's 32)
+            f32x4v acc[8][2];
+#pragma unroll
+            for (int mt = 0; mt < 8; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) acc[mt][nt][g] = 0.f;
+            // unit k (0..35) = tap * 4 + half * 2 + hm: M tiles 4hm .. 4hm+3 of k-step ks = k >> 1 = tap * 2 + half.  The loop runs over
+            // the 9 taps (runtime) x 4 unrolled units.  Per tap four lane registers om[m] = pixel base ^ swizzle term of row m + ki
+            // are formed once (the base is a multiple of 128 and the term < 128, so base + (c ^ t) = base ^ t ^ c): a fragment pair then
+            // costs ONE xor, and the row offsets ki * 2304 (scalar) and 4hm * 2304 + m * 2304 (ds_read immediate) are free.
+            const int c16[2] = {kg << 4, (4 + kg) << 4};
+            auto tap_consts = [&](int ki, int kj, int (&om)[4]) {
+#pragma unroll
+                for (int m = 0; m < 4; ++m) om[m] = ((px + kj) << 7) ^ (((px + kj + 2 * (m + ki)) & 7) << 4);
+            };
+            auto load_a = [&](int ki, int half, int hm, const int (&om)[4], bf16x8 (&ah)[4], bf16x8 (&al)[4]) {
+                const unsigned char *ph = a1h + ki * (B3_AW * 128), *pl = a1l + ki * (B3_AW * 128);      // wave-uniform part
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+                    const int off = om[m] ^ c16[half];
+                    ah[m] = *reinterpret_cast<const bf16x8 *>(ph + off + (4 * hm + m) * (B3_AW * 128));
+                    al[m] = *reinterpret_cast<const bf16x8 *>(pl + off + (4 * hm + m) * (B3_AW * 128));
+                }
+            };
+            bf16x8 ahA[4], alA[4], ahB[4], alB[4];
+            int om[4];
+            tap_consts(0, 0, om);
+            load_a(0, 0, 0, om, ahA, alA);
+            int ki = 0, kj = 0;
+#pragma unroll 1
+            for (int tap = 0; tap < 9; ++tap) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int half = u >> 1, hm = u & 1, slot = half % RING;
+                    if (hm == 0) {
+                        // refill: k-step ks + 1 into the slot consumed one k-step ago.  All four fragments (both N tiles, hi and lo) are
+                        // requested in the FIRST unit of the k-step, right at its start: two units (768 cycles) before their first use.
+                        // Measured placements of the ring loads within a unit: early 1.06 ms, middle 1.075, late 1.11.
+                        int kn = tap * 2 + half + RING - 1;
+                        kn = kn >= 18 ? kn - 18 : kn;
+                        kn = __builtin_amdgcn_readfirstlane(kn);
+#pragma unroll
+                        for (int nt = 0; nt < 2; ++nt) {
+                            bq[(slot + RING - 1) % RING][nt][0] = load_b(kn, 0, nt);
+                            bq[(slot + RING - 1) % RING][nt][1] = load_b(kn, 1, nt);
+                        }
+                    }
+                    if (u < 3) {                                   // next unit: same tap
+                        if (u & 1) load_a(ki, (u + 1) >> 1, (u + 1) & 1, om, ahA, alA);
+                        else load_a(ki, (u + 1) >> 1, (u + 1) & 1, om, ahB, alB);
+                    } else if (tap < 8) {                          // first unit of the next tap (u = 3 is odd: set A)
+                        kj = kj == 2 ? 0 : kj + 1;
+                        ki = kj == 0 ? ki + 1 : ki;
+                        tap_consts(ki, kj, om);
+                        load_a(ki, 0, 0, om, ahA, alA);
+                    }
+                    // product-major emission: consecutive MFMAs go to different accumulators (dependency distance 8 instead of 1); each
+                    // accumulator still sums lo*hi, hi*lo, hi*hi in that order, so results are bitwise those of the chain-major form
+#pragma unroll
+                    for (int pr = 0; pr < 3; ++pr)
+#pragma unroll
+                        for (int m = 0; m < 4; ++m)
+#pragma unroll
+                            for (int nt = 0; nt < 2; ++nt) {
+                                const bf16x8 bh = __builtin_bit_cast(bf16x8, bq[slot][nt][0]);
+                                const bf16x8 bl = __builtin_bit_cast(bf16x8, bq[slot][nt][1]);
+                                f32x4v &c = acc[4 * hm + m][nt];
+                                const bf16x8 ah = (u & 1) ? ahB[m] : ahA[m], al = (u & 1) ? alB[m] : alA[m];
+#if defined(SMK_ENC_ABLATE) && (SMK_ENC_ABLATE & 8)
+                                asm volatile("" :: "v"(al), "v"(ah), "v"(bh), "v"(bl), "v"(c));      // operands stay live, no MFMA
+#else
+                                if (pr == 0) c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, c, 0, 0, 0);
+                                else if (pr == 1) c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, c, 0, 0, 0);
+                                else c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, c, 0, 0, 0);
+#endif
+                            }
+                    // 24 MFMAs of 16 cycles.  The next unit's 8 fragment reads are spread evenly, one after every third MFMA; the ring loads
+                    // go right behind the first MFMAs.  (One read per second MFMA in the first 16 -- what hipcc also does unpinned -- is
+                    // 4 % slower; see DESIGN.md 3.2 for the placements measured.)
+#pragma unroll
+                    for (int i = 0; i < 24; ++i) {
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                        if (i % 3 == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                        else if (hm == 0 && (i == 1 || i == 2 || i == 4 || i == 5)) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+
+            // ---- epilogue: BN2 + ReLU + block-mean pool.  Lane: channel o0 (nt 0) / o0 + 16 (nt 1), pixels (row mt, cols 4kg .. 4kg+3)
 #if defined(SMK_ENC_ABLATE) && (SMK_ENC_ABLATE & 2)
 #pragma unroll
-        for (int mt = 0; mt < 8; ++mt) asm volatile("" :: "v"(acc[mt][0]), "v"(acc[mt][1]));
-        if (false)
+            for (int mt = 0; mt < 8; ++mt) asm volatile("" :: "v"(acc[mt][0]), "v"(acc[mt][1]));
+            if (false)
 #endif
 #pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            const float s2 = nt ? s2b : s2a, t2 = nt ? t2b : t2a;
-            const int o = o0 + 16 * nt;
-            if (PS == 2) {          // cells: rows (mt, mt+1), column pairs (reg 0,1), (reg 2,3)
+            for (int nt = 0; nt < 2; ++nt) {
+                const float s2 = nt ? s2b : s2a, t2 = nt ? t2b : t2a;
+                const int o = o0 + 16 * nt;
+                if (PS == 2) {          // cells: rows (mt, mt+1), column pairs (reg 0,1), (reg 2,3)
 #pragma unroll
-                for (int mp = 0; mp < 4; ++mp)
+                    for (int mp = 0; mp < 4; ++mp)
 #pragma unroll
-                    for (int cg = 0; cg < 2; ++cg) {
+                        for (int cg = 0; cg < 2; ++cg) {
+                            float sum = 0.f;
+#pragma unroll
+                            for (int mt = 2 * mp; mt < 2 * mp + 2; ++mt)
+#pragma unroll
+                                for (int i = 2 * cg; i < 2 * cg + 2; ++i) sum += bn_relu(acc[mt][nt][i], s2, t2);
+                            features[out_index((r0 + 2 * mp) / 2, (c0 + 4 * kg + 2 * cg) / 2, o)] = sum * 0.25f;
+                        }
+                } else if (PS == 4) {   // cells: rows 4mq .. 4mq+3, columns 4kg .. 4kg+3 (all four registers)
+#pragma unroll
+                    for (int mq = 0; mq < 2; ++mq) {
                         float sum = 0.f;
 #pragma unroll
-                        for (int mt = 2 * mp; mt < 2 * mp + 2; ++mt)
+                        for (int mt = 4 * mq; mt < 4 * mq + 4; ++mt)
 #pragma unroll
-                            for (int i = 2 * cg; i < 2 * cg + 2; ++i) sum += bn_relu(acc[mt][nt][i], s2, t2);
-                        features[out_index((r0 + 2 * mp) / 2, (c0 + 4 * kg + 2 * cg) / 2, o)] = sum * 0.25f;
+                            for (int i = 0; i < 4; ++i) sum += bn_relu(acc[mt][nt][i], s2, t2);
+                        features[out_index((r0 + 4 * mq) / 4, (c0 + 4 * kg) / 4, o)] = sum * (1.0f / 16);
                     }
-            } else if (PS == 4) {   // cells: rows 4mq .. 4mq+3, columns 4kg .. 4kg+3 (all four registers)
-#pragma unroll
-                for (int mq = 0; mq < 2; ++mq) {
+                } else if (PS >= 16) {  // frames beyond 256^2: the PS == 8 sum, then one more step over kg for the whole tile's partial
                     float sum = 0.f;
 #pragma unroll
-                    for (int mt = 4 * mq; mt < 4 * mq + 4; ++mt)
+                    for (int mt = 0; mt < 8; ++mt)
 #pragma unroll
                         for (int i = 0; i < 4; ++i) sum += bn_relu(acc[mt][nt][i], s2, t2);
-                    features[out_index((r0 + 4 * mq) / 4, (c0 + 4 * kg) / 4, o)] = sum * (1.0f / 16);
+                    const float half8 = sum + __shfl_xor(sum, 16);             // a+b == b+a at each step: all four lanes agree bitwise
+                    const float total = half8 + __shfl_xor(half8, 32);
+                    if (kg == 0) features[(size_t)wk.t * 128 + o] = total;
+                } else {                // PS == 8: all 8 rows; columns 0-7 = kg 0,1, columns 8-15 = kg 2,3 (lane ^ 16 holds the other half)
+                    float sum = 0.f;
+#pragma unroll
+                    for (int mt = 0; mt < 8; ++mt)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) sum += bn_relu(acc[mt][nt][i], s2, t2);
+                    const float other = __shfl_xor(sum, 16);
+                    const float total = (kg & 1) == 0 ? sum + other : other + sum;   // a+b == b+a: both lanes agree bitwise
+                    if ((kg & 1) == 0) features[out_index(r0 / 8, c0 / 8 + (kg >> 1), o)] = total * (1.0f / 64);
                 }
-            } else if (PS >= 16) {  // frames beyond 256^2: the PS == 8 sum, then one more step over kg for the whole tile's partial
-                float sum = 0.f;
-#pragma unroll
-                for (int mt = 0; mt < 8; ++mt)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) sum += bn_relu(acc[mt][nt][i], s2, t2);
-                const float half8 = sum + __shfl_xor(sum, 16);             // a+b == b+a at each step: all four lanes agree bitwise
-                const float total = half8 + __shfl_xor(half8, 32);
-                if (kg == 0) features[(size_t)wk.t * 128 + o] = total;
-            } else {                // PS == 8: all 8 rows; columns 0-7 = kg 0,1, columns 8-15 = kg 2,3 (lane ^ 16 holds the other half)
-                float sum = 0.f;
-#pragma unroll
-                for (int mt = 0; mt < 8; ++mt)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) sum += bn_relu(acc[mt][nt][i], s2, t2);
-                const float other = __shfl_xor(sum, 16);
-                const float total = (kg & 1) == 0 ? sum + other : other + sum;   // a+b == b+a: both lanes agree bitwise
-                if ((kg & 1) == 0) features[out_index(r0 / 8, c0 / 8 + (kg >> 1), o)] = total * (1.0f / 64);
             }
         }
 
@@ -1325,20 +1551,21 @@ __global__ __launch_bounds__(256, 2) void k_encoder_b16(const float *__restrict_
 #if !defined(SMK_ENC_ABLATE) || !(SMK_ENC_ABLATE & 4)
         __syncthreads();
 #endif
-        wk.t = wk.tn;
+        wk.advance();
     }
-    wk.end<PS, TOKENS>(sa, src, features);
+    wk.template end<PS, TOKENS>(sa, src, features);
 }
 
 // Diagnostic switches, read once per process: SMK_ENC_STAGGER (s_sleep units of the second workgroup wave, default 1),
 // SMK_ENC_WGS_PER_CU (override the occupancy query), SMK_ENC_SHAPE=32 (split-bf16 on the 32x32x16 kernel instead of 16x16x32),
-// SMK_ENC_SKIP=0 (every tile runs: no tile scan, see below).
+// SMK_ENC_SKIP=0 (every tile runs: no tile scan, see below), SMK_ENC_CELLS=0 (the skip decides per tile only: a live tile runs whole).
 struct EncoderKnobs {
     int stagger, wgs_per_cu, shape;
-    bool skip;
+    bool skip, cells;
     EncoderKnobs() {
         const char *sv = getenv("SMK_ENC_STAGGER"), *ov = getenv("SMK_ENC_WGS_PER_CU"), *sh = getenv("SMK_ENC_SHAPE");
-        const char *sk = getenv("SMK_ENC_SKIP");
+        const char *sk = getenv("SMK_ENC_SKIP"), *ce = getenv("SMK_ENC_CELLS");
+        cells = !(ce && atoi(ce) == 0);
         stagger = sv ? atoi(sv) : 1;
         wgs_per_cu = ov && atoi(ov) > 0 ? atoi(ov) : 0;
         shape = sh && atoi(sh) == 32 ? 32 : 16;
@@ -1358,7 +1585,9 @@ static const EncoderKnobs &enc_knobs() {
 //          (16-byte loads when the frames allow), keeps one flag per 4 x 4 pixel block in LDS (window edges fall on multiples of 4),
 //          ORs 4 x 6 flags per tile.  EMPTY means every 32-bit word of the window inside the image is 0x00000000: bits are compared,
 //          so -0.0, denormals, NaN and Inf all keep a tile on the normal path.  The band's non-empty tiles go out as one 64-bit
-//          mask; that is all it writes.
+//          mask, beside two more words of the same form: the tiles whose left 4 x 4 flags are not all empty, and those whose right
+//          4 x 4 are not (the two overlap by two flag columns; at 256^2 they are the windows of the tile's two pooled cells, and
+//          k_encoder_b16 runs a tile with one live cell at half size: "per pooled cell" above).  That is all it writes.
 //   the main kernel (k_encoder_b16, k_encoder_bf16, k_encoder_i8) reads the masks: tiles_to_run / tile_at turn them into "my k-th
 //          tile" inside every workgroup (no list in memory, no pack launch), skip_fill copies the empty tiles' pooled cells from the
 //          handle's zero-response table (the same kernel form's output for one all-zero frame, in the layout of the call) outside the
@@ -1368,7 +1597,8 @@ static const EncoderKnobs &enc_knobs() {
 // boundary orders scan and main kernel.
 template <bool VEC, int ROWS>
 __global__ __launch_bounds__(256) void k_encoder_tile_scan(const float *__restrict__ frames, int64_t fstride, int H, int W, int lg_tiles_x,
-                                                           int bands_per_frame, unsigned long long *__restrict__ masks) {
+                                                           int bands_per_frame, unsigned long long *__restrict__ masks,
+                                                           unsigned long long *__restrict__ cell_l, unsigned long long *__restrict__ cell_r) {
     constexpr int SCAN_ROWS = ROWS;
     constexpr int SCAN_BR = 2 * ROWS + 2;                     // 4-row flag blocks per band (the band's rows + 4 each way)
     constexpr int SCAN_FW = 1024 / ROWS / 4 + 2;              // flag columns: the 4-pixel blocks of the widest frame with ROWS rows per
@@ -1396,16 +1626,22 @@ __global__ __launch_bounds__(256) void k_encoder_tile_scan(const float *__restri
     }
     __syncthreads();
     if (tid < 64) {                                           // wave 0: one lane per tile of the band
-        unsigned int any = 0;
-        if (tid < band_tiles) {
+        unsigned int any[2] = {0, 0};                         // the tile's two 16-column halves with 4 more each way (encoder_cells.h):
+        if (tid < band_tiles) {                               // at 256^2 its two cells' windows; their union is the tile's at any size
             const int tyl = tid >> lg_tiles_x, tx = tid & (tiles_x - 1);
 #pragma unroll
-            for (int br = 0; br < 4; ++br)
+            for (int side = 0; side < 2; ++side)
 #pragma unroll
-                for (int bc = 0; bc < 6; ++bc) any |= flag[2 * tyl + br][4 * tx + bc];
+                for (int br = 0; br < 4; ++br)
+#pragma unroll
+                    for (int bc = 0; bc < ENC_CELL_FLAG_COLS; ++bc) any[side] |= flag[2 * tyl + br][enc_cell_flag_col(tx, side) + bc];
         }
-        const unsigned long long m = __ballot(any != 0);
-        if (tid == 0) masks[band] = m;
+        const unsigned long long l = __ballot(any[0] != 0), r = __ballot(any[1] != 0);
+        if (tid == 0) {
+            masks[band] = enc_cells_tile(l, r);
+            cell_l[band] = l;
+            cell_r[band] = r;
+        }
     }
 }
 
@@ -1478,17 +1714,21 @@ static hipError_t skip_prepare(EncoderSkip *sk, const float *frames, int64_t fst
     const int bands_per_frame = H / B3_TH / scan_rows, nbands = B * bands_per_frame;
     if (sk->ws_bands < (size_t)nbands) {
         if (capturing) return hipSuccess;
-        int *p = nullptr;                                     // [tiles run + pad: 4][band masks: 2 per band]
-        if ((err = hipMalloc((void **)&p, (4 + 2 * (size_t)nbands) * sizeof(int))) != hipSuccess) return err;
+        int *p = nullptr;                                     // [tiles run + pad: 4][band masks, left-cell words, right-cell words: 2 per band each]
+        if ((err = hipMalloc((void **)&p, (4 + 6 * (size_t)nbands) * sizeof(int))) != hipSuccess) return err;
         if (sk->ws) sk->retired.push_back(sk->ws);
         sk->ws = p;
         sk->ws_bands = nbands;
     }
     int *count = sk->ws;
+    // three arrays of the call's band count each: scan and main kernel of one call (or of one captured graph) get the same pointers
     unsigned long long *masks = reinterpret_cast<unsigned long long *>(sk->ws + 4);
+    unsigned long long *cell_l = masks + nbands, *cell_r = cell_l + nbands;
     const bool vec = (reinterpret_cast<uintptr_t>(frames) & 15) == 0 && (fstride & 3) == 0;
     dim3 grid(nbands), block(256);
-    auto scan = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, st, frames, fstride, H, W, lg_tx, bands_per_frame, masks); };
+    auto scan = [&](auto kern) {
+        hipLaunchKernelGGL(kern, grid, block, 0, st, frames, fstride, H, W, lg_tx, bands_per_frame, masks, cell_l, cell_r);
+    };
     switch (scan_rows) {
         case 4: vec ? scan(k_encoder_tile_scan<true, 4>) : scan(k_encoder_tile_scan<false, 4>); break;
         case 2: vec ? scan(k_encoder_tile_scan<true, 2>) : scan(k_encoder_tile_scan<false, 2>); break;
@@ -1496,6 +1736,9 @@ static hipError_t skip_prepare(EncoderSkip *sk, const float *frames, int64_t fst
     }
     if ((err = hipGetLastError()) != hipSuccess) return err;
     plan.masks = masks;
+    // SMK_ENC_CELLS=0: both cell words are the tile mask, i.e. every live tile has two live cells and runs whole
+    plan.cell_l = enc_knobs().cells ? cell_l : masks;
+    plan.cell_r = enc_knobs().cells ? cell_r : masks;
     plan.count = count;
     plan.nbands = nbands;
     plan.lg_band_tiles = lg_tx + 2 < 6 ? lg_tx + 2 : 6;      // scan_rows x tiles_x tiles, at most one mask word
@@ -1561,8 +1804,8 @@ __global__ __launch_bounds__(256, 2) void k_encoder_i8(const float *__restrict__
     const int lane_off = (r >> 4) * 4 * I8_A1_ROW + (r & 15) * I8_A1_PITCH + 16 * hi;
 
     const TileSrc src{frames, fstride, H, W, lg_tiles_x, lg_tiles_per_frame};
-    __shared__ SkipLds skl;
-    TileWalk wk;
+    __shared__ SkipLds<false> skl;
+    TileWalk<> wk;
     wk.begin<PS, TOKENS>(skl, sa, src, ntiles, 0, features, xs, [](float v) { return v; });   // this kernel does not stagger
 
     // [stamp:begin]
@@ -1733,7 +1976,7 @@ __global__ __launch_bounds__(256, 2) void k_encoder_i8(const float *__restrict__
         __syncthreads();
         // [stamp:T7]
         // [stamp:accumulate]
-        wk.t = wk.tn;
+        wk.advance();
     }
     // [stamp:end]
     wk.end<PS, TOKENS>(sa, src, features);
