@@ -396,6 +396,36 @@ int smk_volume_render_camera(const float *vols, int64_t vol_stride, int32_t n, i
                              const double *azimuths, const double *elevations, int32_t n_views, float *image, int64_t image_stride,
                              float *transmittance, int64_t trans_stride, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* The gradient of smk_volume_render_camera, with the promises of smk_volume_render_orbit_backward: given the upstream gradients
+ * G = grad_image and Gt = grad_trans of its two outputs (plane v * n_views + k is view k of volume v, planes `grad_image_stride` /
+ * `grad_trans_stride` floats apart, >= H*W; either may be NULL, which means zero; both NULL is SMK_ERR_INVALID), writes d(loss)/d(rho)
+ * of the same n volumes, summed over each volume's n_views views, into grad_vols (dense [D][H][W] each, `grad_vol_stride` floats
+ * apart).  SPEC_3D.md section 10, "Free camera -- Gradient": Q and R are smk_volume_render_orbit_backward's over the samples rho_s, A of
+ * smk_volume_render_camera, and
+ *   drho[z,y,x] = sum over the views of ( (B^T Q)[z,y,x] + the sum of (B^T R)[z,y'',x] over the voxel rows y'' that y shadows )
+ * (+y: y'' > y, -y: y'' < y), where (B^T F)[z,y,x] = sum over (s, y', x') of w(s,y',x'; z,y,x) F[s,y',x'] and w is the total weight with
+ * which voxel (z, y, x) entered sample (s, y', x') in the forward (its eight taps; a tap outside the volume drops out).  Positions and
+ * weights are the forward's, formed by the same fp32 expressions.  A voxel with rho = 0 has a gradient; a voxel no ray's taps touch
+ * gets 0.  fp32, every sum in one fixed order, the views in ascending order, no atomics: bit-identical from call to call, independent
+ * of the other volumes of the batch and of how the call is cut into launches, and every element of grad_vols is written (no need to
+ * zero it).  Limits: smk_volume_render_camera's and 1 <= H <= 4096 (else SMK_ERR_UNSUPPORTED); the checks of desc, the angle rule and the
+ * status codes are smk_volume_render_camera's (SMK_LIGHT_POS_Z: SMK_ERR_UNSUPPORTED); on any error grad_vols is untouched.  workspace:
+ * device memory of at least smk_volume_render_camera_backward_workspace(n, D, H, W, light) bytes, the same for any n_views (-1 for an
+ * unsupported shape or light).  With row = W floats under SMK_LIGHT_NONE (one value per ray) and (2 S + 1) * W floats under
+ * SMK_LIGHT_POS_Y / SMK_LIGHT_NEG_Y (two per sample and one per ray), fit = floor(2^26 / row) (a cap of 256 MiB), band = min(32, H, fit - 3),
+ * slots = min(band + 3, H) and vols = min(n, 16, floor(fit / slots)), it is vols * slots * row floats of scratch, after two arrays of
+ * n*D*H*W floats (the prefix along y; the sum of B^T R) under SMK_LIGHT_POS_Y / SMK_LIGHT_NEG_Y.  4-byte aligned, passed with its size.
+ * Caller-owned memory, the caller's stream, nothing allocated on the device, no synchronisation.  Launches: two per view and unit (a
+ * unit: up to `vols` volumes x one band of `band` image rows; none for a band that owns no voxel at that view), plus two under
+ * SMK_LIGHT_POS_Y / SMK_LIGHT_NEG_Y. */
+int64_t smk_volume_render_camera_backward_workspace(int32_t n, int32_t D, int32_t H, int32_t W, int32_t light);
+int smk_volume_render_camera_backward(const float *vols, int64_t vol_stride, int32_t n, int32_t D, int32_t H, int32_t W,
+                                      const smk_render_desc *desc, const double *azimuths, const double *elevations, int32_t n_views,
+                                      const float *grad_image, int64_t grad_image_stride,     /* planes v*n_views+k; NULL: zero */
+                                      const float *grad_trans, int64_t grad_trans_stride,     /* NULL: zero; both NULL: SMK_ERR_INVALID */
+                                      float *grad_vols, int64_t grad_vol_stride,              /* dense [D][H][W] each */
+                                      void *workspace, int64_t workspace_bytes, void *stream);
+
 /* RobustnessEvaluator.compute_ssim's SSIM map and F.mse_loss's squared error (robustness_metrics.py:76-103) for n fp32 planes [H][W]
  * (dense rows; plane strides pred_stride / target_stride floats), summed per plane in fp64 in a fixed order (bit-reproducible):
  * ssim_sum [n], sqerr_sum [n].  avg_pool2d(window, stride 1, padding window/2, count_include_pad) with zeros outside the plane;

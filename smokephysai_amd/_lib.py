@@ -123,6 +123,9 @@ _SIGNATURES = {
     "smk_volume_render_camera": [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SmkRenderDesc),
                                  C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                  C.c_void_p, C.c_int64, C.c_void_p],
+    "smk_volume_render_camera_backward": [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SmkRenderDesc),
+                                          C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                          C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p],
     "smk_chaos_features": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                            C.c_void_p, C.c_void_p],
     "smk_image_quality": [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
@@ -210,7 +213,7 @@ _SIGNATURES = {
 EXPORTS = ["smk_abi_version", "smk_last_error", "smk_linear_wgrad_workspace", "smk_bn_train_workspace", "smk_layernorm_bwd_workspace", "smk_conv2_train_workspace", "smk_conv2_train_wgrad_workspace", "smk_conv1_train_wgrad_workspace", "smk_attention_workspace_bytes", "smk_linear_ln_max_rows", "smk_image_quality_workspace", "smk_image_quality_backward_workspace", "smk_convt4s2_train_wgrad_workspace",
            "smk_volume_stats_workspace", "smk_grad_norm_workspace", "smk_train_loss_workspace",
            "smk_conv3_sigmoid_train_workspace", "smk_flow_levels", "smk_flow_farneback_workspace", "smk_warp_workspace",
-           "smk_flow_lk_workspace", "smk_volume_render_workspace", "smk_volume_render_backward_workspace", "smk_volume_render_orbit_workspace", "smk_volume_render_orbit_backward_workspace", "smk_volume_render_camera_workspace", "smk_conv3d_train_workspace", "smk_conv3d_cl_wgrad_workspace",
+           "smk_flow_lk_workspace", "smk_volume_render_workspace", "smk_volume_render_backward_workspace", "smk_volume_render_orbit_workspace", "smk_volume_render_orbit_backward_workspace", "smk_volume_render_camera_workspace", "smk_volume_render_camera_backward_workspace", "smk_conv3d_train_workspace", "smk_conv3d_cl_wgrad_workspace",
            "smk_bn_cl_workspace"] + list(_SIGNATURES)
 
 _lib = None
@@ -275,6 +278,8 @@ def load():
         L.smk_volume_render_orbit_backward_workspace.restype = C.c_int64  # a byte count; -1 = unsupported shape or light
         L.smk_volume_render_camera_workspace.argtypes = [C.c_int32] * 5
         L.smk_volume_render_camera_workspace.restype = C.c_int64  # a byte count; -1 = unsupported shape or light
+        L.smk_volume_render_camera_backward_workspace.argtypes = [C.c_int32] * 5
+        L.smk_volume_render_camera_backward_workspace.restype = C.c_int64  # a byte count; -1 = unsupported shape or light
         L.smk_convt4s2_train_wgrad_workspace.argtypes = [C.c_int32] * 5
         L.smk_convt4s2_train_wgrad_workspace.restype = C.c_int64
         L.smk_conv3_sigmoid_train_workspace.argtypes = [C.c_int32] * 3

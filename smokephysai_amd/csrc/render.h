@@ -65,6 +65,11 @@ int render_launch_status(const char *name, hipError_t e);
 int64_t render_prefix_workspace(int64_t n, int D, int H, int W, int light);
 // workspace[v][z][y][x] = the sum of rho[z][y'][x] over the rows the light crosses before y (up: the light travels along +y)
 hipError_t launch_render_prefix(const float *vols, int64_t stride, int64_t n, int D, int H, int W, bool up, float *workspace, hipStream_t st);
+// The transpose, for the gradients of the moving cameras (render_orbit_grad.hip, render_camera_grad.hip): out[v][z][y][x] += the sum of
+// U[v][z][y'][x] over the rows y' that y shadows, nearest row first.  U: n dense volumes; out: volumes ostride floats apart.
+// render_grad_light_fits: the grid fits a launch (what a launcher asks before its first launch, so that an error leaves `out` untouched).
+bool render_grad_light_fits(int64_t n, int D, int W);
+hipError_t launch_render_grad_light(const float *U, float *out, int64_t ostride, int64_t n, int D, int H, int W, bool up, hipStream_t st);
 
 // bytes of the segment-total workspace: 0 unless the light travels along y and the rows span more than one segment
 int64_t render_workspace(int64_t n, int D, int H, int W, int light);

@@ -19,7 +19,7 @@
 // second half of this file: the same two mappings, the same segment kernels, every element of the result written exactly once.
 //
 // What the moving cameras share with the front view is here too (render.h): k_render_prefix, the whole +-y prefix on the voxel grid, which
-// render_orbit.hip and render_camera.hip interpolate, and, at the end, the host-side checks of all four entry points.
+// render_orbit.hip and render_camera.hip interpolate, its transpose k_render_grad_light for their gradients, and, at the end, the host-side checks of all four entry points.
 #include "render.h"
 
 namespace smk {
@@ -198,6 +198,37 @@ __global__ __launch_bounds__(RV_NT) void k_render_prefix(const float *__restrict
     }
 }
 
+// ---- light +-y, the gradients of the moving cameras: out[v][z][y][x] += the sum of U[v][z][y'][x] over the rows y' that y shadows (up:
+// y' > y), nearest row first.  The transpose of k_render_prefix: a march along y, lanes along x.
+__global__ __launch_bounds__(RV_NT) void k_render_grad_light(const float *__restrict__ U, float *out, int64_t ostride, int D, int H, int W,
+                                                             int bpp, int up) {
+    const int v = blockIdx.x / bpp, q = (blockIdx.x % bpp) * RV_NT + threadIdx.x;
+    if (q >= D * W) return;
+    const int z = q / W, x = q - z * W;
+    const size_t base = (size_t)z * H * W + x;                 // + y * W < D * H * W
+    const float *u = U + (size_t)v * D * H * W + base;
+    float *o = out + (size_t)v * ostride + base;
+    float run = 0.f;
+    constexpr int UN = 8;                                      // rows loaded ahead of their sums
+    for (int i0 = 0; i0 < H; i0 += UN) {
+        float r[UN], d[UN];
+#pragma unroll
+        for (int j = 0; j < UN; ++j) {
+            const int i = i0 + j, y = up ? H - 1 - i : i;
+            r[j] = i < H ? u[(size_t)y * W] : 0.f;
+            d[j] = i < H ? o[(size_t)y * W] : 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < UN; ++j) {
+            const int i = i0 + j, y = up ? H - 1 - i : i;
+            if (i < H) {
+                o[(size_t)y * W] = d[j] + run;
+                run += r[j];
+            }
+        }
+    }
+}
+
 }  // namespace
 
 int64_t render_prefix_workspace(int64_t n, int D, int H, int W, int light) {
@@ -209,6 +240,15 @@ hipError_t launch_render_prefix(const float *vols, int64_t stride, int64_t n, in
     const int64_t bpp = ((int64_t)D * W + RV_NT - 1) / RV_NT, grid = n * bpp;
     if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_render_prefix, dim3((unsigned)grid), dim3(RV_NT), 0, st, vols, stride, D, H, W, (int)bpp, up ? 1 : 0, workspace);
+    return hipGetLastError();
+}
+
+bool render_grad_light_fits(int64_t n, int D, int W) { return n * (((int64_t)D * W + RV_NT - 1) / RV_NT) <= 0x7fffffffLL; }
+
+hipError_t launch_render_grad_light(const float *U, float *out, int64_t ostride, int64_t n, int D, int H, int W, bool up, hipStream_t st) {
+    const int64_t bpp = ((int64_t)D * W + RV_NT - 1) / RV_NT, grid = n * bpp;
+    if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_render_grad_light, dim3((unsigned)grid), dim3(RV_NT), 0, st, U, out, ostride, D, H, W, (int)bpp, up ? 1 : 0);
     return hipGetLastError();
 }
 

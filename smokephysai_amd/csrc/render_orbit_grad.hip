@@ -18,7 +18,8 @@
 //                         ray coordinates in one fixed order, forms each one's position as the forward does and adds weight * Q where one
 //                         of its taps is the voxel.  View 0 of a volume writes drho (and U = B^T R), later views add to it in view order:
 //                         every element is written, a voxel no ray reaches with 0.
-//   k_orbit_grad_light  : +-y only.  drho[z,y,x] += the exclusive sum of U over the rows y shadows: a march along y, lanes along x.
+//   k_render_grad_light : +-y only (render.hip, shared with the free camera's gradient).  drho[z,y,x] += the exclusive sum of U over the
+//                         rows y shadows: a march along y, lanes along x.
 // Under a +-y light k_render_prefix (render.hip) runs first, as in the forward.  Launches per call: 2 * n_views per unit, plus 2 under a
 // +-y light; a unit is up to 16 volumes, fewer (down to a range of rows of one) where their rows exceed the scratch.
 #include "render_orbit_grad.h"
@@ -31,7 +32,7 @@ namespace smk {
 namespace {
 
 constexpr int OG_NT = ORBIT_STRIP * ORBIT_ROWS;       // 128 threads
-constexpr int OG_FLAT = 256;                          // threads per workgroup of the gather and the light pass
+constexpr int OG_FLAT = 256;                          // threads per workgroup of the gather
 constexpr int STAGE_U = 4;                            // box cells a lane loads ahead of their LDS stores
 
 struct OrbitGradViews {
@@ -195,36 +196,6 @@ __global__ __launch_bounds__(OG_FLAT) void k_orbit_grad_gather(int D, int H, int
     }
 }
 
-// ---- light +-y: out[v][z][y][x] += the sum of U[v][z][y'][x] over the rows y' that y shadows (up: y' > y), nearest row first
-__global__ __launch_bounds__(OG_FLAT) void k_orbit_grad_light(const float *__restrict__ U, float *out, int64_t ostride, int D, int H, int W,
-                                                              int bpp, int up) {
-    const int v = blockIdx.x / bpp, q = (blockIdx.x % bpp) * OG_FLAT + threadIdx.x;
-    if (q >= D * W) return;
-    const int z = q / W, x = q - z * W;
-    const size_t base = (size_t)z * H * W + x;                 // + y * W < D * H * W
-    const float *u = U + (size_t)v * D * H * W + base;
-    float *o = out + (size_t)v * ostride + base;
-    float run = 0.f;
-    constexpr int UN = 8;                                      // rows loaded ahead of their sums
-    for (int i0 = 0; i0 < H; i0 += UN) {
-        float r[UN], d[UN];
-#pragma unroll
-        for (int j = 0; j < UN; ++j) {
-            const int i = i0 + j, y = up ? H - 1 - i : i;
-            r[j] = i < H ? u[(size_t)y * W] : 0.f;
-            d[j] = i < H ? o[(size_t)y * W] : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < UN; ++j) {
-            const int i = i0 + j, y = up ? H - 1 - i : i;
-            if (i < H) {
-                o[(size_t)y * W] = d[j] + run;
-                run += r[j];
-            }
-        }
-    }
-}
-
 }  // namespace
 
 int64_t render_orbit_backward_workspace(int64_t n, int D, int H, int W, int light) {
@@ -243,8 +214,7 @@ hipError_t launch_volume_render_orbit_backward(const float *vols, int64_t stride
     float *wsA = lit ? workspace : nullptr, *wsU = lit ? workspace + n * cells : nullptr;
     float *scratch = lit ? workspace + 2 * n * cells : workspace;
     const int nstrips = (W + ORBIT_STRIP - 1) / ORBIT_STRIP;
-    const int64_t bpp = ((int64_t)D * W + OG_FLAT - 1) / OG_FLAT;
-    if (n * bpp > 0x7fffffffLL) return hipErrorInvalidValue;
+    if (lit && !render_grad_light_fits(n, D, W)) return hipErrorInvalidValue;
     hipError_t e;
     if (lit && (e = launch_render_prefix(vols, stride, n, D, H, W, light == SMK_LIGHT_POS_Y, wsA, st)) != hipSuccess) return e;
     int64_t v0 = 0;
@@ -278,12 +248,7 @@ hipError_t launch_volume_render_orbit_backward(const float *vols, int64_t stride
         }
         more = orbit_grad_next(u, n, H, &v0, &y0);
     }
-    if (lit) {
-        hipLaunchKernelGGL(k_orbit_grad_light, dim3((unsigned)(n * bpp)), dim3(OG_FLAT), 0, st, wsU, out, ostride, D, H, W, (int)bpp,
-                           light == SMK_LIGHT_POS_Y ? 1 : 0);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return lit ? launch_render_grad_light(wsU, out, ostride, n, D, H, W, light == SMK_LIGHT_POS_Y, st) : hipSuccess;
 }
 
 }  // namespace smk

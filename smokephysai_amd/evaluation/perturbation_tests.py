@@ -18,7 +18,8 @@ reconstruction with the front view of the clean volume (SPEC_3D.md section 10) a
 gradient reaches the volume through Encoder3D's 'frozen' route (smk_conv3d_s7_dgrad).  With render=RenderSettings(...) the model is an
 IMAGE model that is shown the render of the perturbed volume: the perturbation lives on the smoke, the gradient reaches it through the
 render's backward (smk_volume_render_backward), and with azimuth=... as well from one or several orbit views of it
-(physics.render_orbit(..., differentiable=True), smk_volume_render_orbit_backward).  viewpoint_test shows an IMAGE model the same volumes from a ring of camera azimuths
+(physics.render_orbit(..., differentiable=True), smk_volume_render_orbit_backward), or with elevation=... from pitched views
+(physics.render_camera(..., differentiable=True), smk_volume_render_camera_backward).  viewpoint_test shows an IMAGE model the same volumes from a ring of camera azimuths
 (physics.render_orbit, SPEC_3D.md section 10 "Orbit views") and reports how far its physics features move with the viewpoint; with
 elevation=... the ring is seen from above or below (physics.render_camera, "Free camera").
 physics_perturbation_test is 2-D only.
@@ -133,7 +134,7 @@ class PerturbationTester:
         return result
 
     def adversarial_test(self, model: nn.Module, test_data: torch.Tensor, epsilon: float = 0.1, num_steps: int = 10, *,
-                         target: Optional[torch.Tensor] = None, render=None, azimuth=None) -> Dict:
+                         target: Optional[torch.Tensor] = None, render=None, azimuth=None, elevation=None) -> Dict:
         """PGD on the reconstruction error (perturbation_tests.py:54-98): {'adversarial_feature_stability',
         'adversarial_perturbation_norm'}.  The gradient is taken with respect to the perturbation only (module docstring): with every
         parameter frozen, a SmokePhysNet with input_grad == "hip" serves 128^2 / 256^2 frames on its libsmokehip route (forward and
@@ -150,10 +151,16 @@ class PerturbationTester:
         camera stands, render_orbit(clamp(test_data + delta, 0, 1)[:, 0], azimuth, render, differentiable=True) as [B*V, 1, H, W] frames
         (SPEC_3D.md section 10, "Orbit views -- Gradient"; smk_volume_render_orbit_backward): the loss is the mean over all B*V frames,
         the default comparison image the clean volume's render from the same views, and the closing forwards run over the B*V frames.
-        None: the front view above."""
+        None: the front view above.
+        elevation (needs render=): a number of degrees in [-90, 90] or a sequence of them.  The views are then the free camera's,
+        render_camera(..., azimuth, elevation, render, differentiable=True) (SPEC_3D.md section 10, "Free camera -- Gradient";
+        smk_volume_render_camera_backward), azimuth (0 when not given) and elevation paired view by view as render_camera pairs them;
+        everything else as with azimuth=.  None: the code path without it."""
         model.eval()
         if azimuth is not None and render is None:
             raise ValueError("adversarial_test: azimuth= needs render=RenderSettings(...): it is the rendered volume that is seen from there")
+        if elevation is not None and render is None:
+            raise ValueError("adversarial_test: elevation= needs render=RenderSettings(...): it is the rendered volume that is seen from there")
         shown = lambda x: x                  # noqa: E731  what the model sees of the (perturbed) data
         if render is not None:
             from ..physics.render import RenderSettings, render_volumes
@@ -163,9 +170,13 @@ class PerturbationTester:
                 raise ValueError("adversarial_test: with render=, test_data must be volumes [B, 1, D, H, W]")
             test_data = test_data.detach().float().contiguous()
             shown = lambda v: render_volumes(v[:, 0], render)[:, None]          # noqa: E731
-            if azimuth is not None:
+            hw = tuple(test_data.shape[-2:])
+            if elevation is not None:
+                from ..physics.render import render_camera
+                az = 0.0 if azimuth is None else azimuth
+                shown = lambda v: render_camera(v[:, 0], az, elevation, render, differentiable=True).reshape(-1, 1, *hw)      # noqa: E731
+            elif azimuth is not None:
                 from ..physics.render import render_orbit
-                hw = tuple(test_data.shape[-2:])
                 shown = lambda v: render_orbit(v[:, 0], azimuth, render, differentiable=True).reshape(-1, 1, *hw)      # noqa: E731
             if target is None:
                 with torch.no_grad():

@@ -3,11 +3,11 @@ from .navier_stokes3d import NavierStokesSimulator3D
 from .smoke_simulator import SmokeSimulator
 from .smoke_simulator3d import SmokeSimulator3D
 from .fractal_generator import FractalGenerator
-from .render import (RenderSettings, camera_samples, camera_supported, camera_workspace, orbit_backward_workspace, orbit_samples, orbit_supported,
+from .render import (RenderSettings, camera_backward_supported, camera_backward_workspace, camera_samples, camera_supported, camera_workspace, orbit_backward_workspace, orbit_samples, orbit_supported,
                      orbit_workspace,
                      render_backward_workspace, render_camera, render_orbit, render_supported, render_volumes, render_workspace)
 
 __all__ = ["NavierStokesSimulator", "NavierStokesSimulator3D", "SmokeSimulator", "SmokeSimulator3D", "FractalGenerator", "RenderSettings",
-           "camera_samples", "camera_supported", "camera_workspace", "orbit_backward_workspace", "orbit_samples", "orbit_supported",
+           "camera_backward_supported", "camera_backward_workspace", "camera_samples", "camera_supported", "camera_workspace", "orbit_backward_workspace", "orbit_samples", "orbit_supported",
            "orbit_workspace",
            "render_backward_workspace", "render_camera", "render_orbit", "render_supported", "render_volumes", "render_workspace"]

@@ -11,7 +11,9 @@ the volumes: smk_volume_render_orbit_backward (csrc/render_orbit_grad.hip), the 
 transpose of the interpolation, summed over the views (section 10, "Orbit views -- Gradient"; oracle: tests/render_orbit_grad_oracle.py).
 
 render_camera adds an elevation to that camera (section 10, "Free camera"; csrc/render_camera.hip, smk_volume_render_camera; oracle:
-tests/render_camera_oracle.py): azimuth and elevation paired view by view, trilinear samples, forward only.
+tests/render_camera_oracle.py): azimuth and elevation paired view by view, trilinear samples.  With differentiable=True it carries a
+backward too: smk_volume_render_camera_backward (csrc/render_camera_grad.hip; section 10, "Free camera -- Gradient"; oracle:
+tests/render_camera_grad_oracle.py).
 """
 import ctypes as C
 import math
@@ -64,6 +66,7 @@ ORBIT_MAX_WIDTH = 1024     # csrc/orbit_plan.h ORBIT_MAX_WIDTH
 ORBIT_LIGHTS = ("none", "+y", "-y")
 CAMERA_MAX_WIDTH = 1024    # csrc/camera_plan.h CAMERA_MAX_WIDTH
 CAMERA_MAX_HEIGHT = 65536  # csrc/camera_plan.h CAMERA_MAX_HEIGHT: the image row enters the fp32 positions
+CAMERA_GRAD_MAX_HEIGHT = 4096  # csrc/camera_grad_plan.h CAMERA_GRAD_MAX_HEIGHT: the margin of the gather's candidate window
 CAMERA_LIGHTS = ORBIT_LIGHTS
 
 
@@ -97,6 +100,8 @@ _ORBIT_BACKWARD = _ORBIT._replace(stem="orbit_backward", entry="smk_volume_rende
                                  query="smk_volume_render_orbit_backward_workspace")
 _CAMERA = _Kind("render_camera", "camera", "smk_volume_render_camera", "smk_volume_render_camera_workspace", CAMERA_MAX_HEIGHT,
                 CAMERA_MAX_WIDTH, CAMERA_LIGHTS, "float32 [D,H,W] or [n,D,H,W]", (3, 4), "a moving camera", "free-camera")
+_CAMERA_BACKWARD = _CAMERA._replace(stem="camera_backward", entry="smk_volume_render_camera_backward",
+                                   query="smk_volume_render_camera_backward_workspace", max_h=CAMERA_GRAD_MAX_HEIGHT)
 
 
 def _within(kind: _Kind, D: int, H: int, W: int) -> bool:
@@ -143,6 +148,11 @@ def camera_supported(D: int, H: int, W: int) -> bool:
     return _supported(_CAMERA, D, H, W)
 
 
+def camera_backward_supported(D: int, H: int, W: int) -> bool:
+    """Whether smk_volume_render_camera_backward takes volumes of this shape: camera_supported's limits and H <= 4096."""
+    return _supported(_CAMERA_BACKWARD, D, H, W)
+
+
 def render_workspace(n: int, shape, light: str, device) -> Optional[torch.Tensor]:
     """The scratch buffer smk_volume_render wants for n volumes of `shape` = (D, H, W) under `light` (None when it wants none);
     reusable across calls on one stream."""
@@ -172,6 +182,13 @@ def camera_workspace(n: int, shape, light: str, device) -> Optional[torch.Tensor
     """The scratch buffer smk_volume_render_camera wants for n volumes of `shape` = (D, H, W) under `light` (None when it wants none:
     "none"; the prefix along y, n*D*H*W floats, under "+y" / "-y"); the same for any number of views; reusable on one stream."""
     return _workspace(_CAMERA, n, shape, light, device)
+
+
+def camera_backward_workspace(n: int, shape, light: str, device) -> Optional[torch.Tensor]:
+    """The scratch buffer smk_volume_render_camera_backward wants for n volumes of `shape` = (D, H, W) under `light`: one value per ray of
+    a band of image rows of at most 16 volumes under "none"; the prefix along y and the shadow sums (n*D*H*W floats each) and at most
+    256 MiB of banded per-sample scratch under "+y" / "-y"; the same for any number of views; reusable on one stream."""
+    return _workspace(_CAMERA_BACKWARD, n, shape, light, device)
 
 
 def _ray_samples(q: int, D: int) -> int:
@@ -305,16 +322,16 @@ def _forward(kind: _Kind, vols, settings, angles, *, transmittance, out, workspa
     tables, views = ((), False) if angles is None else angles(n)
     if angles is not None:
         if not differentiable and torch.is_grad_enabled() and vols.requires_grad:
-            if kind is _ORBIT:
-                raise RuntimeError("render_orbit: the orbit render has no backward unless it is asked for, and the volumes require a "
-                                   "gradient; pass differentiable=True, call under torch.no_grad() or detach them")
-            raise RuntimeError(f"{kind.fn}: the {kind.render} render has no backward yet, and the volumes require a gradient; call under "
-                               "torch.no_grad() or detach them (render_volumes, the front view, is differentiable)")
+            raise RuntimeError(f"{kind.fn}: the {kind.render} render has no backward unless it is asked for, and the volumes require a "
+                               "gradient; pass differentiable=True, call under torch.no_grad() or detach them")
         if tables_out is not None:
             tables_out.extend(tables)
         dev = _lib.require_cuda(vols.device, kind.fn)
     if not _within(kind, D, H, W):
         raise ValueError(f"{kind.fn}: shape {tuple(vols.shape)} is not supported ({kind.limits()} per volume)")
+    if differentiable and kind is _CAMERA and not _within(_CAMERA_BACKWARD, D, H, W):
+        raise ValueError(f"render_camera: shape {tuple(vols.shape)} has no backward ({_CAMERA_BACKWARD.limits()} per volume); call "
+                         "without differentiable=True")
     if vols.is_contiguous():                       # the usual case: nothing to check, and what _runs makes of it
         runs = [(0, n, D * H * W)]
     else:
@@ -412,25 +429,26 @@ def _orbit_angles(azimuth):
     return lambda n: _tables((_angle(azimuth, n, "azimuth", "render_orbit"),), n, "render_orbit")
 
 
-def _orbit_backward(vols: torch.Tensor, settings: RenderSettings, table: torch.Tensor, grad_image, grad_trans) -> torch.Tensor:
-    """smk_volume_render_orbit_backward over the runs of `vols` (checked by render_orbit): the gradient in vols' shape, contiguous.
-    table: the [n][V] azimuths of the forward; grad_image / grad_trans: the image's shape, or None (= zero); not both None."""
+def _moving_backward(kind: _Kind, vols: torch.Tensor, settings: RenderSettings, tables, grad_image, grad_trans) -> torch.Tensor:
+    """The backward entry point of a moving camera (_ORBIT_BACKWARD, _CAMERA_BACKWARD) over the runs of `vols` (checked by the forward):
+    the gradient in vols' shape, contiguous.  tables: the [n][V] angle tables of the forward, as the entry point takes them;
+    grad_image / grad_trans: the image's shape, or None (= zero); not both None."""
     shape = D, H, W = tuple(int(s) for s in vols.shape[-3:])
     lead = tuple(vols.shape[:-3])
-    cells, HW, V = D * H * W, H * W, int(table.shape[1])
+    cells, HW, V = D * H * W, H * W, int(tables[0].shape[1])
     gi = None if grad_image is None else grad_image.to(torch.float32).contiguous()
     gt = None if grad_trans is None else grad_trans.to(torch.float32).contiguous()
     grad = torch.empty(lead + shape, dtype=torch.float32, device=vols.device)      # every element is written
     runs = _runs(lead, vols.stride()[:-3], cells)
-    ws, nbytes = _call_workspace(_ORBIT_BACKWARD, max(r[1] for r in runs), shape, settings.light, None, vols.device)
+    ws, nbytes = _call_workspace(kind, max(r[1] for r in runs), shape, settings.light, None, vols.device)
     ibase, tbase, gbase = gi is not None and gi.data_ptr(), gt is not None and gt.data_ptr(), grad.data_ptr()
-    flat = table.reshape(-1).tolist()
+    flat = [t.reshape(-1).tolist() for t in tables]
 
-    def middle(done, count):                       # the run's azimuths and V, the upstream gradients (None: zero) and the result
+    def middle(done, count):                       # the run's angles and V, the upstream gradients (None: zero) and the result
         at = 4 * done * V * HW
-        return ((C.c_double * (count * V))(*flat[done * V:(done + count) * V]), V, ibase and ibase + at, HW, tbase and tbase + at, HW,
-                gbase + 4 * done * cells, cells)
-    _each_run(_ORBIT_BACKWARD, vols, runs, shape, settings, middle, ws, nbytes)
+        return (*((C.c_double * (count * V))(*f[done * V:(done + count) * V]) for f in flat), V, ibase and ibase + at, HW,
+                tbase and tbase + at, HW, gbase + 4 * done * cells, cells)
+    _each_run(kind, vols, runs, shape, settings, middle, ws, nbytes)
     return grad
 
 
@@ -455,7 +473,7 @@ class _RenderOrbit(torch.autograd.Function):
         (vols,) = ctx.saved_tensors
         if grad_image is None and grad_trans is None:
             return None, None, None, None, None
-        return _orbit_backward(vols, ctx.settings, ctx.table, grad_image, grad_trans), None, None, None, None
+        return _moving_backward(_ORBIT_BACKWARD, vols, ctx.settings, (ctx.table,), grad_image, grad_trans), None, None, None, None
 
 
 def render_orbit(vols: torch.Tensor, azimuth, settings: Optional[RenderSettings] = None, *, transmittance: bool = False,
@@ -487,8 +505,39 @@ def render_orbit(vols: torch.Tensor, azimuth, settings: Optional[RenderSettings]
     return _forward(_ORBIT, vols, settings, _orbit_angles(azimuth), transmittance=transmittance, out=out, workspace=workspace)
 
 
+def _camera_angle_tables(azimuth, elevation):
+    def angles(n):
+        az, el, views = _camera_angles(azimuth, elevation, n)
+        return (az, el), views
+    return angles
+
+
+class _RenderCamera(torch.autograd.Function):
+    """render_camera with a backward: the forward is the plain call (the same values bit for bit), the backward is
+    smk_volume_render_camera_backward on the saved volumes and the forward's angle tables.  Differentiable once."""
+
+    @staticmethod
+    def forward(ctx, vols, azimuth, elevation, settings, transmittance, workspace):
+        ctx.settings = settings
+        ctx.set_materialize_grads(False)           # an unused output's gradient arrives as None: the NULL of the entry point
+        ctx.save_for_backward(vols)
+        tables = []
+        res = _forward(_CAMERA, vols, settings, _camera_angle_tables(azimuth, elevation), transmittance=transmittance, out=None,
+                       workspace=workspace, differentiable=True, tables_out=tables)
+        ctx.tables = tuple(tables)
+        return res
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_image, grad_trans=None):
+        (vols,) = ctx.saved_tensors
+        if grad_image is None and grad_trans is None:
+            return None, None, None, None, None, None
+        return _moving_backward(_CAMERA_BACKWARD, vols, ctx.settings, ctx.tables, grad_image, grad_trans), None, None, None, None, None
+
+
 def render_camera(vols: torch.Tensor, azimuth, elevation, settings: Optional[RenderSettings] = None, *, transmittance: bool = False,
-                  out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+                  out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, **options):
     """Render [n,D,H,W] or [D,H,W] float32 volumes from an orthographic camera with an azimuth and an elevation (SPEC_3D.md section 10,
     "Free camera").  azimuth: render_orbit's, in degrees.  elevation, in degrees in [-90, 90]: positive raises the camera toward larger
     y, so that it looks down on the smoke (90: the top view).  Each of the two is
@@ -499,9 +548,28 @@ def render_camera(vols: torch.Tensor, azimuth, elevation, settings: Optional[Ren
     volume) when both are numbers and [n,V,H,W] ([V,H,W]) otherwise.  Returns the image, or (image, transmittance).  The batch may have
     any non-negative stride; every volume must be dense.  Lights: "none", "+y", "-y", fixed to the world ("+z" raises ValueError).  out: a
     contiguous float32 tensor of the image's shape to write into.  workspace: camera_workspace(...) of at least this call's size.  One
-    call renders all the views.  elevation=0 is the orbit's view on a longer ray: close to render_orbit's image, not equal to it.  There is
-    no backward yet: volumes that require a gradient raise RuntimeError (call under torch.no_grad() or detach them)."""
-    def angles(n):
-        az, el, views = _camera_angles(azimuth, elevation, n)
-        return (az, el), views
-    return _forward(_CAMERA, vols, settings, angles, transmittance=transmittance, out=out, workspace=workspace)
+    call renders all the views.  elevation=0 is the orbit's view on a longer ray: close to render_orbit's image, not equal to it.
+
+    differentiable=False (the default): there is no backward, and volumes that require a gradient raise RuntimeError (call under
+    torch.no_grad(), detach them, or pass differentiable=True).  differentiable=True: when autograd is on and `vols.requires_grad`, the
+    outputs carry a backward with respect to the volumes (SPEC_3D.md section 10, "Free camera -- Gradient";
+    smk_volume_render_camera_backward; H <= 4096, camera_backward_supported): it takes the gradient of the image ([n,(V),H,W]) and, with
+    transmittance=True, of the transmittance, and returns a gradient of vols' shape, the views summed.  The forward values are the plain
+    call's bit for bit.  `out=` raises ValueError then (an autograd output cannot be the caller's buffer), and a second derivative is
+    not supported (RuntimeError from autograd).  With nothing that requires a gradient it is the plain path.
+
+    `differentiable` is the one keyword taken through **options (any other raises TypeError, as a named parameter list would): the named
+    parameters are those of the forward-only render, which tests/test_render_orbit_grad_host.py holds in place."""
+    differentiable = options.pop("differentiable", False)
+    if options:
+        raise TypeError(f"render_camera() got an unexpected keyword argument {next(iter(options))!r}")
+    if differentiable and torch.is_grad_enabled() and isinstance(vols, torch.Tensor) and vols.requires_grad:
+        if out is not None:
+            raise ValueError("render_camera: out= cannot be used when the volumes require a gradient (an autograd output cannot be the "
+                             "caller's buffer); call under torch.no_grad() or detach the volumes")
+        settings = RenderSettings() if settings is None else settings
+        if not isinstance(settings, RenderSettings):
+            raise TypeError("render_camera: settings must be a RenderSettings")
+        return _RenderCamera.apply(vols, azimuth, elevation, settings, bool(transmittance), workspace)
+    return _forward(_CAMERA, vols, settings, _camera_angle_tables(azimuth, elevation), transmittance=transmittance, out=out,
+                    workspace=workspace)
