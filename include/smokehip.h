@@ -217,6 +217,36 @@ int smk_apply_fractal(const float *in, float *out, int32_t n_fields, int32_t N, 
  * which = 0/1/2 selects the field's shape (u-like [H+1][pitch_c], v-like [H][pitch_v], cell [H][pitch_c]); no decay. */
 int smk_advect(const float *field, float *out, int32_t which, const float *u, const float *v, int32_t B, int32_t H,
                int32_t W, int32_t pitch_c, int32_t pitch_v, double dt, void *stream);
+/* The adjoint of one step() (navier_stokes.py:151-173) with respect to its state, stage by stage -- no reference counterpart (the reference
+ * is differentiated by torch autograd).  The derivative is that of the expressions as written: floor and integer casts have derivative 0,
+ * a clamp of a coordinate passes its gradient where lo <= x <= hi (bounds included), dt / viscosity / jacobi_iters are constants.
+ * Buffers are fp32 in the layout of smk_advect (batch-major, planes rows * pitch floats apart, pitch_c >= W, pitch_v >= W + 1), caller-owned,
+ * 4-byte aligned and no better; no output may alias an input or another output; every element [row][col < columns] of every output is
+ * written (the caller need not zero them; the pitch padding is left alone); fp32 sums in one fixed order, no atomics: bit-identical from
+ * call to call, a grid's result independent of its batch mates.  All work is enqueued on `stream`, nothing is allocated, no
+ * synchronisation.  1 <= B <= 65535, 3 <= H, W <= 32766.
+ *
+ * smk_advect_backward: out = advection_step(field; u, v) of smk_advect (which = 2: times 0.995, the density stage of step()), gout the
+ *   gradient of out (field-shaped) -> dfield (field-shaped), du [H+1][pitch_c], dv [H][pitch_v]; field may be the same buffer as u or v (then
+ *   the caller adds dfield to du or dv).  One launch.  The kernel gathers over the 3 x 3 destinations around a source cell, which holds while
+ *   every back-trace moves less than one cell (|x - dt u| and |y - dt v| as the forward evaluates them); a grid that breaks this has
+ *   far[b] = 1 (int32 [B]; 0 otherwise, every word written) and its three outputs are then unspecified finite-or-not values the caller
+ *   must discard.  The other grids are unaffected.
+ * smk_project_backward: pressure_projection (navier_stokes.py:133-149) with jacobi_iters >= 0 sweeps, (gu, gv, gp) the gradients of its
+ *   results -> (du, dv, dp) those of its inputs.  ceil(jacobi_iters / 4) + 2 launches (four transposed sweeps per launch).  workspace: device memory of at
+ *   least smk_project_backward_workspace(B, H, W) bytes (-1 for an unsupported shape), 4-byte aligned, contents unspecified afterwards.
+ * smk_buoy_diffuse_backward: buoyancy + the three diffusion_steps (navier_stokes.py:154-160), (gu, gv, gd) the gradients of the diffused
+ *   u, v, density -> (du, dv, dd) those of the step's inputs.  One launch. */
+int smk_advect_backward(int32_t which, const float *field, const float *u, const float *v, const float *gout, float *dfield, float *du,
+                        float *dv, int32_t *far, int32_t B, int32_t H, int32_t W, int32_t pitch_c, int32_t pitch_v, double dt,
+                        void *stream);
+int64_t smk_project_backward_workspace(int32_t B, int32_t H, int32_t W);
+int smk_project_backward(const float *gu, const float *gv, const float *gp, float *du, float *dv, float *dp, int32_t B, int32_t H,
+                         int32_t W, int32_t pitch_c, int32_t pitch_v, int32_t jacobi_iters, double dt, void *workspace,
+                         int64_t workspace_bytes, void *stream);
+int smk_buoy_diffuse_backward(const float *gu, const float *gv, const float *gd, float *du, float *dv, float *dd, int32_t B, int32_t H,
+                              int32_t W, int32_t pitch_c, int32_t pitch_v, double dt, double viscosity, void *stream);
+
 /* NavierStokesSimulator.bilinear_interpolate(field, y, x) (navier_stokes.py:111-131; mode 0),
  * .interpolate_velocity_u(u, y, x) (:97-102; mode 1: x + 0.5 clamped to [0, w-1] first) and .interpolate_velocity_v(v, y, x)
  * (:104-109; mode 2: y + 0.5 clamped to [0, h-1] first) as pure gathers: B fields [h][pitch] (field_stride floats apart), n

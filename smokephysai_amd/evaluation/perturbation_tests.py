@@ -23,6 +23,8 @@ render's backward (smk_volume_render_backward), and with azimuth=... as well fro
 (physics.render_orbit, SPEC_3D.md section 10 "Orbit views") and reports how far its physics features move with the viewpoint; with
 elevation=... the ring is seen from above or below (physics.render_camera, "Free camera").
 physics_perturbation_test is 2-D only.
+adversarial_test(..., simulate=FluidRollout(steps=k)) perturbs the INITIAL smoke of 2-D frames: the model sees the density after k steps of
+the stepper, and the gradient reaches the initial density through physics.fluid_step's adjoint kernels (csrc/fluid_grad.hip).
 """
 import numbers
 import warnings
@@ -134,7 +136,7 @@ class PerturbationTester:
         return result
 
     def adversarial_test(self, model: nn.Module, test_data: torch.Tensor, epsilon: float = 0.1, num_steps: int = 10, *,
-                         target: Optional[torch.Tensor] = None, render=None, azimuth=None, elevation=None) -> Dict:
+                         target: Optional[torch.Tensor] = None, render=None, azimuth=None, elevation=None, simulate=None) -> Dict:
         """PGD on the reconstruction error (perturbation_tests.py:54-98): {'adversarial_feature_stability',
         'adversarial_perturbation_norm'}.  The gradient is taken with respect to the perturbation only (module docstring): with every
         parameter frozen, a SmokePhysNet with input_grad == "hip" serves 128^2 / 256^2 frames on its libsmokehip route (forward and
@@ -155,14 +157,33 @@ class PerturbationTester:
         elevation (needs render=): a number of degrees in [-90, 90] or a sequence of them.  The views are then the free camera's,
         render_camera(..., azimuth, elevation, render, differentiable=True) (SPEC_3D.md section 10, "Free camera -- Gradient";
         smk_volume_render_camera_backward), azimuth (0 when not given) and elevation paired view by view as render_camera pairs them;
-        everything else as with azimuth=.  None: the code path without it."""
+        everything else as with azimuth=.  None: the code path without it.
+        simulate: a physics.FluidRollout(steps=k, dt=..., viscosity=..., jacobi_iters=...); test_data is then initial densities
+        [B, 1, H, W] at rest (u = v = p = 0) and the model sees the density after k steps of clamp(test_data + delta, 0, 1) -- which change
+        to the smoke a frame GREW OUT OF changes the model's answer.  The gradient reaches the initial smoke through the stepper's adjoint
+        kernels (physics.fluid_step); the perturbation (and its norm) is the initial smoke's, the default comparison
+        image the clean rollout.  Not together with render=.  A grid whose back-traces move a cell or more has no gradient on that route
+        (NaN): a non-finite perturbation after the loop raises.  None: the code path without it."""
         model.eval()
+        if simulate is not None and render is not None:
+            raise ValueError("adversarial_test: simulate= and render= are two different ways to what the model sees: give one")
         if azimuth is not None and render is None:
             raise ValueError("adversarial_test: azimuth= needs render=RenderSettings(...): it is the rendered volume that is seen from there")
         if elevation is not None and render is None:
             raise ValueError("adversarial_test: elevation= needs render=RenderSettings(...): it is the rendered volume that is seen from there")
         shown = lambda x: x                  # noqa: E731  what the model sees of the (perturbed) data
-        if render is not None:
+        if simulate is not None:
+            from ..physics.fluid_grad import FluidRollout
+            if not isinstance(simulate, FluidRollout):
+                raise TypeError("adversarial_test: simulate must be a physics.FluidRollout")
+            if test_data.dim() != 4 or test_data.shape[1] != 1:
+                raise ValueError("adversarial_test: with simulate=, test_data must be initial densities [B, 1, H, W]")
+            test_data = test_data.detach().float().contiguous()
+            shown = lambda d: simulate(d[:, 0])[:, None]                        # noqa: E731
+            if target is None:
+                with torch.no_grad():
+                    target = shown(test_data)
+        elif render is not None:
             from ..physics.render import RenderSettings, render_volumes
             if not isinstance(render, RenderSettings):
                 raise TypeError("adversarial_test: render must be a RenderSettings")
@@ -218,6 +239,10 @@ class PerturbationTester:
                 p.requires_grad_(True)
             if warned is None:
                 model.__dict__.pop("_warned_grad", None)        # a later, unintended autograd forward still gets its hint
+        if simulate is not None and not bool(torch.isfinite(delta).all()):
+            raise RuntimeError("adversarial_test(simulate=): the perturbation is not finite.  The stepper's gradient on route='hip' holds "
+                               "while every back-trace moves less than one cell (|dt * velocity| < 1); a grid past that one-cell limit "
+                               "gets NaN gradients.  Use a smaller dt or FluidRollout(route='torch').")
         with torch.no_grad():
             baseline = model(shown(test_data))
             adversarial_output = model(shown(torch.clamp(test_data + delta, 0, 1)))

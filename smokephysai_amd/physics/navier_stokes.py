@@ -92,6 +92,12 @@ class NavierStokesSimulator(nn.Module):
     p = property(lambda s: s._view(s._p, s.w), lambda s, x: s._assign(s._p, s.w, x))
     density = property(lambda s: s._view(s._density, s.w), lambda s, x: s._assign(s._density, s.w, x))
 
+    def state(self):
+        """Clones of (u, v, p, density) in the batched shapes [B, H+1, W], [B, H, W+1], [B, H, W], [B, H, W] (B = 1 when un-batched):
+        what physics.fluid_step takes."""
+        w = self.w
+        return (self._u[:, :, :w].clone(), self._v[:, :, :w + 1].clone(), self._p[:, :, :w].clone(), self._density[:, :, :w].clone())
+
     def _st(self):
         return _lib.stream_ptr(self._dev)
 
