@@ -18,6 +18,16 @@
  *  - fields are fp32, batch-major [B][rows][pitch] with explicit row pitches (in floats):
  *        u [B][H+1][pitch_c]  v [B][H][pitch_v]  p,density [B][H][pitch_c]     pitch_c >= W, pitch_v >= W+1
  *    (the reference's shapes are u[H+1,W], v[H,W+1], p/density[H,W]: navier_stokes.py:27-32).
+ *  - state layouts (smk_sim, smk_sim3d and the stateless field helpers alike; DESIGN.md "Stepper state layouts"):
+ *      * every pitch_c >= W and pitch_v >= W+1 is accepted, the reference's dense pitch_c = W, pitch_v = W+1 included;
+ *      * u, v, (w,) p, density and frames need 4-byte alignment and nothing more;
+ *      * every frame_stride_b and frame_stride_t under which the [H][W] ([D][H][W]) frames do not overlap is accepted, gaps and a
+ *        transposed order (frame_stride_t < frame_stride_b) included;
+ *      * results are bit-identical across all accepted layouts: a kernel form that accesses rows 8 or 16 bytes at a time is selected
+ *        only where pitches, base pointers and grid strides make every such access naturally aligned, the narrower form otherwise
+ *        (smk_sim_describe / smk_sim3d_describe name the forms and the alignment facts they were chosen on);
+ *      * pad columns (col >= W, or > W for v, inside a row) never influence a result; their contents after a call are unspecified;
+ *      * nothing outside a field's [B][rows][pitch] extent, or outside a frame's [H][W] elements, is read into a result or written.
  */
 #ifndef SMOKEHIP_H
 #define SMOKEHIP_H
@@ -136,7 +146,11 @@ int smk_sim_fractal(smk_sim *sim, int32_t kind, const float **dev_ptr);
 
 /* Diagnostic: a JSON object (NUL-terminated, written into buf[capacity]) describing how this handle's step is launched -- the
  * projection's kernel, bands per grid, launches and sweeps per launch.  No reference counterpart (the reference runs 20 separate
- * sweeps, navier_stokes.py:139-145); bench.py reports it beside the stencil roofline. */
+ * sweeps, navier_stokes.py:139-145); bench.py reports it beside the stencil roofline.  Members: "projection" (the plan), "buoy_diffuse"
+ * (the form a step's buoyancy + diffusion takes: "vec4", "scalar" or "folded into the projection"), "buoy_diffuse_stage" (the form of
+ * SMK_STAGE_BUOY_DIFFUSE run alone: "vec4" or "scalar"), "alignment" (what the gates were given: the common alignment in bytes of the
+ * caller's u, v, density and of the projected u, v, the pitches and grid strides, the bytes of a band kernel's row access),
+ * "advection". */
 int smk_sim_describe(smk_sim *sim, char *buf, int64_t capacity);
 
 /* ------------------------------------------------------------------ 3-D simulation state (BASELINE configs[4])
@@ -191,6 +205,13 @@ typedef enum smk_stage3d {
     SMK_STAGE3D_ADVECT_D = 5      /* density advect + 0.995 decay */
 } smk_stage3d;
 int smk_sim3d_run_stage(smk_sim3d *sim, int32_t stage, void *stream);
+
+/* Diagnostic, as smk_sim_describe: a JSON object naming the form of every stage of this handle's step that has more than one.  "jacobi":
+ * "quad v4<T>" (four cells per thread, 16-byte accesses) or "xt" (one cell per thread) for the temporally blocked launches -- or, where
+ * jacobi_iters has none, the form of the single sweeps; "jacobi_sweep": "quad per-sweep" / "per-sweep" for the single sweeps left over
+ * (null: none); "jacobi_launches": the launches of 4, 2 and 1 sweeps; "alignment": the common alignment in bytes of p and the pressure
+ * scratch, pitch_c, the grid stride and the two predicates of the gate. */
+int smk_sim3d_describe(smk_sim3d *sim, char *buf, int64_t capacity);
 
 /* ------------------------------------------------------------------ 3-D encoder pieces (BASELINE configs[4]; SPEC_3D.md section 8)
  * No reference counterpart (the reference's input_encoder is Conv2d: smokephys_net.py:24-32).  Conv3d runs as an explicit GEMM on the

@@ -76,6 +76,7 @@ _SIGNATURES = {
     "smk_sim3d_step": [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p],
     "smk_sim3d_step_emit": [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_void_p],
     "smk_sim3d_run_stage": [C.c_void_p, C.c_int32, C.c_void_p],
+    "smk_sim3d_describe": [C.c_void_p, C.c_char_p, C.c_int64],
     "smk_conv3d_im2col": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p],
     "smk_conv3d_cl_forward": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p],
     "smk_conv3d_s7_forward": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p],

@@ -452,8 +452,8 @@ int smk_sim_describe(smk_sim *sim, char *buf, int64_t capacity) {
     SMK_REQUIRE(sim && buf && capacity > 0, "null sim / buf or no capacity");
     DeviceGuard guard(sim->device);
     if (guard.rc) return guard.rc;
-    const std::string d = "{\"projection\": " + describe_projection(sim->g, sim->jacobi_iters, &sim->psync) +
-                          ", \"advection\": \"k_advect_rows<8,4,3> (u, v, density + frame in one launch)\", \"launches_per_step\": null}";
+    const std::string d = "{\"projection\": " + describe_projection(sim->g, sim->jacobi_iters, &sim->psync, &sim->s, &sim->t) + ", " +
+                          describe_step_forms(sim->g, sim->jacobi_iters, &sim->psync, sim->s, sim->t) + ", \"advection\": \"k_advect_rows<8,4,3> (u, v, density + frame in one launch)\", \"launches_per_step\": null}";
     if ((int64_t)d.size() + 1 > capacity) {
         set_error("smk_sim_describe: buffer too small");
         return SMK_ERR_INVALID;
@@ -703,6 +703,18 @@ int smk_sim3d_run_stage(smk_sim3d *sim, int32_t stage, void *stream) {
     }
     set_error("unknown 3-D stage");
     return SMK_ERR_INVALID;
+}
+
+int smk_sim3d_describe(smk_sim3d *sim, char *buf, int64_t capacity) {
+    SMK_REQUIRE(sim && buf && capacity > 0, "null sim / buf or no capacity");
+    const std::string d = "{" + describe3_jacobi(sim->g, sim->s.p, sim->t.p, sim->p3, sim->div, sim->jacobi_iters) +
+                          ", \"buoy_diffuse\": \"k3_diffuse_div_march (one form)\", \"advection\": \"k3_advect_march (one form)\"}";
+    if ((int64_t)d.size() + 1 > capacity) {
+        set_error("smk_sim3d_describe: buffer too small");
+        return SMK_ERR_INVALID;
+    }
+    memcpy(buf, d.c_str(), d.size() + 1);
+    return SMK_OK;
 }
 
 int smk_conv3d_im2col(const float *src, int32_t C, int32_t D, int32_t H, int32_t W, int32_t ksize, int32_t z0, int32_t nz, float *cols,

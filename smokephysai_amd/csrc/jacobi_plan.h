@@ -16,12 +16,53 @@ namespace smk {
 
 constexpr int JB_NW = 16;                                     // waves of a band's workgroup: a tile is JB_NW * rpw rows
 
-// The integers of a Geom (common.h) that the plan depends on.
+// The integers of a Geom (common.h) that the shape plan depends on.
 struct PlanGeom {
     int H, W, B;
     int pc, pv;          // row pitches of the cell fields and of v
     size_t sc;           // plane stride of a cell field
 };
+// What the alignment gates need to know beyond the PlanGeom: the other grid strides and the addresses a call runs on.
+struct PlanLayout {
+    size_t su, sv;       // plane strides of u (H + 1 rows of pc) and of v (H rows of pv)
+    // Alignment in bytes (a power of two, 4 .. 16: ptr_align) common to the base pointers of
+    int in_align;        //   the state a step reads: the caller's u, v and density (k_buoy_diffuse4, the prologue of a plan that folds)
+    int uv_align;        //   the u and v the projection's gradient rewrites (the tail of k_jacobi_band)
+};
+// The strides smk_sim_create derives from the pitches; 16-byte aligned pointers unless said otherwise.
+inline PlanLayout plan_layout_of(const struct PlanGeom &g, int in_align = 16, int uv_align = 16) {
+    return PlanLayout{(size_t)(g.H + 1) * g.pc, (size_t)g.H * g.pv, in_align, uv_align};
+}
+// The alignment the addresses OR-ed into `bits` share, capped at the 16 bytes of the widest access any stepper kernel makes.
+inline int ptr_align(unsigned long long bits) { return (bits & 15) == 0 ? 16 : ((bits & 7) == 0 ? 8 : 4); }
+
+// ---- the alignment gates (DESIGN "Stepper state layouts") ----------------------------------------------------------------------------
+// A row access of `bytes` (4, 8 or 16) at base + grid * stride + row * pitch + j0, with j0 a multiple of bytes / 4 floats, is naturally
+// aligned for every grid and row exactly when base, pitch and grid stride are multiples of it.
+inline bool rows_aligned(int bytes, int pitch, size_t stride, int base_align) {
+    const int n = bytes / 4;
+    return pitch % n == 0 && stride % (size_t)n == 0 && base_align % bytes == 0;
+}
+// The widest row access of k_jacobi_band<vec, ...>: ldv / stv move a lane's `vec` cells as float, float2 or float4 (VecT, stencil.hip).
+SMK_PLAN_HD constexpr int jb_access_bytes(int vec) { return vec >= 4 ? 16 : 4 * vec; }
+// The exchange buffers of the persistent form (the handle's own allocations: 256-byte aligned): pitch pc, stride sc.
+inline bool jb_cell_rows_aligned(const PlanGeom &g, int vec) { return rows_aligned(jb_access_bytes(vec), g.pc, g.sc, 16); }
+// The gradient epilogue's whole-row read-modify-write of u and v (jacobi_band_tail.h).
+inline bool jb_tail_aligned(const PlanGeom &g, const PlanLayout &l, int vec) {
+    const int a = jb_access_bytes(vec);
+    return rows_aligned(a, g.pc, l.su, l.uv_align) && rows_aligned(a, g.pv, l.sv, l.uv_align);
+}
+// The folded prologue's row loads of the step's input u, v, density (its stores go where the tail's do: jb_tail_aligned).
+inline bool jb_fold_aligned(const PlanGeom &g, const PlanLayout &l, int vec) {
+    const int a = jb_access_bytes(vec);
+    return rows_aligned(a, g.pc, l.su, l.in_align) && rows_aligned(a, g.pv, l.sv, l.in_align) && rows_aligned(a, g.pc, g.sc, l.in_align);
+}
+// The buoyancy + diffusion stage as a launch of its own: four columns per thread (k_buoy_diffuse4: 16-byte row accesses on the step's input
+// u, v, density and on the handle's scratch state, which has the same pitches and strides) or one (k_buoy_diffuse).
+inline bool buoy_diffuse_vec4(const PlanGeom &g, const PlanLayout &l) {
+    return g.W % 4 == 0 && rows_aligned(16, g.pc, l.su, l.in_align) && rows_aligned(16, g.pv, l.sv, l.in_align) &&
+           rows_aligned(16, g.pc, g.sc, l.in_align);
+}
 
 // Bands own unequal row ranges: the first and last band of a grid need a halo only on their inner side (the other side is the physical
 // boundary), so they own TR - halo rows and the middle bands TR - 2 halo.  One band: the whole grid.  [own0, own1) are the rows the band
@@ -172,6 +213,20 @@ inline ProjectionPlan plan_projection(const PlanGeom &g, int iters, int num_cu, 
     const bool persist = pp.form == ProjectionForm::persistent;
     pp.two_forms = jb_two_forms(pp.vec, pp.rpw, persist, pp.folds);
     pp.pipelined = jb_pipelined(pp.vec, pp.rpw, persist);
+    return pp;
+}
+
+// The plan a launch takes: the shape plan above, held to the layout it is to run on.  plan_projection works the bands out from the grid's
+// shape on the assumption that every row access of the band kernel is aligned; here a band plan whose accesses (jb_access_bytes(vec) wide)
+// would not be naturally aligned under `l` gives way to the per-sweep kernel, and a plan folds only where the prologue's loads of the
+// step's input are aligned too.  All band candidates of a shape have the same cells per lane, so no other band plan could pass instead.
+inline ProjectionPlan plan_projection_on(const PlanGeom &g, const PlanLayout &l, int iters, int num_cu, bool allow_persist, bool with_gradient) {
+    ProjectionPlan pp = plan_projection(g, iters, num_cu, allow_persist, with_gradient);
+    if (pp.form == ProjectionForm::sweeps) return pp;
+    if (!jb_cell_rows_aligned(g, pp.vec) || (with_gradient && !jb_tail_aligned(g, l, pp.vec))) return ProjectionPlan{};
+    const bool persist = pp.form == ProjectionForm::persistent;
+    pp.folds = pp.folds && jb_fold_aligned(g, l, pp.vec);
+    pp.two_forms = jb_two_forms(pp.vec, pp.rpw, persist, pp.folds);
     return pp;
 }
 

@@ -86,7 +86,12 @@ hipError_t launch_project(const Geom &g, float *u, float *v, float *p, float *p2
 // folds (jacobi_plan.h), the first stage runs as the prologue of that one launch.
 hipError_t launch_buoy_project(const Geom &g, StateView in, StateView out, float *p, float *div, int iters, hipStream_t st, ProjectSync *ps);
 // JSON description of what launch_project does for this geometry (kernel, bands, launches, sweeps per launch, on-chip estimates).
-std::string describe_projection(const Geom &g, int iters, const ProjectSync *ps = nullptr);
+// in / out: the state a step reads and the scratch state its projection rewrites (their alignment is part of the plan); null: aligned.
+std::string describe_projection(const Geom &g, int iters, const ProjectSync *ps = nullptr, const StateView *in = nullptr,
+                                const StateView *out = nullptr);
+// "buoy_diffuse": the form a step's buoyancy + diffusion takes ("vec4", "scalar", "folded into the projection"), "buoy_diffuse_stage":
+// the form of the stage run alone (smk_sim_run_stage), "alignment": what the gates were given -- members of smk_sim_describe's object.
+std::string describe_step_forms(const Geom &g, int iters, const ProjectSync *ps, const StateView &in, const StateView &out);
 hipError_t launch_grad_subtract(const Geom &g, float *u, float *v, const float *p, hipStream_t st);
 // kind 0: field=u (H+1 x W), 1: field=v (H x W+1), 2: density (H x W) with *0.995 decay and optional frame emit.
 hipError_t launch_advect(const Geom &g, int kind, const float *field, float *out, const float *u, const float *v,

@@ -28,6 +28,22 @@ __device__ __forceinline__ int clampi(int x, int lo, int hi) {
     return t > hi ? hi : t;
 }
 
+// The plan's view of a call: the geometry (plan_geom), and the layout it runs on (plan_layout): the strides and the alignment of the state
+// the step reads (`in`, may be null: no such stage in this call) and of the u, v the projection rewrites.
+static unsigned long long addr_bits(const float *a, const float *b, const float *c = nullptr) {
+    return (unsigned long long)(uintptr_t)a | (unsigned long long)(uintptr_t)b | (unsigned long long)(uintptr_t)c;
+}
+static PlanGeom plan_geom(const Geom &g) { return PlanGeom{g.H, g.W, g.B, g.pc, g.pv, g.sc}; }
+static PlanLayout plan_layout(const Geom &g, const StateView *in, const float *u, const float *v) {
+    return PlanLayout{g.su, g.sv, in ? ptr_align(addr_bits(in->u, in->v, in->d)) : 16, ptr_align(addr_bits(u, v))};
+}
+// The buoyancy + diffusion stage as a launch of its own has one gate for the loads of `in` and the stores of `out`: both sides' pointers count.
+static PlanLayout buoy_diffuse_layout(const Geom &g, const StateView &in, const StateView &out) {
+    PlanLayout l = plan_layout(g, &in, out.u, out.v);
+    l.in_align = ptr_align(addr_bits(in.u, in.v, in.d) | addr_bits(out.u, out.v, out.d));
+    return l;
+}
+
 // ---------------------------------------------------------------- reset (navier_stokes.py:24-35)
 __global__ void k_zero_state(Geom g, StateView s, const uint8_t *mask) {
     int b = blockIdx.z;
@@ -211,7 +227,7 @@ __global__ __launch_bounds__(256) void k_buoy_diffuse4(Geom g, StateView in, Sta
 }
 
 hipError_t launch_buoy_diffuse(const Geom &g, StateView in, StateView out, hipStream_t st) {
-    if (g.W % 4 == 0 && g.pc % 4 == 0 && g.pv % 4 == 0) {
+    if (buoy_diffuse_vec4(plan_geom(g), buoy_diffuse_layout(g, in, out))) {
         dim3 grid(cdiv(g.W / 4, TX), cdiv(g.H + 1, TY), g.B), block(TX, TY);
         hipLaunchKernelGGL(k_buoy_diffuse4, grid, block, 0, st, g, in, out);
         return hipGetLastError();
@@ -286,7 +302,8 @@ template <> struct VecT<1> { using type = float; };
 template <> struct VecT<2> { using type = float2; };
 template <> struct VecT<4> { using type = float4; };
 template <> struct VecT<8> { using type = float4; };
-// VEC consecutive floats of a lane as vector loads / stores (rows are 128-byte aligned and a lane's cells start at a multiple of VEC)
+// VEC consecutive floats of a lane as vector loads / stores of jb_access_bytes(VEC) bytes.  A lane's cells start at a multiple of VEC; that the
+// rows do at a multiple of those bytes is what jb_tail_aligned / jb_fold_aligned (jacobi_plan.h) hold a band plan to before it is launched
 template <int VEC>
 __device__ __forceinline__ void ldv(float (&dst)[VEC], const float *src) {
     using V = typename VecT<VEC>::type;
@@ -617,8 +634,6 @@ static const StencilKnobs &knobs() {
     return k;
 }
 
-static PlanGeom plan_geom(const Geom &g) { return PlanGeom{g.H, g.W, g.B, g.pc, g.pv, g.sc}; }
-
 // A plan's (vec, rpw) as compile-time constants: f(VEC, RPW), two std::integral_constant, for every pair that has a kernel -- 6 and 8
 // rows per wave only up to 4 cells per lane (the register budget of jb_search_bands).
 template <class F>
@@ -689,7 +704,7 @@ static void launch_persist(const Geom &g, const ProjectionPlan &pp, bool fold, f
 hipError_t launch_jacobi(const Geom &g, float *p, float *p2, const float *div, int iters, hipStream_t st) {
     if (iters <= 0) return hipSuccess;
     dim3 grid(cdiv(g.W, TX), cdiv(g.H, TY), g.B), block(TX, TY);
-    const ProjectionPlan pp = plan_projection(plan_geom(g), iters, 0, false, false);    // (never persistent: the CU count is not read)
+    const ProjectionPlan pp = plan_projection_on(plan_geom(g), plan_layout(g, nullptr, nullptr, nullptr), iters, 0, false, false);    // (never persistent: the CU count is not read)
     float *cur = p, *nxt = p2;
     if (pp.form == ProjectionForm::bands) {
         cur = launch_band_runs(g, pp, p, p2, const_cast<float *>(div), nullptr, nullptr, iters, st);
@@ -726,11 +741,11 @@ static bool handle_allows_persist(const ProjectSync *ps) { return ps && ps->flag
 
 // The plan of a projection enqueued on `st` now.  A captured launch would replay with the hand-off count of capture time: under stream
 // capture the multi-launch form is recorded.  So it is while a time-out of an earlier launch waits to be reported.
-static ProjectionPlan plan_call(const Geom &g, int iters, hipStream_t st, const ProjectSync *ps) {
+static ProjectionPlan plan_call(const Geom &g, const PlanLayout &lay, int iters, hipStream_t st, const ProjectSync *ps) {
     hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
     const bool capturing = hipStreamIsCapturing(st, &cap_status) == hipSuccess && cap_status != hipStreamCaptureStatusNone;
     const bool pending_error = ps && ps->status && *ps->status != 0u;
-    return plan_projection(plan_geom(g), iters, device_num_cu(), handle_allows_persist(ps) && !capturing && !pending_error, true);
+    return plan_projection_on(plan_geom(g), lay, iters, device_num_cu(), handle_allows_persist(ps) && !capturing && !pending_error, true);
 }
 
 // Two persistent projections cannot share the device: each needs all of its workgroups resident at once, and two half-resident grids
@@ -809,13 +824,13 @@ hipError_t launch_project(const Geom &g, float *u, float *v, float *p, float *p2
     // a wait inside an earlier persistent launch timed out (its workgroups were not co-resident within the limit): that projection's
     // result is invalid (NaN).  Say so once, loudly, and use the multi-launch form from here on.
     if (ps && project_sync_take_timeout(*ps)) return hipErrorLaunchTimeOut;
-    return run_projection(g, plan_call(g, iters, st, ps), u, v, p, p2, div, iters, st, ps);
+    return run_projection(g, plan_call(g, plan_layout(g, nullptr, u, v), iters, st, ps), u, v, p, p2, div, iters, st, ps);
 }
 
 // Stages 1-3 of a time step (navier_stokes.py:154-163): buoyancy + diffusion (in -> out.u, out.v, out.d) and the projection of
 // (out.u, out.v) with the pressure p.  One persistent launch where the plan allows, otherwise the two stages as before.
 hipError_t launch_buoy_project(const Geom &g, StateView in, StateView out, float *p, float *div, int iters, hipStream_t st, ProjectSync *ps) {
-    const ProjectionPlan pp = plan_call(g, iters, st, ps);
+    const ProjectionPlan pp = plan_call(g, plan_layout(g, &in, out.u, out.v), iters, st, ps);
     const bool fold = pp.form == ProjectionForm::persistent && pp.folds;
     if (!fold) {
         const hipError_t e = launch_buoy_diffuse(g, in, out, st);
@@ -826,9 +841,27 @@ hipError_t launch_buoy_project(const Geom &g, StateView in, StateView out, float
 }
 
 // What one projection launches for this geometry, as a JSON object (describe_plan).
-std::string describe_projection(const Geom &g, int iters, const ProjectSync *ps) {
+std::string describe_projection(const Geom &g, int iters, const ProjectSync *ps, const StateView *in, const StateView *out) {
     const PlanGeom pg = plan_geom(g);
-    return describe_plan(plan_projection(pg, iters, device_num_cu(), handle_allows_persist(ps), true), iters, pg, device_num_cu());
+    const PlanLayout lay = plan_layout(g, in, out ? out->u : nullptr, out ? out->v : nullptr);
+    return describe_plan(plan_projection_on(pg, lay, iters, device_num_cu(), handle_allows_persist(ps), true), iters, pg, device_num_cu());
+}
+
+// The form a step's buoyancy + diffusion stage takes (in -> out) and the alignment facts its gate and the projection's were given, as
+// members of the JSON object of smk_sim_describe.
+std::string describe_step_forms(const Geom &g, int iters, const ProjectSync *ps, const StateView &in, const StateView &out) {
+    const PlanLayout lay = plan_layout(g, &in, out.u, out.v);
+    const ProjectionPlan pp = plan_projection_on(plan_geom(g), lay, iters, device_num_cu(), handle_allows_persist(ps), true);
+    const bool fold = pp.form == ProjectionForm::persistent && pp.folds;
+    const int in_align = lay.in_align, uv_align = lay.uv_align;
+    const bool vec4 = buoy_diffuse_vec4(plan_geom(g), buoy_diffuse_layout(g, in, out));
+    char buf[512];
+    snprintf(buf, sizeof buf,
+             "\"buoy_diffuse\": \"%s\", \"buoy_diffuse_stage\": \"%s\", \"alignment\": {\"state_in_bytes\": %d, \"projected_uv_bytes\": %d, "
+             "\"pitch_c\": %d, \"pitch_v\": %d, \"stride_u\": %zu, \"stride_v\": %zu, \"stride_c\": %zu, \"band_row_access_bytes\": %d}",
+             fold ? "folded into the projection" : (vec4 ? "vec4" : "scalar"), vec4 ? "vec4" : "scalar", in_align, uv_align, g.pc, g.pv, g.su,
+             g.sv, g.sc, pp.form == ProjectionForm::sweeps ? 4 : jb_access_bytes(pp.vec));
+    return buf;
 }
 
 __global__ void k_grad_subtract(Geom g, float *u, float *v, const float *p) {

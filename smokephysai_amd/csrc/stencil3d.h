@@ -1,6 +1,8 @@
 // 3-D stepper (BASELINE configs[4]); semantics: SPEC_3D.md, the rule-by-rule generalisation of
 // /root/reference/src/physics/navier_stokes.py:24-173 (the reference itself is 2-D only).
 #pragma once
+#include <string>
+
 #include "common.h"
 
 namespace smk {
@@ -26,6 +28,8 @@ hipError_t launch3_diffuse_div_march(const Geom3 &g, State3 in, State3 out, floa
 // `iters` sweeps on `div`; result in p (p2, and p3 if not null, scratch of the same layout: a third buffer lets an odd number of launches
 // end in p without a copy)
 hipError_t launch3_jacobi(const Geom3 &g, float *p, float *p2, float *p3, const float *div, int iters, hipStream_t st);
+// the Jacobi members of smk_sim3d_describe's JSON object for these buffers (jacobi3d_plan.h: describe_plan3)
+std::string describe3_jacobi(const Geom3 &g, const float *p, const float *p2, const float *p3, const float *div, int iters);
 hipError_t launch3_grad_subtract(const Geom3 &g, State3 s, const float *p, hipStream_t st);
 // which 0..3 = u, v, w, density (x 0.995, + optional frame [B][D][H][W] dense at frame_stride_b floats per grid)
 hipError_t launch3_advect(const Geom3 &g, int which, const float *field, float *out, const float *u, const float *v, const float *w,

@@ -9,6 +9,7 @@
 // J = 20), 64 consecutive x per wavefront, z-neighbour planes served by the L2 / Infinity Cache (workgroups are issued plane-major, so
 // the planes z-1, z, z+1 of a grid are in flight together).
 #include "stencil3d.h"
+#include "jacobi3d_plan.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -484,25 +485,27 @@ static void launch3_jacobi_xt(const Geom3 &g, const float *cur, float *nxt, cons
     hipLaunchKernelGGL((k3_jacobi_xt<T, TXB, TYB, CY>), grid, block, 0, st, g, cur, nxt, div);
 }
 
+// What the plan (jacobi3d_plan.h) sees of a call.
+static Jacobi3Geom plan3_geom(const Geom3 &g, const float *p, const float *p2, const float *p3, const float *div) {
+    const uintptr_t bits = (uintptr_t)p | (uintptr_t)p2 | (uintptr_t)p3 | (uintptr_t)div;
+    return Jacobi3Geom{g.B, g.W, g.pc, g.sc, (bits & 15) == 0 ? 16 : ((bits & 7) == 0 ? 8 : 4), p3 != nullptr};
+}
+
+std::string describe3_jacobi(const Geom3 &g, const float *p, const float *p2, const float *p3, const float *div, int iters) {
+    const Jacobi3Geom pg = plan3_geom(g, p, p2, p3, div);
+    return describe_plan3(plan3_jacobi(pg, iters), pg);
+}
+
 hipError_t launch3_jacobi(const Geom3 &g, float *p, float *p2, float *p3, const float *div, int iters, hipStream_t st) {
-    const bool vec = g.W % 4 == 0 && g.pc % 4 == 0;
-    dim3 block(TX3, TY3), grid(cdiv(vec ? g.W / 4 : g.W, TX3), cdiv(g.H, TY3), g.B * g.D);
-    // temporally blocked launches of at most 4 sweeps first, single sweeps for the rest; four cells per thread (k3_jacobi_v4) where rows
-    // are whole aligned quads, otherwise the one-cell-per-thread blocked kernel (k3_jacobi_xt)
-    const bool quad = vec && (((uintptr_t)p | (uintptr_t)p2 | (uintptr_t)p3 | (uintptr_t)div) & 15) == 0 && g.sc % 4 == 0;
-    // the launch plan: sweeps per launch.  The result must end in p without a copy.  Two buffers ping-pong, so an even launch count does;
-    // an odd count of three or more goes p -> p2 -> p3 -> p2 -> ... -> p through the third buffer (J = 20: five 4-sweep launches); without a
-    // third buffer one 4-sweep launch is traded for two 2-sweep ones (round 3's plan: 4 x 4 + 2 x 2)
-    int plan[64], n = 0, left = iters;
-    const bool blocked = g.B <= 65535;
-    int n4 = blocked ? left / 4 : 0;
-    if (n4 > 60) n4 = 60;
-    const bool third = p3 != nullptr;
-    if (!third && left % 4 == 0 && (n4 & 1) && n4 * 4 == left) --n4;
-    for (int k = 0; k < n4; ++k) plan[n++] = 4;
-    left -= 4 * n4;
-    if (blocked)
-        for (; left >= 2 && n < 62; left -= 2) plan[n++] = 2;
+    // temporally blocked launches of at most 4 sweeps first, single sweeps for the rest; four cells per thread (k3_jacobi_v4, k3_jacobi4)
+    // where rows are whole aligned quads, otherwise one cell per thread (k3_jacobi_xt, k3_jacobi): the plan of jacobi3d_plan.h
+    const Jacobi3Plan pl = plan3_jacobi(plan3_geom(g, p, p2, p3, div), iters);
+    const bool quad = pl.quad, third = p3 != nullptr;
+    dim3 block(TX3, TY3), grid(cdiv(quad ? g.W / 4 : g.W, TX3), cdiv(g.H, TY3), g.B * g.D);
+    int plan[64], n = 0;
+    for (int k = 0; k < pl.n4; ++k) plan[n++] = 4;
+    for (int k = 0; k < pl.n2; ++k) plan[n++] = 2;
+    const int left = pl.n1;
     float *cur = p;
     auto target = [&](int i, int total) -> float * {            // where launch i of `total` writes
         if (i == total - 1 && cur != p) return p;
@@ -523,7 +526,7 @@ hipError_t launch3_jacobi(const Geom3 &g, float *p, float *p2, float *p3, const 
     }
     for (int i = n; i < total; ++i) {
         float *nxt = target(i, total);
-        if (vec) hipLaunchKernelGGL(k3_jacobi4, grid, block, 0, st, g, cur, nxt, div);
+        if (quad) hipLaunchKernelGGL(k3_jacobi4, grid, block, 0, st, g, cur, nxt, div);
         else hipLaunchKernelGGL(k3_jacobi, grid, block, 0, st, g, cur, nxt, div);
         cur = nxt;
     }

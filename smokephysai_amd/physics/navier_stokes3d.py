@@ -99,6 +99,13 @@ class NavierStokesSimulator3D(nn.Module):
         """One stage of step() (include/smokehip.h smk_stage3d) -- parity-test hook."""
         _lib.check(self._L.smk_sim3d_run_stage(self._handle, stage, self._st()))
 
+    def jacobi_plan(self) -> dict:
+        """How libsmokehip launches this simulator's Jacobi sweeps (kernel form, launches, the alignment facts of the gate)."""
+        import json
+        buf = C.create_string_buffer(4096)
+        _lib.check(self._L.smk_sim3d_describe(self._handle, buf, 4096))
+        return json.loads(buf.value.decode())
+
     def pressure_projection(self):
         """navier_stokes.py:133-149 in 3-D (in place on u, v, w, p)."""
         self.run_stage(STAGE3D_PROJECT)

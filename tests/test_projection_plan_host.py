@@ -5,7 +5,13 @@
     rows of the bands tile the grid, every tile lies in the grid and holds its owned rows and halo, the runs add up and fit the halo, a
     persistent plan fits the device, and the keep buffer's slots are used once;
   * recomputes tests/host/projection_plans_parent.txt, the plans and descriptions recorded from the planner as it was before it moved into
-    the header, byte for byte.
+    the header, byte for byte;
+(Both of these are about plan_projection, the plan worked out from the grid's shape; what a launch takes is plan_projection_on, that plan
+held to the layout it runs on, which the next two are about.)
+  * recomputes the plans of the simulator classes' own layout at every shape bench.py and tests/test_hip_physics.py step and holds them to
+    the literals recorded before pointer and stride terms entered the gates (the alignment gates must not reroute that layout);
+  * enumerates pitches W .. W+9, pointer offsets 0 / 4 / 8 / 12, odd and even H: every 8- or 16-byte access of the forms the gates select
+    (DESIGN "Stepper state layouts") is naturally aligned, checked by address arithmetic and not by the gates' own predicate.
 On the GPU a fresh simulator's jacobi_plan() must give the recorded description of its row (no kernel runs)."""
 import json
 import os
@@ -28,7 +34,9 @@ def exe(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("projplan") / "projection_plan")
     base = [cxx, "-O2", "-std=c++17", "-Wall", "-I", INC, SRC, "-o", out]
     # a plain host executable: undefined-behaviour checks where the toolchain has the runtime, without them otherwise
-    r = subprocess.run(base + ["-fsanitize=undefined", "-fno-sanitize-recover=undefined"], capture_output=True, text=True)
+    r = subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], capture_output=True, text=True)
+    if r.returncode != 0:
+        r = subprocess.run(base + ["-fsanitize=undefined", "-fno-sanitize-recover=undefined"], capture_output=True, text=True)
     if r.returncode != 0:
         r = subprocess.run(base, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -55,6 +63,27 @@ def test_same_plans_as_before_the_move(exe):
     differing = [(w, g) for w, g in zip(want_lines, got_lines) if w != g]
     assert not differing, differing[:5]
     assert run.stdout == want
+
+
+def test_the_simulator_layout_keeps_the_plans_it_had(exe):
+    """Rows padded to 32 floats, 16-byte aligned pointers: plan structs and the buoyancy/diffusion form equal to the recorded literals."""
+    run = subprocess.run([exe, "wrapper"], capture_output=True, text=True, timeout=600)
+    assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-2000:])
+    m = re.search(r"^WRAPPER (\d+) MISMATCH (\d+)$", run.stdout, flags=re.M)
+    assert m, run.stdout[-2000:]
+    assert int(m.group(1)) >= 60 and int(m.group(2)) == 0, run.stdout[:4000]
+
+
+def test_every_selected_wide_access_is_naturally_aligned(exe):
+    run = subprocess.run([exe, "alignment"], capture_output=True, text=True, timeout=600)
+    assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-2000:])
+    m = re.search(r"^ALIGNMENT CASES (\d+) VEC4 (\d+) SCALAR (\d+) FOLD (\d+) BAND1 (\d+) BAND2 (\d+) BAND4 (\d+) BAND8 (\d+) SWEEPS (\d+) "
+                  r"MISALIGNED (\d+)$", run.stdout, flags=re.M)
+    assert m, run.stdout[-2000:]
+    cases, vec4, scalar, fold, b1, b2, b4, b8, sweeps, bad = map(int, m.groups())
+    assert cases == 7 * 7 * 10 * 10 * 4 * 4 * 2 * 2 * 2      # H x W x pitch_c x pitch_v x input offset x projected-uv offset x B x iters x allow_persist
+    assert min(vec4, scalar, fold, b1, b2, b4, b8, sweeps) > 0          # the enumeration reaches every form
+    assert bad == 0, run.stdout[:4000]
 
 
 def _recorded_description(H, W, B, iters):
