@@ -267,6 +267,40 @@ int smk_project_backward(const float *gu, const float *gv, const float *gp, floa
                          int64_t workspace_bytes, void *stream);
 int smk_buoy_diffuse_backward(const float *gu, const float *gv, const float *gd, float *du, float *dv, float *dd, int32_t B, int32_t H,
                               int32_t W, int32_t pitch_c, int32_t pitch_v, double dt, double viscosity, void *stream);
+/* The adjoint of one 3-D step() (SPEC_3D.md sections 3-6) with respect to its state (u, v, w, p, density), stage by stage: the 3-D
+ * counterpart of the three entry points above, with the same derivative conventions (floor and integer casts have derivative 0, a clamp
+ * of a coordinate passes its gradient where lo <= x <= hi, bounds included, dt / viscosity / jacobi_iters are constants; the velocity
+ * sample coordinates are index grids, so a sample is linear in its component: 0.5 / 0.5 on c[z][y][x] and its +1 neighbour along the
+ * acting axis where every index is <= extent - 2, exactly 0 elsewhere).  Buffers are fp32 in the 3-D stepper's layout (smk_sim3d_desc:
+ * batch-major, [planes][rows][pitch], u [D][H+1][pitch_c], v [D][H][pitch_v], w [D+1][H][pitch_c], cell fields [D][H][pitch_c],
+ * pitch_c >= W, pitch_v >= W + 1), caller-owned, 4-byte aligned and no better; no output may alias an input or another output; every
+ * element [plane][row][col < columns] of every output is written (the caller need not zero them; the pitch padding is left alone); fp32
+ * sums in one fixed order, no atomics: bit-identical from call to call, a grid's result independent of its batch mates.  All work is
+ * enqueued on `stream`, nothing is allocated, no synchronisation.  Limits: smk_sim3d_create's -- B >= 1, 3 <= D, H, W <= 32766,
+ * B * (D + 1) <= 65535, one grid's field below 2^31 elements.
+ *
+ * smk_advect3d_backward: out = advection_step(field; u, v, w) (which = 0 / 1 / 2 / 3: field shaped like u / v / w / a cell field;
+ *   3: times 0.995, the density stage of step()), gout the gradient of out (field-shaped) -> dfield (field-shaped), du, dv, dw; field may
+ *   be the same buffer as u, v or w (then the caller adds dfield to du, dv or dw).  One kernel launch.  The kernel gathers over the
+ *   3 x 3 x 3 destinations around a source cell, which holds while every back-trace moves less than one cell on every axis (as the
+ *   forward evaluates x - dt u, y - dt v, z - dt w); a grid that breaks this has far[b] = 1 (int32 [B]; 0 otherwise, every word written)
+ *   and its four outputs are then unspecified finite-or-not values the caller must discard.  The other grids are unaffected.
+ * smk_project3d_backward: pressure_projection with jacobi_iters >= 0 sweeps, (gu, gv, gw, gp) the gradients of its results ->
+ *   (du, dv, dw, dp) those of its inputs.  ceil(jacobi_iters / 2) + 2 launches (two transposed sweeps per launch).  workspace: device
+ *   memory of at least smk_project3d_backward_workspace(B, D, H, W) bytes (-1 for an unsupported shape), 4-byte aligned, contents
+ *   unspecified afterwards; a smaller one is refused with SMK_ERR_INVALID and nothing is written.
+ * smk_buoy_diffuse3d_backward: buoyancy + the four diffusion_steps, (gu, gv, gw, gd) the gradients of the diffused u, v, w, density ->
+ *   (du, dv, dw, dd) those of the step's inputs.  One launch. */
+int smk_advect3d_backward(int32_t which, const float *field, const float *u, const float *v, const float *w, const float *gout,
+                          float *dfield, float *du, float *dv, float *dw, int32_t *far, int32_t B, int32_t D, int32_t H, int32_t W,
+                          int32_t pitch_c, int32_t pitch_v, double dt, void *stream);
+int64_t smk_project3d_backward_workspace(int32_t B, int32_t D, int32_t H, int32_t W);
+int smk_project3d_backward(const float *gu, const float *gv, const float *gw, const float *gp, float *du, float *dv, float *dw, float *dp,
+                           int32_t B, int32_t D, int32_t H, int32_t W, int32_t pitch_c, int32_t pitch_v, int32_t jacobi_iters, double dt,
+                           void *workspace, int64_t workspace_bytes, void *stream);
+int smk_buoy_diffuse3d_backward(const float *gu, const float *gv, const float *gw, const float *gd, float *du, float *dv, float *dw,
+                                float *dd, int32_t B, int32_t D, int32_t H, int32_t W, int32_t pitch_c, int32_t pitch_v, double dt,
+                                double viscosity, void *stream);
 
 /* NavierStokesSimulator.bilinear_interpolate(field, y, x) (navier_stokes.py:111-131; mode 0),
  * .interpolate_velocity_u(u, y, x) (:97-102; mode 1: x + 0.5 clamped to [0, w-1] first) and .interpolate_velocity_v(v, y, x)

@@ -25,6 +25,8 @@ elevation=... the ring is seen from above or below (physics.render_camera, "Free
 physics_perturbation_test is 2-D only.
 adversarial_test(..., simulate=FluidRollout(steps=k)) perturbs the INITIAL smoke of 2-D frames: the model sees the density after k steps of
 the stepper, and the gradient reaches the initial density through physics.fluid_step's adjoint kernels (csrc/fluid_grad.hip).
+adversarial_test(..., simulate=FluidRollout3D(steps=k)) does the same for volumes [B, 1, D, H, W] through physics.fluid_step3d
+(csrc/fluid_grad3d.hip): alone a volume model sees the evolved volume, with render= (and azimuth= / elevation=) an image model sees its render.
 """
 import numbers
 import warnings
@@ -163,19 +165,32 @@ class PerturbationTester:
         to the smoke a frame GREW OUT OF changes the model's answer.  The gradient reaches the initial smoke through the stepper's adjoint
         kernels (physics.fluid_step); the perturbation (and its norm) is the initial smoke's, the default comparison
         image the clean rollout.  Not together with render=.  A grid whose back-traces move a cell or more has no gradient on that route
-        (NaN): a non-finite perturbation after the loop raises.  None: the code path without it."""
+        (NaN): a non-finite perturbation after the loop raises.  None: the code path without it.
+        simulate: a physics.FluidRollout3D(steps=k, ...); test_data is then initial VOLUMES [B, 1, D, H, W] at rest (u = v = w = p = 0) and
+        the gradient reaches them through the 3-D stepper's adjoint kernels (physics.fluid_step3d).  Alone, the
+        model is a volume model (SmokePhysNet3D) that sees the evolved volume, and the default target is the front view of the clean
+        evolved volume (the 5-D rule above).  With render= (and azimuth= / elevation= as above) an image model sees the render of the
+        evolved volume; the perturbation (and its norm) is the initial volume's and the default comparison image is the clean rollout's
+        render from the same views.  The same one-cell limit and the same RuntimeError hold."""
         model.eval()
-        if simulate is not None and render is not None:
+        from ..physics.fluid_grad3d import FluidRollout3D
+        evolve = None                        # the 3-D rollout in front of whatever the model sees of a volume
+        if isinstance(simulate, FluidRollout3D):
+            if test_data.dim() != 5 or test_data.shape[1] != 1:
+                raise ValueError("adversarial_test: with simulate=FluidRollout3D(...), test_data must be initial volumes [B, 1, D, H, W]")
+            test_data = test_data.detach().float().contiguous()
+            evolve = lambda v: simulate(v[:, 0])[:, None]                       # noqa: E731
+        elif simulate is not None and render is not None:
             raise ValueError("adversarial_test: simulate= and render= are two different ways to what the model sees: give one")
         if azimuth is not None and render is None:
             raise ValueError("adversarial_test: azimuth= needs render=RenderSettings(...): it is the rendered volume that is seen from there")
         if elevation is not None and render is None:
             raise ValueError("adversarial_test: elevation= needs render=RenderSettings(...): it is the rendered volume that is seen from there")
         shown = lambda x: x                  # noqa: E731  what the model sees of the (perturbed) data
-        if simulate is not None:
+        if simulate is not None and evolve is None:
             from ..physics.fluid_grad import FluidRollout
             if not isinstance(simulate, FluidRollout):
-                raise TypeError("adversarial_test: simulate must be a physics.FluidRollout")
+                raise TypeError("adversarial_test: simulate must be a physics.FluidRollout or a physics.FluidRollout3D")
             if test_data.dim() != 4 or test_data.shape[1] != 1:
                 raise ValueError("adversarial_test: with simulate=, test_data must be initial densities [B, 1, H, W]")
             test_data = test_data.detach().float().contiguous()
@@ -199,9 +214,18 @@ class PerturbationTester:
             elif azimuth is not None:
                 from ..physics.render import render_orbit
                 shown = lambda v: render_orbit(v[:, 0], azimuth, render, differentiable=True).reshape(-1, 1, *hw)      # noqa: E731
+            if evolve is not None:
+                view = shown
+                shown = lambda v: view(evolve(v))                               # noqa: E731
             if target is None:
                 with torch.no_grad():
                     target = shown(test_data)
+        elif evolve is not None:
+            shown = evolve
+            if target is None:
+                from ..physics.render import render_volumes
+                with torch.no_grad():
+                    target = render_volumes(evolve(test_data)[:, 0].contiguous())[:, None]
         elif target is None:
             target = test_data
             if test_data.dim() == 5:
@@ -242,7 +266,7 @@ class PerturbationTester:
         if simulate is not None and not bool(torch.isfinite(delta).all()):
             raise RuntimeError("adversarial_test(simulate=): the perturbation is not finite.  The stepper's gradient on route='hip' holds "
                                "while every back-trace moves less than one cell (|dt * velocity| < 1); a grid past that one-cell limit "
-                               "gets NaN gradients.  Use a smaller dt or FluidRollout(route='torch').")
+                               "gets NaN gradients.  Use a smaller dt or FluidRollout(route='torch') / FluidRollout3D(route='torch').")
         with torch.no_grad():
             baseline = model(shown(test_data))
             adversarial_output = model(shown(torch.clamp(test_data + delta, 0, 1)))

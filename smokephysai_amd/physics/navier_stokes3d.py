@@ -69,6 +69,13 @@ class NavierStokesSimulator3D(nn.Module):
     p = property(lambda s: s._view(s._p, s.w_), lambda s, x: s._assign(s._p, s.w_, x))
     density = property(lambda s: s._view(s._density, s.w_), lambda s, x: s._assign(s._density, s.w_, x))
 
+    def state(self):
+        """Clones of (u, v, w, p, density) in the batched shapes [B, D, H+1, W], [B, D, H, W+1], [B, D+1, H, W], [B, D, H, W] twice
+        (B = 1 when un-batched): what physics.fluid_step3d takes."""
+        W = self.w_
+        return (self._u[..., :W].clone(), self._v[..., :W + 1].clone(), self._w[..., :W].clone(), self._p[..., :W].clone(),
+                self._density[..., :W].clone())
+
     def _st(self):
         return _lib.stream_ptr(self._dev)
 
