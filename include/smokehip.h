@@ -267,6 +267,39 @@ int smk_project_backward(const float *gu, const float *gv, const float *gp, floa
                          int64_t workspace_bytes, void *stream);
 int smk_buoy_diffuse_backward(const float *gu, const float *gv, const float *gd, float *du, float *dv, float *dd, int32_t B, int32_t H,
                               int32_t W, int32_t pitch_c, int32_t pitch_v, double dt, double viscosity, void *stream);
+/* The tangent-linear (forward-mode) counterpart of the three entry points above: J t beside the step, nothing saved.  Buoyancy, the
+ * diffusions and the projection are linear and homogeneous in the state, so their tangent is the stepper's own stage on the tangent state
+ * (smk_sim_run_stage on a simulator of B * T grids); only the advection needs a kernel.  Same derivative conventions as the adjoint (floor
+ * and integer casts have derivative 0, a clamp of a coordinate passes its tangent where lo <= x <= hi, bounds included, the weights'
+ * derivatives are those of the weights as written, formed from the clamped indices, so they cancel on the upper-edge quirk; dt is a
+ * constant).  Base buffers are [B] planes in the layout of smk_advect, tangent buffers [B][T] planes in the layout of their base field
+ * (tangent t of grid b is plane b * T + t), fp32, caller-owned, 4-byte aligned and no better, pitch_c >= W, pitch_v >= W + 1.  fp32 sums in
+ * one fixed order, no atomics, no LDS: bit-identical from call to call, a tangent's result independent of T and of its batch mates.  All
+ * work is enqueued on `stream`, nothing is allocated, no synchronisation.  B, T >= 1, B * T <= 65535, 3 <= H, W <= 32766.
+ *
+ * smk_advect_tangent: out = advection_step(field; u, v) of smk_advect (which = 0 / 1 / 2: field shaped like u / v / a cell field; 2: times
+ *   0.995, the density stage of step()); (tfield, tu, tv) the tangents of (field, u, v) -> tout, the tangent of out (field-shaped, [B][T]).
+ *   Per destination cell the back-trace, the clamp decisions, the taps (y0,x0), (y0,x1), (y1,x0), (y1,x1) and their weights wa..wd are the
+ *   forward's own, bit for bit, formed once; then per tangent, in this order:
+ *     r = ((wa tf[y0,x0] + wb tf[y0,x1]) + wc tf[y1,x0]) + wd tf[y1,x1];   r = r + sx * dpx;   r = r + sy * dpy;   (which = 2: r = r * 0.995)
+ *     sx = (fy1 - py)(f01 - f00) + (py - fy0)(f11 - f10),  sy = (fx1 - px)(f10 - f00) + (px - fx0)(f11 - f01)   (the interpolant's slopes)
+ *     dpx = -(dt * ui') where 0 <= X - dt ui <= columns - 1, else 0;  dpy likewise from Y - dt vi and vi';  ui', vi': the forward's velocity
+ *     samples of tu, tv at the fixed sample coordinates (same taps, weights and order as ui, vi).
+ *   Every element [row][col < columns] of tout is written (the pitch padding is left alone); tout aliases no input; tfield may be the same
+ *   buffer as tu or tv, as field may be u or v.  One launch.  A back-trace may move any number of cells: there is no far case, no far word.
+ * smk_tangent_renorm: per grid and tangent, norms[b * T + t] (fp64, 8-byte aligned) = the Euclidean norm of the whole tangent state
+ *   (tu [H+1][pitch_c], tv [H][pitch_v], tp, td [H][pitch_c]; four distinct buffers): each element converted to fp64 and squared there, the
+ *   squares summed in fp64 in one fixed order (two levels: runs of consecutive rows per workgroup, then the runs in ascending order), no
+ *   atomics.  The four fields are then divided in place by (float)norm with a true fp32 divide (the pitch padding is left alone); a norm
+ *   that is 0 or not finite (as fp64, or once converted to fp32) leaves that tangent unscaled and is reported as it is.  Two launches.
+ *   workspace: device memory of at least smk_tangent_renorm_workspace(B, T, H, W) bytes (-1 for an unsupported shape), 8-byte aligned,
+ *   contents unspecified afterwards. */
+int smk_advect_tangent(int32_t which, const float *field, const float *u, const float *v, const float *tfield, const float *tu,
+                       const float *tv, float *tout, int32_t B, int32_t T, int32_t H, int32_t W, int32_t pitch_c, int32_t pitch_v,
+                       double dt, void *stream);
+int64_t smk_tangent_renorm_workspace(int32_t B, int32_t T, int32_t H, int32_t W);
+int smk_tangent_renorm(float *tu, float *tv, float *tp, float *td, double *norms, int32_t B, int32_t T, int32_t H, int32_t W,
+                       int32_t pitch_c, int32_t pitch_v, void *workspace, int64_t workspace_bytes, void *stream);
 /* The adjoint of one 3-D step() (SPEC_3D.md sections 3-6) with respect to its state (u, v, w, p, density), stage by stage: the 3-D
  * counterpart of the three entry points above, with the same derivative conventions (floor and integer casts have derivative 0, a clamp
  * of a coordinate passes its gradient where lo <= x <= hi, bounds included, dt / viscosity / jacobi_iters are constants; the velocity

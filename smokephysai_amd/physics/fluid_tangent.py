@@ -1,0 +1,313 @@
+"""Tangent-linear 2-D fluid step: one NavierStokesSimulator.step() (navier_stokes.py:151-173) together with J t, the product of its
+Jacobian with respect to the whole state (u, v, p, density) and tangent states t, on libsmokehip (csrc/fluid_tangent.hip), and the
+Lyapunov exponents of the flow that come from it (Benettin's method).  DESIGN.md section 3.11.
+
+  fluid_step_jvp(state, tangents, ...)        one step -> (state', tangents'); route="hip": the stepper's own stage kernels for the state
+                                              (bit-identical to step()) and, on a stepper of B * T grids, for the tangents' linear stages
+                                              (buoyancy + diffusion, projection), then smk_advect_tangent three times; route="torch":
+                                              fluid_step_jvp_rule.
+  fluid_step_jvp_rule(state, tangents, ...)   torch.autograd.forward_ad over fluid_step_rule (any dtype and device): the tests' oracle.
+  fluid_tangent_rollout(state, tangents, n)   n chained fluid_step_jvp calls; nothing is saved between steps.
+  lyapunov_exponents(u, v, p, density, n)     the k largest Lyapunov exponents per unit time, with renormalisation every renorm_every
+                                              steps -> LyapunovResult(exponents [B, k], log_growth [B, n_renorms, k], state, tangents).
+
+Derivative conventions: fluid_grad's -- that of the expressions as written (floor and integer casts have derivative 0, a clamp of a
+coordinate passes its tangent where lo <= x <= hi, bounds included, the interpolation weights are formed from the clamped indices).
+Unlike fluid_step's backward the hip route has no one-cell limit: the tangent of the advection is a gather at the forward's own taps, so a
+back-trace may move any number of cells.
+
+Hot path and what is not: for k = 1 the renormalisation is smk_tangent_renorm (two launches, no host synchronisation; the norms stay on
+the device until the end).  For k > 1 the tangents are re-orthonormalised by modified Gram-Schmidt in plain torch operations with fp64
+coefficients: that part is NOT a hot path (k (k + 1) / 2 reductions and updates per renormalisation).
+
+Out of scope: torch.func.jvp / torch.autograd.forward_ad through fluid_step itself (call fluid_step_jvp), the 3-D step, and the dataset
+labels (the `lyapunov_exponent` of get_chaos_features() stays the reference's frame-difference proxy)."""
+from dataclasses import dataclass
+from typing import Optional, Tuple
+
+import torch
+import torch.autograd.forward_ad as fwad
+
+from .. import _lib
+from .fluid_grad import Branches, _check_state, _simulator, fluid_step_rule
+
+__all__ = ["LyapunovResult", "fluid_step_jvp", "fluid_step_jvp_rule", "fluid_tangent_rollout", "lyapunov_exponents"]
+
+MAX_K = 8
+MAX_PLANES = 65535          # B * T, the launch grid's reach (include/smokehip.h)
+
+
+# ------------------------------------------------------------------------------------------------ shapes
+def _check_tangents(state, tangents):
+    """-> T, or None where the tangents are state-shaped.  state: checked [B, ...] tensors."""
+    if len(tangents) != 4:
+        raise ValueError("fluid_step_jvp: tangents are (tu, tv, tp, tdensity)")
+    dims = {t.dim() - s.dim() for s, t in zip(state, tangents)}
+    if dims not in ({0}, {1}):
+        raise ValueError("fluid_step_jvp: tangents must all be state-shaped [B, ...] or all [B, T, ...]")
+    extra = dims.pop()
+    T = None if extra == 0 else int(tangents[0].shape[1])
+    for name, s, t in zip(("u", "v", "p", "density"), state, tangents):
+        want = tuple(s.shape) if T is None else (s.shape[0], T) + tuple(s.shape[1:])
+        if tuple(t.shape) != want:
+            raise ValueError(f"fluid_step_jvp: the tangent of {name} must be {want}, got {tuple(t.shape)}")
+    if T is not None and T < 1:
+        raise ValueError("fluid_step_jvp: T >= 1")
+    if state[3].shape[0] * (T or 1) > MAX_PLANES:
+        raise ValueError(f"fluid_step_jvp: B * T = {state[3].shape[0] * (T or 1)} exceeds {MAX_PLANES}")
+    return T
+
+
+def _batched(state, tangents):
+    """Un-batched states ([H, W]; tangents [H, W]-like or [T, ...]) get their leading 1 -> (state, tangents, was batched)."""
+    _check_state(*state)
+    if state[3].dim() == 3:
+        return tuple(state), tuple(tangents), True
+    return tuple(t[None] for t in state), tuple(t[None] for t in tangents), False
+
+
+# ------------------------------------------------------------------------------------------------ the rule: forward-mode AD of fluid_step_rule
+def fluid_step_jvp_rule(state, tangents, *, dt: float = 0.01, viscosity: float = 0.001, jacobi_iters: int = 20,
+                        branches: Optional[Branches] = None):
+    """(state', tangents') of one step by torch.autograd.forward_ad over fluid_step_rule: any floating dtype, any device.  state
+    (u, v, p, density) with leading dimensions [B] (or none); tangents state-shaped, or [B, T, ...]: then the state is expanded along T and
+    one pass carries all T tangents (a Branches recorder then holds decisions of that expanded shape).  branches: as fluid_step_rule's."""
+    state, tangents, batched = _batched(state, tangents)
+    T = _check_tangents(state, tangents)
+    if T is not None:
+        state = tuple(s[:, None].expand(s.shape[0], T, *s.shape[1:]).contiguous() for s in state)
+    with fwad.dual_level():
+        duals = [fwad.make_dual(s.detach(), t.detach().to(s.dtype)) for s, t in zip(state, tangents)]
+        outs = fluid_step_rule(*duals, dt=dt, viscosity=viscosity, jacobi_iters=jacobi_iters, branches=branches)
+        new, tan = [], []
+        for o in outs:
+            primal, tangent = fwad.unpack_dual(o)
+            new.append(primal.detach())
+            tan.append(torch.zeros_like(primal) if tangent is None else tangent.detach())
+    if T is not None:
+        new = [s[:, 0] for s in new]
+    if not batched:
+        new, tan = [s[0] for s in new], [t[0] for t in tan]
+    return tuple(new), tuple(tan)
+
+
+# ------------------------------------------------------------------------------------------------ the hip route
+def _advect_tangent(L, st, which, field, u, v, tfield, tu, tv, B, T, H, W, dt):
+    out = torch.empty_like(tfield)
+    _lib.check(L.smk_advect_tangent(which, field.data_ptr(), u.data_ptr(), v.data_ptr(), tfield.data_ptr(), tu.data_ptr(), tv.data_ptr(),
+                                    out.data_ptr(), B, T, H, W, W, W + 1, dt, st))
+    return out
+
+
+def _hip_step(state, tangents, T, dt, viscosity, jacobi_iters):
+    """state [B, ...], tangents [B * T, ...] (fp32, on one ROCm device) -> (state', tangents' [B * T, ...])."""
+    B, H, W = state[3].shape
+    dev = state[3].device
+    L = _lib.load()
+    with torch.cuda.device(dev):
+        st = _lib.stream_ptr(dev)
+        # the base state, stage by stage as fluid_step's forward runs it (bit-identical to step()); a timed-out persistent projection is
+        # reported as step() reports it, here and for the tangents below
+        sim = _simulator(B, H, W, dt, viscosity, jacobi_iters, dev)
+        sim.u, sim.v, sim.p, sim.density = state
+        sim.run_stage(_lib.STAGE_BUOY_DIFFUSE)
+        sim.run_stage(_lib.STAGE_PROJECT)
+        u_p, v_p, d_d = sim.u.clone(), sim.v.clone(), sim.density.clone()
+        sim.run_stage(_lib.STAGE_ADVECT_U)
+        sim.run_stage(_lib.STAGE_ADVECT_V)
+        sim.run_stage(_lib.STAGE_ADVECT_D)
+        u_a, v_a, p_n, d_n = sim.state()
+        # the tangents' linear stages: the same kernels on a stepper of B * T grids (buoyancy, diffusion and projection are linear and
+        # homogeneous in (u, v, p, density), so their tangent is themselves, with the same rounding)
+        tsim = _simulator(B * T, H, W, dt, viscosity, jacobi_iters, dev)
+        tsim.u, tsim.v, tsim.p, tsim.density = tangents
+        tsim.run_stage(_lib.STAGE_BUOY_DIFFUSE)
+        tsim.run_stage(_lib.STAGE_PROJECT)
+        tu_p, tv_p, tp_n, td_d = tsim.state()
+        # the three advections with the forward's operand wiring: u_a <- (u_p; u_p, v_p), v_a <- (v_p; u_a, v_p), density <- (d_d; u_a, v_a)
+        tu_a = _advect_tangent(L, st, 0, u_p, u_p, v_p, tu_p, tu_p, tv_p, B, T, H, W, dt)
+        tv_a = _advect_tangent(L, st, 1, v_p, u_a, v_p, tv_p, tu_a, tv_p, B, T, H, W, dt)
+        td_n = _advect_tangent(L, st, 2, d_d, u_a, v_a, td_d, tu_a, tv_a, B, T, H, W, dt)
+    return (u_a, v_a, p_n, d_n), (tu_a, tv_a, tp_n, td_n)
+
+
+def _check_hip(state, tangents, jacobi_iters, what):
+    _lib.require_cuda(state[3].device, f"{what}(route='hip')")
+    for t in tuple(state) + tuple(tangents):
+        if t.dtype != torch.float32 or t.device != state[3].device:
+            raise ValueError(f"{what}(route='hip'): the state and the tangents must be float32 tensors on one device")
+    if int(jacobi_iters) < 0:
+        raise ValueError(f"{what}: jacobi_iters >= 0")
+
+
+def fluid_step_jvp(state, tangents, *, dt: float = 0.01, viscosity: float = 0.001, jacobi_iters: int = 20, route: str = "hip"):
+    """One NavierStokesSimulator.step() with the tangent-linear step beside it -> ((u, v, p, density)', (tu, tv, tp, tdensity)').
+    state: u [B, H+1, W], v [B, H, W+1], p, density [B, H, W] (or without the B); tangents: state-shaped, or [B, T, ...] for T tangents
+    per grid.  route="hip": fp32 ROCm tensors; the returned state is bit-identical to step() on the same state; nothing is saved; no
+    one-cell limit.  route="torch": fluid_step_jvp_rule, any dtype and device.  Not differentiable itself (outputs carry no graph)."""
+    if route == "torch":
+        return fluid_step_jvp_rule(state, tangents, dt=dt, viscosity=viscosity, jacobi_iters=jacobi_iters)
+    if route != "hip":
+        raise ValueError(f"fluid_step_jvp: route is 'hip' or 'torch', got {route!r}")
+    state, tangents, batched = _batched(state, tangents)
+    T = _check_tangents(state, tangents)
+    _check_hip(state, tangents, jacobi_iters, "fluid_step_jvp")
+    with torch.no_grad():
+        flat = tuple(t.reshape(-1, *t.shape[-2:]) for t in tangents)
+        new, tan = _hip_step(state, flat, T or 1, float(dt), float(viscosity), int(jacobi_iters))
+    tan = tuple(t.view(x.shape) for t, x in zip(tan, tangents))
+    if not batched:
+        new, tan = tuple(s[0] for s in new), tuple(t[0] for t in tan)
+    return new, tan
+
+
+def fluid_tangent_rollout(state, tangents, n_steps: int, **settings):
+    """n_steps chained fluid_step_jvp calls -> (state, tangents) after the last.  settings: fluid_step_jvp's keywords.  Nothing is kept
+    between steps, so memory does not grow with n_steps; the tangents are not renormalised (lyapunov_exponents does that)."""
+    if n_steps < 1:
+        raise ValueError("fluid_tangent_rollout: n_steps >= 1")
+    for _ in range(n_steps):
+        state, tangents = fluid_step_jvp(state, tangents, **settings)
+    return state, tangents
+
+
+# ------------------------------------------------------------------------------------------------ Lyapunov exponents (Benettin)
+@dataclass
+class LyapunovResult:
+    """exponents [B, k] fp64, per unit time: sum of log_growth / (n_steps * dt), largest first for k > 1 (Gram-Schmidt order).
+    log_growth [B, n_renorms, k] fp64: the log of each tangent's norm at each renormalisation.  state: (u, v, p, density) after the last
+    step; tangents: the k unit (k > 1: orthonormal) tangent states [B, k, ...] after the last renormalisation."""
+    exponents: torch.Tensor
+    log_growth: torch.Tensor
+    state: Tuple[torch.Tensor, ...]
+    tangents: Tuple[torch.Tensor, ...]
+
+
+def _dot64(a, b):
+    """<a, b> over whole states [B, ...] in fp64 -> [B]."""
+    return sum((x.double() * y.double()).flatten(1).sum(dim=1) for x, y in zip(a, b))
+
+
+def _gram_schmidt(tangents):
+    """Modified Gram-Schmidt over the k tangent states [B, k, ...] with fp64 coefficients -> (orthonormal tangents, norms [B, k] fp64):
+    vector j loses its components along the finished vectors 0 .. j-1 one after another, the norm of what remains is its growth.  A zero
+    or non-finite remainder is left unscaled.  Plain torch operations: not a hot path."""
+    k = tangents[0].shape[1]
+    done, norms = [], []
+    for j in range(k):
+        vec = [t[:, j] for t in tangents]
+        for q in done:
+            c = _dot64(q, vec)
+            vec = [x - c.to(x.dtype)[:, None, None] * y for x, y in zip(vec, q)]
+        n = _dot64(vec, vec).sqrt()
+        norms.append(n)
+        ok = (n > 0) & torch.isfinite(n)
+        div = torch.where(ok, n, torch.ones_like(n))
+        done.append([x / div.to(x.dtype)[:, None, None] for x in vec])
+    return tuple(torch.stack([q[i] for q in done], dim=1) for i in range(4)), torch.stack(norms, dim=1)
+
+
+def _renorm_torch(tangents):
+    """k = 1 in torch ops, as smk_tangent_renorm does it: fp64 norm of the whole state, a divide by the norm in the tangents' dtype."""
+    n = _dot64([t[:, 0] for t in tangents], [t[:, 0] for t in tangents]).sqrt()
+    ok = (n > 0) & torch.isfinite(n)
+    div = torch.where(ok, n, torch.ones_like(n))
+    return tuple(t / div.to(t.dtype)[:, None, None, None] for t in tangents), n[:, None]
+
+
+class _HipRenorm:
+    """smk_tangent_renorm on tangents [B, 1, ...] in place, its workspace allocated once."""
+
+    def __init__(self, B, T, H, W, dev):
+        self.L, self.dims, self.dev = _lib.load(), (B, T, H, W), dev
+        self.nbytes = int(self.L.smk_tangent_renorm_workspace(B, T, H, W))
+        if self.nbytes < 0:
+            raise ValueError(f"lyapunov_exponents: B={B}, k={T}, grid {H} x {W} is not supported (B * k <= {MAX_PLANES}, 3 <= H, W <= 32766)")
+        self.ws = torch.empty(self.nbytes // 8, dtype=torch.float64, device=dev)
+
+    def __call__(self, tangents, norms):
+        B, T, H, W = self.dims
+        tangents = tuple(t if t.is_contiguous() else t.contiguous() for t in tangents)
+        with torch.cuda.device(self.dev):
+            _lib.check(self.L.smk_tangent_renorm(*[t.data_ptr() for t in tangents], norms.data_ptr(), B, T, H, W, W, W + 1,
+                                                 self.ws.data_ptr(), self.nbytes, _lib.stream_ptr(self.dev)))
+        return tangents
+
+
+def _draw_tangent0(state, k, seed):
+    """Unit-normal noise for every field, drawn on the CPU from `seed` and copied: independent of the device's generator."""
+    g = torch.Generator().manual_seed(int(seed))
+    return tuple(torch.randn(s.shape[0], k, *s.shape[1:], generator=g, dtype=torch.float32).to(device=s.device, dtype=s.dtype) for s in state)
+
+
+def lyapunov_exponents(u, v, p, density, n_steps: int, *, k: int = 1, renorm_every: int = 1, tangent0=None, seed: int = 0,
+                       dt: float = 0.01, viscosity: float = 0.001, jacobi_iters: int = 20, route: str = "hip",
+                       branches: Optional[Branches] = None) -> LyapunovResult:
+    """The k largest Lyapunov exponents of the flow from the state (u, v, p, density), by Benettin's method: k tangent states are pushed
+    through n_steps tangent-linear steps (fluid_step_jvp) beside the state and renormalised every renorm_every steps (n_steps must be a
+    multiple); the exponents are the summed logs of the growth factors per unit time, n_steps * dt.  k = 1: smk_tangent_renorm on the
+    hip route.  1 < k <= 8: modified Gram-Schmidt in torch operations with fp64 coefficients (module docstring: not a hot path).
+    tangent0: (tu, tv, tp, tdensity), state-shaped (k = 1) or [B, k, ...]; default: unit-normal noise drawn on the CPU from `seed`.  It is
+    normalised (orthonormalised) first, so its scale does not matter.  route="torch": the rule, any dtype and device; branches: a
+    Branches recorder / replayer handed to every step of that route (the tests' fp64 run along the fp32 run's decisions).
+    The hip route synchronises once, at the end, to check the steppers' status."""
+    if route not in ("hip", "torch"):
+        raise ValueError(f"lyapunov_exponents: route is 'hip' or 'torch', got {route!r}")
+    if not 1 <= int(k) <= MAX_K:
+        raise ValueError(f"lyapunov_exponents: 1 <= k <= {MAX_K}, got {k}")
+    if n_steps < 1 or renorm_every < 1 or n_steps % renorm_every:
+        raise ValueError("lyapunov_exponents: n_steps >= 1 and a multiple of renorm_every >= 1")
+    if branches is not None and route != "torch":
+        raise ValueError("lyapunov_exponents: branches goes with route='torch'")
+    k = int(k)
+    _check_state(u, v, p, density)
+    batched = density.dim() == 3
+    state = (u, v, p, density) if batched else tuple(t[None] for t in (u, v, p, density))
+    state = tuple(t.detach() for t in state)
+    B, H, W = state[3].shape
+    if tangent0 is None:
+        tangents = _draw_tangent0(state, k, seed)
+    else:
+        tangents = tuple(t.detach() if batched else t.detach()[None] for t in tangent0)
+        if len(tangents) == 4 and all(t.dim() == s.dim() for t, s in zip(tangents, state)):
+            tangents = tuple(t[:, None] for t in tangents)
+        if _check_tangents(state, tangents) != k:
+            raise ValueError(f"lyapunov_exponents: tangent0 must hold k = {k} tangents per grid")
+        tangents = tuple(t.clone() for t in tangents)
+    settings = dict(dt=dt, viscosity=viscosity, jacobi_iters=jacobi_iters)
+    n_renorms = n_steps // renorm_every
+    hip = route == "hip"
+    if hip:
+        _check_hip(state, tangents, jacobi_iters, "lyapunov_exponents")
+    norms = torch.empty(n_renorms + 1, B, k, dtype=torch.float64, device=state[3].device)
+    if k > 1:
+        def renorm(ts, i):
+            ts, norms[i] = _gram_schmidt(ts)
+            return ts
+    elif hip:
+        hip_renorm = _HipRenorm(B, 1, H, W, state[3].device)
+
+        def renorm(ts, i):
+            return hip_renorm(ts, norms[i])
+    else:
+        def renorm(ts, i):
+            ts, norms[i] = _renorm_torch(ts)
+            return ts
+    with torch.no_grad():
+        tangents = renorm(tangents, 0)                       # (the initial scale: not a growth factor)
+        for i in range(n_renorms):
+            for _ in range(renorm_every):
+                if hip:
+                    state, tangents = fluid_step_jvp(state, tangents, route="hip", **settings)
+                else:
+                    state, tangents = fluid_step_jvp_rule(state, tangents, branches=branches, **settings)
+            tangents = renorm(tangents, i + 1)
+    if hip:                                                  # the frames leave the steppers: a timed-out projection is reported here
+        for batch in sorted({B, B * k}):
+            _simulator(batch, H, W, dt, viscosity, jacobi_iters, state[3].device).check()
+    log_growth = norms[1:].log().permute(1, 0, 2).contiguous()
+    exponents = log_growth.sum(dim=1) / (n_steps * float(dt))
+    if not batched:
+        state, tangents = tuple(s[0] for s in state), tuple(t[0] for t in tangents)
+        exponents, log_growth = exponents[0], log_growth[0]
+    return LyapunovResult(exponents, log_growth, tuple(state), tuple(tangents))

@@ -101,6 +101,19 @@ class SmokeSimulator(nn.Module):
         feats = chaos_features_device(norms, box, hist, *self._feature_rows[key])
         return feats if self.batch_size is not None else feats[0]
 
+    def flow_lyapunov(self, n_steps: int = 20, **kw):
+        """The largest Lyapunov exponent of the flow per unit time from the simulator's CURRENT state: physics.lyapunov_exponents
+        (Benettin's method on the tangent-linear step) over n_steps further steps, run on clones -- the
+        simulator, its history and get_chaos_features() (whose `lyapunov_exponent` stays the reference's frame-difference proxy) are
+        untouched.  kw: lyapunov_exponents' keywords (renorm_every, seed, route, tangent0 in the batched
+        shapes of ns_solver.state(), B = 1 when un-batched); k is 1.  A float when un-batched, an fp64
+        tensor [B] when batched."""
+        from .fluid_tangent import lyapunov_exponents
+        ns = self.ns_solver
+        ns.check()
+        res = lyapunov_exponents(*ns.state(), n_steps, k=1, dt=ns.dt, viscosity=ns.viscosity, jacobi_iters=ns.jacobi_iters, **kw)
+        return res.exponents[:, 0] if self.batch_size is not None else float(res.exponents[0, 0])
+
     def _single_grid(self, what):
         if self.batch_size is not None:
             raise ValueError(f"{what}: batched simulator -- use get_chaos_features(), which returns one dict per grid")
