@@ -28,6 +28,13 @@
 namespace smk {
 static thread_local std::string g_err;
 void set_error(const std::string &msg) { g_err = msg; }
+int check_launch(hipError_t e, const char *what) {
+    if (e != hipSuccess) {
+        set_error(std::string(what) + ": " + hipGetErrorString(e));
+        return SMK_ERR_HIP;
+    }
+    return SMK_OK;
+}
 
 namespace {
 std::mutex g_dev_mu;
@@ -149,14 +156,6 @@ struct DeviceGuard {
     DeviceGuard(const DeviceGuard &) = delete;
     DeviceGuard &operator=(const DeviceGuard &) = delete;
 };
-
-int check_launch(hipError_t e, const char *what) {
-    if (e != hipSuccess) {
-        set_error(std::string(what) + ": " + hipGetErrorString(e));
-        return SMK_ERR_HIP;
-    }
-    return SMK_OK;
-}
 
 int report_timeout() {
     set_error("persistent projection: a band waited longer than 0.5 s for its neighbour's hand-off (its workgroups were not all "

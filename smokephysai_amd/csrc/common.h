@@ -10,6 +10,8 @@
 namespace smk {
 
 void set_error(const std::string &msg);
+// An entry point's return value from its launches' status: SMK_OK, or SMK_ERR_HIP with "<what>: <HIP's message>" as the error text.
+int check_launch(hipError_t e, const char *what);
 
 #define SMK_HIP_TRY(expr)                                                                         \
     do {                                                                                          \

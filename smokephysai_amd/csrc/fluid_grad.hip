@@ -3,57 +3,14 @@
 //
 // Arithmetic rules (the project's gradient rules): fp32 throughout, every sum in one fixed order, no atomics, every output element written,
 // results bit-identical from call to call and independent of a grid's batch mates.  The back-trace positions, indices, clamp decisions and
-// weights are formed by the forward's own expressions (csrc/stencil.hip: bilinear, k_advect; the build keeps -ffp-contract=off), so they
-// are the forward's bit for bit and the backward is the transpose of what the forward used.
+// weights are formed by the forward's own expressions (csrc/fluid_trace.h, shared with csrc/fluid_tangent.hip), so they are the forward's
+// bit for bit and the backward is the transpose of what the forward used.
 #include "fluid_grad.h"
-
-#include <math.h>
+#include "fluid_trace.h"
 
 namespace smk {
 
 namespace {
-
-__device__ __forceinline__ float fg_clampf(float x, float lo, float hi) {
-    float t = x < lo ? lo : x;   // torch.clamp = min(max(x, lo), hi)
-    return t > hi ? hi : t;
-}
-__device__ __forceinline__ int fg_clampi(int x, int lo, int hi) {
-    int t = x < lo ? lo : x;
-    return t > hi ? hi : t;
-}
-
-// bilinear_interpolate's taps and weights (navier_stokes.py:111-131) exactly as csrc/stencil.hip's bilinear() forms them.
-struct Taps {
-    int x0, x1, y0, y1;
-    float wa, wb, wc, wd;        // weights of (y0,x0), (y0,x1), (y1,x0), (y1,x1)
-    float fx0, fx1, fy0, fy1;
-};
-__device__ __forceinline__ Taps taps_at(int h, int w, float y, float x) {
-    Taps t;
-    int x0 = (int)floorf(x), y0 = (int)floorf(y);
-    int x1 = x0 + 1, y1 = y0 + 1;
-    t.x0 = fg_clampi(x0, 0, w - 1); t.x1 = fg_clampi(x1, 0, w - 1);
-    t.y0 = fg_clampi(y0, 0, h - 1); t.y1 = fg_clampi(y1, 0, h - 1);
-    t.fx0 = (float)t.x0; t.fx1 = (float)t.x1; t.fy0 = (float)t.y0; t.fy1 = (float)t.y1;
-    t.wa = (t.fx1 - x) * (t.fy1 - y);
-    t.wb = (x - t.fx0) * (t.fy1 - y);
-    t.wc = (t.fx1 - x) * (y - t.fy0);
-    t.wd = (x - t.fx0) * (y - t.fy0);
-    return t;
-}
-__device__ __forceinline__ float gather(const float *f, int pitch, const Taps &t) {
-    float r = t.wa * f[(size_t)t.y0 * pitch + t.x0] + t.wb * f[(size_t)t.y0 * pitch + t.x1];
-    r = r + t.wc * f[(size_t)t.y1 * pitch + t.x0];
-    r = r + t.wd * f[(size_t)t.y1 * pitch + t.x1];
-    return r;
-}
-// interpolate_velocity_u at the cell (Y, X) (navier_stokes.py:97-102): taps of u [H+1][W] at (Y, clamp(X + 0.5)); _v likewise (:104-109).
-__device__ __forceinline__ Taps u_sample_taps(const Geom &g, int Y, int X) {
-    return taps_at(g.H + 1, g.W, (float)Y, fg_clampf((float)X + 0.5f, 0.f, (float)(g.W - 1)));
-}
-__device__ __forceinline__ Taps v_sample_taps(const Geom &g, int Y, int X) {
-    return taps_at(g.H, g.W + 1, fg_clampf((float)Y + 0.5f, 0.f, (float)(g.H - 1)), (float)X);
-}
 
 // ---------------------------------------------------------------- advection backward
 // out = adv(f; u, v).  A workgroup owns a FG_TY x FG_TX tile of SOURCE cells of the union domain [H+1][W+1] (it holds u [H+1][W], v [H][W+1]
@@ -85,24 +42,14 @@ __global__ __launch_bounds__(FG_NT) void k_advect_backward(Geom g, const float *
         float w0 = 0.f, w1 = 0.f, w2 = 0.f, w3 = 0.f, tx = 0.f, ty = 0.f;
         int xs = -1, ys = -1;
         if (Y >= 0 && Y < R && X >= 0 && X < C) {
-            const float fY = (float)Y, fX = (float)X;
-            const float ui = gather(ub, g.pc, u_sample_taps(g, Y, X));
-            const float vi = gather(vb, g.pv, v_sample_taps(g, Y, X));
-            const float pxu = fX - g.dt * ui, pyu = fY - g.dt * vi;             // :87-92, before the clamp
-            const float hx = (float)(C - 1), hy = (float)(R - 1);
-            const float px = fg_clampf(pxu, 0.f, hx), py = fg_clampf(pyu, 0.f, hy);
-            if (!(fabsf(pxu - fX) < 1.0f) || !(fabsf(pyu - fY) < 1.0f)) far[b] = 1;   // (NaN included; every writer stores the same 1)
-            const Taps t = taps_at(R, C, py, px);
-            const float f00 = fb[(size_t)t.y0 * pitch + t.x0], f01 = fb[(size_t)t.y0 * pitch + t.x1];
-            const float f10 = fb[(size_t)t.y1 * pitch + t.x0], f11 = fb[(size_t)t.y1 * pitch + t.x1];
+            const Trace tr = trace_at(g, R, C, pitch, ub, vb, fb, Y, X);
+            if (!(fabsf(tr.pxu - (float)X) < 1.0f) || !(fabsf(tr.pyu - (float)Y) < 1.0f)) far[b] = 1;   // (NaN included; every writer stores the same 1)
+            const Taps &t = tr.t;
             float gi = gb[(size_t)Y * pitch + X];
             if (WHICH == 2) gi = gi * 0.995f;                                   // :171
             w0 = gi * t.wa; w1 = gi * t.wb; w2 = gi * t.wc; w3 = gi * t.wd;
-            const float sx = (t.fy1 - py) * (f01 - f00) + (py - t.fy0) * (f11 - f10);
-            const float sy = (t.fx1 - px) * (f10 - f00) + (px - t.fx0) * (f11 - f01);
-            // clamp passes its gradient where lo <= x <= hi, bounds included (torch's convention)
-            const float gpx = (pxu >= 0.f && pxu <= hx) ? gi * sx : 0.f;
-            const float gpy = (pyu >= 0.f && pyu <= hy) ? gi * sy : 0.f;
+            const float gpx = tr.pass_x ? gi * tr.sx : 0.f;
+            const float gpy = tr.pass_y ? gi * tr.sy : 0.f;
             tx = -(g.dt * gpx); ty = -(g.dt * gpy);
             xs = t.x0 | (t.x1 << 16); ys = t.y0 | (t.y1 << 16);
         }
@@ -333,29 +280,8 @@ using namespace smk;
 
 namespace {
 
-int fg_status(hipError_t e, const char *what) {
-    if (e != hipSuccess) {
-        set_error(std::string(what) + ": " + hipGetErrorString(e));
-        return SMK_ERR_HIP;
-    }
-    return SMK_OK;
-}
-
-// Shapes every entry point of this file takes: what NavierStokesSimulator takes, within the launch grid's and the tap packing's reach.
-bool fg_shape_ok(int32_t B, int32_t H, int32_t W, int32_t pitch_c, int32_t pitch_v) {
-    return B >= 1 && B <= 65535 && H >= 3 && W >= 3 && H <= 32766 && W <= 32766 && pitch_c >= W && pitch_v >= W + 1;
-}
+// Shapes every entry point of this file takes: fluid_trace.h's.
 const char *const FG_SHAPE = "1 <= B <= 65535, 3 <= H, W <= 32766, pitch_c >= W, pitch_v >= W + 1";
-
-Geom fg_geom(int32_t B, int32_t H, int32_t W, int32_t pitch_c, int32_t pitch_v, double dt, double viscosity) {
-    Geom g{};
-    g.B = B; g.H = H; g.W = W; g.pc = pitch_c; g.pv = pitch_v;
-    g.su = (size_t)(H + 1) * pitch_c; g.sv = (size_t)H * pitch_v; g.sc = (size_t)H * pitch_c;
-    g.dt = (float)dt;
-    g.coef_uv = (float)(dt * viscosity);
-    g.coef_d = (float)(dt * (viscosity * 0.1));
-    return g;
-}
 
 }  // namespace
 
@@ -367,16 +293,16 @@ int smk_advect_backward(int32_t which, const float *field, const float *u, const
                         void *stream) {
     SMK_REQUIRE(field && u && v && gout && dfield && du && dv && far, "advect_backward: null pointer");
     SMK_REQUIRE(which >= 0 && which <= 2, "advect_backward: which in 0..2");
-    SMK_REQUIRE(fg_shape_ok(B, H, W, pitch_c, pitch_v), FG_SHAPE);
+    SMK_REQUIRE(fluid2d_shape_ok(B, H, W, pitch_c, pitch_v), FG_SHAPE);
     SMK_REQUIRE(dfield != field && dfield != gout && dfield != u && dfield != v && du != u && du != field && du != gout && dv != v &&
                     dv != field && dv != gout && dfield != du && dfield != dv && du != dv,
                 "advect_backward: an output aliases an input or another output");
-    const Geom g = fg_geom(B, H, W, pitch_c, pitch_v, dt, 0.0);
-    return fg_status(launch_advect_backward(g, which, field, u, v, gout, dfield, du, dv, far, (hipStream_t)stream), "advect_backward");
+    const Geom g = fluid2d_geom(B, H, W, pitch_c, pitch_v, dt, 0.0);
+    return check_launch(launch_advect_backward(g, which, field, u, v, gout, dfield, du, dv, far, (hipStream_t)stream), "advect_backward");
 }
 
 int64_t smk_project_backward_workspace(int32_t B, int32_t H, int32_t W) {
-    if (!fg_shape_ok(B, H, W, W, W + 1)) return -1;
+    if (!fluid2d_shape_ok(B, H, W, W, W + 1)) return -1;
     return (int64_t)3 * B * H * W * (int64_t)sizeof(float);
 }
 
@@ -384,25 +310,25 @@ int smk_project_backward(const float *gu, const float *gv, const float *gp, floa
                          int32_t W, int32_t pitch_c, int32_t pitch_v, int32_t jacobi_iters, double dt, void *workspace,
                          int64_t workspace_bytes, void *stream) {
     SMK_REQUIRE(gu && gv && gp && du && dv && dp, "project_backward: null pointer");
-    SMK_REQUIRE(fg_shape_ok(B, H, W, pitch_c, pitch_v), FG_SHAPE);
+    SMK_REQUIRE(fluid2d_shape_ok(B, H, W, pitch_c, pitch_v), FG_SHAPE);
     SMK_REQUIRE(jacobi_iters >= 0, "project_backward: jacobi_iters >= 0");
     SMK_REQUIRE(dt != 0.0, "project_backward: dt != 0");
     SMK_REQUIRE(du != gu && dv != gv && dp != gp, "project_backward: an output aliases its input");
     SMK_REQUIRE(workspace && workspace_bytes >= smk_project_backward_workspace(B, H, W),
                 "project_backward: workspace smaller than smk_project_backward_workspace(B, H, W) bytes");
     SMK_REQUIRE(((uintptr_t)workspace & 3) == 0, "project_backward: workspace must be 4-byte aligned");
-    const Geom g = fg_geom(B, H, W, pitch_c, pitch_v, dt, 0.0);
-    return fg_status(launch_project_backward(g, gu, gv, gp, du, dv, dp, jacobi_iters, (float *)workspace, (hipStream_t)stream),
+    const Geom g = fluid2d_geom(B, H, W, pitch_c, pitch_v, dt, 0.0);
+    return check_launch(launch_project_backward(g, gu, gv, gp, du, dv, dp, jacobi_iters, (float *)workspace, (hipStream_t)stream),
                      "project_backward");
 }
 
 int smk_buoy_diffuse_backward(const float *gu, const float *gv, const float *gd, float *du, float *dv, float *dd, int32_t B, int32_t H,
                               int32_t W, int32_t pitch_c, int32_t pitch_v, double dt, double viscosity, void *stream) {
     SMK_REQUIRE(gu && gv && gd && du && dv && dd, "buoy_diffuse_backward: null pointer");
-    SMK_REQUIRE(fg_shape_ok(B, H, W, pitch_c, pitch_v), FG_SHAPE);
+    SMK_REQUIRE(fluid2d_shape_ok(B, H, W, pitch_c, pitch_v), FG_SHAPE);
     SMK_REQUIRE(du != gu && dv != gv && dd != gd, "buoy_diffuse_backward: an output aliases its input");
-    const Geom g = fg_geom(B, H, W, pitch_c, pitch_v, dt, viscosity);
-    return fg_status(launch_buoy_diffuse_backward(g, gu, gv, gd, du, dv, dd, (hipStream_t)stream), "buoy_diffuse_backward");
+    const Geom g = fluid2d_geom(B, H, W, pitch_c, pitch_v, dt, viscosity);
+    return check_launch(launch_buoy_diffuse_backward(g, gu, gv, gd, du, dv, dd, (hipStream_t)stream), "buoy_diffuse_backward");
 }
 
 }  // extern "C"

@@ -399,14 +399,6 @@ using namespace smk;
 
 namespace {
 
-int fg3_status(hipError_t e, const char *what) {
-    if (e != hipSuccess) {
-        set_error(std::string(what) + ": " + hipGetErrorString(e));
-        return SMK_ERR_HIP;
-    }
-    return SMK_OK;
-}
-
 // Shapes every entry point of this file takes: smk_sim3d_create's, within the tap packing's reach.
 bool fg3_shape_ok(int32_t B, int32_t D, int32_t H, int32_t W, int32_t pitch_c, int32_t pitch_v) {
     return B >= 1 && D >= 3 && H >= 3 && W >= 3 && D <= 32766 && H <= 32766 && W <= 32766 && pitch_c >= W && pitch_v >= W + 1 &&
@@ -447,8 +439,8 @@ int smk_advect3d_backward(int32_t which, const float *field, const float *u, con
     }
     SMK_REQUIRE(!alias, "advect3d_backward: an output aliases an input or another output");
     const Geom3 g = fg3_geom(B, D, H, W, pitch_c, pitch_v, dt, 0.0);
-    return fg3_status(launch3_advect_backward(g, which, field, u, v, w, gout, dfield, du, dv, dw, far, (hipStream_t)stream),
-                      "advect3d_backward");
+    return check_launch(launch3_advect_backward(g, which, field, u, v, w, gout, dfield, du, dv, dw, far, (hipStream_t)stream),
+                        "advect3d_backward");
 }
 
 int64_t smk_project3d_backward_workspace(int32_t B, int32_t D, int32_t H, int32_t W) {
@@ -468,8 +460,8 @@ int smk_project3d_backward(const float *gu, const float *gv, const float *gw, co
                 "project3d_backward: workspace smaller than smk_project3d_backward_workspace(B, D, H, W) bytes");
     SMK_REQUIRE(((uintptr_t)workspace & 3) == 0, "project3d_backward: workspace must be 4-byte aligned");
     const Geom3 g = fg3_geom(B, D, H, W, pitch_c, pitch_v, dt, 0.0);
-    return fg3_status(launch3_project_backward(g, gu, gv, gw, gp, du, dv, dw, dp, jacobi_iters, (float *)workspace, (hipStream_t)stream),
-                      "project3d_backward");
+    return check_launch(launch3_project_backward(g, gu, gv, gw, gp, du, dv, dw, dp, jacobi_iters, (float *)workspace, (hipStream_t)stream),
+                        "project3d_backward");
 }
 
 int smk_buoy_diffuse3d_backward(const float *gu, const float *gv, const float *gw, const float *gd, float *du, float *dv, float *dw,
@@ -479,7 +471,7 @@ int smk_buoy_diffuse3d_backward(const float *gu, const float *gv, const float *g
     SMK_REQUIRE(fg3_shape_ok(B, D, H, W, pitch_c, pitch_v), FG3_SHAPE);
     SMK_REQUIRE(du != gu && dv != gv && dw != gw && dd != gd, "buoy_diffuse3d_backward: an output aliases its input");
     const Geom3 g = fg3_geom(B, D, H, W, pitch_c, pitch_v, dt, viscosity);
-    return fg3_status(launch3_buoy_diffuse_backward(g, gu, gv, gw, gd, du, dv, dw, dd, (hipStream_t)stream), "buoy_diffuse3d_backward");
+    return check_launch(launch3_buoy_diffuse_backward(g, gu, gv, gw, gd, du, dv, dw, dd, (hipStream_t)stream), "buoy_diffuse3d_backward");
 }
 
 }  // extern "C"

@@ -7,54 +7,14 @@
 //
 // Arithmetic rules (the project's gradient rules): fp32 throughout, every sum in one fixed order, no atomics, every output element written,
 // results bit-identical from call to call and independent of T and of a grid's batch mates.  The back-trace positions, indices, clamp
-// decisions and weights are formed by the forward's own expressions (csrc/stencil.hip: bilinear, k_advect; the build keeps
-// -ffp-contract=off), the convention of csrc/fluid_grad.hip, so they are the forward's bit for bit.
+// decisions and weights are formed by the forward's own expressions (csrc/fluid_trace.h, shared with csrc/fluid_grad.hip), so they are
+// the forward's bit for bit.
 #include "fluid_tangent.h"
-
-#include <math.h>
+#include "fluid_trace.h"
 
 namespace smk {
 
 namespace {
-
-__device__ __forceinline__ float ft_clampf(float x, float lo, float hi) {
-    float t = x < lo ? lo : x;   // torch.clamp = min(max(x, lo), hi)
-    return t > hi ? hi : t;
-}
-__device__ __forceinline__ int ft_clampi(int x, int lo, int hi) {
-    int t = x < lo ? lo : x;
-    return t > hi ? hi : t;
-}
-
-// bilinear_interpolate's taps and weights (navier_stokes.py:111-131) exactly as csrc/stencil.hip's bilinear() forms them; o00 .. o11 are
-// the element offsets of (y0,x0), (y0,x1), (y1,x0), (y1,x1) in a plane of the given pitch.
-struct Taps {
-    size_t o00, o01, o10, o11;
-    float wa, wb, wc, wd;
-    float fx0, fx1, fy0, fy1;
-};
-__device__ __forceinline__ Taps taps_at(int h, int w, int pitch, float y, float x) {
-    Taps t;
-    int x0 = (int)floorf(x), y0 = (int)floorf(y);
-    int x1 = x0 + 1, y1 = y0 + 1;
-    x0 = ft_clampi(x0, 0, w - 1); x1 = ft_clampi(x1, 0, w - 1);
-    y0 = ft_clampi(y0, 0, h - 1); y1 = ft_clampi(y1, 0, h - 1);
-    t.fx0 = (float)x0; t.fx1 = (float)x1; t.fy0 = (float)y0; t.fy1 = (float)y1;
-    t.wa = (t.fx1 - x) * (t.fy1 - y);
-    t.wb = (x - t.fx0) * (t.fy1 - y);
-    t.wc = (t.fx1 - x) * (y - t.fy0);
-    t.wd = (x - t.fx0) * (y - t.fy0);
-    t.o00 = (size_t)y0 * pitch + x0; t.o01 = (size_t)y0 * pitch + x1;
-    t.o10 = (size_t)y1 * pitch + x0; t.o11 = (size_t)y1 * pitch + x1;
-    return t;
-}
-// ((wa f00 + wb f01) + wc f10) + wd f11: bilinear()'s sum, in its order
-__device__ __forceinline__ float gather(const float *f, const Taps &t) {
-    float r = t.wa * f[t.o00] + t.wb * f[t.o01];
-    r = r + t.wc * f[t.o10];
-    r = r + t.wd * f[t.o11];
-    return r;
-}
 
 // ---------------------------------------------------------------- advection tangent
 // out = adv(f; u, v) (times 0.995 for WHICH = 2).  One thread per destination cell (Y, X): it forms the forward's velocity samples, the
@@ -79,27 +39,16 @@ __global__ __launch_bounds__(FT_NT) void k_advect_tangent(Geom g, int T, const f
     const int X = blockIdx.x * FT_TX + threadIdx.x % FT_TX, Y = blockIdx.y * FT_TY + threadIdx.x / FT_TX;
     if (Y >= R || X >= C) return;
     const float *ub = u + (size_t)b * g.su, *vb = v + (size_t)b * g.sv, *fb = field + (size_t)b * fs;
-    const float fY = (float)Y, fX = (float)X;
-    // interpolate_velocity_u / _v at the cell (navier_stokes.py:97-109)
-    const Taps su = taps_at(g.H + 1, g.W, g.pc, fY, ft_clampf(fX + 0.5f, 0.f, (float)(g.W - 1)));
-    const Taps sv = taps_at(g.H, g.W + 1, g.pv, ft_clampf(fY + 0.5f, 0.f, (float)(g.H - 1)), fX);
-    const float ui = gather(ub, su), vi = gather(vb, sv);
-    const float pxu = fX - g.dt * ui, pyu = fY - g.dt * vi;                     // :87-92, before the clamp
-    const float hx = (float)(C - 1), hy = (float)(R - 1);
-    const float px = ft_clampf(pxu, 0.f, hx), py = ft_clampf(pyu, 0.f, hy);
-    const bool pass_x = pxu >= 0.f && pxu <= hx, pass_y = pyu >= 0.f && pyu <= hy;      // the clamp passes its tangent, bounds included
-    const Taps t = taps_at(R, C, pitch, py, px);
-    const float f00 = fb[t.o00], f01 = fb[t.o01], f10 = fb[t.o10], f11 = fb[t.o11];
-    const float sx = (t.fy1 - py) * (f01 - f00) + (py - t.fy0) * (f11 - f10);
-    const float sy = (t.fx1 - px) * (f10 - f00) + (px - t.fx0) * (f11 - f01);
+    const Trace tr = trace_at(g, R, C, pitch, ub, vb, fb, Y, X);
+    const Taps &su = tr.su, &sv = tr.sv, &t = tr.t;
     const size_t cell = (size_t)Y * pitch + X;
     for (int k = 0; k < T; ++k) {
         const size_t plane = (size_t)b * T + k;
         const float tui = gather(tu + plane * g.su, su), tvi = gather(tv + plane * g.sv, sv);
-        const float dpx = pass_x ? -(g.dt * tui) : 0.f, dpy = pass_y ? -(g.dt * tvi) : 0.f;
+        const float dpx = tr.pass_x ? -(g.dt * tui) : 0.f, dpy = tr.pass_y ? -(g.dt * tvi) : 0.f;
         float r = gather(tfield + plane * fs, t);
-        r = r + sx * dpx;
-        r = r + sy * dpy;
+        r = r + tr.sx * dpx;
+        r = r + tr.sy * dpy;
         if (WHICH == 2) r = r * 0.995f;                                         // :171
         tout[plane * fs + cell] = r;
     }
@@ -194,26 +143,11 @@ using namespace smk;
 
 namespace {
 
-int ft_status(hipError_t e, const char *what) {
-    if (e != hipSuccess) {
-        set_error(std::string(what) + ": " + hipGetErrorString(e));
-        return SMK_ERR_HIP;
-    }
-    return SMK_OK;
-}
-
-bool ft_shape_ok(int32_t B, int32_t T, int32_t H, int32_t W) {
-    return B >= 1 && T >= 1 && (int64_t)B * T <= 65535 && H >= 3 && W >= 3 && H <= 32766 && W <= 32766;
+bool ft_shape_ok(int32_t B, int32_t T, int32_t H, int32_t W, int32_t pitch_c, int32_t pitch_v) {
+    return fluid2d_shape_ok(B, H, W, pitch_c, pitch_v) &&
+           T >= 1 && (int64_t)B * T <= 65535;                   // the tangents' planes are the launch grid's z
 }
 const char *const FT_SHAPE = "B, T >= 1, B * T <= 65535, 3 <= H, W <= 32766, pitch_c >= W, pitch_v >= W + 1";
-
-Geom ft_geom(int32_t B, int32_t H, int32_t W, int32_t pitch_c, int32_t pitch_v, double dt) {
-    Geom g{};
-    g.B = B; g.H = H; g.W = W; g.pc = pitch_c; g.pv = pitch_v;
-    g.su = (size_t)(H + 1) * pitch_c; g.sv = (size_t)H * pitch_v; g.sc = (size_t)H * pitch_c;
-    g.dt = (float)dt;
-    return g;
-}
 
 }  // namespace
 
@@ -225,27 +159,27 @@ int smk_advect_tangent(int32_t which, const float *field, const float *u, const 
                        double dt, void *stream) {
     SMK_REQUIRE(field && u && v && tfield && tu && tv && tout, "advect_tangent: null pointer");
     SMK_REQUIRE(which >= 0 && which <= 2, "advect_tangent: which in 0..2");
-    SMK_REQUIRE(ft_shape_ok(B, T, H, W) && pitch_c >= W && pitch_v >= W + 1, FT_SHAPE);
+    SMK_REQUIRE(ft_shape_ok(B, T, H, W, pitch_c, pitch_v), FT_SHAPE);
     SMK_REQUIRE(tout != field && tout != u && tout != v && tout != tfield && tout != tu && tout != tv,
                 "advect_tangent: the output aliases an input");
-    const Geom g = ft_geom(B, H, W, pitch_c, pitch_v, dt);
-    return ft_status(launch_advect_tangent(g, T, which, field, u, v, tfield, tu, tv, tout, (hipStream_t)stream), "advect_tangent");
+    const Geom g = fluid2d_geom(B, H, W, pitch_c, pitch_v, dt, 0.0);
+    return check_launch(launch_advect_tangent(g, T, which, field, u, v, tfield, tu, tv, tout, (hipStream_t)stream), "advect_tangent");
 }
 
 int64_t smk_tangent_renorm_workspace(int32_t B, int32_t T, int32_t H, int32_t W) {
-    if (!ft_shape_ok(B, T, H, W)) return -1;
+    if (!ft_shape_ok(B, T, H, W, W, W + 1)) return -1;
     return (int64_t)B * T * ft_groups(H) * (int64_t)sizeof(double);
 }
 
 int smk_tangent_renorm(float *tu, float *tv, float *tp, float *td, double *norms, int32_t B, int32_t T, int32_t H, int32_t W,
                        int32_t pitch_c, int32_t pitch_v, void *workspace, int64_t workspace_bytes, void *stream) {
     SMK_REQUIRE(tu && tv && tp && td && norms, "tangent_renorm: null pointer");
-    SMK_REQUIRE(ft_shape_ok(B, T, H, W) && pitch_c >= W && pitch_v >= W + 1, FT_SHAPE);
+    SMK_REQUIRE(ft_shape_ok(B, T, H, W, pitch_c, pitch_v), FT_SHAPE);
     SMK_REQUIRE(workspace && workspace_bytes >= smk_tangent_renorm_workspace(B, T, H, W),
                 "tangent_renorm: workspace smaller than smk_tangent_renorm_workspace(B, T, H, W) bytes");
     SMK_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)norms & 7) == 0, "tangent_renorm: workspace and norms must be 8-byte aligned");
-    const Geom g = ft_geom(B * T, H, W, pitch_c, pitch_v, 0.0);
-    return ft_status(launch_tangent_renorm(g, tu, tv, tp, td, norms, (double *)workspace, (hipStream_t)stream), "tangent_renorm");
+    const Geom g = fluid2d_geom(B * T, H, W, pitch_c, pitch_v, 0.0, 0.0);
+    return check_launch(launch_tangent_renorm(g, tu, tv, tp, td, norms, (double *)workspace, (hipStream_t)stream), "tangent_renorm");
 }
 
 }  // extern "C"

@@ -11,6 +11,10 @@ Lyapunov exponents of the flow that come from it (Benettin's method).  DESIGN.md
   lyapunov_exponents(u, v, p, density, n)     the k largest Lyapunov exponents per unit time, with renormalisation every renorm_every
                                               steps -> LyapunovResult(exponents [B, k], log_growth [B, n_renorms, k], state, tangents).
 
+Where things live: the rule under forward_ad is fluid_grad.fluid_step_rule, i.e. physics/fluid_rule.py's 2-D instance; the state's staged
+forward, the shape check and the stepper cache are fluid_grad.py's (staged_forward, check_state, simulator over the record HIP2), shared
+with fluid_step; the kernel's back-trace is csrc/fluid_trace.h, shared with csrc/fluid_grad.hip.
+
 Derivative conventions: fluid_grad's -- that of the expressions as written (floor and integer casts have derivative 0, a clamp of a
 coordinate passes its tangent where lo <= x <= hi, bounds included, the interpolation weights are formed from the clamped indices).
 Unlike fluid_step's backward the hip route has no one-cell limit: the tangent of the advection is a gather at the forward's own taps, so a
@@ -29,7 +33,7 @@ import torch
 import torch.autograd.forward_ad as fwad
 
 from .. import _lib
-from .fluid_grad import Branches, _check_state, _simulator, fluid_step_rule
+from .fluid_grad import HIP2, Branches, check_state, fluid_step_rule, simulator, staged_forward
 
 __all__ = ["LyapunovResult", "fluid_step_jvp", "fluid_step_jvp_rule", "fluid_tangent_rollout", "lyapunov_exponents"]
 
@@ -60,7 +64,7 @@ def _check_tangents(state, tangents):
 
 def _batched(state, tangents):
     """Un-batched states ([H, W]; tangents [H, W]-like or [T, ...]) get their leading 1 -> (state, tangents, was batched)."""
-    _check_state(*state)
+    check_state(HIP2, state)
     if state[3].dim() == 3:
         return tuple(state), tuple(tangents), True
     return tuple(t[None] for t in state), tuple(t[None] for t in tangents), False
@@ -106,20 +110,12 @@ def _hip_step(state, tangents, T, dt, viscosity, jacobi_iters):
     L = _lib.load()
     with torch.cuda.device(dev):
         st = _lib.stream_ptr(dev)
-        # the base state, stage by stage as fluid_step's forward runs it (bit-identical to step()); a timed-out persistent projection is
-        # reported as step() reports it, here and for the tangents below
-        sim = _simulator(B, H, W, dt, viscosity, jacobi_iters, dev)
-        sim.u, sim.v, sim.p, sim.density = state
-        sim.run_stage(_lib.STAGE_BUOY_DIFFUSE)
-        sim.run_stage(_lib.STAGE_PROJECT)
-        u_p, v_p, d_d = sim.u.clone(), sim.v.clone(), sim.density.clone()
-        sim.run_stage(_lib.STAGE_ADVECT_U)
-        sim.run_stage(_lib.STAGE_ADVECT_V)
-        sim.run_stage(_lib.STAGE_ADVECT_D)
-        u_a, v_a, p_n, d_n = sim.state()
+        # the base state, stage by stage as fluid_step's forward runs it (fluid_grad.staged_forward: bit-identical to step(); a timed-out
+        # persistent projection is reported as step() reports it, here and for the tangents below)
+        (u_a, v_a, p_n, d_n), (u_p, v_p, d_d) = staged_forward(HIP2, simulator(HIP2, B, (H, W), dt, viscosity, jacobi_iters, dev), state)
         # the tangents' linear stages: the same kernels on a stepper of B * T grids (buoyancy, diffusion and projection are linear and
         # homogeneous in (u, v, p, density), so their tangent is themselves, with the same rounding)
-        tsim = _simulator(B * T, H, W, dt, viscosity, jacobi_iters, dev)
+        tsim = simulator(HIP2, B * T, (H, W), dt, viscosity, jacobi_iters, dev)
         tsim.u, tsim.v, tsim.p, tsim.density = tangents
         tsim.run_stage(_lib.STAGE_BUOY_DIFFUSE)
         tsim.run_stage(_lib.STAGE_PROJECT)
@@ -260,7 +256,7 @@ def lyapunov_exponents(u, v, p, density, n_steps: int, *, k: int = 1, renorm_eve
     if branches is not None and route != "torch":
         raise ValueError("lyapunov_exponents: branches goes with route='torch'")
     k = int(k)
-    _check_state(u, v, p, density)
+    check_state(HIP2, (u, v, p, density))
     batched = density.dim() == 3
     state = (u, v, p, density) if batched else tuple(t[None] for t in (u, v, p, density))
     state = tuple(t.detach() for t in state)
@@ -304,7 +300,7 @@ def lyapunov_exponents(u, v, p, density, n_steps: int, *, k: int = 1, renorm_eve
             tangents = renorm(tangents, i + 1)
     if hip:                                                  # the frames leave the steppers: a timed-out projection is reported here
         for batch in sorted({B, B * k}):
-            _simulator(batch, H, W, dt, viscosity, jacobi_iters, state[3].device).check()
+            simulator(HIP2, batch, (H, W), dt, viscosity, jacobi_iters, state[3].device).check()
     log_growth = norms[1:].log().permute(1, 0, 2).contiguous()
     exponents = log_growth.sum(dim=1) / (n_steps * float(dt))
     if not batched:

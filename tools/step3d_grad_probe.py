@@ -135,8 +135,8 @@ def main():
     shapes = []
     for shape in SHAPES[::-1]:                             # the small shape first: its figures are kept if the large one fails
         shapes.append(measure_shape(*shape, kw))
-        from smokephysai_amd.physics import fluid_grad3d
-        fluid_grad3d._SIMS.clear()
+        from smokephysai_amd.physics import fluid_grad
+        fluid_grad._SIMS.clear()                           # (the hip route's one stepper cache, 2-D and 3-D)
         torch.cuda.empty_cache()
     result = {"device": torch.cuda.get_device_name(0), "stamp": bench.source_stamp(), "reps": args.reps, "rounds": args.rounds,
               "shapes": shapes[::-1]}
