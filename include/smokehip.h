@@ -334,6 +334,48 @@ int smk_project3d_backward(const float *gu, const float *gv, const float *gw, co
 int smk_buoy_diffuse3d_backward(const float *gu, const float *gv, const float *gw, const float *gd, float *du, float *dv, float *dw,
                                 float *dd, int32_t B, int32_t D, int32_t H, int32_t W, int32_t pitch_c, int32_t pitch_v, double dt,
                                 double viscosity, void *stream);
+/* The tangent-linear (forward-mode) counterpart of the three entry points above: J t beside the 3-D step, nothing saved; the 3-D twin of
+ * smk_advect_tangent / smk_tangent_renorm.  Buoyancy, the diffusions and the projection are linear and homogeneous in the state, so their
+ * tangent is the stepper's own stage on the tangent state (smk_sim3d_run_stage on a simulator of B * T grids); only the advection needs a
+ * kernel.  Same derivative conventions as the adjoint (floor and integer casts have derivative 0, a clamp of a coordinate passes its
+ * tangent where lo <= x <= hi, bounds included, the weights' derivatives are those of the weights as written, formed from the clamped
+ * indices, so they cancel on the upper-edge quirk; the velocity samples are linear in their component; dt is a constant).  Base buffers
+ * are [B] grids in the layout of smk_advect3d_backward, tangent buffers [B][T] grids in the layout of their base field (tangent t of grid
+ * b is grid b * T + t), fp32, caller-owned, 4-byte aligned and no better, pitch_c >= W, pitch_v >= W + 1.  fp32 sums in one fixed order,
+ * no atomics, no LDS in the advection: bit-identical from call to call, a tangent's result independent of T and of its batch mates.  All
+ * work is enqueued on `stream`, nothing is allocated, no synchronisation.  Limits: smk_sim3d_create's at B * T grids -- B, T >= 1,
+ * 3 <= D, H, W <= 32766, B * T * (D + 1) <= 65535, one grid's field below 2^31 elements -- for both entry points and the query.
+ *
+ * smk_advect3d_tangent: out = advection_step(field; u, v, w) (which = 0 / 1 / 2 / 3: field shaped like u / v / w / a cell field; 3: times
+ *   0.995, the density stage of step()); (tfield, tu, tv, tw) the tangents of (field, u, v, w) -> tout, the tangent of out (field-shaped,
+ *   [B][T]).  Per destination cell (z, y, x) the velocity samples ui, vi, wi (0.5 c[o] + 0.5 c[o + step] where every index is
+ *   <= extent - 2, exactly 0 elsewhere), the back-trace px, py, pz before and after its clamp, the clamped tap indices, the six per-axis
+ *   weights wx0 = x1 - px, wx1 = px - x0, ... and the field's eight tap values f[zyx] are the forward's own, bit for bit, formed once;
+ *   then per tangent, in this order:
+ *     r = the forward's eight-term sum over tfield: weights (wx wy) wz, z-low plane first, x fastest, low before high, added left to right;
+ *     r = r + sx * dpx;   r = r + sy * dpy;   r = r + sz * dpz;   (which = 3: r = r * 0.995)
+ *     sx = (((wy0 wz0)(f001 - f000) + (wy1 wz0)(f011 - f010)) + (wy0 wz1)(f101 - f100)) + (wy1 wz1)(f111 - f110)
+ *     sy = (((wx0 wz0)(f010 - f000) + (wx1 wz0)(f011 - f001)) + (wx0 wz1)(f110 - f100)) + (wx1 wz1)(f111 - f101)
+ *     sz = (((wx0 wy0)(f100 - f000) + (wx1 wy0)(f101 - f001)) + (wx0 wy1)(f110 - f010)) + (wx1 wy1)(f111 - f011)
+ *     dpx = -(dt * ui') where 0 <= x - dt ui <= columns - 1, else 0;  dpy, dpz likewise from y - dt vi, z - dt wi and vi', wi';
+ *     ui', vi', wi': the forward's velocity samples of tu, tv, tw (same guard, same two elements, same 0.5 / 0.5).
+ *   Every element [plane][row][col < columns] of tout is written (the pitch padding is left alone); tout aliases no input; tfield may be
+ *   the same buffer as tu, tv or tw, as field may be u, v or w.  One launch.  A back-trace may move any number of cells: there is no far
+ *   case, no far word.
+ * smk_tangent3d_renorm: per grid and tangent, norms[b * T + t] (fp64, 8-byte aligned) = the Euclidean norm of the whole tangent state
+ *   (tu [D][H+1][pitch_c], tv [D][H][pitch_v], tw [D+1][H][pitch_c], tp, td [D][H][pitch_c]; five distinct buffers): each element
+ *   converted to fp64 and squared there, the squares summed in fp64 in one fixed order (two levels: the state's rows -- u's, v's, w's,
+ *   p's, the density's, planes before rows -- in runs of consecutive rows per workgroup, a thread's elements in ascending order and the
+ *   256 threads folded by halves; then the runs in ascending order), no atomics.  The five fields are then divided in place by
+ *   (float)norm with a true fp32 divide (the pitch padding is left alone); a norm that is 0 or not finite (as fp64, or once converted to
+ *   fp32) leaves that tangent unscaled and is reported as it is.  Two launches.  workspace: device memory of at least
+ *   smk_tangent3d_renorm_workspace(B, T, D, H, W) bytes (-1 for an unsupported shape), 8-byte aligned, contents unspecified afterwards. */
+int smk_advect3d_tangent(int32_t which, const float *field, const float *u, const float *v, const float *w, const float *tfield,
+                         const float *tu, const float *tv, const float *tw, float *tout, int32_t B, int32_t T, int32_t D, int32_t H,
+                         int32_t W, int32_t pitch_c, int32_t pitch_v, double dt, void *stream);
+int64_t smk_tangent3d_renorm_workspace(int32_t B, int32_t T, int32_t D, int32_t H, int32_t W);
+int smk_tangent3d_renorm(float *tu, float *tv, float *tw, float *tp, float *td, double *norms, int32_t B, int32_t T, int32_t D, int32_t H,
+                         int32_t W, int32_t pitch_c, int32_t pitch_v, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* NavierStokesSimulator.bilinear_interpolate(field, y, x) (navier_stokes.py:111-131; mode 0),
  * .interpolate_velocity_u(u, y, x) (:97-102; mode 1: x + 0.5 clamped to [0, w-1] first) and .interpolate_velocity_v(v, y, x)

@@ -13,7 +13,9 @@ Lyapunov exponents of the flow that come from it (Benettin's method).  DESIGN.md
 
 Where things live: the rule under forward_ad is fluid_grad.fluid_step_rule, i.e. physics/fluid_rule.py's 2-D instance; the state's staged
 forward, the shape check and the stepper cache are fluid_grad.py's (staged_forward, check_state, simulator over the record HIP2), shared
-with fluid_step; the kernel's back-trace is csrc/fluid_trace.h, shared with csrc/fluid_grad.hip.
+with fluid_step; the kernel's back-trace is csrc/fluid_trace.h, shared with csrc/fluid_grad.hip.  The route, the tangents' shape checks
+and the Benettin loop below are written once over that per-dimension record (the route_* functions); the public functions here bind them
+to HIP2, those of fluid_tangent3d.py to HIP3.
 
 Derivative conventions: fluid_grad's -- that of the expressions as written (floor and integer casts have derivative 0, a clamp of a
 coordinate passes its tangent where lo <= x <= hi, bounds included, the interpolation weights are formed from the clamped indices).
@@ -24,8 +26,8 @@ Hot path and what is not: for k = 1 the renormalisation is smk_tangent_renorm (t
 the device until the end).  For k > 1 the tangents are re-orthonormalised by modified Gram-Schmidt in plain torch operations with fp64
 coefficients: that part is NOT a hot path (k (k + 1) / 2 reductions and updates per renormalisation).
 
-Out of scope: torch.func.jvp / torch.autograd.forward_ad through fluid_step itself (call fluid_step_jvp), the 3-D step, and the dataset
-labels (the `lyapunov_exponent` of get_chaos_features() stays the reference's frame-difference proxy)."""
+Out of scope: torch.func.jvp / torch.autograd.forward_ad through fluid_step itself (call fluid_step_jvp), and the dataset labels (the
+`lyapunov_exponent` of get_chaos_features() stays the reference's frame-difference proxy).  The 3-D step is fluid_tangent3d.py."""
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -33,56 +35,73 @@ import torch
 import torch.autograd.forward_ad as fwad
 
 from .. import _lib
-from .fluid_grad import HIP2, Branches, check_state, fluid_step_rule, simulator, staged_forward
+from .fluid_grad import HIP2, Branches, check_state, simulator, staged_forward
 
 __all__ = ["LyapunovResult", "fluid_step_jvp", "fluid_step_jvp_rule", "fluid_tangent_rollout", "lyapunov_exponents"]
 
 MAX_K = 8
-MAX_PLANES = 65535          # B * T, the launch grid's reach (include/smokehip.h)
+MAX_PLANES = 65535          # B * T in 2-D, B * T * (D + 1) in 3-D: the launch grids' reach (include/smokehip.h)
 
 
-# ------------------------------------------------------------------------------------------------ shapes
-def _check_tangents(state, tangents):
+# ------------------------------------------------------------------------------------------------ names and shapes, per dimension record
+def _jvp_name(dim):
+    return f"{dim.name}_jvp"                                   # fluid_step_jvp, fluid_step3d_jvp
+
+
+def _lyapunov_name(dim):
+    return "lyapunov_exponents" + ("" if dim.nd == 2 else f"{dim.nd}d")
+
+
+def _tangent_names(dim):
+    return "(" + ", ".join("t" + f for f in dim.fields) + ")"  # (tu, tv, tp, tdensity)
+
+
+def _planes(dim, density, T):
+    """(what the launch grids count, its value) for a batched density and T tangents per grid."""
+    n = density.shape[0] * (T or 1)
+    return ("B * T", n) if dim.nd == 2 else ("B * T * (D + 1)", n * (density.shape[1] + 1))
+
+
+def _check_tangents(dim, state, tangents):
     """-> T, or None where the tangents are state-shaped.  state: checked [B, ...] tensors."""
-    if len(tangents) != 4:
-        raise ValueError("fluid_step_jvp: tangents are (tu, tv, tp, tdensity)")
+    what = _jvp_name(dim)
+    if len(tangents) != len(dim.fields):
+        raise ValueError(f"{what}: tangents are {_tangent_names(dim)}")
     dims = {t.dim() - s.dim() for s, t in zip(state, tangents)}
     if dims not in ({0}, {1}):
-        raise ValueError("fluid_step_jvp: tangents must all be state-shaped [B, ...] or all [B, T, ...]")
+        raise ValueError(f"{what}: tangents must all be state-shaped [B, ...] or all [B, T, ...]")
     extra = dims.pop()
     T = None if extra == 0 else int(tangents[0].shape[1])
-    for name, s, t in zip(("u", "v", "p", "density"), state, tangents):
+    for name, s, t in zip(dim.fields, state, tangents):
         want = tuple(s.shape) if T is None else (s.shape[0], T) + tuple(s.shape[1:])
         if tuple(t.shape) != want:
-            raise ValueError(f"fluid_step_jvp: the tangent of {name} must be {want}, got {tuple(t.shape)}")
+            raise ValueError(f"{what}: the tangent of {name} must be {want}, got {tuple(t.shape)}")
     if T is not None and T < 1:
-        raise ValueError("fluid_step_jvp: T >= 1")
-    if state[3].shape[0] * (T or 1) > MAX_PLANES:
-        raise ValueError(f"fluid_step_jvp: B * T = {state[3].shape[0] * (T or 1)} exceeds {MAX_PLANES}")
+        raise ValueError(f"{what}: T >= 1")
+    counted, n = _planes(dim, state[-1], T)
+    if n > MAX_PLANES:
+        raise ValueError(f"{what}: {counted} = {n} exceeds {MAX_PLANES}")
     return T
 
 
-def _batched(state, tangents):
-    """Un-batched states ([H, W]; tangents [H, W]-like or [T, ...]) get their leading 1 -> (state, tangents, was batched)."""
-    check_state(HIP2, state)
-    if state[3].dim() == 3:
+def _batched(dim, state, tangents):
+    """Un-batched states (grid-shaped; tangents likewise or [T, ...]) get their leading 1 -> (state, tangents, was batched)."""
+    check_state(dim, state)
+    if state[-1].dim() == dim.nd + 1:
         return tuple(state), tuple(tangents), True
     return tuple(t[None] for t in state), tuple(t[None] for t in tangents), False
 
 
-# ------------------------------------------------------------------------------------------------ the rule: forward-mode AD of fluid_step_rule
-def fluid_step_jvp_rule(state, tangents, *, dt: float = 0.01, viscosity: float = 0.001, jacobi_iters: int = 20,
-                        branches: Optional[Branches] = None):
-    """(state', tangents') of one step by torch.autograd.forward_ad over fluid_step_rule: any floating dtype, any device.  state
-    (u, v, p, density) with leading dimensions [B] (or none); tangents state-shaped, or [B, T, ...]: then the state is expanded along T and
-    one pass carries all T tangents (a Branches recorder then holds decisions of that expanded shape).  branches: as fluid_step_rule's."""
-    state, tangents, batched = _batched(state, tangents)
-    T = _check_tangents(state, tangents)
+# ------------------------------------------------------------------------------------------------ the rule: forward-mode AD of the step rule
+def route_jvp_rule(dim, state, tangents, dt, viscosity, jacobi_iters, branches):
+    """fluid_step_jvp_rule / fluid_step3d_jvp_rule: forward_ad over dim.rule."""
+    state, tangents, batched = _batched(dim, state, tangents)
+    T = _check_tangents(dim, state, tangents)
     if T is not None:
         state = tuple(s[:, None].expand(s.shape[0], T, *s.shape[1:]).contiguous() for s in state)
     with fwad.dual_level():
         duals = [fwad.make_dual(s.detach(), t.detach().to(s.dtype)) for s, t in zip(state, tangents)]
-        outs = fluid_step_rule(*duals, dt=dt, viscosity=viscosity, jacobi_iters=jacobi_iters, branches=branches)
+        outs = dim.rule(*duals, dt=dt, viscosity=viscosity, jacobi_iters=jacobi_iters, branches=branches)
         new, tan = [], []
         for o in outs:
             primal, tangent = fwad.unpack_dual(o)
@@ -95,45 +114,86 @@ def fluid_step_jvp_rule(state, tangents, *, dt: float = 0.01, viscosity: float =
     return tuple(new), tuple(tan)
 
 
+def fluid_step_jvp_rule(state, tangents, *, dt: float = 0.01, viscosity: float = 0.001, jacobi_iters: int = 20,
+                        branches: Optional[Branches] = None):
+    """(state', tangents') of one step by torch.autograd.forward_ad over fluid_step_rule: any floating dtype, any device.  state
+    (u, v, p, density) with leading dimensions [B] (or none); tangents state-shaped, or [B, T, ...]: then the state is expanded along T and
+    one pass carries all T tangents (a Branches recorder then holds decisions of that expanded shape).  branches: as fluid_step_rule's."""
+    return route_jvp_rule(HIP2, state, tangents, dt, viscosity, jacobi_iters, branches)
+
+
 # ------------------------------------------------------------------------------------------------ the hip route
-def _advect_tangent(L, st, which, field, u, v, tfield, tu, tv, B, T, H, W, dt):
-    out = torch.empty_like(tfield)
-    _lib.check(L.smk_advect_tangent(which, field.data_ptr(), u.data_ptr(), v.data_ptr(), tfield.data_ptr(), tu.data_ptr(), tv.data_ptr(),
-                                    out.data_ptr(), B, T, H, W, W, W + 1, dt, st))
-    return out
-
-
-def _hip_step(state, tangents, T, dt, viscosity, jacobi_iters):
+def _hip_step(dim, state, tangents, T, dt, viscosity, jacobi_iters):
     """state [B, ...], tangents [B * T, ...] (fp32, on one ROCm device) -> (state', tangents' [B * T, ...])."""
-    B, H, W = state[3].shape
-    dev = state[3].device
+    nd = dim.nd
+    B, *grid = state[-1].shape
+    dev = state[-1].device
     L = _lib.load()
+    advect = getattr(L, dim.tangent[0])
     with torch.cuda.device(dev):
         st = _lib.stream_ptr(dev)
-        # the base state, stage by stage as fluid_step's forward runs it (fluid_grad.staged_forward: bit-identical to step(); a timed-out
-        # persistent projection is reported as step() reports it, here and for the tangents below)
-        (u_a, v_a, p_n, d_n), (u_p, v_p, d_d) = staged_forward(HIP2, simulator(HIP2, B, (H, W), dt, viscosity, jacobi_iters, dev), state)
+        # the base state, stage by stage as the differentiable step's forward runs it (fluid_grad.staged_forward: bit-identical to step();
+        # a timed-out persistent projection is reported as step() reports it, here and for the tangents below)
+        new, kept = staged_forward(dim, simulator(dim, B, grid, dt, viscosity, jacobi_iters, dev), state)
+        vel_a, vel_p, d_d = list(new[:nd]), kept[:nd], kept[nd]
         # the tangents' linear stages: the same kernels on a stepper of B * T grids (buoyancy, diffusion and projection are linear and
-        # homogeneous in (u, v, p, density), so their tangent is themselves, with the same rounding)
-        tsim = simulator(HIP2, B * T, (H, W), dt, viscosity, jacobi_iters, dev)
-        tsim.u, tsim.v, tsim.p, tsim.density = tangents
-        tsim.run_stage(_lib.STAGE_BUOY_DIFFUSE)
-        tsim.run_stage(_lib.STAGE_PROJECT)
-        tu_p, tv_p, tp_n, td_d = tsim.state()
-        # the three advections with the forward's operand wiring: u_a <- (u_p; u_p, v_p), v_a <- (v_p; u_a, v_p), density <- (d_d; u_a, v_a)
-        tu_a = _advect_tangent(L, st, 0, u_p, u_p, v_p, tu_p, tu_p, tv_p, B, T, H, W, dt)
-        tv_a = _advect_tangent(L, st, 1, v_p, u_a, v_p, tv_p, tu_a, tv_p, B, T, H, W, dt)
-        td_n = _advect_tangent(L, st, 2, d_d, u_a, v_a, td_d, tu_a, tv_a, B, T, H, W, dt)
-    return (u_a, v_a, p_n, d_n), (tu_a, tv_a, tp_n, td_n)
+        # homogeneous in the state, so their tangent is themselves, with the same rounding)
+        tsim = simulator(dim, B * T, grid, dt, viscosity, jacobi_iters, dev)
+        for name, t in zip(dim.fields, tangents):
+            setattr(tsim, name, t)
+        tsim.run_stage(dim.stages[0])
+        tsim.run_stage(dim.stages[1])
+        *tvel_p, tp_n, td_d = tsim.state()
+
+        def advect_tangent(which, field, vel, tfield, tvel):
+            out = torch.empty_like(tfield)
+            _lib.check(advect(which, *[t.data_ptr() for t in (field, *vel, tfield, *tvel, out)], B, T, *grid, grid[-1], grid[-1] + 1, dt, st))
+            return out
+        # the advections with the forward's operand wiring: component k <- (c_p[k]; the advected components before it, the projected ones
+        # from itself on), then density <- (d_d; the advected components) -- 2-D: u_a <- (u_p; u_p, v_p), v_a <- (v_p; u_a, v_p),
+        # density <- (d_d; u_a, v_a).  Each call takes the tangents of its own velocity operands.
+        tvel_a = []
+        for k in range(nd):
+            tvel_a.append(advect_tangent(k, vel_p[k], (*vel_a[:k], *vel_p[k:]), tvel_p[k], (*tvel_a[:k], *tvel_p[k:])))
+        td_n = advect_tangent(nd, d_d, vel_a, td_d, tvel_a)
+    return new, (*tvel_a, tp_n, td_n)
 
 
 def _check_hip(state, tangents, jacobi_iters, what):
-    _lib.require_cuda(state[3].device, f"{what}(route='hip')")
+    _lib.require_cuda(state[-1].device, f"{what}(route='hip')")
     for t in tuple(state) + tuple(tangents):
-        if t.dtype != torch.float32 or t.device != state[3].device:
+        if t.dtype != torch.float32 or t.device != state[-1].device:
             raise ValueError(f"{what}(route='hip'): the state and the tangents must be float32 tensors on one device")
     if int(jacobi_iters) < 0:
         raise ValueError(f"{what}: jacobi_iters >= 0")
+
+
+def route_jvp(dim, state, tangents, dt=0.01, viscosity=0.001, jacobi_iters=20, route="hip"):
+    """fluid_step_jvp / fluid_step3d_jvp: the checks, then the rule or the hip route."""
+    what = _jvp_name(dim)
+    if route == "torch":
+        return route_jvp_rule(dim, state, tangents, dt, viscosity, jacobi_iters, None)
+    if route != "hip":
+        raise ValueError(f"{what}: route is 'hip' or 'torch', got {route!r}")
+    state, tangents, batched = _batched(dim, state, tangents)
+    T = _check_tangents(dim, state, tangents)
+    _check_hip(state, tangents, jacobi_iters, what)
+    with torch.no_grad():
+        flat = tuple(t.reshape(-1, *t.shape[-dim.nd:]) for t in tangents)
+        new, tan = _hip_step(dim, state, flat, T or 1, float(dt), float(viscosity), int(jacobi_iters))
+    tan = tuple(t.view(x.shape) for t, x in zip(tan, tangents))
+    if not batched:
+        new, tan = tuple(s[0] for s in new), tuple(t[0] for t in tan)
+    return new, tan
+
+
+def route_tangent_rollout(dim, state, tangents, n_steps, settings):
+    """fluid_tangent_rollout / fluid_tangent_rollout3d: n_steps chained tangent steps."""
+    if n_steps < 1:
+        raise ValueError(f"fluid_tangent_rollout{'' if dim.nd == 2 else f'{dim.nd}d'}: n_steps >= 1")
+    for _ in range(n_steps):
+        state, tangents = route_jvp(dim, state, tangents, **settings)
+    return state, tangents
 
 
 def fluid_step_jvp(state, tangents, *, dt: float = 0.01, viscosity: float = 0.001, jacobi_iters: int = 20, route: str = "hip"):
@@ -141,38 +201,22 @@ def fluid_step_jvp(state, tangents, *, dt: float = 0.01, viscosity: float = 0.00
     state: u [B, H+1, W], v [B, H, W+1], p, density [B, H, W] (or without the B); tangents: state-shaped, or [B, T, ...] for T tangents
     per grid.  route="hip": fp32 ROCm tensors; the returned state is bit-identical to step() on the same state; nothing is saved; no
     one-cell limit.  route="torch": fluid_step_jvp_rule, any dtype and device.  Not differentiable itself (outputs carry no graph)."""
-    if route == "torch":
-        return fluid_step_jvp_rule(state, tangents, dt=dt, viscosity=viscosity, jacobi_iters=jacobi_iters)
-    if route != "hip":
-        raise ValueError(f"fluid_step_jvp: route is 'hip' or 'torch', got {route!r}")
-    state, tangents, batched = _batched(state, tangents)
-    T = _check_tangents(state, tangents)
-    _check_hip(state, tangents, jacobi_iters, "fluid_step_jvp")
-    with torch.no_grad():
-        flat = tuple(t.reshape(-1, *t.shape[-2:]) for t in tangents)
-        new, tan = _hip_step(state, flat, T or 1, float(dt), float(viscosity), int(jacobi_iters))
-    tan = tuple(t.view(x.shape) for t, x in zip(tan, tangents))
-    if not batched:
-        new, tan = tuple(s[0] for s in new), tuple(t[0] for t in tan)
-    return new, tan
+    return route_jvp(HIP2, state, tangents, dt, viscosity, jacobi_iters, route)
 
 
 def fluid_tangent_rollout(state, tangents, n_steps: int, **settings):
     """n_steps chained fluid_step_jvp calls -> (state, tangents) after the last.  settings: fluid_step_jvp's keywords.  Nothing is kept
     between steps, so memory does not grow with n_steps; the tangents are not renormalised (lyapunov_exponents does that)."""
-    if n_steps < 1:
-        raise ValueError("fluid_tangent_rollout: n_steps >= 1")
-    for _ in range(n_steps):
-        state, tangents = fluid_step_jvp(state, tangents, **settings)
-    return state, tangents
+    return route_tangent_rollout(HIP2, state, tangents, n_steps, settings)
 
 
 # ------------------------------------------------------------------------------------------------ Lyapunov exponents (Benettin)
 @dataclass
 class LyapunovResult:
     """exponents [B, k] fp64, per unit time: sum of log_growth / (n_steps * dt), largest first for k > 1 (Gram-Schmidt order).
-    log_growth [B, n_renorms, k] fp64: the log of each tangent's norm at each renormalisation.  state: (u, v, p, density) after the last
-    step; tangents: the k unit (k > 1: orthonormal) tangent states [B, k, ...] after the last renormalisation."""
+    log_growth [B, n_renorms, k] fp64: the log of each tangent's norm at each renormalisation.  state: (u, v, p, density) -- in 3-D
+    (u, v, w, p, density) -- after the last step; tangents: the k unit (k > 1: orthonormal) tangent states [B, k, ...] after the last
+    renormalisation."""
     exponents: torch.Tensor
     log_growth: torch.Tensor
     state: Tuple[torch.Tensor, ...]
@@ -182,6 +226,11 @@ class LyapunovResult:
 def _dot64(a, b):
     """<a, b> over whole states [B, ...] in fp64 -> [B]."""
     return sum((x.double() * y.double()).flatten(1).sum(dim=1) for x, y in zip(a, b))
+
+
+def _per_grid(c, x):
+    """A per-grid coefficient [B] in x's dtype, shaped to broadcast over x [B, ...]."""
+    return c.to(x.dtype).view(-1, *[1] * (x.dim() - 1))
 
 
 def _gram_schmidt(tangents):
@@ -194,13 +243,13 @@ def _gram_schmidt(tangents):
         vec = [t[:, j] for t in tangents]
         for q in done:
             c = _dot64(q, vec)
-            vec = [x - c.to(x.dtype)[:, None, None] * y for x, y in zip(vec, q)]
+            vec = [x - _per_grid(c, x) * y for x, y in zip(vec, q)]
         n = _dot64(vec, vec).sqrt()
         norms.append(n)
         ok = (n > 0) & torch.isfinite(n)
         div = torch.where(ok, n, torch.ones_like(n))
-        done.append([x / div.to(x.dtype)[:, None, None] for x in vec])
-    return tuple(torch.stack([q[i] for q in done], dim=1) for i in range(4)), torch.stack(norms, dim=1)
+        done.append([x / _per_grid(div, x) for x in vec])
+    return tuple(torch.stack([q[i] for q in done], dim=1) for i in range(len(tangents))), torch.stack(norms, dim=1)
 
 
 def _renorm_torch(tangents):
@@ -208,25 +257,28 @@ def _renorm_torch(tangents):
     n = _dot64([t[:, 0] for t in tangents], [t[:, 0] for t in tangents]).sqrt()
     ok = (n > 0) & torch.isfinite(n)
     div = torch.where(ok, n, torch.ones_like(n))
-    return tuple(t / div.to(t.dtype)[:, None, None, None] for t in tangents), n[:, None]
+    return tuple(t / _per_grid(div, t) for t in tangents), n[:, None]
 
 
 class _HipRenorm:
-    """smk_tangent_renorm on tangents [B, 1, ...] in place, its workspace allocated once."""
+    """smk_tangent_renorm / smk_tangent3d_renorm on tangents [B, 1, ...] in place, its workspace allocated once."""
 
-    def __init__(self, B, T, H, W, dev):
-        self.L, self.dims, self.dev = _lib.load(), (B, T, H, W), dev
-        self.nbytes = int(self.L.smk_tangent_renorm_workspace(B, T, H, W))
+    def __init__(self, dim, B, T, grid, dev):
+        self.L, self.dims, self.dev = _lib.load(), (B, T, *grid), dev
+        self.renorm = getattr(self.L, dim.tangent[1])
+        self.nbytes = int(getattr(self.L, dim.tangent[2])(B, T, *grid))
         if self.nbytes < 0:
-            raise ValueError(f"lyapunov_exponents: B={B}, k={T}, grid {H} x {W} is not supported (B * k <= {MAX_PLANES}, 3 <= H, W <= 32766)")
+            counted = "B * k" if dim.nd == 2 else "B * k * (D + 1)"
+            raise ValueError(f"{_lyapunov_name(dim)}: B={B}, k={T}, grid {' x '.join(str(n) for n in grid)} is not supported "
+                             f"({counted} <= {MAX_PLANES}, 3 <= {dim.axes} <= 32766)")
         self.ws = torch.empty(self.nbytes // 8, dtype=torch.float64, device=dev)
 
     def __call__(self, tangents, norms):
-        B, T, H, W = self.dims
+        W = self.dims[-1]
         tangents = tuple(t if t.is_contiguous() else t.contiguous() for t in tangents)
         with torch.cuda.device(self.dev):
-            _lib.check(self.L.smk_tangent_renorm(*[t.data_ptr() for t in tangents], norms.data_ptr(), B, T, H, W, W, W + 1,
-                                                 self.ws.data_ptr(), self.nbytes, _lib.stream_ptr(self.dev)))
+            _lib.check(self.renorm(*[t.data_ptr() for t in tangents], norms.data_ptr(), *self.dims, W, W + 1,
+                                   self.ws.data_ptr(), self.nbytes, _lib.stream_ptr(self.dev)))
         return tangents
 
 
@@ -234,6 +286,73 @@ def _draw_tangent0(state, k, seed):
     """Unit-normal noise for every field, drawn on the CPU from `seed` and copied: independent of the device's generator."""
     g = torch.Generator().manual_seed(int(seed))
     return tuple(torch.randn(s.shape[0], k, *s.shape[1:], generator=g, dtype=torch.float32).to(device=s.device, dtype=s.dtype) for s in state)
+
+
+def route_lyapunov(dim, state, n_steps, k=1, renorm_every=1, tangent0=None, seed=0, dt=0.01, viscosity=0.001, jacobi_iters=20,
+                   route="hip", branches=None) -> LyapunovResult:
+    """lyapunov_exponents / lyapunov_exponents3d: Benettin's loop over the dimension record."""
+    what = _lyapunov_name(dim)
+    if route not in ("hip", "torch"):
+        raise ValueError(f"{what}: route is 'hip' or 'torch', got {route!r}")
+    if not 1 <= int(k) <= MAX_K:
+        raise ValueError(f"{what}: 1 <= k <= {MAX_K}, got {k}")
+    if n_steps < 1 or renorm_every < 1 or n_steps % renorm_every:
+        raise ValueError(f"{what}: n_steps >= 1 and a multiple of renorm_every >= 1")
+    if branches is not None and route != "torch":
+        raise ValueError(f"{what}: branches goes with route='torch'")
+    k = int(k)
+    check_state(dim, state)
+    batched = state[-1].dim() == dim.nd + 1
+    state = tuple(t.detach() if batched else t.detach()[None] for t in state)
+    B, *grid = state[-1].shape
+    if tangent0 is None:
+        tangents = _draw_tangent0(state, k, seed)
+    else:
+        tangents = tuple(t.detach() if batched else t.detach()[None] for t in tangent0)
+        if len(tangents) == len(state) and all(t.dim() == s.dim() for t, s in zip(tangents, state)):
+            tangents = tuple(t[:, None] for t in tangents)
+        if _check_tangents(dim, state, tangents) != k:
+            raise ValueError(f"{what}: tangent0 must hold k = {k} tangents per grid")
+        tangents = tuple(t.clone() for t in tangents)
+    settings = dict(dt=dt, viscosity=viscosity, jacobi_iters=jacobi_iters)
+    n_renorms = n_steps // renorm_every
+    hip = route == "hip"
+    if hip:
+        _check_hip(state, tangents, jacobi_iters, what)
+    norms = torch.empty(n_renorms + 1, B, k, dtype=torch.float64, device=state[-1].device)
+    if k > 1:
+        def renorm(ts, i):
+            ts, norms[i] = _gram_schmidt(ts)
+            return ts
+    elif hip:
+        hip_renorm = _HipRenorm(dim, B, 1, grid, state[-1].device)
+
+        def renorm(ts, i):
+            return hip_renorm(ts, norms[i])
+    else:
+        def renorm(ts, i):
+            ts, norms[i] = _renorm_torch(ts)
+            return ts
+    with torch.no_grad():
+        tangents = renorm(tangents, 0)                       # (the initial scale: not a growth factor)
+        for i in range(n_renorms):
+            for _ in range(renorm_every):
+                if hip:
+                    state, tangents = route_jvp(dim, state, tangents, route="hip", **settings)
+                else:
+                    state, tangents = route_jvp_rule(dim, state, tangents, branches=branches, **settings)
+            tangents = renorm(tangents, i + 1)
+    if hip:                                                  # the frames leave the steppers: a timed-out projection is reported here
+        for batch in sorted({B, B * k}):                     # (by the steppers that can time out: the 3-D one has no check())
+            check = getattr(simulator(dim, batch, grid, dt, viscosity, jacobi_iters, state[-1].device), "check", None)
+            if check is not None:
+                check()
+    log_growth = norms[1:].log().permute(1, 0, 2).contiguous()
+    exponents = log_growth.sum(dim=1) / (n_steps * float(dt))
+    if not batched:
+        state, tangents = tuple(s[0] for s in state), tuple(t[0] for t in tangents)
+        exponents, log_growth = exponents[0], log_growth[0]
+    return LyapunovResult(exponents, log_growth, tuple(state), tuple(tangents))
 
 
 def lyapunov_exponents(u, v, p, density, n_steps: int, *, k: int = 1, renorm_every: int = 1, tangent0=None, seed: int = 0,
@@ -247,63 +366,4 @@ def lyapunov_exponents(u, v, p, density, n_steps: int, *, k: int = 1, renorm_eve
     normalised (orthonormalised) first, so its scale does not matter.  route="torch": the rule, any dtype and device; branches: a
     Branches recorder / replayer handed to every step of that route (the tests' fp64 run along the fp32 run's decisions).
     The hip route synchronises once, at the end, to check the steppers' status."""
-    if route not in ("hip", "torch"):
-        raise ValueError(f"lyapunov_exponents: route is 'hip' or 'torch', got {route!r}")
-    if not 1 <= int(k) <= MAX_K:
-        raise ValueError(f"lyapunov_exponents: 1 <= k <= {MAX_K}, got {k}")
-    if n_steps < 1 or renorm_every < 1 or n_steps % renorm_every:
-        raise ValueError("lyapunov_exponents: n_steps >= 1 and a multiple of renorm_every >= 1")
-    if branches is not None and route != "torch":
-        raise ValueError("lyapunov_exponents: branches goes with route='torch'")
-    k = int(k)
-    check_state(HIP2, (u, v, p, density))
-    batched = density.dim() == 3
-    state = (u, v, p, density) if batched else tuple(t[None] for t in (u, v, p, density))
-    state = tuple(t.detach() for t in state)
-    B, H, W = state[3].shape
-    if tangent0 is None:
-        tangents = _draw_tangent0(state, k, seed)
-    else:
-        tangents = tuple(t.detach() if batched else t.detach()[None] for t in tangent0)
-        if len(tangents) == 4 and all(t.dim() == s.dim() for t, s in zip(tangents, state)):
-            tangents = tuple(t[:, None] for t in tangents)
-        if _check_tangents(state, tangents) != k:
-            raise ValueError(f"lyapunov_exponents: tangent0 must hold k = {k} tangents per grid")
-        tangents = tuple(t.clone() for t in tangents)
-    settings = dict(dt=dt, viscosity=viscosity, jacobi_iters=jacobi_iters)
-    n_renorms = n_steps // renorm_every
-    hip = route == "hip"
-    if hip:
-        _check_hip(state, tangents, jacobi_iters, "lyapunov_exponents")
-    norms = torch.empty(n_renorms + 1, B, k, dtype=torch.float64, device=state[3].device)
-    if k > 1:
-        def renorm(ts, i):
-            ts, norms[i] = _gram_schmidt(ts)
-            return ts
-    elif hip:
-        hip_renorm = _HipRenorm(B, 1, H, W, state[3].device)
-
-        def renorm(ts, i):
-            return hip_renorm(ts, norms[i])
-    else:
-        def renorm(ts, i):
-            ts, norms[i] = _renorm_torch(ts)
-            return ts
-    with torch.no_grad():
-        tangents = renorm(tangents, 0)                       # (the initial scale: not a growth factor)
-        for i in range(n_renorms):
-            for _ in range(renorm_every):
-                if hip:
-                    state, tangents = fluid_step_jvp(state, tangents, route="hip", **settings)
-                else:
-                    state, tangents = fluid_step_jvp_rule(state, tangents, branches=branches, **settings)
-            tangents = renorm(tangents, i + 1)
-    if hip:                                                  # the frames leave the steppers: a timed-out projection is reported here
-        for batch in sorted({B, B * k}):
-            simulator(HIP2, batch, (H, W), dt, viscosity, jacobi_iters, state[3].device).check()
-    log_growth = norms[1:].log().permute(1, 0, 2).contiguous()
-    exponents = log_growth.sum(dim=1) / (n_steps * float(dt))
-    if not batched:
-        state, tangents = tuple(s[0] for s in state), tuple(t[0] for t in tangents)
-        exponents, log_growth = exponents[0], log_growth[0]
-    return LyapunovResult(exponents, log_growth, tuple(state), tuple(tangents))
+    return route_lyapunov(HIP2, (u, v, p, density), n_steps, k, renorm_every, tangent0, seed, dt, viscosity, jacobi_iters, route, branches)

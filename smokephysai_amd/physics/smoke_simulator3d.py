@@ -167,6 +167,17 @@ class SmokeSimulator3D(nn.Module):
                   "entropy": entropy_from_hist(hist[b])} for b in range(B)]
         return feats if self.batch_size is not None else feats[0]
 
+    def flow_lyapunov(self, n_steps: int = 20, **kw):
+        """The largest Lyapunov exponent of the flow per unit time from the simulator's CURRENT state: physics.lyapunov_exponents3d
+        (Benettin's method on the tangent-linear step) over n_steps further steps, run on clones -- the
+        simulator, its ring of norms and get_chaos_features() (whose `lyapunov_exponent` stays the frame-difference proxy) are untouched.
+        kw: lyapunov_exponents3d's keywords (renorm_every, seed, route, tangent0 in the batched shapes of ns_solver.state(), B = 1 when
+        un-batched); k is 1.  A float when un-batched, an fp64 tensor [B] when batched."""
+        from .fluid_tangent3d import lyapunov_exponents3d
+        ns = self.ns_solver
+        res = lyapunov_exponents3d(*ns.state(), n_steps, k=1, dt=ns.dt, viscosity=ns.viscosity, jacobi_iters=ns.jacobi_iters, **kw)
+        return res.exponents[:, 0] if self.batch_size is not None else float(res.exponents[0, 0])
+
     def _single_grid(self, what):
         if self.batch_size is not None:
             raise ValueError(f"{what}: batched simulator -- use get_chaos_features(), which returns one dict per grid")
