@@ -376,6 +376,33 @@ int smk_advect3d_tangent(int32_t which, const float *field, const float *u, cons
 int64_t smk_tangent3d_renorm_workspace(int32_t B, int32_t T, int32_t D, int32_t H, int32_t W);
 int smk_tangent3d_renorm(float *tu, float *tv, float *tw, float *tp, float *td, double *norms, int32_t B, int32_t T, int32_t D, int32_t H,
                          int32_t W, int32_t pitch_c, int32_t pitch_v, void *workspace, int64_t workspace_bytes, void *stream);
+/* The T tangent states of every grid orthonormalised in place by modified Gram-Schmidt: what a Lyapunov spectrum (k > 1 exponents) needs
+ * where smk_tangent_renorm / smk_tangent3d_renorm serve k = 1.  Buffers are those of the renorm entry points -- [B][T] grids (vector t of
+ * grid b is grid b * T + t), fp32, caller-owned, 4-byte aligned and no better, distinct buffers, pitch_c >= W, pitch_v >= W + 1 -- and the
+ * state's rows are taken in the renorm entry points' order (2-D: u's, v's, p's, the density's; 3-D: u's, v's, w's, p's, the density's,
+ * planes before rows).  Per grid, for j = 0 .. T-1 in turn:
+ *   1. n_j = sqrt(sum (double)x (double)x) over the whole state of vector j;  norms[b * T + j] = n_j (fp64, 8-byte aligned);
+ *   2. vector j is divided in place by (float)n_j with a true fp32 divide -- unless n_j is 0 or not finite (as fp64, or once converted to
+ *      fp32): then it is left unscaled and n_j is reported as it is;
+ *   3. for every i > j:  c = sum (double)q (double)x over (vector j after step 2, vector i), then x <- x - (float)c * q in fp32: one rounded
+ *      multiply and one rounded subtract.
+ * Every sum is fp64 in the renorm entry points' fixed order (two levels: runs of consecutive rows per workgroup, a thread's terms in
+ * ascending order and the 256 threads folded by halves; then the runs in ascending order), no atomics: bit-identical from call to call, a
+ * grid's result independent of its batch mates; with T = 1, norms and fields are bit-identical to the renorm entry point's, and for any T
+ * norms[b * T] and vector 0 are those of the T = 1 call.  A zero vector stays zero, reports norm 0 and leaves the later vectors as they
+ * were; a NaN makes the later vectors of its own grid NaN and touches no other grid.  The pitch padding is left alone.  2 T launches (the
+ * sum of squares of vector 0; per vector one pass that reports the norm, scales and forms the dot products with the later vectors, and,
+ * but for the last, one that updates the later vectors and sums the squares of the next).  All work is enqueued on `stream`, nothing is
+ * allocated, no synchronisation.  Limits: the renorm entry point's and T <= 8.  workspace: device memory of at least
+ * smk_tangent_orthonormalize_workspace(B, T, H, W) / smk_tangent3d_orthonormalize_workspace(B, T, D, H, W) bytes (-1 for an unsupported
+ * shape), 8-byte aligned, contents unspecified afterwards; a smaller one is refused with SMK_ERR_INVALID and nothing is written. */
+int64_t smk_tangent_orthonormalize_workspace(int32_t B, int32_t T, int32_t H, int32_t W);
+int smk_tangent_orthonormalize(float *tu, float *tv, float *tp, float *td, double *norms, int32_t B, int32_t T, int32_t H, int32_t W,
+                               int32_t pitch_c, int32_t pitch_v, void *workspace, int64_t workspace_bytes, void *stream);
+int64_t smk_tangent3d_orthonormalize_workspace(int32_t B, int32_t T, int32_t D, int32_t H, int32_t W);
+int smk_tangent3d_orthonormalize(float *tu, float *tv, float *tw, float *tp, float *td, double *norms, int32_t B, int32_t T, int32_t D,
+                                 int32_t H, int32_t W, int32_t pitch_c, int32_t pitch_v, void *workspace, int64_t workspace_bytes,
+                                 void *stream);
 
 /* NavierStokesSimulator.bilinear_interpolate(field, y, x) (navier_stokes.py:111-131; mode 0),
  * .interpolate_velocity_u(u, y, x) (:97-102; mode 1: x + 0.5 clamped to [0, w-1] first) and .interpolate_velocity_v(v, y, x)

@@ -88,6 +88,7 @@ class HipRoute:
     backward: Tuple[str, str, str, str]    # advect, project, buoy-diffuse backward and the projection's workspace query
     rule: object                      # the *_step_rule of route="torch"
     tangent: Tuple[str, str, str]     # advect tangent, tangent renorm and its workspace query (fluid_tangent.py, fluid_tangent3d.py)
+    orthonormalize: Tuple[str, str]   # Gram-Schmidt over a grid's tangents and its workspace query (csrc/tangent_qr.hip)
 
     def shapes(self, lead, grid):
         """The shapes of the components and of p beside a density lead + grid."""
@@ -97,7 +98,8 @@ class HipRoute:
 HIP2 = HipRoute(2, "fluid_step", "H, W", ("u", "v", "p", "density"), NavierStokesSimulator,
                 (_lib.STAGE_BUOY_DIFFUSE, _lib.STAGE_PROJECT, _lib.STAGE_ADVECT_U, _lib.STAGE_ADVECT_V, _lib.STAGE_ADVECT_D), ((1, 0), (0, 1), (0, 0)),
                 ("smk_advect_backward", "smk_project_backward", "smk_buoy_diffuse_backward", "smk_project_backward_workspace"),
-                fluid_step_rule, ("smk_advect_tangent", "smk_tangent_renorm", "smk_tangent_renorm_workspace"))
+                fluid_step_rule, ("smk_advect_tangent", "smk_tangent_renorm", "smk_tangent_renorm_workspace"),
+                ("smk_tangent_orthonormalize", "smk_tangent_orthonormalize_workspace"))
 
 _SIMS = {}
 

@@ -74,7 +74,8 @@ HIP3 = HipRoute(3, "fluid_step3d", "D, H, W", ("u", "v", "w", "p", "density"), N
                 (N.STAGE3D_BUOY_DIFFUSE, N.STAGE3D_PROJECT, N.STAGE3D_ADVECT_U, N.STAGE3D_ADVECT_V, N.STAGE3D_ADVECT_W, N.STAGE3D_ADVECT_D),
                 ((0, 1, 0), (0, 0, 1), (1, 0, 0), (0, 0, 0)),
                 ("smk_advect3d_backward", "smk_project3d_backward", "smk_buoy_diffuse3d_backward", "smk_project3d_backward_workspace"),
-                fluid_step3d_rule, ("smk_advect3d_tangent", "smk_tangent3d_renorm", "smk_tangent3d_renorm_workspace"))
+                fluid_step3d_rule, ("smk_advect3d_tangent", "smk_tangent3d_renorm", "smk_tangent3d_renorm_workspace"),
+                ("smk_tangent3d_orthonormalize", "smk_tangent3d_orthonormalize_workspace"))
 
 
 def fluid_step3d(u, v, w, p, density, *, dt: float = 0.01, viscosity: float = 0.001, jacobi_iters: int = 20, route: str = "hip"):

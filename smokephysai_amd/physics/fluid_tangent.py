@@ -10,6 +10,9 @@ Lyapunov exponents of the flow that come from it (Benettin's method).  DESIGN.md
   fluid_tangent_rollout(state, tangents, n)   n chained fluid_step_jvp calls; nothing is saved between steps.
   lyapunov_exponents(u, v, p, density, n)     the k largest Lyapunov exponents per unit time, with renormalisation every renorm_every
                                               steps -> LyapunovResult(exponents [B, k], log_growth [B, n_renorms, k], state, tangents).
+  flow_chaos(u, v, p, density, n)             the spectrum's three summaries -> FlowChaos(exponents sorted, lyapunov = the largest,
+                                              kaplan_yorke, ks_entropy, truncated, log_growth); kaplan_yorke_dimension and ks_entropy
+                                              are the two formulas on any spectrum (fp64 torch, any device).  DESIGN.md section 3.13.
 
 Where things live: the rule under forward_ad is fluid_grad.fluid_step_rule, i.e. physics/fluid_rule.py's 2-D instance; the state's staged
 forward, the shape check and the stepper cache are fluid_grad.py's (staged_forward, check_state, simulator over the record HIP2), shared
@@ -23,11 +26,14 @@ Unlike fluid_step's backward the hip route has no one-cell limit: the tangent of
 back-trace may move any number of cells.
 
 Hot path and what is not: for k = 1 the renormalisation is smk_tangent_renorm (two launches, no host synchronisation; the norms stay on
-the device until the end).  For k > 1 the tangents are re-orthonormalised by modified Gram-Schmidt in plain torch operations with fp64
-coefficients: that part is NOT a hot path (k (k + 1) / 2 reductions and updates per renormalisation).
+the device until the end).  For k > 1 the tangents are re-orthonormalised by modified Gram-Schmidt with fp64 coefficients: with
+gram_schmidt="torch" (lyapunov_exponents' default, as before) in plain torch operations, k (k + 1) / 2 reductions and updates per
+renormalisation and NOT a hot path; with gram_schmidt="hip" (flow_chaos' default on the hip route) by smk_tangent_orthonormalize
+(csrc/tangent_qr.hip: 2 k launches, no host synchronisation, the same rule operation for operation).
 
 Out of scope: torch.func.jvp / torch.autograd.forward_ad through fluid_step itself (call fluid_step_jvp), and the dataset labels (the
-`lyapunov_exponent` of get_chaos_features() stays the reference's frame-difference proxy).  The 3-D step is fluid_tangent3d.py."""
+`lyapunov_exponent` / `fractal_dimension` / `entropy` of get_chaos_features() and of the datasets stay the reference's proxies; a
+labels="flow" dataset mode that would put flow_chaos' quantities there is not built).  The 3-D step is fluid_tangent3d.py."""
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -37,7 +43,8 @@ import torch.autograd.forward_ad as fwad
 from .. import _lib
 from .fluid_grad import HIP2, Branches, check_state, simulator, staged_forward
 
-__all__ = ["LyapunovResult", "fluid_step_jvp", "fluid_step_jvp_rule", "fluid_tangent_rollout", "lyapunov_exponents"]
+__all__ = ["FlowChaos", "LyapunovResult", "flow_chaos", "fluid_step_jvp", "fluid_step_jvp_rule", "fluid_tangent_rollout",
+           "kaplan_yorke_dimension", "ks_entropy", "lyapunov_exponents"]
 
 MAX_K = 8
 MAX_PLANES = 65535          # B * T in 2-D, B * T * (D + 1) in 3-D: the launch grids' reach (include/smokehip.h)
@@ -261,12 +268,14 @@ def _renorm_torch(tangents):
 
 
 class _HipRenorm:
-    """smk_tangent_renorm / smk_tangent3d_renorm on tangents [B, 1, ...] in place, its workspace allocated once."""
+    """smk_tangent_renorm / smk_tangent3d_renorm on tangents [B, 1, ...] in place -- or, with entry = dim.orthonormalize,
+    smk_tangent_orthonormalize / smk_tangent3d_orthonormalize on tangents [B, T, ...] -- its workspace allocated once."""
 
-    def __init__(self, dim, B, T, grid, dev):
+    def __init__(self, dim, B, T, grid, dev, entry=None):
         self.L, self.dims, self.dev = _lib.load(), (B, T, *grid), dev
-        self.renorm = getattr(self.L, dim.tangent[1])
-        self.nbytes = int(getattr(self.L, dim.tangent[2])(B, T, *grid))
+        call, query = entry or dim.tangent[1:]
+        self.renorm = getattr(self.L, call)
+        self.nbytes = int(getattr(self.L, query)(B, T, *grid))
         if self.nbytes < 0:
             counted = "B * k" if dim.nd == 2 else "B * k * (D + 1)"
             raise ValueError(f"{_lyapunov_name(dim)}: B={B}, k={T}, grid {' x '.join(str(n) for n in grid)} is not supported "
@@ -289,11 +298,15 @@ def _draw_tangent0(state, k, seed):
 
 
 def route_lyapunov(dim, state, n_steps, k=1, renorm_every=1, tangent0=None, seed=0, dt=0.01, viscosity=0.001, jacobi_iters=20,
-                   route="hip", branches=None) -> LyapunovResult:
+                   route="hip", branches=None, gram_schmidt="torch") -> LyapunovResult:
     """lyapunov_exponents / lyapunov_exponents3d: Benettin's loop over the dimension record."""
     what = _lyapunov_name(dim)
     if route not in ("hip", "torch"):
         raise ValueError(f"{what}: route is 'hip' or 'torch', got {route!r}")
+    if gram_schmidt not in ("hip", "torch"):
+        raise ValueError(f"{what}: gram_schmidt is 'torch' or 'hip', got {gram_schmidt!r}")
+    if gram_schmidt == "hip" and route != "hip":
+        raise ValueError(f"{what}: gram_schmidt='hip' goes with route='hip'")
     if not 1 <= int(k) <= MAX_K:
         raise ValueError(f"{what}: 1 <= k <= {MAX_K}, got {k}")
     if n_steps < 1 or renorm_every < 1 or n_steps % renorm_every:
@@ -320,12 +333,12 @@ def route_lyapunov(dim, state, n_steps, k=1, renorm_every=1, tangent0=None, seed
     if hip:
         _check_hip(state, tangents, jacobi_iters, what)
     norms = torch.empty(n_renorms + 1, B, k, dtype=torch.float64, device=state[-1].device)
-    if k > 1:
+    if k > 1 and gram_schmidt == "torch":
         def renorm(ts, i):
             ts, norms[i] = _gram_schmidt(ts)
             return ts
-    elif hip:
-        hip_renorm = _HipRenorm(dim, B, 1, grid, state[-1].device)
+    elif hip:                                                # (k = 1: the renorm entry point; the orthonormalisation at T = 1 is the same bits)
+        hip_renorm = _HipRenorm(dim, B, k, grid, state[-1].device, dim.orthonormalize if k > 1 else None)
 
         def renorm(ts, i):
             return hip_renorm(ts, norms[i])
@@ -357,13 +370,72 @@ def route_lyapunov(dim, state, n_steps, k=1, renorm_every=1, tangent0=None, seed
 
 def lyapunov_exponents(u, v, p, density, n_steps: int, *, k: int = 1, renorm_every: int = 1, tangent0=None, seed: int = 0,
                        dt: float = 0.01, viscosity: float = 0.001, jacobi_iters: int = 20, route: str = "hip",
-                       branches: Optional[Branches] = None) -> LyapunovResult:
+                       branches: Optional[Branches] = None, gram_schmidt: str = "torch") -> LyapunovResult:
     """The k largest Lyapunov exponents of the flow from the state (u, v, p, density), by Benettin's method: k tangent states are pushed
     through n_steps tangent-linear steps (fluid_step_jvp) beside the state and renormalised every renorm_every steps (n_steps must be a
     multiple); the exponents are the summed logs of the growth factors per unit time, n_steps * dt.  k = 1: smk_tangent_renorm on the
-    hip route.  1 < k <= 8: modified Gram-Schmidt in torch operations with fp64 coefficients (module docstring: not a hot path).
+    hip route.  1 < k <= 8: modified Gram-Schmidt with fp64 coefficients -- gram_schmidt="torch" (the default): in torch operations
+    (module docstring: not a hot path); gram_schmidt="hip" (route="hip" only): smk_tangent_orthonormalize, 2 k launches, the same rule.
     tangent0: (tu, tv, tp, tdensity), state-shaped (k = 1) or [B, k, ...]; default: unit-normal noise drawn on the CPU from `seed`.  It is
     normalised (orthonormalised) first, so its scale does not matter.  route="torch": the rule, any dtype and device; branches: a
     Branches recorder / replayer handed to every step of that route (the tests' fp64 run along the fp32 run's decisions).
     The hip route synchronises once, at the end, to check the steppers' status."""
-    return route_lyapunov(HIP2, (u, v, p, density), n_steps, k, renorm_every, tangent0, seed, dt, viscosity, jacobi_iters, route, branches)
+    return route_lyapunov(HIP2, (u, v, p, density), n_steps, k, renorm_every, tangent0, seed, dt, viscosity, jacobi_iters, route, branches,
+                          gram_schmidt)
+
+
+# ------------------------------------------------------------------------------------------------ the spectrum's summaries
+@dataclass
+class FlowChaos:
+    """What the first k Lyapunov exponents say about a flow, per grid (un-batched states: without the B).  exponents [B, k] fp64 per unit
+    time, sorted descending; lyapunov [B] = exponents[:, 0]; kaplan_yorke [B]: kaplan_yorke_dimension(exponents), a lower bound where
+    truncated [B] (bool) is set -- the partial sums did not turn negative within k; ks_entropy [B]: the sum of the positive exponents
+    (Pesin's bound on the Kolmogorov-Sinai entropy); log_growth [B, n_renorms, k]: LyapunovResult's, in Gram-Schmidt order."""
+    exponents: torch.Tensor
+    lyapunov: torch.Tensor
+    kaplan_yorke: torch.Tensor
+    ks_entropy: torch.Tensor
+    truncated: torch.Tensor
+    log_growth: torch.Tensor
+
+
+def kaplan_yorke_dimension(exponents):
+    """The Kaplan-Yorke (Lyapunov) dimension of spectra [..., k] -> (D [...] fp64, truncated [...] bool).  The exponents are sorted
+    descending first; with S_j = the sum of the j largest, j* the largest j with S_j >= 0:  D = j* + S_j* / |lambda_(j*+1)|;  D = 0 where
+    the largest exponent is negative;  where S_k >= 0 there is no crossing within the k exponents given: D = k and truncated is set -- a
+    lower bound.  A spectrum holding a NaN gives NaN."""
+    lam = torch.as_tensor(exponents).to(torch.float64).sort(dim=-1, descending=True).values
+    k = lam.shape[-1]
+    sums = lam.cumsum(dim=-1)
+    j = (sums >= 0).sum(dim=-1)                              # (sorted descending, the sums rise and then fall: S_j >= 0 holds on a prefix)
+    inside = (j > 0) & (j < k)
+    s_j = sums.gather(-1, (j - 1).clamp(0, k - 1)[..., None])[..., 0]
+    l_next = lam.gather(-1, j.clamp(0, k - 1)[..., None])[..., 0].abs()
+    frac = torch.where(inside, s_j / torch.where(inside, l_next, torch.ones_like(l_next)), torch.zeros_like(s_j))
+    dim = j.to(torch.float64) + frac
+    return torch.where(torch.isnan(lam).any(dim=-1), torch.full_like(dim, float("nan")), dim), j == k
+
+
+def ks_entropy(exponents):
+    """The sum of the positive exponents of spectra [..., k] -> [...] fp64: Pesin's upper bound on the Kolmogorov-Sinai entropy."""
+    return torch.as_tensor(exponents).to(torch.float64).clamp_min(0).sum(dim=-1)
+
+
+def route_flow_chaos(dim, state, n_steps, k=4, renorm_every=1, seed=0, dt=0.01, viscosity=0.001, jacobi_iters=20, route="hip",
+                     gram_schmidt=None) -> FlowChaos:
+    """flow_chaos / flow_chaos3d: the spectrum, then the formulas."""
+    if gram_schmidt is None:
+        gram_schmidt = "hip" if route == "hip" else "torch"
+    res = route_lyapunov(dim, state, n_steps, k, renorm_every, None, seed, dt, viscosity, jacobi_iters, route, None, gram_schmidt)
+    exponents = res.exponents.sort(dim=-1, descending=True).values
+    ky, truncated = kaplan_yorke_dimension(exponents)
+    return FlowChaos(exponents, exponents[..., 0], ky, ks_entropy(exponents), truncated, res.log_growth)
+
+
+def flow_chaos(u, v, p, density, n_steps: int, *, k: int = 4, renorm_every: int = 1, seed: int = 0, dt: float = 0.01,
+               viscosity: float = 0.001, jacobi_iters: int = 20, route: str = "hip", gram_schmidt: Optional[str] = None) -> FlowChaos:
+    """The dynamical-systems counterparts of the three chaos labels from the state (u, v, p, density): the k largest Lyapunov exponents
+    by lyapunov_exponents (same keywords; tangent0 drawn from `seed`) -> FlowChaos: the largest exponent, the Kaplan-Yorke dimension of
+    the attractor and the Kolmogorov-Sinai entropy bound.  gram_schmidt: None = "hip" (smk_tangent_orthonormalize) on route="hip",
+    "torch" on route="torch"; or either by name.  k exponents bound the dimension by k: see FlowChaos.truncated."""
+    return route_flow_chaos(HIP2, (u, v, p, density), n_steps, k, renorm_every, seed, dt, viscosity, jacobi_iters, route, gram_schmidt)

@@ -114,6 +114,22 @@ class SmokeSimulator(nn.Module):
         res = lyapunov_exponents(*ns.state(), n_steps, k=1, dt=ns.dt, viscosity=ns.viscosity, jacobi_iters=ns.jacobi_iters, **kw)
         return res.exponents[:, 0] if self.batch_size is not None else float(res.exponents[0, 0])
 
+    def flow_chaos(self, n_steps: int = 20, k: int = 4, **kw):
+        """The k largest Lyapunov exponents of the flow from the simulator's CURRENT state and what they say about it: physics.flow_chaos
+         over n_steps further steps, run on clones -- the simulator, its history and get_chaos_features() (whose
+        three labels stay the reference's proxies) are untouched, as with flow_lyapunov.  kw: flow_chaos's keywords (renorm_every, seed,
+        route, gram_schmidt).  Batched: a FlowChaos of fp64 tensors [B, ...].  Un-batched: a dict of floats -- "lyapunov" (the largest
+        exponent per unit time), "kaplan_yorke" (the attractor's dimension; a lower bound where "truncated" is True), "ks_entropy" (the
+        sum of the positive exponents) -- with "exponents", the k floats sorted descending."""
+        from .fluid_tangent import flow_chaos
+        ns = self.ns_solver
+        ns.check()
+        res = flow_chaos(*ns.state(), n_steps, k=k, dt=ns.dt, viscosity=ns.viscosity, jacobi_iters=ns.jacobi_iters, **kw)
+        if self.batch_size is not None:
+            return res
+        return {"lyapunov": float(res.lyapunov[0]), "kaplan_yorke": float(res.kaplan_yorke[0]), "ks_entropy": float(res.ks_entropy[0]),
+                "truncated": bool(res.truncated[0]), "exponents": [float(x) for x in res.exponents[0]]}
+
     def _single_grid(self, what):
         if self.batch_size is not None:
             raise ValueError(f"{what}: batched simulator -- use get_chaos_features(), which returns one dict per grid")
