@@ -403,6 +403,38 @@ int64_t smk_tangent3d_orthonormalize_workspace(int32_t B, int32_t T, int32_t D, 
 int smk_tangent3d_orthonormalize(float *tu, float *tv, float *tw, float *tp, float *td, double *norms, int32_t B, int32_t T, int32_t D,
                                  int32_t H, int32_t W, int32_t pitch_c, int32_t pitch_v, void *workspace, int64_t workspace_bytes,
                                  void *stream);
+/* The flow map of the 2-D stepper and its finite-time Lyapunov exponent (FTLE).  A displacement field disp [B][2][H][pitch_m] = (dx, dy) at
+ * the cell centres, in cells, stands for the map x -> x + disp; u [B][H+1][pitch_c] and v [B][H][pitch_v] are the layout of smk_advect (a
+ * simulator's own stores may be passed as they are).  fp32, caller-owned, 4-byte aligned and no better; 1 <= B <= 65535, 3 <= H, W <=
+ * 32766, pitch_c >= W, pitch_v >= W + 1, pitch_m >= W.  fp32 with one rounding per listed operation, no atomics, every element
+ * [row][col < W] of an output written, the pitch padding neither read nor written, bit-identical from call to call, a grid independent of
+ * its batch mates.  All work is enqueued on `stream`, nothing is allocated, no synchronisation.
+ *
+ * smk_flow_map_step: one step's first-order trace composed into the map; called after every step() with that step's output velocities (the
+ *   ones its density advection sampled).  One launch, one thread per cell (Y, X).  disp_out aliases no input.
+ *   direction 0, backward (x + disp: where the particle now at x was when the window began):  su, sv = the density advection's velocity
+ *     samples at the cell;  ax = X - dt su,  px = clamp(ax, 0, W - 1);  ix = -(dt su) where 0 <= ax <= W - 1 (bounds included), px - X
+ *     otherwise;  dx' = bilinear(dx; py, px) + ix;  y likewise, dy' from bilinear(dy; py, px).  Samples, back-trace, clamp decisions, taps
+ *     and weights are the density advection's, bit for bit (floor, clamped indices, weights from the clamped indices: a position on the
+ *     last index reads 0).
+ *   direction 1, forward (x + disp: where the particle that began at x is now):  qx = clamp(X + dx, 0, W - 1), qy likewise (sample
+ *     positions only);  su = interpolate_velocity_u(u, qy, qx), sv = interpolate_velocity_v(v, qy, qx) as smk_interpolate forms them;
+ *     dx' = min(max(dx + dt su, -X), W - 1 - X);  y likewise.
+ * smk_ftle_field: ftle [B][H][pitch_m] of the map, and stats [B][2] = (mean, max) of each grid's field in fp64 (8-byte aligned).  With
+ *   a = dx, b = dy and their differences at unit spacing (central with a factor 0.5 inside, one-sided on the first and last row and column):
+ *     exx = a_x + 0.5 (a_x a_x + b_x b_x);  eyy = b_y + 0.5 (a_y a_y + b_y b_y);  exy = 0.5 (a_y + b_x) + 0.5 (a_x a_y + b_x b_y);
+ *     m = 0.5 (exx + eyy);  d = 0.5 (exx - eyy);  emax = m + sqrt(d d + exy exy);
+ *     ftle = log1p(max(2 emax, lo)) / (float)(2 horizon),  lo = -1 + 2^-24 (the fp32 number next above -1), a true fp32 divide.
+ *   horizon > 0: the window's length in time units, n_steps * dt.  The sum is fp64 in smk_tangent_renorm's fixed order (two levels: runs
+ *   of consecutive rows per workgroup, a thread's values in ascending order and the 256 threads folded by halves; then the runs in
+ *   ascending order by one thread), the maximum alongside (a NaN wins).  Two launches.  workspace: device memory of at least
+ *   smk_ftle_workspace(B, H, W) bytes (-1 for an unsupported shape), 8-byte aligned, contents unspecified afterwards; a smaller or
+ *   misaligned one is refused with SMK_ERR_INVALID and nothing is written.  ftle does not alias disp. */
+int smk_flow_map_step(int32_t direction, const float *u, const float *v, const float *disp_in, float *disp_out, int32_t B, int32_t H,
+                      int32_t W, int32_t pitch_c, int32_t pitch_v, int32_t pitch_m, double dt, void *stream);
+int64_t smk_ftle_workspace(int32_t B, int32_t H, int32_t W);
+int smk_ftle_field(const float *disp, float *ftle, double *stats, int32_t B, int32_t H, int32_t W, int32_t pitch_m, double horizon,
+                   void *workspace, int64_t workspace_bytes, void *stream);
 
 /* NavierStokesSimulator.bilinear_interpolate(field, y, x) (navier_stokes.py:111-131; mode 0),
  * .interpolate_velocity_u(u, y, x) (:97-102; mode 1: x + 0.5 clamped to [0, w-1] first) and .interpolate_velocity_v(v, y, x)

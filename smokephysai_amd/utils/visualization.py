@@ -1,5 +1,6 @@
 """Figures of the reference's src/utils/visualization.py (SmokeVisualizer: the same three methods and argument names), drawn with
-matplotlib alone, and plot_turntable, a row of orbit views of one volume (physics.render_orbit), which the reference has no like of.  The attention panel takes what SmokePhysNet.attention_maps returns: the full [B, heads, L, L] weights as in the
+matplotlib alone, and two the reference has no like of: plot_turntable, a row of orbit views of one volume (physics.render_orbit), and
+plot_ftle, a frame beside the finite-time Lyapunov exponent field of its flow (physics.flow_ftle).  The attention panel takes what SmokePhysNet.attention_maps returns: the full [B, heads, L, L] weights as in the
 reference, or the `received` map [B, heads, h, w] the libsmokehip kernels produce without ever forming an L x L tensor.
 Without a display the Agg backend is used; plt.show() is called only on an interactive backend."""
 import math
@@ -109,6 +110,33 @@ class SmokeVisualizer:
             ax.axis("off")
             fig.colorbar(im, ax=ax)
         return _finish(fig, save_path)
+
+    def plot_ftle(self, frame, ftle, path: Optional[str] = None):
+        """The frame, the finite-time Lyapunov exponent field of its flow (physics.flow_ftle) and the field's upper decile as a contour
+        over the frame: where the backward field's ridges lie, smoke filaments collect.  frame, ftle: [H, W] arrays or tensors (leading
+        dimensions of size 1, or a batch whose first entry is drawn, are dropped as plot_attention_maps drops them).  A constant field
+        has no upper decile and gets no contour."""
+        img, field = _numpy(frame), _numpy(ftle)
+        while img.ndim > 2:
+            img = img[0]
+        while field.ndim > 2:
+            field = field[0]
+        if img.shape != field.shape:
+            raise ValueError(f"plot_ftle: frame and ftle must have one shape, got {img.shape} and {field.shape}")
+        fig, axes = plt.subplots(1, 3, figsize=(15, 5))
+        axes[0].imshow(img, cmap="hot")
+        axes[0].set_title("Input Smoke")
+        im = axes[1].imshow(field, cmap="plasma")
+        axes[1].set_title("FTLE")
+        fig.colorbar(im, ax=axes[1])
+        axes[2].imshow(img, cmap="hot")
+        level = float(np.quantile(field, 0.9))
+        if np.isfinite(level) and float(field.max()) > level:
+            axes[2].contour(field, levels=[level], colors="cyan", linewidths=1.0)
+        axes[2].set_title("FTLE Upper Decile")
+        for ax in axes:
+            ax.axis("off")
+        return _finish(fig, path)
 
     def plot_turntable(self, frames, azimuths, save_path: Optional[str] = None):
         """One 'hot' panel per orbit view (render_orbit's [V, H, W] frames of one volume), at most 8 per row, titled by the view's azimuth in
