@@ -435,6 +435,49 @@ int smk_flow_map_step(int32_t direction, const float *u, const float *v, const f
 int64_t smk_ftle_workspace(int32_t B, int32_t H, int32_t W);
 int smk_ftle_field(const float *disp, float *ftle, double *stats, int32_t B, int32_t H, int32_t W, int32_t pitch_m, double horizon,
                    void *workspace, int64_t workspace_bytes, void *stream);
+/* The flow map of the 3-D stepper and its FTLE: the counterparts of the three entry points above for volumes.  A displacement
+ * disp [B][3][D][H][pitch_m] = (dx, dy, dz) at the cell centres, in cells, stands for the map x -> x + disp; component k acts along the
+ * axis velocity component k acts along (dx along W, dy along H, dz along D).  u [B][D][H+1][pitch_c], v [B][D][H][pitch_v] and
+ * w [B][D+1][H][pitch_c] are the layout of smk_advect3d_tangent (a 3-D simulator's own stores may be passed as they are).  fp32,
+ * caller-owned, 4-byte aligned and no better.  Limits: those of smk_advect3d_tangent with T = 1 (B >= 1, 3 <= D, H, W <= 32766,
+ * B * (D + 1) <= 65535, pitch_c >= W, pitch_v >= W + 1, (D + 1) * (H + 1) * pitch_c and ... * pitch_v < 2^31), pitch_m >= W and
+ * D * H * pitch_m < 2^31.  fp32 with one rounding per listed operation, no atomics, every element [plane][row][col < W] of an output
+ * written, the pitch padding neither read nor written, bit-identical from call to call, a grid independent of its batch mates; every
+ * index is clamped before use, so no position -- NaN and +-inf included -- reads outside its volume.  All work is enqueued on `stream`,
+ * nothing is allocated, no synchronisation.
+ *
+ * smk_flow_map3d_step: one step's first-order trace composed into the map; called after every step() with that step's output velocities.
+ *   One launch, one thread per cell (Z, Y, X).  disp_out aliases no input.
+ *   direction 0, backward:  su, sv, sw = the density advection's velocity samples at the cell;  per axis a = X - dt s,
+ *     p = clamp(a, 0, n - 1), in the order px, py, pz;  the increment i = -(dt s) where 0 <= a <= n - 1 (bounds included), p - X otherwise;
+ *     d' = trilinear(d; pz, py, px) + i for each of dx, dy, dz, at one set of eight taps.  Samples, back-trace, clamp decisions, taps and
+ *     weights are the density advection's, bit for bit (floor, clamped indices, weights (wx wy) wz from the clamped indices: a position
+ *     on the last index reads 0).
+ *   direction 1, forward:  per axis q = clamp(X + d, 0, n - 1) (sample positions only);  s = the component sampled at (qz, qy, qx): +0.5
+ *     along the axis it acts on, every coordinate clamped to the component's extent, then the trilinear taps;
+ *     d' = min(max(d + dt s, -X), n - 1 - X).
+ * smk_ftle3d_field: ftle [B][D][H][pitch_m] of the map, and stats [B][2] = (mean, max) of each grid's field in fp64 (8-byte aligned).
+ *   With g[k][j] the difference of component k along axis j (x, y, z) at unit spacing (central with a factor 0.5 inside, one-sided on the
+ *   first and last index of each axis):
+ *     E_ii = g[i][i] + 0.5 ((g[x][i] g[x][i] + g[y][i] g[y][i]) + g[z][i] g[z][i]);
+ *     E_ij = 0.5 (g[i][j] + g[j][i]) + 0.5 ((g[x][i] g[x][j] + g[y][i] g[y][j]) + g[z][i] g[z][j]);
+ *     emax = the largest eigenvalue of E by cyclic Jacobi: exactly 4 sweeps of the rotations (x, y), (x, z), (y, z), no early exit; a
+ *       rotation (p, q; r the third index):  theta = (a_qq - a_pp) / (2 a_pq);  t = sign(theta) / (|theta| + sqrt(theta theta + 1)),
+ *       sign(theta) = +1 for theta >= 0;  where a_pq == 0 the divide is by 1 and t = 0;  c = 1 / sqrt(t t + 1), s = t c;
+ *       a_pp -= t a_pq, a_qq += t a_pq, a_pq = 0;  a_rp' = c a_rp - s a_rq, a_rq' = s a_rp + c a_rq (correctly rounded divides and square
+ *       roots);  emax = the maximum of the three diagonal entries (a NaN wins);
+ *     ftle = log1p(max(2 emax, lo)) / (float)(2 horizon),  lo = -1 + 2^-24, a true fp32 divide.
+ *   horizon > 0 (and finite as fp32): the window's length in time units.  The sum is fp64 in smk_tangent_renorm's fixed order (two levels:
+ *   the grid's D H rows, planes before rows, in runs of at least 16 consecutive rows for at most 256 workgroups, a thread's values in
+ *   ascending order and the 256 threads folded by halves; then the runs in ascending order by one thread), the maximum alongside (a NaN
+ *   wins).  Two launches.  workspace: device memory of at least smk_ftle3d_workspace(B, D, H, W) bytes (-1 for an unsupported shape),
+ *   8-byte aligned, contents unspecified afterwards; a smaller or misaligned one is refused with SMK_ERR_INVALID and nothing is written.
+ *   ftle does not alias disp. */
+int smk_flow_map3d_step(int32_t direction, const float *u, const float *v, const float *w, const float *disp_in, float *disp_out, int32_t B,
+                        int32_t D, int32_t H, int32_t W, int32_t pitch_c, int32_t pitch_v, int32_t pitch_m, double dt, void *stream);
+int64_t smk_ftle3d_workspace(int32_t B, int32_t D, int32_t H, int32_t W);
+int smk_ftle3d_field(const float *disp, float *ftle, double *stats, int32_t B, int32_t D, int32_t H, int32_t W, int32_t pitch_m,
+                     double horizon, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* NavierStokesSimulator.bilinear_interpolate(field, y, x) (navier_stokes.py:111-131; mode 0),
  * .interpolate_velocity_u(u, y, x) (:97-102; mode 1: x + 0.5 clamped to [0, w-1] first) and .interpolate_velocity_v(v, y, x)

@@ -115,6 +115,8 @@ _SIGNATURES = {
     "smk_tangent3d_orthonormalize": [C.c_void_p] * 6 + [C.c_int32] * 7 + [C.c_void_p, C.c_int64, C.c_void_p],
     "smk_flow_map_step": [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] * 6 + [C.c_double, C.c_void_p],
     "smk_ftle_field": [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_double, C.c_void_p, C.c_int64, C.c_void_p],
+    "smk_flow_map3d_step": [C.c_int32] + [C.c_void_p] * 5 + [C.c_int32] * 7 + [C.c_double, C.c_void_p],
+    "smk_ftle3d_field": [C.c_void_p] * 3 + [C.c_int32] * 5 + [C.c_double, C.c_void_p, C.c_int64, C.c_void_p],
     "smk_advect3d_backward": [C.c_int32] + [C.c_void_p] * 10 + [C.c_int32] * 6 + [C.c_double, C.c_void_p],
     "smk_project3d_backward": [C.c_void_p] * 8 + [C.c_int32] * 7 + [C.c_double, C.c_void_p, C.c_int64, C.c_void_p],
     "smk_buoy_diffuse3d_backward": [C.c_void_p] * 8 + [C.c_int32] * 6 + [C.c_double, C.c_double, C.c_void_p],
@@ -230,7 +232,7 @@ EXPORTS = ["smk_abi_version", "smk_last_error", "smk_linear_wgrad_workspace", "s
            "smk_conv3_sigmoid_train_workspace", "smk_flow_levels", "smk_flow_farneback_workspace", "smk_warp_workspace",
            "smk_flow_lk_workspace", "smk_volume_render_workspace", "smk_volume_render_backward_workspace", "smk_volume_render_orbit_workspace", "smk_volume_render_orbit_backward_workspace", "smk_volume_render_camera_workspace", "smk_volume_render_camera_backward_workspace", "smk_conv3d_train_workspace", "smk_conv3d_cl_wgrad_workspace",
            "smk_bn_cl_workspace", "smk_project_backward_workspace", "smk_project3d_backward_workspace", "smk_tangent_renorm_workspace", "smk_tangent3d_renorm_workspace",
-           "smk_tangent_orthonormalize_workspace", "smk_tangent3d_orthonormalize_workspace", "smk_ftle_workspace"] + list(_SIGNATURES)
+           "smk_tangent_orthonormalize_workspace", "smk_tangent3d_orthonormalize_workspace", "smk_ftle_workspace", "smk_ftle3d_workspace"] + list(_SIGNATURES)
 
 _lib = None
 
@@ -324,6 +326,8 @@ def load():
         L.smk_tangent3d_orthonormalize_workspace.restype = C.c_int64
         L.smk_ftle_workspace.argtypes = [C.c_int32] * 3
         L.smk_ftle_workspace.restype = C.c_int64                  # a byte count; -1 = unsupported shape
+        L.smk_ftle3d_workspace.argtypes = [C.c_int32] * 4
+        L.smk_ftle3d_workspace.restype = C.c_int64
         L.smk_flow_levels.argtypes = [C.c_int32] * 2
         L.smk_flow_levels.restype = C.c_int32                     # a level count, not a status
         for name in ("smk_flow_farneback_workspace", "smk_warp_workspace", "smk_flow_lk_workspace"):

@@ -23,8 +23,24 @@ hipError_t launch_flow_map(const Geom &g, int pm, int dir, const float *u, const
 // disp [B][2][H][pm] -> ftle [B][H][pm], stats [B][2] (mean, max).  partial: g.B * fm_groups(g.H) * 2 doubles.  Two launches.
 hipError_t launch_ftle(const Geom &g, int pm, float two_horizon, const float *disp, float *ftle, double *stats, double *partial,
                        hipStream_t st);
+// Level two of the FTLE's statistics, shared with csrc/flow_map3d.hip: partial [B][P][2] (sum, max) -> stats [B][2] (sum / cells, max),
+// one thread per grid, the P runs in ascending order.  One launch.
+hipError_t launch_ftle_stats(int B, int P, double cells, const double *partial, double *stats, hipStream_t st);
 
 namespace {
+
+// d f / d i at unit spacing, f pointing at element i of n, `stride` elements apart: central with a factor 0.5 inside, one-sided at both ends.
+__device__ __forceinline__ float diff_at(const float *f, int i, int n, size_t stride) {
+    if (i == 0) return f[stride] - f[0];
+    if (i == n - 1) return f[0] - *(f - stride);
+    return 0.5f * (f[stride] - *(f - stride));
+}
+// max in which a NaN wins (torch's convention), so a grid holding one reports it
+__device__ __forceinline__ double nanmax(double a, double b) {
+    if (a != a) return a;
+    if (b != b) return b;
+    return a > b ? a : b;
+}
 
 // interpolate_velocity_u / _v (navier_stokes.py:97-109) at a position (y, x) in cells, as csrc/stencil.hip's k_interp forms them: the
 // +0.5 shift along the axis the component acts on, that coordinate clamped to the component's extent, then bilinear()'s taps.  (The other

@@ -53,19 +53,6 @@ __global__ __launch_bounds__(FT_NT) void k_flow_map(Geom g, int pm, const float 
 }
 
 // ---------------------------------------------------------------- the FTLE of a displacement field
-// d f / d i at unit spacing, f pointing at element i of n, `stride` elements apart: central with a factor 0.5 inside, one-sided at both ends.
-__device__ __forceinline__ float diff_at(const float *f, int i, int n, size_t stride) {
-    if (i == 0) return f[stride] - f[0];
-    if (i == n - 1) return f[0] - *(f - stride);
-    return 0.5f * (f[stride] - *(f - stride));
-}
-// max in which a NaN wins (torch's convention), so a grid holding one reports it
-__device__ __forceinline__ double nanmax(double a, double b) {
-    if (a != a) return a;
-    if (b != b) return b;
-    return a > b ? a : b;
-}
-
 // Level one: workgroup (p, b) owns rows [p * rpg, (p + 1) * rpg) of grid b.  Wave w takes the rows w, w + 4, ... of the run, lane l their
 // columns l, l + 64, ...  Per cell, with a = dx, b = dy and G = [[a_x, a_y], [b_x, b_y]] their differences, the Green-Lagrange strain
 // E = (G + G^T + G^T G) / 2 formed so that the identity never enters, its larger eigenvalue, and
@@ -137,13 +124,16 @@ hipError_t launch_flow_map(const Geom &g, int pm, int dir, const float *u, const
     return hipGetLastError();
 }
 
+hipError_t launch_ftle_stats(int B, int P, double cells, const double *partial, double *stats, hipStream_t st) {
+    hipLaunchKernelGGL(k_ftle_stats, dim3((unsigned)cdiv(B, 64)), dim3(64), 0, st, B, P, cells, partial, stats);
+    return hipGetLastError();
+}
+
 hipError_t launch_ftle(const Geom &g, int pm, float two_horizon, const float *disp, float *ftle, double *stats, double *partial,
                        hipStream_t st) {
     const int rpg = fm_rows_per_group(g.H), P = fm_groups(g.H);
     hipLaunchKernelGGL(k_ftle, dim3((unsigned)P, (unsigned)g.B), dim3(FT_NT), 0, st, g, pm, rpg, two_horizon, disp, ftle, partial);
-    hipLaunchKernelGGL(k_ftle_stats, dim3((unsigned)cdiv(g.B, 64)), dim3(64), 0, st, g.B, P, (double)g.H * (double)g.W,
-                       (const double *)partial, stats);
-    return hipGetLastError();
+    return launch_ftle_stats(g.B, P, (double)g.H * (double)g.W, partial, stats, st);
 }
 
 }  // namespace smk

@@ -34,17 +34,22 @@ column), the Green-Lagrange strain formed so that the identity never enters --
   ftle = log1p(max(2 emax, lo)) / (2 horizon),  lo = the fp32 number next above -1 (so the result is finite).
 Values may be negative where the map contracts in every direction: the projected velocities are only approximately divergence-free.
 
-Out of scope: the 3-D counterpart, a dataset label built from the statistics, derivatives of the map, higher-order particle integration (the
-stepper's own first-order trace is the flow being described)."""
+Where things live: what the flow map of a 2-D and of a 3-D stepper share -- the direction, route and window checks, the shape checks, the
+result packing, the single calls and the chained loop -- is written once here over a MapRoute record (fluid_grad's HipRoute, the two rules
+and the entry points' names): the route_* functions.  The public functions below bind them to MAP2, those of flow_map3d.py (DESIGN.md
+section 3.15, which also has the 3-D rule) to MAP3.
+
+Out of scope: a dataset label built from the statistics, derivatives of the map, higher-order particle integration (the stepper's own
+first-order trace is the flow being described)."""
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from typing import Callable, Optional, Tuple
 
 import numpy as np
 import torch
 
 from .. import _lib
 from . import fluid_rule
-from .fluid_grad import HIP2, Branches, check_state, simulator
+from .fluid_grad import HIP2, Branches, HipRoute, check_state, simulator
 
 __all__ = ["FtleResult", "flow_ftle", "flow_ftle_rule", "flow_map_step", "flow_map_step_rule", "ftle_field", "ftle_rule"]
 
@@ -67,24 +72,25 @@ def _direction(direction, what):
     return DIRECTIONS[direction]
 
 
-def _check_disp(disp, u, v, what):
-    """Shapes of one map step's operands (leading dimensions: [B] or none) -> (H, W)."""
-    if disp.dim() not in (3, 4) or disp.shape[-3] != 2:
-        raise ValueError(f"{what}: disp must be [2, H, W] or [B, 2, H, W], got {tuple(disp.shape)}")
-    lead, (H, W) = tuple(disp.shape[:-3]), disp.shape[-2:]
-    for name, t, want in (("u", u, lead + (H + 1, W)), ("v", v, lead + (H, W + 1))):
+def _check_disp(dim, disp, vel, what):
+    """Shapes of one map step's operands (leading dimensions: [B] or none) over the dimension record -> the grid (H, W) or (D, H, W)."""
+    nd = dim.nd
+    if disp.dim() not in (nd + 1, nd + 2) or disp.shape[-nd - 1] != nd:
+        raise ValueError(f"{what}: disp must be [{nd}, {dim.axes}] or [B, {nd}, {dim.axes}], got {tuple(disp.shape)}")
+    lead, grid = tuple(disp.shape[:-nd - 1]), tuple(disp.shape[-nd:])
+    for name, t, want in zip(dim.fields, vel, dim.shapes(lead, grid)):
         if tuple(t.shape) != want:
             raise ValueError(f"{what}: {name} must be {want} beside disp {tuple(disp.shape)}, got {tuple(t.shape)}")
-    if min(H, W) < 3:
-        raise ValueError(f"{what}: H, W >= 3")
-    return H, W
+    if min(grid) < 3:
+        raise ValueError(f"{what}: {dim.axes} >= 3")
+    return grid
 
 
 def flow_map_step_rule(disp, u, v, *, dt: float = 0.01, direction: str = "backward", branches: Optional[Branches] = None):
     """One map step in torch ops (module docstring): disp [..., 2, H, W], u [..., H+1, W], v [..., H, W+1] of any floating dtype on any
     device -> disp'.  branches: a Branches recorder (filled) or replayer (followed); None: decisions are made and not kept."""
     forward = _direction(direction, "flow_map_step_rule")
-    H, W = _check_disp(disp, u, v, "flow_map_step_rule")
+    H, W = _check_disp(HIP2, disp, (u, v), "flow_map_step_rule")
     br = Branches() if branches is None else branches
     Y, X = torch.meshgrid(*[torch.arange(n, dtype=disp.dtype, device=disp.device) for n in (H, W)], indexing="ij")
     dx, dy = disp[..., 0, :, :], disp[..., 1, :, :]
@@ -107,11 +113,11 @@ def flow_map_step_rule(disp, u, v, *, dt: float = 0.01, direction: str = "backwa
     return moved + torch.stack([ix, iy], dim=-3)
 
 
-def _differences(f):
-    """(d f / d x, d f / d y) of f [..., H, W] at unit spacing: central with a factor 0.5 inside, one-sided on the first and last row and
-    column."""
+def _differences(f, nd=2):
+    """(d f / d x, d f / d y) -- with nd = 3 also d f / d z -- of f [..., H, W] at unit spacing: central with a factor 0.5 inside, one-sided
+    on the first and last index of each axis."""
     out = []
-    for dim in (-1, -2):
+    for dim in (-1, -2, -3)[:nd]:
         n = f.shape[dim]
         inner = 0.5 * (f.narrow(dim, 2, n - 2) - f.narrow(dim, 0, n - 2))
         first = f.narrow(dim, 1, 1) - f.narrow(dim, 0, 1)
@@ -140,12 +146,28 @@ def ftle_rule(disp, horizon: float):
 @dataclass
 class FtleResult:
     """ftle [B, H, W]: the field, per unit time.  displacement [B, 2, H, W]: the map's (dx, dy) in cells.  mean, max [B] fp64: of each
-    grid's field.  state: (u, v, p, density) after the last step.  Un-batched states: everything without the B."""
+    grid's field.  state: (u, v, p, density) after the last step.  Un-batched states: everything without the B.  Of a volume's flow
+    (flow_map3d.py): ftle [B, D, H, W], displacement [B, 3, D, H, W] = (dx, dy, dz), state (u, v, w, p, density)."""
     ftle: torch.Tensor
     displacement: torch.Tensor
     mean: torch.Tensor
     max: torch.Tensor
     state: Tuple[torch.Tensor, ...]
+
+
+# ------------------------------------------------------------------------------------------------ what 2-D and 3-D share, over one record
+@dataclass(frozen=True)
+class MapRoute:
+    """What the shared code needs to know about a dimension's flow map: the HipRoute record of its stepper, the public names as the error
+    texts spell them, the two rules, the three entry points (map step, FTLE field, its workspace query) and the hip route's limits."""
+    dim: HipRoute
+    step_name: str
+    field_name: str
+    flow_name: str
+    step_rule: Callable
+    ftle_rule: Callable
+    entries: Tuple[str, str, str]
+    limits: str
 
 
 def _check_window(n_steps, dt, what):
@@ -161,26 +183,12 @@ def _result(ftle, disp, mean, top, state, batched):
     return FtleResult(ftle, disp, mean, top, tuple(state))
 
 
-def flow_ftle_rule(u, v, p, density, n_steps: int, *, dt: float = 0.01, viscosity: float = 0.001, jacobi_iters: int = 20,
-                   direction: str = "backward", branches: Optional[Branches] = None) -> FtleResult:
-    """n_steps of fluid_rule.step from the state (u, v, p, density), each followed by flow_map_step_rule with the step's output
-    velocities, from a zero displacement; then ftle_rule over n_steps * dt.  Any dtype and device; mean and max in fp64 by torch."""
-    _direction(direction, "flow_ftle")
-    _check_window(n_steps, dt, "flow_ftle")
-    state = (u, v, p, density)
-    check_state(HIP2, state)
-    batched = density.dim() == 3
-    state = tuple(t.detach() if batched else t.detach()[None] for t in state)
-    disp = density.new_zeros(state[3].shape[0], 2, *state[3].shape[1:])
-    for _ in range(int(n_steps)):
-        state = fluid_rule.step(state, dt, viscosity, jacobi_iters, branches)
-        disp = flow_map_step_rule(disp, state[0], state[1], dt=dt, direction=direction, branches=branches)
-    ftle = ftle_rule(disp, int(n_steps) * float(dt))
+def _stats64(ftle):
+    """(mean, max) per grid of a field [B, ...] in fp64 by torch."""
     flat = ftle.double().flatten(1)
-    return _result(ftle, disp, flat.mean(dim=1), flat.max(dim=1).values, state, batched)
+    return flat.mean(dim=1), flat.max(dim=1).values
 
 
-# ------------------------------------------------------------------------------------------------ the hip route
 def _check_hip(tensors, what):
     dev = tensors[0].device
     _lib.require_cuda(dev, f"{what}(route='hip')")
@@ -195,59 +203,132 @@ def _route(route, what):
     return route == "hip"
 
 
-def _launch_map_step(direction, u, v, disp, out, dims, dt, dev):
-    """smk_flow_map_step on device stores: dims = (B, H, W, pitch_c, pitch_v, pitch_m)."""
-    _lib.check(_lib.load().smk_flow_map_step(direction, u.data_ptr(), v.data_ptr(), disp.data_ptr(), out.data_ptr(), *dims, float(dt),
-                                             _lib.stream_ptr(dev)))
+def _launch_map_step(m, direction, vel, disp, out, dims, dt, dev):
+    """The map-step entry point on device stores: vel = the velocity components, dims = (B, *grid, pitch_c, pitch_v, pitch_m)."""
+    _lib.check(getattr(_lib.load(), m.entries[0])(direction, *[c.data_ptr() for c in vel], disp.data_ptr(), out.data_ptr(), *dims,
+                                                  float(dt), _lib.stream_ptr(dev)))
+
+
+def route_flow_ftle_rule(m, state, n_steps, dt, viscosity, jacobi_iters, direction, branches) -> FtleResult:
+    """flow_ftle_rule / flow_ftle3d_rule: fluid_rule.step and the map step's rule chained from a zero displacement, then the FTLE's."""
+    dim = m.dim
+    _direction(direction, m.flow_name)
+    _check_window(n_steps, dt, m.flow_name)
+    check_state(dim, state)
+    batched = state[-1].dim() == dim.nd + 1
+    state = tuple(t.detach() if batched else t.detach()[None] for t in state)
+    disp = state[-1].new_zeros(state[-1].shape[0], dim.nd, *state[-1].shape[1:])
+    for _ in range(int(n_steps)):
+        state = fluid_rule.step(state, dt, viscosity, jacobi_iters, branches)
+        disp = m.step_rule(disp, *state[:dim.nd], dt=dt, direction=direction, branches=branches)
+    ftle = m.ftle_rule(disp, int(n_steps) * float(dt))
+    return _result(ftle, disp, *_stats64(ftle), state, batched)
+
+
+def route_map_step(m, disp, vel, dt, direction, route):
+    """flow_map_step / flow_map_step3d: the checks, then the rule or one launch on dense tensors."""
+    dim = m.dim
+    code = _direction(direction, m.step_name)
+    if not _route(route, m.step_name):
+        return m.step_rule(disp, *vel, dt=dt, direction=direction)
+    grid = _check_disp(dim, disp, vel, m.step_name)
+    _check_hip((disp, *vel), m.step_name)
+    batched = disp.dim() == dim.nd + 2
+    d, *vv = (t.detach().contiguous() if batched else t.detach()[None].contiguous() for t in (disp, *vel))
+    out = torch.empty_like(d)
+    W = grid[-1]
+    with torch.cuda.device(d.device):
+        _launch_map_step(m, code, vv, d, out, (d.shape[0], *grid, W, W + 1, W), dt, d.device)
+    return out if batched else out[0]
+
+
+def route_ftle_field(m, disp, horizon, route):
+    """ftle_field / ftle_field3d: the checks, then the rule with torch's fp64 statistics or the entry point's two launches."""
+    dim, what = m.dim, m.field_name
+    nd = dim.nd
+    if disp.dim() not in (nd + 1, nd + 2) or disp.shape[-nd - 1] != nd or min(disp.shape[-nd:]) < 3:
+        raise ValueError(f"{what}: disp must be [{nd}, {dim.axes}] or [B, {nd}, {dim.axes}] with {dim.axes} >= 3, got {tuple(disp.shape)}")
+    if not float(horizon) > 0:
+        raise ValueError(f"{what}: horizon > 0, got {horizon}")
+    batched = disp.dim() == nd + 2
+    d = disp.detach() if batched else disp.detach()[None]
+    if _route(route, what):
+        _check_hip((d,), what)
+        d = d.contiguous()
+        B, grid = d.shape[0], tuple(d.shape[2:])
+        L = _lib.load()
+        nbytes = int(getattr(L, m.entries[2])(B, *grid))
+        if nbytes < 0:
+            raise ValueError(f"{what}: B={B}, grid {' x '.join(str(n) for n in grid)} is not supported ({m.limits})")
+        ftle = torch.empty(B, *grid, dtype=torch.float32, device=d.device)
+        stats = torch.empty(B, 2, dtype=torch.float64, device=d.device)
+        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=d.device)
+        with torch.cuda.device(d.device):
+            _lib.check(getattr(L, m.entries[1])(d.data_ptr(), ftle.data_ptr(), stats.data_ptr(), B, *grid, grid[-1], float(horizon),
+                                                ws.data_ptr(), nbytes, _lib.stream_ptr(d.device)))
+        mean, top = stats[:, 0], stats[:, 1]
+    else:
+        ftle = m.ftle_rule(d, horizon)
+        mean, top = _stats64(ftle)
+    return (ftle, mean, top) if batched else (ftle[0], mean[0], top[0])
+
+
+def route_flow_ftle(m, state, n_steps, dt, viscosity, jacobi_iters, direction, route) -> FtleResult:
+    """flow_ftle / flow_ftle3d: the checks, then the rule or the chained loop on the cached stepper -- every step is step_into(None, 1)
+    followed by the map step straight on the stepper's padded velocity stores, two displacement buffers swapping; then the FTLE's two
+    launches; one host synchronisation, where the stepper reports its status."""
+    dim, what = m.dim, m.flow_name
+    code = _direction(direction, what)
+    if not _route(route, what):
+        return route_flow_ftle_rule(m, state, n_steps, dt, viscosity, jacobi_iters, direction, None)
+    _check_window(n_steps, dt, what)
+    check_state(dim, state)
+    _check_hip(state, what)
+    if int(jacobi_iters) < 0:
+        raise ValueError(f"{what}: jacobi_iters >= 0")
+    batched = state[-1].dim() == dim.nd + 1
+    state = tuple(t.detach() if batched else t.detach()[None] for t in state)
+    B, *grid = state[-1].shape
+    dev = state[-1].device
+    with torch.no_grad(), torch.cuda.device(dev):
+        sim = simulator(dim, B, grid, dt, viscosity, jacobi_iters, dev)
+        for name, t in zip(dim.fields, state):
+            setattr(sim, name, t)
+        vel = [getattr(sim, "_" + name) for name in dim.fields[:dim.nd]]
+        dims = (B, *grid, sim._pc, sim._pv, grid[-1])
+        disp, other = torch.zeros(B, dim.nd, *grid, device=dev), torch.empty(B, dim.nd, *grid, device=dev)
+        for _ in range(int(n_steps)):
+            sim.step_into(None, 1)
+            _launch_map_step(m, code, vel, disp, other, dims, dt, dev)
+            disp, other = other, disp
+        ftle, mean, top = route_ftle_field(m, disp, int(n_steps) * float(dt), "hip")
+        state = sim.state()
+        check = getattr(sim, "check", None)                  # the frames leave the stepper: a timed-out projection is reported here
+        if check is not None:                                # (by the stepper that can time out: the 3-D one has no check(), and then
+            check()                                          # the call does not synchronise at all)
+    return _result(ftle, disp, mean, top, state, batched)
+
+
+# ------------------------------------------------------------------------------------------------ the public functions, 2-D
+def flow_ftle_rule(u, v, p, density, n_steps: int, *, dt: float = 0.01, viscosity: float = 0.001, jacobi_iters: int = 20,
+                   direction: str = "backward", branches: Optional[Branches] = None) -> FtleResult:
+    """n_steps of fluid_rule.step from the state (u, v, p, density), each followed by flow_map_step_rule with the step's output
+    velocities, from a zero displacement; then ftle_rule over n_steps * dt.  Any dtype and device; mean and max in fp64 by torch."""
+    return route_flow_ftle_rule(MAP2, (u, v, p, density), n_steps, dt, viscosity, jacobi_iters, direction, branches)
 
 
 def flow_map_step(disp, u, v, *, dt: float = 0.01, direction: str = "backward", route: str = "hip"):
     """One map step -> disp' (module docstring).  disp [B, 2, H, W], u [B, H+1, W], v [B, H, W+1] (or all without the B): the velocities
     are the output of the step() the map is composed with.  route="hip": fp32 ROCm tensors, smk_flow_map_step (one launch);
     route="torch": flow_map_step_rule, any dtype and device."""
-    code = _direction(direction, "flow_map_step")
-    if not _route(route, "flow_map_step"):
-        return flow_map_step_rule(disp, u, v, dt=dt, direction=direction)
-    H, W = _check_disp(disp, u, v, "flow_map_step")
-    _check_hip((disp, u, v), "flow_map_step")
-    batched = disp.dim() == 4
-    d, uu, vv = (t.detach().contiguous() if batched else t.detach()[None].contiguous() for t in (disp, u, v))
-    out = torch.empty_like(d)
-    with torch.cuda.device(d.device):
-        _launch_map_step(code, uu, vv, d, out, (d.shape[0], H, W, W, W + 1, W), dt, d.device)
-    return out if batched else out[0]
+    return route_map_step(MAP2, disp, (u, v), dt, direction, route)
 
 
 def ftle_field(disp, horizon: float, route: str = "hip"):
     """(ftle [B, H, W], mean [B] fp64, max [B] fp64) of the map x + disp, disp [B, 2, H, W] (or without the B), over a window of
     `horizon` = n_steps * dt > 0 time units.  route="hip": fp32 ROCm tensor, smk_ftle_field (two launches, no host synchronisation);
     route="torch": ftle_rule, the statistics in fp64 by torch."""
-    if disp.dim() not in (3, 4) or disp.shape[-3] != 2 or min(disp.shape[-2:]) < 3:
-        raise ValueError(f"ftle_field: disp must be [2, H, W] or [B, 2, H, W] with H, W >= 3, got {tuple(disp.shape)}")
-    if not float(horizon) > 0:
-        raise ValueError(f"ftle_field: horizon > 0, got {horizon}")
-    batched = disp.dim() == 4
-    d = disp.detach() if batched else disp.detach()[None]
-    if _route(route, "ftle_field"):
-        _check_hip((d,), "ftle_field")
-        d = d.contiguous()
-        B, _, H, W = d.shape
-        L = _lib.load()
-        nbytes = int(L.smk_ftle_workspace(B, H, W))
-        if nbytes < 0:
-            raise ValueError(f"ftle_field: B={B}, grid {H} x {W} is not supported (B <= 65535, 3 <= H, W <= 32766)")
-        ftle = torch.empty(B, H, W, dtype=torch.float32, device=d.device)
-        stats = torch.empty(B, 2, dtype=torch.float64, device=d.device)
-        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=d.device)
-        with torch.cuda.device(d.device):
-            _lib.check(L.smk_ftle_field(d.data_ptr(), ftle.data_ptr(), stats.data_ptr(), B, H, W, W, float(horizon), ws.data_ptr(), nbytes,
-                                        _lib.stream_ptr(d.device)))
-        mean, top = stats[:, 0], stats[:, 1]
-    else:
-        ftle = ftle_rule(d, horizon)
-        flat = ftle.double().flatten(1)
-        mean, top = flat.mean(dim=1), flat.max(dim=1).values
-    return (ftle, mean, top) if batched else (ftle[0], mean[0], top[0])
+    return route_ftle_field(MAP2, disp, horizon, route)
 
 
 def flow_ftle(u, v, p, density, n_steps: int, *, dt: float = 0.01, viscosity: float = 0.001, jacobi_iters: int = 20,
@@ -257,29 +338,8 @@ def flow_ftle(u, v, p, density, n_steps: int, *, dt: float = 0.01, viscosity: fl
     the cached stepper fluid_step uses, every step is step_into(None, 1) (bit-identical to step()) followed by smk_flow_map_step
     straight on the stepper's velocity stores, then smk_ftle_field; one host synchronisation, at the end, to check the stepper's status.
     route="torch": flow_ftle_rule, any dtype and device."""
-    code = _direction(direction, "flow_ftle")
-    if not _route(route, "flow_ftle"):
-        return flow_ftle_rule(u, v, p, density, n_steps, dt=dt, viscosity=viscosity, jacobi_iters=jacobi_iters, direction=direction)
-    _check_window(n_steps, dt, "flow_ftle")
-    state = (u, v, p, density)
-    check_state(HIP2, state)
-    _check_hip(state, "flow_ftle")
-    if int(jacobi_iters) < 0:
-        raise ValueError("flow_ftle: jacobi_iters >= 0")
-    batched = density.dim() == 3
-    state = tuple(t.detach() if batched else t.detach()[None] for t in state)
-    B, H, W = state[3].shape
-    dev = density.device
-    with torch.no_grad(), torch.cuda.device(dev):
-        sim = simulator(HIP2, B, (H, W), dt, viscosity, jacobi_iters, dev)
-        for name, t in zip(HIP2.fields, state):
-            setattr(sim, name, t)
-        disp, other = torch.zeros(B, 2, H, W, device=dev), torch.empty(B, 2, H, W, device=dev)
-        for _ in range(int(n_steps)):
-            sim.step_into(None, 1)
-            _launch_map_step(code, sim._u, sim._v, disp, other, (B, H, W, sim._pc, sim._pv, W), dt, dev)
-            disp, other = other, disp
-        ftle, mean, top = ftle_field(disp, int(n_steps) * float(dt))
-        state = sim.state()
-        sim.check()                                          # the frames leave the stepper: a timed-out projection is reported here
-    return _result(ftle, disp, mean, top, state, batched)
+    return route_flow_ftle(MAP2, (u, v, p, density), n_steps, dt, viscosity, jacobi_iters, direction, route)
+
+
+MAP2 = MapRoute(HIP2, "flow_map_step", "ftle_field", "flow_ftle", flow_map_step_rule, ftle_rule,
+                ("smk_flow_map_step", "smk_ftle_field", "smk_ftle_workspace"), "B <= 65535, 3 <= H, W <= 32766")

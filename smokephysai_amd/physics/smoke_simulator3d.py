@@ -193,6 +193,19 @@ class SmokeSimulator3D(nn.Module):
         return {"lyapunov": float(res.lyapunov[0]), "kaplan_yorke": float(res.kaplan_yorke[0]), "ks_entropy": float(res.ks_entropy[0]),
                 "truncated": bool(res.truncated[0]), "exponents": [float(x) for x in res.exponents[0]]}
 
+    def flow_ftle(self, n_steps: int = 20, **kw):
+        """The finite-time Lyapunov exponent field of the flow from the simulator's CURRENT state: physics.flow_ftle3d (DESIGN.md section
+        3.15) over n_steps further steps, run on clones -- the simulator, its ring of norms and get_chaos_features() are untouched, as
+        with flow_chaos.  kw: flow_ftle3d's keywords (direction, route).  Batched: an FtleResult of tensors [B, ...].  Un-batched: an
+        FtleResult with the [D, H, W] field, the [3, D, H, W] displacement, mean and max as floats, and the state in ns_solver.state()'s
+        shapes (B = 1)."""
+        from .flow_map3d import FtleResult, flow_ftle3d
+        ns = self.ns_solver
+        res = flow_ftle3d(*ns.state(), n_steps, dt=ns.dt, viscosity=ns.viscosity, jacobi_iters=ns.jacobi_iters, **kw)
+        if self.batch_size is not None:
+            return res
+        return FtleResult(res.ftle[0], res.displacement[0], float(res.mean[0]), float(res.max[0]), res.state)
+
     def _single_grid(self, what):
         if self.batch_size is not None:
             raise ValueError(f"{what}: batched simulator -- use get_chaos_features(), which returns one dict per grid")

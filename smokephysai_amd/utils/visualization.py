@@ -121,13 +121,32 @@ class SmokeVisualizer:
             img = img[0]
         while field.ndim > 2:
             field = field[0]
+        return self._draw_ftle("plot_ftle", img, field, "FTLE", path)
+
+    def plot_ftle3d(self, frame, ftle, path: Optional[str] = None):
+        """plot_ftle for a volume: the rendered frame [H, W] (SmokeSimulator3D.render), the FTLE volume [D, H, W] of its flow
+        (physics.flow_ftle3d) as its maximum over depth -- the view of the default render, along z -- and that image's upper decile as a
+        contour over the frame.  Leading dimensions of size 1, or a batch whose first entry is drawn, are dropped.  torch or numpy; not
+        a hot path."""
+        img, vol = _numpy(frame), _numpy(ftle)
+        while img.ndim > 2:
+            img = img[0]
+        while vol.ndim > 3:
+            vol = vol[0]
+        if vol.ndim != 3:
+            raise ValueError(f"plot_ftle3d: ftle must be a [D, H, W] volume, got {vol.shape}")
+        return self._draw_ftle("plot_ftle3d", img, vol.max(axis=0), "FTLE (max over depth)", path)
+
+    @staticmethod
+    def _draw_ftle(what, img, field, title, path):
+        """The three panels of plot_ftle / plot_ftle3d: img and field [H, W] numpy arrays."""
         if img.shape != field.shape:
-            raise ValueError(f"plot_ftle: frame and ftle must have one shape, got {img.shape} and {field.shape}")
+            raise ValueError(f"{what}: frame and ftle must have one shape, got {img.shape} and {field.shape}")
         fig, axes = plt.subplots(1, 3, figsize=(15, 5))
         axes[0].imshow(img, cmap="hot")
         axes[0].set_title("Input Smoke")
         im = axes[1].imshow(field, cmap="plasma")
-        axes[1].set_title("FTLE")
+        axes[1].set_title(title)
         fig.colorbar(im, ax=axes[1])
         axes[2].imshow(img, cmap="hot")
         level = float(np.quantile(field, 0.9))
