@@ -61,21 +61,32 @@
     // Buffer s & 1 is rewritten in sweep s + 2, after barrier s + 1, which every wave passes only after it has consumed (in sweep
     // s + 1's first two rows) what it read from buffer s.  RPW 2 / 3 have 0 / 1 interior rows: the same chain as the plain order.
     // Plain order (PIPE false): publish src's edge rows, interior rows, barrier, read, the two edge rows.
+    // STAIRS (jb_prio_stairs): the wave's issue priority falls stage by stage from one barrier to the next -- 3, 2 behind the barrier, 1 over
+    // the edge rows and the publish, 0 ahead of the barrier -- so a wave that is behind outranks the ones ahead of it instead of waiting
+    // for its turn by age; no instruction of a stage moves (profiles/r34).
     constexpr bool PIPE = jb_pipelined(VEC, RPW, PERSIST);
-    constexpr int NA = jb_rows_before_barrier(RPW);           // interior rows ahead of the barrier (cover the stores); the rest follow the reads
+    constexpr bool STAIRS = jb_prio_stairs(VEC, RPW, PERSIST, FOLD);   // the wave's priority falls from one barrier to the next (jacobi_plan.h)
+    constexpr int NA = jb_rows_before_barrier(RPW, STAIRS);   // interior rows ahead of the barrier (cover the stores); the rest follow the reads
+    static_assert(!STAIRS || (PIPE && RPW - 2 > NA), "the staircase needs the pipelined order and an interior row behind the barrier");
     auto sweep = [&](const float (&src)[RPW][VEC], float (&dst)[RPW][VEC], int par) {
         if constexpr (PIPE) {
+            wave_prio<STAIRS, 1>();                           // the next sweep's edge rows and their publish
             edge_rows(src, dst);
             publish(dst, par);
             __builtin_amdgcn_sched_barrier(0);                // first: the neighbours' next sweep waits on these stores
+            wave_prio<STAIRS, 0>();                           // the rows ahead of the barrier: whoever is still behind goes first
 #pragma unroll
             for (int k = 1; k < 1 + NA; ++k) row(src, dst, k, src[k - 1], src[k + 1]);
             __builtin_amdgcn_sched_barrier(0);                // (hipcc otherwise sinks these rows below the barrier)
             __syncthreads();
+            wave_prio<STAIRS, 3>();                           // the reads and the first interior rows behind the barrier
             fetch(par);
             __builtin_amdgcn_sched_barrier(0);                // reads in flight before the rows that cover them
 #pragma unroll
-            for (int k = 1 + NA; k < RPW - 1; ++k) row(src, dst, k, src[k - 1], src[k + 1]);
+            for (int k = 1 + NA; k < RPW - 1; ++k) {
+                if (k == RPW - 2) wave_prio<STAIRS, 2>();     // the last of them
+                row(src, dst, k, src[k - 1], src[k + 1]);
+            }
             __builtin_amdgcn_sched_barrier(0);                // (the wait for the reads belongs to the next sweep's first rows)
         } else {
             publish(src, par);
@@ -109,6 +120,7 @@
 #pragma unroll
                 for (int c = 0; c < VEC; ++c) pv[k][c] = pw[k][c];
         }
+        wave_prio<STAIRS, 0>();                               // outside a sweep a wave runs at priority 0
     };
     if constexpr (!PERSIST) {
         run(iters);

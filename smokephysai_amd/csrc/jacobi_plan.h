@@ -85,9 +85,6 @@ SMK_PLAN_HD int jb_run_sweeps(int iters, int done, int parts, int c) { return (i
 // Which order a sweep of k_jacobi_band takes (see `sweep` there), and how its interior rows split around the barrier.
 // The persistent 4 x 8 instantiations sit at the 128-VGPR cap of a 1024-thread workgroup and would spill more in the pipelined order.
 SMK_PLAN_HD constexpr bool jb_pipelined(int vec, int rpw, bool persist) { return !(persist && vec == 4 && rpw == 8); }
-// Interior rows computed ahead of the barrier (they cover the publish); the others follow the reads.  Measured at 6 and 8 rows per wave
-// (profiles/r07): one row ahead is the fastest split at 4 cells per lane; with none the stores are exposed, with all of them the reads.
-SMK_PLAN_HD constexpr int jb_rows_before_barrier(int rpw) { return rpw > 2 ? 1 : 0; }
 
 // Whether an instantiation carries both forms of the cell (stencil.h) and the guard that picks one per launch and workgroup: the form of
 // the 256^2 x 64 step alone (persistent with the prologue, 4 cells per lane, 6 rows per wave), whose registers, scratch and occupancy stay
@@ -96,6 +93,18 @@ SMK_PLAN_HD constexpr int jb_rows_before_barrier(int rpw) { return rpw > 2 ? 1 :
 // of them past the 64 that let two workgroups share a CU), 8 x 3 and 4 x 6 persistent went to the 128 cap, and the 32-cell forms spilled
 // more.
 SMK_PLAN_HD constexpr bool jb_two_forms(int vec, int rpw, bool persist, bool fold) { return persist && fold && vec == 4 && rpw == 6; }
+// Whether the pipelined sweep of an instantiation steps its wave priority down between two barriers (`sweep`, jacobi_band_tail.h): 3 over
+// the reads and the first interior rows behind the barrier, 2 over the last of them, 1 over the next sweep's edge rows and their publish, 0
+// over the row ahead of the barrier and everywhere outside a sweep.  Issue goes to the highest priority first and among equals to the oldest
+// wave, so with one level the four waves of a SIMD finish a sweep one after the other and wait at the barrier (profiles/r07); with the
+// staircase whichever wave is behind wins the slot.  Arithmetic, LDS traffic and synchronisation are the same instructions in the same
+// order.  True only for forms that have been timed with it (profiles/r34): the form of the 256^2 x 64 step.  Every other instantiation
+// compiles to the instructions it had.
+SMK_PLAN_HD constexpr bool jb_prio_stairs(int vec, int rpw, bool persist, bool fold) { return persist && fold && vec == 4 && rpw == 6; }
+// Interior rows computed ahead of the barrier (they cover the publish); the others follow the reads.  Measured at 6 and 8 rows per wave
+// (profiles/r07): one row ahead is the fastest split at 4 cells per lane; with none the stores are exposed, with all of them the reads.
+// Under the staircase those rows run at the lowest priority and two of them are faster than one or none (profiles/r34/ab_variants.json).
+SMK_PLAN_HD constexpr int jb_rows_before_barrier(int rpw, bool stairs = false) { return stairs ? 2 : (rpw > 2 ? 1 : 0); }
 // The keep buffer of the PERSIST && FOLD form: the diffused u2 / v2 rows a band owns wait in LDS between the prologue and the gradient
 // epilogue instead of going to HBM and back.  Beside `edge` (64 rows) and the flag word a workgroup, alone on its CU anyway, may declare
 // the rest of the 160 KiB: that many rows of 64 * vec floats, at most the 2 * 16 * rpw a band can own.
@@ -131,6 +140,7 @@ struct ProjectionPlan {
     bool folds = false;            // persistent: a step's buoyancy + diffusion stage can run as the launch's prologue
     bool two_forms = false;        // the kernel a whole step launches has both cell forms (jb_two_forms)
     bool pipelined = false;        // jb_pipelined
+    bool prio_stairs = false;      // jb_prio_stairs
 };
 
 // Chunks of the persistent form: sizes are ceil / floor of iters / chunks (jb_run_sweeps), the largest <= halo, the last <= halo - 1 (the
@@ -213,6 +223,7 @@ inline ProjectionPlan plan_projection(const PlanGeom &g, int iters, int num_cu, 
     const bool persist = pp.form == ProjectionForm::persistent;
     pp.two_forms = jb_two_forms(pp.vec, pp.rpw, persist, pp.folds);
     pp.pipelined = jb_pipelined(pp.vec, pp.rpw, persist);
+    pp.prio_stairs = jb_prio_stairs(pp.vec, pp.rpw, persist, pp.folds);
     return pp;
 }
 
@@ -227,6 +238,7 @@ inline ProjectionPlan plan_projection_on(const PlanGeom &g, const PlanLayout &l,
     const bool persist = pp.form == ProjectionForm::persistent;
     pp.folds = pp.folds && jb_fold_aligned(g, l, pp.vec);
     pp.two_forms = jb_two_forms(pp.vec, pp.rpw, persist, pp.folds);
+    pp.prio_stairs = jb_prio_stairs(pp.vec, pp.rpw, persist, pp.folds);
     return pp;
 }
 

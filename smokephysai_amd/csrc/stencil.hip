@@ -296,6 +296,16 @@ __device__ __forceinline__ float wave_shr1(float x) {   // lane i <- lane i-1 (l
 __device__ __forceinline__ float wave_shl1(float x) {   // lane i <- lane i+1 (lane 63: 0, unused)
     return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x130, 0xf, 0xf, true));
 }
+// One step of the sweep's priority staircase (jb_prio_stairs, jacobi_plan.h): nothing at all in an instantiation without it.  The
+// scheduling barriers keep the compiler from moving the change off the stage boundary it marks.
+template <bool ON, int LEVEL>
+__device__ __forceinline__ void wave_prio() {
+    if constexpr (ON) {
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_setprio(LEVEL);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
 
 template <int VEC> struct VecT;
 template <> struct VecT<1> { using type = float; };
@@ -844,7 +854,11 @@ hipError_t launch_buoy_project(const Geom &g, StateView in, StateView out, float
 std::string describe_projection(const Geom &g, int iters, const ProjectSync *ps, const StateView *in, const StateView *out) {
     const PlanGeom pg = plan_geom(g);
     const PlanLayout lay = plan_layout(g, in, out ? out->u : nullptr, out ? out->v : nullptr);
-    return describe_plan(plan_projection_on(pg, lay, iters, device_num_cu(), handle_allows_persist(ps), true), iters, pg, device_num_cu());
+    const ProjectionPlan pp = plan_projection_on(pg, lay, iters, device_num_cu(), handle_allows_persist(ps), true);
+    std::string d = describe_plan(pp, iters, pg, device_num_cu());
+    // (a member of its own, and only where it is true: describe_plan's text is recorded byte for byte, tests/host/projection_plans_parent.txt)
+    if (pp.prio_stairs) d.insert(d.size() - 1, ", \"prio_stairs\": true");
+    return d;
 }
 
 // The form a step's buoyancy + diffusion stage takes (in -> out) and the alignment facts its gate and the projection's were given, as

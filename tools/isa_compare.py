@@ -11,6 +11,11 @@ Exit status 1 if a kernel is missing, a K-loop block differs, or scratch / occup
 --mfma-blocks adds a column for kernels whose K loop spans several basic blocks (csrc/linear.hip: the chunk loop of k_linear_x3 /
 k_linear_b16 is not one block, so the K-loop column reads "none" for them): the ordered mnemonic sequences of EVERY basic block that
 holds a v_mfma, old against new; a difference is exit status 1 as well.
+
+--sweep-blocks is for kernels that iterate on registers between workgroup barriers (csrc/stencil.hip: k_jacobi_band): for every kernel whose
+stream differs it lists the basic blocks that hold an s_barrier, an LDS store and vector adds -- the sweep blocks -- with the counts of
+v_add*, v_fma* / v_mul* / v_sub*, v_cndmask*, ds_read_b128 and ds_write_b128 in each, old against new, and the s_setprio of each; a
+different number of such blocks or a different count (s_setprio aside) is exit status 1.
 """
 import argparse, re, sys
 
@@ -63,11 +68,31 @@ def mfma_blocks(body, loops_only):
     return res
 
 
+SWEEP_CLASSES = (("v_add",), ("v_fma", "v_mul", "v_sub"), ("v_cndmask",), ("ds_read_b128",), ("ds_write_b128",))
+
+
+def sweep_blocks(body):
+    """[(counts per SWEEP_CLASSES, number of s_setprio)] of the basic blocks that hold s_barrier, an LDS store and vector adds, in order"""
+    blocks, cur = [], []
+    for l in body + [".LBB_end:"]:
+        if l.endswith(":"):
+            blocks.append(cur)
+            cur = []
+        else:
+            cur.append(l.split()[0])
+    res = []
+    for ins in blocks:
+        if "s_barrier" in ins and any(i.startswith("ds_write") for i in ins) and any(i.startswith("v_add") for i in ins):
+            res.append(([sum(i.startswith(c) for i in ins) for c in SWEEP_CLASSES], sum(i == "s_setprio" for i in ins)))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--old", nargs="+", required=True)
     ap.add_argument("--new", nargs="+", required=True)
     ap.add_argument("--mfma-blocks", action="store_true", help="also compare every basic block that holds a v_mfma")
+    ap.add_argument("--sweep-blocks", action="store_true", help="for kernels that differ: instruction-class counts of every sweep block")
     a = ap.parse_args()
     old, new = {}, {}
     for p in a.old:
@@ -94,11 +119,22 @@ def main():
             nd = sum(x != y for x, y in zip(ao, an)) + abs(len(ao) - len(an))
             kl += " | " + ("none" if not ao and not an else f"{len(ao)} same" if not nd else f"{len(ao)}/{len(an)} {nd} DIFFER")
             ok = ok and not nd
+        sweep_lines = []
+        if a.sweep_blocks and not same:
+            so, sn = sweep_blocks(bo), sweep_blocks(bn)
+            ok = ok and [c for c, _ in so] == [c for c, _ in sn]
+            sweep_lines.append(f"    sweep blocks {len(so)}/{len(sn)}: v_add | v_fma+v_mul+v_sub | v_cndmask | ds_read_b128 | ds_write_b128 (old/new), s_setprio")
+            for i in range(max(len(so), len(sn))):
+                co_, po = so[i] if i < len(so) else (None, None)
+                cn_, pn = sn[i] if i < len(sn) else (None, None)
+                sweep_lines.append(f"    block {i}: {co_} / {cn_} {'same' if co_ == cn_ else 'DIFFER'}, s_setprio {po}/{pn}")
         bad += not ok
         pair = lambda k: f"{mo.get(k)}/{mn.get(k)}" if mo.get(k) != mn.get(k) else f"{mo.get(k)}"
         print(f"{name} | {mo.get('vgpr')}/{mn.get('vgpr')} | {mo.get('sgpr')}/{mn.get('sgpr')} | {pair('scratch')} | {pair('lds')} | "
               f"{pair('occ')} | {' '.join(f'{x}' if x == y else f'{x}/{y}' for x, y in zip(co, cn))} | {len(bo)}/{len(bn)} | "
               f"{'identical' if same else 'differs'} | {kl}{'' if ok else ' | CHECK'}")
+        for l in sweep_lines:
+            print(l)
     for name in sorted(set(new) - set(old)):
         print(f"{name} | only in new")
     return 1 if bad else 0
